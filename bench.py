@@ -18,19 +18,25 @@ collective: a labelled option, not the headline).  Default: per-GPU work is fixe
 `--single-process` drives the C ABI's own multi-device front end instead (ivfadc_mg_search, host
 pointers, optional in-library ncclAllGather).
 
-Prints ONE JSON line on rank 0.  `value` is the MEDIAN of `--windows` (default 5) timed windows of exactly `--steps` steps each (every
-window bracketed by barrier + synchronize on both sides, MAX over ranks); min / max of the windows are in `windows`.  The default
-single-GPU run also measures the other BASELINE.json shapes (Deep1B, HD, SIFT1B w = 8 and w = 1) briefly -- step time, scan-kernel
-time, roofline fractions and a 64-query oracle parity bit each -- and reports them under `other_configs`.
+Prints ONE JSON line on rank 0.  A plain run sets up, warms up, times ONE window of exactly `--steps` steps (bracketed by barrier +
+synchronize on both sides, MAX over ranks), writes the last step's results when `--dump-outputs DIR` is given, prints the line and exits:
+`value` is the queries/s of that window and `ms_per_step` its milliseconds per step.
+
+`--full` adds everything else the benchmark measures and checks.  `value` is then the MEDIAN of `--windows` (default 5) timed windows of
+exactly `--steps` steps each (min / max of the windows are in `windows`), and the run goes on to the roofline of the scan kernel, the oracle
+parity and CPU baseline, the same-run comparison legs, the recall sweep, the host-to-host block, the scaling base and, on the default
+single-GPU workload, the other BASELINE.json shapes (Deep1B, HD, SIFT1B w = 8 and w = 1, K = 1 / 100, skewed lists) -- step time,
+scan-kernel time, roofline fractions and a 64-query oracle parity bit each -- under `other_configs`.
 
 Batches in flight (`--inflight`, default: by shape): on the shapes whose launch is only a few workgroups per CU (sift1m, hd, toy) the steps
 alternate between the index and a read-only VIEW of it (ivfadc_clone_view: the same device arrays, a second stream and workspace), so that a
 launch's ramp and tail overlap the neighbouring batches' kernels; every batch is still searched whole, results bit-identical.  `value` is
-that rate; `batches_in_flight` carries the one-at-a-time rates of the same run (with the next-batch hint, and as plain knn_search-per-batch
-calls), and everything profiled (roofline, pruning off, sweep, other_configs' primary figures) runs one batch at a time.
+that rate; with `--full`, `batches_in_flight` carries the one-at-a-time rates of the same run (with the next-batch hint, and as plain
+knn_search-per-batch calls), and everything profiled (roofline, pruning off, sweep, other_configs' primary figures) runs one batch at a time.
 
-`--single-mode` runs ONE kernel population only (no same-run comparison legs, no sweep, no other configs): the form the rocprofv3
-passes of tools/profile_all.sh are taken on, once per mode (hinted / `--no-next-hint` / `--no-next-hint --no-pruning`).
+`--single-mode` runs ONE kernel population only (one batch in flight; with `--full`: no same-run comparison legs, no sweep, no other
+configs): `--full --single-mode` is the form the rocprofv3 passes of tools/profile_all.sh are taken on, once per mode (hinted /
+`--no-next-hint` / `--no-next-hint --no-pruning`).
 """
 import argparse
 import json
@@ -573,7 +579,8 @@ def compact_line(full):
     rates["scaling_base_qps"] = sb.get("qps_per_rank")
     if sb.get("error"):
         rates["scaling_base_error"] = str(sb["error"])[:120]
-    c["rates"] = rates
+    if any(v is not None for v in rates.values()):      # (a plain run measures none of them)
+        c["rates"] = rates
     oc = full.get("other_configs")
     if isinstance(oc, dict):
         o = {}
@@ -598,20 +605,17 @@ def compact_line(full):
         c["distributed"] = _pick(d, ("ranks_seen_by_rccl", "gather_check", "partition_check", "collectives_in_timed_region", "batches_per_collective",
                                      "bytes_per_rank_per_collective"))
         c["distributed"]["backend"] = str(d.get("backend", ""))[:60]
-    c["full_record"] = FULL_RECORD
     return c
 
 
-def emit(full, json_out):
-    """Full record -> gpurun_out/bench_full.json and stderr; compact line (<= LINE_LIMIT bytes, enforced) -> stdout."""
-    try:
-        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
-        with open(os.path.join(ROOT, FULL_RECORD), "w") as f:
-            json.dump(full, f, indent=1)
-    except OSError as e:
-        log("[bench] could not write %s: %s" % (FULL_RECORD, e))
+def emit(full, json_out, record=True):
+    """Full record -> stderr and (record: `--full` runs) the side file FULL_RECORD; compact line (<= LINE_LIMIT bytes, enforced) -> stdout."""
+    if record:
+        write_full_record(full)
     log("[bench] full record: " + json.dumps(full))
     c = compact_line(full)
+    if record:
+        c["full_record"] = FULL_RECORD
     text = json.dumps(c, separators=(",", ":"))
     for victim in ("other_configs", "windows", "rates", "distributed"):      # never reached with today's fields; the limit is a promise
         if len(text) <= LINE_LIMIT:
@@ -620,6 +624,38 @@ def emit(full, json_out):
         c["dropped_to_fit"] = c.get("dropped_to_fit", []) + [victim]
         text = json.dumps(c, separators=(",", ":"))
     print(text, file=json_out, flush=True)
+
+
+def write_full_record(full):
+    try:
+        os.makedirs(os.path.join(ROOT, "gpurun_out"), exist_ok=True)
+        with open(os.path.join(ROOT, FULL_RECORD), "w") as f:
+            json.dump(full, f, indent=1)
+    except OSError as e:
+        log("[bench] could not write %s: %s" % (FULL_RECORD, e))
+
+
+DUMP_LIMIT = 64 << 20      # bytes that --dump-outputs writes at most
+
+
+def dump_outputs(out_dir, ids, dists, counts):
+    """--dump-outputs: the results of the last timed step as a caller of the search receives them, for the whole global batch --
+    ids.npy (float64: uint32 ids are exact), dists.npy (float32) and counts.npy (float64); past a query's count its ids are -1 and its
+    distances +inf.  A batch whose arrays exceed DUMP_LIMIT is written as a fixed, seeded sample of its queries (rows.npy: their
+    numbers in the batch)."""
+    nq, K = ids.shape
+    valid = np.arange(K)[None, :] < counts[:, None]
+    out = {"ids": np.where(valid, ids.astype(np.float64), -1.0), "dists": np.where(valid, dists, np.inf).astype(np.float32),
+           "counts": counts.astype(np.float64)}
+    row_bytes = 8 * K + 4 * K + 8
+    if nq * row_bytes > DUMP_LIMIT:
+        rows = np.sort(np.random.default_rng(0).choice(nq, DUMP_LIMIT // (row_bytes + 8), replace=False))
+        out = {k: v[rows] for k, v in out.items()}
+        out["rows"] = rows.astype(np.float64)
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    log("[bench] last step's results of %d queries -> %s: %s" % (nq, out_dir, ", ".join("%s%s" % (k, v.shape) for k, v in out.items())))
 
 
 def median_of(xs):
@@ -640,7 +676,7 @@ def oracle_parity(ora, oidx, qh, K, w, ids, dists, counts, pick):
 TWO_LANE_CONFIGS = ("sift1m", "hd", "deep1b", "toy")   # shapes on which a second batch in flight pays (measured; see --inflight: round 5 HD +6 %, Deep1B +2 %, SIFT1B -2 %)
 
 
-def measure_other_config(torch, pkg, name, cases, dev, device_index, budget_s=20.0, skew=False, two_lanes=True):
+def measure_other_config(torch, pkg, name, cases, dev, device_index, budget_s=20.0, skew=False):
     """One of the other BASELINE.json shapes, briefly: a few windows of steps, a profiled region for the scan kernel's own time, the
     roofline fractions and a 64-query oracle parity bit.  Device-synthesised index (seconds), queries resident in HBM."""
     from oracle import oracle as ora
@@ -686,7 +722,7 @@ def measure_other_config(torch, pkg, name, cases, dev, device_index, budget_s=20
         par = oracle_parity(ora, oidx, qh, K, w, ids, dists, counts, pick)
         med = median_of(wins)
         two = None
-        if name in TWO_LANE_CONFIGS and two_lanes:
+        if name in TWO_LANE_CONFIGS:
             # two batches in flight (index + view in turn, results into separate buffers); the roofline above stays that of one at a time
             view = idx.clone_view()
             res2 = torch.zeros_like(res)
@@ -981,7 +1017,8 @@ def main():
     ap.add_argument("--no-next-hint", action="store_true",
                     help="do not tell the library which queries the next step searches (ivfadc_set_next_queries): every step then runs its "
                          "coarse search as a launch of its own instead of behind the previous step's scan")
-    ap.add_argument("--windows", type=int, default=5, help="timed windows of --steps steps each; `value` is their median")
+    ap.add_argument("--windows", type=int, default=0,
+                    help="timed windows of --steps steps each; `value` is their median (default: 1, with --full 5)")
     ap.add_argument("--no-pruning", action="store_true", help="scan every probed list (ivfadc_set_pruning(h, 0)): the reference's own byte count")
     ap.add_argument("--single-mode", action="store_true",
                     help="one kernel population only: no same-run comparison legs (un-hinted, pruning off, table build alone), no sweep, no "
@@ -1005,14 +1042,20 @@ def main():
     ap.add_argument("--selftest-cpu", action="store_true",
                     help="no GPU: run the launcher, the query partition and the gather over gloo with a stub searcher")
     ap.add_argument("--full", action="store_true",
-                    help="also run the long legs: recall sweep over w (and the low-rank dataset), pruning-off / un-hinted windows, K = 1 / K = 100 / "
-                         "skewed variants of the other shapes, the trained kc = 65 536 two-level block, every kind of caller memory on the host "
-                         "path.  The default run measures what the compact line carries and nothing else")
+                    help="everything besides the headline: 5 windows, roofline, oracle parity, CPU baseline, recall sweep over w (and the "
+                         "low-rank dataset), pruning-off / un-hinted / one-in-flight windows, host-to-host block, scaling base, the other "
+                         "BASELINE shapes (with K = 1 / K = 100 / skewed variants) and the trained kc = 65 536 two-level block.  Without it "
+                         "a run sets up, warms up, times --steps steps and prints the line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default="",
+                    help="after the timed steps, write the last step's results (ids, dists, counts of the whole batch) as DIR/<name>.npy")
     args = ap.parse_args()
+    nwin = args.windows or (5 if args.full else 1)
 
     if args.single_process:
         return single_process(args)
     if args.lists_rehearsal:
+        if args.dump_outputs:
+            raise SystemExit("--dump-outputs: --lists-rehearsal times pieces of a step, not steps")
         return lists_rehearsal(args)
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         launch_ranks(args.gpus, sys.argv[1:], args.selftest_cpu)          # does not return
@@ -1235,16 +1278,79 @@ def main():
             break
 
     coll0 = rings.collectives
-    elapsed, wins = windows(args.steps, args.windows)
+    elapsed, wins = windows(args.steps, nwin)
     coll_timed = (rings.collectives - coll0) // max(1, len(wins))
-    # both lanes searched the same batch into their own result slots: the blocks must be identical, bit for bit
-    lanes_agree = None
-    if gpu and len(lane_list) == 2 and dist is None and rings.G >= 2:
-        lanes_agree = bool(torch.equal(rings.slot_view(0), rings.slot_view(1)))
+
+    def last_results():
+        """(ids uint32, dists float32, counts int32) of the whole global batch as step --steps - 1 left them (the timed loop drained)"""
+        i = args.steps - 1
+        if lp is not None:
+            parts = [(lp["ids"], lp["dists"], lp["counts"])]
+        else:
+            rr, sl = rings.slot_of(i)
+            per = nq * rings.width
+            if dist is None:
+                blocks = [rings.slot_view(i)]
+            else:                       # rank r's block of the batch in the gathered ring
+                blk = rings.G * per
+                blocks = [rings.gath[rr][r * blk + sl * per: r * blk + (sl + 1) * per] for r in range(world)]
+            parts = [(b[:nq * K], b[nq * K:2 * nq * K], b[2 * nq * K:]) for b in blocks]
+        ids = np.concatenate([p[0].cpu().numpy().reshape(-1) for p in parts]).view(np.uint32).reshape(-1, K)
+        dists = np.concatenate([p[1].contiguous().view(torch.int32).cpu().numpy().reshape(-1) for p in parts]).view(np.float32).reshape(-1, K)
+        counts = np.concatenate([p[2].cpu().numpy().reshape(-1) for p in parts]).astype(np.int32)
+        return ids, dists, counts
+
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, *last_results())
     qps = nq_total * args.steps / elapsed
     win_info = {"n": len(wins), "steps_each": args.steps, "value_is": "median window",
                 "ms_per_step_min": round(min(wins) / args.steps * 1e3, 4), "ms_per_step_max": round(max(wins) / args.steps * 1e3, 4),
                 "qps_min": round(nq_total * args.steps / max(wins), 1), "qps_max": round(nq_total * args.steps / min(wins), 1)}
+
+    def headline(recall=None, recall_ceiling=None):
+        return {
+            "metric": "queries/sec at recall@1 (k=10), SIFT1M-shape d=128 m=8 k=256, 1/2/4/8 GPU"
+                      if args.config == "sift1m" else "queries/sec, %s-shape, K=%d" % (args.config, K),
+            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
+            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
+            "config": {"global_batch": nq_total, "queries_per_rank": nq, "workload": "%s-shape: d=%d n=%d kc=%d k=256 m=%d UInt8 codes, batch=%d queries/GPU (global batch %d), K=%d, w=%d%s"
+                                   % (args.config, cfg["d"], cfg["n"], cfg["kc"], cfg["m"], nq, nq_total, K, w,
+                                      ", skewed lists" if args.skew else ""),
+                       "index": ("trained (k-means + PQ, 25 iters), %s data" % ("Gaussian-mixture" if args.data == "mixture" else "low-rank mixture"))
+                                if cfg["kind"] == "trained" else "device-synthesised codes, N(0,1) quantizers",
+                       "parallelism": (("one global batch of %d queries per step, every one of the %d GPUs searches ALL of it over its own lists (l %% %d == rank), "
+                                        "index replicated, 1 all-gather of the partial top-k keys per batch + K-way merge on every rank" % (nq_total, world, world))
+                                       if by_lists else
+                                       ("one global batch of %d queries per step partitioned over %d GPUs (contiguous blocks), index "
+                                        "replicated, %s" % (nq_total, world, "1 all-gather of the packed top-k per batch" if G == 1 else
+                                                            "1 all-gather per %d batches (--gather-every)" % G)))
+                                      if world > 1 else "1 GPU",
+                       "partition": args.partition,
+                       "pruning": pruning_on, "single_mode": single_mode, "batches_in_flight": inflight_used,
+                       "recall_at_1_in_top%d" % K: recall, "recall_ceiling_w=kc": recall_ceiling,
+                       "recall_note": "the BASELINE dataset (isotropic Gaussian mixture, sigma = 0.1 in 128 dimensions) leaves an 8-byte product "
+                                      "quantizer nothing to use: recall sits at the PQ ceiling (w = kc) for every w, so 'at recall@1' carries no "
+                                      "information here; the recall-vs-w curve is the one of sweep['lowrank dataset ...'] (same shape, structured residuals)"
+                                      if (cfg["kind"] == "trained" and args.data == "mixture") else None},
+            "windows": win_info,
+        }
+
+    if gpu and not args.full:
+        # a plain run: the headline and nothing else -- every measurement and check below is --full
+        if rank == 0:
+            line = headline()
+            if dist is not None:
+                line["collectives_in_timed_region"] = coll_timed
+            emit(line, json_out, record=False)
+        if dist is not None:
+            dist.destroy_process_group()
+        return
+
+    # both lanes searched the same batch into their own result slots: the blocks must be identical, bit for bit
+    lanes_agree = None
+    if gpu and len(lane_list) == 2 and dist is None and rings.G >= 2:
+        lanes_agree = bool(torch.equal(rings.slot_view(0), rings.slot_view(1)))
     # the same steps without the next-batch hint (every step's coarse search as a launch of its own), same run: reported beside `value`
     hint_info = None
     if gpu:
@@ -1261,12 +1367,12 @@ def main():
             hint_next = hinted
             for i in range(20):
                 step(i)
-            el_v, w_v = windows(args.steps, args.windows)
+            el_v, w_v = windows(args.steps, nwin)
             hint_next = keep
             return {"qps": round(nq_total * args.steps / el_v, 1), "ms_per_step": round(el_v / args.steps * 1e3, 4), "windows": len(w_v),
                     "qps_min": round(nq_total * args.steps / max(w_v), 1), "qps_max": round(nq_total * args.steps / min(w_v), 1)}
 
-        if hint_used and dist is None and not single_mode and args.full:
+        if hint_used and dist is None and not single_mode:
             hint_info["without_hint_same_run"] = variant(False)
     # one batch in flight, same run: the index alone, a step waits for nothing but the stream order (with the hint, and as plain
     # knn_search-per-batch calls -- the reference's own calling pattern)
@@ -1337,7 +1443,8 @@ def main():
                   "selftest_cpu": True, "distributed": dist_info, "scaling": args.scaling, "windows": win_info,
                   "gather_check": dist_info["gather_check"] if dist_info else None,
                   "ranks_seen_by_rccl": dist_info["ranks_seen_by_rccl"] if dist_info else None,
-                  "config": {"workload": "stub", "global_batch": nq_total, "queries_per_rank": nq, "partition": args.partition}}, json_out)
+                  "config": {"workload": "stub", "global_batch": nq_total, "queries_per_rank": nq, "partition": args.partition}}, json_out,
+                 record=args.full)
         if dist is not None:
             dist.destroy_process_group()
         return
@@ -1376,7 +1483,7 @@ def main():
     if world == 1 and pruned_frac > 0 and not single_mode:
         idx.set_pruning(0)
         _, st0 = profiled(prof_steps)
-        el0, w0 = windows(args.steps, args.windows if args.full else 1)
+        el0, w0 = windows(args.steps, nwin)
         scan_ms0 = st0["scan_ms"] / max(1, st0["scan_launches"])
         no_prune = {"qps": round(nq_total * args.steps / el0, 1), "ms_per_step": round(el0 / args.steps * 1e3, 4), "windows": len(w0),
                     "scan_ms_per_launch": round(scan_ms0, 5), "alg_bytes_per_launch": int(balg_sec8d),
@@ -1437,7 +1544,7 @@ def main():
 
     sweep = None
     recall_ceiling = None
-    if rank == 0 and world == 1 and dist is None and cfg["kind"] == "trained" and not args.w and not args.no_sweep and not single_mode and args.full:
+    if rank == 0 and world == 1 and dist is None and cfg["kind"] == "trained" and not args.w and not args.no_sweep and not single_mode:
         # the reference default is w=1; BASELINE.md asks for w in {1, 8, 32}; w = kc scans every list: the recall the
         # product quantizer itself allows (the ceiling no choice of w can beat).  Un-hinted plain searches.
         sweep = {}
@@ -1540,7 +1647,7 @@ def main():
                 idx.comm_wait()
                 torch.cuda.synchronize()
                 idx.comm_destroy()          # (the run's own communicator has done its work: checks above, timing long before)
-            scaling_base = measure_scaling_base(torch, pkg, idx, nq, q, K, w, dev, args.steps, args.windows, bool(gpu and not args.no_next_hint))
+            scaling_base = measure_scaling_base(torch, pkg, idx, nq, q, K, w, dev, args.steps, nwin, bool(gpu and not args.no_next_hint))
         except Exception as e:           # noqa: BLE001
             scaling_base = {"error": "%s: %s" % (type(e).__name__, e)}
         if dist is not None:
@@ -1557,8 +1664,7 @@ def main():
     host_to_host = None
     if rank == 0 and world == 1 and dist is None and cfg["kind"] == "trained" and not single_mode and not args.no_host_to_host:
         try:
-            host_to_host = measure_host_to_host(torch, pkg, idx, cfg, K, w, dev, local_rank, args.data,
-                                                kinds=("pageable", "registered", "library_pinned") if args.full else ("registered",))
+            host_to_host = measure_host_to_host(torch, pkg, idx, cfg, K, w, dev, local_rank, args.data)
         except Exception as e:           # noqa: BLE001  (a failure here must not cost the headline line)
             host_to_host = {"error": "%s: %s" % (type(e).__name__, e)}
 
@@ -1572,11 +1678,10 @@ def main():
         # and its lists are as uneven as its data: the SIFT1B shape once more with skewed list sizes)
         # (... and one rank's share of the SIFT1B configuration's 8-GPU batch: 16 384 / 8 = 2048 queries against the full replica)
         shapes = (("deep1b", ((32, K), (32, 1), (32, 100)), False), ("hd", ((8, K),), False),
-                  ("sift1b", ((8, K), (1, K), (8, K, 2048)), False), ("sift1b", ((8, K),), True)) if args.full else \
-                 (("deep1b", ((32, K),), False), ("hd", ((8, K),), False), ("sift1b", ((8, K), (1, K), (8, K, 2048)), False))
+                  ("sift1b", ((8, K), (1, K), (8, K, 2048)), False), ("sift1b", ((8, K),), True))
         for name, cases, skew in shapes:
             try:
-                for ent in measure_other_config(torch, pkg, name, cases, dev, local_rank, skew=skew, two_lanes=args.full):
+                for ent in measure_other_config(torch, pkg, name, cases, dev, local_rank, skew=skew):
                     tag = "%s w=%d" % (name, ent["w"]) + ("" if ent["K"] == K else " K=%d" % ent["K"]) + (" skewed" if skew else "") + \
                           ("" if ent["batch"] == CONFIGS[name]["nq"] else " batch=%d (one rank's share of the 8-GPU batch)" % ent["batch"])
                     other[tag] = ent
@@ -1584,10 +1689,9 @@ def main():
                 other["%s%s (failed)" % (name, " skewed" if skew else "")] = {"error": "%s: %s" % (type(e).__name__, e)}
         other["seconds_total"] = round(time.perf_counter() - t_o, 1)
         try:
-            if args.full:
-                t_tl = time.perf_counter()
-                other["two_level_coarse (trained kc=65536)"] = measure_two_level(torch, pkg, K, dev, local_rank)
-                other["two_level_coarse (trained kc=65536)"]["seconds"] = round(time.perf_counter() - t_tl, 1)
+            t_tl = time.perf_counter()
+            other["two_level_coarse (trained kc=65536)"] = measure_two_level(torch, pkg, K, dev, local_rank)
+            other["two_level_coarse (trained kc=65536)"]["seconds"] = round(time.perf_counter() - t_tl, 1)
         except Exception as e:           # noqa: BLE001
             other["two_level_coarse (failed)"] = {"error": "%s: %s" % (type(e).__name__, e)}
 
@@ -1603,35 +1707,11 @@ def main():
                       "what": "exact coarse distances + ADC tables of the scanned probes + scan adds of one batch / the step time of the timed mode "
                               "(two batches in flight overlap one batch's coarse launch with the other's scan)"}
     if rank == 0:
-        line = {
-            "metric": "queries/sec at recall@1 (k=10), SIFT1M-shape d=128 m=8 k=256, 1/2/4/8 GPU"
-                      if args.config == "sift1m" else "queries/sec, %s-shape, K=%d" % (args.config, K),
-            "value": round(qps, 1), "unit": "queries/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-            "ms_per_step": round(elapsed / args.steps * 1e3, 4), "higher_is_better": True, "scaling": args.scaling,
-            "vs_baseline": None, "dtype": "f32", "data": "synthetic",
-            "config": {"global_batch": nq_total, "queries_per_rank": nq, "workload": "%s-shape: d=%d n=%d kc=%d k=256 m=%d UInt8 codes, batch=%d queries/GPU (global batch %d), K=%d, w=%d%s"
-                                   % (args.config, cfg["d"], cfg["n"], cfg["kc"], cfg["m"], nq, nq_total, K, w,
-                                      ", skewed lists" if args.skew else ""),
-                       "index": ("trained (k-means + PQ, 25 iters), %s data" % ("Gaussian-mixture" if args.data == "mixture" else "low-rank mixture"))
-                                if cfg["kind"] == "trained" else "device-synthesised codes, N(0,1) quantizers",
-                       "parallelism": (("one global batch of %d queries per step, every one of the %d GPUs searches ALL of it over its own lists (l %% %d == rank), "
-                                        "index replicated, 1 all-gather of the partial top-k keys per batch + K-way merge on every rank" % (nq_total, world, world))
-                                       if by_lists else
-                                       ("one global batch of %d queries per step partitioned over %d GPUs (contiguous blocks), index "
-                                        "replicated, %s" % (nq_total, world, "1 all-gather of the packed top-k per batch" if G == 1 else
-                                                            "1 all-gather per %d batches (--gather-every)" % G)))
-                                      if world > 1 else "1 GPU",
-                       "partition": args.partition,
-                       "pruning": pruning_on, "single_mode": single_mode, "batches_in_flight": inflight_used,
-                       "recall_at_1_in_top%d" % K: recall, "recall_ceiling_w=kc": recall_ceiling,
-                       "recall_note": "the BASELINE dataset (isotropic Gaussian mixture, sigma = 0.1 in 128 dimensions) leaves an 8-byte product "
-                                      "quantizer nothing to use: recall sits at the PQ ceiling (w = kc) for every w, so 'at recall@1' carries no "
-                                      "information here; the recall-vs-w curve is the one of sweep['lowrank dataset ...'] (same shape, structured residuals)"
-                                      if (cfg["kind"] == "trained" and args.data == "mixture") else None},
-            "windows": win_info,
+        line = headline(recall, recall_ceiling)
+        line.update({
             "roofline": roofline, "cpu_baseline": cpu_baseline, "parity": parity, "next_batch_hint": hint_info, "batches_in_flight": inflight_info, "host_to_host": host_to_host, "scaling_base": scaling_base, "other_configs": other,
             "sweep": sweep,
-        }
+        })
         if isinstance(scaling_base, dict) and "efficiency_vs_scaling_base" in scaling_base:
             line["efficiency_vs_scaling_base"] = scaling_base["efficiency_vs_scaling_base"]
         if dist_info is not None:
@@ -1689,16 +1769,17 @@ def lists_rehearsal(args):
         return median_of(wins), wins
 
     nsteps = max(3, min(args.steps, 20))
-    t_full, _ = timed(lambda: idx.search_device(nq, q.data_ptr(), K, w, ids.data_ptr(), dists.data_ptr(), counts.data_ptr()), nsteps, args.windows)
+    nwin = args.windows or 5
+    t_full, _ = timed(lambda: idx.search_device(nq, q.data_ptr(), K, w, ids.data_ptr(), dists.data_ptr(), counts.data_ptr()), nsteps, nwin)
     full = (ids.cpu().numpy().view(np.uint32).reshape(nq, K).copy(), dists.cpu().numpy().reshape(nq, K).copy(), counts.cpu().numpy().copy())
     t_slice = []
     for r in range(N):
         idx.set_list_partition(N, r)
-        t, _ = timed(lambda: idx.search_device_partial(nq, q.data_ptr(), K, w, keys_all[r].data_ptr(), cnts_all[r].data_ptr()), nsteps, args.windows)
+        t, _ = timed(lambda: idx.search_device_partial(nq, q.data_ptr(), K, w, keys_all[r].data_ptr(), cnts_all[r].data_ptr()), nsteps, nwin)
         t_slice.append(t)
     # (the handle's probe arrays are those of the last partial search -- the same batch, as on every rank)
     t_merge, _ = timed(lambda: idx.merge_partials_device(nq, K, N, keys_all.data_ptr(), cnts_all.data_ptr(), ids.data_ptr(), dists.data_ptr(),
-                                                       counts.data_ptr()), nsteps, args.windows)
+                                                       counts.data_ptr()), nsteps, nwin)
     torch.cuda.synchronize()
     merged = (ids.cpu().numpy().view(np.uint32).reshape(nq, K), dists.cpu().numpy().reshape(nq, K), counts.cpu().numpy())
     same = bool(np.array_equal(merged[2], full[2]) and np.array_equal(merged[0], full[0]) and np.array_equal(merged[1], full[1]))
@@ -1780,6 +1861,8 @@ def single_process(args):
         el = time.perf_counter() - t0
         c1 = C.c_int64(0)
         nat.check(L.ivfadc_mg_collectives(g, C.byref(c1)))
+        if args.dump_outputs:
+            dump_outputs(args.dump_outputs, ids, dists, counts)
         parity = None
         if not args.no_cpu_baseline:
             from oracle import oracle as ora

@@ -206,6 +206,53 @@ def test_bench_shard_bounds_match_library_rule():
                 assert bench.shard_bounds(nq, world, r) == pkg.distributed.shard_bounds(nq, world, r)
 
 
+def test_bench_dump_outputs_of_the_gathered_batch_world2(tmp_path):
+    """--dump-outputs DIR after a plain run of --steps steps (one timed window): the last step's results of the WHOLE global batch, both
+    ranks' blocks in query order, as float64 ids / float32 dists / float64 counts (stub searcher: slot q carries global query q)."""
+    out = str(tmp_path / "out")
+    K = 10
+    line = _run_bench(["--gpus", "2", "--selftest-cpu", "--steps", "4", "--warmup", "1", "--nq", "5", "--dump-outputs", out])
+    assert line["steps"] == 4 and line["windows"]["n"] == 1 and line["windows"]["steps_each"] == 4
+    assert line["distributed"]["collectives_in_timed_region"] == 4 and "full_record" not in line
+    ids, dists, counts = (np.load(os.path.join(out, n + ".npy")) for n in ("ids", "dists", "counts"))
+    assert ids.dtype == np.float64 and dists.dtype == np.float32 and counts.dtype == np.float64
+    q, j = np.arange(10)[:, None], np.arange(K)[None, :]
+    assert np.array_equal(ids, q * K + j) and np.array_equal(dists, (q + 0.5 * j).astype(np.float32)) and np.all(counts == K)
+
+
+def test_bench_dump_outputs_masks_past_counts_and_samples_large_batches(tmp_path):
+    sys.path.insert(0, ROOT)
+    import importlib.util
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(ROOT, "bench.py"))
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    nq, K = 40, 4
+    ids = np.arange(nq * K, dtype=np.uint32).reshape(nq, K) + np.uint32(4_000_000_000 - nq * K)     # beyond float32's exact integers
+    dists = np.arange(nq * K, dtype=np.float32).reshape(nq, K)
+    counts = (np.arange(nq) % (K + 1)).astype(np.int32)
+    bench.dump_outputs(str(tmp_path / "a"), ids, dists, counts)
+    got = {n: np.load(str(tmp_path / "a" / (n + ".npy"))) for n in ("ids", "dists", "counts")}
+    valid = np.arange(K)[None, :] < counts[:, None]
+    assert np.array_equal(got["ids"][valid], ids[valid].astype(np.float64)) and np.all(got["ids"][~valid] == -1)
+    assert np.array_equal(got["dists"][valid], dists[valid]) and np.all(np.isinf(got["dists"][~valid]))
+    assert np.array_equal(got["counts"], counts) and not os.path.exists(str(tmp_path / "a" / "rows.npy"))
+    # over the limit: a fixed, seeded sample of the queries, the same from call to call, with their numbers
+    limit = 10 * (8 * K + 4 * K + 8 + 8)
+    old = bench.DUMP_LIMIT
+    bench.DUMP_LIMIT = limit
+    try:
+        for d in ("b", "c"):
+            bench.dump_outputs(str(tmp_path / d), ids, dists, counts)
+    finally:
+        bench.DUMP_LIMIT = old
+    b = {n: np.load(str(tmp_path / "b" / (n + ".npy"))) for n in ("ids", "dists", "counts", "rows")}
+    c = {n: np.load(str(tmp_path / "c" / (n + ".npy"))) for n in ("ids", "dists", "counts", "rows")}
+    assert sum(a.nbytes for a in b.values()) <= limit and len(b["rows"]) == 10
+    assert all(np.array_equal(b[n], c[n]) for n in b)
+    rows = b["rows"].astype(np.int64)
+    assert np.all(np.diff(rows) > 0) and np.array_equal(b["ids"], got["ids"][rows]) and np.array_equal(b["counts"], got["counts"][rows])
+
+
 import pytest  # noqa: E402
 
 
@@ -217,7 +264,7 @@ def test_bench_single_rank_rccl_and_single_process_front_end():
     import subprocess
     env = dict(os.environ, BENCH_FORCE_DIST="1", MASTER_ADDR="127.0.0.1", MASTER_PORT=str(_free_port()), RANK="0", WORLD_SIZE="1",
                LOCAL_RANK="0")
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "12", "--warmup", "3", "--no-sweep"],
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "12", "--warmup", "3", "--no-sweep"],
                          capture_output=True, text=True, timeout=900, env=env)
     assert out.returncode == 0, out.stderr[-3000:]
     line = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -233,10 +280,11 @@ def test_bench_single_rank_rccl_and_single_process_front_end():
 
 @pytest.mark.gpu
 def test_bench_driver_command_prints_a_compact_parsable_line():
-    """The driver's own command (`python3 bench.py --gpus 1 --steps 20 --warmup 5`): ONE stdout line under 4 KB carrying the contract's
-    keys, a live roofline and CPU baseline, the contract rates and one tuple per other BASELINE shape; the full record in the side file."""
+    """The driver's command with every leg (`python3 bench.py --gpus 1 --steps 20 --warmup 5 --full`): ONE stdout line under 4 KB carrying
+    the contract's keys, a live roofline and CPU baseline, the contract rates and one tuple per other BASELINE shape; the full record in the
+    side file."""
     import json
-    line = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5"], timeout=900)
+    line = _run_bench(["--gpus", "1", "--steps", "20", "--warmup", "5", "--full"], timeout=900)
     assert all(k in line for k in CONTRACT_KEYS), sorted(line)
     assert line["n_gpus"] == 1 and line["steps"] == 20 and line["warmup"] == 5 and line["value"] > 0
     rl, cb = line["roofline"], line["cpu_baseline"]
@@ -250,3 +298,29 @@ def test_bench_driver_command_prints_a_compact_parsable_line():
     assert all(v.get("parity") is True for v in oc.values()), oc
     full = json.load(open(os.path.join(ROOT, line["full_record"])))
     assert full["value"] == line["value"] and "host_to_host" in full
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_times_its_steps_and_dumps_what_they_computed(tmp_path):
+    """A plain run (`bench.py --gpus 1 --steps N --warmup W`) times exactly N steps in one window and prints the headline alone (no roofline,
+    CPU baseline, parity or other shapes: those are --full's); --dump-outputs writes the last timed step's results, the same from run to
+    run and the same as a --full run of the same arguments computes, whose parity against the oracle holds."""
+    args = ["--gpus", "1", "--config", "toy", "--steps", "7", "--warmup", "2"]
+    dirs = [str(tmp_path / d) for d in ("a", "b", "full")]
+    line = _run_bench(args + ["--dump-outputs", dirs[0]], timeout=600)
+    assert all(k in line for k in CONTRACT_KEYS), sorted(line)
+    assert line["steps"] == 7 and line["warmup"] == 2 and line["windows"]["n"] == 1 and line["windows"]["steps_each"] == 7
+    assert line["value"] > 0 and line["ms_per_step"] > 0 and line["unit"] == "queries/s" and line["higher_is_better"] is True
+    assert line["roofline"] is None and line["cpu_baseline"] is None and line["parity"] is None
+    assert not ({"other_configs", "rates", "full_record"} & set(line)), sorted(line)
+    _run_bench(args + ["--dump-outputs", dirs[1]], timeout=600)
+    full = _run_bench(args + ["--full", "--dump-outputs", dirs[2]], timeout=600)
+    assert full["parity"]["ids_bit_exact"] and full["parity"]["dists_rtol_1e-4"] and full["windows"]["n"] == 5
+    got = [{n: np.load(os.path.join(d, n + ".npy")) for n in ("ids", "dists", "counts")} for d in dirs]
+    for g in got[1:]:
+        assert all(np.array_equal(got[0][n], g[n]) for n in g)
+    ids, dists, counts = got[0]["ids"], got[0]["dists"], got[0]["counts"]
+    assert ids.shape == (64, 10) and dists.shape == (64, 10) and counts.shape == (64,)
+    valid = np.arange(10)[None, :] < counts[:, None]
+    assert np.all(counts >= 1) and np.all((ids[valid] >= 0) & (ids[valid] < 1000)) and np.all(ids[~valid] == -1)
+    assert all(np.all(np.diff(dists[r, :int(counts[r])]) >= 0) for r in range(64))

@@ -8,7 +8,7 @@ for v in prod "$@"; do
   touch libivfadc_hip.so
   line="$v:"
   for extra in "" "--w 1" "--nq 2048"; do
-    r=$(cd $GRAFT_REPO_ROOT; timeout -k 10 300 python3 bench.py --config sift1b --table-mode ${TM:-6} --single-mode --no-cpu-baseline --steps 10 --warmup 3 --windows 1 $extra 2>/dev/null | grep -oE "scan_ms_per_launch\": ?[0-9.]+" | head -1 | grep -oE "[0-9.]+$")
+    r=$(cd ../..; timeout -k 10 300 python3 bench.py --full --config sift1b --table-mode ${TM:-6} --single-mode --no-cpu-baseline --steps 10 --warmup 3 --windows 1 $extra 2>/dev/null | grep -oE "scan_ms_per_launch\": ?[0-9.]+" | head -1 | grep -oE "[0-9.]+$")
     line="$line  $r"
   done
   echo "$line"

@@ -7,7 +7,7 @@ for nq in 64 1024 4096 16384; do
   for w in 1 8 32; do
     line="$cfg nq=$nq w=$w:"
     for qg in 0 -1 4; do
-      v=$(python bench.py --config $cfg --no-cpu-baseline --no-sweep --steps 40 --warmup 5 --nq $nq --w $w --qg $qg 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('%.2fM(%s)' % (j['value']/1e6, 'LM' if 'list-major' in j['roofline']['kernel'] else 'QM'))")
+      v=$(python bench.py --full --config $cfg --no-cpu-baseline --no-sweep --steps 40 --warmup 5 --nq $nq --w $w --qg $qg 2>/dev/null | tail -1 | python -c "import sys,json; j=json.loads(sys.stdin.read()); print('%.2fM(%s)' % (j['value']/1e6, 'LM' if 'list-major' in j['roofline']['kernel'] else 'QM'))")
       line="$line  qg=$qg $v"
     done
     echo "$line"

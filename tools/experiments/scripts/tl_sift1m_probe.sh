@@ -7,5 +7,5 @@ print(sys.argv[1], "qps=%.0f" % d["value"], "ms/step=%.4f" % d["ms_per_step"], "
 for data in mixture lowrank; do
 for mode in "" "--single-mode"; do
 for cm in 0 6; do
-timeout -k 10 300 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-sweep --no-other-configs --no-host-to-host --data $data --coarse-mode $cm $mode 2>gpurun_out/tl_err.txt | python -c "$fmt" "sift1m $data coarse_mode=$cm $mode" || tail -5 gpurun_out/tl_err.txt
+timeout -k 10 300 python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-sweep --no-other-configs --no-host-to-host --data $data --coarse-mode $cm $mode 2>"${TMPDIR:-/tmp}/tl_err.txt" | python -c "$fmt" "sift1m $data coarse_mode=$cm $mode" || tail -5 "${TMPDIR:-/tmp}/tl_err.txt"
 done; done; done

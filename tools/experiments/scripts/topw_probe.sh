@@ -5,7 +5,7 @@ cd $GRAFT_REPO_ROOT
 fmt='import sys,json
 d=json.loads(sys.stdin.read()); r=d["roofline"]
 print(sys.argv[1], "qps=%.0f" % d["value"], "ms/step=%.4f" % d["ms_per_step"], "scan_ms=%.4f" % r["scan_ms_per_launch"], "coarse_ms=%.4f" % r["coarse_ms_per_launch"])'
-run() { timeout -k 10 300 python bench.py --steps 300 --warmup 30 --no-cpu-baseline --no-sweep --no-other-configs --no-host-to-host "$@" 2>gpurun_out/topw_err.txt | python -c "$fmt" "$LABEL" || tail -3 gpurun_out/topw_err.txt; }
+run() { timeout -k 10 300 python bench.py --full --steps 300 --warmup 30 --no-cpu-baseline --no-sweep --no-other-configs --no-host-to-host "$@" 2>"${TMPDIR:-/tmp}/topw_err.txt" | python -c "$fmt" "$LABEL" || tail -3 "${TMPDIR:-/tmp}/topw_err.txt"; }
 for rep in 1 2; do
 for n in 2 3; do
 LABEL="fused inflight=$n" run --inflight $n

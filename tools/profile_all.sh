@@ -7,7 +7,7 @@ cd /tmp && export TMPDIR=/tmp
 cd "$GRAFT_REPO_ROOT"
 OUT=gpurun_out/prof_${1:-x}
 mkdir -p $OUT
-B="--single-mode --no-cpu-baseline --no-sweep"
+B="--full --single-mode --no-cpu-baseline --no-sweep"
 run() {  # name, extra bench args...
   name=$1; shift
   echo "== $name: $*"

@@ -6,7 +6,7 @@
 out=${1:-gpurun_out/strong_rehearsal.jsonl}; shift
 : > $out
 for w in 8 1; do for nq in 16384 8192 4096 2048; do
-  timeout -k 10 280 python bench.py --config sift1b --nq $nq --w $w --steps 12 --warmup 3 --no-cpu-baseline --no-sweep "$@" 2>/dev/null >> $out || echo "{\"failed\": [$nq, $w]}" >> $out
+  timeout -k 10 280 python bench.py --full --config sift1b --nq $nq --w $w --steps 12 --warmup 3 --no-cpu-baseline --no-sweep "$@" 2>/dev/null >> $out || echo "{\"failed\": [$nq, $w]}" >> $out
 done; done
 python - $out <<'PY'
 import json, sys
