@@ -13,7 +13,7 @@
  *     last failure on the calling thread.
  *   - the caller owns every host buffer; the library owns device memory.
  *   - matrices are Julia-native column-major: "d x n" means n contiguous vectors of d.
- *   - T = Float32, U = UInt8 (ksub <= 256), I = UInt32, distance = SqEuclidean for both
+ *   - T = Float32, U in {UInt8 (ksub <= 256), UInt16 (ksub <= 65536)}, I = UInt32, distance = SqEuclidean for both
  *     the coarse and the residual quantizer (defaults.jl:6,8), NaiveQuantizer only.
  *   - one HIP stream per handle.  Threads: every entry point locks its handle, so calls on ONE handle from several
  *     threads are serialised (correct, not concurrent); calls on DIFFERENT handles -- an index and its views
@@ -73,9 +73,29 @@ int ivfadc_abi_version(void);
  *   code_labels m x ksub: codebooks[i].codes (the byte that names codeword c of block i);
  *               labels of one block must be distinct (LittleDict keys, index.jl:235)
  * Requires d % m == 0 (QuantizedArrays.rowrange for other shapes is third-party and
- * unverifiable), 1 <= ksub <= 256, kc >= 1.                                            */
+ * unverifiable), 1 <= ksub <= 256 (ivfadc_create_u16 below: up to 65536), kc >= 1.     */
 int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
                   const float *centroids, const float *codebooks, const uint8_t *code_labels);
+
+/* Code width.  A handle is created for U = UInt8 (ivfadc_create, ivfadc_load_index of a UInt8 file) or U = UInt16 (ivfadc_create_u16,
+ * ivfadc_load_index of a UInt16 file: IVFADCIndex{UInt16,...}, persistency.jl:57,102-128).  On a 16-bit handle the entries that move
+ * codes or labels are the _u16 ones below; their uint8_t counterparts (ivfadc_set_lists, _get_lists, _encode, _append, _get_quantizers,
+ * _synth_lists, ivfadc_debug_lb_table) return IVFADC_ERR_STATE there, and the _u16 entries return IVFADC_ERR_STATE on an 8-bit handle.
+ * Every other entry (the searches, views, delete / shift, dims, save / load, stats, tuning, pruning, coarse modes) serves both widths.
+ * Code and label buffers of the _u16 entries are declared void * and hold uint16_t (little-endian, as the file stores them).
+ * ivfadc_set_list_partition with nparts > 1 returns IVFADC_ERR_INVALID on a 16-bit handle.                                    */
+/* As ivfadc_create, for U = UInt16: 1 <= ksub <= 65536, code_labels is m x ksub uint16_t (distinct within a block).  Validation runs
+ * before any device call.                                                                                                  */
+int ivfadc_create_u16(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
+                      const float *centroids, const float *codebooks, const void *code_labels);
+/* The handle's code width in bits: 8 or 16. */
+int ivfadc_code_bits(ivfadc_t *h, int *bits);
+/* ivfadc_set_lists / _get_lists / _encode / _append / _get_quantizers with n x m uint16_t codes and m x ksub uint16_t labels. */
+int ivfadc_set_lists_u16(ivfadc_t *h, const int64_t *offsets, const void *codes, const uint32_t *ids);
+int ivfadc_get_lists_u16(ivfadc_t *h, int64_t *offsets, void *codes, uint32_t *ids);
+int ivfadc_encode_u16(ivfadc_t *h, int64_t n, const float *pts, int32_t *out_list, void *out_codes);
+int ivfadc_append_u16(ivfadc_t *h, int64_t nnew, const float *pts, const uint32_t *ids, int32_t *out_list, void *out_codes);
+int ivfadc_get_quantizers_u16(ivfadc_t *h, float *centroids, float *codebooks, void *code_labels);
 
 /* Replaces (statistically, not bit for bit: both are third-party and unseeded in the reference) the training half
  * of the IVFADCIndex constructor, index.jl:127-147: Clustering.kmeans(data, kc; init=:kmpp, maxiter) for the coarse
@@ -83,7 +103,7 @@ int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
  *   data d x n; out_centroids d x kc; out_codebooks m blocks of dsub x k (the layout ivfadc_create takes; labels are
  *   0..k-1).  Runs on the device: k-means++ seeding, exact-distance assignment (the search path's coarse kernel), and
  *   order-independent fixed-point sums, so the result is deterministic for a given seed.
- * Constructor checks of index.jl:118-123 (kc >= 2, k <= n, 1 <= m <= d, maxiter > 0) -> IVFADC_ERR_ASSERT.          */
+ * Constructor checks of index.jl:118-123 (kc >= 2, k <= n, 1 <= m <= d, maxiter > 0) -> IVFADC_ERR_ASSERT; then 1 <= k <= 65536.   */
 int ivfadc_train(int device, int d, int64_t n, const float *data, int kc, int k, int m,
                  int coarse_maxiter, int quant_maxiter, uint64_t seed,
                  float *out_centroids, float *out_codebooks);

@@ -11,7 +11,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(_HERE, "csrc")
 SO_PATH = os.path.join(CSRC, "libivfadc_hip.so")
 SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "train.hip.h"), os.path.join(CSRC, "wave_sort.hip.h"),
-           os.path.join(CSRC, "generic.hip.h"), os.path.join(CSRC, "lbscan.hip.h"), os.path.join(CSRC, "nfscan.hip.h"), os.path.join(CSRC, "smallq.hip.h"), os.path.join(CSRC, "twolevel.hip.h"), os.path.join(CSRC, "wg8scan.hip.h"), os.path.join(CSRC, "wg8q8scan.hip.h"),
+           os.path.join(CSRC, "generic.hip.h"), os.path.join(CSRC, "lbscan.hip.h"), os.path.join(CSRC, "nfscan.hip.h"), os.path.join(CSRC, "smallq.hip.h"), os.path.join(CSRC, "twolevel.hip.h"), os.path.join(CSRC, "wg8scan.hip.h"), os.path.join(CSRC, "wg8q8scan.hip.h"), os.path.join(CSRC, "u16scan.hip.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]
@@ -82,6 +82,13 @@ def lib():
     L.ivfadc_last_error.restype = C.c_char_p
     L.ivfadc_create.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, u8p]
     L.ivfadc_set_lists.argtypes = [vp, i64p, u8p, u32p]
+    L.ivfadc_create_u16.argtypes = [C.POINTER(vp), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, fp, fp, vp]
+    L.ivfadc_code_bits.argtypes = [vp, C.POINTER(C.c_int)]
+    L.ivfadc_set_lists_u16.argtypes = [vp, i64p, vp, u32p]
+    L.ivfadc_get_lists_u16.argtypes = [vp, i64p, vp, u32p]
+    L.ivfadc_encode_u16.argtypes = [vp, C.c_int64, fp, i32p, vp]
+    L.ivfadc_append_u16.argtypes = [vp, C.c_int64, fp, u32p, i32p, vp]
+    L.ivfadc_get_quantizers_u16.argtypes = [vp, fp, fp, vp]
     L.ivfadc_train.argtypes = [C.c_int, C.c_int, C.c_int64, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, fp, fp]
     L.ivfadc_train.restype = C.c_int
     L.ivfadc_synth_lists.argtypes = [vp, i64p, C.c_uint64]

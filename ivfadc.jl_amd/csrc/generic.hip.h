@@ -107,6 +107,54 @@ __global__ __launch_bounds__(256) void gen_dump_kernel(const IndexView ix, const
     }
 }
 
+// The same for U = UInt16 codes (codeword indices, cs / 2 uint16_t per point): the table of a probe is m x ksub floats, built one
+// sub-space at a time in tiles of GEN16_TILE codewords (u16scan.hip.h); the running sums of the list's points live in their own key
+// slots (low word: f32 bits) until the keys are written, so every point gets its terms in ascending ii whatever the list length.
+// One workgroup per (probe, query), any m and ksub <= 65536.
+constexpr int GEN16_TILE = 8192;
+__global__ __launch_bounds__(256) void gen_dump_u16_kernel(const IndexView ix, const float *__restrict__ queries, int w,
+                                                           const int *__restrict__ probe_list, const float *__restrict__ probe_dc,
+                                                           const u32 *__restrict__ probe_base, const u32 *__restrict__ key_off,
+                                                           u64 *__restrict__ keys)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    float *resid = (float *)smem_raw;                       // [d]
+    float *tab = resid + (((size_t)ix.d + 3) & ~(size_t)3);   // [GEN16_TILE]
+    const int j = blockIdx.x, q = blockIdx.y, tid = threadIdx.x;
+    const int l = probe_list[(size_t)q * w + j];
+    const u32 len = ix.list_len[l];
+    if (len == 0) return;   // uniform
+    for (int i = tid; i < ix.d; i += 256) resid[i] = queries[(size_t)q * ix.d + i] - ix.centroids[(size_t)l * ix.d + i];
+    const float dc = probe_dc[(size_t)q * w + j];
+    const u32 base = probe_base[(size_t)q * w + j];
+    const uint16_t *codes = (const uint16_t *)(ix.codes + ix.list_codeoff[l]);
+    const size_t cs2 = (size_t)ix.cs >> 1;
+    u64 *dst = keys + key_off[q] + base;
+    for (u32 p = tid; p < len; p += 256) dst[p] = (u64)__float_as_uint(dc);
+    for (int ii = 0; ii < ix.m; ++ii) {
+        const float *rr = resid + (size_t)ii * ix.dsub;
+        for (int c0 = 0; c0 < ix.ksub; c0 += GEN16_TILE) {
+            const int c1 = min(ix.ksub, c0 + GEN16_TILE);
+            __syncthreads();
+            for (int c = c0 + tid; c < c1; c += 256) {
+                const float *cw = ix.codebooks + ((size_t)ii * ix.ksub + c) * ix.dsub;
+                float sum = 0.0f;
+                for (int t = 0; t < ix.dsub; ++t) {
+                    const float df = cw[t] - rr[t];
+                    sum = sum + df * df;
+                }
+                tab[c - c0] = sum;
+            }
+            __syncthreads();
+            for (u32 p = tid; p < len; p += 256) {
+                const int c = (int)codes[(size_t)p * cs2 + ii];
+                if (c >= c0 && c < c1) dst[p] = (u64)__float_as_uint(__uint_as_float((u32)dst[p]) + tab[c - c0]);
+            }
+        }
+    }
+    for (u32 p = tid; p < len; p += 256) dst[p] = ((u64)(u32)dst[p] << 32) | (base + p);
+}
+
 // first K sorted keys of every query -> ids and distances (index.jl:248,252,257)
 __global__ __launch_bounds__(256) void gen_emit_kernel(const u64 *__restrict__ sorted, const u32 *__restrict__ key_off,
                                                        const u32 *__restrict__ totals, int w, int K, const int *__restrict__ probe_list,

@@ -9,6 +9,7 @@
 #include "kernels.hip.h"
 #include "train.hip.h"
 #include "generic.hip.h"
+#include "u16scan.hip.h"
 #include "twolevel.hip.h"
 
 #include <algorithm>
@@ -411,6 +412,12 @@ struct ivfadc_index {
     }
     std::vector<uint8_t> h_label_ok;   // m x 256 validity
     bool identity_labels = false;
+    // U = UInt16 (ivfadc_create_u16, u16scan.hip.h): the host mirror and the device hold CODEWORD INDICES (little-endian uint16, cb = 2m
+    // bytes per point); labels are translated at the boundary (set / get lists, encode, save / load), so a table needs m x ksub slots
+    bool u16 = false;
+    int cb = 0;                        // code bytes per point of the host mirror: m (UInt8) or 2m (UInt16)
+    std::vector<uint16_t> lab16;       // [m][ksub] labels of a 16-bit handle
+    std::vector<uint32_t> lab_sorted;  // [m][ksub] label << 16 | codeword index, ascending within each block (label -> index lookups)
     // the residual quantizer's rotation as loaded from an index file (nrows x nrows, column by column as persistency.jl:62-64 writes it);
     // empty = identity (:pq).  knn_search never reads it (index.jl:204-258): a rotated (:opq) index is SEARCHED as it is; quantize_data --
     // push! / encode -- would need it (third-party arithmetic, unverifiable here), so those entries refuse on such a handle.
@@ -593,7 +600,7 @@ int upload_list_tables(ivfadc_index *h)
 // full re-layout: host mirror -> device, every list gets spare capacity behind it
 int upload_lists(ivfadc_index *h)
 {
-    const int kc = h->kc, m = h->m, cs = h->cs;
+    const int kc = h->kc, m = h->cb, cs = h->cs;
     h->d_cap.assign(kc, 0);
     for (int l = 0; l < kc; ++l) h->d_cap[l] = h->h_len[l] + std::max<int64_t>(32, h->h_len[l] / 8);
     size_t total = 0;
@@ -822,6 +829,45 @@ int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its s
     HIP_TRY(hipMemcpyAsync(h->fb_pin.p, h->misc.p, 4096, hipMemcpyDeviceToHost, h->stream));
     HIP_TRY(hipEventRecord(h->fb_ev, h->stream));
     h->fb_pending = true;
+    return IVFADC_OK;
+}
+
+// U = UInt16 (u16scan.hip.h): always list-major, K <= 64 (search_dev sends larger K to the generic path).  Pairs per work item from
+// the expected probes per list (a codeword read serves every pair of the item); chunks of whole passes, about two items per CU.
+int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
+{
+    pl.fits = true;
+    pl.lanes = false;
+    pl.small_k = true;
+    pl.small_w = w <= 64;
+    pl.cap = 64;
+    pl.capw = pl.small_w ? 64 : std::max(128, pow2ceil(w + 64));
+    pl.query_major = false;
+    pl.fuse_topw = pl.lb = pl.nf = pl.wg8 = pl.wg8q8 = false;
+    pl.coarse_mfma = h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
+    pl.twolevel = h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
+                  (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
+    if (pl.twolevel) pl.coarse_mfma = false;
+    const double avg_len = (double)h->n / std::max(1, h->kc);
+    const double ppl = (double)nq * w / std::max(1, h->kc);
+    int qg = ppl >= 6.0 ? 8 : (ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1));
+    if (h->force_qg == 1 || h->force_qg == 2 || h->force_qg == 4 || h->force_qg == 8) qg = h->force_qg;
+    pl.qg = qg;
+    pl.lds = u16_lds_bytes(h->m, h->dsub);
+    if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
+    const double ch = (double)nq * w * avg_len / qg / (2.0 * h->num_cu);
+    uint32_t CH = U16_PASS;
+    while ((double)CH < ch && CH < (1u << 18)) CH <<= 1;
+    if (h->force_chunk > 0) CH = (uint32_t)align_up((size_t)h->force_chunk, U16_PASS);
+    while ((h->maxlen + CH - 1) / CH > 64) CH <<= 1;   // bound the partial-result slots per probe
+    pl.CH = CH;
+    pl.maxch = (int)std::max<int64_t>(1, (h->maxlen + CH - 1) / CH);
+    const size_t per_q = (pl.twolevel ? (size_t)h->tl_G : (size_t)h->kc) * 4 + (size_t)w * pl.maxch * ((size_t)K * 8 + 4) + (size_t)w * 20 +
+                         (size_t)K * 8 + 64;
+    int64_t nb = (int64_t)std::max<size_t>(64, h->ws_budget / per_q);
+    nb = std::min<int64_t>(nb, (int64_t)1 << 22);
+    nb = std::min<int64_t>(nb, std::max<int64_t>(64, ((int64_t)1 << 30) / std::max(1, w * pl.maxch)));
+    pl.nb = std::min<int64_t>(nq, nb);
     return IVFADC_OK;
 }
 
@@ -1518,7 +1564,17 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         h->stats.last_nf = pl.nf ? 1 : 0;
         const size_t upper = np * (size_t)pl.maxch;
         ivfadc_index::EvPair ep;
-        if (pl.wg8 && !direct) {
+        if (h->u16) {
+            int occ = 0;
+            TRY(fn_occupancy(h, (const void *)u16_scan_kernel, pl.lds, occ));
+            const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
+            if (h->profiling) TRY(ev_begin(h, 0, ep));
+            hipLaunchKernelGGL(u16_scan_kernel, dim3(grid), dim3(256), pl.lds, h->stream, a, pl.qg);
+            HIP_TRY(hipGetLastError());
+            if (h->profiling) TRY(ev_end(h, ep));
+            h->stats.last_scan_grid = (int)grid;
+            h->stats.last_striped = 0;
+        } else if (pl.wg8 && !direct) {
             void (*wk)(const ScanArgs, float *, const u32 *, u32 *, int) = pl.wg8q8 ? wg8q8_scan_kernel : wg8_scan_kernel;
             u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
             static const bool one_queue = env_knob("IVFADC_W8_NO_XCD") != nullptr;   // A/B (debug build): one queue for all workgroups
@@ -1688,9 +1744,11 @@ int gen_sort(ivfadc_index *h, const u64 *in, u64 *out, int64_t total, int segmen
 int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts)
 {
     const int kc = h->kc;
-    const size_t lds = (align_up((size_t)h->d, 4) + (size_t)h->m * 256) * 4;
+    const size_t lds = (align_up((size_t)h->d, 4) + (h->u16 ? (size_t)GEN16_TILE : (size_t)h->m * 256)) * 4;
     if (lds > LDS_MAX) return fail(IVFADC_ERR_INVALID, "m=%d needs %zu B of LDS in the generic path (> %zu)", h->m, lds, LDS_MAX);
-    TRY(fn_raise_lds(h->device, (const void *)gen_dump_kernel, lds, false));
+    void (*dump)(const IndexView, const float *, int, const int *, const float *, const u32 *, const u32 *, u64 *) =
+        h->u16 ? gen_dump_u16_kernel : gen_dump_kernel;
+    TRY(fn_raise_lds(h->device, (const void *)dump, lds, false));
     TRY(ensure_common_ws(h));
     u64 *d_scanned = h->misc.as<u64>();
     const IndexView ix = index_view(h);
@@ -1747,7 +1805,7 @@ int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, 
             const u32 *pb = h->probe_base.as<u32>() + (size_t)g0 * w;
             for (int64_t y0 = 0; y0 < ng; y0 += 32768) {   // grid.y limit
                 const int64_t ny = std::min<int64_t>(32768, ng - y0);
-                hipLaunchKernelGGL(gen_dump_kernel, dim3((unsigned)w, (unsigned)ny), dim3(256), lds, h->stream, ix,
+                hipLaunchKernelGGL(dump, dim3((unsigned)w, (unsigned)ny), dim3(256), lds, h->stream, ix,
                                    qa + (size_t)(g0 + y0) * h->d, w, pl + (size_t)y0 * w, pd + (size_t)y0 * w, pb + (size_t)y0 * w,
                                    h->gen_off.as<u32>() + y0, h->gen_a.as<u64>());
                 HIP_TRY(hipGetLastError());
@@ -1781,7 +1839,7 @@ int sq_inside_kc(const ivfadc_index *h)
 bool sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
 {
     static const bool off = env_knob("IVFADC_NO_SMALLQ") != nullptr;
-    if (off || !h->allow_sq || h->force_qg != 0) return false;
+    if (off || !h->allow_sq || h->force_qg != 0 || h->u16) return false;
     if (K > 64 || w > 64 || nq > 64 || nq * w > 512) return false;
     if ((h->d & 3) != 0) return false;
     const size_t lds = scan_lds_bytes(h, 1, 64, true) + 64 + (h->kc <= sq_inside_kc(h) ? (size_t)h->kc * 4 : 0);
@@ -2053,13 +2111,13 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
     if (!h->tl_tried && !h->is_view && !tl_env_off && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
     const bool parted = h->part_n > 1;
     if (!parted && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
-    if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2) {
+    if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64)) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
         return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
     }
     Plan pl;
     TRY(fb_poll(h));
-    TRY(make_plan(h, nq, K, w, pl));
+    TRY(h->u16 ? make_plan_u16(h, nq, K, w, pl) : make_plan(h, nq, K, w, pl));
     if (!pl.fits) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the selection kernels' LDS need exceeds a CU for this m and K");
         return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts);   // "any K and w" holds for every m
@@ -2083,18 +2141,22 @@ int encode_dev(ivfadc_index *h, int64_t n, const float *pts, int32_t *out_list, 
         const int64_t nb = std::min(bmax, n - b0);
         TRY(h->pts_stage.ensure((size_t)nb * h->d * 4));
         TRY(h->assign.ensure((size_t)nb * 4));
-        TRY(h->enc_codes.ensure((size_t)nb * h->m));
+        TRY(h->enc_codes.ensure((size_t)nb * h->cb));
         TRY(h2d_copy(h->pts_stage.p, pts + (size_t)b0 * h->d, (size_t)nb * h->d * 4, h->stream));
         TRY(run_coarse(h, h->pts_stage.as<float>(), nb, false));   // push! path: exact distances
         hipLaunchKernelGGL(argmin_rows_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, h->cdist.as<float>(), (int)nb,
                            h->kc, h->assign.as<int>());
         HIP_TRY(hipGetLastError());
+        if (h->u16)   // codeword indices; the caller translates them to labels
+            hipLaunchKernelGGL(encode_u16_kernel, dim3((unsigned)nb), dim3(256), lds, h->stream, h->pts_stage.as<float>(), h->assign.as<int>(),
+                               h->d, h->m, h->ksub, h->dsub, h->centroids.as<float>(), h->codebooks.as<float>(), h->enc_codes.as<uint16_t>());
+        else
         hipLaunchKernelGGL(encode_kernel, dim3((unsigned)nb), dim3(256), lds, h->stream, h->pts_stage.as<float>(), h->assign.as<int>(),
                            h->d, h->m, h->ksub, h->dsub, h->centroids.as<float>(), h->codebooks.as<float>(), h->labels.as<uint8_t>(),
                            h->enc_codes.as<uint8_t>());
         HIP_TRY(hipGetLastError());
         TRY(d2h_copy(out_list + b0, h->assign.p, (size_t)nb * 4, h->stream));
-        TRY(d2h_copy(out_codes + (size_t)b0 * h->m, h->enc_codes.p, (size_t)nb * h->m, h->stream));
+        TRY(d2h_copy(out_codes + (size_t)b0 * h->cb, h->enc_codes.p, (size_t)nb * h->cb, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
     }
     return IVFADC_OK;
@@ -2219,7 +2281,7 @@ int train_impl(int device, int d, int64_t n, const float *data, int kc, int k, i
     if (m < 1 || m > d) return fail(IVFADC_ERR_ASSERT, "Number of codebooks has to be between 1 and %d", d);       // :120
     if (coarse_maxiter < 1 || quant_maxiter < 1) return fail(IVFADC_ERR_ASSERT, "Number of clustering iterations has to be > 0");
     if (d % m != 0) return fail(IVFADC_ERR_INVALID, "d %% m != 0 is not supported");
-    if (k < 1 || k > 256) return fail(IVFADC_ERR_INVALID, "k must be in 1..256");
+    if (k < 1 || k > 65536) return fail(IVFADC_ERR_INVALID, "k must be in 1..65536 (UInt8 or UInt16 codes)");
     if (kc > n) return fail(IVFADC_ERR_INVALID, "kc > n");
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
@@ -2277,16 +2339,40 @@ extern "C" {
 
 const char *ivfadc_last_error(void) { return g_err.c_str(); }
 
-int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub, const float *centroids, const float *codebooks,
-                  const uint8_t *code_labels)
-try {
+// UInt16 labels -> per block (label << 16 | codeword index), ascending; false (and the block / label) on a duplicate label
+static bool sort_labels16(const uint16_t *lab16, int m, int ksub, std::vector<uint32_t> &out, int &dup_block, int &dup_label)
+{
+    out.resize((size_t)m * ksub);
+    for (int i = 0; i < m; ++i) {
+        uint32_t *b = out.data() + (size_t)i * ksub;
+        for (int c = 0; c < ksub; ++c) b[c] = ((uint32_t)lab16[(size_t)i * ksub + c] << 16) | (uint32_t)c;
+        std::sort(b, b + ksub);
+        for (int c = 1; c < ksub; ++c)
+            if ((b[c] >> 16) == (b[c - 1] >> 16)) { dup_block = i; dup_label = (int)(b[c] >> 16); return false; }
+    }
+    return true;
+}
+
+// codeword index of label v in block i of a sorted label table (sort_labels16), -1: not a label of the block
+static int32_t find_label16(const std::vector<uint32_t> &sorted, int ksub, int i, uint16_t v)
+{
+    const uint32_t *b = sorted.data() + (size_t)i * ksub, *e = b + ksub;
+    const uint32_t *it = std::lower_bound(b, e, (uint32_t)v << 16);
+    return (it != e && (*it >> 16) == v) ? (int32_t)(*it & 0xFFFFu) : -1;
+}
+
+// one of code_labels (U = UInt8) and lab16 (U = UInt16) is given
+static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksub, const float *centroids, const float *codebooks,
+                       const uint8_t *code_labels, const uint16_t *lab16)
+{
     if (!out) return fail(IVFADC_ERR_INVALID, "out is null");
     *out = nullptr;
     if (d < 1 || kc < 1 || m < 1 || ksub < 1) return fail(IVFADC_ERR_INVALID, "d, kc, m, ksub must be >= 1");
     if (m > d) return fail(IVFADC_ERR_ASSERT, "Number of codebooks has to be between 1 and %d", d);
     if (d % m != 0) return fail(IVFADC_ERR_INVALID, "d %% m != 0 is not supported (rowrange for ragged sub-spaces is unverifiable)");
-    if (ksub > 256) return fail(IVFADC_ERR_INVALID, "ksub > 256 does not fit UInt8 codes");
-    if (!centroids || !codebooks || !code_labels) return fail(IVFADC_ERR_INVALID, "null array");
+    if (!lab16 && ksub > 256) return fail(IVFADC_ERR_INVALID, "ksub > 256 does not fit UInt8 codes");
+    if (lab16 && ksub > 65536) return fail(IVFADC_ERR_INVALID, "ksub > 65536 does not fit UInt16 codes");
+    if (!centroids || !codebooks || (!code_labels && !lab16)) return fail(IVFADC_ERR_INVALID, "null array");
     // Quantizers must be finite: every bound the filters certify (coarse score filter, lower-bound tables) is computed from their norms.
     // (Queries are not scanned -- that would cost the hot path a pass over every batch: a query with a NaN or infinite component gets
     // unspecified neighbours, valid ids and counts, and leaves the other queries of its batch untouched; tests/test_gpu_parity.py.)
@@ -2294,25 +2380,37 @@ try {
         if (!std::isfinite(centroids[i])) return fail(IVFADC_ERR_INVALID, "centroid %zu has a non-finite component", i / (size_t)d);
     for (size_t i = 0; i < (size_t)d * ksub; ++i)
         if (!std::isfinite(codebooks[i])) return fail(IVFADC_ERR_INVALID, "codebook %zu has a non-finite component", i / ((size_t)(d / m) * ksub));
-    std::vector<uint8_t> ok((size_t)m * 256, 0);
-    for (int i = 0; i < m; ++i)
-        for (int c = 0; c < ksub; ++c) {
-            uint8_t lab = code_labels[(size_t)i * ksub + c];
-            if (ok[(size_t)i * 256 + lab]) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", (int)lab, i);
-            ok[(size_t)i * 256 + lab] = 1;
-        }
+    std::vector<uint8_t> ok;
+    std::vector<uint32_t> inv;
+    if (lab16) {
+        int db = 0, dl = 0;
+        if (!sort_labels16(lab16, m, ksub, inv, db, dl)) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", dl, db);
+    } else {
+        ok.assign((size_t)m * 256, 0);
+        for (int i = 0; i < m; ++i)
+            for (int c = 0; c < ksub; ++c) {
+                uint8_t lab = code_labels[(size_t)i * ksub + c];
+                if (ok[(size_t)i * 256 + lab]) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", (int)lab, i);
+                ok[(size_t)i * 256 + lab] = 1;
+            }
+    }
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail(IVFADC_ERR_HIP, "no HIP device");
     if (device < 0 || device >= ndev) return fail(IVFADC_ERR_INVALID, "device %d out of range [0,%d)", device, ndev);
     ivfadc_index *h = new ivfadc_index();
     h->device = device;
-    h->d = d; h->kc = kc; h->m = m; h->ksub = ksub; h->dsub = d / m; h->cs = code_stride(m);
+    h->d = d; h->kc = kc; h->m = m; h->ksub = ksub; h->dsub = d / m;
+    h->u16 = lab16 != nullptr;
+    h->cb = h->u16 ? 2 * m : m;
+    h->cs = code_stride(h->cb);
     h->h_label_ok.swap(ok);
+    h->lab_sorted.swap(inv);
+    if (lab16) h->lab16.assign(lab16, lab16 + (size_t)m * ksub);
     h->identity_labels = true;
     for (int i = 0; i < m && h->identity_labels; ++i)
         for (int c = 0; c < ksub; ++c)
-            if (code_labels[(size_t)i * ksub + c] != (uint8_t)c) { h->identity_labels = false; break; }
+            if ((lab16 ? (int)lab16[(size_t)i * ksub + c] : (int)code_labels[(size_t)i * ksub + c]) != c) { h->identity_labels = false; break; }
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     hipDeviceProp_t prop;
@@ -2322,7 +2420,7 @@ try {
     int rc = h->centroids.ensure((size_t)d * kc * 4);
     if (rc == IVFADC_OK) rc = h->codebooks.ensure((size_t)d * ksub * 4);
     if (rc == IVFADC_OK) rc = h->codebooks_t.ensure((size_t)m * (((d / m) + 3) & ~3) * ksub * 4);
-    if (rc == IVFADC_OK) rc = h->labels.ensure((size_t)m * ksub);
+    if (rc == IVFADC_OK) rc = h->labels.ensure((size_t)m * ksub * (lab16 ? 2 : 1));
     if (rc == IVFADC_OK) {
         e = h2d_hip(h->centroids.p, centroids, (size_t)d * kc * 4, h->stream);
         if (e == hipSuccess) e = h2d_hip(h->codebooks.p, codebooks, (size_t)d * ksub * 4, h->stream);
@@ -2330,7 +2428,7 @@ try {
             // regrouped copy for the table build (IndexView::codebooks_t)
             const int dsub = d / m, dp = (dsub + 3) & ~3;   // [m][dp / 4][ksub][4], zero-padded
             std::vector<float> t((size_t)m * dp * ksub, 0.0f);
-            if (dsub == 6 && (m & 1) == 0) {
+            if (dsub == 6 && (m & 1) == 0 && !lab16) {   // (a 16-bit handle keeps the plain layout: u16_scan_kernel reads it)
                 // pair-packed (build_tables_t, DSUB == 6): [m / 2][3][ksub][4], element e = 0..11 of pair p, codeword c =
                 // dimension e of sub-quantizer 2p (e < 6) or dimension e - 6 of sub-quantizer 2p + 1
                 for (int p = 0; p < m / 2; ++p)
@@ -2359,9 +2457,10 @@ try {
                 if (rc == IVFADC_OK) e = h2d_hip(h->codebooks_p.p, pp.data(), pp.size() * 4, h->stream);
             }
         }
-        if (e == hipSuccess) e = h2d_hip(h->labels.p, code_labels, (size_t)m * ksub, h->stream);
+        if (e == hipSuccess)
+            e = lab16 ? h2d_hip(h->labels.p, lab16, (size_t)m * ksub * 2, h->stream) : h2d_hip(h->labels.p, code_labels, (size_t)m * ksub, h->stream);
         if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-        if (rc == IVFADC_OK && lb_shape(m, d / m) && ksub == 256) {
+        if (rc == IVFADC_OK && !lab16 && lb_shape(m, d / m) && ksub == 256) {
             // operands of the lower-bound table build (lbscan.hip.h), everything in LABEL order (table slot = code byte):
             // split[ii][g][p][lane] = 8 bf16 of label 64 g + lane -- parts p < NP / 2: hi pieces of dimensions 8 p .. 8 p + 7,
             // the others the lo pieces (x = hi + lo + O(2^-18 |x|)); n2 = ||codeword||^2 in double, rounded once
@@ -2441,7 +2540,7 @@ try {
             }
         }
     }
-    if (rc == IVFADC_OK && nf_shape(m, d / m) && ksub == 256) {
+    if (rc == IVFADC_OK && !lab16 && nf_shape(m, d / m) && ksub == 256) {
         // operands of the narrow-field list-major kernel (nfscan.hip.h): ||codeword||^2 by CODEWORD index (double, rounded once) for the
         // filter tables, and the f32 codewords in LABEL order (table slot = code byte) for the exact sums of what the filter lets through
         const int dsub = d / m;
@@ -2561,6 +2660,30 @@ try {
     h->hl_ids.assign((size_t)kc, {});
     h->dirty = true;
     *out = h;
+    return IVFADC_OK;
+}
+
+int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub, const float *centroids, const float *codebooks,
+                  const uint8_t *code_labels)
+try {
+    return create_impl(out, device, d, kc, m, ksub, centroids, codebooks, code_labels, nullptr);
+} IVF_CATCH
+
+int ivfadc_create_u16(ivfadc_t **out, int device, int d, int kc, int m, int ksub, const float *centroids, const float *codebooks,
+                      const void *code_labels)
+try {
+    if (!code_labels) {
+        if (out) *out = nullptr;
+        return fail(IVFADC_ERR_INVALID, "null array");
+    }
+    return create_impl(out, device, d, kc, m, ksub, centroids, codebooks, nullptr, (const uint16_t *)code_labels);
+} IVF_CATCH
+
+int ivfadc_code_bits(ivfadc_t *h, int *bits)
+try {
+    HandleLock lk_(h);
+    if (!h || !bits) return fail(IVFADC_ERR_INVALID, "null argument");
+    *bits = h->u16 ? 16 : 8;
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -2773,10 +2896,84 @@ try {
     return clone_view(h, out);
 } IVF_CATCH
 
+// a 16-bit handle refuses the uint8_t entries, an 8-bit handle the _u16 ones
+static int check_width(ivfadc_index *h, bool want_u16, const char *what)
+{
+    if (h->u16 && !want_u16) return fail(IVFADC_ERR_STATE, "%s: this index has UInt16 codes; use %s_u16", what, what);
+    if (!h->u16 && want_u16) return fail(IVFADC_ERR_STATE, "%s: this index has UInt8 codes; use the entry without _u16", what);
+    return IVFADC_OK;
+}
+
+static int check_offsets(ivfadc_index *h, const int64_t *offsets, const void *codes, const uint32_t *ids)
+{
+    const int kc = h->kc;
+    if (offsets[0] != 0) return fail(IVFADC_ERR_INVALID, "offsets[0] must be 0");
+    for (int l = 0; l < kc; ++l)
+        if (offsets[l + 1] < offsets[l]) return fail(IVFADC_ERR_INVALID, "offsets must be non-decreasing (list %d)", l);
+    const int64_t n = offsets[kc];
+    if (n > (int64_t)0xFFFFFFFFll) return fail(IVFADC_ERR_ASSERT, "index capacity of UInt32 ids exceeded");
+    if (n > 0 && (!codes || !ids)) return fail(IVFADC_ERR_INVALID, "null codes/ids");
+    return IVFADC_OK;
+}
+
+// mirror <- (offsets, codes in mirror form: cb bytes per point, ids), then the device copy
+static int set_lists_mirror(ivfadc_t *h, const int64_t *offsets, const uint8_t *codes, const uint32_t *ids, const char *what)
+{
+    const int kc = h->kc, cb = h->cb;
+    TRY(set_device(h));
+    MutationScope ms;
+    TRY(ms.begin(h, what));
+    for (int l = 0; l < kc; ++l) {
+        const int64_t a = offsets[l], b = offsets[l + 1];
+        h->h_len[l] = b - a;
+        h->hl_codes[l].assign(codes + (size_t)a * cb, codes + (size_t)b * cb);
+        h->hl_ids[l].assign(ids + a, ids + b);
+    }
+    return upload_lists(h);
+}
+
+// labels (n x m uint16_t) -> codeword indices in mirror form; ERR_INVALID names the first code that is not a label of its block
+static int labels_to_indices(const ivfadc_index *h, int64_t n, const uint16_t *lab, std::vector<uint8_t> &out)
+{
+    const int m = h->m;
+    out.resize((size_t)n * h->cb);
+    uint16_t *dst = (uint16_t *)out.data();
+    for (int64_t p = 0; p < n; ++p)
+        for (int i = 0; i < m; ++i) {
+            const uint16_t v = lab[(size_t)p * m + i];
+            const int32_t c = h->identity_labels ? (v < h->ksub ? (int32_t)v : -1) : find_label16(h->lab_sorted, h->ksub, i, v);
+            if (c < 0) return fail(IVFADC_ERR_INVALID, "code %d of point %lld is not a label of codebook %d", (int)v, (long long)p, i);
+            dst[(size_t)p * m + i] = (uint16_t)c;
+        }
+    return IVFADC_OK;
+}
+
+// codeword indices (mirror form) -> labels, in place
+static void indices_to_labels(const ivfadc_index *h, int64_t n, uint16_t *codes)
+{
+    if (h->identity_labels) return;
+    const int m = h->m, ksub = h->ksub;
+    for (int64_t p = 0; p < n; ++p)
+        for (int i = 0; i < m; ++i) codes[(size_t)p * m + i] = h->lab16[(size_t)i * ksub + codes[(size_t)p * m + i]];
+}
+
+int ivfadc_set_lists_u16(ivfadc_t *h, const int64_t *offsets, const void *codes, const uint32_t *ids)
+try {
+    HandleLock lk_(h);
+    if (!h || !offsets) return fail(IVFADC_ERR_INVALID, "null argument");
+    TRY(check_width(h, true, "ivfadc_set_lists"));
+    TRY(check_mutable(h, "ivfadc_set_lists_u16"));
+    TRY(check_offsets(h, offsets, codes, ids));
+    std::vector<uint8_t> idx;
+    TRY(labels_to_indices(h, offsets[h->kc], (const uint16_t *)codes, idx));
+    return set_lists_mirror(h, offsets, idx.data(), ids, "ivfadc_set_lists_u16");
+} IVF_CATCH
+
 int ivfadc_set_lists(ivfadc_t *h, const int64_t *offsets, const uint8_t *codes, const uint32_t *ids)
 try {
     HandleLock lk_(h);
     if (!h || !offsets) return fail(IVFADC_ERR_INVALID, "null argument");
+    TRY(check_width(h, false, "ivfadc_set_lists"));
     TRY(check_mutable(h, "ivfadc_set_lists"));
     const int kc = h->kc, m = h->m;
     if (offsets[0] != 0) return fail(IVFADC_ERR_INVALID, "offsets[0] must be 0");
@@ -2808,6 +3005,7 @@ int ivfadc_synth_lists(ivfadc_t *h, const int64_t *offsets, uint64_t seed)
 try {
     HandleLock lk_(h);
     if (!h || !offsets) return fail(IVFADC_ERR_INVALID, "null argument");
+    TRY(check_width(h, false, "ivfadc_synth_lists"));
     TRY(check_mutable(h, "ivfadc_synth_lists"));
     if (h->ksub != 256) return fail(IVFADC_ERR_INVALID, "synthetic lists need ksub == 256");
     TRY(set_device(h));
@@ -2852,9 +3050,25 @@ try {
     if (n < 0) return fail(IVFADC_ERR_INVALID, "n < 0");
     if (n == 0) return IVFADC_OK;
     if (!pts || !out_list || !out_codes) return fail(IVFADC_ERR_INVALID, "null argument");
+    TRY(check_width(h, false, "ivfadc_encode"));
     if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_encode: the residual quantizer carries a rotation (:opq); this index is served for search only");
     TRY(set_device(h));
     return encode_dev(h, n, pts, out_list, out_codes);
+} IVF_CATCH
+
+int ivfadc_encode_u16(ivfadc_t *h, int64_t n, const float *pts, int32_t *out_list, void *out_codes)
+try {
+    HandleLock lk_(h);
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    if (n < 0) return fail(IVFADC_ERR_INVALID, "n < 0");
+    TRY(check_width(h, true, "ivfadc_encode"));
+    if (n == 0) return IVFADC_OK;
+    if (!pts || !out_list || !out_codes) return fail(IVFADC_ERR_INVALID, "null argument");
+    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_encode_u16: the residual quantizer carries a rotation (:opq); this index is served for search only");
+    TRY(set_device(h));
+    TRY(encode_dev(h, n, pts, out_list, (uint8_t *)out_codes));
+    indices_to_labels(h, n, (uint16_t *)out_codes);
+    return IVFADC_OK;
 } IVF_CATCH
 
 // The mirror edit of push!: `lst` / `cod` are the (already computed) assignment and codes of the new points.  The
@@ -2863,7 +3077,7 @@ try {
 // leaves a handle whose next search re-lays the lists out from the mirror instead of one that searches stale lists.
 static int append_encoded(ivfadc_t *h, int64_t nnew, const int32_t *lst, const uint8_t *cod, const uint32_t *ids)
 {
-    const int m = h->m, cs = h->cs;
+    const int m = h->cb, cs = h->cs;   // (cod: mirror form, cb bytes per point)
     const int64_t n_old = h->ntotal();
     MutationScope ms;
     TRY(ms.begin(h, "ivfadc_append"));
@@ -2942,6 +3156,7 @@ try {
     HandleLock lk_(h);
     TRY(append_check(h, nnew, pts, ids));
     TRY(check_mutable(h, "ivfadc_append"));
+    TRY(check_width(h, false, "ivfadc_append"));
     if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_append: the residual quantizer carries a rotation (:opq); this index is served for search only");
     if (nnew == 0) return IVFADC_OK;
     TRY(set_device(h));
@@ -2951,6 +3166,27 @@ try {
     TRY(append_encoded(h, nnew, lst.data(), cod.data(), ids));
     if (out_list) memcpy(out_list, lst.data(), (size_t)nnew * 4);
     if (out_codes) memcpy(out_codes, cod.data(), (size_t)nnew * h->m);
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_append_u16(ivfadc_t *h, int64_t nnew, const float *pts, const uint32_t *ids, int32_t *out_list, void *out_codes)
+try {
+    HandleLock lk_(h);
+    TRY(append_check(h, nnew, pts, ids));
+    TRY(check_width(h, true, "ivfadc_append"));
+    TRY(check_mutable(h, "ivfadc_append_u16"));
+    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_append_u16: the residual quantizer carries a rotation (:opq); this index is served for search only");
+    if (nnew == 0) return IVFADC_OK;
+    TRY(set_device(h));
+    std::vector<int32_t> lst((size_t)nnew);
+    std::vector<uint8_t> cod((size_t)nnew * h->cb);
+    TRY(encode_dev(h, nnew, pts, lst.data(), cod.data()));   // codeword indices; nothing has changed yet if this fails
+    TRY(append_encoded(h, nnew, lst.data(), cod.data(), ids));
+    if (out_list) memcpy(out_list, lst.data(), (size_t)nnew * 4);
+    if (out_codes) {
+        memcpy(out_codes, cod.data(), (size_t)nnew * h->cb);
+        indices_to_labels(h, nnew, (uint16_t *)out_codes);
+    }
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -2971,7 +3207,7 @@ try {
     const bool was_dirty = h->dirty;
     h->dirty = true;
     // host mirror, pass 1: drop the entries (stable) and collect the ids that were really there
-    const int kc = h->kc, m = h->m;
+    const int kc = h->kc, m = h->cb;
     std::vector<uint32_t> rem;
     for (int l = 0; l < kc; ++l) {
         auto &lid = h->hl_ids[l];
@@ -3074,6 +3310,7 @@ try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
     if (nparts < 1 || part < 0 || part >= nparts) return fail(IVFADC_ERR_INVALID, "part %d of %d", part, nparts);
+    if (h->u16 && nparts > 1) return fail(IVFADC_ERR_INVALID, "the list-partitioned mode serves UInt8 codes only");
     h->part_n = nparts;
     h->part_i = part;
     h->partial_nq = -1;
@@ -4058,6 +4295,7 @@ int ivfadc_get_lists(ivfadc_t *h, int64_t *offsets, uint8_t *codes, uint32_t *id
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_width(h, false, "ivfadc_get_lists"));
     if (h->is_view) return fail(IVFADC_ERR_STATE, "a view keeps no host mirror of the lists");
     if (h->synthetic) return fail(IVFADC_ERR_STATE, "device-synthesised lists keep no host mirror");
     int64_t run = 0;
@@ -4065,6 +4303,28 @@ try {
         const int64_t len = h->h_len[l];
         if (offsets) offsets[l] = run;
         if (codes && len) memcpy(codes + (size_t)run * h->m, h->hl_codes[l].data(), (size_t)len * h->m);
+        if (ids && len) memcpy(ids + run, h->hl_ids[l].data(), (size_t)len * 4);
+        run += len;
+    }
+    if (offsets) offsets[h->kc] = run;
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_get_lists_u16(ivfadc_t *h, int64_t *offsets, void *codes, uint32_t *ids)
+try {
+    HandleLock lk_(h);
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_width(h, true, "ivfadc_get_lists"));
+    if (h->is_view) return fail(IVFADC_ERR_STATE, "a view keeps no host mirror of the lists");
+    int64_t run = 0;
+    for (int l = 0; l < h->kc; ++l) {
+        const int64_t len = h->h_len[l];
+        if (offsets) offsets[l] = run;
+        if (codes && len) {
+            uint16_t *dst = (uint16_t *)codes + (size_t)run * h->m;
+            memcpy(dst, h->hl_codes[l].data(), (size_t)len * h->cb);
+            indices_to_labels(h, len, dst);
+        }
         if (ids && len) memcpy(ids + run, h->hl_ids[l].data(), (size_t)len * 4);
         run += len;
     }
@@ -4087,11 +4347,25 @@ int ivfadc_get_quantizers(ivfadc_t *h, float *centroids, float *codebooks, uint8
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_width(h, false, "ivfadc_get_quantizers"));
     TRY(set_device(h));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (centroids) TRY(d2h_copy(centroids, h->centroids.p, (size_t)h->d * h->kc * 4, h->stream));
     if (codebooks) TRY(d2h_copy(codebooks, h->codebooks.p, (size_t)h->d * h->ksub * 4, h->stream));
     if (code_labels) HIP_TRY(hipMemcpy(code_labels, h->labels.p, (size_t)h->m * h->ksub, hipMemcpyDeviceToHost));
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_get_quantizers_u16(ivfadc_t *h, float *centroids, float *codebooks, void *code_labels)
+try {
+    HandleLock lk_(h);
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_width(h, true, "ivfadc_get_quantizers"));
+    TRY(set_device(h));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (centroids) TRY(d2h_copy(centroids, h->centroids.p, (size_t)h->d * h->kc * 4, h->stream));
+    if (codebooks) TRY(d2h_copy(codebooks, h->codebooks.p, (size_t)h->d * h->ksub * 4, h->stream));
+    if (code_labels) memcpy(code_labels, h->lab16.data(), h->lab16.size() * 2);
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -4360,6 +4634,7 @@ try {
     HandleLock lk_(h);
     if (!h || !query || !out_table || !out_consts) return fail(IVFADC_ERR_INVALID, "null argument");
     if (cell < 0 || cell >= h->kc) return fail(IVFADC_ERR_INVALID, "cell out of range");
+    if (h->u16) return fail(IVFADC_ERR_STATE, "ivfadc_debug_lb_table: this index has UInt16 codes (no 8-bit lower-bound tables)");
     if (!h->lb_split.p || !lb_shape(h->m, h->dsub)) return fail(IVFADC_ERR_STATE, "no matrix-core table kernels for m=%d dsub=%d", h->m, h->dsub);
     TRY(set_device(h));
     const int m = h->m;
@@ -4470,21 +4745,24 @@ try {
     }
     const int d = h->d, kc = h->kc, m = h->m, k = h->ksub, dsub = h->dsub;
     std::vector<float> cent((size_t)kc * d), cbs((size_t)d * k);
-    std::vector<uint8_t> lab((size_t)m * k);
+    const int ub = h->u16 ? 2 : 1;   // bytes of U
+    std::vector<uint8_t> lab((size_t)m * k * ub);
     HIP_TRY(hipStreamSynchronize(h->stream));
     TRY(d2h_copy(cent.data(), h->centroids.p, cent.size() * 4, h->stream));
     TRY(d2h_copy(cbs.data(), h->codebooks.p, cbs.size() * 4, h->stream));
-    HIP_TRY(hipMemcpy(lab.data(), h->labels.p, lab.size(), hipMemcpyDeviceToHost));
+    if (h->u16) memcpy(lab.data(), h->lab16.data(), lab.size());
+    else HIP_TRY(hipMemcpy(lab.data(), h->labels.p, lab.size(), hipMemcpyDeviceToHost));
     FileCloser fc{fopen(path, "wb")};
     FILE *f = fc.f;
     if (!f) return fail(IVFADC_ERR_INVALID, "cannot open %s for writing", path);
     const char *iname = index_bits == 8 ? "UInt8" : (index_bits == 16 ? "UInt16" : "UInt32");
-    fprintf(f, "%d %d\n%lld %d %d %d\nNaiveQuantizer\nQuantizedArrays.OrthogonalQuantization\nUInt8\n%s\n"
-               "Distances.SqEuclidean\nDistances.SqEuclidean\nFloat32\n", d, kc, (long long)h->ntotal(), m, k, dsub, iname);
+    fprintf(f, "%d %d\n%lld %d %d %d\nNaiveQuantizer\nQuantizedArrays.OrthogonalQuantization\n%s\n%s\n"
+               "Distances.SqEuclidean\nDistances.SqEuclidean\nFloat32\n", d, kc, (long long)h->ntotal(), m, k, dsub, h->u16 ? "UInt16" : "UInt8",
+            iname);
     bool ok = fwrite(cent.data(), 4, cent.size(), f) == cent.size();                  // centroid c = column c
     std::vector<float> row((size_t)k);
     for (int i = 0; i < m && ok; ++i) {
-        ok = fwrite(lab.data() + (size_t)i * k, 1, (size_t)k, f) == (size_t)k;
+        ok = fwrite(lab.data() + (size_t)i * k * ub, 1, (size_t)k * ub, f) == (size_t)k * ub;
         for (int j = 0; j < dsub && ok; ++j) {                                        // vectors[j, :]
             for (int c = 0; c < k; ++c) row[c] = cbs[((size_t)i * k + c) * dsub + j];
             ok = fwrite(row.data(), 4, (size_t)k, f) == (size_t)k;
@@ -4500,7 +4778,7 @@ try {
             rot[i] = 0.0f;
         }
     }
-    std::vector<uint8_t> narrow;
+    std::vector<uint8_t> narrow, wide;
     for (int l = 0; l < kc && ok; ++l) {
         const int64_t len = h->h_len[l];
         ok = fwrite(&len, 8, 1, f) == 1;
@@ -4516,6 +4794,11 @@ try {
             }
             ok = ok && (len == 0 || fwrite(narrow.data(), 1, narrow.size(), f) == narrow.size());
         }
+        if (h->u16) {   // codeword indices -> labels
+            wide = h->hl_codes[l];
+            indices_to_labels(h, len, (uint16_t *)wide.data());
+            ok = ok && (len == 0 || fwrite(wide.data(), 1, (size_t)len * h->cb, f) == (size_t)len * h->cb);
+        } else
         ok = ok && (len == 0 || fwrite(h->hl_codes[l].data(), 1, (size_t)len * m, f) == (size_t)len * m);
     }
     if (!ok) return fail(IVFADC_ERR_INVALID, "short write to %s", path);
@@ -4545,7 +4828,9 @@ try {
         return fail(IVFADC_ERR_INVALID, "only NaiveQuantizer files are supported, got %s", ln[2].c_str());
     if (last_component(ln[3]) != "OrthogonalQuantization")
         return fail(IVFADC_ERR_INVALID, "quantization %s is not supported (only OrthogonalQuantization, i.e. :pq)", ln[3].c_str());
-    if (ln[4] != "UInt8") return fail(IVFADC_ERR_INVALID, "quantization element type %s (only UInt8)", ln[4].c_str());
+    int ub = 0;   // bytes of U
+    if (ln[4] == "UInt8") ub = 1; else if (ln[4] == "UInt16") ub = 2;
+    else return fail(IVFADC_ERR_INVALID, "quantization element type %s (only UInt8 and UInt16)", ln[4].c_str());
     int ibytes = 0;
     if (ln[5] == "UInt8") ibytes = 1; else if (ln[5] == "UInt16") ibytes = 2; else if (ln[5] == "UInt32") ibytes = 4;
     else return fail(IVFADC_ERR_INVALID, "index type %s is not supported by the HIP path", ln[5].c_str());
@@ -4556,7 +4841,8 @@ try {
     int tbytes = 0;
     if (ln[8] == "Float32") tbytes = 4; else if (ln[8] == "Float64") tbytes = 8;
     else return fail(IVFADC_ERR_INVALID, "element type %s", ln[8].c_str());
-    if (nrows < 1 || nclusters < 1 || m < 1 || k < 1 || k > 256 || dsub < 1 || n < 0) return fail(IVFADC_ERR_INVALID, "%s: inconsistent sizes", path);
+    if (nrows < 1 || nclusters < 1 || m < 1 || k < 1 || k > (ub == 1 ? 256 : 65536) || dsub < 1 || n < 0)
+        return fail(IVFADC_ERR_INVALID, "%s: inconsistent sizes", path);
     // every size is checked against what the file can hold BEFORE anything is allocated from it (a corrupt or hostile
     // header must come back as IVFADC_ERR_INVALID, not as std::bad_alloc); 128-bit products cannot wrap
     typedef unsigned __int128 u128;
@@ -4566,9 +4852,9 @@ try {
     if (nrows > (1ll << 24) || nclusters > (1ll << 31) - 1 || m > nrows || dsub > nrows || (u128)m * (u128)dsub != (u128)nrows)
         return fail(IVFADC_ERR_INVALID, "%s: inconsistent sizes", path);
     if (n > (long long)0xFFFFFFFFll) return fail(IVFADC_ERR_INVALID, "%s: %lld vectors exceed UInt32 ids", path, n);
-    const u128 quant_bytes = (u128)tbytes * (u128)nrows * (u128)nclusters + (u128)m * ((u128)k + (u128)tbytes * (u128)dsub * (u128)k) +
+    const u128 quant_bytes = (u128)tbytes * (u128)nrows * (u128)nclusters + (u128)m * ((u128)k * ub + (u128)tbytes * (u128)dsub * (u128)k) +
                              (u128)tbytes * (u128)nrows * (u128)nrows;
-    const u128 list_bytes = (u128)nclusters * 8 + (u128)n * (u128)(ibytes + m);
+    const u128 list_bytes = (u128)nclusters * 8 + (u128)n * (u128)(ibytes + m * ub);
     if (quant_bytes + list_bytes > remain)
         return fail(IVFADC_ERR_INVALID, "%s: header describes more data than the file holds (truncated or corrupt)", path);
     auto read_floats = [&](float *dst, size_t cnt) {
@@ -4579,10 +4865,10 @@ try {
         return true;
     };
     std::vector<float> cent((size_t)nclusters * nrows), cbs((size_t)nrows * k), row((size_t)std::max(k, nrows));
-    std::vector<uint8_t> lab((size_t)m * k);
+    std::vector<uint8_t> lab((size_t)m * k * ub);
     if (!read_floats(cent.data(), cent.size())) return fail(IVFADC_ERR_INVALID, "%s: truncated centroids", path);
     for (long long i = 0; i < m; ++i) {
-        if (!read_exact(f, lab.data() + (size_t)i * k, (size_t)k)) return fail(IVFADC_ERR_INVALID, "%s: truncated codebook", path);
+        if (!read_exact(f, lab.data() + (size_t)i * k * ub, (size_t)k * ub)) return fail(IVFADC_ERR_INVALID, "%s: truncated codebook", path);
         for (long long j = 0; j < dsub; ++j) {
             if (!read_floats(row.data(), (size_t)k)) return fail(IVFADC_ERR_INVALID, "%s: truncated codebook", path);
             for (long long c = 0; c < k; ++c) cbs[((size_t)i * k + c) * dsub + j] = row[c];
@@ -4603,7 +4889,7 @@ try {
     std::vector<int64_t> offsets((size_t)nclusters + 1, 0);
     std::vector<uint8_t> codes, raw;
     std::vector<uint32_t> ids;
-    codes.reserve((size_t)n * m);
+    codes.reserve((size_t)n * m * ub);
     ids.reserve((size_t)n);
     for (long long l = 0; l < nclusters; ++l) {
         int64_t len = 0;
@@ -4617,14 +4903,28 @@ try {
             ids.push_back(v);
         }
         const size_t at = codes.size();
-        codes.resize(at + (size_t)len * m);
-        if (!read_exact(f, codes.data() + at, (size_t)len * m)) return fail(IVFADC_ERR_INVALID, "%s: truncated list %lld", path, l);
+        codes.resize(at + (size_t)len * m * ub);
+        if (!read_exact(f, codes.data() + at, (size_t)len * m * ub)) return fail(IVFADC_ERR_INVALID, "%s: truncated list %lld", path, l);
         offsets[l + 1] = offsets[l] + len;
     }
     if (offsets[nclusters] != n) return fail(IVFADC_ERR_INVALID, "%s: the lists hold %lld entries, the header says %lld", path, (long long)offsets[nclusters], n);
     ivfadc_t *h = nullptr;
-    TRY(ivfadc_create(&h, device, (int)nrows, (int)nclusters, (int)m, (int)k, cent.data(), cbs.data(), lab.data()));
-    const int rc = ivfadc_set_lists(h, offsets.data(), codes.data(), ids.data());
+    if (ub == 2) {
+        // UInt16: labels distinct per block and every code a label of its block, checked here, before any device call
+        const uint16_t *lab16 = (const uint16_t *)lab.data(), *c16 = (const uint16_t *)codes.data();
+        std::vector<uint32_t> sorted;
+        int db = 0, dl = 0;
+        if (!sort_labels16(lab16, (int)m, (int)k, sorted, db, dl)) return fail(IVFADC_ERR_INVALID, "%s: duplicate label %d in codebook %d", path, dl, db);
+        for (long long p = 0; p < n; ++p)
+            for (long long i = 0; i < m; ++i)
+                if (find_label16(sorted, (int)k, (int)i, c16[(size_t)p * m + i]) < 0)
+                    return fail(IVFADC_ERR_INVALID, "%s: code %d of point %lld is not a label of codebook %lld", path, (int)c16[(size_t)p * m + i], p, i);
+        TRY(create_impl(&h, device, (int)nrows, (int)nclusters, (int)m, (int)k, cent.data(), cbs.data(), nullptr, lab16));
+    } else {
+        TRY(ivfadc_create(&h, device, (int)nrows, (int)nclusters, (int)m, (int)k, cent.data(), cbs.data(), lab.data()));
+    }
+    const int rc = ub == 2 ? ivfadc_set_lists_u16(h, offsets.data(), codes.data(), ids.data())
+                           : ivfadc_set_lists(h, offsets.data(), codes.data(), ids.data());
     if (rc != IVFADC_OK) { ivfadc_destroy(h); return rc; }
     if (!rot_identity) h->rot = std::move(rotm);
     if (out_index_bits) *out_index_bits = ibytes * 8;

@@ -62,14 +62,14 @@ class ResidualQuantizer:
 
 
 class InvertedList:
-    """index.jl:8-11: idxs (0-based ids) and codes ((len, m) bytes) of one Voronoi cell."""
+    """index.jl:8-11: idxs (0-based ids) and codes ((len, m) uint8 or uint16) of one Voronoi cell."""
 
     def __init__(self, idxs, codes):
         self.idxs = idxs
         self.codes = codes
 
     def __repr__(self):
-        return "InvertedList{%s,UInt8}, %d vectors" % (_JULIA_NAMES[self.idxs.dtype], len(self.idxs))
+        return "InvertedList{%s,%s}, %d vectors" % (_JULIA_NAMES[self.idxs.dtype], _JULIA_NAMES[self.codes.dtype], len(self.idxs))
 
 
 class IVFADCIndex:
@@ -101,8 +101,8 @@ class IVFADCIndex:
             raise NotImplementedError("the HIP path implements SqEuclidean / :pq only (the reference defaults)")
         if nrows % m != 0:
             raise NotImplementedError("d % m != 0: QuantizedArrays.rowrange for ragged sub-spaces is unverifiable")
-        if k > 256:
-            raise NotImplementedError("k > 256 does not fit UInt8 codes")
+        if k > 65536:
+            raise NotImplementedError("k > 65536 does not fit UInt16 codes")
         cent, cbs, labels = trainer.train_ivfadc_hip(data, kc, k, m, coarse_maxiter, quantization_maxiter, seed, device)
         self._init_native(cent, cbs, labels, index_type, device)
         if nvectors:
@@ -127,6 +127,9 @@ class IVFADCIndex:
         nat.check(nat.lib().ivfadc_load_index(C.byref(h), int(device), str(filename).encode(), C.byref(bits)))
         self._h = h
         self.index_type = np.dtype({8: np.uint8, 16: np.uint16, 32: np.uint32}[bits.value])
+        cbits = C.c_int(0)
+        nat.check(nat.lib().ivfadc_code_bits(h, C.byref(cbits)))
+        self.code_type = np.dtype(np.uint16 if cbits.value == 16 else np.uint8)
         self.device = device
         # quantizer arrays for the reference-shaped views (host copies of what the native reader uploaded)
         dims = [C.c_int32(0) for _ in range(4)]
@@ -134,10 +137,14 @@ class IVFADCIndex:
         d, kc, m, ksub = (int(x.value) for x in dims)
         self._centroids = np.zeros((kc, d), np.float32)
         self._codebooks = np.zeros((m, ksub, d // m), np.float32)
-        self._labels = np.zeros((m, ksub), np.uint8)
-        nat.check(nat.lib().ivfadc_get_quantizers(h, self._centroids.ctypes.data_as(C.POINTER(C.c_float)),
-                                                  self._codebooks.ctypes.data_as(C.POINTER(C.c_float)),
-                                                  self._labels.ctypes.data_as(C.POINTER(C.c_uint8))))
+        self._labels = np.zeros((m, ksub), self.code_type)
+        if self.code_type == np.uint16:
+            nat.check(nat.lib().ivfadc_get_quantizers_u16(h, nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
+                                                          self._labels.ctypes.data_as(C.c_void_p)))
+        else:
+            nat.check(nat.lib().ivfadc_get_quantizers(h, self._centroids.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      self._codebooks.ctypes.data_as(C.POINTER(C.c_float)),
+                                                      self._labels.ctypes.data_as(C.POINTER(C.c_uint8))))
         self.kc, self.d = self._centroids.shape
         self.m, self.ksub, self.dsub = self._codebooks.shape
         self._mirror = None
@@ -156,15 +163,23 @@ class IVFADCIndex:
     def _init_native(self, centroids, codebooks, labels, index_type, device):
         self._centroids = np.ascontiguousarray(centroids, np.float32)
         self._codebooks = np.ascontiguousarray(codebooks, np.float32)
-        self._labels = np.ascontiguousarray(labels, np.uint8)
         self.kc, self.d = self._centroids.shape
         self.m, self.ksub, self.dsub = self._codebooks.shape
+        # U (the code type): UInt16 for uint16 labels or more than 256 codewords per sub-quantizer, UInt8 otherwise
+        labels = np.asarray(labels)
+        self.code_type = np.dtype(np.uint16 if (labels.dtype == np.uint16 or self.ksub > 256) else np.uint8)
+        self._labels = np.ascontiguousarray(labels, self.code_type)
         assert self.m * self.dsub == self.d and self._labels.shape == (self.m, self.ksub)
         self.index_type = np.dtype(index_type)
         self._h = C.c_void_p()
-        nat.check(nat.lib().ivfadc_create(C.byref(self._h), int(device), self.d, self.kc, self.m, self.ksub,
-                                          nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
-                                          nat.ptr(self._labels, C.c_uint8)))
+        if self.code_type == np.uint16:
+            nat.check(nat.lib().ivfadc_create_u16(C.byref(self._h), int(device), self.d, self.kc, self.m, self.ksub,
+                                                  nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
+                                                  self._labels.ctypes.data_as(C.c_void_p)))
+        else:
+            nat.check(nat.lib().ivfadc_create(C.byref(self._h), int(device), self.d, self.kc, self.m, self.ksub,
+                                              nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
+                                              nat.ptr(self._labels, C.c_uint8)))
         self._mirror = None
 
     def clone_view(self):
@@ -173,7 +188,7 @@ class IVFADCIndex:
         v = IVFADCIndex.__new__(IVFADCIndex)
         v._h = C.c_void_p()
         nat.check(nat.lib().ivfadc_clone_view(self._h, C.byref(v._h)))
-        for name in ("_centroids", "_codebooks", "_labels", "kc", "d", "m", "ksub", "dsub", "index_type"):
+        for name in ("_centroids", "_codebooks", "_labels", "kc", "d", "m", "ksub", "dsub", "index_type", "code_type"):
             setattr(v, name, getattr(self, name))
         v.device = getattr(self, "device", 0)
         v.requested_coarse_quantizer = getattr(self, "requested_coarse_quantizer", "naive")
@@ -194,10 +209,15 @@ class IVFADCIndex:
     def set_lists(self, offsets, codes, ids):
         offsets = np.ascontiguousarray(offsets, np.int64)
         n = int(offsets[-1])
-        codes = np.ascontiguousarray(codes, np.uint8).reshape(n, self.m)
         ids = np.ascontiguousarray(ids, np.uint32)
-        nat.check(nat.lib().ivfadc_set_lists(self._h, nat.ptr(offsets, C.c_int64), nat.ptr(codes, C.c_uint8),
-                                             nat.ptr(ids, C.c_uint32)))
+        if self.code_type == np.uint16:
+            codes = np.ascontiguousarray(codes, np.uint16).reshape(n, self.m)
+            nat.check(nat.lib().ivfadc_set_lists_u16(self._h, nat.ptr(offsets, C.c_int64), codes.ctypes.data_as(C.c_void_p),
+                                                     nat.ptr(ids, C.c_uint32)))
+        else:
+            codes = np.ascontiguousarray(codes, np.uint8).reshape(n, self.m)
+            nat.check(nat.lib().ivfadc_set_lists(self._h, nat.ptr(offsets, C.c_int64), nat.ptr(codes, C.c_uint8),
+                                                 nat.ptr(ids, C.c_uint32)))
         self._mirror = None
 
     def synth_lists(self, offsets, seed):
@@ -209,18 +229,22 @@ class IVFADCIndex:
         if self._mirror is None:
             n = len(self)
             offsets = np.zeros(self.kc + 1, np.int64)
-            codes = np.zeros((n, self.m), np.uint8)
+            codes = np.zeros((n, self.m), self.code_type)
             ids = np.zeros(n, np.uint32)
-            nat.check(nat.lib().ivfadc_get_lists(self._h, nat.ptr(offsets, C.c_int64), nat.ptr(codes, C.c_uint8),
-                                                 nat.ptr(ids, C.c_uint32)))
+            if self.code_type == np.uint16:
+                nat.check(nat.lib().ivfadc_get_lists_u16(self._h, nat.ptr(offsets, C.c_int64), codes.ctypes.data_as(C.c_void_p),
+                                                         nat.ptr(ids, C.c_uint32)))
+            else:
+                nat.check(nat.lib().ivfadc_get_lists(self._h, nat.ptr(offsets, C.c_int64), nat.ptr(codes, C.c_uint8),
+                                                     nat.ptr(ids, C.c_uint32)))
             self._mirror = (offsets, codes, ids)
         return self._mirror
 
     def _append(self, pts, ids):
         pts = np.ascontiguousarray(pts, np.float32)
         ids = np.ascontiguousarray(ids, np.uint32)
-        nat.check(nat.lib().ivfadc_append(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(ids, C.c_uint32),
-                                          None, None))
+        append = nat.lib().ivfadc_append_u16 if self.code_type == np.uint16 else nat.lib().ivfadc_append
+        nat.check(append(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(ids, C.c_uint32), None, None))
         self._mirror = None
 
     def _delete_ids(self, ids):
@@ -236,15 +260,19 @@ class IVFADCIndex:
         self._mirror = None
 
     def encode(self, pts):
-        """_encode_point for a batch: (list (n,) int32 0-based, codes (n, m) uint8)."""
+        """_encode_point for a batch: (list (n,) int32 0-based, codes (n, m) of the index's code type)."""
         pts = np.ascontiguousarray(pts, np.float32)
         if pts.ndim == 1:
             pts = pts[None, :]
         assert pts.shape[1] == self.d
         lst = np.zeros(pts.shape[0], np.int32)
-        codes = np.zeros((pts.shape[0], self.m), np.uint8)
-        nat.check(nat.lib().ivfadc_encode(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(lst, C.c_int32),
-                                          nat.ptr(codes, C.c_uint8)))
+        codes = np.zeros((pts.shape[0], self.m), self.code_type)
+        if self.code_type == np.uint16:
+            nat.check(nat.lib().ivfadc_encode_u16(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(lst, C.c_int32),
+                                                  codes.ctypes.data_as(C.c_void_p)))
+        else:
+            nat.check(nat.lib().ivfadc_encode(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(lst, C.c_int32),
+                                              nat.ptr(codes, C.c_uint8)))
         return lst, codes
 
     # ---- reference-shaped views ----------------------------------------------------------------
@@ -284,8 +312,9 @@ class IVFADCIndex:
         # centroids, which is what the graph of coarsequantizers.jl:58-92 approximates
         req = getattr(self, "requested_coarse_quantizer", "naive")
         cq = "naive" if req == "naive" else "%s (requested; served by the exact naive search)" % req
-        return ("IVFADCIndex, %s coarse quantizer, %d-byte encoding (%d + 1×%d), %d Float32 vectors"
-                % (cq, self.m + idxsize, idxsize, self.m, len(self)))
+        csize = getattr(self, "code_type", np.dtype(np.uint8)).itemsize
+        return ("IVFADCIndex, %s coarse quantizer, %d-byte encoding (%d + %d×%d), %d Float32 vectors"
+                % (cq, csize * self.m + idxsize, idxsize, csize, self.m, len(self)))
 
     # ---- search --------------------------------------------------------------------------------
     def _io_lock(self):

@@ -17,7 +17,7 @@ from . import _native as nat
 
 def train_ivfadc_hip(data, kc, k, m, coarse_maxiter=25, quantization_maxiter=25, seed=0, device=0):
     """The native trainer (ivfadc_train: k-means++ + Lloyd on the GPU, deterministic per seed).
-    data (n, d) float32 -> centroids (kc, d), codebooks (m, k, dsub), labels (m, k) uint8."""
+    data (n, d) float32 -> centroids (kc, d), codebooks (m, k, dsub), labels (m, k) uint8 (k <= 256) or uint16 (256 < k <= 65536)."""
     x = np.ascontiguousarray(data, np.float32)
     n, d = x.shape
     cent = np.zeros((kc, d), np.float32)
@@ -25,5 +25,5 @@ def train_ivfadc_hip(data, kc, k, m, coarse_maxiter=25, quantization_maxiter=25,
     nat.check(nat.lib().ivfadc_train(int(device), d, n, nat.ptr(x, C.c_float), int(kc), int(k), int(m), int(coarse_maxiter),
                                      int(quantization_maxiter), C.c_uint64(int(seed)), nat.ptr(cent, C.c_float),
                                      nat.ptr(cbs, C.c_float)))
-    labels = np.tile(np.arange(k, dtype=np.uint8), (m, 1))
+    labels = np.tile(np.arange(k, dtype=np.uint8 if k <= 256 else np.uint16), (m, 1))
     return cent, cbs, labels

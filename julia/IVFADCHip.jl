@@ -4,7 +4,7 @@
 # src/IVFADC.jl).  It adds MORE SPECIFIC methods of the reference's own generic functions -- knn_search
 # (src/index.jl:204-273), push! / pushfirst! (src/utils.jl:114-145), pop! / popfirst! (src/utils.jl:29-68),
 # delete_from_index! (src/utils.jl:90-105) -- for the element types the HIP library implements
-# (U = UInt8, T = Float32, SqEuclidean for both distances, NaiveQuantizer); every other index keeps the CPU methods.
+# (U = UInt8 or UInt16, T = Float32, SqEuclidean for both distances, NaiveQuantizer); every other index keeps the CPU methods.
 # Every C symbol is declared in include/ivfadc_hip.h, which cites the reference interface it replaces.
 #
 # The same text is shown in INTEGRATION.md section 3 (tests/test_abi.py checks that the two stay identical and that every
@@ -87,8 +87,11 @@ function _check(rc::Cint)
     rc == 1 ? throw(AssertionError(msg)) : error("ivfadc_hip status $rc: $msg")
 end
 
-const GpuIndex = IVFADCIndex{UInt8,I,Distances.SqEuclidean,Distances.SqEuclidean,Float32,
-                             NaiveQuantizer{Distances.SqEuclidean,Float32}} where {I<:Unsigned}
+# U = UInt8 codes go through the uint8_t entries, U = UInt16 codes (k up to 65536) through the _u16 entries, whose code and label
+# buffers are untyped (Ptr{Cvoid}) in the C ABI and hold UInt16.  (GpuIndex{I} binds the index type I.)
+const GpuIndex = IVFADCIndex{U,I,Distances.SqEuclidean,Distances.SqEuclidean,Float32,
+                             NaiveQuantizer{Distances.SqEuclidean,Float32}} where {I<:Unsigned, U<:Union{UInt8,UInt16}}
+_codetype(::IVFADCIndex{U}) where {U} = U
 
 # IVFADCIndex is an immutable struct (src/index.jl:39): it can carry no finalizer, and a WeakKeyDict would compare its mutable fields by
 # CONTENT.  Its inverse_index field is a Vector -- mutable, identity-stable, and exactly as long-lived as the index that holds it -- so
@@ -157,9 +160,16 @@ function hip_sync!(ivfadc::GpuIndex; device::Int=0)
         cbs = reduce(hcat, [vec(cb.vectors) for cb in rq.codebooks])        # m blocks of dsub×ksub, column-major
         labels = reduce(vcat, [cb.codes for cb in rq.codebooks])            # m×ksub
         out = Ref{Ptr{Cvoid}}(C_NULL)
-        _check(ccall((:ivfadc_create, LIBIVFADC), Cint,
-                     (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}),
-                     out, device, d, kc, m, ksub, cq.vectors, cbs, labels))
+        if _codetype(ivfadc) === UInt16
+            labels16 = Vector{UInt16}(labels)                               # block after block, ksub labels each
+            _check(ccall((:ivfadc_create_u16, LIBIVFADC), Cint,
+                         (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
+                         out, device, d, kc, m, ksub, cq.vectors, cbs, labels16))
+        else
+            _check(ccall((:ivfadc_create, LIBIVFADC), Cint,
+                         (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}),
+                         out, device, d, kc, m, ksub, cq.vectors, cbs, labels))
+        end
         hh = HipHandle(out[])
         finalizer(hh) do x
             x.ptr == C_NULL || ccall((:ivfadc_destroy, LIBIVFADC), Cvoid, (Ptr{Cvoid},), x.ptr)
@@ -171,11 +181,17 @@ function hip_sync!(ivfadc::GpuIndex; device::Int=0)
       end
     end
     offsets = Int64[0; cumsum(length(l.idxs) for l in ivfadc.inverse_index)]
-    codes = isempty(ivfadc.inverse_index) ? UInt8[] :
-            reduce(vcat, (reduce(vcat, l.codes; init=UInt8[]) for l in ivfadc.inverse_index))   # n×m, list order
+    U = _codetype(ivfadc)
+    codes = isempty(ivfadc.inverse_index) ? U[] :
+            reduce(vcat, (reduce(vcat, l.codes; init=U[]) for l in ivfadc.inverse_index))       # n×m, list order
     ids = UInt32.(reduce(vcat, (l.idxs for l in ivfadc.inverse_index)))                           # 0-based (index.jl:189)
-    _check(ccall((:ivfadc_set_lists, LIBIVFADC), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}, Ptr{UInt32}),
-                 h.ptr, offsets, codes, ids))
+    if U === UInt16
+        _check(ccall((:ivfadc_set_lists_u16, LIBIVFADC), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{Cvoid}, Ptr{UInt32}),
+                     h.ptr, offsets, codes, ids))
+    else
+        _check(ccall((:ivfadc_set_lists, LIBIVFADC), Cint, (Ptr{Cvoid}, Ptr{Int64}, Ptr{UInt8}, Ptr{UInt32}),
+                     h.ptr, offsets, codes, ids))
+    end
     return h
 end
 
@@ -254,12 +270,19 @@ function _gpu_push!(ivfadc::GpuIndex{I}, point::Vector{Float32}, position::Symbo
     h = _handle(ivfadc)
     m = length(ivfadc.residual_quantizer.codebooks)
     (vecid, shift) = position == :first ? (0, 1) : (nvectors, 0)            # utils.jl:139
-    lst = Ref{Int32}(0); code = Vector{UInt8}(undef, m); id = UInt32[vecid]
+    U = _codetype(ivfadc)
+    lst = Ref{Int32}(0); code = Vector{U}(undef, m); id = UInt32[vecid]
     _on_device(ivfadc) do
         shift == 0 || _check(ccall((:ivfadc_shift_ids, LIBIVFADC), Cint, (Ptr{Cvoid}, Int32), h.ptr, shift))   # _shift_up_inverse_index!
-        _check(ccall((:ivfadc_append, LIBIVFADC), Cint,
-                     (Ptr{Cvoid}, Int64, Ptr{Float32}, Ptr{UInt32}, Ref{Int32}, Ptr{UInt8}),
-                     h.ptr, 1, point, id, lst, code))
+        if U === UInt16
+            _check(ccall((:ivfadc_append_u16, LIBIVFADC), Cint,
+                         (Ptr{Cvoid}, Int64, Ptr{Float32}, Ptr{UInt32}, Ref{Int32}, Ptr{Cvoid}),
+                         h.ptr, 1, point, id, lst, code))
+        else
+            _check(ccall((:ivfadc_append, LIBIVFADC), Cint,
+                         (Ptr{Cvoid}, Int64, Ptr{Float32}, Ptr{UInt32}, Ref{Int32}, Ptr{UInt8}),
+                         h.ptr, 1, point, id, lst, code))
+        end
     end
     if shift != 0
         for l in ivfadc.inverse_index
