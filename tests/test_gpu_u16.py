@@ -9,6 +9,7 @@ import pytest
 
 import helpers
 import u16_ref
+from u16_ref import assert_exact
 
 pytestmark = pytest.mark.gpu
 GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
@@ -17,16 +18,6 @@ GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 def u16_index(native, ix):
     return native.IVFADCIndex.from_arrays(ix.centroids, ix.codebooks, ix.labels.astype(np.uint16), ix.offsets, ix.codes.astype(np.uint16),
                                           ix.ids)
-
-
-def assert_exact(got, exp, what=""):
-    gi, gd, gc = got
-    ei, ed, ec = exp
-    assert np.array_equal(gc, ec), "%s counts %s vs %s" % (what, gc[:8], ec[:8])
-    for r in range(gc.shape[0]):
-        c = int(gc[r])
-        assert np.array_equal(gi[r, :c], ei[r, :c]), "%s ids differ at query %d: %s vs %s" % (what, r, gi[r, :c], ei[r, :c])
-        assert np.array_equal(gd[r, :c].view(np.uint32), ed[r, :c].view(np.uint32)), "%s dists differ at query %d" % (what, r)
 
 
 def path_of(g):

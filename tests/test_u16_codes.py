@@ -111,6 +111,82 @@ def test_numpy_restatement_equals_oracle_on_8bit_data():
         ol, ocodes = oidx.encode(data[:50])
         ul, ucodes = u16_ref.encode(ix, data[:50])
         assert np.array_equal(ol, ul) and np.array_equal(ocodes.astype(np.uint16), ucodes)
+    # the edges 8-bit data can express: +inf sums, zero codebooks with queries on centroids (every sum equals dc = +0), duplicate
+    # centroids, dsub 5 / 7 / 32, empty lists probed with w = kc, K above the number of probed points
+    for seed, (case, d, m) in enumerate([("inf_sums", 16, 4), ("zero_codebooks", 16, 4), ("dup_centroids", 16, 4), ("dsub5", 20, 4),
+                                          ("dsub7", 28, 4), ("dsub32", 64, 2), ("empty_lists", 16, 4)]):
+        kc = 10
+        oidx, data = helpers.build_index(70 + seed, 400, d, kc, m, ksub=256, label_perm=True, mode="random", ndistinct=30)
+        q = (data[:10] + np.float32(0.01)).astype(np.float32)
+        if case == "inf_sums":
+            u = np.random.default_rng(seed).random(oidx.codebooks.shape, dtype=np.float32)
+            oidx.codebooks[:] = np.where(u < 0.5, np.float32(-1), np.float32(1)) * (np.float32(1) + u) * np.float32(1e20)
+        elif case == "zero_codebooks":
+            oidx.codebooks[:] = 0
+            q[:5] = oidx.centroids[:5]
+        elif case == "dup_centroids":
+            oidx.centroids[5:] = oidx.centroids[:5]
+            q[:5] = oidx.centroids[:5]
+        elif case == "empty_lists":
+            lens = np.diff(oidx.offsets)
+            lens[[0, 3, 7]] = 0
+            sel = np.concatenate([np.arange(oidx.offsets[l], oidx.offsets[l] + lens[l]) for l in range(kc)]).astype(np.int64)
+            oidx.codes, oidx.ids = np.ascontiguousarray(oidx.codes[sel]), np.ascontiguousarray(oidx.ids[sel])
+            oidx.offsets = np.concatenate([[0], np.cumsum(lens)]).astype(np.int64)
+        ix = u16_ref.U16Index(oidx.centroids, oidx.codebooks, oidx.labels.astype(np.uint16), oidx.offsets, oidx.codes.astype(np.uint16),
+                              oidx.ids)
+        if case == "inf_sums":
+            assert np.isinf(u16_ref.knn(ix, q, 5, 2)[1]).all()
+        for K, w in ((1, 1), (10, 3), (64, 2), (500, kc)):
+            oi, od, oc = oidx.knn_search(q, K, w)
+            ui, ud, uc = u16_ref.knn(ix, q, K, w)
+            assert np.array_equal(oc, uc), (case, K, w)
+            for r in range(q.shape[0]):
+                c = int(oc[r])
+                assert np.array_equal(oi[r, :c], ui[r, :c]), (case, K, w, r)
+                assert np.array_equal(od[r, :c].view(np.uint32), ud[r, :c].view(np.uint32)), (case, K, w, r)
+        assert (oc < 500).all()           # K = 500 is more than every list together holds
+
+
+@pytest.mark.parametrize("ksub", [257, 4096, 65536])
+def test_numpy_restatement_against_float64(ksub):
+    """An independent check of u16_ref for ksub > 256, where nothing pins it to the C oracle: every returned distance is recomputed in
+    float64 without tables, dc + sum_i |r_i - cw_i[label^-1(code_i)]|^2, through a label -> codeword map built from a dict (not
+    u16_ref.inv); the returned ids are the float64 top-K of the float64 top-w lists, wherever the float64 gap at the w-th and at the
+    K-th boundary is above the tolerance.  Catches a label-translation or indexing error the GPU code and u16_ref could share."""
+    m, dsub = (2, 4) if ksub == 65536 else (4, 4)
+    d, kc, K, w = m * dsub, 12, 10, 3
+    ix = u16_ref.make_index(ksub + 1, 3000, d, kc, m, ksub, perm_labels=True)
+    assert (ix.labels.astype(np.int64) != np.arange(ksub)).any()
+    inv = [dict(zip(ix.labels[i].tolist(), range(ksub))) for i in range(m)]
+    cb64 = ix.codebooks.astype(np.float64)
+    cent64 = ix.centroids.astype(np.float64)
+    lst_of = np.searchsorted(ix.offsets, np.arange(ix.codes.shape[0]), side="right") - 1
+    cw = np.array([[inv[i][int(c)] for i, c in enumerate(row)] for row in ix.codes], np.int64)
+    tol = 1e-5 * m
+    q = np.random.default_rng(ksub).random((24, d), dtype=np.float32)
+    ids, dists, cnt = u16_ref.knn(ix, q, K, w)
+    checked = 0
+    for r in range(q.shape[0]):
+        q64 = q[r].astype(np.float64)
+        dc = ((cent64 - q64) ** 2).sum(1)
+        full = dc[lst_of] + sum(((cb64[i, cw[:, i]] - (q64 - cent64[lst_of])[:, i * dsub:(i + 1) * dsub]) ** 2).sum(1) for i in range(m))
+        # every returned distance
+        pos = np.array([int(np.nonzero(ix.ids == i)[0][0]) for i in ids[r, :cnt[r]]])
+        assert np.allclose(dists[r, :cnt[r]], full[pos], rtol=tol, atol=0), (ksub, r)
+        # the id set, where float64 separates the boundaries
+        order = np.argsort(dc, kind="stable")
+        if dc[order[w]] - dc[order[w - 1]] <= tol * dc[order[w]]:
+            continue
+        probed = np.isin(lst_of, order[:w])
+        cand = np.nonzero(probed)[0]
+        fo = cand[np.argsort(full[cand], kind="stable")]
+        assert cnt[r] == min(K, cand.shape[0])
+        if fo.shape[0] > K and full[fo[K]] - full[fo[K - 1]] <= tol * full[fo[K]]:
+            continue
+        assert set(ix.ids[fo[:K]].tolist()) == set(ids[r, :cnt[r]].tolist()), (ksub, r)
+        checked += 1
+    assert checked >= 12
 
 
 def test_u16_kernel_resources(native):

@@ -91,12 +91,15 @@ def encode(ix, pts):
     return lst, codes
 
 
-def make_index(seed, n, d, kc, m, ksub, perm_labels=True, empty_every=0, ndistinct=0, scale=0.25):
-    """Random quantizers, random list assignment and codes (labels; `ndistinct` > 0: only that many code rows -> exact ties),
-    ids a permutation.  empty_every > 0: every such list is left empty."""
+def make_index(seed, n, d, kc, m, ksub, perm_labels=True, empty_every=0, ndistinct=0, scale=0.25, centroids=None, list_sizes=None):
+    """Random quantizers, random list assignment and codes (labels; `ndistinct` > 0: only that many code rows -> exact ties; 1: every
+    point has the same code row), ids a permutation.  empty_every > 0: every such list is left empty.  `centroids` (kc, d): used
+    instead of random ones; `list_sizes` (kc,): exact list lengths instead of a random assignment (n is then their sum)."""
     rng = np.random.default_rng(seed)
     dsub = d // m
     cent = rng.random((kc, d), dtype=f32)
+    if centroids is not None:
+        cent = np.ascontiguousarray(centroids, f32).reshape(kc, d)
     cbs = ((rng.random((m, ksub, dsub), dtype=f32) - 0.5) * 2 * scale).astype(f32)
     if perm_labels:
         labels = np.stack([rng.permutation(65536)[:ksub] for _ in range(m)]).astype(np.uint16)
@@ -104,6 +107,9 @@ def make_index(seed, n, d, kc, m, ksub, perm_labels=True, empty_every=0, ndistin
         labels = np.tile(np.arange(ksub, dtype=np.uint16), (m, 1))
     lists = np.arange(kc) if not empty_every else np.array([l for l in range(kc) if l % empty_every])
     lst = lists[rng.integers(0, len(lists), n)]
+    if list_sizes is not None:
+        lst = rng.permutation(np.repeat(np.arange(kc), np.asarray(list_sizes, np.int64)))
+        n = lst.shape[0]
     if ndistinct:
         pool = np.stack([labels[i][rng.integers(0, ksub, ndistinct)] for i in range(m)], 1)
         codes = pool[rng.integers(0, ndistinct, n)]
@@ -114,3 +120,14 @@ def make_index(seed, n, d, kc, m, ksub, perm_labels=True, empty_every=0, ndistin
     np.cumsum(np.bincount(lst, minlength=kc), out=offsets[1:])
     ids = rng.permutation(n).astype(np.uint32)
     return U16Index(cent, cbs, labels, offsets, codes[order].astype(np.uint16), ids)
+
+
+def assert_exact(got, exp, what=""):
+    """(ids, dists, counts) of a search entry against the reference (or another entry): counts, ids and distance bits identical."""
+    gi, gd, gc = got
+    ei, ed, ec = exp
+    assert np.array_equal(gc, ec), "%s counts %s vs %s" % (what, gc[:8], ec[:8])
+    for r in range(gc.shape[0]):
+        c = int(gc[r])
+        assert np.array_equal(gi[r, :c], ei[r, :c]), "%s ids differ at query %d: %s vs %s" % (what, r, gi[r, :c], ei[r, :c])
+        assert np.array_equal(gd[r, :c].view(np.uint32), ed[r, :c].view(np.uint32)), "%s dists differ at query %d" % (what, r)
