@@ -266,23 +266,9 @@ static inline int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; 
 }  // namespace
 
 // ---- environment -------------------------------------------------------------------------------------------------------------------
-// The library reads EIGHT environment variables (include/ivfadc_hip.h lists them): switches a deployment may need without a rebuild --
-// validation (exact kernels only), safety valves (no zero-copy host access, no stream probing, one batch in flight), the abort trace.
-// Every other IVFADC_* name in this file is an A/B switch of a measured-and-closed experiment: it is looked up only in the diagnostic
-// build (-DIVFADC_DEBUG, libivfadc_hip_dbg.so); the production library answers "not set" without touching the environment.
-static const char *env_knob(const char *name)
-{
-    static const char *const product[] = {"IVFADC_NO_PRUNE", "IVFADC_NO_PIPELINE", "IVFADC_EXACT_TABLES", "IVFADC_NO_ZERO_COPY",
-                                          "IVFADC_NO_STREAM_PROBE", "IVFADC_COARSE_EXACT", "IVFADC_NO_SMALLQ"};
-#ifndef IVFADC_DEBUG
-    bool ok = false;
-    for (const char *k : product) ok = ok || strcmp(k, name) == 0;
-    if (!ok) return nullptr;
-#else
-    (void)product;
-#endif
-    return getenv(name);
-}
+// The library reads EIGHT environment variables (include/ivfadc_hip.h lists them), with getenv where they are used: switches a deployment
+// may need without a rebuild -- validation (exact kernels only), safety valves (no zero-copy host access, no stream probing, one batch in
+// flight), the abort trace.
 
 // ---- thread safety ------------------------------------------------------------------------------------------------------------------
 // Every entry point locks its handle (a recursive mutex: entry points call each other), so calls on ONE handle from several threads
@@ -325,7 +311,7 @@ struct ivfadc_index {
     // label order, and max ||codeword|| per sub-quantizer; present for the shapes lb_shape() names
     DevBuf lb_split, lb_n2, lb_lab, lb_maxn;
     DevBuf lb_f16, lb_isc;       // round 5: f16 codewords x 2^e_ii and 2^-e_ii for the one-product build (lb_build_tables_f16)
-    bool lb_use_f16 = true;      // IVFADC_LB_BF16=1 / ivfadc_set_table_mode(h, 3): the three-product bf16 split instead (A/B)
+    bool lb_use_f16 = true;      // ivfadc_set_table_mode(h, 3): the three-product bf16 split instead (A/B)
     // narrow-field list-major scan (nfscan.hip.h; m = 8, dsub = 16, ksub = 256): ||codeword||^2 by codeword index, f32 codewords by label
     DevBuf nf_n2, nf_lab;
     bool allow_nf = true;
@@ -438,7 +424,7 @@ struct ivfadc_index {
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
-    bool hc_out_direct = false, hc_legacy = false;   // the running host-pointer call: results go straight into the caller's arrays / old copy chain
+    bool hc_out_direct = false;   // the running host-pointer call: results go straight into the caller's arrays
     hipStream_t copy_stream = nullptr;               // ivfadc_search_batches: query ingest ahead of the searches
     hipStream_t copy_probed_a = nullptr, copy_probed_b = nullptr;   // ... probed to run beside these two (ensure_overlap)
     std::vector<hipEvent_t> ingest_ev;               // ... one event per upload group
@@ -457,7 +443,7 @@ struct ivfadc_index {
     std::vector<EvPair> free_ev;
     ivfadc_stats stats{};
     int64_t scanned_base = 0, fallback_base = 0, pruned_base = 0, surv_base = 0;
-    int force_qg = 0, force_chunk = 0, force_pg = 0;
+    int force_qg = 0, force_chunk = 0;
     bool own_stream = true;
     struct FnCfg { const void *fn; size_t lds; int occ; };
     std::vector<FnCfg> fn_cfg;
@@ -471,7 +457,7 @@ struct ivfadc_index {
     uint64_t generation = 0, view_gen = 0;
     std::vector<ivfadc_index *> views;
     ivfadc_index *pipe_view = nullptr;            // ivfadc_search_batches' second lane (created on first use)
-    hipEvent_t pipe_ev_in = nullptr, pipe_ev_out = nullptr;
+    hipEvent_t pipe_ev_in = nullptr;
 };
 
 // the lock of an entry point on handle h (null: nothing to lock).  A view takes the topology mutex first and lets it go once its own
@@ -762,12 +748,7 @@ size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool l
 
 constexpr size_t LDS_MAX = 160 << 10;
 // the eight-wave list-major kernel (wg8scan.hip.h) as the plan's own choice on long lists (ivfadc_set_table_mode(h, 6) asks for it anywhere)
-#ifndef W9_MIN_PPL
-#define W9_MIN_PPL 8.0      // probes per list from which the eight-query form of the eight-wave kernel is planned
-#endif
-#ifndef W8_DEFAULT_ON
-#define W8_DEFAULT_ON 1
-#endif
+constexpr double W9_MIN_PPL = 8.0;   // probes per list from which the eight-query form of the eight-wave kernel is planned
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
 constexpr size_t MISC_BYTES = 4096 + 256 + 512;
@@ -820,8 +801,7 @@ int fb_poll(ivfadc_index *h)
 }
 int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its stream
 {
-    static const bool off = env_knob("IVFADC_NO_PG_FEEDBACK") != nullptr;
-    if (off || h->fb_pending || !h->misc.p) return IVFADC_OK;
+    if (h->fb_pending || !h->misc.p) return IVFADC_OK;
     if (--h->fb_countdown > 0) return IVFADC_OK;
     h->fb_countdown = 8;
     TRY(h->fb_pin.ensure(4096));
@@ -921,45 +901,36 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
                   (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);   // (its four waves keep their queries in LDS)
     if (pl.twolevel) pl.coarse_mfma = false;
     if (pl.query_major) {
-        static const bool no_fuse = env_knob("IVFADC_NO_FUSE_TOPW") != nullptr;
         // large kc: the selection is a 4*kc-byte stream per query, better done by the lean stand-alone kernel
-        pl.fuse_topw = pl.small_w && !no_fuse && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel;
+        pl.fuse_topw = pl.small_w && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel;
         // Several batches in flight on this replica (the index has views, or this IS a view: ivfadc_search_batches' second lane, a serving
         // loop's lanes): what bounds the chip then is register-file time, not one launch's latency -- and the fused selection holds a scan
-        // workgroup's four waves and 126 VGPRs each for the 10 k cycles (28 % of its life on the SIFT1M shape, IVFADC_DEBUG_STAMPS) in which
+        // workgroup's four waves and 126 VGPRs each for the 10 k cycles (28 % of its life on the SIFT1M shape, by phase stamps) in which
         // wave 0 selects and the others wait.  A stand-alone selection, one lean wave per query, costs a launch and gives the scan its
         // registers back: 42.5 -> 44.7 M q/s with two batches in flight (profiles/r05_topw_probe.txt); one batch at a time keeps the fused form.
-        static const bool lanes_fused = env_knob("IVFADC_LANES_FUSE_TOPW") != nullptr;
         // (device-pointer entries only, and only while the lanes really run side by side -- h->dev_entry, set by the entry from the root
         // index's tickets: the host entries are bound by the host's enqueue time, where one more launch per batch costs
         // ivfadc_search_batches 27.8 -> 25.8 M q/s, and a caller who owns views but searches one batch at a time would pay a launch for nothing)
         pl.lanes = h->dev_entry && (h->is_view || h->n_views.load() > 0) && nq >= 4 * (int64_t)h->num_cu && h->kc >= 512;
-        if (pl.lanes && !lanes_fused) pl.fuse_topw = false;
+        if (pl.lanes) pl.fuse_topw = false;
         // probes per round: share each codeword fetch between PG tables, keep >= 4 workgroups per CU when possible
         int pg = w >= 2 ? 2 : 1;   // measured: PG=2 beats PG=4 (register pressure halves the occupancy at 4)
         if (pl.small_k && h->allow_prune && h->prune_est >= PG1_MIN_PRUNED) pg = 1;   // (fb_poll: most of what is probed gets pruned)
-        if (h->force_pg == 1 || h->force_pg == 2 || h->force_pg == 4) pg = h->force_pg;
-        static const int big_cap_kb = env_knob("IVFADC_PG_LDS_CAP_KB") ? atoi(env_knob("IVFADC_PG_LDS_CAP_KB")) : 40;
-        const size_t pg_lds_cap = (h->force_pg == 4) ? LDS_MAX : (pl.small_k ? (size_t)(40 << 10) : (size_t)big_cap_kb << 10);   // forcing 4 lifts the 4-workgroups-per-CU cap
-        while (pg > 1 && scan_lds_bytes(h, pg, pl.cap, pl.small_k) > pg_lds_cap) pg >>= 1;
+        while (pg > 1 && scan_lds_bytes(h, pg, pl.cap, pl.small_k) > (size_t)(40 << 10)) pg >>= 1;
         pl.qg = pg;
         pl.lds = scan_lds_bytes(h, pg, pl.cap, pl.small_k);
         // lower-bound tables on the matrix cores: four probes per round share one pass over the codebook (a quarter of the exact
         // build's L1 traffic, a fraction of its vector-ALU work); register selectors and the LDS probe copy only
-        static const bool no_lb = env_knob("IVFADC_NO_LB") != nullptr;
-        static const bool lb_everywhere = env_knob("IVFADC_LB_EVERYWHERE") != nullptr;   // = ivfadc_set_table_mode(h, 2), for A/B runs of bench.py
         // (measured: m = 48, where the exact build re-reads 768 KB of codewords per probe, +20 % on the HD shape; m = 16 with 1.5 k-point
         // lists -- the Deep1B shape -- loses 12 %: four barriers and the round's setup per four 24 KB lists cost what the cheaper tables
         // save, so there the rounds run only on request, ivfadc_set_table_mode(h, 2))
-        pl.lb = !no_lb && h->allow_lb && h->allow_filt && h->lb_split.p != nullptr && lb_shape(h->m, h->dsub) && pl.small_k && w <= 32 &&
-                h->ksub == 256 && (h->m >= 32 || h->force_lb || lb_everywhere);
+        pl.lb = h->allow_lb && h->allow_filt && h->lb_split.p != nullptr && lb_shape(h->m, h->dsub) && pl.small_k && w <= 32 &&
+                h->ksub == 256 && (h->m >= 32 || h->force_lb);
         if (pl.lb) {
             // the top-w selection of a large batch runs as its own launch, one wave per query at full occupancy (per-tile records,
             // no score matrix); inside this kernel -- two workgroups per CU, three waves idle -- it was a sixth of the launch
-            static const bool lb_fuse = env_knob("IVFADC_LB_FUSE_TOPW") != nullptr;
-            if ((nq >= 4 * (int64_t)h->num_cu && !lb_fuse) || pl.twolevel) pl.fuse_topw = false;
+            if (nq >= 4 * (int64_t)h->num_cu || pl.twolevel) pl.fuse_topw = false;
             pl.qg = w >= 3 ? 4 : w;
-            if (h->force_pg >= 1 && h->force_pg <= 4) pl.qg = std::min(w, h->force_pg);
             pl.lds = lb_lds_bytes(h->m, h->dsub, pl.qg);
         }
         if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }   // e.g. m = 48 with K near 2048: tables + selector buffers
@@ -976,19 +947,17 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
         // 0.316 / 0.544 / 0.92-0.93 (round 6)
         const bool w8_shape = pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && h->dsub == 16 && h->ksub == 256 && h->d == 128 &&
-                              h->maxlen < ((int64_t)1 << 28) && h->part_n <= 1 && W8_DEFAULT_ON && avg_len >= 8192.0;
+                              h->maxlen < ((int64_t)1 << 28) && h->part_n <= 1 && avg_len >= 8192.0;
         if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
         if (forced) qg = h->force_qg;
         // eight queries per code stream behind the 4-bit narrow-field filter (nfscan.hip.h): conflict-free gathers, a third of the vector
         // instructions per (query, point), every list streamed once per eight queries -- where the shape has the kernel, K fits the
         // register selectors and the lists are probed often enough to fill the groups
         // (measured, SIFT1B shape, 16 384 x w = 8: 7.76 ms against 7.44 ms for the 16-bit four-query kernel -- DESIGN.md 4.11 -- so the kernel
-        // runs on request only: ivfadc_set_tuning(h, 8, 0), or IVFADC_NF=1 for A/B runs of bench.py)
-        static const bool nf_auto = env_knob("IVFADC_NF") != nullptr;
+        // runs on request only: ivfadc_set_tuning(h, 8, 0))
         const bool nf_ok = h->allow_nf && h->allow_filt && h->nf_n2.p != nullptr && nf_shape(h->m, h->dsub) && h->ksub == 256 && pl.small_k;
-        static const double nf_min_ppl = env_knob("IVFADC_NF_MIN_PPL") ? atof(env_knob("IVFADC_NF_MIN_PPL")) : 3.0;
         if (h->force_qg == 8 && !nf_ok) qg = 4;
-        pl.nf = nf_ok && (h->force_qg == 8 || (nf_auto && !forced && ppl >= nf_min_ppl && avg_len >= 2048.0));
+        pl.nf = nf_ok && h->force_qg == 8;
         if (pl.nf) {
             qg = 8;
             pl.qg = 8;
@@ -1007,7 +976,7 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // list-partitioned mode keeps the four-wave kernel it was validated with)
         pl.wg8 = qg == 4 && pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && h->dsub == 16 && h->ksub == 256 && h->d == 128 &&
                  h->maxlen < ((int64_t)1 << 28) && h->part_n <= 1 &&
-                 (h->wg8_mode > 0 || (W8_DEFAULT_ON && avg_len >= 8192.0));   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
+                 (h->wg8_mode > 0 || avg_len >= 8192.0);   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
         if (pl.wg8) pl.lds = (size_t)W8Lds::END;
         // ... and EIGHT queries per code stream (wg8q8scan.hip.h: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
         // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
@@ -1110,7 +1079,7 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
                 h->tlist_ldq = (int)nb;
             }
             const float neg2 = -2.0f / (h->f16_scale * h->f16_scale);
-            hipLaunchKernelGGL((coarse_bf16_kernel<128, 0, true>), grid, dim3(256), 0, h->stream, h->q_f16.as<unsigned short>(),
+            hipLaunchKernelGGL((coarse_bf16_kernel<128, true>), grid, dim3(256), 0, h->stream, h->q_f16.as<unsigned short>(),
                                (const unsigned short *)nullptr, h->cent_f16.as<unsigned short>(), (const unsigned short *)nullptr,
                                h->cnorm.as<float>(), listed ? (float *)nullptr : h->cdist.as<float>(), (int)nb, h->kc, dp, tmin, ntiles, tl,
                                (int)nb, neg2);
@@ -1129,23 +1098,6 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
                 h->last_listed = true;
                 h->tlist_ldq = (int)nb;
             }
-#ifdef IVFADC_DEBUG
-            // (read per launch: tools/coarse_probe.py runs a correct search first, then sets the variable)
-            const int cdbg = env_knob("IVFADC_COARSE_DBG") ? atoi(env_knob("IVFADC_COARSE_DBG")) : 0;
-#define IVFADC_COARSE_LAUNCH(D) hipLaunchKernelGGL((coarse_bf16_kernel<128, D>), grid, dim3(256), 0, h->stream, h->q_hi.as<unsigned short>(), \
-                               h->q_lo.as<unsigned short>(), h->cent_hi.as<unsigned short>(), h->cent_lo.as<unsigned short>(), \
-                               h->cnorm.as<float>(), listed ? (float *)nullptr : h->cdist.as<float>(), (int)nb, h->kc, dp, tmin, ntiles, tl, \
-                               (int)nb, -2.0f);
-            if (listed && cdbg == 1) { IVFADC_COARSE_LAUNCH(1) }
-            else if (listed && cdbg == 2) { IVFADC_COARSE_LAUNCH(2) }
-            else if (listed && cdbg == 3) { IVFADC_COARSE_LAUNCH(3) }
-            else if (listed && cdbg == 5) { IVFADC_COARSE_LAUNCH(5) }
-            else if (listed && cdbg == 6) { IVFADC_COARSE_LAUNCH(6) }
-            else if (listed && cdbg == 7) { IVFADC_COARSE_LAUNCH(7) }
-            else if (listed && cdbg == 8) { IVFADC_COARSE_LAUNCH(8) }
-            else
-#undef IVFADC_COARSE_LAUNCH
-#endif
             hipLaunchKernelGGL(coarse_bf16_kernel<128>, grid, dim3(256), 0, h->stream, h->q_hi.as<unsigned short>(),
                                h->q_lo.as<unsigned short>(), h->cent_hi.as<unsigned short>(), h->cent_lo.as<unsigned short>(),
                                h->cnorm.as<float>(), listed ? (float *)nullptr : h->cdist.as<float>(), (int)nb, h->kc, dp, tmin, ntiles, tl,
@@ -1163,13 +1115,10 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
         // small batches: narrower query tiles multiply the workgroup count until every SIMD has its four waves
         const int64_t wg64 = (int64_t)((h->kc + CO_T - 1) / CO_T) * ((nb + 63) / 64);
         int tq = wg64 >= 4 * (int64_t)h->num_cu ? 64 : (2 * wg64 >= 4 * (int64_t)h->num_cu ? 32 : 16);
-        static const int force_tq = env_knob("IVFADC_COARSE_TQ") ? atoi(env_knob("IVFADC_COARSE_TQ")) : 0;
-        if (force_tq == 16 || force_tq == 32 || force_tq == 64) tq = force_tq;
         dim3 grid((h->kc + CO_T - 1) / CO_T, (unsigned)((nb + tq - 1) / tq));
         // small problems (every workgroup resident at once): centroid per lane, queries in SGPRs -- no LDS traffic to
         // speak of, the wave's instruction stream is the VALU minimum (SIFT1M-shape, 1024 queries: 14.9 -> see DESIGN 4.1)
-        static const int sgpr_mode = env_knob("IVFADC_COARSE_SGPR") ? atoi(env_knob("IVFADC_COARSE_SGPR")) : -1;
-        const bool sgpr = (h->d & 7) == 0 && (nb + 15) / 16 <= 65535 && (sgpr_mode < 0 ? tq < 64 : sgpr_mode > 0);
+        const bool sgpr = (h->d & 7) == 0 && (nb + 15) / 16 <= 65535 && tq < 64;
         if (sgpr)
             hipLaunchKernelGGL(coarse_sgpr_kernel<4>, dim3((h->kc + 63) / 64, (unsigned)((nb + 15) / 16)), dim3(256), 0, h->stream, d_q,
                                h->centroids.as<float>(), h->cdist.as<float>(), (int)nb, h->kc, h->d);
@@ -1226,8 +1175,7 @@ IndexView index_view(const ivfadc_index *h)
     ix.centroids = h->centroids.as<float>();
     ix.codebooks = h->codebooks.as<float>();
     ix.codebooks_t = h->codebooks_t.as<float>();
-    static const bool no_pk = env_knob("IVFADC_NO_PK_BUILD") != nullptr;
-    ix.codebooks_p = (h->codebooks_p.p && !no_pk) ? h->codebooks_p.as<float>() : (const float *)nullptr;
+    ix.codebooks_p = h->codebooks_p.as<float>();
     ix.labels = h->labels.as<uint8_t>();
     ix.codes = h->codes.as<uint8_t>();
     ix.list_pos = h->list_pos.as<int64_t>();
@@ -1236,12 +1184,6 @@ IndexView index_view(const ivfadc_index *h)
     ix.ids = h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>();
     ix.d = h->d; ix.kc = h->kc; ix.m = h->m; ix.ksub = h->ksub; ix.dsub = h->dsub; ix.cs = h->cs;
     ix.identity_labels = h->identity_labels ? 1 : 0;
-#ifdef IVFADC_DEBUG
-    static const int dbg_flags = env_knob("IVFADC_DEBUG_FLAGS") ? atoi(env_knob("IVFADC_DEBUG_FLAGS")) : 0;
-    ix.dbg_flags = dbg_flags;
-#else
-    ix.dbg_flags = 0;
-#endif
     return ix;
 }
 
@@ -1345,9 +1287,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
     const bool direct = !pl.query_major && pl.qg == 1 && np * (size_t)pl.maxch < ((size_t)1 << 31) && h->part_n <= 1;
 
     // one wave per query leaves the chip empty on small batches: the stand-alone top-w uses a workgroup per query there
-    static const bool wpq1_env = env_knob("IVFADC_TOPW_WPQ1") != nullptr;   // A/B: a wave per query also on small batches (throughput runs with several batches in flight)
-    const bool wpq4 = !wpq1_env && !pl.lanes && nb * 1 < (int64_t)8 * h->num_cu * 4 && h->kc >= 512 && !(pl.lb && !pl.fuse_topw);
-    static const bool no_tmin = env_knob("IVFADC_NO_TILE_MIN") != nullptr;
+    const bool wpq4 = !pl.lanes && nb * 1 < (int64_t)8 * h->num_cu * 4 && h->kc >= 512 && !(pl.lb && !pl.fuse_topw);
     // the rows of these very queries may stand already: written by the previous search's launch behind a hint (ivfadc_set_next_queries)
     const bool have_rows = single && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
     h->avail_q = nullptr;
@@ -1364,7 +1304,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         h->tmin_tiles = 0;
         h->last_listed = false;
     } else {
-        TRY(run_coarse(h, d_q, nb, pl.coarse_mfma, pl.coarse_mfma && !no_tmin && (pl.fuse_topw ? h->m > 16 : !wpq4),   // who reads them
+        TRY(run_coarse(h, d_q, nb, pl.coarse_mfma, pl.coarse_mfma && (pl.fuse_topw ? h->m > 16 : !wpq4),   // who reads them
                        !pl.fuse_topw && !wpq4, w));
     }
     // riders: the hinted batch will take the exact small-problem coarse kernel whatever its K and w (no matrix-core filter at this kc)
@@ -1412,7 +1352,6 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         a.approx = pl.coarse_mfma ? 1 : 0;
         a.rf = refine_args(h, d_q);
         a.prune = h->allow_prune ? 1 : 0;
-        a.dbg = nullptr;
         a.lb.cb_split = h->lb_split.as<uint4>();
         a.lb.cb_n2 = h->lb_n2.as<float>();
         a.lb.cb_lab = h->lb_lab.as<float>();
@@ -1421,15 +1360,6 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         a.lb.cb_isc = h->lb_isc.as<float>();
         a.lb.mu = a.lb.cb_f16 ? 1.48e-3f : 9.2e-5f;
         h->stats.last_lb = pl.lb ? 1 : 0;
-#ifdef IVFADC_DEBUG
-        static const bool dbg_on = env_knob("IVFADC_DEBUG_STAMPS") != nullptr;
-#else
-        constexpr bool dbg_on = false;
-#endif
-        if (dbg_on) {
-            TRY(h->dbg.ensure((size_t)nb * 128));
-            a.dbg = h->dbg.as<u64>();
-        }
         qscan_fn_t fn = pl.lb ? pick_qscan_lb(h->m, h->dsub, pl.qg) : pick_qscan(h->m, h->dsub, pl.qg, pl.small_k);
         int occ = 0;
         TRY(fn_occupancy(h, (const void *)fn, pl.lds, occ));
@@ -1476,37 +1406,6 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
                                h->dbg.as<u32>());
             HIP_TRY(hipGetLastError());
             TRY(ev_end(h, eb));
-        }
-        if (dbg_on) {
-            std::vector<u64> st((size_t)nb * 16);
-            HIP_TRY(hipMemcpyAsync(st.data(), h->dbg.p, st.size() * 8, hipMemcpyDeviceToHost, h->stream));
-            HIP_TRY(hipStreamSynchronize(h->stream));
-            double acc[16] = {0};
-            for (int64_t i = 0; i < nb; ++i)
-                for (int k = 0; k < 16; ++k) acc[k] += (double)st[i * 16 + k];
-            fprintf(stderr, "[ivfadc stamps] prologue (wave 0): to first barrier=%.0f row select+store=%.0f barrier=%.0f merge=%.0f lens+prefix=%.0f "
-                            "barrier=%.0f\n", acc[8] / nb, acc[9] / nb, acc[10] / nb, acc[11] / nb, acc[12] / nb, acc[13] / nb);
-            fprintf(stderr, "[ivfadc stamps] per-WG mean cycles: wait_prev=%.0f resid=%.0f table=%.0f scan=%.0f | prologue+loop=%.0f "
-                            "tail=%.0f | top-w row select (wave 0)=%.0f\n", acc[0] / nb, acc[1] / nb, acc[2] / nb, acc[3] / nb, acc[4] / nb,
-                    acc[5] / nb, acc[6] / nb);
-            if (pl.lb)
-                fprintf(stderr, "[ivfadc stamps] lower-bound rounds (wave 0): resid = setup (norms, scales, bf16 residuals), table = MFMA build, "
-                                "scan = integer scan + drains; final drains=%.0f rounds=%.2f\n", acc[14] / nb, acc[15] / nb);
-            // balance: every workgroup is resident from the start, so the launch lasts as long as its slowest one
-            std::vector<double> dur((size_t)nb);
-            u64 t_first = ~0ull, t_last = 0;
-            for (int64_t i = 0; i < nb; ++i) {
-                const u64 du = st[i * 16 + 4] + st[i * 16 + 5];
-                dur[i] = (double)du;
-                t_first = std::min(t_first, st[i * 16 + 7] - du);
-                t_last = std::max(t_last, st[i * 16 + 7]);
-            }
-            std::sort(dur.begin(), dur.end());
-            double mean = 0;
-            for (double v : dur) mean += v;
-            mean /= (double)nb;
-            fprintf(stderr, "[ivfadc stamps] workgroup duration cycles: mean=%.0f p50=%.0f p90=%.0f p99=%.0f max=%.0f | first start -> last end=%.0f\n",
-                    mean, dur[nb / 2], dur[(size_t)(nb * 0.9)], dur[(size_t)(nb * 0.99)], dur[nb - 1], (double)(t_last - t_first));
         }
     } else {
         TRY(h->bucket_items.ensure(np * 4));
@@ -1577,40 +1476,17 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         } else if (pl.wg8 && !direct) {
             void (*wk)(const ScanArgs, float *, const u32 *, u32 *, int) = pl.wg8q8 ? wg8q8_scan_kernel : wg8_scan_kernel;
             u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
-            static const bool one_queue = env_knob("IVFADC_W8_NO_XCD") != nullptr;   // A/B (debug build): one queue for all workgroups
-#ifdef W8_ONE_QUEUE
-            const int nranges = 1;
-#else
-            const int nranges = one_queue ? 1 : 8;
-#endif
             HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
             int occ = 0;
             TRY(fn_occupancy(h, (const void *)wk, pl.lds, occ, true, W8_THREADS));
             const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * W9_GTAB_FLOATS * 4 + 256));   // (occupancy is clamped to 8 workgroups per CU; 256 B: W8_PROF's counters)
-#ifdef W8_PROF
-            HIP_TRY(hipMemsetAsync((char *)h->wg8_tabs.p + (size_t)grid * (pl.wg8q8 ? W9_GTAB_FLOATS : W8_GTAB_FLOATS) * 4, 0, 128, h->stream));
-#endif
+            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * W9_GTAB_FLOATS * 4));   // (occupancy is clamped to 8 workgroups per CU)
             if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(wk, dim3(grid), dim3(W8_THREADS), pl.lds, h->stream, a, h->wg8_tabs.as<float>(), h->wg8_items.as<u32>(), xq, nranges);
+            hipLaunchKernelGGL(wk, dim3(grid), dim3(W8_THREADS), pl.lds, h->stream, a, h->wg8_tabs.as<float>(), h->wg8_items.as<u32>(), xq, 8);
             HIP_TRY(hipGetLastError());
             if (h->profiling) TRY(ev_end(h, ep));
             h->stats.last_scan_grid = (int)grid;
             h->stats.last_striped = pl.wg8q8 ? 3 : 2;
-#ifdef W8_PROF
-            {
-                u64 pc[16];
-                HIP_TRY(hipMemcpyAsync(pc, (char *)h->wg8_tabs.p + (size_t)grid * (pl.wg8q8 ? W9_GTAB_FLOATS : W8_GTAB_FLOATS) * 4, 128, hipMemcpyDeviceToHost, h->stream));
-                HIP_TRY(hipStreamSynchronize(h->stream));
-                static int shown = 0;
-                if (shown++ % 8 == 4) {
-                    const double wv_ = (double)grid * (double)W8_NW;
-                    fprintf(stderr, "[w8prof] per wave: loop %.0f setup %.0f build %.0f scan %.0f (cand %.0f, drains %.0f of it waiting %.0f) merge %.0f cycles | steps %.0f cand-steps %.0f drains %.0f "
-                                    "drained %.0f crowds %.0f build: residuals %.0f entries %.0f items %.1f\n", pc[0] / wv_, pc[1] / wv_, pc[2] / wv_, pc[3] / wv_, pc[4] / wv_, pc[5] / wv_, pc[7] / wv_, pc[6] / wv_,
-                            pc[8] / wv_, pc[9] / wv_, pc[10] / wv_, pc[11] / wv_, pc[12] / wv_, pc[13] / wv_, (pc[15] - pc[13]) / wv_, pc[14] / wv_);
-                }
-            }
-#endif
         } else if (pl.nf) {
             // four points per lane and step (measured: two 9.2 ms, eight 8.1 ms -- and 74 spilled registers -- against 7.76 ms)
             void (*nk)(const ScanArgs, const NfView) = nf_scan_kernel<4>;
@@ -1619,8 +1495,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
             nv.cb_lab = h->nf_lab.as<float>();
             nv.maxn2 = h->nf_n2.as<float>() + (size_t)h->m * 256;
             nv.xq = (u32 *)((char *)h->misc.p + 4096 + 256);
-            static const bool no_xcd = env_knob("IVFADC_NF_NO_XCD") != nullptr;   // A/B: one queue for all workgroups
-            nv.nranges = no_xcd ? 1 : 8;
+            nv.nranges = 8;
             HIP_TRY(hipMemsetAsync(nv.xq, 0, 512, h->stream));
             int occ = 0;
             TRY(fn_occupancy(h, (const void *)nk, pl.lds, occ));
@@ -1633,13 +1508,10 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         } else {
         scan_fn_t fn = pick_scan(h->m, h->dsub, pl.qg, pl.small_k, stripe);
         int occ = 0;
-        // IVFADC_LDS_PAD (bytes, diagnostic): unused LDS behind the kernel's own, to see what a workgroup per CU fewer costs
-        static const size_t lds_pad = env_knob("IVFADC_LDS_PAD") ? (size_t)atol(env_knob("IVFADC_LDS_PAD")) : 0;
-        const size_t lds_launch = std::min<size_t>(LDS_MAX, pl.lds + lds_pad);
-        TRY(fn_occupancy(h, (const void *)fn, lds_launch, occ));
+        TRY(fn_occupancy(h, (const void *)fn, pl.lds, occ));
         const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
         if (h->profiling) TRY(ev_begin(h, 0, ep));
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds_launch, h->stream, a);
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), pl.lds, h->stream, a);
         HIP_TRY(hipGetLastError());
         if (h->profiling) TRY(ev_end(h, ep));
         h->stats.last_scan_grid = (int)grid;
@@ -1832,13 +1704,12 @@ int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, 
 // coarse kernel one launch earlier: the default is the separate kernel; ivfadc_set_coarse_mode(h, 5) takes the single-launch form.
 int sq_inside_kc(const ivfadc_index *h)
 {
-    static const bool env_on = env_knob("IVFADC_SQ_INSIDE") != nullptr;   // A/B runs
-    return ((h->sq_inside || env_on) && h->cent_t.p) ? SQ_COARSE_INSIDE : 0;
+    return (h->sq_inside && h->cent_t.p) ? SQ_COARSE_INSIDE : 0;
 }
 
 bool sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
 {
-    static const bool off = env_knob("IVFADC_NO_SMALLQ") != nullptr;
+    static const bool off = getenv("IVFADC_NO_SMALLQ") != nullptr;
     if (off || !h->allow_sq || h->force_qg != 0 || h->u16) return false;
     if (K > 64 || w > 64 || nq > 64 || nq * w > 512) return false;
     if ((h->d & 3) != 0) return false;
@@ -1851,8 +1722,7 @@ int search_small(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, ui
     TRY(ensure_common_ws(h));
     const bool inside = h->kc <= sq_inside_kc(h);
     if (!inside) {
-        static const bool no_lane = env_knob("IVFADC_SQ_TILE_COARSE") != nullptr;   // A/B: the tiled small-problem kernel instead
-        if (h->cent_t.p && !no_lane && nq <= 65535) {
+        if (h->cent_t.p && nq <= 65535) {
             // exact distances, a lane per (centroid, query): half the time of the tiled kernel for a handful of queries (smallq.hip.h)
             TRY(h->cdist.ensure((size_t)nq * h->kc * 4));
             ivfadc_index::EvPair ec;
@@ -2107,8 +1977,7 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
     if (h->dirty) TRY(upload_lists(h));
     if (nq == 0) return IVFADC_OK;
     // the grouping of a large quantizer is built on its first search (automatic mode), or on request (ivfadc_set_coarse_mode(h, 6))
-    static const bool tl_env_off = env_knob("IVFADC_NO_TWOLEVEL") != nullptr;
-    if (!h->tl_tried && !h->is_view && !tl_env_off && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
+    if (!h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
     const bool parted = h->part_n > 1;
     if (!parted && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
     if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64)) {
@@ -2525,7 +2394,6 @@ static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksu
                     if (e == hipSuccess) e = h2d_hip(h->lb_isc.p, isc.data(), isc.size() * 4, h->stream);
                     if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
                 }
-                if (env_knob("IVFADC_LB_BF16") != nullptr) h->lb_use_f16 = false;
             }
             if (rc == IVFADC_OK) rc = h->lb_split.ensure(sp.size() * 2);
             if (rc == IVFADC_OK) rc = h->lb_n2.ensure(n2.size() * 4);
@@ -2640,18 +2508,14 @@ static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksu
         } else {
             h->allow_bf16 = false;
         }
-        if (env_knob("IVFADC_COARSE_F32") != nullptr) h->allow_bf16 = false;
-        if (env_knob("IVFADC_COARSE_BF16") != nullptr) h->allow_f16 = false;   // A/B: the three-product bf16 split instead of the f16 form
-        if (env_knob("IVFADC_NO_LISTED") != nullptr) h->allow_listed = false;
-        if (env_knob("IVFADC_NO_PRUNE") != nullptr) h->allow_prune = false;
+        if (getenv("IVFADC_NO_PRUNE") != nullptr) h->allow_prune = false;
         if (rc == IVFADC_OK) rc = h->cnorm.ensure((size_t)kc * 4);
         if (rc == IVFADC_OK) {
             e = h2d_hip(h->cnorm.p, cn.data(), (size_t)kc * 4, h->stream);
             if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
         }
-        h->allow_filt = env_knob("IVFADC_EXACT_TABLES") == nullptr;
-        h->allow_mfma = env_knob("IVFADC_COARSE_EXACT") == nullptr;
-        if (const char *e = env_knob("IVFADC_MFMA_MIN_KC")) h->mfma_min_kc = std::max(128, atoi(e));   // tuning knob
+        h->allow_filt = getenv("IVFADC_EXACT_TABLES") == nullptr;
+        h->allow_mfma = getenv("IVFADC_COARSE_EXACT") == nullptr;
     }
     if (rc != IVFADC_OK) { ivfadc_destroy(h); return rc; }
     // an index starts with kc empty lists
@@ -2700,7 +2564,6 @@ void ivfadc_destroy(ivfadc_t *h)
     if (h->fb_ev) { (void)hipEventSynchronize(h->fb_ev); (void)hipEventDestroy(h->fb_ev); }
     h->fb_pin.release();
     if (h->pipe_ev_in) (void)hipEventDestroy(h->pipe_ev_in);
-    if (h->pipe_ev_out) (void)hipEventDestroy(h->pipe_ev_out);
     if (h->copy_stream) { (void)hipStreamSynchronize(h->copy_stream); (void)hipStreamDestroy(h->copy_stream); }
     for (hipEvent_t e : h->ingest_ev) (void)hipEventDestroy(e);
     // views that outlive the index keep dangling aliases: they are told, and refuse to search
@@ -2761,7 +2624,7 @@ static int streams_serialised(hipStream_t a, hipStream_t b, bool &serial)
 // *cand ends up on a hardware queue of its own with respect to every stream in fixed[] (as far as six tries reach)
 static int ensure_overlap(const hipStream_t *fixed, int nfixed, hipStream_t *cand, int64_t *replaced)
 {
-    static const bool off = env_knob("IVFADC_NO_STREAM_PROBE") != nullptr;
+    static const bool off = getenv("IVFADC_NO_STREAM_PROBE") != nullptr;
     if (off) return IVFADC_OK;
     std::vector<hipStream_t> rejected;
     int rc = IVFADC_OK;
@@ -2822,7 +2685,7 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
     v->fb_countdown = 0;
     v->fb_sp = v->fb_pp = 0;
     v->pipe_view = nullptr;
-    v->pipe_ev_in = v->pipe_ev_out = nullptr;
+    v->pipe_ev_in = nullptr;
     v->copy_stream = nullptr;
     v->copy_probed_a = v->copy_probed_b = nullptr;
     v->ingest_ev.clear();
@@ -2884,7 +2747,7 @@ static void copy_search_config(ivfadc_index *dst, const ivfadc_index *src)
     dst->allow_nf = src->allow_nf; dst->allow_sq = src->allow_sq; dst->sq_inside = src->sq_inside; dst->allow_lb = src->allow_lb;
     dst->force_lb = src->force_lb; dst->allow_bf16 = src->allow_bf16; dst->allow_f16 = src->allow_f16; dst->lb_use_f16 = src->lb_use_f16; dst->allow_prune = src->allow_prune; dst->allow_listed = src->allow_listed;
     dst->allow_filt = src->allow_filt; dst->allow_mfma = src->allow_mfma; dst->mfma_min_kc = src->mfma_min_kc; dst->ws_budget = src->ws_budget;
-    dst->force_qg = src->force_qg; dst->force_chunk = src->force_chunk; dst->force_pg = src->force_pg;
+    dst->force_qg = src->force_qg; dst->force_chunk = src->force_chunk;
     dst->part_n = src->part_n; dst->part_i = src->part_i;
     dst->tl_use = src->tl_use && dst->tl_cent.p != nullptr; dst->tl_mode = src->tl_mode;
 }
@@ -3084,7 +2947,7 @@ static int append_encoded(ivfadc_t *h, int64_t nnew, const int32_t *lst, const u
     TRY(set_device(h));
     // In place when the device layout is current and every target list has room; otherwise the host mirror takes
     // the points and the next search re-lays the lists out with fresh spare capacity.
-    bool inplace = h->have_lists && !h->dirty && env_knob("IVFADC_NO_INPLACE_APPEND") == nullptr;
+    bool inplace = h->have_lists && !h->dirty;
     if (inplace) {
         std::vector<int64_t> add((size_t)h->kc, 0);
         for (int64_t i = 0; i < nnew; ++i) add[lst[i]]++;
@@ -3372,20 +3235,17 @@ try {
 // compute queue a few more.  So: queries are ingested by a kernel that reads page-locked host memory (the caller's own array when the
 // library knows it -- ivfadc_host_register / ivfadc_host_alloc -- else pin_in), a handful of queries (latency path) are read in place,
 // and the final kernel of the search writes ids / distances / counts straight into page-locked host memory (the caller's arrays when
-// known, else pin_out): no device result block and no D2H copy in the chain.  IVFADC_HOST_LEGACY=1 keeps round 4's copy chain (A/B).
+// known, else pin_out): no device result block and no D2H copy in the chain.
 static inline double now_us()
 {
     return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count();
 }
 
-static bool host_legacy() { return env_knob("IVFADC_HOST_LEGACY") != nullptr; }   // (read per call: bench.py measures both chains in one run)
-
 // page-locked host rows -> device, on stream s
 static int ingest_rows(ivfadc_index *h, hipStream_t s, const void *src, void *dst, size_t bytes)
 {
-    static const bool by_dma = env_knob("IVFADC_INGEST_DMA") != nullptr;   // A/B: the copy engine instead of the compute queue
     if (bytes == 0) return IVFADC_OK;
-    if (by_dma || bytes > ((size_t)256 << 20) || (bytes & 3) != 0) {
+    if (bytes > ((size_t)256 << 20) || (bytes & 3) != 0) {
         HIP_TRY(hipMemcpyAsync(dst, src, bytes, hipMemcpyHostToDevice, s));
         return IVFADC_OK;
     }
@@ -3410,24 +3270,6 @@ try {
     const size_t obytes = 2 * idb + cb;
     h->hstats.calls++;
     h->hstats.batches++;
-    h->hc_legacy = host_legacy();
-    if (h->hc_legacy) {
-        // round 4's chain: memcpy -> H2D copy -> kernels -> D2H copy of the packed block -> memcpy
-        TRY(h->q_stage.ensure(qbytes));
-        TRY(h->out_ids.ensure(obytes));
-        TRY(h->pin_in.ensure(qbytes));
-        TRY(h->pin_out.ensure(obytes));
-        memcpy(h->pin_in.p, queries, qbytes);
-        const double t1 = now_us();
-        HIP_TRY(hipMemcpyAsync(h->q_stage.p, h->pin_in.p, qbytes, hipMemcpyHostToDevice, h->stream));
-        uint8_t *dout = (uint8_t *)h->out_ids.p;
-        TRY(search_dev(h, nq, h->q_stage.as<float>(), K, w, (uint32_t *)dout, (float *)(dout + idb), (int32_t *)(dout + 2 * idb)));
-        HIP_TRY(hipMemcpyAsync(h->pin_out.p, dout, obytes, hipMemcpyDeviceToHost, h->stream));
-        h->hc_out_direct = false;
-        h->hstats.stage_in_us += t1 - t0;
-        h->hstats.enqueue_us += now_us() - t1;
-        return IVFADC_OK;
-    }
     const float *src = queries;
     if (host_known(queries, qbytes)) {
         h->hstats.queries_direct++;
@@ -3439,7 +3281,7 @@ try {
     const double t1 = now_us();
     if (h->dirty) TRY(upload_lists(h));
     const float *d_q = src;
-    static const bool no_zero_copy = env_knob("IVFADC_NO_ZERO_COPY") != nullptr;
+    static const bool no_zero_copy = getenv("IVFADC_NO_ZERO_COPY") != nullptr;
     if (!no_zero_copy && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, K, w)) {
         // the latency path: a handful of rows, read in place by the two launches (a few KB over PCIe; no ingest step in the chain)
         h->hstats.zero_copy++;
@@ -3543,15 +3385,13 @@ try {
     const size_t qbytes = (size_t)total * h->d * 4;
     const size_t idb = (size_t)total * K * 4, cb = (size_t)total * 4;
     const size_t obytes = 2 * idb + cb;
-    const bool legacy = host_legacy();
-    const bool q_known = !legacy && host_known(queries, qbytes);
-    const bool o_known = !legacy && host_known(out_ids, idb) && host_known(out_dists, idb) && host_known(out_counts, cb);
+    const bool q_known = host_known(queries, qbytes);
+    const bool o_known = host_known(out_ids, idb) && host_known(out_dists, idb) && host_known(out_counts, cb);
     TRY(h->q_stage.ensure(qbytes));
     if (!q_known) TRY(h->pin_in.ensure(qbytes));
     if (!o_known) TRY(h->pin_out.ensure(obytes));
-    if (legacy) TRY(h->out_ids.ensure(obytes));
-    // where the kernels write: the caller's arrays, the library's pinned block, or (legacy) a device block that is copied back at the end
-    uint8_t *ob = legacy ? (uint8_t *)h->out_ids.p : (uint8_t *)h->pin_out.p;
+    // where the kernels write: the caller's arrays or the library's pinned block
+    uint8_t *ob = (uint8_t *)h->pin_out.p;
     uint32_t *oi = o_known ? out_ids : (uint32_t *)ob;
     float *od = o_known ? out_dists : (float *)(ob + idb);
     int32_t *oc = o_known ? out_counts : (int32_t *)(ob + 2 * idb);
@@ -3573,7 +3413,7 @@ try {
     auto token_of = [&](size_t i) { return (base + i + 1) | ((uint64_t)1 << 63); };   // never 0; the library's own numbering
     // Two batches in flight: even batches on this handle, odd ones on a view of it (second stream, second workspace), each lane naming
     // ITS next batch (i + 2) as the successor.  Not while profiling (the statistics are this handle's) and not for a view.
-    static const bool no_pipe = env_knob("IVFADC_NO_PIPELINE") != nullptr;
+    static const bool no_pipe = getenv("IVFADC_NO_PIPELINE") != nullptr;
     ivfadc_index *lane2 = nullptr;
     if (h->pipe_view && h->pipe_view->view_gen != h->generation) {
         fold_view_counters(h, h->pipe_view);
@@ -3659,8 +3499,7 @@ try {
                 memcpy((uint8_t *)h->pin_in.p + off, (const uint8_t *)queries + off, bytes);
                 t_stage += now_us() - t0;
             }
-            if (legacy) HIP_TRY(hipMemcpyAsync((uint8_t *)h->q_stage.p + off, qsrc + off, bytes, hipMemcpyHostToDevice, h->copy_stream));
-            else TRY(ingest_rows(h, h->copy_stream, qsrc + off, (uint8_t *)h->q_stage.p + off, bytes));
+            TRY(ingest_rows(h, h->copy_stream, qsrc + off, (uint8_t *)h->q_stage.p + off, bytes));
             HIP_TRY(hipEventRecord(h->ingest_ev[up_next], h->copy_stream));
             ++up_next;
         }
@@ -3720,14 +3559,6 @@ try {
         TRY(search_dev(ln, cnt[i], dq + (size_t)start[i] * h->d, K, w, oi + (size_t)start[i] * K, od + (size_t)start[i] * K, oc + start[i]));
     }
     const double t_issued = now_us();
-    if (legacy) {
-        if (lane2) {
-            if (!h->pipe_ev_out) HIP_TRY(hipEventCreateWithFlags(&h->pipe_ev_out, hipEventDisableTiming));
-            HIP_TRY(hipEventRecord(h->pipe_ev_out, lane2->stream));
-            HIP_TRY(hipStreamWaitEvent(h->stream, h->pipe_ev_out, 0));
-        }
-        HIP_TRY(hipMemcpyAsync(h->pin_out.p, ob, obytes, hipMemcpyDeviceToHost, h->stream));
-    }
     if (lane2) TRY(wait_stream(lane2));
     TRY(wait_stream(h));
     drain.armed = false;   // (the copy lane's work ended before the searches that read it)
@@ -4139,11 +3970,10 @@ try {
     auto rest = [&]() -> int {
         HIP_TRY(hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
         // search -> collective: the event orders the search's writes to the send block before the all-gather, and a PEER GPU may read that
-        // block directly over xGMI (RCCL's P2P-read and registered-buffer paths), so the record carries its system-scope release by
-        // default.  The relaxed form (no system fence: 2-3 us less per step, measured with a single-rank communicator only) is opt-in,
-        // IVFADC_EVENT_NO_SYSFENCE=1, until a run with >= 2 ranks has passed bench.py's gather_check with it.
-        static const bool no_sysfence = env_knob("IVFADC_EVENT_NO_SYSFENCE") != nullptr;
-        HIP_TRY(hipEventCreateWithFlags(&h->comm_ready, hipEventDisableTiming | (no_sysfence ? (unsigned)hipEventDisableSystemFence : 0u)));
+        // block directly over xGMI (RCCL's P2P-read and registered-buffer paths), so the record carries its system-scope release.  The
+        // relaxed form (no system fence: 2-3 us less per step, measured with a single-rank communicator only) waits for a run with >= 2
+        // ranks that passes bench.py's gather_check with it.
+        HIP_TRY(hipEventCreateWithFlags(&h->comm_ready, hipEventDisableTiming));
         for (int i = 0; i < ivfadc_index::COMM_SLOTS; ++i) HIP_TRY(hipEventCreateWithFlags(&h->comm_done[i], hipEventDisableTiming));
         return IVFADC_OK;
     };
@@ -4574,16 +4404,16 @@ try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
     if (mode < 0 || mode > 8) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 8");
-    h->allow_f16 = mode != 8 && mode != 3 && env_knob("IVFADC_COARSE_BF16") == nullptr;   // 8: as 0 with the three-product bf16 split (A/B, tests)
+    h->allow_f16 = mode != 8 && mode != 3;   // 8: as 0 with the three-product bf16 split (A/B, tests)
     // 6: the certified two-level search whatever the self-probe says (built on the next search); 7: never; anything else: automatic
     h->tl_mode = mode == 6 ? 1 : (mode == 7 ? -1 : 0);
     if (h->tl_tried) h->tl_use = h->tl_G > 0 && (h->tl_mode > 0 || (h->tl_mode == 0 && h->tl_probe_fraction >= 0.f && h->tl_probe_fraction <= 0.02f));
     if (h->tl_mode > 0 && h->tl_G == 0) h->tl_tried = false;   // (automatic mode did not build it for a small quantizer: build on request)
     h->sq_inside = mode == 5;
-    h->allow_mfma = (mode != 1) && env_knob("IVFADC_COARSE_EXACT") == nullptr;
+    h->allow_mfma = (mode != 1) && getenv("IVFADC_COARSE_EXACT") == nullptr;
     h->mfma_min_kc = (mode == 2) ? 128 : 2048;
-    h->allow_bf16 = mode != 3 && h->cent_hi.p != nullptr && env_knob("IVFADC_COARSE_F32") == nullptr;
-    h->allow_listed = mode != 4 && env_knob("IVFADC_NO_LISTED") == nullptr;
+    h->allow_bf16 = mode != 3 && h->cent_hi.p != nullptr;
+    h->allow_listed = mode != 4;
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -4591,7 +4421,7 @@ int ivfadc_set_pruning(ivfadc_t *h, int on)
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    h->allow_prune = on != 0 && env_knob("IVFADC_NO_PRUNE") == nullptr;
+    h->allow_prune = on != 0 && getenv("IVFADC_NO_PRUNE") == nullptr;
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -4619,10 +4449,10 @@ try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
     if (mode < 0 || mode > 7) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 7");
-    h->allow_filt = mode != 1 && env_knob("IVFADC_EXACT_TABLES") == nullptr;
+    h->allow_filt = mode != 1 && getenv("IVFADC_EXACT_TABLES") == nullptr;
     h->force_lb = mode == 2 || mode == 4;
     // 3 / 4: as 0 / 2 with the matrix-core tables built from the three-product bf16 split instead of one f16 product (A/B runs, tests)
-    h->lb_use_f16 = mode != 3 && mode != 4 && env_knob("IVFADC_LB_BF16") == nullptr;
+    h->lb_use_f16 = mode != 3 && mode != 4;
     // 5 / 6: as 0 with the eight-wave list-major kernel (wg8scan.hip.h) never / wherever it is instantiated (A/B runs, tests);
     // 7: as 6 with its eight-query form (wg8q8scan.hip.h) wherever that is instantiated
     h->wg8_mode = mode == 5 ? -1 : (mode == 6 ? 1 : (mode == 7 ? 2 : 0));
@@ -4683,10 +4513,6 @@ try {
 int ivfadc_set_tuning(ivfadc_t *h, int qg, int chunk_points)
 try {
     HandleLock lk_(h);
-    if (h) {
-        const char *e = env_knob("IVFADC_FORCE_PG");
-        h->force_pg = e ? atoi(e) : 0;
-    }
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
     if (!(qg == 0 || qg == -1 || qg == -2 || qg == -3 || qg == 1 || qg == 2 || qg == 4 || qg == 8))
         return fail(IVFADC_ERR_INVALID, "qg must be 0, -1, -2, -3, 1, 2, 4 or 8");

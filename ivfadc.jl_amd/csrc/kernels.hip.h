@@ -25,14 +25,11 @@ typedef float v4f __attribute__((ext_vector_type(4)));
 
 #define KEY_MAX 0xFFFFFFFFFFFFFFFFull
 
-// Register sets of the list-major code stream (striped_scan_range): 1 = one step ahead (the default), n > 1 = n sets in rotation.
-// Round 5 measured the deeper forms on the SIFT1B shape (profiles/r05_sift1b_prefetch_depth.txt): 16 384 x w = 1 scan 1.674 ms at
-// depth 1, 1.671 at 2, 1.711 at 3, 2.22 at 4 (registers: one workgroup per CU fewer); w = 8: 7.47 against 7.73 ms at depth 3; with the
-// loop unrolled per set instead of rotating registers 2.1-2.3 ms (the step body is large: instruction fetch).  The stream's latency is
-// NOT what holds these launches at 0.36-0.38 of the HBM peak -- more kilobytes in flight change nothing.
-#ifndef IVFADC_PF_DEPTH
-#define IVFADC_PF_DEPTH 1
-#endif
+// The list-major code stream (striped_scan_range) keeps one register set of codes one step ahead.  Round 5 measured deeper forms, n sets
+// in rotation, on the SIFT1B shape (profiles/r05_sift1b_prefetch_depth.txt): 16 384 x w = 1 scan 1.674 ms at depth 1, 1.671 at 2, 1.711
+// at 3, 2.22 at 4 (registers: one workgroup per CU fewer); w = 8: 7.47 against 7.73 ms at depth 3; with the loop unrolled per set instead
+// of rotating registers 2.1-2.3 ms (the step body is large: instruction fetch).  The stream's latency is NOT what holds these launches at
+// 0.36-0.38 of the HBM peak -- more kilobytes in flight change nothing.
 // (Also measured in round 5 and dropped: adding an entry's four 16-bit fields of the m = 8 integer filter with ONE v_lshl_add_u64 instead
 // of two v_add_u32 -- 3.05 against 3.82 SIMD cycles in isolation, tools/micro/add64_rate.hip, but 8.62 against 7.46 ms in the kernel: the
 // inline-asm operand pins even-aligned register pairs and the compiler's schedule of the sixteen lookups falls apart.)
@@ -828,14 +825,10 @@ static __device__ __forceinline__ void merge4_low(u32 (&a)[4], const u32 (&b)[4]
     cex(a[0], a[2]); cex(a[1], a[3]); cex(a[0], a[1]); cex(a[2], a[3]);
 }
 
-// DBG != 0: knock-outs for tools/coarse_probe.py (wrong results by design; instantiated in -DIVFADC_DEBUG builds only, chosen by IVFADC_COARSE_DBG):
-// 1 = no epilogue at all (loads and matrix work alone), 2 = scores and a per-lane minimum against a threshold that nothing meets (what a
-// threshold filter would cost), 3 = all of the record arithmetic but no store, 5 = no matrix instructions, 6 = no operand loads (5, 6: epilogue of 1),
-// 7 = records stored but not the tile minima, 8 = the minima but not the records
 // (256, 3): three workgroups per CU -- without the bound the listed epilogue is scheduled into 200 registers (two per CU)
 // F16: one f16 product per score (Qh / Ch hold scaled f16 rows, Ql / Cl are not read; neg2 = -2 / (scale_q scale_c)); otherwise the
 // three-product bf16 split (neg2 = -2)
-template <int TB, int DBG = 0, bool F16 = false>
+template <int TB, bool F16 = false>
 __global__ __launch_bounds__(256, 3) void coarse_bf16_kernel(const unsigned short *__restrict__ Qh, const unsigned short *__restrict__ Ql,
                                                           const unsigned short *__restrict__ Ch, const unsigned short *__restrict__ Cl,
                                                           const float *__restrict__ cnorm, float *__restrict__ out, int nq, int kc, int dp,
@@ -866,13 +859,6 @@ __global__ __launch_bounds__(256, 3) void coarse_bf16_kernel(const unsigned shor
                                     Ch + (size_t)(cok ? ci : 0) * dp, F16 ? Ch : Cl + (size_t)(cok ? ci : 0) * dp};
     uint4 pre[4][GPT];
     auto fetch = [&](int k0) {
-        if constexpr (DBG == 6) {   // no operand traffic: what the loop costs with its loads answered at once
-#pragma unroll
-            for (int p = 0; p < 4; ++p)
-#pragma unroll
-                for (int g = 0; g < GPT; ++g) pre[p][g] = make_uint4((u32)k0 + (u32)tid, 0x3f803f80u, (u32)p, 0x3f803f80u);
-            return;
-        }
 #pragma unroll
         for (int p = 0; p < 4; ++p)
 #pragma unroll
@@ -918,13 +904,6 @@ __global__ __launch_bounds__(256, 3) void coarse_bf16_kernel(const unsigned shor
             ch[j] = __builtin_bit_cast(v8bf, L(2, kg, wc * WT + j * 16 + rl));
             cl[j] = __builtin_bit_cast(v8bf, L(3, kg, wc * WT + j * 16 + rl));
         }
-        if constexpr (DBG == 5) {   // no matrix work: loads, LDS traffic and barriers alone
-#pragma unroll
-            for (int i = 0; i < NB; ++i)
-#pragma unroll
-                for (int j = 0; j < NB; ++j) acc[i][j][0] += (float)cl[j][0] + (float)qh[i][0] + (float)ch[j][1] + (float)ql[i][1];
-            continue;
-        }
 #pragma unroll
         for (int i = 0; i < NB; ++i)
 #pragma unroll
@@ -952,30 +931,6 @@ __global__ __launch_bounds__(256, 3) void coarse_bf16_kernel(const unsigned shor
             const int tile = blockIdx.x * 2 + wc, g = lane >> 4;
             const int cb = c0 + wc * WT + g * 4;              // + j * 16: the lane's four consecutive centroids of block j
             const int q16 = q0 + wq * WT + (lane & 15);       // + i * 16
-            if constexpr (DBG == 1 || DBG == 5 || DBG == 6) {
-                float t = 0.f;
-#pragma unroll
-                for (int i = 0; i < NB; ++i)
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) t += acc[i][j][0] + acc[i][j][1] + acc[i][j][2] + acc[i][j][3];
-                if (t == 1.2345e-30f) tmin[0] = t;
-                return;
-            }
-            if constexpr (DBG == 2) {
-#pragma unroll
-                for (int i = 0; i < NB; ++i) {
-                    float m = __builtin_inff();
-#pragma unroll
-                    for (int j = 0; j < NB; ++j) {
-                        const float4 t = *(const float4 *)(cnorm + (cb + j * 16 < kc - 4 ? cb + j * 16 : 0));
-                        const float v0 = __builtin_fmaf(neg2, acc[i][j][0], t.x), v1 = __builtin_fmaf(neg2, acc[i][j][1], t.y);
-                        const float v2 = __builtin_fmaf(neg2, acc[i][j][2], t.z), v3 = __builtin_fmaf(neg2, acc[i][j][3], t.w);
-                        m = fminf(fminf(m, fminf(v0, v1)), fminf(v2, v3));
-                    }
-                    if (__builtin_amdgcn_ballot_w64(m < -3.0e38f)) tmin[(size_t)(q16 + i * 16) * ntiles + tile] = m;
-                }
-                return;
-            }
             auto run = [&](auto ragged_tag) {
                 constexpr bool RAG = decltype(ragged_tag)::value;   // the tile is cut off by kc: clamp loads, blank the keys past kc
 #pragma unroll
@@ -1021,10 +976,9 @@ __global__ __launch_bounds__(256, 3) void coarse_bf16_kernel(const unsigned shor
                         merge4_low(best, o);
                     }
                     const int q = q16 + i * 16;
-                    if (DBG == 3 && best[0] != 0x12345u) continue;
                     if (g == 0 && q < nq && tile < ntiles) {
-                        if (DBG != 8) tlist[(size_t)tile * ldq + q] = make_uint4(best[0], best[1], best[2], best[3]);
-                        if (DBG != 7) tmin[(size_t)q * ntiles + tile] = ordered_to_float(best[0]);
+                        tlist[(size_t)tile * ldq + q] = make_uint4(best[0], best[1], best[2], best[3]);
+                        tmin[(size_t)q * ntiles + tile] = ordered_to_float(best[0]);
                     }
                 }
             };
@@ -1839,7 +1793,6 @@ struct IndexView {
     const u32 *ids;              // [n] or null (id == position)
     int d, kc, m, ksub, dsub, cs;
     int identity_labels;         // labels[i][c] == c for every block: skip the label fetch
-    int dbg_flags;               // diagnostics only (IVFADC_DEBUG_FLAGS): 1 = drop candidates, 2 = skip lookups
 };
 
 template <int QG> struct TabV;
@@ -2271,11 +2224,8 @@ static __device__ __forceinline__ void scan_prefetch(CodeRegs<M, P> &cr, const u
 template <int M, int QG, class S>
 static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>()> &cr, u32 tab_off, u32 pb, u32 p1,
                                                  const float (&dc)[QG], const u32 (&sbase)[QG], int nvalid, S (&sel)[QG],
-                                                 u32 (&thr_hi)[QG], int K, int lane, u64 *sthr, int dbg_flags)
+                                                 u32 (&thr_hi)[QG], int K, int lane, u64 *sthr)
 {
-#ifndef IVFADC_DEBUG
-    dbg_flags = 0;   // knock-outs (wrong results by design) are compiled out of the shipped library
-#endif
     using CR = CodeRegs<M, ppl_of<M, QG>()>;
     constexpr int PPL = CR::PPL;
         float acc[PPL][QG];
@@ -2310,7 +2260,6 @@ static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>
         for (int r = 0; r < PPL; ++r)
 #pragma unroll
             for (int s = 0; s < QG; ++s) acc[r][s] = dc[s];
-        if (!(dbg_flags & 2)) {
 #pragma unroll
         for (int ii = 0; ii < M; ++ii) {
 #pragma unroll
@@ -2319,10 +2268,6 @@ static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>
                 acc[r][0] = acc[r][0] + lds_load_abs<float>(cr.template byte_shl<2>(r, ii) + (tab_off + (u32)ii * 1024u));
             }
         }
-        } else {
-#pragma unroll
-            for (int r = 0; r < PPL; ++r) acc[r][0] += __uint_as_float(cr.byte(r, 0) << 10);
-        }
         }
         bool anyc = false;
 #pragma unroll
@@ -2330,7 +2275,7 @@ static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>
 #pragma unroll
             for (int s = 0; s < QG; ++s)
                 anyc = anyc || (CR::point(pb, r, lane) < p1 && s < nvalid && __float_as_uint(acc[r][s]) <= thr_hi[s]);
-        if (__any(anyc) && !(dbg_flags & 1)) {
+        if (__any(anyc)) {
 #pragma unroll
             for (int s = 0; s < QG; ++s) sel[s].tighten(readfirstlane64(sthr[s]));
 #pragma unroll
@@ -2352,8 +2297,7 @@ static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>
 template <int M, int QG, class S>
 static __device__ __forceinline__ void scan_range(const float *tab, u32 tab_off, const uint8_t *cbase, int cs, int m, u32 p0, u32 p1,
                                                   const float (&dc)[QG], const u32 (&sbase)[QG], int nvalid, S (&sel)[QG],
-                                                  int K, int wv, int lane, CodeRegs<M, ppl_of<M, QG>()> cr, u64 *sthr,
-                                                  int dbg_flags = 0)
+                                                  int K, int wv, int lane, CodeRegs<M, ppl_of<M, QG>()> cr, u64 *sthr)
 {
     // sthr[s] (LDS): the smallest K-th key any wave of the workgroup has found for slot s -- a valid bound
     // for every wave, so the four per-wave selectors prune like one workgroup-wide selector
@@ -2372,7 +2316,7 @@ static __device__ __forceinline__ void scan_range(const float *tab, u32 tab_off,
             const u32 pn = pb + 4 * STEP;
             if (pn < p1) nx.load(cbase, pn, lane);
             else nx = cr;
-            scan_step<M, QG>(cr, tab_off, pb, p1, dc, sbase, nvalid, sel, thr_hi, K, lane, sthr, dbg_flags);
+            scan_step<M, QG>(cr, tab_off, pb, p1, dc, sbase, nvalid, sel, thr_hi, K, lane, sthr);
             cr = nx;
         }
     } else {
@@ -2666,7 +2610,7 @@ static __device__ __forceinline__ void qf_targets(const u32 (&thr_hi)[4], const 
 
 // QF (m = 8 only): the 16-bit integer filter (quantize_tables_m8 / qf_targets): kc.apre holds 8-byte stripes, tg / mk the packed
 // thresholds of the current bounds (refreshed here whenever a bound moved), inv the per-query scales.
-struct QfState { u32 tg[2], mk[2]; float inv[4]; int dbg; };   // dbg: IVFADC_DEBUG_FLAGS in a debug build (1 = drop the filter's candidates)
+struct QfState { u32 tg[2], mk[2]; float inv[4]; };
 template <int M, int QG, bool QF, class S>
 static __device__ __forceinline__ void striped_scan_step(const CodeRegs<M, ppl_of<M, QG>()> &cr, const RotConst<M> &kc, u32 tab_off, u32 pb,
                                                          u32 p1, const float (&dc)[QG], const u32 (&sbase)[QG], int nvalid, S (&sel)[QG],
@@ -2739,11 +2683,6 @@ static __device__ __forceinline__ void striped_scan_step(const CodeRegs<M, ppl_o
         anym |= fm[r];
     }
     }
-#ifdef IVFADC_DEBUG
-    if constexpr (QF) {
-        if (qf.dbg & 1) anym = 0;   // knock-out (wrong results by design): the filter's fast path alone
-    }
-#endif
     if (anym) {
         u32 thr_before[QG];
 #pragma unroll
@@ -2818,8 +2757,7 @@ static __device__ __forceinline__ void striped_scan_step(const CodeRegs<M, ppl_o
 template <int M, int QG, bool QF, class S>
 static __device__ __forceinline__ void striped_scan_range(u32 tab_off, const uint8_t *cbase, u32 p0, u32 p1, const float (&dc)[QG],
                                                           const u32 (&sbase)[QG], int nvalid, S (&sel)[QG], int K, int wv, int lane,
-                                                          CodeRegs<M, ppl_of<M, QG>()> cr, u64 *sthr, u32 *cbuf, const float *qf_inv = nullptr,
-                                                          int dbg_flags = 0)
+                                                          CodeRegs<M, ppl_of<M, QG>()> cr, u64 *sthr, u32 *cbuf, const float *qf_inv = nullptr)
 {
     using CR = CodeRegs<M, ppl_of<M, QG>()>;
     constexpr u32 STEP = CR::STEP;
@@ -2832,14 +2770,12 @@ static __device__ __forceinline__ void striped_scan_range(u32 tab_off, const uin
     RotConst<M> kc;
     kc.template init<QG>(lane);   // (the integer filter does not rotate: kc is dead code there)
     QfState qf;
-    qf.dbg = dbg_flags;
     if constexpr (QF) {
 #pragma unroll
         for (int s = 0; s < QG; ++s) qf.inv[s] = __uint_as_float(__builtin_amdgcn_readfirstlane(__float_as_uint(qf_inv[s])));
         qf_targets(thr_hi, dc, qf.inv, nvalid, qf.tg, qf.mk);
     }
     int ccnt = 0;
-#if IVFADC_PF_DEPTH <= 1
     for (u32 pb = p0 + wv * STEP; pb < p1; pb += 4 * STEP) {
         CR nx;
         const u32 pn = pb + 4 * STEP;
@@ -2848,37 +2784,6 @@ static __device__ __forceinline__ void striped_scan_range(u32 tab_off, const uin
         striped_scan_step<M, QG, QF>(cr, kc, tab_off, pb, p1, dc, sbase, nvalid, sel, thr_hi, K, lane, sthr, cbuf, ccnt, qf);
         cr = nx;
     }
-#else
-    // Code stream, IVFADC_PF_DEPTH register sets in rotation: a set is refilled (for the step DEPTH wave-steps ahead) the moment its own
-    // step has been computed, so DEPTH - 1 loads of 1 KB per wave are in flight at any time and each has DEPTH - 1 steps to arrive.  With
-    // one set ahead (round 1-4) a wave held a single kilobyte in flight for the ~0.25 us a step takes: at three workgroups per CU that is
-    // 3 MB on the whole chip, i.e. ~3 TB/s at the loaded latency of HBM -- what the SIFT1B-shape scans measured (profiles/r04_sift1b_*:
-    // 0.36-0.38 of the HBM peak with SQ_WAIT_ANY at 38 % of the wave cycles and no pipe above 40 %).
-    {
-        // (the sets rotate by register moves -- a few v_mov per step -- rather than by unrolling the loop DEPTH times: the step body is
-        // large, and DEPTH copies of it cost more in instruction fetch than the moves do: measured 2.3 against 1.68 ms)
-        constexpr int DEPTH = IVFADC_PF_DEPTH;
-        constexpr u32 STR = 4 * STEP;
-        CR ahead[DEPTH - 1];
-        const u32 pfirst = p0 + wv * STEP;
-#pragma unroll
-        for (int k = 0; k < DEPTH - 1; ++k) {
-            if (pfirst + (u32)(k + 1) * STR < p1) ahead[k].load(cbase, pfirst + (u32)(k + 1) * STR, lane);
-            else ahead[k] = cr;
-        }
-        for (u32 pb = pfirst; pb < p1; pb += STR) {
-            CR nx;
-            const u32 pn = pb + DEPTH * STR;
-            if (pn < p1) nx.load(cbase, pn, lane);
-            else nx = cr;
-            striped_scan_step<M, QG, QF>(cr, kc, tab_off, pb, p1, dc, sbase, nvalid, sel, thr_hi, K, lane, sthr, cbuf, ccnt, qf);
-            cr = ahead[0];
-#pragma unroll
-            for (int k = 0; k + 1 < DEPTH - 1; ++k) ahead[k] = ahead[k + 1];
-            ahead[DEPTH - 2] = nx;
-        }
-    }
-#endif
     if (ccnt > 0) {
         wave_sync();
         drain_parked<M, QG>(cbuf, ccnt, dc, tab_off, sbase, nvalid, sel, thr_hi, K, lane, sthr);
@@ -2893,8 +2798,7 @@ static __device__ __forceinline__ void striped_scan_range(u32 tab_off, const uin
 template <int M, class S>
 static __device__ __forceinline__ void scan_pair(u32 toff0, u32 toff1, const uint8_t *cb0, const uint8_t *cb1, u32 len0, u32 len1,
                                                  float dc0, float dc1, u32 sb0, u32 sb1, S (&sel)[1], int K, int wv, int lane,
-                                                 CodeRegs<M, ppl_of<M, 1>()> a, CodeRegs<M, ppl_of<M, 1>()> b, u64 *sthr,
-                                                 int dbg_flags)
+                                                 CodeRegs<M, ppl_of<M, 1>()> a, CodeRegs<M, ppl_of<M, 1>()> b, u64 *sthr)
 {
     using CR = CodeRegs<M, ppl_of<M, 1>()>;
     constexpr u32 STEP = CR::STEP;
@@ -2910,7 +2814,7 @@ static __device__ __forceinline__ void scan_pair(u32 toff0, u32 toff1, const uin
             const u32 pn = pa + 4 * STEP;
             if (pn < len0) nx.load(cb0, pn, lane);
             else nx = a;
-            scan_step<M, 1>(a, toff0, pa, len0, dca, sba, 1, sel, thr_hi, K, lane, sthr, dbg_flags);
+            scan_step<M, 1>(a, toff0, pa, len0, dca, sba, 1, sel, thr_hi, K, lane, sthr);
             a = nx;
             pa = pn;
         }
@@ -2919,7 +2823,7 @@ static __device__ __forceinline__ void scan_pair(u32 toff0, u32 toff1, const uin
             const u32 pn = pb + 4 * STEP;
             if (pn < len1) nx.load(cb1, pn, lane);
             else nx = b;
-            scan_step<M, 1>(b, toff1, pb, len1, dcb, sbb, 1, sel, thr_hi, K, lane, sthr, dbg_flags);
+            scan_step<M, 1>(b, toff1, pb, len1, dcb, sbb, 1, sel, thr_hi, K, lane, sthr);
             b = nx;
             pb = pn;
         }
@@ -3118,7 +3022,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanArgs a)
         if constexpr (STRIPE)
             striped_scan_range<M, QG, QF>(0u, cbase, p0, p1, dc, sbase, nvalid, sel, K, wv, lane, cr, L.sthr,
                                           (u32 *)(L.sthr + STHR_WORDS * QG) + 192 + wv * (CAND_CAP * cand_stride<M>()),   // behind the 768-B probe cache
-                                          L.resid + 4, ix.dbg_flags);
+                                          L.resid + 4);
         else scan_range<M, QG>(L.tab, 0u, cbase, ix.cs, m, p0, p1, dc, sbase, nvalid, sel, K, wv, lane, cr, L.sthr);
         __builtin_amdgcn_s_setprio(0);
 
@@ -3316,22 +3220,14 @@ struct QScanArgs {
     u32 *out_ids;
     float *out_dists;
     int *out_counts;
-    u64 *dbg;   // diagnostic phase stamps (IVFADC_DEBUG_STAMPS=1), else null: [workgroup][16] cycles
+    int prune;         // skip the probes whose coarse distance already lies above the K-th best key (exact: see the round loop)
     // fused coarse top-w (w <= 64): when cdist != null the workgroup selects its own probes from its row of the
     // coarse distances (coarsequantizers.jl:35-36) and the probe_* arrays above are not read
     const float *cdist;
     u64 *scanned_points;
     int approx;        // cdist holds MFMA scores: certify + refine (refine_probes)
     RefineArgs rf;
-    int prune;         // skip the probes whose coarse distance already lies above the K-th best key (exact: see the round loop)
 };
-
-// phase stamps and knock-out flags exist only in a diagnostic build (-DIVFADC_DEBUG): the shipped library carries neither
-#ifdef IVFADC_DEBUG
-#define STAMP() (a.dbg ? (u64)__builtin_readcyclecounter() : 0ull)
-#else
-#define STAMP() 0ull
-#endif
 
 // Four workgroups per CU (<= 128 VGPRs) for the light shapes: a batch of 1024 queries is then resident at once.
 // LB: the rounds of lbscan.hip.h (8-bit lower-bound tables from the matrix cores, exact sums for the survivors) instead of
@@ -3364,9 +3260,6 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
     WSel<SMALL> sel[1];
     sel[0].init(KEY_MAX, SMALL ? nullptr : L.selbuf + (size_t)wv * cap, cap, K);
     if (tid == 0) arm_bound<1>(L.sthr, 0, KEY_MAX);   // published by the first round's barriers (one slot: the PG probes of a round are one query's)
-    u64 tph[5] = {0, 0, 0, 0, 0};
-    u64 tpro[6] = {0, 0, 0, 0, 0, 0};
-    const u64 tstart = STAMP();
 
     // probes of this query: rows of the global arrays, or selected here and kept in LDS
     const int *prow_list = a.probe_list + (size_t)q * w;
@@ -3389,8 +3282,6 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
         ws.init(KEY_MAX, nullptr, 64, Ksel);
         const float *row = a.cdist + (size_t)q * ix.kc;
         __syncthreads();                                 // L.sthr[0] = KEY_MAX is visible: it is the shared bound of this phase
-        const u64 tp0 = STAMP();
-        tpro[0] = tp0;
         bool have = false;   // uniform over the workgroup
         if constexpr (LB && M > 16) {
             // rows of up to 8192 scores through the short-row selection (16 / 32 keys per lane: this kernel has the registers)
@@ -3403,8 +3294,6 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
                 else
                     have = a.approx ? select_row_short<true, 8>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt)
                                     : select_row_short<false, 8>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt);
-                tph[4] = STAMP() - tp0;
-                tpro[1] = tpro[2] = tpro[3] = STAMP();
             }
         }
         if (!have && Ksel <= SHORT_ROW_MAXK && ix.kc <= 2048 && (ix.kc & 3) == 0) {
@@ -3414,8 +3303,6 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
             u32 *ccnt = (u32 *)(s_list + 168);
             have = a.approx ? select_row_short<true>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt)
                             : select_row_short<false>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt);
-            tph[4] = STAMP() - tp0;
-            tpro[1] = tpro[2] = tpro[3] = STAMP();
         }
         if constexpr (M > 16) {   // wide codes only: in the m = 8 / 16 kernels this path costs 40 VGPRs and a workgroup per CU
         if (!have && a.approx && a.rf.tmin != nullptr) {   // uniform
@@ -3429,26 +3316,20 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
             }
             __syncthreads();
             have = *flag != 0;
-            tph[4] = STAMP() - tp0;
-            tpro[1] = tpro[2] = tpro[3] = STAMP();
         }
         }
         if (!have) {
             if (a.approx) select_row<true, 4>(ws, row, ix.kc, Ksel, wv, lane, L.sthr);
             else select_row<false, 4>(ws, row, ix.kc, Ksel, wv, lane, L.sthr);
-            tph[4] = STAMP() - tp0;
             const int wc = ws.finish(Ksel, lane);
             ws.store(L.xch + (size_t)wv * 64, wc, lane);     // the exchange area aliases the (not yet built) tables
             if (lane == 0) L.scnt[wv] = wc;
-            tpro[1] = STAMP();
             __syncthreads();
-            tpro[2] = STAMP();
         }
         int fc = 0;
         if (wv == 0) {
             if (lane == 0) arm_bound<1>(L.sthr, 0, KEY_MAX);   // re-armed for the scan (published by the barrier below)
             if (!have) merge_waves(ws, L.xch, (size_t)64, L.scnt, 1, Ksel, KEY_MAX, 0, lane);
-            tpro[3] = STAMP();
             fc = ws.finish(Ksel, lane);                 // == min(Ksel, kc)
         }
         if (a.approx) {   // uniform; every wave helps to stage the candidates' rows (the table area is still free)
@@ -3479,10 +3360,8 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
             }
             const u32 total = __shfl(incl, 63);
             if (lane == 0) atomicAdd(a.scanned_points + (size_t)(q & 63) * 8, (u64)total);
-            tpro[4] = STAMP();
         }
         __syncthreads();
-        tpro[5] = STAMP();
         prow_list = s_list;
         prow_dc = s_dc;
         prow_base = s_base;
@@ -3505,7 +3384,7 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
     // wider rows -- where the table build dwarfs everything else -- take the plain three-barrier round.)
     if constexpr (LB) {
         lb_rounds<M, DS, PG>(ix, a.lb, a.queries, smem_raw, q, w, K, a.prune, a.scanned_points, sel[0], L.sthr, s_list, s_dc, s_base, s_len, s_coff, wv,
-                             lane, tid, a.dbg);
+                             lane, tid);
     } else {
     constexpr int RU = (M > 0 && M * DS * PG <= 256) ? 1 : 2;
     constexpr bool can_pipe = M == 0 || M * DS * PG <= 256 * RU;   // statically out for wide rows: no dead state in their loops
@@ -3568,9 +3447,7 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
         CodeRegs<M, ppl_of<M, 1>()> cr[PG];
 #pragma unroll
         for (int s = 0; s < PG; ++s) scan_prefetch(cr[s], cb[s], 0u, len[s], wv, lane);   // in flight while the tables are built
-        const u64 t0 = STAMP();
         __syncthreads();          // every wave is done with the previous round's tables (and has written this round's residuals)
-        const u64 t1 = STAMP();
         // Exact pruning.  A point's sum starts from its list's coarse distance and only grows (index.jl:242-244: every table
         // entry is a sum of squares, >= +0), so no point of a list whose dc lies above the K-th best key found so far can
         // enter the result; probes come in ascending dc (coarsequantizers.jl:35-36), so the first such list ends the
@@ -3615,7 +3492,6 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
             }
             __syncthreads();
         }
-        const u64 t2 = STAMP();
         if constexpr (M == 48 && DS == 16) {
             if (pkb) build_tables_pk<DS>(ix, m, L.resid, L.tab, tid);
             else build_tables_deep<PG, DS, 4>(ix, m, L.resid, L.tab, tid);   // registers to spare: four stages in flight
@@ -3626,13 +3502,12 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
             } else build_tables_t<PG, DS, TAB_SEP>(ix, m, L.resid, L.tab, tid);
         }
         __syncthreads();
-        const u64 t3 = STAMP();
         const bool more = pipe && (j0 + np) < w;
         if (more) resid_fetch(j0 + np);
         __builtin_amdgcn_s_setprio(3);   // see scan_kernel
         if constexpr (PG == 2 && M > 0 && M <= 16 && SMALL) {   // wider codes / LDS selectors: the extra live state costs a wave per SIMD
             scan_pair<M>(0u, (u32)M * 1024u, cb[0], cb[1], len[0], len[1], dcv[0], dcv[1], sb[0], sb[1], sel, K, wv, lane, cr[0], cr[1],
-                         L.sthr, ix.dbg_flags);
+                         L.sthr);
         } else {
 #pragma unroll
             for (int s = 0; s < PG; ++s) {
@@ -3640,16 +3515,13 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
                 const float dc1[1] = {dcv[s]};
                 const u32 sb1[1] = {sb[s]};
                 scan_range<M, 1>(L.tab + (size_t)s * m * 256, (u32)s * (u32)m * 1024u, cb[s], ix.cs, m, 0u, len[s], dc1, sb1, 1, sel, K, wv,
-                                 lane, cr[s], L.sthr, ix.dbg_flags);
+                                 lane, cr[s], L.sthr);
             }
         }
         __builtin_amdgcn_s_setprio(0);
         if (more) resid_store();   // the table build of this round is behind the barrier above: the buffer is free
-        const u64 t4 = STAMP();
-        tph[0] += t1 - t0; tph[1] += t2 - t1; tph[2] += t3 - t2; tph[3] += t4 - t3;
     }
     }
-    const u64 tloop = STAMP();
     const int mycnt = sel[0].finish(K, lane);
     __syncthreads();              // exchange area aliases the table
     sel[0].store(L.xch + (size_t)wv * L.xcap, mycnt, lane);
@@ -3663,24 +3535,10 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
         });
         if (lane == 0) a.out_counts[q] = fc;
     }
-#ifdef IVFADC_DEBUG
-    if (a.dbg && tid == 0) {
-        const u64 tend = STAMP();
-        u64 *o = a.dbg + (size_t)q * 16;
-        if constexpr (!LB) { o[0] = tph[0]; o[1] = tph[1]; o[2] = tph[2]; o[3] = tph[3]; }
-        o[4] = tloop - tstart; o[5] = tend - tloop; o[6] = tph[4]; o[7] = tend;
-        o[8] = tpro[0] - tstart; o[9] = tpro[1] - tpro[0]; o[10] = tpro[2] - tpro[1]; o[11] = tpro[3] - tpro[2];
-        o[12] = tpro[4] - tpro[3]; o[13] = tpro[5] - tpro[4];
-        if constexpr (!LB) { o[14] = 0; o[15] = 0; }
-    }
-#endif
 }
 
 template <int M, int DS, int PG, bool SMALL, bool LB = false>
-#ifndef IVFADC_QSCAN_MINW
-#define IVFADC_QSCAN_MINW 1
-#endif
-__global__ __launch_bounds__(256, LB ? (M <= 16 ? 3 : (PG >= 4 ? 2 : (PG == 3 ? 3 : 4))) : ((M == 8 && SMALL && PG <= 2) ? IVFADC_QSCAN_MINW : 1)) void qscan_kernel(const QScanArgs a)
+__global__ __launch_bounds__(256, LB ? (M <= 16 ? 3 : (PG >= 4 ? 2 : (PG == 3 ? 3 : 4))) : 1) void qscan_kernel(const QScanArgs a)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     qscan_body<M, DS, PG, SMALL, LB>(a, smem_raw, (int)blockIdx.x);
@@ -3688,10 +3546,7 @@ __global__ __launch_bounds__(256, LB ? (M <= 16 ? 3 : (PG >= 4 ? 2 : (PG == 3 ? 
 
 // The query-major scan of one batch with the exact small-problem coarse search of the NEXT batch riding behind it in the same grid:
 // workgroups [0, a.nq) scan, the rest each take one tile of the next batch's coarse distances as the scanning workgroups retire.
-#ifndef IVFADC_RIDER_QW
-#define IVFADC_RIDER_QW 4
-#endif
-constexpr int RIDER_QW = IVFADC_RIDER_QW;   // queries per wave of a rider tile (a tile: 64 centroids x 4 RIDER_QW queries)
+constexpr int RIDER_QW = 4;   // queries per wave of a rider tile (a tile: 64 centroids x 4 RIDER_QW queries)
 struct CoarseNext {
     const float *queries;   // next batch
     float *out;             // its [nq][kc] distance rows

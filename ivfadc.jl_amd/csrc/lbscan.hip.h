@@ -656,14 +656,8 @@ static __device__ __forceinline__ void lb_ub_merge(WSel<true> &usel, WSel<true> 
 template <int M, int DS, int PG>
 static __device__ __forceinline__ void lb_rounds(const IndexView &ix, const LbView &lb, const float *queries, unsigned char *smem, int q, int w, int K,
                                                  int prune, u64 *scanned_points, WSel<true> &sel, u64 *sthr, const int *s_list, const float *s_dc,
-                                                 const u32 *s_base, const u32 *s_len, const u32 *s_coff, int wv, int lane, int tid, u64 *dbg = nullptr)
+                                                 const u32 *s_base, const u32 *s_len, const u32 *s_coff, int wv, int lane, int tid)
 {
-#ifdef IVFADC_DEBUG
-#define LB_STAMP() (dbg ? (u64)__builtin_readcyclecounter() : 0ull)
-#else
-#define LB_STAMP() 0ull
-#endif
-    u64 tl[6] = {0, 0, 0, 0, 0, 0};   // diagnostic build: cycles in (A) wait, setup, build, scan, final drain; rounds
     using C = LbCfg<M, DS, PG>;
     constexpr int D = M * DS;
     constexpr int PPL = PG >= 4 ? 2 : 1;          // points per lane and step, codeword groups of a drain: register budget, as NBUF
@@ -684,10 +678,8 @@ static __device__ __forceinline__ void lb_rounds(const IndexView &ix, const LbVi
     u32 nsurv = 0;
     u32 thr_hi = 0xFFFFFFFFu;
     for (int j0 = 0; j0 < w; j0 += PG) {
-        const u64 ta = LB_STAMP();
         if (j0 > 0) lb_ub_store(usel, ubx, ubc, K, wv, lane);
         __syncthreads();   // (A)
-        const u64 tb = LB_STAMP();
         if (j0 > 0) lb_ub_merge(usel, sel, ubx, ubc, K, wv, lane, sthr, thr_hi);
         // exact pruning, as in the exact rounds: nothing writes the shared bound between barrier (A) and the next scan
         const u32 thi = (u32)(readfirstlane64(sthr[0]) >> 32);
@@ -710,7 +702,6 @@ static __device__ __forceinline__ void lb_rounds(const IndexView &ix, const LbVi
         }
         lb_prepare_round<M, DS, PG>(ix, lb, smem, qf, s_list, j0, w, wv, lane, tid);   // barriers (B), (C), (D) inside
         if (tid < PG) { pcu[8 + tid] = 0u; pcu[20 + tid] = 0u; }   // range maxima (and sums of N) of the next round (every reader of this round's is behind barrier (D))
-        const u64 td = LB_STAMP();
         // scan: the four waves interleave the steps of each list; a wave's next step (of this or the next list) is in flight
         __builtin_amdgcn_s_setprio(3);
         int s = 0;
@@ -749,24 +740,14 @@ static __device__ __forceinline__ void lb_rounds(const IndexView &ix, const LbVi
             cr = nx; s = s2; pb = pb2;
         }
         __builtin_amdgcn_s_setprio(0);
-        const u64 te = LB_STAMP();
-        tl[0] += tb - ta; tl[2] += td - tb; tl[3] += te - td; tl[5] += 1;
     }
     {   // what is still viable under the final bound gets its exact sum (the pool outlives the rounds: most of it never does)
-        const u64 te = LB_STAMP();
         lb_ub_store(usel, ubx, ubc, K, wv, lane);
         __syncthreads();
         lb_ub_merge(usel, sel, ubx, ubc, K, wv, lane, sthr, thr_hi);
         if (ccnt > 0)
             lb_pool_make_room<M, DS, (M / 4) % 3 == 0 ? 3 : ((M / 4) % 2 == 0 ? 2 : 1), C::PCAP>(pbuf, ccnt, lb, ix.centroids, qf, s_list, s_dc, pp, sel, thr_hi, K, lane, sthr, nsurv, true);
-        tl[4] += LB_STAMP() - te;
     }
-#ifdef IVFADC_DEBUG
-    if (dbg && tid == 0) {
-        u64 *o = dbg + (size_t)q * 16;
-        o[0] = tl[0]; o[1] = tl[1]; o[2] = tl[2]; o[3] = tl[3]; o[14] = tl[4]; o[15] = tl[5];
-    }
-#endif
     if (lane == 0 && nsurv) atomicAdd(scanned_points + (size_t)(q & 63) * 8 + 2, (u64)nsurv);
 }
 

@@ -276,8 +276,7 @@ struct NfTargets {
 //      under an older, looser bound goes);
 //   3. if the pool is still more than half full (or at a flush) the newest pairs get their exact sums, 64 at a time.
 static __device__ __forceinline__ void nf_make_room(u32 *pool, int &pcnt, const float *cb_lab, unsigned char *smem, int nvalid,
-                                                    WSel<true> (&sel)[NF_QG], WSel<true> (&usel)[NF_QG], int K, int wv, int lane, u32 &nsurv, bool flush,
-                                                    bool count_exact = true)
+                                                    WSel<true> (&sel)[NF_QG], WSel<true> (&usel)[NF_QG], int K, int wv, int lane, u32 &nsurv, bool flush)
 {
     const float *qc = (const float *)(smem + NfLds::QC);
     const u32 *sbase = (const u32 *)(smem + NfLds::QI) + 16;
@@ -285,7 +284,7 @@ static __device__ __forceinline__ void nf_make_room(u32 *pool, int &pcnt, const 
     if (flush && pcnt <= 16) {
         // a handful of pairs at the end of an item (the common case once bounds are tight): one pass of exact sums costs less than
         // offering, re-targeting and compacting them first
-        if (count_exact) nsurv += (u32)pcnt;
+        nsurv += (u32)pcnt;
         nf_drain(pool, pcnt, cb_lab, smem, sel, K, lane);
         pcnt = 0;
         wave_sync();
@@ -335,7 +334,7 @@ static __device__ __forceinline__ void nf_make_room(u32 *pool, int &pcnt, const 
         pcnt = kept;
         if (pcnt == 0 || (!flush && pcnt <= NF_POOL / 2)) break;
         const int take = pcnt < 64 ? pcnt : 64;
-        if (count_exact) nsurv += (u32)take;
+        nsurv += (u32)take;
         nf_drain(pool + (size_t)(pcnt - take) * NF_ES, take, cb_lab, smem, sel, K, lane);
         pcnt -= take;
         if (!flush) break;   // (a flush goes round: the exact sums have tightened the bounds, the rest is re-tested first)
@@ -345,7 +344,7 @@ static __device__ __forceinline__ void nf_make_room(u32 *pool, int &pcnt, const 
 
 template <int PPL>
 static __device__ __forceinline__ void nf_scan_range(const uint8_t *cbase, u32 p0, u32 p1, int nvalid, WSel<true> (&sel)[NF_QG], int K, int wv,
-                                                     int lane, CodeRegs<8, PPL> cr, unsigned char *smem, const float *cb_lab, u32 &nsurv, int dbg_flags)
+                                                     int lane, CodeRegs<8, PPL> cr, unsigned char *smem, const float *cb_lab, u32 &nsurv)
 {
     using CR = CodeRegs<8, PPL>;
     constexpr u32 STEP = CR::STEP;
@@ -455,16 +454,7 @@ static __device__ __forceinline__ void nf_scan_range(const uint8_t *cbase, u32 p
             cm[r] = __builtin_amdgcn_ballot_w64(c && CR::point(pb, r, lane) < p1);
             any |= cm[r];
         }
-#ifdef IVFADC_DEBUG
-        if (dbg_flags & 1) any = 0;   // knock-out (wrong results by design): the filter's fast path alone
-#endif
-#ifdef IVFADC_DEBUG
-        const u64 tc0 = (dbg_flags & 512) ? (u64)__builtin_readcyclecounter() : 0ull;
-#endif
         if (any) {   // uniform, rare once the bounds are tight
-#ifdef IVFADC_DEBUG
-            if (dbg_flags & 8) nsurv += 1u;    // diagnostic counters instead of the exact-sum count: steps with candidates
-#endif
             // Candidates are only PARKED here -- (code bytes, position, integer sum, query) -- and worked on in batches when the pool fills
             // (nf_make_room): a streaming selection moves its bound ~K ln(N / K) times per query, and paying selector insertions,
             // target and bias updates per move was most of this kernel's time before.
@@ -497,14 +487,7 @@ static __device__ __forceinline__ void nf_scan_range(const uint8_t *cbase, u32 p
                 u32 m8 = ((cmr >> lane) & 1ull) ? below(f0, f1, f2, f3) : 0u;
                 for (u64 bm; (bm = __builtin_amdgcn_ballot_w64(m8 != 0u)) != 0;) {   // one pair per lane and trip (a point rarely passes for two queries)
                     if (pcnt + __popcll(bm) > NF_POOL) {
-#ifdef IVFADC_DEBUG
-                        if (dbg_flags & 32) nsurv += 1u;              // pool overflows
-                        const u64 tm0 = (dbg_flags & 128) ? (u64)__builtin_readcyclecounter() : 0ull;
-#endif
-                        nf_make_room(pool, pcnt, cb_lab, smem, nvalid, sel, usel, K, wv, lane, nsurv, false, (dbg_flags & 1016) == 0);
-#ifdef IVFADC_DEBUG
-                        if (dbg_flags & 128) nsurv += (u32)(((u64)__builtin_readcyclecounter() - tm0) >> 6);   // cycles / 64 in overflow handling
-#endif
+                        nf_make_room(pool, pcnt, cb_lab, smem, nvalid, sel, usel, K, wv, lane, nsurv, false);
                         exchange();
                         tg.set(smem, nvalid, sel, wv, lane);
                         m8 &= below(q0 + tg.b0, q1 + tg.b1, q2 + tg.b2, q3 + tg.b3);   // the budgets have moved: what still passes (no carry: Q <= 32760, bias <= 0x8000)
@@ -519,29 +502,16 @@ static __device__ __forceinline__ void nf_scan_range(const uint8_t *cbase, u32 p
                         *(uint4 *)ent = make_uint4(w0, w1, pt, (Q << 8) | s);
                     }
                     pcnt += __popcll(bm);
-#ifdef IVFADC_DEBUG
-                    if (dbg_flags & 16) nsurv += (u32)__popcll(bm);   // parked pairs
-                    if (dbg_flags & 64) nsurv += 1u;                  // trips of the parking loop
-#endif
                     m8 &= m8 - 1u;
                 }
             }
         }
-#ifdef IVFADC_DEBUG
-        if ((dbg_flags & 512) && any) nsurv += (u32)(((u64)__builtin_readcyclecounter() - tc0) >> 6);   // cycles / 64 in the whole candidate path
-#endif
         cr = cr1;
         cr1 = nx;
     }
     // what is still viable under the final bounds gets its exact sum (most of what was parked never does)
     exchange();
-#ifdef IVFADC_DEBUG
-    const u64 tf0 = (dbg_flags & 256) ? (u64)__builtin_readcyclecounter() : 0ull;
-#endif
-    if (pcnt > 0) nf_make_room(pool, pcnt, cb_lab, smem, nvalid, sel, usel, K, wv, lane, nsurv, true, (dbg_flags & 1016) == 0);
-#ifdef IVFADC_DEBUG
-    if (dbg_flags & 256) nsurv += (u32)(((u64)__builtin_readcyclecounter() - tf0) >> 6);   // cycles / 64 in the final flush
-#endif
+    if (pcnt > 0) nf_make_room(pool, pcnt, cb_lab, smem, nvalid, sel, usel, K, wv, lane, nsurv, true);
     exchange();
 }
 
@@ -686,14 +656,6 @@ __global__ __launch_bounds__(256, 2) void nf_scan_kernel(const ScanArgs a, const
         int tidb = tid, laneb = lane;
         asm volatile("" : "+v"(tidb), "+v"(laneb));
         NfBuild bld;
-#ifdef IVFADC_DEBUG
-        if (ix.dbg_flags & 4) {       // knock-out: no table build (the scan runs on whatever the LDS holds)
-#pragma unroll
-            for (int k = 0; k < 8; ++k)
-#pragma unroll
-                for (int s = 0; s < 8; ++s) bld.e[k][s] = (float)(k + s + tidb);
-        } else
-#endif
         nf_entries(ix, nf.n2, smem, tidb, laneb, bld);
         nf_reduce_publish<true>(bld, smem, laneb);
         nf_reduce_publish<false>(bld, smem, laneb);
@@ -735,10 +697,7 @@ __global__ __launch_bounds__(256, 2) void nf_scan_kernel(const ScanArgs a, const
         __syncthreads();
 
         __builtin_amdgcn_s_setprio(3);
-#ifdef IVFADC_DEBUG
-        if (!(ix.dbg_flags & 2))      // knock-out: table build only
-#endif
-        nf_scan_range<PPL>(cbase, p0, p1, nvalid, sel, K, wv, lane, cr, smem, nf.cb_lab, nsurv, ix.dbg_flags);
+        nf_scan_range<PPL>(cbase, p0, p1, nvalid, sel, K, wv, lane, cr, smem, nf.cb_lab, nsurv);
         __builtin_amdgcn_s_setprio(0);
 
         // ---- per-wave flush, then wave v merges slots v and v + 4 of the four waves and publishes them (as scan_kernel)

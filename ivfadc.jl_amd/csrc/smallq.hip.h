@@ -207,7 +207,7 @@ __global__ __launch_bounds__(256) void sq_kernel(const SqArgs a)
         __syncthreads();
         const float dc1[1] = {dcv};
         const u32 sb1[1] = {sb};
-        scan_range<M, 1>(L.tab, 0u, cbase, ix.cs, m, p0, p1, dc1, sb1, 1, sel, K, wv, lane, cr, L.sthr, 0);
+        scan_range<M, 1>(L.tab, 0u, cbase, ix.cs, m, p0, p1, dc1, sb1, 1, sel, K, wv, lane, cr, L.sthr);
         const int mycnt = sel[0].finish(K, lane);
         __syncthreads();              // the exchange area aliases the tables
         sel[0].store(L.xch + (size_t)wv * L.xcap, mycnt, lane);

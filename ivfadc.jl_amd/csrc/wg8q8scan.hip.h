@@ -1,5 +1,5 @@
 // wg8q8scan.hip.h -- the eight-wave list-major scan (wg8scan.hip.h) with EIGHT queries per code stream.  Included by kernels.hip.h behind
-// wg8scan.hip.h (its constants, W8_* knobs and W8Prof macros are shared), namespace ivf.
+// wg8scan.hip.h (its constants are shared), namespace ivf.
 //
 // Reference: src/coarsequantizers.jl:40-45 (residuals), src/index.jl:232-236 (table build), :240-246 (scan), :247-254 (bounded top-K).
 //
@@ -31,8 +31,6 @@ struct W9Lds {
 };
 static_assert(W9Lds::END <= 80u * 1024u, "two workgroups per CU");
 static_assert((W9Lds::HARD & 7u) == 0 && (W9Lds::STHR & 7u) == 0 && (W9Lds::POOL & 7u) == 0, "8-byte bounds");
-
-typedef W8Prof W9Prof;
 
 static __device__ __forceinline__ u32 w9_perm(u32 s0, u32 s1, u32 sel)
 {
@@ -182,7 +180,7 @@ static __device__ __forceinline__ void w9_pass_issue(W9Pass &ps, u32 cbuf_addr, 
 
 // Works a pass off.  (Measured and dropped: everything the pass needs from LDS -- constants, bounds, a snapshot of every slot's pool, the
 // bias arithmetic's operands -- requested in one go ahead of the running sums, the bias computed from registers: 16 384 x w = 8
-// 5.87 -> 5.91 ms, w = 1 1.38 -> 1.44.  The pass does not wait for memory -- W8_PROF: 260 of its 7 700 cycles -- it is ~400 dependent
+// 5.87 -> 5.91 ms, w = 1 1.38 -> 1.44.  The pass does not wait for memory -- 260 of its 7 700 cycles, by cycle counters -- it is ~400 dependent
 // instructions on a SIMD it shares with three scanning waves.)
 static __device__ __forceinline__ void w9_pass_finish(const W9Pass &ps, int nvalid, int K, int lane)
 {
@@ -229,7 +227,7 @@ static __device__ __attribute__((noinline)) u32 w9_kth_sum4(u32 v0, u32 v1, u32 
 }
 
 static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t codes, u32 p0, u32 p1, int nvalid, int K, int wv, int lane,
-                                                     v4u ca, v4u cb, __amdgpu_buffer_rsrc_t gt, W9Prof &pr)
+                                                     v4u ca, v4u cb, __amdgpu_buffer_rsrc_t gt)
 {
     // A step of a wave is 256 points: four per lane in two 16-byte registers sets, ca (points pb + 2 lane, + 1) and cb (pb + 128 + 2 lane,
     // + 1), requested by the caller for the first step.  The code stream comes through a buffer resource over the list: the lane's offset
@@ -292,27 +290,18 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
             for (int r = 0; r < 4; ++r) fm[r] = 0;
         } else {
             if (__builtin_expect(pend, 0)) {   // uniform: the pass requested during the previous step
-                W8_T0(td0);
-                W8_CNT(pr, 10, 1);
-#ifdef W8_PROF
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the pass's wait for its entries (and the code requests ahead of them) on its own
-                W8_ADD(pr, 7, td0);
-#endif
                 pend = false;
                 w9_pass_finish(ps, nvalid, K, lane);
                 since = 0;
                 w9_bias(nvalid, bias);   // (the other waves' offers moved the bounds as well)
                 if (ccnt >= W8_TRIG || (ccnt > 0 && pb >= ptail)) {   // the next ones are waiting already (or the range ends)
-                    W8_CNT(pr, 11, 8);
                     w9_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
                     pend = true;
                 }
-                W8_ADD(pr, 5, td0);
             } else if (__builtin_expect(ccnt > 0 && pb >= ptail, 0)) {
                 // the wave's last two steps: what is parked does not wait for company -- its pass is under way while these steps are
                 // scanned, and the end of the range finds an empty ring nine times in ten (a pass worked off THERE is a trip to L2 the
                 // wave sits out, with the other seven waiting for it at the barrier behind: the wait was 8 % of the kernel)
-                W8_CNT(pr, 11, ccnt < 8 ? ccnt : 8);
                 wave_sync();
                 w9_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
                 pend = true;
@@ -377,11 +366,6 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
 #pragma unroll
             for (int r = 0; r < 4; ++r) x[r] = (qa[r][0] & qa[r][1]) & (qa[r][2] & qa[r][3]);
             u64 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
-#if defined(W8_KO) && (W8_KO & 1)
-            asm volatile("" :: "s"(anym));
-            anym = 0;   // knock-out build (wrong results by design): the filter's fast path alone
-#endif
-            W8_CNT(pr, 8, 1);
             if (__builtin_expect(first && coldmask != 0u, 0)) {   // uniform over the WORKGROUP: see above
                 const int r8 = (K + W8_NW - 1) / W8_NW;
                 static_for<8>([&](auto sc) {
@@ -422,12 +406,9 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
 #pragma unroll
                 for (int i = 0; i < 4; ++i) bias[i] = nb[i];
                 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
-                W8_CNT(pr, 12, 1);
             }
             first = false;
             if (__builtin_expect(anym != 0, 0)) {   // uniform; a step in ten once the bounds are tight
-                W8_T0(tc0);
-                W8_CNT(pr, 9, 1);
                 // the lane's four candidate flags; a list's last step masks the points past its end (they carry whatever was loaded)
                 bool c[4];
 #pragma unroll
@@ -470,7 +451,6 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
                         }
                     });
                     if (moved) {
-                        W8_CNT(pr, 12, 1);
                         // the step's fields were accumulated under the old bias: re-based on the new one before they are tested again
                         u32 nb[4];
                         w9_bias(nvalid, nb);
@@ -505,7 +485,6 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
                     ccnt += ntot;
                     // a pass is requested when eight points wait and none is in flight; it is worked off at the top of the next step
                     if (!pend && (ccnt >= W8_TRIG || pb >= ptail)) {
-                        W8_CNT(pr, 11, 8);
                         wave_sync();
                         w9_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
                         pend = true;
@@ -515,7 +494,6 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
                     for (int r = 0; r < 4; ++r) fm[r] = m[r];
                     overflow = true;
                 }
-                W8_ADD(pr, 4, tc0);
             }
         }
         // No room in the ring (a crowd the integer bound could not thin out), or the end of the range: ONE copy of the code that parks in
@@ -542,7 +520,6 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
                 }
                 const bool more = (fm[0] | fm[1] | fm[2] | fm[3]) != 0;
                 if (pend) {
-                    W8_CNT(pr, 10, 1);
                     pend = false;
                     w9_pass_finish(ps, nvalid, K, lane);
                     w9_bias(nvalid, bias);
@@ -570,11 +547,6 @@ static __device__ __forceinline__ void w9_scan_range(__amdgpu_buffer_rsrc_t code
 __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
                                                                  u32 *__restrict__ xq, int nranges)
 {
-    W9Prof pr;
-#ifdef W8_PROF
-    pr.zero();
-    const u64 tk0 = __builtin_readcyclecounter();
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const IndexView &ix = a.ix;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -617,8 +589,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const
         u32 pulled = 0;
         if (tid == 0 && qtried < nranges) pulled = atomicAdd(xq + qcur * 16, 1u);
         do {   // (one trip: `break` = this work item is finished)
-        W8_T0(ts0);
-        W8_CNT(pr, 14, 1);
         const int l = __builtin_amdgcn_readfirstlane((int)item_list[wi]);
         const u32 cnt = __builtin_amdgcn_readfirstlane(a.list_cnt[l]);
         const u32 ng = (cnt + 7u) / 8u;
@@ -664,8 +634,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const
         // (a chunk's byte offset pb * 8 stays below 2^31: lists of < 2^28 points)
         const uint8_t *cbase = ix.codes + (int64_t)readfirstlane64((u64)ix.list_codeoff[l]);
 
-        W8_ADD(pr, 1, ts0);
-        W8_T0(tb0);
         // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), two elements per thread: res[ii][t][s], 17 rows of eight per sub-quantizer
         {
             const int tb = tid & 511;
@@ -698,7 +666,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const
         };
         ldcw(cwa, 0);       // on its way while the residuals settle
         __syncthreads();
-        W8_ADD(pr, 13, tb0);   // (of the build: residuals up to the barrier)
         // (2) the f32 entries (index.jl:232-236: df = cb - r, sum += df * df for t ascending; no contraction; two queries per packed
         // instruction: the same IEEE operations element by element), to device memory by label; per-query maxima
         v4f ent[4][2];      // [codeword][queries 0 .. 3, 4 .. 7]
@@ -757,7 +724,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const
             }
         }
         __syncthreads();
-        W8_ADD(pr, 15, tb0);   // (of the build: up to the barrier behind the entries)
         // (3) quantise (quantize_tables_m8's rule: q = min(4095, floor(t * inv)), inv = 4095 / largest entry of the query) and write the two
         // copies: copy (cp + lane / 4) mod 2 of sub-quantizer ii -- the 8 lanes of a 16-byte store's service group write 8 different
         // four-bank groups (consecutive labels are 256 B apart: the same banks).
@@ -800,16 +766,9 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const
         }
         __syncthreads();   // tables complete (LDS copies; the f32 stores have left for L2: the barrier's release covers them)
 
-        W8_ADD(pr, 2, tb0);
-        W8_T0(tsc0);
         __builtin_amdgcn_s_setprio(W8_PRIO_SCAN);
-#if defined(W8_KO) && (W8_KO & 2)
-        if (K < 0)                    // knock-out build: table build only
-#endif
-        w9_scan_range(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr, pr);
+        w9_scan_range(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr);
         __builtin_amdgcn_s_setprio(W8_PRIO_REST);
-        W8_ADD(pr, 3, tsc0);
-        W8_T0(tm0);
 
         // ---- every wave has offered what it had: wave s < nvalid hands slot s of the pool over as it is -- the entries fill from index 0
         // (an offer takes the first empty one), the merge kernel behind pushes them through a selector in any order
@@ -826,18 +785,10 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8q8_scan_kernel(const
             }
             if (lane == 0) a.part_cnt[slot] = (u32)fc;
         }
-        W8_ADD(pr, 6, tm0);
         } while (false);
         __syncthreads();            // every wave is done with this item's state in LDS
         if (tid == 0) swi[0] = qtried < nranges ? resolve(pulled) : 0xFFFFFFFFu;
         __syncthreads();
         wi = __builtin_amdgcn_readfirstlane(swi[0]);
     }
-#ifdef W8_PROF
-    pr.c[0] = __builtin_readcyclecounter() - tk0;
-    if (lane == 0) {
-        u64 *dst = (u64 *)(gtabs + (size_t)gridDim.x * W9_GTAB_FLOATS);
-        for (int i = 0; i < 16; ++i) atomicAdd(dst + i, pr.c[i]);
-    }
-#endif
 }

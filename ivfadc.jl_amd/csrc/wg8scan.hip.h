@@ -28,15 +28,12 @@
 // scan_kernel; the work items are the same (list, group of <= 4 queries, chunk).
 #pragma once
 
-#ifndef W8_NWAVES
-#define W8_NWAVES 8
-#endif
 // Waves per workgroup.  Measured with more (round 6; the table build is laid out for 512 threads, further waves repeat the first ones' share --
 // the same values to the same places): TEN (640 threads at <= 96 registers) run one workgroup per CU -- a workgroup's waves spread 3-3-2-2
 // over the SIMDs, two of them would need six register sets on a SIMD -- 9.6 ms; TWELVE (<= 80 registers: the scan loop still holds no
 // spilled register, the candidate path 150) run two per CU and take 9.1 ms, 8.5 without candidates against 5.0: six waves per SIMD on the
 // same LDS are slower than four, whatever the guide's 2 cycles per ds_read_b64 leave free on paper.
-constexpr int W8_NW = W8_NWAVES;
+constexpr int W8_NW = 8;
 constexpr int W8_THREADS = 64 * W8_NW;
 constexpr int W8_ES = 3;                      // dwords per parked point: code bytes (2), list position
 constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (4 copies x 8 sub-quantizers x 8 bytes)
@@ -57,24 +54,6 @@ struct W8Lds {
 };
 static_assert(W8Lds::END <= 80u * 1024u, "two workgroups per CU");
 static_assert((W8Lds::HARD & 7u) == 0 && (W8Lds::STHR & 7u) == 0 && (W8Lds::POOL & 7u) == 0, "8-byte bounds");
-
-// W8_PROF (diagnostic builds only: tools/build_variant.sh prof -DW8_PROF): cycle and event counters per wave, summed into 16 words behind the
-// f32 table blocks.  0 item loop, 1 setup, 2 build, 3 scan, 4 candidate path, 5 drains, 6 merge, 7 of the drains: the wait for memory; 8 steps, 9 steps with candidates, 10 drains,
-// 11 drained points, 12 crowd bounds, 13 refreshes that moved a bound, 14 items
-#ifdef W8_PROF
-struct W8Prof {
-    u64 c[16];
-    __device__ __forceinline__ void zero() { for (int i = 0; i < 16; ++i) c[i] = 0; }
-};
-#define W8_T0(name) const u64 name = __builtin_readcyclecounter()
-#define W8_ADD(pr, i, t0) (pr).c[i] += __builtin_readcyclecounter() - (t0)
-#define W8_CNT(pr, i, n) (pr).c[i] += (u64)(n)
-#else
-struct W8Prof {};
-#define W8_T0(name)
-#define W8_ADD(pr, i, t0)
-#define W8_CNT(pr, i, n)
-#endif
 
 static __device__ __forceinline__ u32 w8_perm(u32 s0, u32 s1, u32 sel)
 {
@@ -217,21 +196,11 @@ struct W8Pass {
 // cache policy of the code stream's requests (aux of raw_buffer_load).  Measured with 2 (nt, "streaming": the lines are not kept in L2 ahead
 // of the work items' f32 tables, which the passes gather from): 16 384 x w = 8 scan 6.15 -> 7.35 ms, 2048 x w = 8 1.15 -> 1.31 -- the four
 // or five groups that stream the same list side by side live on each other's lines in L2 / the memory-side cache.  Default policy.
-#ifndef W8_STREAM_AUX
-#define W8_STREAM_AUX 0
-#endif
-#ifndef W8_TRIG
-#define W8_TRIG 8        // parked points that trigger a pass
-#endif
-#ifndef W8_REFRESH
-#define W8_REFRESH 8     // steps between looks at the workgroup's shared bounds
-#endif
-#ifndef W8_PRIO_SCAN
-#define W8_PRIO_SCAN 3
-#endif
-#ifndef W8_PRIO_REST
-#define W8_PRIO_REST 0
-#endif
+constexpr int W8_STREAM_AUX = 0;
+constexpr int W8_TRIG = 8;        // parked points that trigger a pass
+constexpr int W8_REFRESH = 8;     // steps between looks at the workgroup's shared bounds
+constexpr int W8_PRIO_SCAN = 3;   // wave priority while the code stream is scanned, and after it
+constexpr int W8_PRIO_REST = 0;
 constexpr int W8_RING = 32;    // parked points per wave (a ring: entries head .. head + cnt - 1 mod 32)
 
 static __device__ __forceinline__ void w8_pass_issue(W8Pass &ps, u32 cbuf_addr, int &head, int &cnt, __amdgpu_buffer_rsrc_t gt, int lane)
@@ -253,7 +222,7 @@ static __device__ __forceinline__ void w8_pass_issue(W8Pass &ps, u32 cbuf_addr, 
 
 // Works a pass off.  (Measured and dropped: everything the pass needs from LDS -- constants, bounds, a snapshot of every slot's pool, the
 // bias arithmetic's operands -- requested in one go ahead of the running sums, the bias computed from registers: 16 384 x w = 8
-// 5.87 -> 5.91 ms, w = 1 1.38 -> 1.44.  The pass does not wait for memory -- W8_PROF: 260 of its 7 700 cycles -- it is ~400 dependent
+// 5.87 -> 5.91 ms, w = 1 1.38 -> 1.44.  The pass does not wait for memory -- 260 of its 7 700 cycles, by cycle counters -- it is ~400 dependent
 // instructions on a SIMD it shares with three scanning waves.)
 static __device__ __forceinline__ void w8_pass_finish(const W8Pass &ps, int nvalid, int K, int lane)
 {
@@ -302,7 +271,7 @@ static __device__ __attribute__((noinline)) u32 w8_kth_sum4(u32 v0, u32 v1, u32 
 }
 
 static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t codes, u32 p0, u32 p1, int nvalid, int K, int wv, int lane,
-                                                     v4u ca, v4u cb, __amdgpu_buffer_rsrc_t gt, W8Prof &pr)
+                                                     v4u ca, v4u cb, __amdgpu_buffer_rsrc_t gt)
 {
     // A step of a wave is 256 points: four per lane in two 16-byte registers sets, ca (points pb + 2 lane, + 1) and cb (pb + 128 + 2 lane,
     // + 1), requested by the caller for the first step.  The code stream comes through a buffer resource over the list: the lane's offset
@@ -364,27 +333,18 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
             for (int r = 0; r < 4; ++r) fm[r] = 0;
         } else {
             if (__builtin_expect(pend, 0)) {   // uniform: the pass requested during the previous step
-                W8_T0(td0);
-                W8_CNT(pr, 10, 1);
-#ifdef W8_PROF
-                asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the pass's wait for its entries (and the code requests ahead of them) on its own
-                W8_ADD(pr, 7, td0);
-#endif
                 pend = false;
                 w8_pass_finish(ps, nvalid, K, lane);
                 since = 0;
                 w8_bias(nvalid, bias);   // (the other waves' offers moved the bounds as well)
                 if (ccnt >= W8_TRIG || (ccnt > 0 && pb >= ptail)) {   // the next ones are waiting already (or the range ends)
-                    W8_CNT(pr, 11, 8);
                     w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
                     pend = true;
                 }
-                W8_ADD(pr, 5, td0);
             } else if (__builtin_expect(ccnt > 0 && pb >= ptail, 0)) {
                 // the wave's last two steps: what is parked does not wait for company -- its pass is under way while these steps are
                 // scanned, and the end of the range finds an empty ring nine times in ten (a pass worked off THERE is a trip to L2 the
                 // wave sits out, with the other seven waiting for it at the barrier behind: the wait was 8 % of the kernel)
-                W8_CNT(pr, 11, ccnt < 8 ? ccnt : 8);
                 wave_sync();
                 w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
                 pend = true;
@@ -409,17 +369,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 rw[2 * h + 1][0] = __builtin_amdgcn_perm(cx.w, cx.z, rsel0);
                 rw[2 * h + 1][1] = __builtin_amdgcn_perm(cx.w, cx.z, rsel1);
                 asm volatile("" : "+v"(rw[2 * h][0]), "+v"(rw[2 * h][1]), "+v"(rw[2 * h + 1][0]), "+v"(rw[2 * h + 1][1]), "+v"(cx));
-#if defined(W8_KO) && (W8_KO & 8)
-                asm volatile("" :: "s"(pnext));          // knock-out build: no code stream (every step scans the first step's bytes)
-#else
                 cx = __builtin_amdgcn_raw_buffer_load_b128(codes, lane16, (int)(pnext * 8u), W8_STREAM_AUX);
-#endif
-#if defined(W8_KO) && (W8_KO & 16)
-                // knock-out build: the code stream alone (no table lookups: the fields are made of the bytes themselves)
-                qa[2 * h][0] = bias[0] + rw[2 * h][0]; qa[2 * h][1] = bias[1] + rw[2 * h][1];
-                qa[2 * h + 1][0] = bias[0] + rw[2 * h + 1][0]; qa[2 * h + 1][1] = bias[1] + rw[2 * h + 1][1];
-                return;
-#endif
                 // all sixteen gathers of the half are issued before the first add (left alone the compiler waits after every second read)
                 v2u ev[2][8];
                 static_for<2>([&](auto rc) {
@@ -450,11 +400,6 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 #pragma unroll
             for (int r = 0; r < 4; ++r) x[r] = qa[r][0] & qa[r][1];
             u64 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
-#if defined(W8_KO) && (W8_KO & 1)
-            asm volatile("" :: "s"(anym));
-            anym = 0;   // knock-out build (wrong results by design): the filter's fast path alone
-#endif
-            W8_CNT(pr, 8, 1);
             if (__builtin_expect(first && coldmask != 0u, 0)) {   // uniform over the WORKGROUP: see above
                 const int r8 = (K + W8_NW - 1) / W8_NW;
                 static_for<4>([&](auto sc) {
@@ -495,12 +440,9 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 bias[0] = nb[0];
                 bias[1] = nb[1];
                 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
-                W8_CNT(pr, 12, 1);
             }
             first = false;
             if (__builtin_expect(anym != 0, 0)) {   // uniform; a step in ten once the bounds are tight
-                W8_T0(tc0);
-                W8_CNT(pr, 9, 1);
                 // the lane's four candidate flags; a list's last step masks the points past its end (they carry whatever was loaded)
                 bool c[4];
 #pragma unroll
@@ -543,7 +485,6 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                         }
                     });
                     if (moved) {
-                        W8_CNT(pr, 12, 1);
                         // the step's fields were accumulated under the old bias: re-based on the new one before they are tested again
                         u32 nb[2];
                         w8_bias(nvalid, nb);
@@ -578,7 +519,6 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                     ccnt += ntot;
                     // a pass is requested when eight points wait and none is in flight; it is worked off at the top of the next step
                     if (!pend && (ccnt >= W8_TRIG || pb >= ptail)) {
-                        W8_CNT(pr, 11, 8);
                         wave_sync();
                         w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
                         pend = true;
@@ -588,7 +528,6 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                     for (int r = 0; r < 4; ++r) fm[r] = m[r];
                     overflow = true;
                 }
-                W8_ADD(pr, 4, tc0);
             }
         }
         // No room in the ring (a crowd the integer bound could not thin out), or the end of the range: ONE copy of the code that parks in
@@ -615,7 +554,6 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 }
                 const bool more = (fm[0] | fm[1] | fm[2] | fm[3]) != 0;
                 if (pend) {
-                    W8_CNT(pr, 10, 1);
                     pend = false;
                     w8_pass_finish(ps, nvalid, K, lane);
                     w8_bias(nvalid, bias);
@@ -643,11 +581,6 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
                                                                  u32 *__restrict__ xq, int nranges)
 {
-    W8Prof pr;
-#ifdef W8_PROF
-    pr.zero();
-    const u64 tk0 = __builtin_readcyclecounter();
-#endif
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const IndexView &ix = a.ix;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -690,8 +623,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         u32 pulled = 0;
         if (tid == 0 && qtried < nranges) pulled = atomicAdd(xq + qcur * 16, 1u);
         do {   // (one trip: `break` = this work item is finished)
-        W8_T0(ts0);
-        W8_CNT(pr, 14, 1);
         const int l = __builtin_amdgcn_readfirstlane((int)item_list[wi]);
         const u32 cnt = __builtin_amdgcn_readfirstlane(a.list_cnt[l]);
         const u32 ng = (cnt + 3u) / 4u;
@@ -737,8 +668,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         // (a chunk's byte offset pb * 8 stays below 2^31: lists of < 2^28 points)
         const uint8_t *cbase = ix.codes + (int64_t)readfirstlane64((u64)ix.list_codeoff[l]);
 
-        W8_ADD(pr, 1, ts0);
-        W8_T0(tb0);
         // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), one element per thread: res[ii][t][s], 17 rows of four per sub-quantizer
         {
             const int tb = tid & 511, i = tb >> 2, s = tb & 3;
@@ -767,17 +696,9 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         };
         ldcw(cwa, 0);       // on its way while the residuals settle
         __syncthreads();
-        W8_ADD(pr, 13, tb0);   // (of the build: residuals up to the barrier)
         // (2) the f32 entries (index.jl:232-236: df = cb - r, sum += df * df for t ascending; no contraction; two queries per packed
         // instruction: the same IEEE operations element by element), to device memory by label; per-query maxima
         v4f ent[4];
-#if defined(W8_KO) && (W8_KO & 4)
-        if (K > 0) {                  // knock-out build: no table build (the scan runs on made-up entries)
-#pragma unroll
-            for (int k = 0; k < 4; ++k) ent[k] = (v4f){(float)(k + cg), (float)(k + 2 * cg), (float)cg, 1.0f};
-            if (tid < 4) smax[tid] = __float_as_uint(600.0f);
-        } else
-#endif
         {
             v2f sum[4][2];
 #pragma unroll
@@ -831,7 +752,6 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
             }
         }
         __syncthreads();
-        W8_ADD(pr, 15, tb0);   // (of the build: up to the barrier behind the entries)
         // (3) quantise (quantize_tables_m8's rule: q = min(4095, floor(t * inv)), inv = 4095 / largest entry of the query) and write the four
         // copies: copy (cp + lane / 4) mod 4 of sub-quantizer ii -- the 16 lanes of a store's service group write 16 different bank pairs
         // (consecutive labels are 256 B apart: the same banks).
@@ -874,16 +794,9 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         }
         __syncthreads();   // tables complete (LDS copies; the f32 stores have left for L2: the barrier's release covers them)
 
-        W8_ADD(pr, 2, tb0);
-        W8_T0(tsc0);
         __builtin_amdgcn_s_setprio(W8_PRIO_SCAN);
-#if defined(W8_KO) && (W8_KO & 2)
-        if (K < 0)                    // knock-out build: table build only
-#endif
-        w8_scan_range(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr, pr);
+        w8_scan_range(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr);
         __builtin_amdgcn_s_setprio(W8_PRIO_REST);
-        W8_ADD(pr, 3, tsc0);
-        W8_T0(tm0);
 
         // ---- every wave has offered what it had: wave s < nvalid hands slot s of the pool over as it is -- the entries fill from index 0
         // (an offer takes the first empty one), the merge kernel behind pushes them through a selector in any order
@@ -900,18 +813,10 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
             }
             if (lane == 0) a.part_cnt[slot] = (u32)fc;
         }
-        W8_ADD(pr, 6, tm0);
         } while (false);
         __syncthreads();            // every wave is done with this item's state in LDS
         if (tid == 0) swi[0] = qtried < nranges ? resolve(pulled) : 0xFFFFFFFFu;
         __syncthreads();
         wi = __builtin_amdgcn_readfirstlane(swi[0]);
     }
-#ifdef W8_PROF
-    pr.c[0] = __builtin_readcyclecounter() - tk0;
-    if (lane == 0) {
-        u64 *dst = (u64 *)(gtabs + (size_t)gridDim.x * W8_GTAB_FLOATS);
-        for (int i = 0; i < 16; ++i) atomicAdd(dst + i, pr.c[i]);
-    }
-#endif
 }

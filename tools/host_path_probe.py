@@ -1,7 +1,7 @@
 """Host-to-host rates of the reference's calling patterns on the SIFT1M shape (knn_search takes and returns HOST arrays, index.jl:261-265):
 blocking ivfadc_search per batch and ivfadc_search_batches over 16 batches, with pageable arrays, caller-registered arrays
 (ivfadc_host_register) and library-allocated page-locked arrays (ivfadc_host_alloc), plus where the host time went (ivfadc_get_host_stats).
-Run with IVFADC_HOST_LEGACY=1 for round 4's copy chain.  Usage: host_path_probe.py [nq=1024]"""
+Usage: host_path_probe.py [nq=1024]"""
 import sys, time, os, ctypes as C
 import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -18,7 +18,6 @@ idx = pkg.IVFADCIndex.from_arrays(cent, cbs, labels, off, rng.integers(0, 256, (
 L = nat.lib()
 nb = 16
 qsrc = rng.random((nb * nq, d), dtype=np.float32)
-print("mode: %s" % ("LEGACY copy chain (IVFADC_HOST_LEGACY)" if os.environ.get("IVFADC_HOST_LEGACY") else "kernel ingest + results written in place"))
 
 
 def hstats():

@@ -13,7 +13,6 @@ K = int(sys.argv[3]) if len(sys.argv) > 3 else 10
 if os.environ.get("LB_N"):
     cfg["n"] = int(os.environ["LB_N"])
 idx, _ = bench.build_synth(pkg, cfg, 0)
-idx.set_tuning(0, 0)   # reads IVFADC_FORCE_PG
 q = np.random.default_rng(11).standard_normal((nq, cfg["d"]), dtype=np.float32)
 for mode in (0, 1):
     idx.set_table_mode(mode)

@@ -1,5 +1,4 @@
-"""push! latency: one point appended then one small search, repeated -- in place on the device vs the
-re-layout path (IVFADC_NO_INPLACE_APPEND=1 in the environment).  SIFT1M-shape random lists.
+"""push! latency: one point appended (in place on the device) then one small search, repeated.  SIFT1M-shape random lists.
 usage: python tools/push_probe.py [n] [reps]"""
 import os
 import sys
@@ -43,7 +42,6 @@ def main():
         t_search += t2 - t1
     st = idx.get_stats()
     print({"n": n, "reps": reps, "inplace_appends": st["inplace_appends"],
-           "mode": "relayout" if os.environ.get("IVFADC_NO_INPLACE_APPEND") else "inplace",
            "push_us": round(1e6 * t_push / reps, 1), "search_after_push_us": round(1e6 * t_search / reps, 1)})
 
 
