@@ -102,7 +102,13 @@ int ivfadc_get_quantizers_u16(ivfadc_t *h, float *centroids, float *codebooks, v
  *   data d x n; out_centroids d x kc; out_codebooks m blocks of dsub x k (the layout ivfadc_create takes; labels are
  *   0..k-1).  Runs on the device: k-means++ seeding, exact-distance assignment (the search path's coarse kernel), and
  *   order-independent fixed-point sums, so the result is deterministic for a given seed.
- * Constructor checks of index.jl:118-123 (kc >= 2, k <= n, 1 <= m <= d, maxiter > 0) -> IVFADC_ERR_ASSERT; then 1 <= k <= 65536.   */
+ *   Guarantee: a centre that stops changing is the Float32-rounded mean of its points up to the fixed-point quantum
+ *   2^(e-61) of its stage, where n * max|x| < 2^e over that stage's data (|c - mean| <= ulp(c)/2 + quantum); the
+ *   quantum follows the data's binary magnitude, so training x * 2^j gives the quantizers of x times 2^j while the
+ *   Float32 arithmetic stays normal.
+ * Constructor checks of index.jl:118-123 (kc >= 2, k <= n, 1 <= m <= d, maxiter > 0) -> IVFADC_ERR_ASSERT; then 1 <= k <= 65536.
+ * Data with a NaN or infinite component -> IVFADC_ERR_INVALID, before any device call (as ivfadc_create refuses such
+ * quantizers).                                                                                                         */
 int ivfadc_train(int device, int d, int64_t n, const float *data, int kc, int k, int m,
                  int coarse_maxiter, int quant_maxiter, uint64_t seed,
                  float *out_centroids, float *out_codebooks);

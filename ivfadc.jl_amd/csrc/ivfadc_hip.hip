@@ -2059,7 +2059,8 @@ int kmeans_dev(TrainCtx &t, const float *d_x, int64_t n, int dcols, int ld, int 
                            t.partial.as<double>(), nblk, (u64)seed, j, d_centres);
         HIP_TRY(hipGetLastError());
     }
-    // ---- fixed-point scale: |sum| <= n * maxabs must stay below 2^62
+    // ---- fixed-point scale 2^(61 - e), n * maxabs < 2^e exactly: |sum| <= n * maxabs * scale + n / 2 < 2^62, and the quantum
+    // 1 / scale follows the data's binary magnitude, so training x * 2^j gives the centres of x times 2^j (all-zero data: e = 0)
     const int mb = 1024;
     TRY(t.blockmax.ensure((size_t)mb * 4));
     hipLaunchKernelGGL(tr_maxabs_kernel, dim3(mb), dim3(256), 0, t.stream, d_x, n, dcols, ld, t.blockmax.as<float>());
@@ -2067,10 +2068,11 @@ int kmeans_dev(TrainCtx &t, const float *d_x, int64_t n, int dcols, int ld, int 
     std::vector<float> bm(mb);
     HIP_TRY(hipMemcpyAsync(bm.data(), t.blockmax.p, (size_t)mb * 4, hipMemcpyDeviceToHost, t.stream));
     HIP_TRY(hipStreamSynchronize(t.stream));
-    double maxabs = 1e-30;
+    double maxabs = 0.0;
     for (float v : bm) maxabs = std::max(maxabs, (double)v);
-    const int ex = 61 - (int)std::ceil(std::log2((double)n * maxabs + 1.0));
-    const double scale = std::ldexp(1.0, std::max(-60, std::min(ex, 60)));
+    int ex = 0;
+    std::frexp((double)n * maxabs, &ex);
+    const double scale = std::ldexp(1.0, 61 - ex);
 
     // ---- Lloyd
     const int64_t chunk = std::max<int64_t>(256, (int64_t)(((size_t)1 << 30) / ((size_t)k * 4)));
@@ -2152,6 +2154,10 @@ int train_impl(int device, int d, int64_t n, const float *data, int kc, int k, i
     if (d % m != 0) return fail(IVFADC_ERR_INVALID, "d %% m != 0 is not supported");
     if (k < 1 || k > 65536) return fail(IVFADC_ERR_INVALID, "k must be in 1..65536 (UInt8 or UInt16 codes)");
     if (kc > n) return fail(IVFADC_ERR_INVALID, "kc > n");
+    // the fixed-point scale and every distance assume finite data (fmaxf drops a NaN, an Inf has no binary exponent)
+    for (int64_t e = 0; e < n * d; ++e)
+        if (!std::isfinite(data[e]))
+            return fail(IVFADC_ERR_INVALID, "training data is not finite: point %lld, component %d", (long long)(e / d), (int)(e % d));
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (device < 0 || device >= ndev) return fail(IVFADC_ERR_HIP, "no such HIP device %d", device);

@@ -126,7 +126,8 @@ typedef struct {
     uint64_t synth_seed;
 } ora_lists_t;
 
-static inline uint64_t ora_mix64(uint64_t x)
+/* also used by train_oracle.c */
+uint64_t ora_mix64(uint64_t x)
 {
     x ^= x >> 30; x *= 0xBF58476D1CE4E5B9ull;
     x ^= x >> 27; x *= 0x94D049BB133111EBull;

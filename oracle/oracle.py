@@ -1,4 +1,4 @@
-"""ctypes front-end of the CPU oracle (oracle/ivfadc_oracle.c).
+"""ctypes front-end of the CPU oracle (oracle/ivfadc_oracle.c, oracle/train_oracle.c).
 
 TEST INFRASTRUCTURE ONLY: imported by tests/, __graft_entry__.smoke() and
 bench.py's cpu_baseline leg.  The product package never imports this module.
@@ -15,8 +15,8 @@ _SO = os.path.join(_HERE, "liboracle.so")
 
 
 def build(force=False):
-    src = os.path.join(_HERE, "ivfadc_oracle.c")
-    if force or not os.path.exists(_SO) or os.path.getmtime(_SO) < os.path.getmtime(src):
+    srcs = [os.path.join(_HERE, f) for f in ("ivfadc_oracle.c", "train_oracle.c", "Makefile")]
+    if force or not os.path.exists(_SO) or any(os.path.getmtime(_SO) < os.path.getmtime(s) for s in srcs):
         subprocess.check_call(["make", "-C", _HERE, "-B", "liboracle.so"], stdout=subprocess.DEVNULL)
     return _SO
 
@@ -41,6 +41,9 @@ def lib():
         L.ora_synth_fill.argtypes = [C.c_uint64, C.c_uint64, C.c_uint64, C.c_int, u8p]
         L.ora_synth_fill.restype = None
         L.ora_max_threads.restype = C.c_int
+        L.ora_train.argtypes = [C.c_int, C.c_int64, fp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_uint64, fp, fp,
+                                i32p, i32p]
+        L.ora_train.restype = C.c_int
         _lib = L
     return _lib
 
@@ -125,6 +128,28 @@ def synth_fill(seed, g0, n, m):
     out = np.zeros((n, m), np.uint8)
     lib().ora_synth_fill(C.c_uint64(seed), C.c_uint64(g0), C.c_uint64(n), int(m), _p(out, C.c_uint8))
     return out
+
+
+def train(data, kc, k, m, coarse_maxiter=25, quant_maxiter=25, seed=0):
+    """CPU restatement of ivfadc_train (train_oracle.c), bit for bit.  data (n, d) float32 ->
+    centroids (kc, d), codebooks (m, k, dsub), iters (1 + m,) int32 Lloyd iterations run and
+    converged (1 + m,) bool fixed point reached -- coarse stage first, then sub-space 0..m-1."""
+    x = np.ascontiguousarray(data, np.float32)
+    n, d = x.shape
+    cent = np.zeros((kc, d), np.float32)
+    cbs = np.zeros((m, k, d // max(m, 1)), np.float32)
+    iters = np.zeros(1 + m, np.int32)
+    conv = np.zeros(1 + m, np.int32)
+    rc = lib().ora_train(d, n, _p(x, C.c_float), int(kc), int(k), int(m), int(coarse_maxiter), int(quant_maxiter),
+                         C.c_uint64(int(seed) % (1 << 64)), _p(cent, C.c_float), _p(cbs, C.c_float),
+                         _p(iters, C.c_int32), _p(conv, C.c_int32))
+    if rc == 1:
+        raise AssertionError("oracle train: invalid shape or parameters")
+    if rc == 3:
+        raise ValueError("oracle train: non-finite training data")
+    if rc != 0:
+        raise MemoryError("oracle train: rc=%d" % rc)
+    return cent, cbs, iters, conv.astype(bool)
 
 
 def max_threads():

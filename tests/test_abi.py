@@ -39,6 +39,25 @@ def test_argument_validation_needs_no_gpu(native):
     assert rc == 1
 
 
+@pytest.mark.parametrize("bad", [np.nan, np.inf, -np.inf])
+@pytest.mark.parametrize("where", [0, -1])
+def test_trainer_refuses_non_finite_data_without_gpu(native, bad, where):
+    """ivfadc_train checks its data before any device call, as ivfadc_create checks its quantizers: fmaxf would drop a
+    NaN from the fixed-point scale and an Inf has no binary exponent."""
+    lib = native.load_library()
+    x = np.random.default_rng(0).random((300, 4), dtype=np.float32)
+    x.reshape(-1)[where] = bad
+    cent = np.zeros((4, 4), np.float32)
+    cbs = np.zeros((2, 8, 2), np.float32)
+    fp = C.POINTER(C.c_float)
+    rc = lib.ivfadc_train(0, 4, 300, x.ctypes.data_as(fp), 4, 8, 2, 25, 25, C.c_uint64(0), cent.ctypes.data_as(fp),
+                          cbs.ctypes.data_as(fp))
+    msg = lib.ivfadc_last_error()
+    assert rc == 2, (rc, msg)                                # IVFADC_ERR_INVALID
+    point = 299 if where == -1 else 0
+    assert b"not finite" in msg and (b"point %d," % point) in msg, msg
+
+
 def test_no_cpu_fallback(native):
     import torch
     if torch.cuda.is_available():

@@ -4,6 +4,7 @@ import pytest
 
 import helpers
 import torch_kmeans
+import train_ref
 from oracle import oracle as ora
 
 pytestmark = pytest.mark.gpu
@@ -127,3 +128,94 @@ def test_trainer_quality_at_the_benchmark_shape_vs_sklearn(native):
         err_sk += float(KMeans(n_clusters=k, init="k-means++", n_init=1, max_iter=25, algorithm="lloyd", random_state=i).fit(sub).inertia_)
     assert err_nat <= 1.10 * err_sk, "PQ error %.4g vs sklearn %.4g" % (err_nat, err_sk)
     print("trainer vs sklearn: coarse inertia %.4g / %.4g, PQ error %.4g / %.4g" % (inertia_nat, inertia_sk, err_nat, err_sk))
+
+
+# ---- bit-exact pinning against the CPU restatement (oracle/train_oracle.c) ------------------------------------------
+
+def _train_data(kind, seed, n, d):
+    rng = np.random.default_rng(seed)
+    if kind == "uniform":
+        return rng.random((n, d), dtype=np.float32)
+    if kind == "normal":                                    # negative fixed-point sums
+        return rng.standard_normal((n, d)).astype(np.float32)
+    if kind == "mixture":
+        return _mixture(seed, n, d, 40, 0.05)
+    if kind == "zeros":                                     # maxabs = 0; k-means++ takes the total <= 0 branch
+        return np.zeros((n, d), np.float32)
+    if kind == "repeated":                                  # one point n times: total <= 0 branch
+        return np.tile(rng.standard_normal((1, d)).astype(np.float32), (n, 1))
+    if kind == "few":                                       # 300 distinct points < k: empty clusters restart every iteration
+        return rng.random((300, d), dtype=np.float32)[rng.integers(0, 300, n)]
+    if kind == "mixed":                                     # columns of magnitude 1e4 next to 1e-4
+        return (rng.standard_normal((n, d)) * np.where(np.arange(d) % 2 == 0, 1e4, 1e-4)).astype(np.float32)
+    raise ValueError(kind)
+
+
+def _bits(a):
+    return np.ascontiguousarray(a, np.float32).view(np.uint32)
+
+
+# every value of every axis at least once: n % 256 tails (300, 4097) and the strided k-means++ sample (40 000 > S);
+# dsub 4 / 5 / 1 / 16 / 6 (5, 1 and 6 leave sub-space windows that are not 16-byte aligned: coarse_dist_kernel's scalar
+# loads); k > 256 (UInt16 labels) and k = 8192 at n = 40 000 (two Lloyd assignment chunks); maxiter 1 / 2 / 25
+@pytest.mark.parametrize("kind,n,d,m,kc,k,maxiter,seed", [
+    ("uniform", 300, 32, 8, 2, 2, 25, 0),
+    ("normal", 4097, 50, 10, 64, 16, 25, 3),
+    ("mixture", 4097, 12, 12, 64, 256, 2, 2**64 - 1),
+    ("mixture", 40000, 128, 8, 1024, 256, 1, 0),
+    ("uniform", 40000, 32, 8, 2, 8192, 2, 3),
+    ("few", 4097, 96, 16, 64, 1024, 25, 0),
+    ("zeros", 300, 32, 8, 2, 16, 25, 3),
+    ("repeated", 300, 50, 10, 2, 16, 25, 2**64 - 1),
+    ("mixed", 4097, 32, 8, 64, 256, 25, 3),
+])
+def test_trainer_matches_cpu_restatement_bit_for_bit(native, kind, n, d, m, kc, k, maxiter, seed):
+    x = _train_data(kind, seed, n, d)
+    cent, cbs, _ = native.trainer.train_ivfadc_hip(x, kc, k, m, maxiter, maxiter, seed=seed)
+    ecent, ecbs, _, _ = ora.train(x, kc, k, m, maxiter, maxiter, seed)
+    assert np.array_equal(_bits(cent), _bits(ecent)), "centroids differ in %d of %d values" % (
+        int((_bits(cent) != _bits(ecent)).sum()), cent.size)
+    assert np.array_equal(_bits(cbs), _bits(ecbs)), "codebooks differ in %d of %d values" % (
+        int((_bits(cbs) != _bits(ecbs)).sum()), cbs.size)
+
+
+@pytest.mark.parametrize("e", [-40, -20, 20, 40])
+def test_trainer_commutes_with_power_of_two_scaling(native, e):
+    """train(x * 2^e) == train(x) * 2^e bit for bit: the fixed-point quantum follows the data's binary exponent, and
+    every Float32 / double operation of the trainer is exact under a power-of-two scaling while its results stay
+    normal.  The data (|x| < 2^5) keep them so for |e| <= 40: at the trained quantizer the smallest nonzero squared
+    difference (x - c)^2 is ~2^-42 and the largest distance ~2^11, i.e. 2^-122 and 2^91 after scaling by 2^(2e)
+    (Float32 normals: 2^-126 .. 2^128); the premise is asserted below."""
+    rng = np.random.default_rng(21)
+    n, d, m, kc, k = 4097, 32, 8, 16, 16
+    c = rng.random((12, d)) * 16.0
+    x = (c[rng.integers(0, 12, n)] + rng.standard_normal((n, d))).astype(np.float32)
+    cent, cbs, _ = native.trainer.train_ivfadc_hip(x, kc, k, m, 25, 25, seed=3)
+    xs, subs = train_ref.stages(x, cent, m)
+    for pts, cen in [(xs, cent)] + [(subs[i], cbs[i]) for i in range(m)]:
+        t = pts[:, None, :] - cen[None]
+        t2 = t * t
+        assert t2[t2 > 0].min() >= 2.0 ** (-126 + 80) and t2.sum(-1).max() < 2.0 ** (128 - 80 - 1)
+    xe = np.ldexp(x, e).astype(np.float32)
+    assert np.array_equal(np.ldexp(xe, -e).astype(np.float32), x)          # the scaling itself is exact
+    scent, scbs, _ = native.trainer.train_ivfadc_hip(xe, kc, k, m, 25, 25, seed=3)
+    assert np.array_equal(_bits(scent), _bits(np.ldexp(cent, e).astype(np.float32))), "centroids, e = %d" % e
+    assert np.array_equal(_bits(scbs), _bits(np.ldexp(cbs, e).astype(np.float32))), "codebooks, e = %d" % e
+
+
+@pytest.mark.parametrize("scale", [1.0, 1e-18])
+def test_trainer_output_is_a_float64_lloyd_fixed_point(native, scale):
+    """On a well-separated mixture, with maxiter chosen so that every stage reaches its fixed point (the restatement
+    reports it), every centroid and every codeword is the float64 mean of its cluster within half a Float32 ulp plus
+    the fixed-point quantum (tests/train_ref.py:check_float64_means).  At 1e-18, n * max|x| < 1."""
+    n, d, m, kc, k, maxiter = 4097, 16, 4, 8, 16, 100
+    rng = np.random.default_rng(8)
+    centres = rng.random((8, d)) * 4.0
+    x = ((centres[rng.integers(0, 8, n)] + 0.05 * rng.standard_normal((n, d))) * scale).astype(np.float32)
+    _, _, iters, conv = ora.train(x, kc, k, m, maxiter, maxiter, 5)
+    assert conv.all(), iters
+    cent, cbs, _ = native.trainer.train_ivfadc_hip(x, kc, k, m, maxiter, maxiter, seed=5)
+    xs, subs = train_ref.stages(x, cent, m)
+    train_ref.check_float64_means(xs, cent, "coarse")
+    for i in range(m):
+        train_ref.check_float64_means(subs[i], cbs[i], "sub-space %d" % i)
