@@ -5,8 +5,8 @@ batch 16384) and the HD text-embedding shape (n=1e7, d=768, kc=4096, m=48, w=8, 
 
 The index is synthesised on the device (`ivfadc_synth_lists`: counter-based code bytes the oracle can replay for
 any probed list, ids = canonical position), exactly as bench.py builds these shapes.  Every test checks
-  * the automatic plan against the CPU oracle on >= 64 sampled queries: ids bit-exact, Float32 distances within
-    1e-4 relative (the north_star tolerance; reference semantics: src/index.jl:204-273);
+  * the automatic plan against the CPU oracle on >= 64 sampled queries: ids bit-exact, Float32 distances identical
+    bit for bit (reference semantics: src/index.jl:204-273);
   * the size-independent properties: full counts, ascending distances, distinct ids, ids inside [0, n);
   * the OTHER scan plan (forced) and the second, selection-free GPU implementation of the coarse stage (exact VALU
     kernel instead of the MFMA filter) agree with the automatic plan bit for bit;
@@ -61,7 +61,7 @@ def oracle_sample(o, qs, got, K, w, nsample, seed, what):
     rng = np.random.default_rng(seed)
     pick = np.sort(rng.choice(qs.shape[0], nsample, replace=False))
     exp = o.knn_search(qs[pick], K, w, nthreads=ora.max_threads())
-    helpers.assert_same_results(tuple(a[pick] for a in got), exp, rtol=1e-4, what=what)
+    helpers.assert_same_results(tuple(a[pick] for a in got), exp, what=what)
     # the float order of the HIP path is the oracle's: distances are in fact identical bit for bit
     assert np.array_equal(got[1][pick], exp[1]), what + ": distances not bit-identical"
 

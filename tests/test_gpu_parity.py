@@ -1,7 +1,10 @@
 """GPU parity tests: the HIP path (through the C ABI) against the CPU oracle on the same
-seeded inputs.  Bar: neighbour ids bit-exact, Float32 distances within 1e-4 relative
-(BASELINE.json north_star); in practice the float order is identical and distances match
-bit for bit, which the tests also record."""
+seeded inputs.  Bar: neighbour ids bit-exact and Float32 distances bit-identical: every
+result's sum is redone in the reference's order, and helpers.assert_same_results asserts
+the distance bits at every call site (BASELINE.json's north_star asks for 1e-4 relative
+only)."""
+import os
+
 import numpy as np
 import pytest
 
@@ -720,6 +723,74 @@ def test_delete_pop_pushfirst_in_place_on_device(native):
         native.pop(gidx)
 
 
+@pytest.mark.gpu
+def test_ids_in_the_upper_half_of_uint32(native, tmp_path):
+    """Stored ids >= 2^31, 0xFFFFFFFF among them (an id is an unsigned 32-bit number everywhere: keys, payloads, the compaction and
+    shift kernels, the file): search, ivfadc_delete_ids, ivfadc_shift_ids and a save / load round trip against the literal restatement
+    of utils.jl.  The file's index type is UInt32, the widest the reader and writer have (ivfadc_save_index takes 8, 16 or 32 index
+    bits; 64 is refused, and 16 must refuse ids that do not fit rather than truncate them)."""
+    import ctypes as C
+    from ivfadc_jl_amd import _native as nat
+    from test_persistency import _write_reference_style
+    oidx, _ = helpers.build_index(611, 900, 24, 13, 8, 256)
+    rng = np.random.default_rng(611)
+    special = np.array([0xFFFFFFFF, 0xFFFFFFFE, 0x80000000, 0x80000001, 0x7FFFFFFF, 0], np.int64)
+    upper = np.unique(rng.integers(0x80000002, 0xFFFFFFFE, 4000))[:600]
+    lower = np.unique(rng.integers(1, 0x7FFFFFFF, 4000))[:900 - 600 - len(special)]
+    ids = rng.permutation(np.concatenate([special, rng.permutation(upper), rng.permutation(lower)]))
+    assert ids.shape == (900,) and len(set(ids.tolist())) == 900
+    oidx.ids = ids.astype(np.uint32)
+    gidx = gpu_index(native, oidx)
+    model = _RefModel(oidx.offsets, oidx.codes, oidx.ids)
+    qs = rng.random((48, 24), dtype=np.float32)
+
+    def verify(what):
+        off, codes, gids = gidx._lists()
+        moff, mcodes, mids = model.arrays(8)
+        assert np.array_equal(off, moff) and np.array_equal(gids, mids) and np.array_equal(codes, mcodes), what
+        onow = ora.OracleIndex(oidx.centroids, oidx.codebooks, oidx.labels, off, codes, gids)
+        for plan in (-1, 4, -2, 0):
+            gidx.set_tuning(plan, 0)
+            for K, w in ((10, 5), (300, 13)):
+                got = gidx.search_raw(qs, K, w)
+                helpers.assert_same_results(got, onow.knn_search(qs, K, w), what="%s plan %d K=%d w=%d" % (what, plan, K, w))
+        return got
+
+    got = verify("upper-half ids")
+    seen = got[0][np.arange(300)[None, :] < got[2][:, None]]
+    assert (seen >= 0x80000000).any() and (seen == 0xFFFFFFFF).any()        # K = 300, w = kc: most of the index comes back
+    idl, _ = native.knn_search(gidx, qs[0], 300, w=13)
+    assert idl.dtype == np.uint32 and np.array_equal(idl, got[0][0, :got[2][0]])
+    # delete: present ids at both ends of the range, one absent id above 2^31; survivors above a removed id drop by one each
+    absent = int(0x80000002 + np.setdiff1d(np.arange(100000), upper - 0x80000002)[0])
+    dele = [0xFFFFFFFF, 0x80000000, 0, int(upper[7]), int(upper[300]), int(lower[5]), absent]
+    assert gidx._delete_ids(np.array(dele, np.uint32)) == 6
+    model.delete([x + 1 for x in dele])
+    verify("after delete")
+    assert max(pid for l in model.lists for pid, _ in l) == 0xFFFFFFFE - 5
+    # shift up and down again (pushfirst! / popfirst!): no id wraps
+    for delta in (1, 5, -6):                          # the largest id reaches 0xFFFFFFFF on the way
+        gidx._shift_ids(delta)
+        model.lists = [[(pid + delta, c) for pid, c in l] for l in model.lists]
+        verify("after shift %d" % delta)
+    # the file: UInt32 ids, byte for byte the reference's layout; narrower index types refuse, wider ones do not exist
+    off, codes, gids = gidx._lists()
+    path, ref = os.path.join(str(tmp_path), "upper.bin"), os.path.join(str(tmp_path), "ref.bin")
+    native.save_ivfadc_index(path, gidx)
+    _write_reference_style(ref, oidx.centroids, oidx.codebooks, oidx.labels, off, codes, gids, "UInt32")
+    assert open(path, "rb").read() == open(ref, "rb").read()
+    with pytest.raises(AssertionError):
+        nat.check(nat.lib().ivfadc_save_index(gidx._h, os.path.join(str(tmp_path), "narrow.bin").encode(), 16))
+    with pytest.raises(native.IVFADCError):
+        nat.check(nat.lib().ivfadc_save_index(gidx._h, os.path.join(str(tmp_path), "wide.bin").encode(), 64))
+    g2 = native.load_ivfadc_index(path)
+    assert g2.index_type == np.dtype(np.uint32) and len(g2) == 894
+    o2, c2, i2 = g2._lists()
+    assert np.array_equal(o2, off) and np.array_equal(c2, codes) and np.array_equal(i2, gids)
+    onow = ora.OracleIndex(oidx.centroids, oidx.codebooks, oidx.labels, off, codes, gids)
+    helpers.assert_same_results(g2.search_raw(qs, 300, 13), onow.knn_search(qs, 300, 13), what="loaded")
+
+
 class _JuliaShimReplay:
     """julia/IVFADCHip.jl call by call: the same C symbols in the same order with the same arguments, through ctypes.  `model` plays the
     Julia-side lists (a literal restatement of utils.jl); the handle is what `_handles[ivfadc]` holds.  julia is not in the image, so this
@@ -913,7 +984,8 @@ def test_search_batches_runs_one_launch_per_batch(native):
         if b.shape[0]:
             ei, ed, ec = oidx.knn_search(b, 5, 3)
             for r in range(b.shape[0]):
-                assert np.array_equal(idl[r], ei[r, :ec[r]]) and np.allclose(dl[r], ed[r, :ec[r]], rtol=1e-4, atol=0)
+                assert dl[r].dtype == np.float32
+                assert np.array_equal(idl[r], ei[r, :ec[r]]) and np.array_equal(dl[r].view(np.uint32), ed[r, :ec[r]].view(np.uint32))
     assert g.search_batches_raw([], 10, 8) == [] and g.search_batches_raw([batches[2]], 10, 8)[0][0].shape[0] == 0
 
 

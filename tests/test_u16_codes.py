@@ -173,6 +173,7 @@ def test_numpy_restatement_against_float64(ksub):
         full = dc[lst_of] + sum(((cb64[i, cw[:, i]] - (q64 - cent64[lst_of])[:, i * dsub:(i + 1) * dsub]) ** 2).sum(1) for i in range(m))
         # every returned distance
         pos = np.array([int(np.nonzero(ix.ids == i)[0][0]) for i in ids[r, :cnt[r]]])
+        # float32 sums against a float64 recomputation without tables: different arithmetic, so a tolerance (m roundings) and no bits
         assert np.allclose(dists[r, :cnt[r]], full[pos], rtol=tol, atol=0), (ksub, r)
         # the id set, where float64 separates the boundaries
         order = np.argsort(dc, kind="stable")
