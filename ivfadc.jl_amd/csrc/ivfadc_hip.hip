@@ -748,7 +748,7 @@ size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool l
 
 constexpr size_t LDS_MAX = 160 << 10;
 // the eight-wave list-major kernel (wg8scan.hip.h) as the plan's own choice on long lists (ivfadc_set_table_mode(h, 6) asks for it anywhere)
-constexpr double W9_MIN_PPL = 8.0;   // probes per list from which the eight-query form of the eight-wave kernel is planned
+constexpr double W8_Q8_MIN_PPL = 8.0;   // probes per list from which the eight-query form of the eight-wave kernel is planned
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
 constexpr size_t MISC_BYTES = 4096 + 256 + 512;
@@ -759,7 +759,7 @@ struct Plan {
     bool query_major;
     bool lb;            // query-major rounds with 8-bit lower-bound tables from the matrix cores (lbscan.hip.h)
     bool nf;            // list-major with the narrow-field integer filter, eight queries per code stream (nfscan.hip.h)
-    bool wg8q8;         // ... its eight-query form (wg8q8scan.hip.h)
+    bool wg8q8;         // ... its eight-query form (wg8_scan_kernel<8>)
     bool wg8;           // list-major, eight waves per workgroup on four conflict-free copies of the integer filter table (wg8scan.hip.h)
     bool lanes;         // several batches in flight on this replica: stand-alone top-w, a wave per query (see make_plan)
     bool twolevel;      // coarse stage: certified two-level search (twolevel.hip.h) instead of the exhaustive kernels + top-w
@@ -977,14 +977,14 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         pl.wg8 = qg == 4 && pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && h->dsub == 16 && h->ksub == 256 && h->d == 128 &&
                  h->maxlen < ((int64_t)1 << 28) && h->part_n <= 1 &&
                  (h->wg8_mode > 0 || avg_len >= 8192.0);   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
-        if (pl.wg8) pl.lds = (size_t)W8Lds::END;
-        // ... and EIGHT queries per code stream (wg8q8scan.hip.h: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
+        if (pl.wg8) pl.lds = (size_t)W8Lds<4>::END;
+        // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
         // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
-        pl.wg8q8 = pl.wg8 && (h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W9_MIN_PPL));
+        pl.wg8q8 = pl.wg8 && (h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W8_Q8_MIN_PPL));
         if (pl.wg8q8) {
             qg = 8;
             pl.qg = 8;
-            pl.lds = (size_t)W9Lds::END;
+            pl.lds = (size_t)W8Lds<8>::END;
         }
         }
         // chunk size: enough work items to fill the chip, as few table rebuilds as possible.  Two items per CU is the
@@ -1474,13 +1474,13 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
             h->stats.last_scan_grid = (int)grid;
             h->stats.last_striped = 0;
         } else if (pl.wg8 && !direct) {
-            void (*wk)(const ScanArgs, float *, const u32 *, u32 *, int) = pl.wg8q8 ? wg8q8_scan_kernel : wg8_scan_kernel;
+            void (*wk)(const ScanArgs, float *, const u32 *, u32 *, int) = pl.wg8q8 ? wg8_scan_kernel<8> : wg8_scan_kernel<4>;
             u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
             HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
             int occ = 0;
             TRY(fn_occupancy(h, (const void *)wk, pl.lds, occ, true, W8_THREADS));
             const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * W9_GTAB_FLOATS * 4));   // (occupancy is clamped to 8 workgroups per CU)
+            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * W8_GTAB_FLOATS<8> * 4));   // (occupancy is clamped to 8 workgroups per CU)
             if (h->profiling) TRY(ev_begin(h, 0, ep));
             hipLaunchKernelGGL(wk, dim3(grid), dim3(W8_THREADS), pl.lds, h->stream, a, h->wg8_tabs.as<float>(), h->wg8_items.as<u32>(), xq, 8);
             HIP_TRY(hipGetLastError());
@@ -4460,7 +4460,7 @@ try {
     // 3 / 4: as 0 / 2 with the matrix-core tables built from the three-product bf16 split instead of one f16 product (A/B runs, tests)
     h->lb_use_f16 = mode != 3 && mode != 4;
     // 5 / 6: as 0 with the eight-wave list-major kernel (wg8scan.hip.h) never / wherever it is instantiated (A/B runs, tests);
-    // 7: as 6 with its eight-query form (wg8q8scan.hip.h) wherever that is instantiated
+    // 7: as 6 with its eight-query form (wg8_scan_kernel<8>) wherever that is instantiated
     h->wg8_mode = mode == 5 ? -1 : (mode == 6 ? 1 : (mode == 7 ? 2 : 0));
     return IVFADC_OK;
 } IVF_CATCH

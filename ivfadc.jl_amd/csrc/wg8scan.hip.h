@@ -1,5 +1,5 @@
 // wg8scan.hip.h -- list-major scan for long lists, EIGHT waves per workgroup on ONE table set (m = 8, dsub = 16, ksub = 256, K <= 64:
-// the SIFT1B shape).  Included by kernels.hip.h, namespace ivf.
+// the SIFT1B shape), for NQ = 4 or 8 queries per code stream: wg8_scan_kernel<NQ>.  Included by kernels.hip.h, namespace ivf.
 //
 // Reference: src/coarsequantizers.jl:40-45 (residuals), src/index.jl:232-236 (table build), :240-246 (scan), :247-254 (bounded top-K).
 //
@@ -25,7 +25,18 @@
 //     bound that K real points meet without one exact sum, and only what still passes under it is parked.
 //
 // Selection, bounds (workgroup-shared word in LDS, per-query word in HBM), partial results and the merge kernel behind it are those of
-// scan_kernel; the work items are the same (list, group of <= 4 queries, chunk).
+// scan_kernel; the work items are the same (list, group of <= NQ queries, chunk).
+//
+// EIGHT QUERIES PER CODE STREAM (NQ = 8).  The four-query form is bound by instruction issue (vector ALU 63 % + LDS
+// instructions 18 % of the SIMD cycles, and the two add): a point costs 8 address perms + 8 gathers + 8 three-operand adds per FOUR
+// queries.  With 16-byte table entries -- eight 16-bit fields -- the same perm and ONE ds_read_b128 serve EIGHT queries, 16 adds: 32
+// instructions per point and eight queries instead of 48.  The table keeps its 64 KB: a code's row is 2 copies x 8 sub-quantizers x 16 B
+// = 256 B, lane l reads sub-quantizer (t + l) mod 8 in copy (l / 16) mod 2 -- the four 16-lane service groups of a ds_read_b128 ({0-3,
+// 12-15, 20-27}, {4-11, 16-19, 28-31}, and the same + 32: MI355X_MICROARCH.md) each see 16 different four-bank groups.  Work items are
+// (list, group of <= 8 queries, chunk): half as many table builds, set-ups and hand-overs per probed list; the f32 tables in device
+// memory are 64 KB per workgroup.  Everything else is the four-query form's, eight slots wide: the two differ in the half-step gather,
+// the residual fill, the table build's trips and the quantised store, each behind `if constexpr (NQ == 8)`.  The plan takes this form
+// where a list is probed by eight queries or more on average.
 #pragma once
 
 // Waves per workgroup.  Measured with more (round 6; the table build is laid out for 512 threads, further waves repeat the first ones' share --
@@ -36,24 +47,25 @@
 constexpr int W8_NW = 8;
 constexpr int W8_THREADS = 64 * W8_NW;
 constexpr int W8_ES = 3;                      // dwords per parked point: code bytes (2), list position
-constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (4 copies x 8 sub-quantizers x 8 bytes)
-constexpr u32 W8_GTAB_FLOATS = 8u * 256u * 4u;   // f32 tables of a work item in device memory: [ii][label][4 queries]
+constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (32 / NQ copies x 8 sub-quantizers x 2 NQ bytes)
+template <int NQ> constexpr u32 W8_GTAB_FLOATS = 8u * 256u * (u32)NQ;   // f32 tables of a work item in device memory: [ii][label][NQ queries]
 
-struct W8Lds {
-    static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (16 x 4 + 4 of padding) x 4 B (a sub-quantizer's block starts 4 banks on)
-    static constexpr u32 SMAX = RES + 2176u;                  // u32 [4]: bits of the per-query largest entry (atomicMax); f32 inv[4] behind
-    static constexpr u32 QC = SMAX + 32u;                     // f32 dc[4]; u32 visit-order base[4]; u32 probe index[4]; u32 query[4]
-    static constexpr u32 HARD = QC + 64u;                     // u64 [4]: the bounds the item started from
-    static constexpr u32 STHR = HARD + 32u;                   // u64 [4]: workgroup-shared bounds
-    static constexpr u32 SCNT = STHR + 32u;                   // int [8][4] + [4]
-    static constexpr u32 SWI = SCNT + 144u;                   // u32 [4]
-    static constexpr u32 POOL = SWI + 16u;                    // u64 [4][64]: the workgroup's K smallest keys per slot, unordered (w8_pool_offer)
-    static constexpr u32 PARK = POOL + 4u * 64u * 8u;         // u32 [8][32][W8_ES]: the waves' rings of parked points (W8_RING)
-    static constexpr u32 COLD = PARK + (u32)W8_NW * 32u * W8_ES * 4u;     // u32 [4][8]: a cold work item's first step, every wave's ceil(K / 8)-th smallest integer sum per slot
-    static constexpr u32 END = COLD + 256u;                   // (u32 [4][16]: up to sixteen waves)
+template <int NQ> struct W8Lds {
+    static_assert(NQ == 4 || NQ == 8, "four or eight queries per code stream");
+    static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (16 x NQ + NQ of padding) x 4 B (a sub-quantizer's block starts NQ banks on)
+    static constexpr u32 SMAX = RES + 8u * (16u * NQ + NQ) * 4u;   // u32 [NQ]: bits of the per-query largest entry (atomicMax); f32 inv[NQ] behind
+    static constexpr u32 QC = SMAX + 8u * NQ;                 // f32 dc[NQ]; u32 visit-order base[NQ]; u32 probe index[NQ]; u32 query[NQ]
+    static constexpr u32 HARD = QC + 16u * NQ;                // u64 [NQ]: the bounds the item started from
+    static constexpr u32 STHR = HARD + 8u * NQ;               // u64 [NQ]: workgroup-shared bounds
+    static constexpr u32 SWI = STHR + 8u * NQ;                // u32 [4]
+    static constexpr u32 POOL = SWI + 16u;                    // u64 [NQ][64]: the workgroup's K smallest keys per slot, unordered (w8_pool_offer)
+    static constexpr u32 PARK = POOL + NQ * 64u * 8u;         // u32 [8][32][W8_ES]: the waves' rings of parked points (W8_RING)
+    static constexpr u32 COLD = PARK + (u32)W8_NW * 32u * W8_ES * 4u;     // u32 [NQ][16]: a cold work item's first step, every wave's ceil(K / 8)-th smallest integer sum per slot
+    static constexpr u32 END = COLD + 64u * NQ;               // (up to sixteen waves)
+    static_assert(END <= 80u * 1024u, "two workgroups per CU");
+    static_assert((HARD & 7u) == 0 && (STHR & 7u) == 0 && (POOL & 7u) == 0, "8-byte bounds");
 };
-static_assert(W8Lds::END <= 80u * 1024u, "two workgroups per CU");
-static_assert((W8Lds::HARD & 7u) == 0 && (W8Lds::STHR & 7u) == 0 && (W8Lds::POOL & 7u) == 0, "8-byte bounds");
+static_assert(W8Lds<4>::END == 73264u && W8Lds<8>::END == 77904u, "the layout the plan's LDS figures and the measurements were taken with");
 
 static __device__ __forceinline__ u32 w8_perm(u32 s0, u32 s1, u32 sel)
 {
@@ -71,21 +83,25 @@ template <class T> static __device__ __forceinline__ T *w8_ptr(u32 byte_off)
     extern __shared__ __attribute__((aligned(16))) unsigned char w8_smem[];
     return (T *)(w8_smem + byte_off);
 }
-static __device__ __forceinline__ float w8_dc(int s) { return __uint_as_float(__builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds::QC + 4u * s))); }
-static __device__ __forceinline__ u32 w8_sbase(int s) { return __builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds::QC + 16u + 4u * s)); }
-static __device__ __forceinline__ float w8_inv(int s) { return __uint_as_float(__builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds::SMAX + 16u + 4u * s))); }
-static __device__ __forceinline__ u64 w8_sthr(int s) { return readfirstlane64(w8_lds<u64>(W8Lds::STHR + 8u * s)); }
+template <int NQ> static __device__ __forceinline__ float w8_dc(int s) { return __uint_as_float(__builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds<NQ>::QC + 4u * s))); }
+template <int NQ> static __device__ __forceinline__ u32 w8_sbase(int s) { return __builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds<NQ>::QC + 4u * NQ + 4u * s)); }
+template <int NQ> static __device__ __forceinline__ float w8_inv(int s) { return __uint_as_float(__builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds<NQ>::SMAX + 4u * NQ + 4u * s))); }
+template <int NQ> static __device__ __forceinline__ u64 w8_sthr(int s) { return readfirstlane64(w8_lds<u64>(W8Lds<NQ>::STHR + 8u * s)); }
 
-// The accumulator BIAS of the four queries under the bounds of the moment: field s of a point's accumulators starts at
-// B_s = 0x7FFF - T_s (T_s = qf_targets' integer budget of query s; an unused slot gets 0x8000), so "field < 0x8000" <=> "sum_s <= T_s":
-// the candidate test of a step is four ANDs and a compare, and the first add of a point absorbs the bias.  sum <= 32760, B <= 0x8000:
-// fields never carry.  The bounds are the workgroup's (STHR in LDS: the pool's K-th key, the item's bound from outside, an integer-sum
-// bound of a cold start -- whichever is smallest); a wave holds no bound of its own.
-// Lane s (mod 4) evaluates slot s -- qf_targets' arithmetic, operation for operation (its argument is what makes the filter exact) -- on the
-// slot's constants in LDS: one round trip and a dozen vector instructions for the four slots (evaluated slot by slot on uniform values it
+// The accumulator BIAS of the NQ queries under the bounds of the moment (two 16-bit fields per dword): field s of a point's accumulators
+// starts at B_s = 0x7FFF - T_s (T_s = qf_targets' integer budget of query s; an unused slot gets 0x8000), so "field < 0x8000" <=>
+// "sum_s <= T_s": the candidate test of a step is NQ ANDs and a compare, and the first add of a point absorbs the bias.  sum <= 32760,
+// B <= 0x8000: fields never carry.  The bounds are the workgroup's (STHR in LDS: the pool's K-th key, the item's bound from outside, an
+// integer-sum bound of a cold start -- whichever is smallest); a wave holds no bound of its own.
+// Lane s (mod NQ) evaluates slot s -- qf_targets' arithmetic, operation for operation (its argument is what makes the filter exact) -- on the
+// slot's constants in LDS: one round trip and a dozen vector instructions for the slots (evaluated slot by slot on uniform values it
 // was eight dependent LDS round trips and ~200 instructions, paid at every refresh and after every pass: most of the candidate path).
-static __device__ __forceinline__ void w8_bias_of(u32 th, float dc, float inv, u32 sl, int nvalid, u32 (&bias)[2])
+template <int NQ> static __device__ __forceinline__ void w8_bias(int nvalid, u32 (&bias)[NQ / 2])
 {
+    const u32 sl = (u32)lane_id() & (u32)(NQ - 1);
+    const u32 th = w8_lds<u32>(W8Lds<NQ>::STHR + 8u * sl + 4u);
+    const float dc = w8_lds<float>(W8Lds<NQ>::QC + 4u * sl);
+    const float inv = w8_lds<float>(W8Lds<NQ>::SMAX + 4u * NQ + 4u * sl);
     u32 T = 0x7FFFu;
     if (th < 0x7F800000u) {   // a finite bound
         const float thr = __uint_as_float(th);
@@ -93,16 +109,18 @@ static __device__ __forceinline__ void w8_bias_of(u32 th, float dc, float inv, u
         T = x < 0.0f ? 0u : (x < 32000.0f ? (u32)x + 2u : 0x7FFFu);
     }
     const u32 B = (int)sl < nvalid ? 0x7FFFu - T : 0x8000u;
-    bias[0] = (u32)__builtin_amdgcn_readlane((int)B, 0) | ((u32)__builtin_amdgcn_readlane((int)B, 1) << 16);
-    bias[1] = (u32)__builtin_amdgcn_readlane((int)B, 2) | ((u32)__builtin_amdgcn_readlane((int)B, 3) << 16);
+#pragma unroll
+    for (int i = 0; i < NQ / 2; ++i)
+        bias[i] = (u32)__builtin_amdgcn_readlane((int)B, 2 * i) | ((u32)__builtin_amdgcn_readlane((int)B, 2 * i + 1) << 16);
 }
-static __device__ __forceinline__ void w8_bias(int nvalid, u32 (&bias)[2])
+// the AND of a point's accumulator dwords: a field's top bit survives only if it is set for every query
+static __device__ __forceinline__ u32 w8_and(const u32 (&q)[2]) { return q[0] & q[1]; }
+static __device__ __forceinline__ u32 w8_and(const u32 (&q)[4]) { return (q[0] & q[1]) & (q[2] & q[3]); }
+// ... of accumulators that were summed under the bias b and are to be tested under n
+static __device__ __forceinline__ u32 w8_and_rebased(const u32 (&q)[2], const u32 (&b)[2], const u32 (&n)[2]) { return (q[0] - b[0] + n[0]) & (q[1] - b[1] + n[1]); }
+static __device__ __forceinline__ u32 w8_and_rebased(const u32 (&q)[4], const u32 (&b)[4], const u32 (&n)[4])
 {
-    const u32 sl = (u32)lane_id() & 3u;
-    const u32 th = w8_lds<u32>(W8Lds::STHR + 8u * sl + 4u);
-    const float dc = w8_lds<float>(W8Lds::QC + 4u * sl);
-    const float inv = w8_lds<float>(W8Lds::SMAX + 16u + 4u * sl);
-    w8_bias_of(th, dc, inv, sl, nvalid, bias);
+    return ((q[0] - b[0] + n[0]) & (q[1] - b[1] + n[1])) & ((q[2] - b[2] + n[2]) & (q[3] - b[3] + n[3]));
 }
 
 // ---- the workgroup's selection: ONE pool of K keys per slot in LDS, shared by the eight waves ---------------------------------------------
@@ -137,9 +155,9 @@ static __device__ __forceinline__ u64 w8_wave_max_u64(u64 v)
     return ((u64)mh << 32) | ml;
 }
 // the pool's entries of slot s, one per lane (lanes >= K: 0, below every key)
-static __device__ __forceinline__ u64 w8_pool_read(int s, int K, int lane)
+template <int NQ> static __device__ __forceinline__ u64 w8_pool_read(int s, int K, int lane)
 {
-    return lane < K ? w8_lds<u64>(W8Lds::POOL + 512u * (u32)s + 8u * (u32)lane) : 0ull;
+    return lane < K ? w8_lds<u64>(W8Lds<NQ>::POOL + 512u * (u32)s + 8u * (u32)lane) : 0ull;
 }
 // Offers the keys of the lanes in `mask` (uniform, non-empty) to slot s, starting from the snapshot v the caller read a while ago.  A stale
 // snapshot is as good as a fresh one for every decision above -- each of its values WAS that entry's, entries only decrease -- it merely
@@ -147,10 +165,10 @@ static __device__ __forceinline__ u64 w8_pool_read(int s, int K, int lane)
 // without another read.  An offer costs one LDS round trip per swap attempt (under the scan's gathers a round trip is several hundred
 // cycles: the dependent trips, not the instructions, were the cost of a pass).  Returns the slot's new bound, KEY_MAX if nothing went in
 // or the pool is not full.
-static __device__ __forceinline__ u64 w8_pool_offer(int s, u64 v, u64 key, u64 mask, int K, int lane)
+template <int NQ> static __device__ __forceinline__ u64 w8_pool_offer(int s, u64 v, u64 key, u64 mask, int K, int lane)
 {
     bool any = false;
-    u64 *pool = w8_ptr<u64>(W8Lds::POOL + 512u * (u32)s);
+    u64 *pool = w8_ptr<u64>(W8Lds<NQ>::POOL + 512u * (u32)s);
     u64 mx = w8_wave_max_u64(v);
     for (;;) {   // uniform
         mask &= __builtin_amdgcn_ballot_w64(key < mx);   // (every lane's key against the bound of this moment: most offers of a crowd end here)
@@ -171,25 +189,26 @@ static __device__ __forceinline__ u64 w8_pool_offer(int s, u64 v, u64 key, u64 m
         mx = w8_wave_max_u64(v);
     }
     if (!any || mx == KEY_MAX) return KEY_MAX;
-    if (lane == 0) atomicMin(w8_ptr<u64>(W8Lds::STHR + 8u * (u32)s), mx);
+    if (lane == 0) atomicMin(w8_ptr<u64>(W8Lds<NQ>::STHR + 8u * (u32)s), mx);
     return mx;
 }
 
 // ---- reference-order sums of parked points, 8 per pass, entries from the work item's f32 tables in device memory -------------------
 // (scope: the tables were written by this workgroup before a barrier; the loads go to L2 -- sc1 -- so that no line of an earlier work
 // item's tables can be served from this CU's vector cache)
-static __device__ __forceinline__ v4f w8_gtab_load(__amdgpu_buffer_rsrc_t rs, u32 ii, u32 byte)
+// queries 4 q4 .. 4 q4 + 3 of entry [ii][byte]
+template <int NQ> static __device__ __forceinline__ v4f w8_gtab_load(__amdgpu_buffer_rsrc_t rs, u32 ii, u32 byte, int q4)
 {
-    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)(((ii << 8) | byte) << 4), 0, 16);
+    const v4u v = __builtin_amdgcn_raw_buffer_load_b128(rs, (int)((((ii << 8) | byte) * (4u * NQ)) + 16u * (u32)q4), 0, 16);
     return (v4f){__uint_as_float(v.x), __uint_as_float(v.y), __uint_as_float(v.z), __uint_as_float(v.w)};
 }
 
-// A pass in flight: lane 8 e + ii holds the f32 entries (four queries) of sub-quantizer ii at parked point e's code byte, and the point's
-// position.  Requested when eight points are waiting (w8_pass_issue) and worked off at the top of the NEXT step, right behind the wait
-// for that step's code bytes -- older than the gather -- so the trip to L2 costs the wave nothing (a pass worked off where it is
-// requested waits for the code stream's request in flight AND its own: ~4 us per pass, measured).
-struct W8Pass {
-    v4f ev;
+// A pass in flight: lane 8 e + ii holds the f32 entries (four queries per register set) of sub-quantizer ii at parked point e's code
+// byte, and the point's position.  Requested when eight points are waiting (w8_pass_issue) and worked off at the top of the NEXT step,
+// right behind the wait for that step's code bytes -- older than the gather -- so the trip to L2 costs the wave nothing (a pass worked off
+// where it is requested waits for the code stream's request in flight AND its own: ~4 us per pass, measured).
+template <int NQ> struct W8Pass {
+    v4f ev[NQ / 4];
     u32 pos;
     bool ok;
 };
@@ -203,7 +222,7 @@ constexpr int W8_PRIO_SCAN = 3;   // wave priority while the code stream is scan
 constexpr int W8_PRIO_REST = 0;
 constexpr int W8_RING = 32;    // parked points per wave (a ring: entries head .. head + cnt - 1 mod 32)
 
-static __device__ __forceinline__ void w8_pass_issue(W8Pass &ps, u32 cbuf_addr, int &head, int &cnt, __amdgpu_buffer_rsrc_t gt, int lane)
+template <int NQ> static __device__ __forceinline__ void w8_pass_issue(W8Pass<NQ> &ps, u32 cbuf_addr, int &head, int &cnt, __amdgpu_buffer_rsrc_t gt, int lane)
 {
     const int seg = lane >> 3, ii = lane & 7;
     ps.ok = seg < cnt;
@@ -214,7 +233,8 @@ static __device__ __forceinline__ void w8_pass_issue(W8Pass &ps, u32 cbuf_addr, 
     const u32 idx = ((u32)ii - (pj >> 29)) & 7u;
     const u32 dw = w8_lds<u32>(ea + 4u * (idx >> 2));
     ps.pos = pj & 0x1FFFFFFFu;
-    ps.ev = w8_gtab_load(gt, (u32)ii, (dw >> (8 * (idx & 3))) & 0xffu);
+#pragma unroll
+    for (int q4 = 0; q4 < NQ / 4; ++q4) ps.ev[q4] = w8_gtab_load<NQ>(gt, (u32)ii, (dw >> (8 * (idx & 3))) & 0xffu, q4);
     const int take = cnt < 8 ? cnt : 8;
     head = (head + take) & (W8_RING - 1);
     cnt -= take;
@@ -224,29 +244,31 @@ static __device__ __forceinline__ void w8_pass_issue(W8Pass &ps, u32 cbuf_addr, 
 // bias arithmetic's operands -- requested in one go ahead of the running sums, the bias computed from registers: 16 384 x w = 8
 // 5.87 -> 5.91 ms, w = 1 1.38 -> 1.44.  The pass does not wait for memory -- 260 of its 7 700 cycles, by cycle counters -- it is ~400 dependent
 // instructions on a SIMD it shares with three scanning waves.)
-static __device__ __forceinline__ void w8_pass_finish(const W8Pass &ps, int nvalid, int K, int lane)
+template <int NQ> static __device__ __forceinline__ void w8_pass_finish(const W8Pass<NQ> &ps, int nvalid, int K, int lane)
 {
     const int ii = lane & 7;
-    const float ev[4] = {ps.ev.x, ps.ev.y, ps.ev.z, ps.ev.w};
-    float x[4];
+    float ev[NQ];
 #pragma unroll
-    for (int s = 0; s < 4; ++s) x[s] = w8_dc(s) + ev[s];
+    for (int s = 0; s < NQ; ++s) ev[s] = ps.ev[s >> 2][s & 3];
+    float x[NQ];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) x[s] = w8_dc<NQ>(s) + ev[s];
 #pragma unroll
     for (int i = 1; i < 8; ++i)
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
+        for (int s = 0; s < NQ; ++s) {
             // lane l <- lane l-1 within a row of 16 (row_shr:1): what lane i reads at step i is lane i-1's value of step i-1, so the
             // segment's last lane ends with ((dc + t0) + t1) + ... + t7 (index.jl:242-246)
             const float up = __uint_as_float((u32)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x[s]), 0x111, 0xf, 0xf, false));
             x[s] = up + ev[s];
         }
 #pragma unroll
-    for (int s = 0; s < 4; ++s) {
+    for (int s = 0; s < NQ; ++s) {
         if (s >= nvalid) continue;   // uniform
         // (keys are unique: the exclusive test loses nothing -- a key that IS the bound sits in the pool already, or came from another list)
-        const u64 key = make_key(x[s], w8_sbase(s) + ps.pos);
-        const u64 mask = __builtin_amdgcn_ballot_w64(ps.ok && ii == 7 && key < w8_sthr(s));
-        if (mask != 0) w8_pool_offer(s, w8_pool_read(s, K, lane), key, mask, K, lane);   // uniform: most parked points pass for one query of the four
+        const u64 key = make_key(x[s], w8_sbase<NQ>(s) + ps.pos);
+        const u64 mask = __builtin_amdgcn_ballot_w64(ps.ok && ii == 7 && key < w8_sthr<NQ>(s));
+        if (mask != 0) w8_pool_offer<NQ>(s, w8_pool_read<NQ>(s, K, lane), key, mask, K, lane);   // uniform: most parked points pass for one query of the group
     }
 }
 
@@ -270,6 +292,7 @@ static __device__ __attribute__((noinline)) u32 w8_kth_sum4(u32 v0, u32 v1, u32 
     return prefix;
 }
 
+template <int NQ>
 static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t codes, u32 p0, u32 p1, int nvalid, int K, int wv, int lane,
                                                      v4u ca, v4u cb, __amdgpu_buffer_rsrc_t gt)
 {
@@ -279,20 +302,24 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
     // of the NEXT step is requested into its register set the moment this step's half has left it (rotated, four v_perm): two requests
     // of 1 KB per wave are in flight at any time, each with a whole step to arrive, and there is no second register set and no move.
     // (One request per wave -- 4 MB on the chip -- at the loaded latency of HBM is 2 TB/s: the conflict-free scan waited on every step.)
+    using L = W8Lds<NQ>;
     constexpr u32 STEP = 256;
-    const u32 cbuf_addr = W8Lds::PARK + (u32)wv * (W8_RING * W8_ES * 4u);
-    u32 bias[2];
-    w8_bias(nvalid, bias);
+    constexpr int NB = NQ / 2;          // accumulator dwords of a point: two 16-bit fields each
+    constexpr u32 EB = 2u * NQ, CB = 16u * NQ;   // bytes of a table entry, of a copy's eight entries
+    constexpr int CSH = NQ == 8 ? 4 : 3, CMASK = NQ == 8 ? 1 : 3;   // lane -> copy
+    const u32 cbuf_addr = L::PARK + (u32)wv * (W8_RING * W8_ES * 4u);
+    u32 bias[NB];
+    w8_bias<NQ>(nvalid, bias);
     // lane constants: byte rotation of a point's code (out byte t = code byte (t + j) mod 8) and the low address byte of slot t:
-    // copy << 6 | ((t + j) mod 8) << 3
-    const int j = lane & 7, cpy = (lane >> 3) & 3;
+    // copy * 8 EB | ((t + j) mod 8) * EB (four copies of 8-byte entries, two of 16-byte ones)
+    const int j = lane & 7, cpy = (lane >> CSH) & CMASK;
     u32 rsel0 = 0, rsel1 = 0, ap0 = 0, ap1 = 0;
 #pragma unroll
     for (int b = 0; b < 4; ++b) {
         rsel0 |= (u32)((b + j) & 7) << (8 * b);
         rsel1 |= (u32)((4 + b + j) & 7) << (8 * b);
-        ap0 |= ((u32)((b + j) & 7) * 8u + (u32)cpy * 64u) << (8 * b);
-        ap1 |= ((u32)((4 + b + j) & 7) * 8u + (u32)cpy * 64u) << (8 * b);
+        ap0 |= ((u32)((b + j) & 7) * EB + (u32)cpy * CB) << (8 * b);
+        ap1 |= ((u32)((4 + b + j) & 7) * EB + (u32)cpy * CB) << (8 * b);
     }
     // address of slot t = perm{byte 0: lane part of slot t, byte 1: rotated code byte t, bytes 2, 3: zero}
     const u32 asel[4] = {0x0C0C0400u, 0x0C0C0501u, 0x0C0C0602u, 0x0C0C0703u};
@@ -300,8 +327,9 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
     int head = 0, ccnt = 0;
     u32 since = 0;
     bool pend = false;
-    W8Pass ps;
-    ps.ev = (v4f){0.f, 0.f, 0.f, 0.f};
+    W8Pass<NQ> ps;
+#pragma unroll
+    for (int q4 = 0; q4 < NQ / 4; ++q4) ps.ev[q4] = (v4f){0.f, 0.f, 0.f, 0.f};
     ps.pos = 0;
     ps.ok = false;
     u32 rw[4][2];
@@ -316,9 +344,9 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
     u32 coldmask = 0;
     if (p1 - p0 >= (u32)W8_NW * STEP) {
 #pragma unroll
-        for (int s = 0; s < 4; ++s) {
-            const float inv = w8_inv(s);
-            const u32 hh = __builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds::HARD + 8u * s + 4u));
+        for (int s = 0; s < NQ; ++s) {
+            const float inv = w8_inv<NQ>(s);
+            const u32 hh = __builtin_amdgcn_readfirstlane(w8_lds<u32>(L::HARD + 8u * s + 4u));
             if (s < nvalid && hh >= 0x7F800000u && inv > 0.0f && inv < 1.0e30f) coldmask |= 1u << s;
         }
     }
@@ -334,11 +362,11 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
         } else {
             if (__builtin_expect(pend, 0)) {   // uniform: the pass requested during the previous step
                 pend = false;
-                w8_pass_finish(ps, nvalid, K, lane);
+                w8_pass_finish<NQ>(ps, nvalid, K, lane);
                 since = 0;
-                w8_bias(nvalid, bias);   // (the other waves' offers moved the bounds as well)
+                w8_bias<NQ>(nvalid, bias);   // (the other waves' offers moved the bounds as well)
                 if (ccnt >= W8_TRIG || (ccnt > 0 && pb >= ptail)) {   // the next ones are waiting already (or the range ends)
-                    w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
+                    w8_pass_issue<NQ>(ps, cbuf_addr, head, ccnt, gt, lane);
                     pend = true;
                 }
             } else if (__builtin_expect(ccnt > 0 && pb >= ptail, 0)) {
@@ -346,12 +374,12 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 // scanned, and the end of the range finds an empty ring nine times in ten (a pass worked off THERE is a trip to L2 the
                 // wave sits out, with the other seven waiting for it at the barrier behind: the wait was 8 % of the kernel)
                 wave_sync();
-                w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
+                w8_pass_issue<NQ>(ps, cbuf_addr, head, ccnt, gt, lane);
                 pend = true;
             } else if (++since >= (u32)W8_REFRESH) {
                 // the workgroup's bounds move even when this wave has no candidates of its own
                 since = 0;
-                w8_bias(nvalid, bias);
+                w8_bias<NQ>(nvalid, bias);
             }
             // the next step's offsets: past the end the wave's current halves are read once more (no branch around a request, no second
             // value for a register set to merge with; a half that starts beyond the list repeats the first one: never a byte beyond the
@@ -359,7 +387,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
             const u32 pn = pb + W8_NW * STEP;
             const u32 pa = pn < p1 ? pn : pb;
             const u32 pbb = pa + 128u < p1 ? pa + 128u : pa;
-            u32 qa[4][2];
+            u32 qa[4][NB];
             auto half = [&](auto hc, v4u &cx, u32 pnext) __attribute__((always_inline)) {
                 constexpr int h = decltype(hc)::value;
                 // the half's bytes leave its register set rotated (tied together so that no part of them can sink below the request that
@@ -370,25 +398,59 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 rw[2 * h + 1][1] = __builtin_amdgcn_perm(cx.w, cx.z, rsel1);
                 asm volatile("" : "+v"(rw[2 * h][0]), "+v"(rw[2 * h][1]), "+v"(rw[2 * h + 1][0]), "+v"(rw[2 * h + 1][1]), "+v"(cx));
                 cx = __builtin_amdgcn_raw_buffer_load_b128(codes, lane16, (int)(pnext * 8u), W8_STREAM_AUX);
-                // all sixteen gathers of the half are issued before the first add (left alone the compiler waits after every second read)
-                v2u ev[2][8];
-                static_for<2>([&](auto rc) {
-                    constexpr int r = decltype(rc)::value;
+                // the gathers and adds of the half's two points: each form's order is hand-made and measured
+                if constexpr (NQ == 8) {
+                    // eight gathers (32 registers) in flight: the first point's are issued before the first add; each of its entries, once
+                    // summed, hands its registers to the same slot's gather of the second point (one fill and one drain per half)
+                    v4u ev[8];
                     static_for<8>([&](auto tc) {
                         constexpr int t = decltype(tc)::value;
-                        const u32 ea = w8_perm(rw[2 * h + r][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
-                        ev[r][t] = lds_load_abs<v2u>(ea);
+                        const u32 ea = w8_perm(rw[2 * h][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
+                        ev[t] = lds_load_abs<v4u>(ea);
                     });
-                });
-                __builtin_amdgcn_sched_barrier(0);
+                    __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
-                for (int r = 0; r < 2; ++r) {
-                    qa[2 * h + r][0] = bias[0];
-                    qa[2 * h + r][1] = bias[1];
+                    for (int i = 0; i < 4; ++i) qa[2 * h][i] = bias[i];
+                    static_for<8>([&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        qa[2 * h][0] += ev[t].x;
+                        qa[2 * h][1] += ev[t].y;
+                        qa[2 * h][2] += ev[t].z;
+                        qa[2 * h][3] += ev[t].w;
+                        const u32 ea = w8_perm(rw[2 * h + 1][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
+                        ev[t] = lds_load_abs<v4u>(ea);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) qa[2 * h + 1][i] = bias[i];
 #pragma unroll
                     for (int t = 0; t < 8; ++t) {
-                        qa[2 * h + r][0] += ev[r][t].x;
-                        qa[2 * h + r][1] += ev[r][t].y;
+                        qa[2 * h + 1][0] += ev[t].x;
+                        qa[2 * h + 1][1] += ev[t].y;
+                        qa[2 * h + 1][2] += ev[t].z;
+                        qa[2 * h + 1][3] += ev[t].w;
+                    }
+                } else {
+                    // all sixteen gathers of the half are issued before the first add (left alone the compiler waits after every second read)
+                    v2u ev[2][8];
+                    static_for<2>([&](auto rc) {
+                        constexpr int r = decltype(rc)::value;
+                        static_for<8>([&](auto tc) {
+                            constexpr int t = decltype(tc)::value;
+                            const u32 ea = w8_perm(rw[2 * h + r][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
+                            ev[r][t] = lds_load_abs<v2u>(ea);
+                        });
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        qa[2 * h + r][0] = bias[0];
+                        qa[2 * h + r][1] = bias[1];
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) {
+                            qa[2 * h + r][0] += ev[r][t].x;
+                            qa[2 * h + r][1] += ev[r][t].y;
+                        }
                     }
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -398,11 +460,11 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
             // a field below 0x8000 <=> that query's integer sum is within its budget (w8_bias); one compare for the four points
             u32 x[4];
 #pragma unroll
-            for (int r = 0; r < 4; ++r) x[r] = qa[r][0] & qa[r][1];
+            for (int r = 0; r < 4; ++r) x[r] = w8_and(qa[r]);
             u64 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
             if (__builtin_expect(first && coldmask != 0u, 0)) {   // uniform over the WORKGROUP: see above
                 const int r8 = (K + W8_NW - 1) / W8_NW;
-                static_for<4>([&](auto sc) {
+                static_for<NQ>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     if ((coldmask >> s) & 1u) {   // uniform
                         // (the slot's bias is 0 while it has no bound: the fields are the sums)
@@ -410,35 +472,35 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 #pragma unroll
                         for (int r = 0; r < 4; ++r) f[r] = (s & 1) ? (qa[r][s >> 1] >> 16) : (qa[r][s >> 1] & 0xffffu);
                         const u32 V = w8_kth_sum4(f[0], f[1], f[2], f[3], 0xFu, r8);
-                        if (lane == 0) *w8_ptr<u32>(W8Lds::COLD + 64u * s + 4u * (u32)wv) = V;
+                        if (lane == 0) *w8_ptr<u32>(L::COLD + 64u * s + 4u * (u32)wv) = V;
                     }
                 });
                 __syncthreads();
-                static_for<4>([&](auto sc) {
+                static_for<NQ>([&](auto sc) {
                     constexpr int s = decltype(sc)::value;
                     if ((coldmask >> s) & 1u) {   // uniform
                         u32 T = 0;
 #pragma unroll
                         for (int v = 0; v < W8_NW; ++v) {
-                            const u32 o = __builtin_amdgcn_readfirstlane(w8_lds<u32>(W8Lds::COLD + 64u * s + 4u * (u32)v));
+                            const u32 o = __builtin_amdgcn_readfirstlane(w8_lds<u32>(L::COLD + 64u * s + 4u * (u32)v));
                             T = o > T ? o : T;
                         }
-                        const float ub = (w8_dc(s) + (float)(T + 8u) * (1.00001f / w8_inv(s))) * 1.00002f;
+                        const float ub = (w8_dc<NQ>(s) + (float)(T + 8u) * (1.00001f / w8_inv<NQ>(s))) * 1.00002f;
                         // (every wave arrives at the same bound; the wave's own atomic is ahead of its own reads of the word)
-                        if (ub < 3.0e38f && lane == 0) atomicMin(w8_ptr<u64>(W8Lds::STHR + 8u * s), make_key(ub, 0xFFFFFFFFu));
+                        if (ub < 3.0e38f && lane == 0) atomicMin(w8_ptr<u64>(L::STHR + 8u * s), make_key(ub, 0xFFFFFFFFu));
                     }
                 });
                 // the step's fields were accumulated under the old bias: re-based on the new one, and the step is tested again
-                u32 nb[2];
-                w8_bias(nvalid, nb);
+                u32 nb[NB];
+                w8_bias<NQ>(nvalid, nb);
 #pragma unroll
                 for (int r = 0; r < 4; ++r) {
-                    qa[r][0] = qa[r][0] - bias[0] + nb[0];
-                    qa[r][1] = qa[r][1] - bias[1] + nb[1];
-                    x[r] = qa[r][0] & qa[r][1];
+#pragma unroll
+                    for (int i = 0; i < NB; ++i) qa[r][i] = qa[r][i] - bias[i] + nb[i];
+                    x[r] = w8_and(qa[r]);
                 }
-                bias[0] = nb[0];
-                bias[1] = nb[1];
+#pragma unroll
+                for (int i = 0; i < NB; ++i) bias[i] = nb[i];
                 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
             }
             first = false;
@@ -466,39 +528,39 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                     u32 vb = 0;
 #pragma unroll
                     for (int r = 0; r < 4; ++r) vb |= (pt0 + (u32)(r >> 1) * 128u + (u32)(r & 1) < p1) ? (1u << r) : 0u;
-                    static_for<4>([&](auto sc) {
+                    static_for<NQ>([&](auto sc) {
                         constexpr int s = decltype(sc)::value;
-                        const float inv = w8_inv(s);
+                        const float inv = w8_inv<NQ>(s);
                         // (a scale that is not a normal number -- all-zero or denormal tables -- keeps the plain path)
-                        if (s < nvalid && (u32)(w8_sthr(s) >> 32) >= 0x7F800000u && inv > 0.0f && inv < 1.0e30f) {   // uniform
+                        if (s < nvalid && (u32)(w8_sthr<NQ>(s) >> 32) >= 0x7F800000u && inv > 0.0f && inv < 1.0e30f) {   // uniform
                             // the sums themselves: field - bias (no borrow: every field started from its bias)
                             const u32 bs = (s & 1) ? (bias[s >> 1] >> 16) : (bias[s >> 1] & 0xffffu);
                             u32 f[4];
 #pragma unroll
                             for (int r = 0; r < 4; ++r) f[r] = ((s & 1) ? (qa[r][s >> 1] >> 16) : (qa[r][s >> 1] & 0xffffu)) - bs;
                             const u32 U = w8_kth_sum4(f[0], f[1], f[2], f[3], vb, K);
-                            const float ub = (w8_dc(s) + (float)(U + 8u) * (1.00001f / inv)) * 1.00002f;
+                            const float ub = (w8_dc<NQ>(s) + (float)(U + 8u) * (1.00001f / inv)) * 1.00002f;
                             if (ub < 3.0e38f) {
-                                if (lane == 0) atomicMin(w8_ptr<u64>(W8Lds::STHR + 8u * s), make_key(ub, 0xFFFFFFFFu));
+                                if (lane == 0) atomicMin(w8_ptr<u64>(L::STHR + 8u * s), make_key(ub, 0xFFFFFFFFu));
                                 moved = true;
                             }
                         }
                     });
                     if (moved) {
                         // the step's fields were accumulated under the old bias: re-based on the new one before they are tested again
-                        u32 nb[2];
-                        w8_bias(nvalid, nb);
+                        u32 nb[NB];
+                        w8_bias<NQ>(nvalid, nb);
                         ntot = 0;
 #pragma unroll
                         for (int r = 0; r < 4; ++r) {
-                            const u32 y = (qa[r][0] - bias[0] + nb[0]) & (qa[r][1] - bias[1] + nb[1]);
+                            const u32 y = w8_and_rebased(qa[r], bias, nb);
                             c[r] = (y & 0x80008000u) != 0x80008000u && ((vb >> r) & 1u) != 0u;
                             m[r] = __builtin_amdgcn_ballot_w64(c[r]);
                             n[r] = __popcll(m[r]);
                             ntot += n[r];
                         }
-                        bias[0] = nb[0];
-                        bias[1] = nb[1];
+#pragma unroll
+                        for (int i = 0; i < NB; ++i) bias[i] = nb[i];
                     }
                 }
                 // park (rotated code bytes, position | rotation << 29: positions stay below 2^28, the code stream's byte offsets are 31-bit)
@@ -520,7 +582,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                     // a pass is requested when eight points wait and none is in flight; it is worked off at the top of the next step
                     if (!pend && (ccnt >= W8_TRIG || pb >= ptail)) {
                         wave_sync();
-                        w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
+                        w8_pass_issue<NQ>(ps, cbuf_addr, head, ccnt, gt, lane);
                         pend = true;
                     }
                 } else {
@@ -555,12 +617,12 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 const bool more = (fm[0] | fm[1] | fm[2] | fm[3]) != 0;
                 if (pend) {
                     pend = false;
-                    w8_pass_finish(ps, nvalid, K, lane);
-                    w8_bias(nvalid, bias);
+                    w8_pass_finish<NQ>(ps, nvalid, K, lane);
+                    w8_bias<NQ>(nvalid, bias);
                 }
                 if (ccnt > 0 && (more || flush || ccnt >= 8)) {
                     wave_sync();
-                    w8_pass_issue(ps, cbuf_addr, head, ccnt, gt, lane);
+                    w8_pass_issue<NQ>(ps, cbuf_addr, head, ccnt, gt, lane);
                     pend = true;
                     if (more || flush) continue;   // (uniform) worked off at once: room for what is left / nothing may stay behind
                 }
@@ -578,29 +640,31 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 // neighbours in the queue: the item range is cut into one contiguous part per XCD and a workgroup pulls from the part of the XCD it runs
 // on (HW_REG_XCC_ID) -- the groups that stream the same list then run side by side under ONE L2 and the list crosses the fabric once.
 // Placement is a matter of speed only: a workgroup whose part is exhausted moves on to the next one; every wave leaves when all are.
+template <int NQ>
 __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
                                                                  u32 *__restrict__ xq, int nranges)
 {
+    using L = W8Lds<NQ>;
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const IndexView &ix = a.ix;
     const int tid = threadIdx.x, lane = tid & 63;
     const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);     // (a scalar: branches on the wave's number and its position in the list are scalar branches)
     const int K = a.K;
-    float *res = (float *)(smem + W8Lds::RES);
-    u32 *smax = (u32 *)(smem + W8Lds::SMAX);
-    float *sinv = (float *)(smem + W8Lds::SMAX) + 4;
-    float *sdc = (float *)(smem + W8Lds::QC);
-    u32 *ssb = (u32 *)(smem + W8Lds::QC) + 4;
-    u32 *spi = (u32 *)(smem + W8Lds::QC) + 8;
-    u32 *sqi = (u32 *)(smem + W8Lds::QC) + 12;
-    u64 *shard = (u64 *)(smem + W8Lds::HARD);
-    u64 *sthr = (u64 *)(smem + W8Lds::STHR);
-    u32 *swi = (u32 *)(smem + W8Lds::SWI);
+    float *res = (float *)(smem + L::RES);
+    u32 *smax = (u32 *)(smem + L::SMAX);
+    float *sinv = (float *)(smem + L::SMAX) + NQ;
+    float *sdc = (float *)(smem + L::QC);
+    u32 *ssb = (u32 *)(smem + L::QC) + NQ;
+    u32 *spi = (u32 *)(smem + L::QC) + 2 * NQ;
+    u32 *sqi = (u32 *)(smem + L::QC) + 3 * NQ;
+    u64 *shard = (u64 *)(smem + L::HARD);
+    u64 *sthr = (u64 *)(smem + L::STHR);
+    u32 *swi = (u32 *)(smem + L::SWI);
     const u32 total = a.wi_off[ix.kc];
-    float *gt = gtabs + (size_t)blockIdx.x * W8_GTAB_FLOATS;
-    const __amdgpu_buffer_rsrc_t gtr = __builtin_amdgcn_make_buffer_rsrc((void *)gt, 0, (int)(W8_GTAB_FLOATS * 4u), 0x00020000);
+    float *gt = gtabs + (size_t)blockIdx.x * W8_GTAB_FLOATS<NQ>;
+    const __amdgpu_buffer_rsrc_t gtr = __builtin_amdgcn_make_buffer_rsrc((void *)gt, 0, (int)(W8_GTAB_FLOATS<NQ> * 4u), 0x00020000);
 
-    u64 *pool = (u64 *)(smem + W8Lds::POOL);
+    u64 *pool = (u64 *)(smem + L::POOL);
     // (thread 0's: the part it pulls from, the parts found empty so far)
     int qcur = nranges > 1 ? (int)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u) : 0, qtried = 0;
     // the item behind ticket k of the current part; a part that is exhausted hands over to the next one (a trip per part: the tail only)
@@ -625,19 +689,19 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         do {   // (one trip: `break` = this work item is finished)
         const int l = __builtin_amdgcn_readfirstlane((int)item_list[wi]);
         const u32 cnt = __builtin_amdgcn_readfirstlane(a.list_cnt[l]);
-        const u32 ng = (cnt + 3u) / 4u;
+        const u32 ng = (cnt + (u32)(NQ - 1)) / (u32)NQ;
         const u32 local = wi - __builtin_amdgcn_readfirstlane(a.wi_off[l]);
         const u32 chunk = local / ng, grp = local - chunk * ng;
         const u32 len = __builtin_amdgcn_readfirstlane(ix.list_len[l]);
         const u32 p0 = chunk * a.CH;
         if (p0 >= len) break;   // uniform
         const u32 p1 = min(len, p0 + a.CH);
-        const int nvalid = min(4, (int)(cnt - grp * 4u));
+        const int nvalid = min(NQ, (int)(cnt - grp * (u32)NQ));
 
-        // the queries of the group: thread s < 4 fetches slot s (slots past nvalid repeat slot 0 and can never be candidates)
-        if (tid < 4) {
+        // the queries of the group: thread s < NQ fetches slot s (slots past nvalid repeat slot 0 and can never be candidates)
+        if (tid < NQ) {
             const int ss = tid < nvalid ? tid : 0;
-            const u32 pi = a.bucket_items[a.bucket_off[l] + grp * 4u + ss];
+            const u32 pi = a.bucket_items[a.bucket_off[l] + grp * (u32)NQ + ss];
             const u32 qq = pi / (u32)a.w;
             spi[tid] = pi;
             sqi[tid] = qq;
@@ -648,13 +712,14 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
             sthr[tid] = t0;
             smax[tid] = 0u;
         }
-        if (tid >= 256 && tid < 512) pool[tid - 256] = KEY_MAX;
+        // (the pool's 64 NQ entries: the workgroup's last threads, which fetch no slot)
+        if (tid >= W8_THREADS - 64 * NQ && tid < W8_THREADS) pool[tid - (W8_THREADS - 64 * NQ)] = KEY_MAX;
         __syncthreads();
         // exact pruning of whole work items, as in scan_kernel: no sum of this list lies below its coarse distance
         if (a.prune) {
             bool all = true;
 #pragma unroll
-            for (int s = 0; s < 4; ++s)
+            for (int s = 0; s < NQ; ++s)
                 all = all && (s >= nvalid || __builtin_amdgcn_readfirstlane(__float_as_uint(sdc[s])) > (u32)(readfirstlane64(shard[s]) >> 32));
             if (all) {   // uniform
                 if (tid < nvalid) {
@@ -668,8 +733,15 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         // (a chunk's byte offset pb * 8 stays below 2^31: lists of < 2^28 points)
         const uint8_t *cbase = ix.codes + (int64_t)readfirstlane64((u64)ix.list_codeoff[l]);
 
-        // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), one element per thread: res[ii][t][s], 17 rows of four per sub-quantizer
-        {
+        // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), NQ / 4 elements per thread: res[ii][t][s], 17 rows of NQ per sub-quantizer
+        if constexpr (NQ == 8) {
+            const int tb = tid & 511;
+#pragma unroll
+            for (int e = tb; e < 1024; e += 512) {
+                const int i = e >> 3, s = e & 7;
+                res[(i >> 4) * 136 + (i & 15) * 8 + s] = a.queries[(size_t)sqi[s] * 128 + i] - ix.centroids[(size_t)l * 128 + i];
+            }
+        } else {
             const int tb = tid & 511, i = tb >> 2, s = tb & 3;
             res[tb + (tb >> 6) * 4] = a.queries[(size_t)sqi[s] * 128 + i] - ix.centroids[(size_t)l * 128 + i];
         }
@@ -698,12 +770,65 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         __syncthreads();
         // (2) the f32 entries (index.jl:232-236: df = cb - r, sum += df * df for t ascending; no contraction; two queries per packed
         // instruction: the same IEEE operations element by element), to device memory by label; per-query maxima
-        v4f ent[4];
-        {
+        v4f ent[4][NQ / 4];      // [codeword][queries 4 qh .. 4 qh + 3]
+        if constexpr (NQ == 8) {
+            float mx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const u32 roff = L::RES + (u32)ii * 544u;
+            // four queries at a time (the four-query build on each half of the residual rows; the codewords are requested again)
+            static_for<2>([&](auto qc) {
+                constexpr int qh = decltype(qc)::value;
+                if (qh == 1) ldcw(cwa, 0);
+                v2f sum[4][2];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum[j][0] = sum[j][1] = (v2f){0.0f, 0.0f};
+                // (the rows of a trip -- eight dimensions -- are requested together at its top)
+                v4f rv[8];
+                auto grp = [&](const float4 (&cq)[4], int g2) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const v2f r01 = (v2f){rv[4 * g2 + t].x, rv[4 * g2 + t].y}, r23 = (v2f){rv[4 * g2 + t].z, rv[4 * g2 + t].w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float cv = t == 0 ? cq[j].x : (t == 1 ? cq[j].y : (t == 2 ? cq[j].z : cq[j].w));
+                            const v2f c2 = (v2f){cv, cv};
+                            const v2f d0 = c2 - r01, d1 = c2 - r23;
+                            sum[j][0] = sum[j][0] + d0 * d0;
+                            sum[j][1] = sum[j][1] + d1 * d1;
+                        }
+                    }
+                };
+#pragma unroll 1
+                for (int h = 0; h < 2; ++h) {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(8 * h + t) * 32u + 16u * qh);
+                    ldcw(cwb, 2 * h + 1);
+                    grp(cwa, 0);
+                    ldcw(cwa, h == 0 ? 2 : 3);      // (the second trip repeats a request: no branch around one, no second value to merge)
+                    grp(cwb, 1);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ent[j][qh] = (v4f){sum[j][0].x, sum[j][0].y, sum[j][1].x, sum[j][1].y};
+                    const int c = cg + 64 * j;
+                    const int label = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                    *(v4f *)(gt + ((size_t)(ii * 256 + label) << 3) + 4 * qh) = ent[j][qh];
+                    mx[4 * qh + 0] = fmaxf(mx[4 * qh + 0], ent[j][qh].x);
+                    mx[4 * qh + 1] = fmaxf(mx[4 * qh + 1], ent[j][qh].y);
+                    mx[4 * qh + 2] = fmaxf(mx[4 * qh + 2], ent[j][qh].z);
+                    mx[4 * qh + 3] = fmaxf(mx[4 * qh + 3], ent[j][qh].w);
+                }
+            });
+            // (entries are >= +0: the bit pattern orders like the value; the wave's maximum on the DPP network and the scalar unit)
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const u32 wm = w8_row_max_u32(__float_as_uint(mx[s]));
+                if (lane == 0) atomicMax(&smax[s], wm);
+            }
+        } else {
             v2f sum[4][2];
 #pragma unroll
             for (int j = 0; j < 4; ++j) sum[j][0] = sum[j][1] = (v2f){0.0f, 0.0f};
-            const u32 roff = W8Lds::RES + (u32)ii * 272u;
+            const u32 roff = L::RES + (u32)ii * 272u;
             // (the rows of a trip -- eight dimensions -- are requested together at its top: a request waits ~1 000 cycles in the LDS queue behind
             // the other workgroup's gathers, and the build pays that wait once per batch)
             v4f rv[8];
@@ -731,17 +856,17 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
                 grp(cwb, 1);
             }
 #pragma unroll
-            for (int j = 0; j < 4; ++j) ent[j] = (v4f){sum[j][0].x, sum[j][0].y, sum[j][1].x, sum[j][1].y};
+            for (int j = 0; j < 4; ++j) ent[j][0] = (v4f){sum[j][0].x, sum[j][0].y, sum[j][1].x, sum[j][1].y};
             float mx[4] = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const int c = cg + 64 * j;
                 const int label = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
-                *(v4f *)(gt + ((size_t)(ii * 256 + label) << 2)) = ent[j];
-                mx[0] = fmaxf(mx[0], ent[j].x);
-                mx[1] = fmaxf(mx[1], ent[j].y);
-                mx[2] = fmaxf(mx[2], ent[j].z);
-                mx[3] = fmaxf(mx[3], ent[j].w);
+                *(v4f *)(gt + ((size_t)(ii * 256 + label) << 2)) = ent[j][0];
+                mx[0] = fmaxf(mx[0], ent[j][0].x);
+                mx[1] = fmaxf(mx[1], ent[j][0].y);
+                mx[2] = fmaxf(mx[2], ent[j][0].z);
+                mx[3] = fmaxf(mx[3], ent[j][0].w);
             }
             // (entries are >= +0: the bit pattern orders like the value.  The wave's maximum on the DPP network and the scalar unit: a shuffle
             // is a trip through the LDS queue -- ~1 000 cycles behind the other workgroup's gathers, six of them in a row per query)
@@ -752,32 +877,49 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
             }
         }
         __syncthreads();
-        // (3) quantise (quantize_tables_m8's rule: q = min(4095, floor(t * inv)), inv = 4095 / largest entry of the query) and write the four
-        // copies: copy (cp + lane / 4) mod 4 of sub-quantizer ii -- the 16 lanes of a store's service group write 16 different bank pairs
-        // (consecutive labels are 256 B apart: the same banks).
+        // (3) quantise (quantize_tables_m8's rule: q = min(4095, floor(t * inv)), inv = 4095 / largest entry of the query) and write the
+        // copies of sub-quantizer ii's entry (consecutive labels are 256 B apart: the same banks)
         {
-            float inv[4];
+            float inv[NQ];
 #pragma unroll
-            for (int s = 0; s < 4; ++s) {
+            for (int s = 0; s < NQ; ++s) {
                 const float mxs = __uint_as_float(smax[s]);
                 inv[s] = mxs > 0.0f ? 4095.0f / mxs : 0.0f;
             }
-            if (tid < 4) sinv[tid] = inv[tid];
+            if (tid < NQ) sinv[tid] = inv[tid];
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
-                const float ev[4] = {ent[j].x, ent[j].y, ent[j].z, ent[j].w};
-                u32 f[4];
+                float ev[NQ];
 #pragma unroll
-                for (int s = 0; s < 4; ++s) {
+                for (int qh = 0; qh < NQ / 4; ++qh) {
+                    ev[4 * qh + 0] = ent[j][qh].x;
+                    ev[4 * qh + 1] = ent[j][qh].y;
+                    ev[4 * qh + 2] = ent[j][qh].z;
+                    ev[4 * qh + 3] = ent[j][qh].w;
+                }
+                u32 f[NQ];
+#pragma unroll
+                for (int s = 0; s < NQ; ++s) {
                     const u32 v = (u32)floorf(ev[s] * inv[s]);
                     f[s] = v < 4095u ? v : 4095u;
                 }
-                const uint2 qv = make_uint2(f[0] | (f[1] << 16), f[2] | (f[3] << 16));
-                const int c = cg + 64 * j;
-                const int lb = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
-                const u32 row = ((u32)lb << 8) | ((u32)ii << 3);
+                if constexpr (NQ == 8) {
+                    // two copies, copy (cp + lane / 4) mod 2: the 8 lanes of a 16-byte store's service group write 8 different four-bank groups
+                    const uint4 qv = make_uint4(f[0] | (f[1] << 16), f[2] | (f[3] << 16), f[4] | (f[5] << 16), f[6] | (f[7] << 16));
+                    const int c = cg + 64 * j;
+                    const int lb = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                    const u32 row = ((u32)lb << 8) | ((u32)ii << 4);
 #pragma unroll
-                for (int cp = 0; cp < 4; ++cp) *(uint2 *)(smem + (row | ((u32)((cp + (lane >> 2)) & 3) << 6))) = qv;
+                    for (int cp = 0; cp < 2; ++cp) *(uint4 *)(smem + (row | ((u32)((cp + (lane >> 2)) & 1) << 7))) = qv;
+                } else {
+                    // four copies, copy (cp + lane / 4) mod 4: the 16 lanes of a store's service group write 16 different bank pairs
+                    const uint2 qv = make_uint2(f[0] | (f[1] << 16), f[2] | (f[3] << 16));
+                    const int c = cg + 64 * j;
+                    const int lb = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                    const u32 row = ((u32)lb << 8) | ((u32)ii << 3);
+#pragma unroll
+                    for (int cp = 0; cp < 4; ++cp) *(uint2 *)(smem + (row | ((u32)((cp + (lane >> 2)) & 3) << 6))) = qv;
+                }
             }
         }
         // the wave's first two steps of code bytes: requested here, behind the build (held across it they were spilled: a store that waits
@@ -795,7 +937,7 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         __syncthreads();   // tables complete (LDS copies; the f32 stores have left for L2: the barrier's release covers them)
 
         __builtin_amdgcn_s_setprio(W8_PRIO_SCAN);
-        w8_scan_range(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr);
+        w8_scan_range<NQ>(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr);
         __builtin_amdgcn_s_setprio(W8_PRIO_REST);
 
         // ---- every wave has offered what it had: wave s < nvalid hands slot s of the pool over as it is -- the entries fill from index 0

@@ -14,8 +14,8 @@ def gpu_index(native, oidx):
 
 
 # the two forms of the kernel: (table mode, last_striped, queries per code stream).  Mode 6: four queries per 8-byte entry, four table copies
-# (wg8scan.hip.h); mode 7: eight queries per 16-byte entry, two copies (wg8q8scan.hip.h) -- wherever they are instantiated (default: lists
-# of >= 8192 points; the eight-query form from ten probes per list)
+# (wg8_scan_kernel<4>); mode 7: eight queries per 16-byte entry, two copies (wg8_scan_kernel<8>, same file) -- wherever they are
+# instantiated (default: lists of >= 8192 points; the eight-query form from eight probes per list)
 FORMS = {"q4": (6, 2, 4), "q8": (7, 3, 8)}
 FORM = ["q4"]     # the form the helpers below build (set by the `form` fixture)
 
@@ -152,6 +152,22 @@ def test_eight_wave_kernel_on_long_lists(native):
     pick = np.arange(0, 256, 8)
     exp = oidx.knn_search(qs[pick], 10, 4)
     helpers.assert_same_results(tuple(a[pick] for a in got), exp, what="wg8 default plan")
+
+
+def test_default_plan_picks_the_form(native, form):
+    """No set_tuning, no table mode: the plan's own choice between the two instantiations.  Sixteen lists of 33 000 points (avg_len * m just
+    past 256 KB: the smallest index whose lists count as long, so the plan is list-major and the eight-wave kernel its scan), 96 queries
+    (above the 64-query latency path): w = 2 is 12 probes per list -- eight or more: the eight-query form --, w = 1 is 6: the four-query form."""
+    d, m, kc, n = 128, 8, 16, 16 * 33000
+    oidx, _ = helpers.build_index(5151, n, d, kc, m, 256, mode="random")
+    qs = np.random.default_rng(51).random((96, d), dtype=np.float32)
+    w = {"q8": 2, "q4": 1}[form]
+    g = gpu_index(native, oidx)
+    got = g.search_raw(qs, 10, w)
+    st = g.get_stats()
+    print("default plan, w = %d: last_striped = %d, last_qg = %d" % (w, st["last_striped"], st["last_qg"]))
+    assert st["last_striped"] == striped() and st["last_qg"] == FORMS[form][2], st
+    helpers.assert_same_results(got, oidx.knn_search(qs, 10, w), what="wg8 default plan, w=%d" % w)
 
 
 def test_fuzz_eight_wave_kernel(native):

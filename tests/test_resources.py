@@ -97,20 +97,21 @@ def test_register_budgets(native):
             assert r.get("vgpr_spill_count", 0) == 0, "%s spills %d VGPRs" % (name, r["vgpr_spill_count"])
     # the eight-wave list-major kernel: sixteen waves per CU need <= 128 VGPRs.  Its cold paths (table build, candidate passes, merges) do
     # spill a few registers; what must stay clean is the scan loop itself -- the block with the sixteen-per-half table gathers
-    w8 = {k: v for k, v in res.items() if "wg8_scan_kernel" in k and not k.endswith(".kd")}
-    assert w8, "wg8_scan_kernel not found in the code object"
+    q4, q8 = "wg8_scan_kernelILi4EE", "wg8_scan_kernelILi8EE"    # the two instantiations (queries per code stream)
+    w8 = {k: v for k, v in res.items() if q4 in k and not k.endswith(".kd")}
+    assert w8, "wg8_scan_kernel<4> not found in the code object"
     for name, r in w8.items():
         assert r.get("vgpr_count", 0) <= 128, "%s uses %d VGPRs (budget 128)" % (name, r.get("vgpr_count", 0))
-    w9 = {k: v for k, v in res.items() if "wg8q8_scan_kernel" in k and not k.endswith(".kd")}
-    assert w9, "wg8q8_scan_kernel not found in the code object"
-    for name, r in w9.items():
+    w8q8 = {k: v for k, v in res.items() if q8 in k and not k.endswith(".kd")}
+    assert w8q8, "wg8_scan_kernel<8> not found in the code object"
+    for name, r in w8q8.items():
         assert r.get("vgpr_count", 0) <= 128, "%s uses %d VGPRs (budget 128)" % (name, r.get("vgpr_count", 0))
-    hot9 = [b for b in _kernel_blocks(so, "wg8q8_scan_kernel") if sum("ds_read_b128" in x for x in b) >= 32]
-    assert len(hot9) == 1 and not any("scratch_" in x for x in hot9[0]), "the scan loop of wg8q8_scan_kernel: one block, no scratch memory"
-    blocks = _kernel_blocks(so, "wg8_scan_kernel")
+    hot8 = [b for b in _kernel_blocks(so, q8) if sum("ds_read_b128" in x for x in b) >= 32]
+    assert len(hot8) == 1 and not any("scratch_" in x for x in hot8[0]), "the scan loop of wg8_scan_kernel<8>: one block, no scratch memory"
+    blocks = _kernel_blocks(so, q4)
     hot = [b for b in blocks if sum("ds_read_b64" in x for x in b) >= 32]
     assert len(hot) == 1, "expected ONE block with the step's 32 table gathers, found %d" % len(hot)
-    assert not any("scratch_" in x for x in hot[0]), "the scan loop of wg8_scan_kernel touches scratch memory"
+    assert not any("scratch_" in x for x in hot[0]), "the scan loop of wg8_scan_kernel<4> touches scratch memory"
     assert sum(1 for x in hot[0] if x.startswith("v_")) <= 104, "the scan loop grew: %d vector instructions" % sum(1 for x in hot[0] if x.startswith("v_"))
     stream = [x for x in hot[0] if x.startswith("buffer_load_dwordx4") and "sc1" not in x]
     assert len(stream) == 2, "the step requests its two 16-byte code sets once each: %r" % stream
