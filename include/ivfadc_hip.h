@@ -349,7 +349,10 @@ typedef struct {
     int64_t  coarse_fallbacks; /* queries whose MFMA-filter certificate failed (exact recompute taken)  */
     int32_t  coarse_mfma;      /* 1: the last batch used the MFMA filter + certified exact refine        */
     int32_t  inplace_appends;  /* ivfadc_append calls since creation that were written in place on the device (no re-layout) */
-    int32_t  last_striped;     /* 1: the last list-major launch used bank-striped tables + rotated-order filter sums */
+    int32_t  last_striped;     /* the last list-major launch: 0 = reference-order f32 tables in every lane; 1 = the four-wave kernel with
+                                * bank-striped tables + rotated-order filter sums; 2 / 3 = the eight-wave kernel (wg8scan.hip.h:
+                                * m = 8, dsub = 4 / 8 / 12 / 16, K <= 64), four / eight queries per code stream -- also what a rank
+                                * of the list-partitioned mode reports (ivfadc_set_list_partition) */
     int32_t  coarse_listed;    /* 1: the last batch's coarse filter wrote per-tile records (four smallest keys of every
                                 * (query, 64-centroid tile)) instead of the score matrix, and the top-w enumerated them */
     int64_t  pruned_points;    /* points of probed lists that were NOT scanned: the list's coarse distance already lay above
@@ -442,8 +445,11 @@ int ivfadc_set_query_token(ivfadc_t *h, uint64_t token);
  * rounds for every shape they are instantiated for (also m = 16 / dsub = 6, where they are slower than the exact tables:
  * measurement and tests).  3 / 4 = as 0 / 2 with the matrix-core tables built from the three-product bf16 split of rounds 3-4 instead
  * of ONE f16 product per entry (round 5: power-of-two-scaled f16 operands, half the codeword bytes; the bound is looser by up to half a
- * table unit per entry, which the survivors' exact sums absorb).  5 / 6 = as 0 with the eight-wave list-major kernel (m = 8, dsub = 16,
- * K <= 64: wg8scan.hip.h) never / wherever it is instantiated; 7 = as 6 with its eight-query form (wg8_scan_kernel<8>, same file).  Results are identical in every mode: whatever a filter lets through is recomputed in the reference's
+ * table unit per entry, which the survivors' exact sums absorb).  5 / 6 = as 0 with the eight-wave list-major kernel (wg8scan.hip.h:
+ * m = 8, ksub = 256, K <= 64, dsub = 4 / 8 / 12 / 16, i.e. d = 32 / 64 / 96 / 128; with or without a list partition) never / wherever
+ * it is instantiated; 7 = as 6 with its eight-query form (wg8_scan_kernel<8> and <8, DS>, same file).  Mode 0 takes that kernel on its own
+ * for d = 128 without a list partition, on lists of 8192 points or more; the other widths and the list-partitioned
+ * mode get it through 6 / 7 (stats.last_striped tells which kernel ran).  Results are identical in every mode: whatever a filter lets through is recomputed in the reference's
  * order -- from the f32 tables or, in the matrix-core rounds, from the f32 codebook -- before it meets the bound.       */
 int ivfadc_set_table_mode(ivfadc_t *h, int mode);
 

@@ -315,7 +315,7 @@ struct ivfadc_index {
     // narrow-field list-major scan (nfscan.hip.h; m = 8, dsub = 16, ksub = 256): ||codeword||^2 by codeword index, f32 codewords by label
     DevBuf nf_n2, nf_lab;
     bool allow_nf = true;
-    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 16, ksub = 256, K <= 64): the work items' f32 tables, 32 KB per workgroup
+    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64): the work items' f32 tables, 32 or 64 KB per workgroup
     DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
     int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
     // list-partitioned multi-GPU mode (ivfadc_set_list_partition): this handle scans the probed lists l with l % part_n == part_i only and
@@ -749,6 +749,19 @@ size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool l
 constexpr size_t LDS_MAX = 160 << 10;
 // the eight-wave list-major kernel (wg8scan.hip.h) as the plan's own choice on long lists (ivfadc_set_table_mode(h, 6) asks for it anywhere)
 constexpr double W8_Q8_MIN_PPL = 8.0;   // probes per list from which the eight-query form of the eight-wave kernel is planned
+// sub-space widths the eight-wave kernel is instantiated for (m = 8: d = 32, 64, 96, 128), and the instantiation of a form and a width
+bool w8_dsub(int dsub) { return w8_ds_ok(dsub); }
+typedef void (*wg8_fn_t)(const ScanArgs, float *, const u32 *, u32 *, int);
+wg8_fn_t pick_wg8(bool q8, int dsub)
+{
+    if (dsub == 16) return q8 ? wg8_scan_kernel<8> : wg8_scan_kernel<4>;
+#define X(D_) if (dsub == D_) return q8 ? wg8_scan_kernel<8, D_> : wg8_scan_kernel<4, D_>;
+    X(4) X(8) X(12)
+#undef X
+    return nullptr;
+}
+// ... and where the plan takes the kernel unasked (wg8_mode == 0; table modes 6 / 7 take it wherever it is instantiated): see make_plan
+bool w8_default(const ivfadc_index *h) { return h->dsub == 16 && h->part_n <= 1; }
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
 constexpr size_t MISC_BYTES = 4096 + 256 + 512;
@@ -946,8 +959,8 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // ... and where the eight-wave kernel exists (it is planned below for groups of four) it pays from half a probe per list: scan ms of
         // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
         // 0.316 / 0.544 / 0.92-0.93 (round 6)
-        const bool w8_shape = pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && h->dsub == 16 && h->ksub == 256 && h->d == 128 &&
-                              h->maxlen < ((int64_t)1 << 28) && h->part_n <= 1 && avg_len >= 8192.0;
+        const bool w8_shape = pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
+                              h->maxlen < ((int64_t)1 << 28) && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
         if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
         if (forced) qg = h->force_qg;
         // eight queries per code stream behind the 4-bit narrow-field filter (nfscan.hip.h): conflict-free gathers, a third of the vector
@@ -972,11 +985,13 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // eight waves: lists of at least 8 K points).  Measured on the SIFT1B shape against the four-wave kernel (profiles/r06_w8_sweep.txt,
         // the eight-wave kernel with its workgroup pool): 16 384 queries, scan ms at w = 1 / 8: 1.36 / 5.73 against 1.68 / 7.46;
         // 2048 x w = 8: 1.06 against 1.47.
-        // (positions and byte offsets of a list are 28- / 31-bit quantities in the kernel: lists of fewer than 2^28 points; the
-        // list-partitioned mode keeps the four-wave kernel it was validated with)
-        pl.wg8 = qg == 4 && pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && h->dsub == 16 && h->ksub == 256 && h->d == 128 &&
-                 h->maxlen < ((int64_t)1 << 28) && h->part_n <= 1 &&
-                 (h->wg8_mode > 0 || avg_len >= 8192.0);   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
+        // (positions and byte offsets of a list are 28- / 31-bit quantities in the kernel: lists of fewer than 2^28 points.  The
+        // list-partitioned mode needs nothing of the kernel: the partition is applied in front of it -- the top-w kernel counts this rank's
+        // lists only into list_cnt, which bucket_scan_kernel turns into work items and item_list, bucket_scatter_kernel drops the other
+        // ranks' probes -- and behind it, in merge_kernel; a rank's work items are ordinary ones)
+        pl.wg8 = qg == 4 && pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
+                 h->maxlen < ((int64_t)1 << 28) &&
+                 (h->wg8_mode > 0 || (w8_default(h) && avg_len >= 8192.0));   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
         if (pl.wg8) pl.lds = (size_t)W8Lds<4>::END;
         // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
         // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
@@ -1474,7 +1489,8 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
             h->stats.last_scan_grid = (int)grid;
             h->stats.last_striped = 0;
         } else if (pl.wg8 && !direct) {
-            void (*wk)(const ScanArgs, float *, const u32 *, u32 *, int) = pl.wg8q8 ? wg8_scan_kernel<8> : wg8_scan_kernel<4>;
+            wg8_fn_t wk = pick_wg8(pl.wg8q8, h->dsub);
+            if (!wk) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for dsub = %d, which has no instantiation", h->dsub);
             u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
             HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
             int occ = 0;

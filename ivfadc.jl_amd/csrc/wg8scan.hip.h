@@ -1,5 +1,9 @@
-// wg8scan.hip.h -- list-major scan for long lists, EIGHT waves per workgroup on ONE table set (m = 8, dsub = 16, ksub = 256, K <= 64:
-// the SIFT1B shape), for NQ = 4 or 8 queries per code stream: wg8_scan_kernel<NQ>.  Included by kernels.hip.h, namespace ivf.
+// wg8scan.hip.h -- list-major scan for long lists, EIGHT waves per workgroup on ONE table set (m = 8, ksub = 256, K <= 64; sub-spaces
+// DS = 4, 8, 12 or 16 wide: d = 32, 64, 96 -- the Deep1B-style PQ8 shapes -- and 128, the SIFT1B shape), for NQ = 4 or 8 queries per
+// code stream: wg8_scan_kernel<NQ> (DS = 16) and wg8_scan_kernel<NQ, DS> (DS = 4, 8, 12).  Included by kernels.hip.h, namespace ivf.
+// Only the residual fill and the table build know DS: the scan looks 8 code bytes per point up in a 64 KB integer table whatever the
+// sub-spaces' width, so the scan loop, the pool, the passes and the hand-over are per NQ alone, and the LDS layout is the one of DS = 16
+// (narrower sub-spaces leave residual rows unused).
 //
 // Reference: src/coarsequantizers.jl:40-45 (residuals), src/index.jl:232-236 (table build), :240-246 (scan), :247-254 (bounded top-K).
 //
@@ -52,7 +56,7 @@ template <int NQ> constexpr u32 W8_GTAB_FLOATS = 8u * 256u * (u32)NQ;   // f32 t
 
 template <int NQ> struct W8Lds {
     static_assert(NQ == 4 || NQ == 8, "four or eight queries per code stream");
-    static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (16 x NQ + NQ of padding) x 4 B (a sub-quantizer's block starts NQ banks on)
+    static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (DS x NQ + NQ of padding) x 4 B, sized for DS = 16 (W8_RES_STRIDE)
     static constexpr u32 SMAX = RES + 8u * (16u * NQ + NQ) * 4u;   // u32 [NQ]: bits of the per-query largest entry (atomicMax); f32 inv[NQ] behind
     static constexpr u32 QC = SMAX + 8u * NQ;                 // f32 dc[NQ]; u32 visit-order base[NQ]; u32 probe index[NQ]; u32 query[NQ]
     static constexpr u32 HARD = QC + 16u * NQ;                // u64 [NQ]: the bounds the item started from
@@ -66,6 +70,15 @@ template <int NQ> struct W8Lds {
     static_assert((HARD & 7u) == 0 && (STHR & 7u) == 0 && (POOL & 7u) == 0, "8-byte bounds");
 };
 static_assert(W8Lds<4>::END == 73264u && W8Lds<8>::END == 77904u, "the layout the plan's LDS figures and the measurements were taken with");
+
+// Sub-space widths the kernel is instantiated for (d = 8 DS), and the residuals' floats per sub-quantizer: DS rows of NQ queries and ONE row
+// of padding.  A quad of the table build reads the rows of four neighbouring sub-quantizers at once, 16 B per lane (NQ = 8: 16 B of a
+// 32-byte row): sub-quantizer ii's block starts (DS + 1) ii rows on, and DS + 1 is ODD for every DS here, so ii -> (DS + 1) ii is
+// one-to-one modulo 16 four-bank groups (NQ = 4: 17, 13, 9 and 5 ii mod 16 are four different groups for ii = 0 .. 3 and for 4 .. 7) and
+// modulo 8 eight-bank groups (NQ = 8): the quad's four lanes read four different bank groups at DS = 4, 8, 12 and 16 alike.  Without
+// the padding row the blocks would start DS ii rows apart: the same group twice or four times over (DS = 16: always the same one).
+constexpr bool w8_ds_ok(int ds) { return ds == 4 || ds == 8 || ds == 12 || ds == 16; }
+template <int NQ, int DS> constexpr u32 W8_RES_STRIDE = (u32)((DS + 1) * NQ);
 
 static __device__ __forceinline__ u32 w8_perm(u32 s0, u32 s1, u32 sel)
 {
@@ -640,11 +653,16 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 // neighbours in the queue: the item range is cut into one contiguous part per XCD and a workgroup pulls from the part of the XCD it runs
 // on (HW_REG_XCC_ID) -- the groups that stream the same list then run side by side under ONE L2 and the list crosses the fabric once.
 // Placement is a matter of speed only: a workgroup whose part is exhausted moves on to the next one; every wave leaves when all are.
-template <int NQ>
-__global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
-                                                                 u32 *__restrict__ xq, int nranges)
+template <int NQ, int DS>
+static __device__ __forceinline__ void w8_scan_items(const ScanArgs &a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
+                                                     u32 *__restrict__ xq, int nranges)
 {
     using L = W8Lds<NQ>;
+    static_assert(w8_ds_ok(DS), "sub-spaces of 4, 8, 12 or 16 dimensions");
+    static_assert(8u * W8_RES_STRIDE<NQ, DS> * 4u <= L::SMAX - L::RES, "the residuals fit the block sized for DS = 16");
+    constexpr int D = 8 * DS;               // m = 8
+    constexpr u32 RS = W8_RES_STRIDE<NQ, DS>;
+    constexpr int G = DS / 4;               // 16-byte groups of a codeword
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
     const IndexView &ix = a.ix;
     const int tid = threadIdx.x, lane = tid & 63;
@@ -733,17 +751,19 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         // (a chunk's byte offset pb * 8 stays below 2^31: lists of < 2^28 points)
         const uint8_t *cbase = ix.codes + (int64_t)readfirstlane64((u64)ix.list_codeoff[l]);
 
-        // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), NQ / 4 elements per thread: res[ii][t][s], 17 rows of NQ per sub-quantizer
+        // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), D NQ elements -- NQ / 4 per thread at DS = 16, fewer or none below:
+        // res[ii][t][s], DS + 1 rows of NQ per sub-quantizer (W8_RES_STRIDE)
         if constexpr (NQ == 8) {
-            const int tb = tid & 511;
+            const u32 tb = (u32)tid & 511u;
 #pragma unroll
-            for (int e = tb; e < 1024; e += 512) {
-                const int i = e >> 3, s = e & 7;
-                res[(i >> 4) * 136 + (i & 15) * 8 + s] = a.queries[(size_t)sqi[s] * 128 + i] - ix.centroids[(size_t)l * 128 + i];
+            for (u32 e = tb; e < 8u * D; e += 512u) {
+                const u32 i = e >> 3, s = e & 7u;
+                res[(i / DS) * RS + (i % DS) * 8u + s] = a.queries[(size_t)sqi[s] * D + i] - ix.centroids[(size_t)l * D + i];
             }
         } else {
+            // (element tb = 4 i + s stands 4 (i / DS) floats on: the padding rows of the sub-quantizers below its own)
             const int tb = tid & 511, i = tb >> 2, s = tb & 3;
-            res[tb + (tb >> 6) * 4] = a.queries[(size_t)sqi[s] * 128 + i] - ix.centroids[(size_t)l * 128 + i];
+            if (DS == 16 || tb < 4 * D) res[tb + (i / DS) * 4] = a.queries[(size_t)sqi[s] * D + i] - ix.centroids[(size_t)l * D + i];
         }
         // (the thread number passes through an opaque move inside the item loop: the lane-constant addresses it feeds -- codewords, table
         // rows, LDS slots -- would otherwise be hoisted to kernel entry and live, spilled, across the whole persistent loop)
@@ -756,12 +776,14 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         // service group hold 4 sub-quantizers x 4 copies.
         const int ii = (tidb & 3) | (((tidb >> 6) & 1) << 2);
         const int cg = ((tidb >> 2) & 15) | ((tidb >> 7) << 4);
-        const float4 *ct = (const float4 *)ix.codebooks_t;        // [ii][g][c][4], ksub = 256
-        // The four codewords come four dimensions at a time (g = 0 .. 3), two register sets that take turns inside a REAL loop of two
-        // trips: fully unrolled, the scheduler hoists every request of the build above the arithmetic -- 64 registers of codewords next to
-        // 64 of residual rows -- and spills them as they arrive, a wait for memory each.
+        const float4 *ct = (const float4 *)ix.codebooks_t;        // [ii][g][c][4], G = DS / 4 groups, ksub = 256
+        // The four codewords come four dimensions at a time (g = 0 .. G - 1), two register sets that take turns inside a REAL loop of
+        // G / 2 trips, two groups each: fully unrolled, the scheduler hoists every request of the build above the arithmetic -- 64 registers
+        // of codewords next to 64 of residual rows -- and spills them as they arrive, a wait for memory each.  An odd count (DS = 4: one
+        // group, DS = 12: three) leaves its last group behind the loop: it stands in cwa by then -- requested up front (G = 1) or by the
+        // trip's second request (G = 3) -- and takes four rows of its own.  Dimensions ascend through trips and tail: the reference's order.
         float4 cwa[4], cwb[4];
-        const u32 cofs = (u32)ii * 1024u + (u32)cg;
+        const u32 cofs = (u32)ii * (u32)(G * 256) + (u32)cg;
         auto ldcw = [&](float4 (&d)[4], int g) __attribute__((always_inline)) {
 #pragma unroll
             for (int j = 0; j < 4; ++j) d[j] = ct[cofs + (u32)(g * 256 + 64 * j)];
@@ -773,7 +795,7 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         v4f ent[4][NQ / 4];      // [codeword][queries 4 qh .. 4 qh + 3]
         if constexpr (NQ == 8) {
             float mx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            const u32 roff = L::RES + (u32)ii * 544u;
+            const u32 roff = L::RES + (u32)ii * (RS * 4u);
             // four queries at a time (the four-query build on each half of the residual rows; the codewords are requested again)
             static_for<2>([&](auto qc) {
                 constexpr int qh = decltype(qc)::value;
@@ -798,13 +820,18 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
                     }
                 };
 #pragma unroll 1
-                for (int h = 0; h < 2; ++h) {
+                for (int h = 0; h < G / 2; ++h) {
 #pragma unroll
                     for (int t = 0; t < 8; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(8 * h + t) * 32u + 16u * qh);
                     ldcw(cwb, 2 * h + 1);
                     grp(cwa, 0);
-                    ldcw(cwa, h == 0 ? 2 : 3);      // (the second trip repeats a request: no branch around one, no second value to merge)
+                    if constexpr (G > 2) ldcw(cwa, h == 0 ? 2 : G - 1);      // (the last trip of an even count repeats a request: no branch around one, no second value to merge)
                     grp(cwb, 1);
+                }
+                if constexpr (G & 1) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(4 * (G - 1) + t) * 32u + 16u * qh);
+                    grp(cwa, 0);
                 }
 #pragma unroll
                 for (int j = 0; j < 4; ++j) {
@@ -828,7 +855,7 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
             v2f sum[4][2];
 #pragma unroll
             for (int j = 0; j < 4; ++j) sum[j][0] = sum[j][1] = (v2f){0.0f, 0.0f};
-            const u32 roff = L::RES + (u32)ii * 272u;
+            const u32 roff = L::RES + (u32)ii * (RS * 4u);
             // (the rows of a trip -- eight dimensions -- are requested together at its top: a request waits ~1 000 cycles in the LDS queue behind
             // the other workgroup's gathers, and the build pays that wait once per batch)
             v4f rv[8];
@@ -847,13 +874,18 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
                 }
             };
 #pragma unroll 1
-            for (int h = 0; h < 2; ++h) {
+            for (int h = 0; h < G / 2; ++h) {
 #pragma unroll
                 for (int t = 0; t < 8; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(8 * h + t) * 16u);
                 ldcw(cwb, 2 * h + 1);
                 grp(cwa, 0);
-                ldcw(cwa, h == 0 ? 2 : 3);      // (the second trip repeats a request: no branch around one, no second value to merge)
+                if constexpr (G > 2) ldcw(cwa, h == 0 ? 2 : G - 1);      // (the last trip of an even count repeats a request: no branch around one, no second value to merge)
                 grp(cwb, 1);
+            }
+            if constexpr (G & 1) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(4 * (G - 1) + t) * 16u);
+                grp(cwa, 0);
             }
 #pragma unroll
             for (int j = 0; j < 4; ++j) ent[j][0] = (v4f){sum[j][0].x, sum[j][0].y, sum[j][1].x, sum[j][1].y};
@@ -961,4 +993,20 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
         __syncthreads();
         wi = __builtin_amdgcn_readfirstlane(swi[0]);
     }
+}
+
+// The entry points.  wg8_scan_kernel<NQ> is the kernel of DS = 16 (d = 128) under the name it has always had -- what the profiles, the
+// counters' kernel filters and the register-budget test look for; wg8_scan_kernel<NQ, DS> are the narrower sub-spaces.
+template <int NQ>
+__global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
+                                                                 u32 *__restrict__ xq, int nranges)
+{
+    w8_scan_items<NQ, 16>(a, gtabs, item_list, xq, nranges);
+}
+template <int NQ, int DS>
+__global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
+                                                                 u32 *__restrict__ xq, int nranges)
+{
+    static_assert(DS != 16, "DS = 16 is wg8_scan_kernel<NQ>");
+    w8_scan_items<NQ, DS>(a, gtabs, item_list, xq, nranges);
 }

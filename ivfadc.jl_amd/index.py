@@ -418,7 +418,11 @@ class IVFADCIndex:
     def set_table_mode(self, mode):
         """0: automatic (filter tables where they exist and pay), 1: the reference's f32 tables in every lane, 2: as 0 plus the
         matrix-core lower-bound rounds for every shape they are instantiated for; 3 / 4: as 0 / 2 with those tables built from the
-        three-product bf16 split instead of one f16 product per entry."""
+        three-product bf16 split instead of one f16 product per entry; 5 / 6: as 0 with the eight-wave list-major kernel never /
+        wherever it is instantiated -- m = 8, ksub = 256, K <= 64, d = 32 / 64 / 96 / 128 (dsub = 4 / 8 / 12 / 16), with or without a list
+        partition (set_list_partition); 7: as 6 with its eight-query form.  Mode 0 takes that kernel unasked for d = 128 without a list
+        partition on lists of 8192 points or more; get_stats()["last_striped"] is 2 / 3 when its four- / eight-query form ran.
+        Results are the same bytes in every mode."""
         nat.check(nat.lib().ivfadc_set_table_mode(self._h, int(mode)))
 
     def debug_lb_table(self, query, cell):
