@@ -315,9 +315,11 @@ struct ivfadc_index {
     // narrow-field list-major scan (nfscan.hip.h; m = 8, dsub = 16, ksub = 256): ||codeword||^2 by codeword index, f32 codewords by label
     DevBuf nf_n2, nf_lab;
     bool allow_nf = true;
-    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64): the work items' f32 tables, 32 or 64 KB per workgroup
+    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64, with the wide pool K <= 128): the work items'
+    // f32 tables, 32 or 64 KB per workgroup
     DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
     int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
+    bool wg8_wide = false;       // table modes 8 / 9: 64 < K <= 128 runs the kernel's wide-pool form (wg8_wide_scan_kernel) wherever wg8_mode takes the kernel
     // list-partitioned multi-GPU mode (ivfadc_set_list_partition): this handle scans the probed lists l with l % part_n == part_i only and
     // leaves partial top-K keys; partial_keys: where the running call wants them (null: ids as usual); the batch whose probe arrays stand
     int part_n = 1, part_i = 0;
@@ -760,6 +762,15 @@ wg8_fn_t pick_wg8(bool q8, int dsub)
 #undef X
     return nullptr;
 }
+// the wide-pool form (two pool entries per lane: 64 < K <= 128; table modes 8 / 9)
+constexpr int W8_WIDE_MAX_K = 128;
+wg8_fn_t pick_wg8_wide(bool q8, int dsub)
+{
+#define X(D_) if (dsub == D_) return q8 ? wg8_wide_scan_kernel<8, D_> : wg8_wide_scan_kernel<4, D_>;
+    X(4) X(8) X(12) X(16)
+#undef X
+    return nullptr;
+}
 // ... and where the plan takes the kernel unasked (wg8_mode == 0; table modes 6 / 7 take it wherever it is instantiated): see make_plan
 bool w8_default(const ivfadc_index *h) { return h->dsub == 16 && h->part_n <= 1; }
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
@@ -773,6 +784,7 @@ struct Plan {
     bool lb;            // query-major rounds with 8-bit lower-bound tables from the matrix cores (lbscan.hip.h)
     bool nf;            // list-major with the narrow-field integer filter, eight queries per code stream (nfscan.hip.h)
     bool wg8q8;         // ... its eight-query form (wg8_scan_kernel<8>)
+    bool wg8wide;       // ... with the wide pool (64 < K <= 128: wg8_wide_scan_kernel; the merge behind it is the one of K > 64)
     bool wg8;           // list-major, eight waves per workgroup on four conflict-free copies of the integer filter table (wg8scan.hip.h)
     bool lanes;         // several batches in flight on this replica: stand-alone top-w, a wave per query (see make_plan)
     bool twolevel;      // coarse stage: certified two-level search (twolevel.hip.h) instead of the exhaustive kernels + top-w
@@ -836,7 +848,7 @@ int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
     pl.cap = 64;
     pl.capw = pl.small_w ? 64 : std::max(128, pow2ceil(w + 64));
     pl.query_major = false;
-    pl.fuse_topw = pl.lb = pl.nf = pl.wg8 = pl.wg8q8 = false;
+    pl.fuse_topw = pl.lb = pl.nf = pl.wg8 = pl.wg8q8 = pl.wg8wide = false;
     pl.coarse_mfma = h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
     pl.twolevel = h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
                   (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
@@ -904,6 +916,7 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
     pl.maxch = 1;
     pl.wg8 = false;
     pl.wg8q8 = false;
+    pl.wg8wide = false;
     pl.fuse_topw = false;
     pl.lb = false;
     pl.nf = false;
@@ -959,7 +972,10 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // ... and where the eight-wave kernel exists (it is planned below for groups of four) it pays from half a probe per list: scan ms of
         // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
         // 0.316 / 0.544 / 0.92-0.93 (round 6)
-        const bool w8_shape = pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
+        // (K the kernel's pool holds: 64, or 128 where table mode 8 / 9 asks for the wide pool -- a request, so wg8_mode > 0 there)
+        const bool w8_wide_k = !pl.small_k && h->wg8_wide && h->wg8_mode > 0 && K <= W8_WIDE_MAX_K;
+        const bool w8_k = pl.small_k || w8_wide_k;
+        const bool w8_shape = w8_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
                               h->maxlen < ((int64_t)1 << 28) && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
         if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
         if (forced) qg = h->force_qg;
@@ -977,8 +993,10 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
             pl.lds = (size_t)NfLds::END;
         } else {
         // keep two workgroups per CU when possible (a forced width only yields to the hard LDS limit)
-        while (qg > 1 && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
-        if (scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
+        // (groups of four that the wide-pool kernel takes below need none of the four-wave kernel's LDS selectors: its budget does not narrow them)
+        const bool w8_wide_ok = w8_wide_k && h->allow_filt && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 && h->maxlen < ((int64_t)1 << 28);
+        while (qg > 1 && !(qg == 4 && w8_wide_ok) && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
+        if (!(qg == 4 && w8_wide_ok) && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
         pl.qg = qg;
         pl.lds = scan_lds_bytes(h, qg, pl.cap, pl.small_k, true);
         // four queries per code stream on long lists of the m = 8 / dsub = 16 shape: the eight-wave kernel (a work item must feed
@@ -989,17 +1007,18 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // list-partitioned mode needs nothing of the kernel: the partition is applied in front of it -- the top-w kernel counts this rank's
         // lists only into list_cnt, which bucket_scan_kernel turns into work items and item_list, bucket_scatter_kernel drops the other
         // ranks' probes -- and behind it, in merge_kernel; a rank's work items are ordinary ones)
-        pl.wg8 = qg == 4 && pl.small_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
+        pl.wg8 = qg == 4 && w8_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
                  h->maxlen < ((int64_t)1 << 28) &&
                  (h->wg8_mode > 0 || (w8_default(h) && avg_len >= 8192.0));   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
-        if (pl.wg8) pl.lds = (size_t)W8Lds<4>::END;
+        pl.wg8wide = pl.wg8 && !pl.small_k;
+        if (pl.wg8) pl.lds = pl.wg8wide ? (size_t)W8Lds<4, 2>::END : (size_t)W8Lds<4>::END;
         // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
         // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
         pl.wg8q8 = pl.wg8 && (h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W8_Q8_MIN_PPL));
         if (pl.wg8q8) {
             qg = 8;
             pl.qg = 8;
-            pl.lds = (size_t)W8Lds<8>::END;
+            pl.lds = pl.wg8wide ? (size_t)W8Lds<8, 2>::END : (size_t)W8Lds<8>::END;
         }
         }
         // chunk size: enough work items to fill the chip, as few table rebuilds as possible.  Two items per CU is the
@@ -1489,7 +1508,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
             h->stats.last_scan_grid = (int)grid;
             h->stats.last_striped = 0;
         } else if (pl.wg8 && !direct) {
-            wg8_fn_t wk = pick_wg8(pl.wg8q8, h->dsub);
+            wg8_fn_t wk = pl.wg8wide ? pick_wg8_wide(pl.wg8q8, h->dsub) : pick_wg8(pl.wg8q8, h->dsub);
             if (!wk) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for dsub = %d, which has no instantiation", h->dsub);
             u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
             HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
@@ -1502,7 +1521,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
             HIP_TRY(hipGetLastError());
             if (h->profiling) TRY(ev_end(h, ep));
             h->stats.last_scan_grid = (int)grid;
-            h->stats.last_striped = pl.wg8q8 ? 3 : 2;
+            h->stats.last_striped = (pl.wg8wide ? 4 : 2) + (pl.wg8q8 ? 1 : 0);
         } else if (pl.nf) {
             // four points per lane and step (measured: two 9.2 ms, eight 8.1 ms -- and 74 spilled registers -- against 7.76 ms)
             void (*nk)(const ScanArgs, const NfView) = nf_scan_kernel<4>;
@@ -2765,7 +2784,7 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
 // settings that change how a search runs, copied to the internal second lane before every use
 static void copy_search_config(ivfadc_index *dst, const ivfadc_index *src)
 {
-    dst->wg8_mode = src->wg8_mode;
+    dst->wg8_mode = src->wg8_mode; dst->wg8_wide = src->wg8_wide;
     dst->allow_nf = src->allow_nf; dst->allow_sq = src->allow_sq; dst->sq_inside = src->sq_inside; dst->allow_lb = src->allow_lb;
     dst->force_lb = src->force_lb; dst->allow_bf16 = src->allow_bf16; dst->allow_f16 = src->allow_f16; dst->lb_use_f16 = src->lb_use_f16; dst->allow_prune = src->allow_prune; dst->allow_listed = src->allow_listed;
     dst->allow_filt = src->allow_filt; dst->allow_mfma = src->allow_mfma; dst->mfma_min_kc = src->mfma_min_kc; dst->ws_budget = src->ws_budget;
@@ -4470,14 +4489,17 @@ int ivfadc_set_table_mode(ivfadc_t *h, int mode)
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    if (mode < 0 || mode > 7) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 7");
+    if (mode < 0 || mode > 9) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 9");
     h->allow_filt = mode != 1 && getenv("IVFADC_EXACT_TABLES") == nullptr;
     h->force_lb = mode == 2 || mode == 4;
     // 3 / 4: as 0 / 2 with the matrix-core tables built from the three-product bf16 split instead of one f16 product (A/B runs, tests)
     h->lb_use_f16 = mode != 3 && mode != 4;
     // 5 / 6: as 0 with the eight-wave list-major kernel (wg8scan.hip.h) never / wherever it is instantiated (A/B runs, tests);
     // 7: as 6 with its eight-query form (wg8_scan_kernel<8>) wherever that is instantiated
-    h->wg8_mode = mode == 5 ? -1 : (mode == 6 ? 1 : (mode == 7 ? 2 : 0));
+    // 8 / 9: as 6 / 7, and for 64 < K <= 128 the kernel's wide-pool form (wg8_wide_scan_kernel: two pool entries per lane) instead of the
+    // four-wave kernel with LDS selectors; K <= 64 and K > 128 run exactly what 6 / 7 run
+    h->wg8_mode = mode == 5 ? -1 : (mode == 6 || mode == 8 ? 1 : (mode == 7 || mode == 9 ? 2 : 0));
+    h->wg8_wide = mode == 8 || mode == 9;
     return IVFADC_OK;
 } IVF_CATCH
 

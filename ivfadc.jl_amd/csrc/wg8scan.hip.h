@@ -1,6 +1,10 @@
 // wg8scan.hip.h -- list-major scan for long lists, EIGHT waves per workgroup on ONE table set (m = 8, ksub = 256, K <= 64; sub-spaces
 // DS = 4, 8, 12 or 16 wide: d = 32, 64, 96 -- the Deep1B-style PQ8 shapes -- and 128, the SIFT1B shape), for NQ = 4 or 8 queries per
 // code stream: wg8_scan_kernel<NQ> (DS = 16) and wg8_scan_kernel<NQ, DS> (DS = 4, 8, 12).  Included by kernels.hip.h, namespace ivf.
+// 64 < K <= 128 runs the same body with a pool of TWO entries per lane (KP = 2: wg8_wide_scan_kernel<NQ, DS>, every DS; on request, table
+// modes 8 / 9): the pool is the only thing in the kernel that is tied to 64 -- filter, bias test, rings and passes are per point, the
+// cold-start bounds take the ceil(K / 8)-th and K-th of a step's 256 sums -- see THE WIDE POOL at w8_pool_offer.  KP = 1 is the code that
+// every measurement below was taken with, unchanged behind `if constexpr`.
 // Only the residual fill and the table build know DS: the scan looks 8 code bytes per point up in a 64 KB integer table whatever the
 // sub-spaces' width, so the scan loop, the pool, the passes and the hand-over are per NQ alone, and the LDS layout is the one of DS = 16
 // (narrower sub-spaces leave residual rows unused).
@@ -54,22 +58,29 @@ constexpr int W8_ES = 3;                      // dwords per parked point: code b
 constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (32 / NQ copies x 8 sub-quantizers x 2 NQ bytes)
 template <int NQ> constexpr u32 W8_GTAB_FLOATS = 8u * 256u * (u32)NQ;   // f32 tables of a work item in device memory: [ii][label][NQ queries]
 
-template <int NQ> struct W8Lds {
+// KP: the pool's entries per lane (1: K <= 64, the layout of every measurement so far; 2: K <= 128, the wide pool -- see w8_pool_offer)
+template <int NQ, int KP = 1> struct W8Lds {
     static_assert(NQ == 4 || NQ == 8, "four or eight queries per code stream");
+    static_assert(KP == 1 || KP == 2, "one or two pool entries per lane");
     static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (DS x NQ + NQ of padding) x 4 B, sized for DS = 16 (W8_RES_STRIDE)
     static constexpr u32 SMAX = RES + 8u * (16u * NQ + NQ) * 4u;   // u32 [NQ]: bits of the per-query largest entry (atomicMax); f32 inv[NQ] behind
     static constexpr u32 QC = SMAX + 8u * NQ;                 // f32 dc[NQ]; u32 visit-order base[NQ]; u32 probe index[NQ]; u32 query[NQ]
     static constexpr u32 HARD = QC + 16u * NQ;                // u64 [NQ]: the bounds the item started from
     static constexpr u32 STHR = HARD + 8u * NQ;               // u64 [NQ]: workgroup-shared bounds
     static constexpr u32 SWI = STHR + 8u * NQ;                // u32 [4]
-    static constexpr u32 POOL = SWI + 16u;                    // u64 [NQ][64]: the workgroup's K smallest keys per slot, unordered (w8_pool_offer)
-    static constexpr u32 PARK = POOL + NQ * 64u * 8u;         // u32 [8][32][W8_ES]: the waves' rings of parked points (W8_RING)
+    static constexpr u32 POOL = SWI + 16u;                    // u64 [NQ][64 KP]: the workgroup's K smallest keys per slot, unordered (w8_pool_offer)
+    static constexpr u32 POOL_SLOT = 64u * KP * 8u;           // bytes of a slot's pool
+    static constexpr u32 PARK = POOL + NQ * POOL_SLOT;        // u32 [8][32][W8_ES]: the waves' rings of parked points (W8_RING)
     static constexpr u32 COLD = PARK + (u32)W8_NW * 32u * W8_ES * 4u;     // u32 [NQ][16]: a cold work item's first step, every wave's ceil(K / 8)-th smallest integer sum per slot
-    static constexpr u32 END = COLD + 64u * NQ;               // (up to sixteen waves)
+    // (KP = 1: up to sixteen waves; the wide pool's 8 NQ more entries leave the eight-query form room for the eight waves there are: u32 [NQ][8])
+    static constexpr u32 COLD_SLOT = KP == 1 ? 64u : 4u * (u32)W8_NW;
+    static constexpr u32 END = COLD + COLD_SLOT * NQ;
     static_assert(END <= 80u * 1024u, "two workgroups per CU");
     static_assert((HARD & 7u) == 0 && (STHR & 7u) == 0 && (POOL & 7u) == 0, "8-byte bounds");
 };
 static_assert(W8Lds<4>::END == 73264u && W8Lds<8>::END == 77904u, "the layout the plan's LDS figures and the measurements were taken with");
+static_assert(W8Lds<4, 2>::END == 75184u && W8Lds<8, 2>::END == 81744u, "the wide pool's layouts: 2 / 4 KB more pool, 32 B per slot of cold-start words");
+static_assert(W8Lds<4, 2>::POOL == W8Lds<4>::POOL && W8Lds<8, 2>::POOL == W8Lds<8>::POOL, "everything in front of the pool stands where the helpers below read it");
 
 // Sub-space widths the kernel is instantiated for (d = 8 DS), and the residuals' floats per sub-quantizer: DS rows of NQ queries and ONE row
 // of padding.  A quad of the table build reads the rows of four neighbouring sub-quantizers at once, 16 B per lane (NQ = 8: 16 B of a
@@ -149,6 +160,16 @@ static __device__ __forceinline__ u32 w8_and_rebased(const u32 (&q)[4], const u3
 //   K smallest keys of all offers are never refused and never dropped: the pool ends as the exact top K in any interleaving (ids and
 //   distances bit-identical to the oracle); the order is restored by one 64-lane sort when the work item is done.
 //   The maximum of ANY snapshot -- K distinct keys that were offered -- is an upper bound of the K-th key: published with atomicMin.
+// THE WIDE POOL (KP = 2, 64 < K <= 128; wg8_wide_scan_kernel).  A slot holds 128 entries, lane l owns entries l and l + 64 and a snapshot
+// is two values per lane (v: entries 0 .. 63, vh: entries 64 .. 127; entries >= K read 0).  Nothing above counts lanes: an offer reads the K
+// entries, mx is the wave's maximum of the per-lane maxima -- the value of ONE entry below K, keys being unique -- and the swap's target is the
+// lowest index whose snapshot value is mx (a ballot on the low entries, then one on the high ones: empty entries are KEY_MAX, so the pool
+// still fills from index 0, and an index is filled only by a wave whose snapshot showed every lower one filled -- the hand-over's prefix).
+// Dropping mx is safe as before: the other K - 1 entries are at or below their snapshot values, all below mx.  TERMINATION of the offer loop:
+// every trip either swaps a key in (the mask loses a bit) or fails, and a failed swap returns the value of the moment of the entry that was
+// ADDRESSED, which is below its snapshot value mx (entries only decrease, and it is not mx); that value is patched into the half of the
+// snapshot the index came from -- v for idx < 64, vh for idx >= 64, lane idx mod 64 -- so the sum of the snapshot strictly falls.  (A patch
+// into the other half would leave the addressed entry's snapshot at mx: the same swap fails for ever.)
 static __device__ __forceinline__ u32 w8_row_max_u32(u32 x)
 {
     // running maximum along each row of 16 lanes (row_shr 1, 2, 4, 8: a lane without a source reads 0), rows' last lanes -> scalar unit
@@ -167,20 +188,55 @@ static __device__ __forceinline__ u64 w8_wave_max_u64(u64 v)
     const u32 ml = w8_row_max_u32(hi == mh ? lo : 0u);
     return ((u64)mh << 32) | ml;
 }
-// the pool's entries of slot s, one per lane (lanes >= K: 0, below every key)
-template <int NQ> static __device__ __forceinline__ u64 w8_pool_read(int s, int K, int lane)
+// the pool's entries of slot s, one per lane (lanes >= K: 0, below every key); KP = 2: entry lane + 64 half of the slot (half = 0, 1)
+template <int NQ, int KP = 1> static __device__ __forceinline__ u64 w8_pool_read(int s, int K, int lane, int half = 0)
 {
-    return lane < K ? w8_lds<u64>(W8Lds<NQ>::POOL + 512u * (u32)s + 8u * (u32)lane) : 0ull;
+    if constexpr (KP == 1) {
+        return lane < K ? w8_lds<u64>(W8Lds<NQ>::POOL + 512u * (u32)s + 8u * (u32)lane) : 0ull;
+    } else {
+        const int e = lane + 64 * half;
+        return e < K ? w8_lds<u64>(W8Lds<NQ, 2>::POOL + 1024u * (u32)s + 8u * (u32)e) : 0ull;
+    }
 }
 // Offers the keys of the lanes in `mask` (uniform, non-empty) to slot s, starting from the snapshot v the caller read a while ago.  A stale
 // snapshot is as good as a fresh one for every decision above -- each of its values WAS that entry's, entries only decrease -- it merely
 // fails a swap more often, and a failed swap returns the entry's value of the moment: the snapshot is patched and the offer goes on
 // without another read.  An offer costs one LDS round trip per swap attempt (under the scan's gathers a round trip is several hundred
 // cycles: the dependent trips, not the instructions, were the cost of a pass).  Returns the slot's new bound, KEY_MAX if nothing went in
-// or the pool is not full.
-template <int NQ> static __device__ __forceinline__ u64 w8_pool_offer(int s, u64 v, u64 key, u64 mask, int K, int lane)
+// or the pool is not full.  (KP = 2: vh is the snapshot of entries 64 .. 127; KP = 1 has none.)
+template <int NQ, int KP = 1> static __device__ __forceinline__ u64 w8_pool_offer(int s, u64 v, u64 key, u64 mask, int K, int lane, u64 vh = 0ull)
 {
     bool any = false;
+    if constexpr (KP == 2) {
+        u64 *pool = w8_ptr<u64>(W8Lds<NQ, 2>::POOL + 1024u * (u32)s);
+        u64 mx = w8_wave_max_u64(v > vh ? v : vh);
+        for (;;) {   // uniform; terminates: see THE WIDE POOL above
+            mask &= __builtin_amdgcn_ballot_w64(key < mx);
+            if (mask == 0) break;
+            const int src = __builtin_ctzll(mask);
+            const u64 x = readlane64(key, src);
+            // the lowest index whose snapshot is mx: low entries first (mx is one entry's value, so one of the two ballots is not empty;
+            // an index is never formed from an empty one)
+            const u64 blo = __builtin_amdgcn_ballot_w64(lane < K && v == mx), bhi = __builtin_amdgcn_ballot_w64(lane + 64 < K && vh == mx);
+            if ((blo | bhi) == 0) break;
+            const bool high = blo == 0;
+            const int il = __builtin_ctzll(high ? bhi : blo);    // the owning lane; the entry is il + 64 high < K
+            u64 old = 0;
+            if (lane == 0) old = atomicCAS((unsigned long long *)&pool[il + (high ? 64 : 0)], (unsigned long long)mx, (unsigned long long)x);
+            old = readfirstlane64(old);
+            const u64 now = old == mx ? x : old;   // the addressed entry's value of the moment: x is in, or another wave's key sits there
+            if (high) vh = lane == il ? now : vh;  // (uniform) the half that was addressed, and only that one
+            else v = lane == il ? now : v;
+            if (old == mx) {   // (uniform)
+                any = true;
+                mask &= mask - 1ull;
+            }
+            mx = w8_wave_max_u64(v > vh ? v : vh);
+        }
+        if (!any || mx == KEY_MAX) return KEY_MAX;
+        if (lane == 0) atomicMin(w8_ptr<u64>(W8Lds<NQ>::STHR + 8u * (u32)s), mx);
+        return mx;
+    } else {
     u64 *pool = w8_ptr<u64>(W8Lds<NQ>::POOL + 512u * (u32)s);
     u64 mx = w8_wave_max_u64(v);
     for (;;) {   // uniform
@@ -204,6 +260,7 @@ template <int NQ> static __device__ __forceinline__ u64 w8_pool_offer(int s, u64
     if (!any || mx == KEY_MAX) return KEY_MAX;
     if (lane == 0) atomicMin(w8_ptr<u64>(W8Lds<NQ>::STHR + 8u * (u32)s), mx);
     return mx;
+    }
 }
 
 // ---- reference-order sums of parked points, 8 per pass, entries from the work item's f32 tables in device memory -------------------
@@ -257,7 +314,7 @@ template <int NQ> static __device__ __forceinline__ void w8_pass_issue(W8Pass<NQ
 // bias arithmetic's operands -- requested in one go ahead of the running sums, the bias computed from registers: 16 384 x w = 8
 // 5.87 -> 5.91 ms, w = 1 1.38 -> 1.44.  The pass does not wait for memory -- 260 of its 7 700 cycles, by cycle counters -- it is ~400 dependent
 // instructions on a SIMD it shares with three scanning waves.)
-template <int NQ> static __device__ __forceinline__ void w8_pass_finish(const W8Pass<NQ> &ps, int nvalid, int K, int lane)
+template <int NQ, int KP = 1> static __device__ __forceinline__ void w8_pass_finish(const W8Pass<NQ> &ps, int nvalid, int K, int lane)
 {
     const int ii = lane & 7;
     float ev[NQ];
@@ -281,7 +338,11 @@ template <int NQ> static __device__ __forceinline__ void w8_pass_finish(const W8
         // (keys are unique: the exclusive test loses nothing -- a key that IS the bound sits in the pool already, or came from another list)
         const u64 key = make_key(x[s], w8_sbase<NQ>(s) + ps.pos);
         const u64 mask = __builtin_amdgcn_ballot_w64(ps.ok && ii == 7 && key < w8_sthr<NQ>(s));
+        if constexpr (KP == 1) {
         if (mask != 0) w8_pool_offer<NQ>(s, w8_pool_read<NQ>(s, K, lane), key, mask, K, lane);   // uniform: most parked points pass for one query of the group
+        } else {
+            if (mask != 0) w8_pool_offer<NQ, 2>(s, w8_pool_read<NQ, 2>(s, K, lane, 0), key, mask, K, lane, w8_pool_read<NQ, 2>(s, K, lane, 1));
+        }
     }
 }
 
@@ -305,7 +366,7 @@ static __device__ __attribute__((noinline)) u32 w8_kth_sum4(u32 v0, u32 v1, u32 
     return prefix;
 }
 
-template <int NQ>
+template <int NQ, int KP = 1>
 static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t codes, u32 p0, u32 p1, int nvalid, int K, int wv, int lane,
                                                      v4u ca, v4u cb, __amdgpu_buffer_rsrc_t gt)
 {
@@ -315,7 +376,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
     // of the NEXT step is requested into its register set the moment this step's half has left it (rotated, four v_perm): two requests
     // of 1 KB per wave are in flight at any time, each with a whole step to arrive, and there is no second register set and no move.
     // (One request per wave -- 4 MB on the chip -- at the loaded latency of HBM is 2 TB/s: the conflict-free scan waited on every step.)
-    using L = W8Lds<NQ>;
+    using L = W8Lds<NQ, KP>;
     constexpr u32 STEP = 256;
     constexpr int NB = NQ / 2;          // accumulator dwords of a point: two 16-bit fields each
     constexpr u32 EB = 2u * NQ, CB = 16u * NQ;   // bytes of a table entry, of a copy's eight entries
@@ -375,7 +436,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
         } else {
             if (__builtin_expect(pend, 0)) {   // uniform: the pass requested during the previous step
                 pend = false;
-                w8_pass_finish<NQ>(ps, nvalid, K, lane);
+                w8_pass_finish<NQ, KP>(ps, nvalid, K, lane);
                 since = 0;
                 w8_bias<NQ>(nvalid, bias);   // (the other waves' offers moved the bounds as well)
                 if (ccnt >= W8_TRIG || (ccnt > 0 && pb >= ptail)) {   // the next ones are waiting already (or the range ends)
@@ -485,7 +546,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 #pragma unroll
                         for (int r = 0; r < 4; ++r) f[r] = (s & 1) ? (qa[r][s >> 1] >> 16) : (qa[r][s >> 1] & 0xffffu);
                         const u32 V = w8_kth_sum4(f[0], f[1], f[2], f[3], 0xFu, r8);
-                        if (lane == 0) *w8_ptr<u32>(L::COLD + 64u * s + 4u * (u32)wv) = V;
+                        if (lane == 0) *w8_ptr<u32>(L::COLD + L::COLD_SLOT * s + 4u * (u32)wv) = V;
                     }
                 });
                 __syncthreads();
@@ -495,7 +556,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                         u32 T = 0;
 #pragma unroll
                         for (int v = 0; v < W8_NW; ++v) {
-                            const u32 o = __builtin_amdgcn_readfirstlane(w8_lds<u32>(L::COLD + 64u * s + 4u * (u32)v));
+                            const u32 o = __builtin_amdgcn_readfirstlane(w8_lds<u32>(L::COLD + L::COLD_SLOT * s + 4u * (u32)v));
                             T = o > T ? o : T;
                         }
                         const float ub = (w8_dc<NQ>(s) + (float)(T + 8u) * (1.00001f / w8_inv<NQ>(s))) * 1.00002f;
@@ -630,7 +691,7 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 const bool more = (fm[0] | fm[1] | fm[2] | fm[3]) != 0;
                 if (pend) {
                     pend = false;
-                    w8_pass_finish<NQ>(ps, nvalid, K, lane);
+                    w8_pass_finish<NQ, KP>(ps, nvalid, K, lane);
                     w8_bias<NQ>(nvalid, bias);
                 }
                 if (ccnt > 0 && (more || flush || ccnt >= 8)) {
@@ -653,11 +714,11 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
 // neighbours in the queue: the item range is cut into one contiguous part per XCD and a workgroup pulls from the part of the XCD it runs
 // on (HW_REG_XCC_ID) -- the groups that stream the same list then run side by side under ONE L2 and the list crosses the fabric once.
 // Placement is a matter of speed only: a workgroup whose part is exhausted moves on to the next one; every wave leaves when all are.
-template <int NQ, int DS>
+template <int NQ, int DS, int KP = 1>
 static __device__ __forceinline__ void w8_scan_items(const ScanArgs &a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
                                                      u32 *__restrict__ xq, int nranges)
 {
-    using L = W8Lds<NQ>;
+    using L = W8Lds<NQ, KP>;
     static_assert(w8_ds_ok(DS), "sub-spaces of 4, 8, 12 or 16 dimensions");
     static_assert(8u * W8_RES_STRIDE<NQ, DS> * 4u <= L::SMAX - L::RES, "the residuals fit the block sized for DS = 16");
     constexpr int D = 8 * DS;               // m = 8
@@ -731,7 +792,13 @@ static __device__ __forceinline__ void w8_scan_items(const ScanArgs &a, float *_
             smax[tid] = 0u;
         }
         // (the pool's 64 NQ entries: the workgroup's last threads, which fetch no slot)
+        if constexpr (KP == 1) {
         if (tid >= W8_THREADS - 64 * NQ && tid < W8_THREADS) pool[tid - (W8_THREADS - 64 * NQ)] = KEY_MAX;
+        } else {
+            // (the wide pool's 128 NQ entries: one or two per thread)
+#pragma unroll
+            for (int i = 0; i < 128 * NQ / W8_THREADS; ++i) pool[tid + i * W8_THREADS] = KEY_MAX;
+        }
         __syncthreads();
         // exact pruning of whole work items, as in scan_kernel: no sum of this list lies below its coarse distance
         if (a.prune) {
@@ -969,12 +1036,29 @@ static __device__ __forceinline__ void w8_scan_items(const ScanArgs &a, float *_
         __syncthreads();   // tables complete (LDS copies; the f32 stores have left for L2: the barrier's release covers them)
 
         __builtin_amdgcn_s_setprio(W8_PRIO_SCAN);
-        w8_scan_range<NQ>(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr);
+        w8_scan_range<NQ, KP>(codes, p0, p1, nvalid, K, wv, lane, ca, cb, gtr);
         __builtin_amdgcn_s_setprio(W8_PRIO_REST);
 
         // ---- every wave has offered what it had: wave s < nvalid hands slot s of the pool over as it is -- the entries fill from index 0
         // (an offer takes the first empty one), the merge kernel behind pushes them through a selector in any order
         __syncthreads();
+        if constexpr (KP == 2) {
+        // (the wide pool: both halves of slot s, entries 0 .. fc - 1 -- a prefix, as above -- in the pool's order)
+        if (wv < nvalid) {
+            const int s = wv;
+            const u64 v = lane < K ? pool[128 * s + lane] : 0ull;
+            const u64 vh = lane + 64 < K ? pool[128 * s + 64 + lane] : 0ull;
+            const int fc = __popcll(__builtin_amdgcn_ballot_w64(lane < K && v != KEY_MAX)) + __popcll(__builtin_amdgcn_ballot_w64(lane + 64 < K && vh != KEY_MAX));
+            const size_t slot = (size_t)spi[s] * a.maxch + chunk;
+            if (lane < fc) a.part_keys[slot * K + lane] = v;
+            if (lane + 64 < fc) a.part_keys[slot * K + 64 + lane] = vh;
+            if (fc == K) {   // uniform
+                const u64 kth = w8_wave_max_u64(v > vh ? v : vh);
+                if (lane == 0) atomicMin(&a.qthr[sqi[s]], kth);
+            }
+            if (lane == 0) a.part_cnt[slot] = (u32)fc;
+        }
+        } else {
         if (wv < nvalid) {
             const int s = wv;
             const u64 v = lane < K ? pool[64 * s + lane] : 0ull;
@@ -986,6 +1070,7 @@ static __device__ __forceinline__ void w8_scan_items(const ScanArgs &a, float *_
                 if (lane == 0) atomicMin(&a.qthr[sqi[s]], kth);
             }
             if (lane == 0) a.part_cnt[slot] = (u32)fc;
+        }
         }
         } while (false);
         __syncthreads();            // every wave is done with this item's state in LDS
@@ -1009,4 +1094,12 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_scan_kernel(const S
 {
     static_assert(DS != 16, "DS = 16 is wg8_scan_kernel<NQ>");
     w8_scan_items<NQ, DS>(a, gtabs, item_list, xq, nranges);
+}
+// The wide pool (KP = 2: 64 < K <= 128), every width under one name -- one that does not contain the narrow kernels': what looks those up
+// by name finds what it always found.
+template <int NQ, int DS>
+__global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_wide_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
+                                                                      u32 *__restrict__ xq, int nranges)
+{
+    w8_scan_items<NQ, DS, 2>(a, gtabs, item_list, xq, nranges);
 }

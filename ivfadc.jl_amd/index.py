@@ -420,8 +420,10 @@ class IVFADCIndex:
         matrix-core lower-bound rounds for every shape they are instantiated for; 3 / 4: as 0 / 2 with those tables built from the
         three-product bf16 split instead of one f16 product per entry; 5 / 6: as 0 with the eight-wave list-major kernel never /
         wherever it is instantiated -- m = 8, ksub = 256, K <= 64, d = 32 / 64 / 96 / 128 (dsub = 4 / 8 / 12 / 16), with or without a list
-        partition (set_list_partition); 7: as 6 with its eight-query form.  Mode 0 takes that kernel unasked for d = 128 without a list
-        partition on lists of 8192 points or more; get_stats()["last_striped"] is 2 / 3 when its four- / eight-query form ran.
+        partition (set_list_partition); 7: as 6 with its eight-query form; 8 / 9: as 6 / 7, and for 64 < K <= 128 the kernel's wide-pool
+        form (two pool entries per lane) instead of the four-wave kernel -- K <= 64 and K > 128 run what 6 / 7 run.  Mode 0 takes that
+        kernel unasked for d = 128 without a list partition on lists of 8192 points or more; get_stats()["last_striped"] is 2 / 3 when
+        its four- / eight-query form ran, 4 / 5 for the wide-pool form.
         Results are the same bytes in every mode."""
         nat.check(nat.lib().ivfadc_set_table_mode(self._h, int(mode)))
 

@@ -6,8 +6,11 @@ per list: the eight-query form's regime) and 1024 queries at w = 1 (2 probes per
 mode -- 5: never the eight-wave kernel (what the plan ran before the kernel knew the width), 6 / 7: its four- / eight-query form, 0: the
 plan's own choice -- the scan time from events: the median of `--windows` windows of `--reps` launches each, and the windows' spread.
 With --partition N every search is rank 0's share of an N-way list partition (ivfadc_search_device_partial).
+--k sets K (default 10).  Above 64 the eight-wave kernel runs through table modes 8 / 9 only (its wide-pool form, K <= 128); mode 6 is the
+four-wave kernel with LDS selectors there, which is what the A/B of the wide pool compares with:
 
     python tools/w8_dsub_bench.py [--d 32,64,96,128] [--windows 5] [--reps 8] [--partition 8]
+    python tools/w8_dsub_bench.py --d 128 --k 100,128 --modes 6,8,9 --out profiles/wg8_wide.json
 """
 import argparse
 import json
@@ -21,7 +24,7 @@ import ivfadc_jl_amd as pkg  # noqa: E402
 
 M, KC, LIST = 8, 512, 65536
 BATCHES = ((4096, 2), (4096, 1), (1024, 1))
-KERNEL = {0: "reference-order", 1: "four-wave", 2: "eight-wave q4", 3: "eight-wave q8"}
+KERNEL = {0: "reference-order", 1: "four-wave", 2: "eight-wave q4", 3: "eight-wave q8", 4: "eight-wave wide q4", 5: "eight-wave wide q8"}
 
 
 def build(d, seed=0):
@@ -42,14 +45,16 @@ def main():
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--modes", default="5,6,7,0")
     ap.add_argument("--partition", type=int, default=0)
+    ap.add_argument("--k", default="10", help="K, or several separated by commas")
+    ap.add_argument("--out", default="", help="also write the runs to this JSON file")
     args = ap.parse_args()
     import torch
-    K = 10
+    runs = []
     for d in (int(x) for x in args.d.split(",")):
         g, cent = build(d)
         if args.partition > 1:
             g.set_list_partition(args.partition, 0)
-        for nq, w in BATCHES:
+        for K, (nq, w) in ((int(k), b) for k in args.k.split(",") for b in BATCHES):
             rng = np.random.default_rng(1)
             q = (cent[rng.integers(0, KC, nq)] + rng.normal(0, 0.05, (nq, d))).astype(np.float32)
             dq = torch.from_numpy(q).cuda()
@@ -77,11 +82,18 @@ def main():
                     win.append(g.get_stats()["scan_ms"] / args.reps)
                 st = g.get_stats()
                 g.set_profiling(0)
-                print(json.dumps({"tool": "w8_dsub_bench", "d": d, "dsub": d // M, "kc": KC, "list_len": LIST, "nq": nq, "w": w,
-                                  "probes_per_list": nq * w / KC, "partition": args.partition, "table_mode": mode,
-                                  "kernel": KERNEL.get(st["last_striped"], "?"), "qg": st["last_qg"], "chunk": st["last_chunk"],
-                                  "scan_ms_median": float(np.median(win)), "scan_ms_windows": [round(x, 4) for x in win]}), flush=True)
+                runs.append({"tool": "w8_dsub_bench", "d": d, "dsub": d // M, "kc": KC, "list_len": LIST, "K": K, "nq": nq, "w": w,
+                             "probes_per_list": nq * w / KC, "partition": args.partition, "table_mode": mode,
+                             "last_striped": st["last_striped"], "kernel": KERNEL.get(st["last_striped"], "?"), "qg": st["last_qg"],
+                             "chunk": st["last_chunk"], "scan_lds": st["last_scan_lds"], "scan_grid": st["last_scan_grid"],
+                             "scan_ms_median": float(np.median(win)), "scan_ms_spread": float(max(win) - min(win)),
+                             "scan_ms_windows": [round(x, 4) for x in win]})
+                print(json.dumps(runs[-1]), flush=True)
         del g
+    if args.out:
+        with open(args.out, "w") as f:
+            json.dump({"tool": "tools/w8_dsub_bench.py", "args": vars(args), "runs": runs}, f, indent=1)
+            f.write("\n")
 
 
 if __name__ == "__main__":
