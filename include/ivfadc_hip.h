@@ -351,8 +351,9 @@ typedef struct {
     int32_t  inplace_appends;  /* ivfadc_append calls since creation that were written in place on the device (no re-layout) */
     int32_t  last_striped;     /* the last list-major launch: 0 = reference-order f32 tables in every lane; 1 = the four-wave kernel with
                                 * bank-striped tables + rotated-order filter sums; 2 / 3 = the eight-wave kernel (wg8scan.hip.h:
-                                * m = 8, dsub = 4 / 8 / 12 / 16, K <= 64), four / eight queries per code stream; 4 / 5 = its wide-pool
-                                * form (64 < K <= 128; table modes 8 / 9), four / eight queries per code stream -- also what a rank
+                                * m = 8, dsub = 4 / 8 / 12 / 16, K <= 64; m = 16, dsub = 4 / 8, K <= 64 through table modes 6 / 7 only),
+                                * four / eight queries per code stream; 4 / 5 = its wide-pool
+                                * form (m = 8, 64 < K <= 128; table modes 8 / 9), four / eight queries per code stream -- also what a rank
                                 * of the list-partitioned mode reports (ivfadc_set_list_partition) */
     int32_t  coarse_listed;    /* 1: the last batch's coarse filter wrote per-tile records (four smallest keys of every
                                 * (query, 64-centroid tile)) instead of the score matrix, and the top-w enumerated them */
@@ -450,7 +451,9 @@ int ivfadc_set_query_token(ivfadc_t *h, uint64_t token);
  * m = 8, ksub = 256, K <= 64, dsub = 4 / 8 / 12 / 16, i.e. d = 32 / 64 / 96 / 128; with or without a list partition) never / wherever
  * it is instantiated; 7 = as 6 with its eight-query form (wg8_scan_kernel<8> and <8, DS>, same file).  8 / 9 = as 6 / 7, and for
  * 64 < K <= 128 the kernel's wide-pool form (wg8_wide_scan_kernel<NQ, DS>: two pool entries per lane) instead of the four-wave kernel with
- * LDS selectors; K <= 64 and K > 128 run what 6 / 7 run.  Mode 0 takes that kernel on its own
+ * LDS selectors; K <= 64 and K > 128 run what 6 / 7 run.  Modes 6 / 7 (and 8 / 9 at K <= 64) also take the kernel for m = 16 with
+ * d = 128 or d = 64 (wg8_m16_scan_kernel<NQ, DS>: PQ16; K <= 64, lists below 2^27 points), which no other mode does: the default plan of
+ * an m = 16 index is the four-wave kernel, as before.  Mode 0 takes that kernel on its own
  * for d = 128 without a list partition, on lists of 8192 points or more; the other widths and the list-partitioned
  * mode get it through 6 / 7, K up to 128 through 8 / 9 (stats.last_striped tells which kernel ran).  Results are identical in every mode: whatever a filter lets through is recomputed in the reference's
  * order -- from the f32 tables or, in the matrix-core rounds, from the f32 codebook -- before it meets the bound.       */

@@ -315,7 +315,7 @@ struct ivfadc_index {
     // narrow-field list-major scan (nfscan.hip.h; m = 8, dsub = 16, ksub = 256): ||codeword||^2 by codeword index, f32 codewords by label
     DevBuf nf_n2, nf_lab;
     bool allow_nf = true;
-    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64, with the wide pool K <= 128): the work items'
+    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64, with the wide pool K <= 128; m = 16, dsub = 4 / 8, K <= 64): the work items'
     // f32 tables, 32 or 64 KB per workgroup
     DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
     int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
@@ -753,9 +753,22 @@ constexpr size_t LDS_MAX = 160 << 10;
 constexpr double W8_Q8_MIN_PPL = 8.0;   // probes per list from which the eight-query form of the eight-wave kernel is planned
 // sub-space widths the eight-wave kernel is instantiated for (m = 8: d = 32, 64, 96, 128), and the instantiation of a form and a width
 bool w8_dsub(int dsub) { return w8_ds_ok(dsub); }
+// ... and m = 16 (d = 64, 128: wg8_m16_scan_kernel<NQ, DS>, K <= 64, no wide pool), which runs on request only -- table modes 6 / 7 (8 / 9):
+// not timed against the four-wave kernel yet
+bool w8_m16_dsub(int dsub) { return dsub == 4 || dsub == 8; }
+// the shapes (m, dsub) the handle's table mode admits, and the longest list the kernel's 28-bit positions and 31-bit byte offsets hold
+bool w8_md(const ivfadc_index *h) { return (h->m == 8 && w8_dsub(h->dsub)) || (h->m == 16 && w8_m16_dsub(h->dsub) && h->wg8_mode > 0); }
+int64_t w8_maxlen(const ivfadc_index *h) { return (int64_t)1 << (h->m == 16 ? 27 : 28); }
 typedef void (*wg8_fn_t)(const ScanArgs, float *, const u32 *, u32 *, int);
-wg8_fn_t pick_wg8(bool q8, int dsub)
+wg8_fn_t pick_wg8(bool q8, int m, int dsub)
 {
+    if (m == 16) {
+#define X(D_) if (dsub == D_) return q8 ? wg8_m16_scan_kernel<8, D_> : wg8_m16_scan_kernel<4, D_>;
+        X(4) X(8)
+#undef X
+        return nullptr;
+    }
+    if (m != 8) return nullptr;
     if (dsub == 16) return q8 ? wg8_scan_kernel<8> : wg8_scan_kernel<4>;
 #define X(D_) if (dsub == D_) return q8 ? wg8_scan_kernel<8, D_> : wg8_scan_kernel<4, D_>;
     X(4) X(8) X(12)
@@ -772,7 +785,7 @@ wg8_fn_t pick_wg8_wide(bool q8, int dsub)
     return nullptr;
 }
 // ... and where the plan takes the kernel unasked (wg8_mode == 0; table modes 6 / 7 take it wherever it is instantiated): see make_plan
-bool w8_default(const ivfadc_index *h) { return h->dsub == 16 && h->part_n <= 1; }
+bool w8_default(const ivfadc_index *h) { return h->m == 8 && h->dsub == 16 && h->part_n <= 1; }
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
 constexpr size_t MISC_BYTES = 4096 + 256 + 512;
@@ -973,10 +986,10 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
         // 0.316 / 0.544 / 0.92-0.93 (round 6)
         // (K the kernel's pool holds: 64, or 128 where table mode 8 / 9 asks for the wide pool -- a request, so wg8_mode > 0 there)
-        const bool w8_wide_k = !pl.small_k && h->wg8_wide && h->wg8_mode > 0 && K <= W8_WIDE_MAX_K;
+        const bool w8_wide_k = !pl.small_k && h->wg8_wide && h->wg8_mode > 0 && h->m == 8 && K <= W8_WIDE_MAX_K;
         const bool w8_k = pl.small_k || w8_wide_k;
-        const bool w8_shape = w8_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
-                              h->maxlen < ((int64_t)1 << 28) && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
+        const bool w8_shape = w8_k && h->allow_filt && h->wg8_mode >= 0 && w8_md(h) && h->ksub == 256 &&
+                              h->maxlen < w8_maxlen(h) && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
         if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
         if (forced) qg = h->force_qg;
         // eight queries per code stream behind the 4-bit narrow-field filter (nfscan.hip.h): conflict-free gathers, a third of the vector
@@ -994,7 +1007,9 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         } else {
         // keep two workgroups per CU when possible (a forced width only yields to the hard LDS limit)
         // (groups of four that the wide-pool kernel takes below need none of the four-wave kernel's LDS selectors: its budget does not narrow them)
-        const bool w8_wide_ok = w8_wide_k && h->allow_filt && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 && h->maxlen < ((int64_t)1 << 28);
+        // (... nor do the groups of four of an m = 16 index that the kernel takes on request: the four-wave kernel's 64 KB of f32 tables are not built)
+        const bool w8_m16_ok = pl.small_k && h->allow_filt && h->m == 16 && w8_md(h) && h->ksub == 256 && h->maxlen < w8_maxlen(h);
+        const bool w8_wide_ok = (w8_wide_k && h->allow_filt && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 && h->maxlen < ((int64_t)1 << 28)) || w8_m16_ok;
         while (qg > 1 && !(qg == 4 && w8_wide_ok) && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
         if (!(qg == 4 && w8_wide_ok) && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
         pl.qg = qg;
@@ -1007,18 +1022,19 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
         // list-partitioned mode needs nothing of the kernel: the partition is applied in front of it -- the top-w kernel counts this rank's
         // lists only into list_cnt, which bucket_scan_kernel turns into work items and item_list, bucket_scatter_kernel drops the other
         // ranks' probes -- and behind it, in merge_kernel; a rank's work items are ordinary ones)
-        pl.wg8 = qg == 4 && w8_k && h->allow_filt && h->wg8_mode >= 0 && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 &&
-                 h->maxlen < ((int64_t)1 << 28) &&
+        // (m = 16: 27-bit lists -- a point is 16 bytes -- and on request only: w8_md)
+        pl.wg8 = qg == 4 && w8_k && h->allow_filt && h->wg8_mode >= 0 && w8_md(h) && h->ksub == 256 &&
+                 h->maxlen < w8_maxlen(h) &&
                  (h->wg8_mode > 0 || (w8_default(h) && avg_len >= 8192.0));   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
         pl.wg8wide = pl.wg8 && !pl.small_k;
-        if (pl.wg8) pl.lds = pl.wg8wide ? (size_t)W8Lds<4, 2>::END : (size_t)W8Lds<4>::END;
+        if (pl.wg8) pl.lds = h->m == 16 ? (size_t)W8Lds<4, 1, 16>::END : (pl.wg8wide ? (size_t)W8Lds<4, 2>::END : (size_t)W8Lds<4>::END);
         // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
         // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
         pl.wg8q8 = pl.wg8 && (h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W8_Q8_MIN_PPL));
         if (pl.wg8q8) {
             qg = 8;
             pl.qg = 8;
-            pl.lds = pl.wg8wide ? (size_t)W8Lds<8, 2>::END : (size_t)W8Lds<8>::END;
+            pl.lds = h->m == 16 ? (size_t)W8Lds<8, 1, 16>::END : (pl.wg8wide ? (size_t)W8Lds<8, 2>::END : (size_t)W8Lds<8>::END);
         }
         }
         // chunk size: enough work items to fill the chip, as few table rebuilds as possible.  Two items per CU is the
@@ -1508,14 +1524,15 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
             h->stats.last_scan_grid = (int)grid;
             h->stats.last_striped = 0;
         } else if (pl.wg8 && !direct) {
-            wg8_fn_t wk = pl.wg8wide ? pick_wg8_wide(pl.wg8q8, h->dsub) : pick_wg8(pl.wg8q8, h->dsub);
-            if (!wk) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for dsub = %d, which has no instantiation", h->dsub);
+            wg8_fn_t wk = pl.wg8wide ? (h->m == 8 ? pick_wg8_wide(pl.wg8q8, h->dsub) : nullptr) : pick_wg8(pl.wg8q8, h->m, h->dsub);
+            if (!wk) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for m = %d, dsub = %d, which has no instantiation", h->m, h->dsub);
             u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
             HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
             int occ = 0;
             TRY(fn_occupancy(h, (const void *)wk, pl.lds, occ, true, W8_THREADS));
             const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * W8_GTAB_FLOATS<8> * 4));   // (occupancy is clamped to 8 workgroups per CU)
+            // (occupancy is clamped to 8 workgroups per CU; the larger form of the handle's m: eight queries)
+            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * (h->m == 16 ? W8_GTAB_FLOATS<8, 16> : W8_GTAB_FLOATS<8>) * 4));
             if (h->profiling) TRY(ev_begin(h, 0, ep));
             hipLaunchKernelGGL(wk, dim3(grid), dim3(W8_THREADS), pl.lds, h->stream, a, h->wg8_tabs.as<float>(), h->wg8_items.as<u32>(), xq, 8);
             HIP_TRY(hipGetLastError());

@@ -5,6 +5,9 @@
 // modes 8 / 9): the pool is the only thing in the kernel that is tied to 64 -- filter, bias test, rings and passes are per point, the
 // cold-start bounds take the ceil(K / 8)-th and K-th of a step's 256 sums -- see THE WIDE POOL at w8_pool_offer.  KP = 1 is the code that
 // every measurement below was taken with, unchanged behind `if constexpr`.
+// m = 16 (d = 128 -- PQ16 -- and d = 64; K <= 64; on request, table modes 6 / 7) is wg8_m16_scan_kernel<NQ, DS>: the same design on a
+// 256-byte row of 2 x 16 x 8 B or 16 x 16 B, 11-bit filter fields, one point per 16-byte request -- see THE M-GENERIC BODY and SIXTEEN
+// SUB-QUANTIZERS below, and THE FILTER AT SIXTEEN TERMS at w8m_scan_items' quantisation.
 // Only the residual fill and the table build know DS: the scan looks 8 code bytes per point up in a 64 KB integer table whatever the
 // sub-spaces' width, so the scan loop, the pool, the passes and the hand-over are per NQ alone, and the LDS layout is the one of DS = 16
 // (narrower sub-spaces leave residual rows unused).
@@ -54,14 +57,26 @@
 // same LDS are slower than four, whatever the guide's 2 cycles per ds_read_b64 leave free on paper.
 constexpr int W8_NW = 8;
 constexpr int W8_THREADS = 64 * W8_NW;
-constexpr int W8_ES = 3;                      // dwords per parked point: code bytes (2), list position
-constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (32 / NQ copies x 8 sub-quantizers x 2 NQ bytes)
-template <int NQ> constexpr u32 W8_GTAB_FLOATS = 8u * 256u * (u32)NQ;   // f32 tables of a work item in device memory: [ii][label][NQ queries]
+constexpr int W8_ES = 3;                      // dwords per parked point: code bytes (2), list position (m = 16: W8Lds::ES = 5, four dwords of code bytes)
+constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (32 / NQ copies x 8 sub-quantizers x 2 NQ bytes; m = 16: 16 / NQ copies x 16 sub-quantizers)
+template <int NQ, int M = 8> constexpr u32 W8_GTAB_FLOATS = (u32)M * 256u * (u32)NQ;   // f32 tables of a work item in device memory: [ii][label][NQ queries]
+// the integer filter's cap per entry: M entries of at most W8_QCAP sum to less than 0x8000 (8 x 4095 = 32 760, 16 x 2047 = 32 752) -- see
+// THE FILTER AT SIXTEEN TERMS below
+template <int M> constexpr u32 W8_QCAP = M == 8 ? 4095u : 2047u;
+static_assert(8u * W8_QCAP<8> <= 0x7FFFu && 16u * W8_QCAP<16> <= 0x7FFFu, "a point's integer sum stays below 0x8000");
+static_assert(0x8000u + 16u * W8_QCAP<16> < 0x10000u && 0x8000u + 8u * W8_QCAP<8> < 0x10000u, "a biased field never carries into its neighbour");
 
 // KP: the pool's entries per lane (1: K <= 64, the layout of every measurement so far; 2: K <= 128, the wide pool -- see w8_pool_offer)
-template <int NQ, int KP = 1> struct W8Lds {
+// M: sub-quantizers (8, or 16: SIXTEEN SUB-QUANTIZERS below).  Two sizes depend on it, both behind the pool, so everything the helpers
+// below read at fixed addresses stands where it stood: a parked point takes five dwords instead of three (16 code bytes), and the residuals
+// -- 16 x (DS + 1) x NQ x 4 B, 576 NQ bytes at DS = 8, which the block sized for m = 8 / DS = 16 (544 NQ bytes) does NOT hold -- are built
+// where the rings are: the rings are empty from the end of a work item's scan to the start of the next one's, the residuals live from
+// the top of a work item to the barrier behind its table build, and barriers separate the two (RESB; at m = 16 the block at RES is unused).
+template <int NQ, int KP = 1, int M = 8> struct W8Lds {
     static_assert(NQ == 4 || NQ == 8, "four or eight queries per code stream");
     static_assert(KP == 1 || KP == 2, "one or two pool entries per lane");
+    static_assert(M == 8 || (M == 16 && KP == 1), "eight sub-quantizers, or sixteen with the one-entry-per-lane pool");
+    static constexpr u32 ES = M == 8 ? (u32)W8_ES : 5u;      // dwords per parked point: M / 4 of code bytes, list position
     static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (DS x NQ + NQ of padding) x 4 B, sized for DS = 16 (W8_RES_STRIDE)
     static constexpr u32 SMAX = RES + 8u * (16u * NQ + NQ) * 4u;   // u32 [NQ]: bits of the per-query largest entry (atomicMax); f32 inv[NQ] behind
     static constexpr u32 QC = SMAX + 8u * NQ;                 // f32 dc[NQ]; u32 visit-order base[NQ]; u32 probe index[NQ]; u32 query[NQ]
@@ -71,16 +86,21 @@ template <int NQ, int KP = 1> struct W8Lds {
     static constexpr u32 POOL = SWI + 16u;                    // u64 [NQ][64 KP]: the workgroup's K smallest keys per slot, unordered (w8_pool_offer)
     static constexpr u32 POOL_SLOT = 64u * KP * 8u;           // bytes of a slot's pool
     static constexpr u32 PARK = POOL + NQ * POOL_SLOT;        // u32 [8][32][W8_ES]: the waves' rings of parked points (W8_RING)
-    static constexpr u32 COLD = PARK + (u32)W8_NW * 32u * W8_ES * 4u;     // u32 [NQ][16]: a cold work item's first step, every wave's ceil(K / 8)-th smallest integer sum per slot
+    static constexpr u32 COLD = PARK + (u32)W8_NW * 32u * ES * 4u;     // u32 [NQ][16]: a cold work item's first step, every wave's ceil(K / 8)-th smallest integer sum per slot
     // (KP = 1: up to sixteen waves; the wide pool's 8 NQ more entries leave the eight-query form room for the eight waves there are: u32 [NQ][8])
     static constexpr u32 COLD_SLOT = KP == 1 ? 64u : 4u * (u32)W8_NW;
     static constexpr u32 END = COLD + COLD_SLOT * NQ;
+    static constexpr u32 RESB = M == 8 ? RES : PARK;          // where the residuals are built
     static_assert(END <= 80u * 1024u, "two workgroups per CU");
     static_assert((HARD & 7u) == 0 && (STHR & 7u) == 0 && (POOL & 7u) == 0, "8-byte bounds");
+    static_assert(M == 8 || 16u * (8u + 1u) * NQ * 4u <= COLD - PARK, "m = 16: the residuals of DS <= 8 fit the rings' block");
+    static_assert((RESB & 15u) == 0, "16-byte residual rows");
 };
 static_assert(W8Lds<4>::END == 73264u && W8Lds<8>::END == 77904u, "the layout the plan's LDS figures and the measurements were taken with");
 static_assert(W8Lds<4, 2>::END == 75184u && W8Lds<8, 2>::END == 81744u, "the wide pool's layouts: 2 / 4 KB more pool, 32 B per slot of cold-start words");
 static_assert(W8Lds<4, 2>::POOL == W8Lds<4>::POOL && W8Lds<8, 2>::POOL == W8Lds<8>::POOL, "everything in front of the pool stands where the helpers below read it");
+static_assert(W8Lds<4, 1, 16>::END == 75312u && W8Lds<8, 1, 16>::END == 79952u, "m = 16: 2 KB more of rings (five dwords per parked point), nothing else");
+static_assert(W8Lds<4, 1, 16>::PARK == W8Lds<4>::PARK && W8Lds<8, 1, 16>::PARK == W8Lds<8>::PARK, "m = 16: everything up to the rings stands where it stood");
 
 // Sub-space widths the kernel is instantiated for (d = 8 DS), and the residuals' floats per sub-quantizer: DS rows of NQ queries and ONE row
 // of padding.  A quad of the table build reads the rows of four neighbouring sub-quantizers at once, 16 B per lane (NQ = 8: 16 B of a
@@ -95,6 +115,13 @@ static __device__ __forceinline__ u32 w8_perm(u32 s0, u32 s1, u32 sel)
 {
     u32 o;
     asm("v_perm_b32 %0, %1, %2, %3" : "=v"(o) : "v"(s0), "v"(s1), "s"(sel));
+    return o;
+}
+// ... with the selector in a vector register (m = 16: the byte of the code dword a slot looks up depends on the lane)
+static __device__ __forceinline__ u32 w8_permv(u32 s0, u32 s1, u32 sel)
+{
+    u32 o;
+    asm("v_perm_b32 %0, %1, %2, %3" : "=v"(o) : "v"(s0), "v"(s1), "v"(sel));
     return o;
 }
 
@@ -286,7 +313,8 @@ template <int NQ> struct W8Pass {
 // of the work items' f32 tables, which the passes gather from): 16 384 x w = 8 scan 6.15 -> 7.35 ms, 2048 x w = 8 1.15 -> 1.31 -- the four
 // or five groups that stream the same list side by side live on each other's lines in L2 / the memory-side cache.  Default policy.
 constexpr int W8_STREAM_AUX = 0;
-constexpr int W8_TRIG = 8;        // parked points that trigger a pass
+constexpr int W8_TRIG = 8;        // parked points that trigger a pass (m = 8; a pass takes 64 / M points: w8_pp)
+template <int M> constexpr int w8_pp = 64 / M;   // points per pass: a segment of M lanes per point
 constexpr int W8_REFRESH = 8;     // steps between looks at the workgroup's shared bounds
 constexpr int W8_PRIO_SCAN = 3;   // wave priority while the code stream is scanned, and after it
 constexpr int W8_PRIO_REST = 0;
@@ -294,6 +322,52 @@ constexpr int W8_RING = 32;    // parked points per wave (a ring: entries head .
 
 template <int NQ> static __device__ __forceinline__ void w8_pass_issue(W8Pass<NQ> &ps, u32 cbuf_addr, int &head, int &cnt, __amdgpu_buffer_rsrc_t gt, int lane)
 {
+    const int seg = lane >> 3, ii = lane & 7;
+    ps.ok = seg < cnt;
+    const u32 ea = cbuf_addr + (u32)((head + (ps.ok ? seg : 0)) & (W8_RING - 1)) * (W8_ES * 4u);
+    // (parked: the point's ROTATED code bytes -- out byte t = code byte (t + j) mod 8, j = the parking lane's rotation, kept in the position
+    // word's top three bits: the scan loop holds no unrotated copy of a step's bytes)
+    const u32 pj = w8_lds<u32>(ea + 8u);
+    const u32 idx = ((u32)ii - (pj >> 29)) & 7u;
+    const u32 dw = w8_lds<u32>(ea + 4u * (idx >> 2));
+    ps.pos = pj & 0x1FFFFFFFu;
+#pragma unroll
+    for (int q4 = 0; q4 < NQ / 4; ++q4) ps.ev[q4] = w8_gtab_load<NQ>(gt, (u32)ii, (dw >> (8 * (idx & 3))) & 0xffu, q4);
+    const int take = cnt < 8 ? cnt : 8;
+    head = (head + take) & (W8_RING - 1);
+    cnt -= take;
+}
+
+// ---- THE M-GENERIC BODY (w8m_*) ------------------------------------------------------------------------------------------------------
+// w8m_pass_issue, w8m_pass_finish, w8m_scan_range and w8m_scan_items are the functions above with the number of sub-quantizers M as a
+// template parameter, M = 8 behind `if constexpr`.  They are instantiated for M = 16 ONLY (wg8_m16_scan_kernel): the sixteen m = 8 kernels
+// keep the functions above, untouched.  Instantiating THEM from the M-generic body was tried and changes their register allocation (the same
+// instructions in the scan loop, some eighty more around it, other scalar registers spilled) although every M = 8 branch is the same text --
+// and these are the kernels every measurement in DESIGN.md was taken with: they must disassemble to the same instructions, one for one.
+// Folding the two bodies into one is a change of its own, to be made when it can be timed.
+template <int NQ, int M = 8> static __device__ __forceinline__ void w8m_pass_issue(W8Pass<NQ> &ps, u32 cbuf_addr, int &head, int &cnt, __amdgpu_buffer_rsrc_t gt, int lane)
+{
+    if constexpr (M == 16) {
+        // four points per pass, a row of sixteen lanes each.  Parked: the point's code DWORDS rotated (out dword k = code dword
+        // (k + jd) mod 4, jd = the parking lane's j / 4 -- the bytes inside a dword stand where they stood, see w8_scan_range) and j in the
+        // position word's top four bits
+        // (the lane number passes through an opaque move: what is derived from it here -- segment, sub-quantizer, ring and table offsets --
+        // is computed where it is used, a few instructions of a rare path, instead of living, spilled, across the scan loop)
+        asm volatile("" : "+v"(lane));
+        const int seg = lane >> 4, ii = lane & 15;
+        ps.ok = seg < cnt;
+        const u32 ea = cbuf_addr + (u32)((head + (ps.ok ? seg : 0)) & (W8_RING - 1)) * (5u * 4u);
+        const u32 pj = w8_lds<u32>(ea + 16u);
+        const u32 k = (((u32)ii >> 2) - (pj >> 30)) & 3u;
+        const u32 dw = w8_lds<u32>(ea + 4u * k);
+        ps.pos = pj & 0x0FFFFFFFu;
+#pragma unroll
+        for (int q4 = 0; q4 < NQ / 4; ++q4) ps.ev[q4] = w8_gtab_load<NQ>(gt, (u32)ii, (dw >> (8 * (ii & 3))) & 0xffu, q4);
+        const int take = cnt < 4 ? cnt : 4;
+        head = (head + take) & (W8_RING - 1);
+        cnt -= take;
+        return;
+    }
     const int seg = lane >> 3, ii = lane & 7;
     ps.ok = seg < cnt;
     const u32 ea = cbuf_addr + (u32)((head + (ps.ok ? seg : 0)) & (W8_RING - 1)) * (W8_ES * 4u);
@@ -338,6 +412,38 @@ template <int NQ, int KP = 1> static __device__ __forceinline__ void w8_pass_fin
         // (keys are unique: the exclusive test loses nothing -- a key that IS the bound sits in the pool already, or came from another list)
         const u64 key = make_key(x[s], w8_sbase<NQ>(s) + ps.pos);
         const u64 mask = __builtin_amdgcn_ballot_w64(ps.ok && ii == 7 && key < w8_sthr<NQ>(s));
+        if constexpr (KP == 1) {
+        if (mask != 0) w8_pool_offer<NQ>(s, w8_pool_read<NQ>(s, K, lane), key, mask, K, lane);   // uniform: most parked points pass for one query of the group
+        } else {
+            if (mask != 0) w8_pool_offer<NQ, 2>(s, w8_pool_read<NQ, 2>(s, K, lane, 0), key, mask, K, lane, w8_pool_read<NQ, 2>(s, K, lane, 1));
+        }
+    }
+}
+
+template <int NQ, int KP = 1, int M = 8> static __device__ __forceinline__ void w8m_pass_finish(const W8Pass<NQ> &ps, int nvalid, int K, int lane)
+{
+    const int ii = lane & (M - 1);
+    float ev[NQ];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) ev[s] = ps.ev[s >> 2][s & 3];
+    float x[NQ];
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) x[s] = w8_dc<NQ>(s) + ev[s];
+#pragma unroll
+    for (int i = 1; i < M; ++i)
+#pragma unroll
+        for (int s = 0; s < NQ; ++s) {
+            // lane l <- lane l-1 within a row of 16 (row_shr:1): what lane i reads at step i is lane i-1's value of step i-1, so the
+            // segment's last lane ends with ((dc + t0) + t1) + ... + t7 (index.jl:242-246; m = 16: a segment is the row, ... + t15)
+            const float up = __uint_as_float((u32)__builtin_amdgcn_update_dpp(0, (int)__float_as_uint(x[s]), 0x111, 0xf, 0xf, false));
+            x[s] = up + ev[s];
+        }
+#pragma unroll
+    for (int s = 0; s < NQ; ++s) {
+        if (s >= nvalid) continue;   // uniform
+        // (keys are unique: the exclusive test loses nothing -- a key that IS the bound sits in the pool already, or came from another list)
+        const u64 key = make_key(x[s], w8_sbase<NQ>(s) + ps.pos);
+        const u64 mask = __builtin_amdgcn_ballot_w64(ps.ok && ii == M - 1 && key < w8_sthr<NQ>(s));
         if constexpr (KP == 1) {
         if (mask != 0) w8_pool_offer<NQ>(s, w8_pool_read<NQ>(s, K, lane), key, mask, K, lane);   // uniform: most parked points pass for one query of the group
         } else {
@@ -697,6 +803,469 @@ static __device__ __forceinline__ void w8_scan_range(__amdgpu_buffer_rsrc_t code
                 if (ccnt > 0 && (more || flush || ccnt >= 8)) {
                     wave_sync();
                     w8_pass_issue<NQ>(ps, cbuf_addr, head, ccnt, gt, lane);
+                    pend = true;
+                    if (more || flush) continue;   // (uniform) worked off at once: room for what is left / nothing may stay behind
+                }
+                if (!more) break;
+            }
+            if (flush) break;
+        }
+    }
+}
+
+template <int NQ, int KP = 1, int M = 8>
+static __device__ __forceinline__ void w8m_scan_range(__amdgpu_buffer_rsrc_t codes, u32 p0, u32 p1, int nvalid, int K, int wv, int lane,
+                                                     v4u ca, v4u cb, v4u cc, v4u cd, __amdgpu_buffer_rsrc_t gt)
+{
+    // A step of a wave is 256 points: four per lane in two 16-byte registers sets, ca (points pb + 2 lane, + 1) and cb (pb + 128 + 2 lane,
+    // + 1), requested by the caller for the first step.  The code stream comes through a buffer resource over the list: the lane's offset
+    // (16 lane) is a constant register, the step's offset a scalar -- a request is ONE instruction and no address arithmetic -- and each half
+    // of the NEXT step is requested into its register set the moment this step's half has left it (rotated, four v_perm): two requests
+    // of 1 KB per wave are in flight at any time, each with a whole step to arrive, and there is no second register set and no move.
+    // (One request per wave -- 4 MB on the chip -- at the loaded latency of HBM is 2 TB/s: the conflict-free scan waited on every step.)
+    //
+    // SIXTEEN SUB-QUANTIZERS (M = 16; wg8_m16_scan_kernel<NQ, DS>).  A point is 16 bytes: one 16-byte request is ONE point per lane, a
+    // step keeps its 256 points -- four per lane in FOUR register sets (ca, cc, cb, cd: point pb + 64 r + lane, r = 0 .. 3), each requested in place as above:
+    // four requests of 1 KB per wave in flight.  Registers a step holds: the four sets (16), their rotated copies rw (16: what parks), the
+    // lane constants (4 address dwords, 4 selectors), the accumulators of the four points (2 NQ) and the gathers in flight (32: NQ = 4
+    // all sixteen of a point, NQ = 8 eight at a time, as at m = 8) -- 24 more than the m = 8 forms hold.  The four-query form fits: 128
+    // registers, no scratch access in the loop.  The EIGHT-query form with four points per lane did NOT: the compiler spilled inside the
+    // loop (23 scratch accesses per step; four gathers in flight instead of eight changed nothing: the pressure was the step's state,
+    // not the gathers).  It takes a 128-POINT STEP instead -- two points per lane in the sets ca and cc, two requests of 1 KB in flight
+    // (NPT below) -- and its loop is free of scratch accesses too (tests/test_resources_wg8_m16.py).
+    // A code's 256-byte row is 2 copies x 16 sub-quantizers x 8 B (NQ = 4) or 16 x 16 B (NQ = 8).  With j = lane mod 16 = 4 jd + jb, lane
+    // l looks up, at slot t = 4 td + tb, sub-quantizer sigma(t) = 4 ((td + jd) mod 4) + ((tb + jb) mod 4), in copy (l / 16) mod 2
+    // (NQ = 4): for a fixed slot sigma is one-to-one in j, so the 32 lanes of a ds_read_b64 service group read 16 sub-quantizers x 2
+    // copies = 32 different bank pairs, and the 16-lane service groups of a ds_read_b128 -- {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31},
+    // + 32: sixteen different j each -- read sixteen different four-bank groups, whatever the codes are.  A byte rotation by j across 16
+    // bytes would take a v_perm per output dword and a lane-dependent choice of its two source dwords; sigma needs only the DWORDS rotated by
+    // jd (two rounds of four selects per point: by jd's low bit, then by its high bit) -- the byte inside the dword is picked by the
+    // address perm itself, whose selector is a lane constant in a vector register: ONE v_perm_b32 per lookup, as at m = 8.
+    using L = W8Lds<NQ, KP, M>;
+    // NPT: the step's points per lane.  Four (a 256-point step) with four queries; TWO with eight -- a 128-point step in the sets ca and cc:
+    // with four points the eight-query step holds 24 registers more than at m = 8 (two more sets, their rotated copies, 16-byte code
+    // words) and the compiler spilled inside the loop, the fourth set right behind its request.  Everything below that speaks of the
+    // step takes STEP = 64 NPT points: the cold-start exchange (every wave's ceil(K / 8)-th smallest sum of its first STEP points:
+    // ceil(K / 8) <= 8 <= 128), the crowd bound (the K-th sum of a step: K <= 64 <= 128), the tail (a wave's last two steps), the caller's
+    // first requests.  Points r >= NPT do not exist: their flags and masks are constants the compiler folds.
+    constexpr int NPT = NQ == 8 ? 2 : 4;
+    constexpr u32 STEP = 64u * NPT;
+    static_assert(M == 16, "the M-generic body is instantiated for M = 16 only");
+    static_assert((W8_NW + 64 - 1) / W8_NW <= (int)STEP && 64 <= (int)STEP, "the cold-start bounds take the ceil(K / 8)-th and the K-th of a step's sums, K <= 64");
+    constexpr int NB = NQ / 2;          // accumulator dwords of a point: two 16-bit fields each
+    constexpr u32 EB = 2u * NQ, CB = 2u * M * NQ;   // bytes of a table entry, of a copy's M entries
+    constexpr int CSH = M == 16 ? 4 : (NQ == 8 ? 4 : 3), CMASK = M == 16 ? (NQ == 8 ? 0 : 1) : (NQ == 8 ? 1 : 3);   // lane -> copy
+    static_assert((u32)(CMASK + 1) * CB == 256u, "a code's row is 256 bytes: the 64 banks once");
+    constexpr u32 ES = L::ES;
+    const u32 cbuf_addr = L::PARK + (u32)wv * (W8_RING * ES * 4u);
+    u32 bias[NB];
+    w8_bias<NQ>(nvalid, bias);
+    // lane constants: byte rotation of a point's code (out byte t = code byte (t + j) mod 8) and the low address byte of slot t:
+    // copy * 8 EB | ((t + j) mod 8) * EB (four copies of 8-byte entries, two of 16-byte ones)
+    const int j = lane & (M - 1), cpy = (lane >> CSH) & CMASK;
+    u32 rsel0 = 0, rsel1 = 0, ap0 = 0, ap1 = 0;
+    // (m = 16: apv[td] byte tb = the low address byte of slot 4 td + tb, copy * CB | sigma * EB; aselv[tb] = the address perm's selector)
+    u32 apv[4] = {0u, 0u, 0u, 0u}, aselv[4] = {0u, 0u, 0u, 0u};
+    if constexpr (M == 16) {
+        const int jd = j >> 2, jb = j & 3;
+#pragma unroll
+        for (int td = 0; td < 4; ++td)
+#pragma unroll
+            for (int tb = 0; tb < 4; ++tb)
+                apv[td] |= ((u32)(4 * ((td + jd) & 3) + ((tb + jb) & 3)) * EB + (u32)cpy * CB) << (8 * tb);
+#pragma unroll
+        for (int tb = 0; tb < 4; ++tb) aselv[tb] = 0x0C0C0000u | ((4u + (u32)((tb + jb) & 3)) << 8) | (u32)tb;
+    } else {
+#pragma unroll
+    for (int b = 0; b < 4; ++b) {
+        rsel0 |= (u32)((b + j) & 7) << (8 * b);
+        rsel1 |= (u32)((4 + b + j) & 7) << (8 * b);
+        ap0 |= ((u32)((b + j) & 7) * EB + (u32)cpy * CB) << (8 * b);
+        ap1 |= ((u32)((4 + b + j) & 7) * EB + (u32)cpy * CB) << (8 * b);
+    }
+    }
+    const bool jlo = (j & 4) != 0, jhi = (j & 8) != 0;   // (m = 16) the dword rotation's two rounds
+    // address of slot t = perm{byte 0: lane part of slot t, byte 1: rotated code byte t, bytes 2, 3: zero}
+    const u32 asel[4] = {0x0C0C0400u, 0x0C0C0501u, 0x0C0C0602u, 0x0C0C0703u};
+    const int lane16 = lane * 16;
+    int head = 0, ccnt = 0;
+    u32 since = 0;
+    bool pend = false;
+    W8Pass<NQ> ps;
+#pragma unroll
+    for (int q4 = 0; q4 < NQ / 4; ++q4) ps.ev[q4] = (v4f){0.f, 0.f, 0.f, 0.f};
+    ps.pos = 0;
+    ps.ok = false;
+    u32 rw[4][M / 4] = {};
+    u64 fm[4] = {0, 0, 0, 0};
+    bool flush = false;
+    // A COLD work item (a slot whose query has no bound yet: every point of the first step is a candidate) starts with one exchange between
+    // the eight waves: each takes the ceil(K / 8)-th smallest integer sum of ITS first 256 points, T = the largest of the eight -- every
+    // wave holds ceil(K / 8) points at or below T, the workgroup K -- and (T + 8) / inv + dc bounds K real distances from above (header):
+    // the bound of the 16th-or-so best of 2048 points instead of each wave's own K-th of 256, five times fewer candidates in the steps
+    // that follow, and not one exact sum spent on it.  Workgroup-uniform conditions only (the item's own constants in LDS, a range that
+    // gives every wave a whole first step), so all eight waves reach the barrier.
+    u32 coldmask = 0;
+    if (p1 - p0 >= (u32)W8_NW * STEP) {
+#pragma unroll
+        for (int s = 0; s < NQ; ++s) {
+            const float inv = w8_inv<NQ>(s);
+            const u32 hh = __builtin_amdgcn_readfirstlane(w8_lds<u32>(L::HARD + 8u * s + 4u));
+            if (s < nvalid && hh >= 0x7F800000u && inv > 0.0f && inv < 1.0e30f) coldmask |= 1u << s;
+        }
+    }
+    // the list position of the lane's r-th point of the step that starts at pb
+    auto pidx = [&](u32 pb, int r) __attribute__((always_inline)) -> u32 {
+        if constexpr (M == 16) return pb + 64u * (u32)r + (u32)lane;
+        else return pb + (u32)lane * 2u + (u32)(r >> 1) * 128u + (u32)(r & 1);
+    };
+    constexpr int PP = w8_pp<M>;      // points a pass takes, and the parked points that trigger one
+    static_assert(w8_pp<8> == W8_TRIG, "m = 8: a pass takes the eight points that trigger it");
+    constexpr u32 JSH = M == 16 ? 28u : 29u;   // the parking lane's j in the position word's top bits
+    bool first = true;
+    const u32 ptail = p1 > 2u * W8_NW * STEP ? p1 - 2u * W8_NW * STEP : 0u;   // a wave's last two steps start at or behind this point
+    for (u32 pb = p0 + wv * STEP;; pb += W8_NW * STEP) {
+        bool overflow = false;
+        if (pb >= p1) {   // uniform: past the end -- what is still parked gets its sums, then the wave leaves
+            if (ccnt == 0 && !pend) break;
+            flush = true;
+#pragma unroll
+            for (int r = 0; r < 4; ++r) fm[r] = 0;
+        } else {
+            if (__builtin_expect(pend, 0)) {   // uniform: the pass requested during the previous step
+                pend = false;
+                w8m_pass_finish<NQ, KP, M>(ps, nvalid, K, lane);
+                since = 0;
+                w8_bias<NQ>(nvalid, bias);   // (the other waves' offers moved the bounds as well)
+                if (ccnt >= PP || (ccnt > 0 && pb >= ptail)) {   // the next ones are waiting already (or the range ends)
+                    w8m_pass_issue<NQ, M>(ps, cbuf_addr, head, ccnt, gt, lane);
+                    pend = true;
+                }
+            } else if (__builtin_expect(ccnt > 0 && pb >= ptail, 0)) {
+                // the wave's last two steps: what is parked does not wait for company -- its pass is under way while these steps are
+                // scanned, and the end of the range finds an empty ring nine times in ten (a pass worked off THERE is a trip to L2 the
+                // wave sits out, with the other seven waiting for it at the barrier behind: the wait was 8 % of the kernel)
+                wave_sync();
+                w8m_pass_issue<NQ, M>(ps, cbuf_addr, head, ccnt, gt, lane);
+                pend = true;
+            } else if (++since >= (u32)W8_REFRESH) {
+                // the workgroup's bounds move even when this wave has no candidates of its own
+                since = 0;
+                w8_bias<NQ>(nvalid, bias);
+            }
+            // the next step's offsets: past the end the wave's current halves are read once more (no branch around a request, no second
+            // value for a register set to merge with; a half that starts beyond the list repeats the first one: never a byte beyond the
+            // 127 points of slack the four-wave kernels read too)
+            const u32 pn = pb + W8_NW * STEP;
+            const u32 pa = pn < p1 ? pn : pb;
+            const u32 pbb = pa + 128u < p1 ? pa + 128u : pa;
+            u32 qa[4][NB] = {};
+            auto half = [&](auto hc, v4u &cx, u32 pnext) __attribute__((always_inline)) {
+                constexpr int h = decltype(hc)::value;
+                // the half's bytes leave its register set rotated (tied together so that no part of them can sink below the request that
+                // follows), and the next step's half is requested INTO it
+                rw[2 * h][0] = __builtin_amdgcn_perm(cx.y, cx.x, rsel0);
+                rw[2 * h][1] = __builtin_amdgcn_perm(cx.y, cx.x, rsel1);
+                rw[2 * h + 1][0] = __builtin_amdgcn_perm(cx.w, cx.z, rsel0);
+                rw[2 * h + 1][1] = __builtin_amdgcn_perm(cx.w, cx.z, rsel1);
+                asm volatile("" : "+v"(rw[2 * h][0]), "+v"(rw[2 * h][1]), "+v"(rw[2 * h + 1][0]), "+v"(rw[2 * h + 1][1]), "+v"(cx));
+                cx = __builtin_amdgcn_raw_buffer_load_b128(codes, lane16, (int)(pnext * 8u), W8_STREAM_AUX);
+                // the gathers and adds of the half's two points: each form's order is hand-made and measured
+                if constexpr (NQ == 8) {
+                    // eight gathers (32 registers) in flight: the first point's are issued before the first add; each of its entries, once
+                    // summed, hands its registers to the same slot's gather of the second point (one fill and one drain per half)
+                    v4u ev[8];
+                    static_for<8>([&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        const u32 ea = w8_perm(rw[2 * h][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
+                        ev[t] = lds_load_abs<v4u>(ea);
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) qa[2 * h][i] = bias[i];
+                    static_for<8>([&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        qa[2 * h][0] += ev[t].x;
+                        qa[2 * h][1] += ev[t].y;
+                        qa[2 * h][2] += ev[t].z;
+                        qa[2 * h][3] += ev[t].w;
+                        const u32 ea = w8_perm(rw[2 * h + 1][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
+                        ev[t] = lds_load_abs<v4u>(ea);
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) qa[2 * h + 1][i] = bias[i];
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) {
+                        qa[2 * h + 1][0] += ev[t].x;
+                        qa[2 * h + 1][1] += ev[t].y;
+                        qa[2 * h + 1][2] += ev[t].z;
+                        qa[2 * h + 1][3] += ev[t].w;
+                    }
+                } else {
+                    // all sixteen gathers of the half are issued before the first add (left alone the compiler waits after every second read)
+                    v2u ev[2][8];
+                    static_for<2>([&](auto rc) {
+                        constexpr int r = decltype(rc)::value;
+                        static_for<8>([&](auto tc) {
+                            constexpr int t = decltype(tc)::value;
+                            const u32 ea = w8_perm(rw[2 * h + r][t >> 2], t < 4 ? ap0 : ap1, asel[t & 3]);
+                            ev[r][t] = lds_load_abs<v2u>(ea);
+                        });
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int r = 0; r < 2; ++r) {
+                        qa[2 * h + r][0] = bias[0];
+                        qa[2 * h + r][1] = bias[1];
+#pragma unroll
+                        for (int t = 0; t < 8; ++t) {
+                            qa[2 * h + r][0] += ev[r][t].x;
+                            qa[2 * h + r][1] += ev[r][t].y;
+                        }
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            // (m = 16) a quarter of the step: ONE point per lane.  The set's dwords leave it rotated by jd, the next step's quarter is
+            // requested into it, then the point's sixteen lookups
+            auto quarter = [&](auto rc, v4u &cx, u32 pnext) __attribute__((always_inline)) {
+                constexpr int r = decltype(rc)::value;
+                {
+                    const u32 d0 = jlo ? cx.y : cx.x, d1 = jlo ? cx.z : cx.y, d2 = jlo ? cx.w : cx.z, d3 = jlo ? cx.x : cx.w;
+                    rw[r][0] = jhi ? d2 : d0;
+                    rw[r][1] = jhi ? d3 : d1;
+                    rw[r][2] = jhi ? d0 : d2;
+                    rw[r][3] = jhi ? d1 : d3;
+                }
+                asm volatile("" : "+v"(rw[r][0]), "+v"(rw[r][1]), "+v"(rw[r][2]), "+v"(rw[r][3]), "+v"(cx));
+                // (the lane's offset is formed here from the lane number, one shift per request: held in a register of its own across the
+                // loop it was the one value the eight-query form still spilled)
+                int lq = lane;
+                asm volatile("" : "+v"(lq));
+                cx = __builtin_amdgcn_raw_buffer_load_b128(codes, lq * 16, (int)(pnext * 16u), W8_STREAM_AUX);
+                if constexpr (NQ == 8) {
+                    // eight gathers (32 registers) in flight: slots 0 .. 7 are issued before the first add; each entry, once summed, hands its
+                    // registers to the gather of slot t + 8 (one fill and one drain per point)
+                    v4u ev[8];
+                    static_for<8>([&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        ev[t] = lds_load_abs<v4u>(w8_permv(rw[r][t >> 2], apv[t >> 2], aselv[t & 3]));
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+                    for (int i = 0; i < 4; ++i) qa[r][i] = bias[i];
+                    static_for<8>([&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        qa[r][0] += ev[t].x;
+                        qa[r][1] += ev[t].y;
+                        qa[r][2] += ev[t].z;
+                        qa[r][3] += ev[t].w;
+                        ev[t] = lds_load_abs<v4u>(w8_permv(rw[r][2 + (t >> 2)], apv[2 + (t >> 2)], aselv[t & 3]));
+                        __builtin_amdgcn_sched_barrier(0);
+                    });
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) {
+                        qa[r][0] += ev[t].x;
+                        qa[r][1] += ev[t].y;
+                        qa[r][2] += ev[t].z;
+                        qa[r][3] += ev[t].w;
+                    }
+                } else {
+                    // all sixteen gathers of the point are issued before the first add
+                    v2u ev[16];
+                    static_for<16>([&](auto tc) {
+                        constexpr int t = decltype(tc)::value;
+                        ev[t] = lds_load_abs<v2u>(w8_permv(rw[r][t >> 2], apv[t >> 2], aselv[t & 3]));
+                    });
+                    __builtin_amdgcn_sched_barrier(0);
+                    qa[r][0] = bias[0];
+                    qa[r][1] = bias[1];
+#pragma unroll
+                    for (int t = 0; t < 16; ++t) {
+                        qa[r][0] += ev[t].x;
+                        qa[r][1] += ev[t].y;
+                    }
+                }
+                __builtin_amdgcn_sched_barrier(0);
+            };
+            if constexpr (M == 16) {
+                // (a quarter that starts beyond the list repeats the first one: never a byte beyond the 63 points -- 1 008 bytes -- of slack
+                // behind a request that starts inside the list, less than the 127 x 8 bytes the m = 8 forms read)
+                quarter(IntC<0>{}, ca, pa);
+                quarter(IntC<1>{}, cc, pa + 64u < p1 ? pa + 64u : pa);
+                if constexpr (NPT == 4) {
+                    quarter(IntC<2>{}, cb, pbb);
+                    quarter(IntC<3>{}, cd, pa + 192u < p1 ? pa + 192u : pa);
+                }
+            } else {
+            half(IntC<0>{}, ca, pa);
+            half(IntC<1>{}, cb, pbb);
+            }
+            // a field below 0x8000 <=> that query's integer sum is within its budget (w8_bias); one compare for the four points
+            u32 x[4] = {0x80008000u, 0x80008000u, 0x80008000u, 0x80008000u};   // (a point that does not exist is no candidate)
+#pragma unroll
+            for (int r = 0; r < NPT; ++r) x[r] = w8_and(qa[r]);
+            u64 anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
+            if (__builtin_expect(first && coldmask != 0u, 0)) {   // uniform over the WORKGROUP: see above
+                const int r8 = (K + W8_NW - 1) / W8_NW;
+                static_for<NQ>([&](auto sc) {
+                    constexpr int s = decltype(sc)::value;
+                    if ((coldmask >> s) & 1u) {   // uniform
+                        // (the slot's bias is 0 while it has no bound: the fields are the sums)
+                        u32 f[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                        for (int r = 0; r < NPT; ++r) f[r] = (s & 1) ? (qa[r][s >> 1] >> 16) : (qa[r][s >> 1] & 0xffffu);
+                        const u32 V = w8_kth_sum4(f[0], f[1], f[2], f[3], (1u << NPT) - 1u, r8);
+                        if (lane == 0) *w8_ptr<u32>(L::COLD + L::COLD_SLOT * s + 4u * (u32)wv) = V;
+                    }
+                });
+                __syncthreads();
+                static_for<NQ>([&](auto sc) {
+                    constexpr int s = decltype(sc)::value;
+                    if ((coldmask >> s) & 1u) {   // uniform
+                        u32 T = 0;
+#pragma unroll
+                        for (int v = 0; v < W8_NW; ++v) {
+                            const u32 o = __builtin_amdgcn_readfirstlane(w8_lds<u32>(L::COLD + L::COLD_SLOT * s + 4u * (u32)v));
+                            T = o > T ? o : T;
+                        }
+                        const float ub = (w8_dc<NQ>(s) + (float)(T + (u32)M) * (1.00001f / w8_inv<NQ>(s))) * 1.00002f;
+                        // (every wave arrives at the same bound; the wave's own atomic is ahead of its own reads of the word)
+                        if (ub < 3.0e38f && lane == 0) atomicMin(w8_ptr<u64>(L::STHR + 8u * s), make_key(ub, 0xFFFFFFFFu));
+                    }
+                });
+                // the step's fields were accumulated under the old bias: re-based on the new one, and the step is tested again
+                u32 nb[NB];
+                w8_bias<NQ>(nvalid, nb);
+#pragma unroll
+                for (int r = 0; r < NPT; ++r) {
+#pragma unroll
+                    for (int i = 0; i < NB; ++i) qa[r][i] = qa[r][i] - bias[i] + nb[i];
+                    x[r] = w8_and(qa[r]);
+                }
+#pragma unroll
+                for (int i = 0; i < NB; ++i) bias[i] = nb[i];
+                anym = __builtin_amdgcn_ballot_w64((((x[0] & x[1]) & (x[2] & x[3])) & 0x80008000u) != 0x80008000u);
+            }
+            first = false;
+            if (__builtin_expect(anym != 0, 0)) {   // uniform; a step in ten once the bounds are tight
+                // the lane's four candidate flags; a list's last step masks the points past its end (they carry whatever was loaded)
+                bool c[4] = {false, false, false, false};
+#pragma unroll
+                for (int r = 0; r < NPT; ++r) c[r] = (x[r] & 0x80008000u) != 0x80008000u;
+                if (pb + STEP > p1) {   // uniform
+#pragma unroll
+                    for (int r = 0; r < NPT; ++r) c[r] = c[r] && pidx(pb, r) < p1;
+                }
+                u64 m[4] = {0, 0, 0, 0};
+                int n[4] = {0, 0, 0, 0}, ntot = 0;
+#pragma unroll
+                for (int r = 0; r < NPT; ++r) {
+                    m[r] = __builtin_amdgcn_ballot_w64(c[r]);
+                    n[r] = __popcll(m[r]);
+                    ntot += n[r];
+                }
+                // a crowd with no bound at all (a cold work item's first step): bounds from the integer sums first (header)
+                if (ntot > 8 && (int)min(p1 - pb, STEP) >= K) {
+                    bool moved = false;
+                    u32 vb = 0;
+#pragma unroll
+                    for (int r = 0; r < NPT; ++r) vb |= (pidx(pb, r) < p1) ? (1u << r) : 0u;
+                    static_for<NQ>([&](auto sc) {
+                        constexpr int s = decltype(sc)::value;
+                        const float inv = w8_inv<NQ>(s);
+                        // (a scale that is not a normal number -- all-zero or denormal tables -- keeps the plain path)
+                        if (s < nvalid && (u32)(w8_sthr<NQ>(s) >> 32) >= 0x7F800000u && inv > 0.0f && inv < 1.0e30f) {   // uniform
+                            // the sums themselves: field - bias (no borrow: every field started from its bias)
+                            const u32 bs = (s & 1) ? (bias[s >> 1] >> 16) : (bias[s >> 1] & 0xffffu);
+                            u32 f[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+                            for (int r = 0; r < NPT; ++r) f[r] = ((s & 1) ? (qa[r][s >> 1] >> 16) : (qa[r][s >> 1] & 0xffffu)) - bs;
+                            const u32 U = w8_kth_sum4(f[0], f[1], f[2], f[3], vb, K);
+                            const float ub = (w8_dc<NQ>(s) + (float)(U + (u32)M) * (1.00001f / inv)) * 1.00002f;
+                            if (ub < 3.0e38f) {
+                                if (lane == 0) atomicMin(w8_ptr<u64>(L::STHR + 8u * s), make_key(ub, 0xFFFFFFFFu));
+                                moved = true;
+                            }
+                        }
+                    });
+                    if (moved) {
+                        // the step's fields were accumulated under the old bias: re-based on the new one before they are tested again
+                        u32 nb[NB];
+                        w8_bias<NQ>(nvalid, nb);
+                        ntot = 0;
+#pragma unroll
+                        for (int r = 0; r < NPT; ++r) {
+                            const u32 y = w8_and_rebased(qa[r], bias, nb);
+                            c[r] = (y & 0x80008000u) != 0x80008000u && ((vb >> r) & 1u) != 0u;
+                            m[r] = __builtin_amdgcn_ballot_w64(c[r]);
+                            n[r] = __popcll(m[r]);
+                            ntot += n[r];
+                        }
+#pragma unroll
+                        for (int i = 0; i < NB; ++i) bias[i] = nb[i];
+                    }
+                }
+                // park (rotated code bytes, position | rotation << 29: positions stay below 2^28, the code stream's byte offsets are 31-bit)
+                if (__builtin_expect(ccnt + ntot <= W8_RING, 1)) {
+                    int base = head + ccnt;
+#pragma unroll
+                    for (int r = 0; r < NPT; ++r) {
+                        if (n[r] == 0) continue;   // uniform
+                        const int rank = (int)__builtin_amdgcn_mbcnt_hi((u32)(m[r] >> 32), __builtin_amdgcn_mbcnt_lo((u32)m[r], 0u));
+                        if (c[r]) {
+                            u32 *ent = w8_ptr<u32>(cbuf_addr + (u32)((base + rank) & (W8_RING - 1)) * (ES * 4u));
+#pragma unroll
+                            for (int k = 0; k < M / 4; ++k) ent[k] = rw[r][k];
+                            ent[M / 4] = pidx(pb, r) | ((u32)j << JSH);
+                        }
+                        base += n[r];
+                    }
+                    ccnt += ntot;
+                    // a pass is requested when eight points wait and none is in flight; it is worked off at the top of the next step
+                    if (!pend && (ccnt >= PP || pb >= ptail)) {
+                        wave_sync();
+                        w8m_pass_issue<NQ, M>(ps, cbuf_addr, head, ccnt, gt, lane);
+                        pend = true;
+                    }
+                } else {
+#pragma unroll
+                    for (int r = 0; r < 4; ++r) fm[r] = m[r];
+                    overflow = true;
+                }
+            }
+        }
+        // No room in the ring (a crowd the integer bound could not thin out), or the end of the range: ONE copy of the code that parks in
+        // portions and works passes off here and now (the wave waits for each trip to L2; rare)
+        if (__builtin_expect(overflow || flush, 0)) {
+            for (;;) {   // uniform
+#pragma unroll 1
+                for (int r = 0; r < NPT; ++r) {
+                    const u64 mm = r == 0 ? fm[0] : (r == 1 ? fm[1] : (r == 2 ? fm[2] : fm[3]));
+                    if (mm == 0 || ccnt == W8_RING) continue;
+                    const int room = W8_RING - ccnt;
+                    const int rank = (int)__builtin_amdgcn_mbcnt_hi((u32)(mm >> 32), __builtin_amdgcn_mbcnt_lo((u32)mm, 0u));
+                    const bool mine = ((mm >> lane) & 1ull) != 0 && rank < room;
+                    if (mine) {
+                        u32 *ent = w8_ptr<u32>(cbuf_addr + (u32)((head + ccnt + rank) & (W8_RING - 1)) * (ES * 4u));
+#pragma unroll
+                        for (int k = 0; k < M / 4; ++k) ent[k] = r == 0 ? rw[0][k] : (r == 1 ? rw[1][k] : (r == 2 ? rw[2][k] : rw[3][k]));
+                        ent[M / 4] = pidx(pb, r) | ((u32)j << JSH);
+                    }
+                    const u64 took = __builtin_amdgcn_ballot_w64(mine);
+                    ccnt += __popcll(took);
+                    if (r == 0) fm[0] &= ~took; else if (r == 1) fm[1] &= ~took; else if (r == 2) fm[2] &= ~took; else fm[3] &= ~took;
+                }
+                const bool more = (fm[0] | fm[1] | fm[2] | fm[3]) != 0;
+                if (pend) {
+                    pend = false;
+                    w8m_pass_finish<NQ, KP, M>(ps, nvalid, K, lane);
+                    w8_bias<NQ>(nvalid, bias);
+                }
+                if (ccnt > 0 && (more || flush || ccnt >= PP)) {
+                    wave_sync();
+                    w8m_pass_issue<NQ, M>(ps, cbuf_addr, head, ccnt, gt, lane);
                     pend = true;
                     if (more || flush) continue;   // (uniform) worked off at once: room for what is left / nothing may stay behind
                 }
@@ -1080,6 +1649,445 @@ static __device__ __forceinline__ void w8_scan_items(const ScanArgs &a, float *_
     }
 }
 
+template <int NQ, int DS, int KP = 1, int M = 8>
+static __device__ __forceinline__ void w8m_scan_items(const ScanArgs &a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
+                                                     u32 *__restrict__ xq, int nranges)
+{
+    using L = W8Lds<NQ, KP, M>;
+    static_assert(w8_ds_ok(DS), "sub-spaces of 4, 8, 12 or 16 dimensions");
+    static_assert(M == 8 || (M == 16 && (DS == 4 || DS == 8)), "m = 16: d = 64 and d = 128");
+    static_assert(M != 8 || 8u * W8_RES_STRIDE<NQ, DS> * 4u <= L::SMAX - L::RES, "the residuals fit the block sized for DS = 16");
+    static_assert(M != 16 || 16u * W8_RES_STRIDE<NQ, DS> * 4u <= L::COLD - L::PARK, "m = 16: the residuals fit the rings' block (W8Lds::RESB)");
+    static_assert((u32)M * 256u / 4u == (u32)(M / 8) * (u32)W8_THREADS, "the build: four codewords of one sub-quantizer per thread and trip");
+    static_assert(NQ == 8 || 4 * (DS * M) <= W8_THREADS, "NQ = 4: the residual fill is one element per thread");
+    constexpr int D = M * DS;
+    constexpr u32 RS = W8_RES_STRIDE<NQ, DS>;
+    constexpr int G = DS / 4;               // 16-byte groups of a codeword
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
+    const IndexView &ix = a.ix;
+    const int tid = threadIdx.x, lane = tid & 63;
+    const int wv = __builtin_amdgcn_readfirstlane(tid >> 6);     // (a scalar: branches on the wave's number and its position in the list are scalar branches)
+    const int K = a.K;
+    float *res = (float *)(smem + L::RESB);
+    u32 *smax = (u32 *)(smem + L::SMAX);
+    float *sinv = (float *)(smem + L::SMAX) + NQ;
+    float *sdc = (float *)(smem + L::QC);
+    u32 *ssb = (u32 *)(smem + L::QC) + NQ;
+    u32 *spi = (u32 *)(smem + L::QC) + 2 * NQ;
+    u32 *sqi = (u32 *)(smem + L::QC) + 3 * NQ;
+    u64 *shard = (u64 *)(smem + L::HARD);
+    u64 *sthr = (u64 *)(smem + L::STHR);
+    u32 *swi = (u32 *)(smem + L::SWI);
+    const u32 total = a.wi_off[ix.kc];
+    float *gt = gtabs + (size_t)blockIdx.x * W8_GTAB_FLOATS<NQ, M>;
+    const __amdgpu_buffer_rsrc_t gtr = __builtin_amdgcn_make_buffer_rsrc((void *)gt, 0, (int)(W8_GTAB_FLOATS<NQ, M> * 4u), 0x00020000);
+
+    u64 *pool = (u64 *)(smem + L::POOL);
+    // (thread 0's: the part it pulls from, the parts found empty so far)
+    int qcur = nranges > 1 ? (int)(__builtin_amdgcn_s_getreg(20 | (3 << 11)) & 7u) : 0, qtried = 0;
+    // the item behind ticket k of the current part; a part that is exhausted hands over to the next one (a trip per part: the tail only)
+    auto resolve = [&](u32 k) -> u32 {
+        for (;;) {
+            // (nranges is 8 or 1: no division -- this runs between two barriers of every work item)
+            const u32 r0 = nranges == 1 ? 0u : (u32)(((u64)total * (u32)qcur) >> 3), r1 = nranges == 1 ? total : (u32)(((u64)total * (u32)(qcur + 1)) >> 3);
+            if (k < r1 - r0) return r0 + k;
+            qcur = qcur + 1 == nranges ? 0 : qcur + 1;
+            if (++qtried >= nranges) return 0xFFFFFFFFu;
+            k = atomicAdd(xq + qcur * 16, 1u);
+        }
+    };
+    if (tid == 0) swi[0] = resolve(atomicAdd(xq + qcur * 16, 1u));
+    __syncthreads();
+    u32 wi = __builtin_amdgcn_readfirstlane(swi[0]);
+    for (;;) {
+        if (wi >= total) break;   // uniform: every wave of every workgroup reaches this
+        // the NEXT work item's ticket is pulled now and looked at when this one is done: the atomic's trip is off the critical path
+        u32 pulled = 0;
+        if (tid == 0 && qtried < nranges) pulled = atomicAdd(xq + qcur * 16, 1u);
+        do {   // (one trip: `break` = this work item is finished)
+        const int l = __builtin_amdgcn_readfirstlane((int)item_list[wi]);
+        const u32 cnt = __builtin_amdgcn_readfirstlane(a.list_cnt[l]);
+        const u32 ng = (cnt + (u32)(NQ - 1)) / (u32)NQ;
+        const u32 local = wi - __builtin_amdgcn_readfirstlane(a.wi_off[l]);
+        const u32 chunk = local / ng, grp = local - chunk * ng;
+        const u32 len = __builtin_amdgcn_readfirstlane(ix.list_len[l]);
+        const u32 p0 = chunk * a.CH;
+        if (p0 >= len) break;   // uniform
+        const u32 p1 = min(len, p0 + a.CH);
+        const int nvalid = min(NQ, (int)(cnt - grp * (u32)NQ));
+
+        // the queries of the group: thread s < NQ fetches slot s (slots past nvalid repeat slot 0 and can never be candidates)
+        if (tid < NQ) {
+            const int ss = tid < nvalid ? tid : 0;
+            const u32 pi = a.bucket_items[a.bucket_off[l] + grp * (u32)NQ + ss];
+            const u32 qq = pi / (u32)a.w;
+            spi[tid] = pi;
+            sqi[tid] = qq;
+            ssb[tid] = a.probe_base[pi];
+            sdc[tid] = a.probe_dc[pi];
+            const u64 t0 = __hip_atomic_load(&a.qthr[qq], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            shard[tid] = t0;
+            sthr[tid] = t0;
+            smax[tid] = 0u;
+        }
+        // (the pool's 64 NQ entries: the workgroup's last threads, which fetch no slot)
+        if constexpr (KP == 1) {
+        if (tid >= W8_THREADS - 64 * NQ && tid < W8_THREADS) pool[tid - (W8_THREADS - 64 * NQ)] = KEY_MAX;
+        } else {
+            // (the wide pool's 128 NQ entries: one or two per thread)
+#pragma unroll
+            for (int i = 0; i < 128 * NQ / W8_THREADS; ++i) pool[tid + i * W8_THREADS] = KEY_MAX;
+        }
+        __syncthreads();
+        // exact pruning of whole work items, as in scan_kernel: no sum of this list lies below its coarse distance
+        if (a.prune) {
+            bool all = true;
+#pragma unroll
+            for (int s = 0; s < NQ; ++s)
+                all = all && (s >= nvalid || __builtin_amdgcn_readfirstlane(__float_as_uint(sdc[s])) > (u32)(readfirstlane64(shard[s]) >> 32));
+            if (all) {   // uniform
+                if (tid < nvalid) {
+                    const u32 pi = spi[tid];
+                    a.part_cnt[(size_t)pi * a.maxch + chunk] = 0u;
+                    atomicAdd(a.scanned_points + (size_t)(pi & 63u) * 8 + 1, (u64)(p1 - p0));
+                }
+                break;
+            }
+        }
+        // (a chunk's byte offset pb * 8 stays below 2^31: lists of < 2^28 points; m = 16: pb * 16, lists of < 2^27 points)
+        const uint8_t *cbase = ix.codes + (int64_t)readfirstlane64((u64)ix.list_codeoff[l]);
+
+        // (1) residuals r_s = q_s - c (coarsequantizers.jl:40-45), D NQ elements -- NQ / 4 per thread at DS = 16, fewer or none below:
+        // res[ii][t][s], DS + 1 rows of NQ per sub-quantizer (W8_RES_STRIDE)
+        if constexpr (NQ == 8) {
+            const u32 tb = (u32)tid & 511u;
+#pragma unroll
+            for (u32 e = tb; e < 8u * D; e += 512u) {
+                const u32 i = e >> 3, s = e & 7u;
+                res[(i / DS) * RS + (i % DS) * 8u + s] = a.queries[(size_t)sqi[s] * D + i] - ix.centroids[(size_t)l * D + i];
+            }
+        } else {
+            // (element tb = 4 i + s stands 4 (i / DS) floats on: the padding rows of the sub-quantizers below its own)
+            const int tb = tid & 511, i = tb >> 2, s = tb & 3;
+            if (DS == 16 || tb < 4 * D) res[tb + (i / DS) * 4] = a.queries[(size_t)sqi[s] * D + i] - ix.centroids[(size_t)l * D + i];
+        }
+        // (the thread number passes through an opaque move inside the item loop: the lane-constant addresses it feeds -- codewords, table
+        // rows, LDS slots -- would otherwise be hoisted to kernel entry and live, spilled, across the whole persistent loop)
+        int tidb = tid & 511;
+        asm volatile("" : "+v"(tidb));
+        // A thread builds FOUR codewords' entries of ONE sub-quantizer: ii = lane mod 4 (+ 4 for odd waves), codewords cg, cg + 64, + 128,
+        // + 192.  A residual row read from LDS serves the four codewords (16 reads of 16 B per thread; one codeword in each of four
+        // sub-quantizers per thread was 64 -- on the LDS queue the other workgroup's gathers fill), the four lanes of a quad read four
+        // different bank groups (the padding), and the quantised rows below leave conflict-free as they are: the 16 lanes of a store's
+        // service group hold 4 sub-quantizers x 4 copies.
+        // (m = 16: two trips of the build, sub-quantizers ii and ii + 8; the entries go to device memory by label trip by trip and are
+        // quantised from there, step (3))
+        int ii = (tidb & 3) | (((tidb >> 6) & 1) << 2);
+        const int cg = ((tidb >> 2) & 15) | ((tidb >> 7) << 4);
+        const float4 *ct = (const float4 *)ix.codebooks_t;        // [ii][g][c][4], G = DS / 4 groups, ksub = 256
+        // The four codewords come four dimensions at a time (g = 0 .. G - 1), two register sets that take turns inside a REAL loop of
+        // G / 2 trips, two groups each: fully unrolled, the scheduler hoists every request of the build above the arithmetic -- 64 registers
+        // of codewords next to 64 of residual rows -- and spills them as they arrive, a wait for memory each.  An odd count (DS = 4: one
+        // group, DS = 12: three) leaves its last group behind the loop: it stands in cwa by then -- requested up front (G = 1) or by the
+        // trip's second request (G = 3) -- and takes four rows of its own.  Dimensions ascend through trips and tail: the reference's order.
+        float4 cwa[4], cwb[4];
+        u32 cofs = (u32)ii * (u32)(G * 256) + (u32)cg;
+        auto ldcw = [&](float4 (&d)[4], int g) __attribute__((always_inline)) {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) d[j] = ct[cofs + (u32)(g * 256 + 64 * j)];
+        };
+        ldcw(cwa, 0);       // on its way while the residuals settle
+        __syncthreads();
+        // (2) the f32 entries (index.jl:232-236: df = cb - r, sum += df * df for t ascending; no contraction; two queries per packed
+        // instruction: the same IEEE operations element by element), to device memory by label; per-query maxima
+        v4f ent[4][NQ / 4];      // [codeword][queries 4 qh .. 4 qh + 3]
+#pragma unroll 1
+        for (int tr = 0; tr < M / 8; ++tr) {
+        if (M == 16 && tr > 0) {
+            ii += 8;
+            cofs += 8u * (u32)(G * 256);
+            ldcw(cwa, 0);
+        }
+        if constexpr (NQ == 8) {
+            float mx[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+            const u32 roff = L::RESB + (u32)ii * (RS * 4u);
+            // four queries at a time (the four-query build on each half of the residual rows; the codewords are requested again)
+            static_for<2>([&](auto qc) {
+                constexpr int qh = decltype(qc)::value;
+                if (qh == 1) ldcw(cwa, 0);
+                v2f sum[4][2];
+#pragma unroll
+                for (int j = 0; j < 4; ++j) sum[j][0] = sum[j][1] = (v2f){0.0f, 0.0f};
+                // (the rows of a trip -- eight dimensions -- are requested together at its top)
+                v4f rv[8];
+                auto grp = [&](const float4 (&cq)[4], int g2) __attribute__((always_inline)) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const v2f r01 = (v2f){rv[4 * g2 + t].x, rv[4 * g2 + t].y}, r23 = (v2f){rv[4 * g2 + t].z, rv[4 * g2 + t].w};
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) {
+                            const float cv = t == 0 ? cq[j].x : (t == 1 ? cq[j].y : (t == 2 ? cq[j].z : cq[j].w));
+                            const v2f c2 = (v2f){cv, cv};
+                            const v2f d0 = c2 - r01, d1 = c2 - r23;
+                            sum[j][0] = sum[j][0] + d0 * d0;
+                            sum[j][1] = sum[j][1] + d1 * d1;
+                        }
+                    }
+                };
+#pragma unroll 1
+                for (int h = 0; h < G / 2; ++h) {
+#pragma unroll
+                    for (int t = 0; t < 8; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(8 * h + t) * 32u + 16u * qh);
+                    ldcw(cwb, 2 * h + 1);
+                    grp(cwa, 0);
+                    if constexpr (G > 2) ldcw(cwa, h == 0 ? 2 : G - 1);      // (the last trip of an even count repeats a request: no branch around one, no second value to merge)
+                    grp(cwb, 1);
+                }
+                if constexpr (G & 1) {
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(4 * (G - 1) + t) * 32u + 16u * qh);
+                    grp(cwa, 0);
+                }
+#pragma unroll
+                for (int j = 0; j < 4; ++j) {
+                    ent[j][qh] = (v4f){sum[j][0].x, sum[j][0].y, sum[j][1].x, sum[j][1].y};
+                    const int c = cg + 64 * j;
+                    const int label = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                    *(v4f *)(gt + ((size_t)(ii * 256 + label) << 3) + 4 * qh) = ent[j][qh];
+                    mx[4 * qh + 0] = fmaxf(mx[4 * qh + 0], ent[j][qh].x);
+                    mx[4 * qh + 1] = fmaxf(mx[4 * qh + 1], ent[j][qh].y);
+                    mx[4 * qh + 2] = fmaxf(mx[4 * qh + 2], ent[j][qh].z);
+                    mx[4 * qh + 3] = fmaxf(mx[4 * qh + 3], ent[j][qh].w);
+                }
+            });
+            // (entries are >= +0: the bit pattern orders like the value; the wave's maximum on the DPP network and the scalar unit)
+#pragma unroll
+            for (int s = 0; s < 8; ++s) {
+                const u32 wm = w8_row_max_u32(__float_as_uint(mx[s]));
+                if (lane == 0) atomicMax(&smax[s], wm);
+            }
+        } else {
+            v2f sum[4][2];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) sum[j][0] = sum[j][1] = (v2f){0.0f, 0.0f};
+            const u32 roff = L::RESB + (u32)ii * (RS * 4u);
+            // (the rows of a trip -- eight dimensions -- are requested together at its top: a request waits ~1 000 cycles in the LDS queue behind
+            // the other workgroup's gathers, and the build pays that wait once per batch)
+            v4f rv[8];
+            auto grp = [&](const float4 (&cq)[4], int g2) __attribute__((always_inline)) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) {
+                    const v2f r01 = (v2f){rv[4 * g2 + t].x, rv[4 * g2 + t].y}, r23 = (v2f){rv[4 * g2 + t].z, rv[4 * g2 + t].w};
+#pragma unroll
+                    for (int j = 0; j < 4; ++j) {
+                        const float cv = t == 0 ? cq[j].x : (t == 1 ? cq[j].y : (t == 2 ? cq[j].z : cq[j].w));
+                        const v2f c2 = (v2f){cv, cv};
+                        const v2f d0 = c2 - r01, d1 = c2 - r23;
+                        sum[j][0] = sum[j][0] + d0 * d0;
+                        sum[j][1] = sum[j][1] + d1 * d1;
+                    }
+                }
+            };
+#pragma unroll 1
+            for (int h = 0; h < G / 2; ++h) {
+#pragma unroll
+                for (int t = 0; t < 8; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(8 * h + t) * 16u);
+                ldcw(cwb, 2 * h + 1);
+                grp(cwa, 0);
+                if constexpr (G > 2) ldcw(cwa, h == 0 ? 2 : G - 1);      // (the last trip of an even count repeats a request: no branch around one, no second value to merge)
+                grp(cwb, 1);
+            }
+            if constexpr (G & 1) {
+#pragma unroll
+                for (int t = 0; t < 4; ++t) rv[t] = w8_lds<v4f>(roff + (u32)(4 * (G - 1) + t) * 16u);
+                grp(cwa, 0);
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) ent[j][0] = (v4f){sum[j][0].x, sum[j][0].y, sum[j][1].x, sum[j][1].y};
+            float mx[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                const int c = cg + 64 * j;
+                const int label = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                *(v4f *)(gt + ((size_t)(ii * 256 + label) << 2)) = ent[j][0];
+                mx[0] = fmaxf(mx[0], ent[j][0].x);
+                mx[1] = fmaxf(mx[1], ent[j][0].y);
+                mx[2] = fmaxf(mx[2], ent[j][0].z);
+                mx[3] = fmaxf(mx[3], ent[j][0].w);
+            }
+            // (entries are >= +0: the bit pattern orders like the value.  The wave's maximum on the DPP network and the scalar unit: a shuffle
+            // is a trip through the LDS queue -- ~1 000 cycles behind the other workgroup's gathers, six of them in a row per query)
+#pragma unroll
+            for (int s = 0; s < 4; ++s) {
+                const u32 wm = w8_row_max_u32(__float_as_uint(mx[s]));
+                if (lane == 0) atomicMax(&smax[s], wm);
+            }
+        }
+        }
+        __syncthreads();
+        // (3) quantise (quantize_tables_m8's rule: q = min(4095, floor(t * inv)), inv = 4095 / largest entry of the query) and write the
+        // copies of sub-quantizer ii's entry (consecutive labels are 256 B apart: the same banks)
+        {
+            float inv[NQ];
+#pragma unroll
+            for (int s = 0; s < NQ; ++s) {
+                const float mxs = __uint_as_float(smax[s]);
+                inv[s] = mxs > 0.0f ? (float)W8_QCAP<M> / mxs : 0.0f;
+            }
+            if (tid < NQ) sinv[tid] = inv[tid];
+            if constexpr (M == 16) {
+                // THE FILTER AT SIXTEEN TERMS.  q = min(2047, floor(t * inv)), inv = 2047 / largest entry: 16 x 2047 = 32 752 <= 0x7FFF, and
+                // 0x8000 + 32 752 < 2^16 -- a biased field (w8_bias: B <= 0x8000) never carries.  w8_bias is used AS IT IS, and its constants
+                // hold at sixteen terms for this reason: with S the reference's float sum (dc, then sixteen entries, all >= +0, so
+                // S >= (dc + sum t)(1 - u)^16, u = 2^-24), S <= thr implies sum t <= thr (1 + 17 u) - dc, and
+                //   sum q <= sum fl(t inv) <= inv (1 + u)(thr (1 + 17 u) - dc).
+                // w8_bias computes x = ((thr (1 + 2^-18) - dc) inv)(1 + 2^-18) in floats.  fl(thr (1 + 64 u)) >= thr (1 + 62 u): 45 u thr above
+                // what the argument needs, which covers the subtraction's rounding (<= 1 u of a result <= thr (1 + 64 u)); the second
+                // factor's 64 u covers the (1 + u) above and the three roundings behind the subtraction.  So sum q <= floor(x): the `+ 2` is
+                // margin here as at eight terms (where the same argument needs 1 + 9 u).  x >= 32 000 saturates to "every point passes"
+                // (32 752 <= 0x7FFF); x < 0 means thr (1 + 62 u) < dc: no candidate exists; a scale of 0, inf or NaN (all-zero or denormal
+                // tables) makes x 0, +-inf or NaN: every point passes, or thr < dc.  The cold-start bounds read S < (dc + (Q + 16) / inv)
+                // (1 + 19 u) -- t inv (1 - u) < q + 1 per term, sixteen roundings of S -- against the (1 + 168 u)(1 + 335 u) of the code.
+                // tests/test_wg8_m16_filter.py restates all of this in numpy and shows that the cap 4095 of m = 8 overflows at sixteen terms.
+                // The entries come back from device memory (written by
+                // this workgroup in front of the barrier above, read from L2 as the passes read them), by LABEL: thread -> sub-quantizer
+                // tid mod 16, labels tid / 16 + 32 k, four at a time.  The 16 lanes of a row write the 16 sub-quantizers of one label -- NQ = 8:
+                // 16 x 16 B, the 64 banks once; NQ = 4: 16 x 8 B, and the next row the other copy (copy (cp + lane / 16) mod 2): the 32 lanes
+                // of a store's service group write 32 different bank pairs.
+                const u32 i3 = (u32)tidb & 15u, l0 = (u32)tidb >> 4;
+#pragma unroll 1
+                for (u32 k = 0; k < 8u; k += 4u) {
+                    v4f e[4][NQ / 4];
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj)
+#pragma unroll
+                        for (int q4 = 0; q4 < NQ / 4; ++q4) e[jj][q4] = w8_gtab_load<NQ>(gtr, i3, l0 + 32u * (k + (u32)jj), q4);
+#pragma unroll
+                    for (int jj = 0; jj < 4; ++jj) {
+                        const u32 lb = l0 + 32u * (k + (u32)jj);
+                        u32 f[NQ];
+#pragma unroll
+                        for (int s = 0; s < NQ; ++s) {
+                            const u32 v = (u32)floorf(e[jj][s >> 2][s & 3] * inv[s]);
+                            f[s] = v < W8_QCAP<16> ? v : W8_QCAP<16>;
+                        }
+                        if constexpr (NQ == 8) {
+                            *(uint4 *)(smem + ((lb << 8) | (i3 << 4))) = make_uint4(f[0] | (f[1] << 16), f[2] | (f[3] << 16), f[4] | (f[5] << 16), f[6] | (f[7] << 16));
+                        } else {
+                            const uint2 qv = make_uint2(f[0] | (f[1] << 16), f[2] | (f[3] << 16));
+#pragma unroll
+                            for (int cp = 0; cp < 2; ++cp) *(uint2 *)(smem + ((lb << 8) | (i3 << 3) | ((u32)((cp + (lane >> 4)) & 1) << 7))) = qv;
+                        }
+                    }
+                }
+            } else {
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                float ev[NQ];
+#pragma unroll
+                for (int qh = 0; qh < NQ / 4; ++qh) {
+                    ev[4 * qh + 0] = ent[j][qh].x;
+                    ev[4 * qh + 1] = ent[j][qh].y;
+                    ev[4 * qh + 2] = ent[j][qh].z;
+                    ev[4 * qh + 3] = ent[j][qh].w;
+                }
+                u32 f[NQ];
+#pragma unroll
+                for (int s = 0; s < NQ; ++s) {
+                    const u32 v = (u32)floorf(ev[s] * inv[s]);
+                    f[s] = v < 4095u ? v : 4095u;
+                }
+                if constexpr (NQ == 8) {
+                    // two copies, copy (cp + lane / 4) mod 2: the 8 lanes of a 16-byte store's service group write 8 different four-bank groups
+                    const uint4 qv = make_uint4(f[0] | (f[1] << 16), f[2] | (f[3] << 16), f[4] | (f[5] << 16), f[6] | (f[7] << 16));
+                    const int c = cg + 64 * j;
+                    const int lb = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                    const u32 row = ((u32)lb << 8) | ((u32)ii << 4);
+#pragma unroll
+                    for (int cp = 0; cp < 2; ++cp) *(uint4 *)(smem + (row | ((u32)((cp + (lane >> 2)) & 1) << 7))) = qv;
+                } else {
+                    // four copies, copy (cp + lane / 4) mod 4: the 16 lanes of a store's service group write 16 different bank pairs
+                    const uint2 qv = make_uint2(f[0] | (f[1] << 16), f[2] | (f[3] << 16));
+                    const int c = cg + 64 * j;
+                    const int lb = ix.identity_labels ? c : (int)ix.labels[ii * 256 + c];
+                    const u32 row = ((u32)lb << 8) | ((u32)ii << 3);
+#pragma unroll
+                    for (int cp = 0; cp < 4; ++cp) *(uint2 *)(smem + (row | ((u32)((cp + (lane >> 2)) & 3) << 6))) = qv;
+                }
+            }
+            }
+        }
+        // the wave's first two steps of code bytes: requested here, behind the build (held across it they were spilled: a store that waits
+        // for the load it saves)
+        // (a list's last step reads up to 127 points past p1 -- other lists' bytes or the slack behind the last list, never used: as scan_kernel)
+        const __amdgpu_buffer_rsrc_t codes = __builtin_amdgcn_make_buffer_rsrc((void *)cbase, 0, (int)0x7FFFFFF0, 0x00020000);
+        // (m = 16: four sets -- ca, cc, cb, cd hold the step's quarters 0, 1, 2, 3; m = 8 leaves cc and cd alone)
+        v4u ca = (v4u){0u, 0u, 0u, 0u}, cb = ca, cc = ca, cd = ca;
+        {
+            // (m = 16 with eight queries: a step is 128 points, the sets ca and cc -- w8m_scan_range, NPT)
+            const u32 pb0 = p0 + (u32)wv * (M == 16 && NQ == 8 ? 128u : 256u);
+            if (pb0 < p1) {
+                if constexpr (M == 16 && NQ == 8) {
+                    ca = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)(pb0 * 16u), 0);
+                    cc = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)((pb0 + 64u < p1 ? pb0 + 64u : pb0) * 16u), 0);
+                } else if constexpr (M == 16) {
+                    ca = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)(pb0 * 16u), 0);
+                    cc = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)((pb0 + 64u < p1 ? pb0 + 64u : pb0) * 16u), 0);
+                    cb = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)((pb0 + 128u < p1 ? pb0 + 128u : pb0) * 16u), 0);
+                    cd = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)((pb0 + 192u < p1 ? pb0 + 192u : pb0) * 16u), 0);
+                } else {
+                ca = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)(pb0 * 8u), 0);
+                cb = __builtin_amdgcn_raw_buffer_load_b128(codes, lane * 16, (int)((pb0 + 128u < p1 ? pb0 + 128u : pb0) * 8u), 0);
+                }
+            }
+        }
+        __syncthreads();   // tables complete (LDS copies; the f32 stores have left for L2: the barrier's release covers them)
+
+        __builtin_amdgcn_s_setprio(W8_PRIO_SCAN);
+        w8m_scan_range<NQ, KP, M>(codes, p0, p1, nvalid, K, wv, lane, ca, cb, cc, cd, gtr);
+        __builtin_amdgcn_s_setprio(W8_PRIO_REST);
+
+        // ---- every wave has offered what it had: wave s < nvalid hands slot s of the pool over as it is -- the entries fill from index 0
+        // (an offer takes the first empty one), the merge kernel behind pushes them through a selector in any order
+        __syncthreads();
+        if constexpr (KP == 2) {
+        // (the wide pool: both halves of slot s, entries 0 .. fc - 1 -- a prefix, as above -- in the pool's order)
+        if (wv < nvalid) {
+            const int s = wv;
+            const u64 v = lane < K ? pool[128 * s + lane] : 0ull;
+            const u64 vh = lane + 64 < K ? pool[128 * s + 64 + lane] : 0ull;
+            const int fc = __popcll(__builtin_amdgcn_ballot_w64(lane < K && v != KEY_MAX)) + __popcll(__builtin_amdgcn_ballot_w64(lane + 64 < K && vh != KEY_MAX));
+            const size_t slot = (size_t)spi[s] * a.maxch + chunk;
+            if (lane < fc) a.part_keys[slot * K + lane] = v;
+            if (lane + 64 < fc) a.part_keys[slot * K + 64 + lane] = vh;
+            if (fc == K) {   // uniform
+                const u64 kth = w8_wave_max_u64(v > vh ? v : vh);
+                if (lane == 0) atomicMin(&a.qthr[sqi[s]], kth);
+            }
+            if (lane == 0) a.part_cnt[slot] = (u32)fc;
+        }
+        } else {
+        if (wv < nvalid) {
+            const int s = wv;
+            const u64 v = lane < K ? pool[64 * s + lane] : 0ull;
+            const int fc = __popcll(__builtin_amdgcn_ballot_w64(lane < K && v != KEY_MAX));
+            const size_t slot = (size_t)spi[s] * a.maxch + chunk;
+            if (lane < fc) a.part_keys[slot * K + lane] = v;
+            if (fc == K) {   // uniform
+                const u64 kth = w8_wave_max_u64(v);
+                if (lane == 0) atomicMin(&a.qthr[sqi[s]], kth);
+            }
+            if (lane == 0) a.part_cnt[slot] = (u32)fc;
+        }
+        }
+        } while (false);
+        __syncthreads();            // every wave is done with this item's state in LDS
+        if (tid == 0) swi[0] = qtried < nranges ? resolve(pulled) : 0xFFFFFFFFu;
+        __syncthreads();
+        wi = __builtin_amdgcn_readfirstlane(swi[0]);
+    }
+}
+
 // The entry points.  wg8_scan_kernel<NQ> is the kernel of DS = 16 (d = 128) under the name it has always had -- what the profiles, the
 // counters' kernel filters and the register-budget test look for; wg8_scan_kernel<NQ, DS> are the narrower sub-spaces.
 template <int NQ>
@@ -1102,4 +2110,12 @@ __global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_wide_scan_kernel(co
                                                                       u32 *__restrict__ xq, int nranges)
 {
     w8_scan_items<NQ, DS, 2>(a, gtabs, item_list, xq, nranges);
+}
+// Sixteen sub-quantizers (M = 16: d = 16 DS, DS = 8 -- PQ16 at d = 128 -- and 4; K <= 64; on request, table modes 6 / 7), again under a
+// name of its own.
+template <int NQ, int DS>
+__global__ __launch_bounds__(W8_THREADS, W8_NW / 2) void wg8_m16_scan_kernel(const ScanArgs a, float *__restrict__ gtabs, const u32 *__restrict__ item_list,
+                                                                     u32 *__restrict__ xq, int nranges)
+{
+    w8m_scan_items<NQ, DS, 1, 16>(a, gtabs, item_list, xq, nranges);
 }

@@ -421,7 +421,8 @@ class IVFADCIndex:
         three-product bf16 split instead of one f16 product per entry; 5 / 6: as 0 with the eight-wave list-major kernel never /
         wherever it is instantiated -- m = 8, ksub = 256, K <= 64, d = 32 / 64 / 96 / 128 (dsub = 4 / 8 / 12 / 16), with or without a list
         partition (set_list_partition); 7: as 6 with its eight-query form; 8 / 9: as 6 / 7, and for 64 < K <= 128 the kernel's wide-pool
-        form (two pool entries per lane) instead of the four-wave kernel -- K <= 64 and K > 128 run what 6 / 7 run.  Mode 0 takes that
+        form (two pool entries per lane) instead of the four-wave kernel -- K <= 64 and K > 128 run what 6 / 7 run.  6 / 7 (8 / 9 at K <= 64)
+        also take the kernel for m = 16 at d = 128 or 64 (PQ16; K <= 64), which no other mode does.  Mode 0 takes that
         kernel unasked for d = 128 without a list partition on lists of 8192 points or more; get_stats()["last_striped"] is 2 / 3 when
         its four- / eight-query form ran, 4 / 5 for the wide-pool form.
         Results are the same bytes in every mode."""

@@ -7,10 +7,13 @@ mode -- 5: never the eight-wave kernel (what the plan ran before the kernel knew
 plan's own choice -- the scan time from events: the median of `--windows` windows of `--reps` launches each, and the windows' spread.
 With --partition N every search is rank 0's share of an N-way list partition (ivfadc_search_device_partial).
 --k sets K (default 10).  Above 64 the eight-wave kernel runs through table modes 8 / 9 only (its wide-pool form, K <= 128); mode 6 is the
-four-wave kernel with LDS selectors there, which is what the A/B of the wide pool compares with:
+four-wave kernel with LDS selectors there, which is what the A/B of the wide pool compares with.
+--m 16 builds the index with sixteen sub-quantizers (d = 128 and 64: wg8_m16_scan_kernel<NQ, DS>, on request only -- modes 6 / 7; modes 5
+and 0 are the four-wave kernel with bank-striped f32 tables there, K <= 64):
 
     python tools/w8_dsub_bench.py [--d 32,64,96,128] [--windows 5] [--reps 8] [--partition 8]
     python tools/w8_dsub_bench.py --d 128 --k 100,128 --modes 6,8,9 --out profiles/wg8_wide.json
+    python tools/w8_dsub_bench.py --m 16 --d 128,64 --modes 5,6,7,0 --out profiles/wg8_m16.json
 """
 import argparse
 import json
@@ -22,12 +25,24 @@ import numpy as np
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
 import ivfadc_jl_amd as pkg  # noqa: E402
 
-M, KC, LIST = 8, 512, 65536
+KC, LIST = 512, 65536
 BATCHES = ((4096, 2), (4096, 1), (1024, 1))
 KERNEL = {0: "reference-order", 1: "four-wave", 2: "eight-wave q4", 3: "eight-wave q8", 4: "eight-wave wide q4", 5: "eight-wave wide q8"}
 
 
-def build(d, seed=0):
+def kernel_symbol(m, dsub, striped):
+    """The instantiation behind stats.last_striped 2 ... 5 (csrc/wg8scan.hip.h); None for the four-wave kernels."""
+    if striped not in (2, 3, 4, 5):
+        return None
+    nq = 8 if striped in (3, 5) else 4
+    if m == 16:
+        return "wg8_m16_scan_kernel<%d, %d>" % (nq, dsub)
+    if striped >= 4:
+        return "wg8_wide_scan_kernel<%d, %d>" % (nq, dsub)
+    return "wg8_scan_kernel<%d>" % nq if dsub == 16 else "wg8_scan_kernel<%d, %d>" % (nq, dsub)
+
+
+def build(d, seed=0, M=8):
     rng = np.random.default_rng(seed)
     n = KC * LIST
     cent = rng.random((KC, d), dtype=np.float32)
@@ -41,6 +56,7 @@ def build(d, seed=0):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--d", default="32,64,96,128")
+    ap.add_argument("--m", type=int, default=8, choices=(8, 16), help="sub-quantizers (16: d = 128 and 64)")
     ap.add_argument("--windows", type=int, default=5)
     ap.add_argument("--reps", type=int, default=8)
     ap.add_argument("--modes", default="5,6,7,0")
@@ -49,9 +65,10 @@ def main():
     ap.add_argument("--out", default="", help="also write the runs to this JSON file")
     args = ap.parse_args()
     import torch
+    M = args.m
     runs = []
     for d in (int(x) for x in args.d.split(",")):
-        g, cent = build(d)
+        g, cent = build(d, M=M)
         if args.partition > 1:
             g.set_list_partition(args.partition, 0)
         for K, (nq, w) in ((int(k), b) for k in args.k.split(",") for b in BATCHES):
@@ -82,9 +99,10 @@ def main():
                     win.append(g.get_stats()["scan_ms"] / args.reps)
                 st = g.get_stats()
                 g.set_profiling(0)
-                runs.append({"tool": "w8_dsub_bench", "d": d, "dsub": d // M, "kc": KC, "list_len": LIST, "K": K, "nq": nq, "w": w,
+                runs.append({"tool": "w8_dsub_bench", "m": M, "d": d, "dsub": d // M, "kc": KC, "list_len": LIST, "K": K, "nq": nq, "w": w,
                              "probes_per_list": nq * w / KC, "partition": args.partition, "table_mode": mode,
-                             "last_striped": st["last_striped"], "kernel": KERNEL.get(st["last_striped"], "?"), "qg": st["last_qg"],
+                             "last_striped": st["last_striped"], "kernel": KERNEL.get(st["last_striped"], "?"),
+                             "kernel_symbol": kernel_symbol(M, d // M, st["last_striped"]), "qg": st["last_qg"],
                              "chunk": st["last_chunk"], "scan_lds": st["last_scan_lds"], "scan_grid": st["last_scan_grid"],
                              "scan_ms_median": float(np.median(win)), "scan_ms_spread": float(max(win) - min(win)),
                              "scan_ms_windows": [round(x, 4) for x in win]})
