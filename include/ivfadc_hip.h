@@ -82,7 +82,12 @@ int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
  * _synth_lists, ivfadc_debug_lb_table) return IVFADC_ERR_STATE there, and the _u16 entries return IVFADC_ERR_STATE on an 8-bit handle.
  * Every other entry (the searches, views, delete / shift, dims, save / load, stats, tuning, pruning, coarse modes) serves both widths.
  * Code and label buffers of the _u16 entries are declared void * and hold uint16_t (little-endian, as the file stores them).
- * ivfadc_set_list_partition with nparts > 1 returns IVFADC_ERR_INVALID on a 16-bit handle.                                    */
+ * ivfadc_set_list_partition with nparts > 1 returns IVFADC_ERR_INVALID on a 16-bit handle.
+ * Searches on a 16-bit handle run the list scan of u16scan.hip.h for K <= 64 and the generic path (any K and w) above; with
+ * ivfadc_set_table_mode(h, 10) the scan kernel also serves 64 < K through LDS selectors wherever
+ *     32 (m dsp + qg cap) + 32 912 B <= 160 KB,  dsp = dsub rounded up to 4, cap = max(128, pow2ceil(K + 64)), qg = pairs per work item,
+ * holds at qg = 1 (the plan halves qg until it holds: m dsp + qg cap <= 4091).  That is K <= 1984 for m dsp <= 2040, K <= 960 up to 3064,
+ * K <= 448 up to 3576, K <= 192 up to 3832; any other K > 64 takes the generic path as in mode 0 (stats.last_qg == -2).        */
 /* As ivfadc_create, for U = UInt16: 1 <= ksub <= 65536, code_labels is m x ksub uint16_t (distinct within a block).  Validation runs
  * before any device call.                                                                                                  */
 int ivfadc_create_u16(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
@@ -455,7 +460,10 @@ int ivfadc_set_query_token(ivfadc_t *h, uint64_t token);
  * d = 128 or d = 64 (wg8_m16_scan_kernel<NQ, DS>: PQ16; K <= 64, lists below 2^27 points), which no other mode does: the default plan of
  * an m = 16 index is the four-wave kernel, as before.  Mode 0 takes that kernel on its own
  * for d = 128 without a list partition, on lists of 8192 points or more; the other widths and the list-partitioned
- * mode get it through 6 / 7, K up to 128 through 8 / 9 (stats.last_striped tells which kernel ran).  Results are identical in every mode: whatever a filter lets through is recomputed in the reference's
+ * mode get it through 6 / 7, K up to 128 through 8 / 9 (stats.last_striped tells which kernel ran).  10 = as 0, and on a 16-bit handle
+ * (ivfadc_create_u16) the scan kernel also serves 64 < K wherever its LDS need fits a CU (u16_wide_scan_kernel: K <= 1984 at small
+ * m x dsub, see "Code width" above; stats.last_qg >= 1 and stats.last_scan_lds tell that it ran) instead of the generic path; on an 8-bit
+ * handle 10 plans exactly what 0 plans.  Results are identical in every mode: whatever a filter lets through is recomputed in the reference's
  * order -- from the f32 tables or, in the matrix-core rounds, from the f32 codebook -- before it meets the bound.       */
 int ivfadc_set_table_mode(ivfadc_t *h, int mode);
 

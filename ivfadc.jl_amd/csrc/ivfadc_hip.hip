@@ -319,6 +319,7 @@ struct ivfadc_index {
     // f32 tables, 32 or 64 KB per workgroup
     DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
     int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
+    bool u16_wide = false;       // table mode 10: a 16-bit handle runs 64 < K on the scan kernel's LDS-selector form (u16_wide_scan_kernel) where its LDS need fits
     bool wg8_wide = false;       // table modes 8 / 9: 64 < K <= 128 runs the kernel's wide-pool form (wg8_wide_scan_kernel) wherever wg8_mode takes the kernel
     // list-partitioned multi-GPU mode (ivfadc_set_list_partition): this handle scans the probed lists l with l % part_n == part_i only and
     // leaves partial top-K keys; partial_keys: where the running call wants them (null: ids as usual); the batch whose probe arrays stand
@@ -850,15 +851,16 @@ int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its s
     return IVFADC_OK;
 }
 
-// U = UInt16 (u16scan.hip.h): always list-major, K <= 64 (search_dev sends larger K to the generic path).  Pairs per work item from
-// the expected probes per list (a codeword read serves every pair of the item); chunks of whole passes, about two items per CU.
+// U = UInt16 (u16scan.hip.h): always list-major; K <= 64 on register selectors, 64 < K on LDS selectors where table mode 10 asks for
+// them (search_dev sends larger K to the generic path otherwise).  Pairs per work item from the expected probes per list (a codeword
+// read serves every pair of the item), halved for K > 64 until the selector buffers fit; chunks of whole passes, about two items per CU.
 int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
 {
     pl.fits = true;
     pl.lanes = false;
-    pl.small_k = true;
+    pl.small_k = K <= 64;
     pl.small_w = w <= 64;
-    pl.cap = 64;
+    pl.cap = pl.small_k ? 64 : std::max(128, pow2ceil(K + 64));
     pl.capw = pl.small_w ? 64 : std::max(128, pow2ceil(w + 64));
     pl.query_major = false;
     pl.fuse_topw = pl.lb = pl.nf = pl.wg8 = pl.wg8q8 = pl.wg8wide = false;
@@ -870,8 +872,10 @@ int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
     const double ppl = (double)nq * w / std::max(1, h->kc);
     int qg = ppl >= 6.0 ? 8 : (ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1));
     if (h->force_qg == 1 || h->force_qg == 2 || h->force_qg == 4 || h->force_qg == 8) qg = h->force_qg;
+    if (!pl.small_k)   // 4 x qg x cap keys beside the tables: m dsp + qg cap <= 4091 (u16scan.hip.h)
+        while (qg > 1 && u16_wide_lds_bytes(h->m, h->dsub, qg, pl.cap) > LDS_MAX) qg >>= 1;
     pl.qg = qg;
-    pl.lds = u16_lds_bytes(h->m, h->dsub);
+    pl.lds = pl.small_k ? u16_lds_bytes(h->m, h->dsub) : u16_wide_lds_bytes(h->m, h->dsub, qg, pl.cap);
     if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
     const double ch = (double)nq * w * avg_len / qg / (2.0 * h->num_cu);
     uint32_t CH = U16_PASS;
@@ -1514,11 +1518,12 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         const size_t upper = np * (size_t)pl.maxch;
         ivfadc_index::EvPair ep;
         if (h->u16) {
+            void (*uk)(const ScanArgs, int) = pl.small_k ? u16_scan_kernel : u16_wide_scan_kernel;
             int occ = 0;
-            TRY(fn_occupancy(h, (const void *)u16_scan_kernel, pl.lds, occ));
+            TRY(fn_occupancy(h, (const void *)uk, pl.lds, occ));
             const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
             if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(u16_scan_kernel, dim3(grid), dim3(256), pl.lds, h->stream, a, pl.qg);
+            hipLaunchKernelGGL(uk, dim3(grid), dim3(256), pl.lds, h->stream, a, pl.qg);
             HIP_TRY(hipGetLastError());
             if (h->profiling) TRY(ev_end(h, ep));
             h->stats.last_scan_grid = (int)grid;
@@ -2032,7 +2037,7 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
     if (!h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
     const bool parted = h->part_n > 1;
     if (!parted && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
-    if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64)) {
+    if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64 && !h->u16_wide)) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
         return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
     }
@@ -2801,7 +2806,7 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
 // settings that change how a search runs, copied to the internal second lane before every use
 static void copy_search_config(ivfadc_index *dst, const ivfadc_index *src)
 {
-    dst->wg8_mode = src->wg8_mode; dst->wg8_wide = src->wg8_wide;
+    dst->wg8_mode = src->wg8_mode; dst->wg8_wide = src->wg8_wide; dst->u16_wide = src->u16_wide;
     dst->allow_nf = src->allow_nf; dst->allow_sq = src->allow_sq; dst->sq_inside = src->sq_inside; dst->allow_lb = src->allow_lb;
     dst->force_lb = src->force_lb; dst->allow_bf16 = src->allow_bf16; dst->allow_f16 = src->allow_f16; dst->lb_use_f16 = src->lb_use_f16; dst->allow_prune = src->allow_prune; dst->allow_listed = src->allow_listed;
     dst->allow_filt = src->allow_filt; dst->allow_mfma = src->allow_mfma; dst->mfma_min_kc = src->mfma_min_kc; dst->ws_budget = src->ws_budget;
@@ -4506,7 +4511,7 @@ int ivfadc_set_table_mode(ivfadc_t *h, int mode)
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    if (mode < 0 || mode > 9) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 9");
+    if (mode < 0 || mode > 10) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 10");
     h->allow_filt = mode != 1 && getenv("IVFADC_EXACT_TABLES") == nullptr;
     h->force_lb = mode == 2 || mode == 4;
     // 3 / 4: as 0 / 2 with the matrix-core tables built from the three-product bf16 split instead of one f16 product (A/B runs, tests)
@@ -4517,6 +4522,9 @@ try {
     // four-wave kernel with LDS selectors; K <= 64 and K > 128 run exactly what 6 / 7 run
     h->wg8_mode = mode == 5 ? -1 : (mode == 6 || mode == 8 ? 1 : (mode == 7 || mode == 9 ? 2 : 0));
     h->wg8_wide = mode == 8 || mode == 9;
+    // 10: as 0, and on a 16-bit handle 64 < K runs the scan kernel's LDS-selector form (u16_wide_scan_kernel) wherever its LDS need fits a
+    // CU (K <= 1984 at small m x dsub: u16scan.hip.h) instead of the generic path; an 8-bit handle plans what mode 0 plans
+    h->u16_wide = mode == 10;
     return IVFADC_OK;
 } IVF_CATCH
 

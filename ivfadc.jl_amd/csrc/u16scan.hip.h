@@ -18,6 +18,14 @@
 // four waves' selectors are merged per pair at the end of the chunk, the partial top-K goes out as the other list-major kernels'
 // do, and merge_kernel<true> finishes it.  Exact probe pruning as in scan_kernel: an item whose pairs' K-th keys are all below
 // their coarse distances is skipped.
+//
+// K > 64 (u16_wide_scan_kernel, on request: ivfadc_set_table_mode(h, 10)): the same loop with LDS selectors (WSel<false>), one per wave
+// and pair, selbuf[4 waves][qg][cap] u64 with cap = max(128, pow2ceil(K + 64)) as in make_plan.  The buffers sit BESIDE the table area:
+// the tables are rebuilt for every sub-space, tile and pass, the selectors live for the whole chunk.  At the end of the chunk the waves
+// sort their buffers, wave v absorbs the other waves' entries of pairs v and v + 4 in place, and merge_kernel<false> finishes.
+// Reach: 32 (m dsp + qg cap) + 32 912 B <= 160 KB, i.e. m dsp + qg cap <= 4091 (dsp = dsub rounded up to 4); the plan halves qg until
+// that holds.  cap = 4096 (K >= 1985) never fits, so K <= 1984 where m dsp <= 2040 (qg = 1), K <= 960 up to m dsp <= 3064, K <= 448 up
+// to 3576, K <= 192 up to 3832; beyond that (and for K > 1984) the search takes the generic path as before.
 #pragma once
 #include "kernels.hip.h"
 
@@ -35,18 +43,27 @@ static inline size_t u16_lds_bytes(int m, int dsub)
     return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)U16_TAB_FLOATS * 4 + 4 * U16_P * 4 + 16;
 }
 
-// qg: the bucket grouping of the plan (1, 2, 4 or 8); items carry up to qg pairs
-__global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg)
+// ... of u16_wide_scan_kernel: the selector buffers [4 waves][qg][cap] u64 between the table area and the small words
+static inline size_t u16_wide_lds_bytes(int m, int dsub, int qg, int cap)
+{
+    return u16_lds_bytes(m, dsub) + (size_t)4 * qg * cap * 8;
+}
+
+// qg: the bucket grouping of the plan (1, 2, 4 or 8); items carry up to qg pairs.  SMALL: K <= 64, register selectors
+template <bool SMALL> static __device__ __forceinline__ void u16_scan_body(const ScanArgs &a, int qg)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const IndexView &ix = a.ix;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int d = ix.d, m = ix.m, ksub = ix.ksub, dsub = ix.dsub, K = a.K;
+    const int cap = SMALL ? 64 : a.cap;
     const int dsp = (dsub + 3) & ~3, rstride = m * dsp;
     float *resid = (float *)smem_raw;                                  // [P][m][dsp]
     float *tab = resid + (size_t)U16_P * rstride;                     // [P][T]
-    u64 *xch = (u64 *)tab;                                             // [4 waves][P][64] after the scan
-    int *scnt = (int *)(tab + U16_TAB_FLOATS);                         // [4][P]
+    // SMALL: xch[4 waves][P][64] aliases the tables after the scan; else the selector buffers [4 waves][qg][cap], which ARE the exchange
+    u64 *xch = SMALL ? (u64 *)tab : (u64 *)(tab + U16_TAB_FLOATS);
+    const size_t xw = SMALL ? (size_t)U16_P : (size_t)qg;              // selectors per wave in xch
+    int *scnt = SMALL ? (int *)(tab + U16_TAB_FLOATS) : (int *)(xch + (size_t)4 * qg * cap);   // [4][P]
     u32 *swi = (u32 *)(scnt + 4 * U16_P);                              // [2]
     const bool direct = qg == 1 && a.direct_items != 0;
     const u32 total = direct ? a.direct_items : a.wi_off[ix.kc];
@@ -93,7 +110,7 @@ __global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg)
         int qi[U16_P];
         float dc[U16_P];
         u64 hard[U16_P];
-        WSel<true> sel[U16_P];
+        WSel<SMALL> sel[U16_P];
 #pragma unroll
         for (int s = 0; s < U16_P; ++s) {
             const int ss = s < nvalid ? s : 0;
@@ -102,7 +119,7 @@ __global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg)
             dc[s] = a.probe_dc[pidx[s]];
             sbase[s] = a.probe_base[pidx[s]];
             hard[s] = readfirstlane64(__hip_atomic_load(&a.qthr[qi[s]], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
-            sel[s].init(hard[s], nullptr, 64, K);
+            sel[s].init(hard[s], SMALL ? nullptr : xch + ((size_t)wv * xw + ss) * cap, cap, K);   // (slots >= nvalid are never pushed to)
         }
         // exact probe pruning (scan_kernel): no sum of this list is below its coarse distance
         if (a.prune) {
@@ -206,22 +223,23 @@ __global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg)
             }
         }
 
-        // per-wave results -> LDS (aliasing the tables), then wave v merges pairs v and v + 4 and publishes them
+        // per-wave results -> LDS (SMALL: aliasing the tables; else sorted in place in the selector buffers), then wave v merges pairs v
+        // and v + 4 and publishes them
         int mycnt[U16_P];
 #pragma unroll
         for (int s = 0; s < U16_P; ++s) mycnt[s] = s < nvalid ? sel[s].finish(K, lane) : 0;
-        __syncthreads();
+        if (SMALL) __syncthreads();   // the exchange area aliases the tables: every wave must be done scanning
 #pragma unroll
         for (int s = 0; s < U16_P; ++s)
             if (s < nvalid) {
-                sel[s].store(xch + ((size_t)wv * U16_P + s) * 64, mycnt[s], lane);
+                sel[s].store(xch + ((size_t)wv * xw + s) * cap, mycnt[s], lane);
                 if (lane == 0) scnt[wv * U16_P + s] = mycnt[s];
             }
         __syncthreads();
 #pragma unroll
         for (int s = 0; s < U16_P; ++s) {
             if ((s & 3) == wv && s < nvalid) {
-                merge_waves(sel[s], xch + (size_t)s * 64, (size_t)U16_P * 64, scnt + s, U16_P, K, hard[s], wv, lane);
+                merge_waves(sel[s], xch + (size_t)s * cap, xw * cap, scnt + s, U16_P, K, hard[s], wv, lane);
                 const int fc = sel[s].finish(K, lane);
                 const size_t slot = (size_t)pidx[s] * a.maxch + chunk;
                 u64 *dst = a.part_keys + slot * K;
@@ -234,6 +252,10 @@ __global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg)
         }
     }
 }
+
+__global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<true>(a, qg); }
+// 64 < K: LDS selectors beside the tables (a.cap; dynamic LDS u16_wide_lds_bytes)
+__global__ __launch_bounds__(256) void u16_wide_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<false>(a, qg); }
 
 // _encode_point's quantize_data for UInt16 codes (utils.jl:148-161): per sub-space the codeword index with the smallest
 // sum_t (cb[t] - r[t])^2, first minimum on ties (keys f32 bits << 32 | index).  One workgroup per point; out: n x m uint16_t indices.

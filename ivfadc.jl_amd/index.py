@@ -424,7 +424,8 @@ class IVFADCIndex:
         form (two pool entries per lane) instead of the four-wave kernel -- K <= 64 and K > 128 run what 6 / 7 run.  6 / 7 (8 / 9 at K <= 64)
         also take the kernel for m = 16 at d = 128 or 64 (PQ16; K <= 64), which no other mode does.  Mode 0 takes that
         kernel unasked for d = 128 without a list partition on lists of 8192 points or more; get_stats()["last_striped"] is 2 / 3 when
-        its four- / eight-query form ran, 4 / 5 for the wide-pool form.
+        its four- / eight-query form ran, 4 / 5 for the wide-pool form.  10: as 0, and an index with UInt16 codes runs 64 < K on its scan
+        kernel's LDS-selector form (K <= 1984 at small m x dsub; get_stats()["last_qg"] >= 1) instead of the generic path (last_qg == -2).
         Results are the same bytes in every mode."""
         nat.check(nat.lib().ivfadc_set_table_mode(self._h, int(mode)))
 

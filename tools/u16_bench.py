@@ -6,7 +6,11 @@ are random (the scan's cost does not depend on training); queries are data point
 device-resident batch, scan time from events, pruned fraction, table-build element operations (3 d ksub per (query, probe)) per
 second of scan time against the 78.6 T/s no-FMA vector-ALU peak, and codebook bytes read per table.
 
-    python tools/u16_bench.py [--reps 10] [--only sift1m_k1024,...]
+    python tools/u16_bench.py [--reps 10] [--only sift1m_k1024,...] [--K 100] [--table-mode 10] [--windows 5]
+
+--K overrides the shapes' K; --table-mode is passed to set_table_mode (10: K > 64 on the scan kernel's LDS-selector form instead of the
+generic path, whose scan_ms covers its own kernels).  --windows N times N windows of --reps searches and reports the median window and
+the spread (max - min) next to the mean; get_stats()["last_qg"] (pairs_per_item; -2 = generic path) tells which path ran.
 """
 import argparse
 import json
@@ -45,6 +49,9 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=10)
     ap.add_argument("--only", default="", help="comma-separated shape names (default: all)")
+    ap.add_argument("--K", type=int, default=0, help="K for every shape (default: the shape's own, 10)")
+    ap.add_argument("--table-mode", type=int, default=0, help="ivfadc_set_table_mode (10: UInt16 scan kernel also for 64 < K)")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --reps searches each (median and spread are reported)")
     args = ap.parse_args()
     only = set(filter(None, args.only.split(",")))
     import torch
@@ -52,7 +59,10 @@ def main():
     for name, d, m, ksub, n, kc, nq, K, w in SHAPES:
         if only and name not in only:
             continue
+        K = args.K or K
         g, cent, lst = build(d, m, ksub, n, kc)
+        if args.table_mode:
+            g.set_table_mode(args.table_mode)
         rng = np.random.default_rng(1)
         q = (cent[rng.integers(0, kc, nq)] + rng.normal(0, 0.05, (nq, d))).astype(np.float32)
         dq = torch.from_numpy(q).cuda()
@@ -64,11 +74,14 @@ def main():
         for _ in range(3):
             run()
         g.sync()
-        t0 = time.perf_counter()
-        for _ in range(args.reps):
-            run()
-        g.sync()
-        dt = (time.perf_counter() - t0) / args.reps
+        wins = []
+        for _ in range(max(1, args.windows)):
+            t0 = time.perf_counter()
+            for _ in range(args.reps):
+                run()
+            g.sync()
+            wins.append((time.perf_counter() - t0) / args.reps)
+        dt = sum(wins) / len(wins)
         g.set_profiling(1)
         g.reset_stats()
         for _ in range(args.reps):
@@ -82,7 +95,10 @@ def main():
         ops = 3.0 * d * ksub * tables * (1.0 - pruned)   # (an item that prunes builds no table: approximate by the point fraction)
         out["shapes"][name] = {
             "d": d, "m": m, "k": ksub, "n": n, "kc": kc, "nq": nq, "K": K, "w": w,
-            "qps": nq / dt, "ms_per_batch": dt * 1e3, "scan_ms": scan_s * 1e3, "pruned_fraction": pruned,
+            "table_mode": args.table_mode,
+            "qps": nq / dt, "ms_per_batch": dt * 1e3, "ms_per_batch_median": float(np.median(wins)) * 1e3,
+            "ms_per_batch_spread": (max(wins) - min(wins)) * 1e3, "windows": len(wins), "reps": args.reps,
+            "scan_ms": scan_s * 1e3, "pruned_fraction": pruned,
             "table_ops_per_s": ops / scan_s if scan_s > 0 else None,
             "table_ops_fraction_of_78.6T": (ops / scan_s) / 78.6e12 if scan_s > 0 else None,
             "codebook_bytes_per_table": 4 * d * ksub, "pairs_per_item": st["last_qg"], "chunk": st["last_chunk"],
