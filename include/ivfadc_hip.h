@@ -215,6 +215,50 @@ int ivfadc_clone_view(ivfadc_t *h, ivfadc_t **out_view);
 int ivfadc_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w,
                          uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
 
+/* The seam of the reference's knn_search.  index.jl:204-258 calls coarse_search(cq, point, w) once (index.jl:219) and everything after it
+ * -- residuals, ADC tables, the list scan seeded with dc, top-K (index.jl:220-257) -- reads only the two vectors it returns;
+ * AbstractCoarseQuantizer (coarsequantizers.jl:6) is the reference's one plug-in interface.  The two halves are exported separately, so a
+ * caller can take the coarse result out, or put ANY coarse result in: the reference's HNSW quantizer (coarsequantizers.jl:73-76, run on
+ * the CPU by the Julia shim), a learned router, a cached assignment, one coarse search shared between several indexes.
+ *
+ * Replaces: coarse_search(cq, point, w) (coarsequantizers.jl:33-37, NaiveQuantizer) for a batch.  Row q of out_lists / out_dists (w slots
+ * per query) holds the w closest cells of query q: 0-based, ascending distance, ties to the lower cell (sortperm is stable), in rank
+ * order.  1 <= w <= kc: w < 1 -> IVFADC_ERR_ASSERT (the text of index.jl:211), w > kc -> IVFADC_ERR_INVALID (sortperm(...)[1:w] would
+ * throw).  The bytes are the same in every coarse mode (ivfadc_set_coarse_mode) and are the probes a plain search of the same queries
+ * visits.  Batches are cut into sub-batches under ivfadc_set_workspace_limit; a pending hint (ivfadc_set_next_queries) is dropped as by
+ * any search.  The _device form takes device pointers and is asynchronous on the handle's stream: the selection kernel writes straight
+ * into the caller's rows.                                                                                                      */
+int ivfadc_coarse_search(ivfadc_t *h, int64_t nq, const float *queries, int w, int32_t *out_lists, float *out_dists);
+int ivfadc_coarse_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int w, int32_t *d_lists, float *d_dists);
+
+/* Replaces: index.jl:220-257 given the output of ANY coarse_search (coarsequantizers.jl:33-37 or :73-76).  Row q of lists /
+ * coarse_dists = the w probes of query q in VISIT (rank) order; the outputs are laid out as ivfadc_search's.
+ *   visit order   the supplied rank, NOT the order of the supplied distances: a key is (f32 bits of d) << 32 | (base of rank j + position
+ *                 in the list), base = exclusive prefix sum of the list lengths over the supplied ranks (index.jl:228-255 visits the
+ *                 clusters in the order coarse_search returned them)
+ *   distance seed d starts at the supplied coarse_dists[q][j], not at a recomputed distance (index.jl:229,242)
+ *   residual      q - centroid[lists[q][j]] (coarsequantizers.jl:40-45, 79-89)
+ * Results do not depend on whether the supplied distances ascend: exact pruning judges every list against the bound by itself (a plain
+ * search may stop at the first list above the bound because ITS probes ascend; here that list alone is skipped).
+ * Fed with the output of ivfadc_coarse_search, the results are the bytes of ivfadc_search.
+ * Preconditions on the probes: list numbers in [0, kc); the lists of one query pairwise distinct; distances finite and >= +0 (no -0:
+ * pruning and selection compare float bits as unsigned).  1 <= w <= kc (w > kc -> IVFADC_ERR_INVALID; K < 1, w < 1 -> IVFADC_ERR_ASSERT
+ * as ivfadc_search).
+ *   ivfadc_search_preassigned         host pointers, blocking.  Validates every precondition on the host BEFORE any launch and returns
+ *                                     IVFADC_ERR_INVALID naming the query, the rank and the reason.
+ *   ivfadc_search_device_preassigned  device pointers, asynchronous on the handle's stream.  Cannot validate without a synchronisation:
+ *                                     the preconditions are the caller's.  Its ingest kernel clamps every list number into [0, kc) and
+ *                                     reads a distance outside [+0, FLT_MAX] as +0, so a violated precondition cannot index outside
+ *                                     the index; the results of that query are then unspecified.
+ * Both serve UInt8 and UInt16 handles, views, :opq-loaded handles and device-synthesised lists, every K and w <= kc (the plans of a plain
+ * search minus its coarse stage: no latency path, no fused top-w, no riders; a pending hint is dropped as by any search), and
+ * sub-batch under ivfadc_set_workspace_limit.  A handle with a list partition set (ivfadc_set_list_partition, nparts > 1) ->
+ * IVFADC_ERR_STATE.                                                                                                            */
+int ivfadc_search_preassigned(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, const int32_t *lists, const float *coarse_dists,
+                              uint32_t *out_ids, float *out_dists, int32_t *out_counts);
+int ivfadc_search_device_preassigned(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w, const int32_t *d_lists,
+                                     const float *d_coarse_dists, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
+
 /* Replaces: a loop of knn_search(ivfadc, points, k; w) calls over consecutive batches (index.jl:261-273 once per batch) -- ONE call for
  * the whole run.  batch_nq[b] queries per batch; queries is d x sum(batch_nq), the batches back to back; outputs are laid out like
  * ivfadc_search's for the concatenated queries (K slots per query).  Every batch's results are exactly what ivfadc_search returns

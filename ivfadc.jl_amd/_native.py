@@ -99,6 +99,12 @@ def lib():
     L.ivfadc_get_dims.argtypes = [vp, i32p, i32p, i32p, i32p]
     L.ivfadc_get_quantizers.argtypes = [vp, fp, fp, u8p]
     L.ivfadc_search_device.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp]
+    L.ivfadc_coarse_search.argtypes = [vp, C.c_int64, fp, C.c_int, i32p, fp]
+    L.ivfadc_coarse_search_device.argtypes = [vp, C.c_int64, vp, C.c_int, vp, vp]
+    L.ivfadc_search_preassigned.argtypes = [vp, C.c_int64, fp, C.c_int, C.c_int, i32p, fp, u32p, fp, i32p]
+    L.ivfadc_search_device_preassigned.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, vp, vp]
+    for name in ("coarse_search", "coarse_search_device", "search_preassigned", "search_device_preassigned"):
+        getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_sync.argtypes = [vp]
     L.ivfadc_set_stream.argtypes = [vp, vp]
     L.ivfadc_ntotal.argtypes = [vp, i64p, i64p]

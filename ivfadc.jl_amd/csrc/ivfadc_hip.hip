@@ -424,6 +424,7 @@ struct ivfadc_index {
     uint64_t hint_token = 0, pf_token = 0, cur_token = 0, own_token = 0;   // own_token: numbering of ivfadc_search_batches
     hipEvent_t hint_ev = nullptr;   // ivfadc_search_batches: the hinted rows are on the device once this event has fired (null: they are)
     DevBuf cdist2;
+    DevBuf pre_list, pre_dc;   // ivfadc_search_preassigned (host pointers): the caller's probes on the device
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
@@ -789,7 +790,8 @@ wg8_fn_t pick_wg8_wide(bool q8, int dsub)
 bool w8_default(const ivfadc_index *h) { return h->m == 8 && h->dsub == 16 && h->part_n <= 1; }
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
-constexpr size_t MISC_BYTES = 4096 + 256 + 512;
+constexpr size_t MISC_BYTES = 4096 + 256 + 512 + 4096;
+constexpr size_t MISC_SINK = 4096 + 256 + 512;   // 64 counter lines nobody reads: where a coarse search alone (ivfadc_coarse_search) sends the B_alg counts of its top-w kernel
 
 struct Plan {
     bool coarse_mfma;   // coarse scores on the matrix cores + certified exact refine (w <= 48)
@@ -854,7 +856,7 @@ int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its s
 // U = UInt16 (u16scan.hip.h): always list-major; K <= 64 on register selectors, 64 < K on LDS selectors where table mode 10 asks for
 // them (search_dev sends larger K to the generic path otherwise).  Pairs per work item from the expected probes per list (a codeword
 // read serves every pair of the item), halved for K > 64 until the selector buffers fit; chunks of whole passes, about two items per CU.
-int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
+int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)
 {
     pl.fits = true;
     pl.lanes = false;
@@ -864,8 +866,8 @@ int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
     pl.capw = pl.small_w ? 64 : std::max(128, pow2ceil(w + 64));
     pl.query_major = false;
     pl.fuse_topw = pl.lb = pl.nf = pl.wg8 = pl.wg8q8 = pl.wg8wide = false;
-    pl.coarse_mfma = h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
-    pl.twolevel = h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
+    pl.coarse_mfma = !pre && h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
+    pl.twolevel = !pre && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
                   (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
     if (pl.twolevel) pl.coarse_mfma = false;
     const double avg_len = (double)h->n / std::max(1, h->kc);
@@ -893,7 +895,7 @@ int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
     return IVFADC_OK;
 }
 
-int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
+int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)   // pre: the probes are the caller's (PreProbes): no coarse stage of any kind
 {
     pl.fits = true;
     pl.lanes = false;
@@ -939,13 +941,13 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl)
     pl.nf = false;
     // The filter pays when the coarse search is large: below ~2k centroids the extra selection + refine work in the
     // scan prologue costs more than the VALU kernel it replaces (SIFT1M-shape: 92 -> 121 us per batch).
-    pl.coarse_mfma = h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
-    pl.twolevel = h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
+    pl.coarse_mfma = !pre && h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
+    pl.twolevel = !pre && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
                   (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);   // (its four waves keep their queries in LDS)
     if (pl.twolevel) pl.coarse_mfma = false;
     if (pl.query_major) {
         // large kc: the selection is a 4*kc-byte stream per query, better done by the lean stand-alone kernel
-        pl.fuse_topw = pl.small_w && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel;
+        pl.fuse_topw = pl.small_w && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel && !pre;
         // Several batches in flight on this replica (the index has views, or this IS a view: ivfadc_search_batches' second lane, a serving
         // loop's lanes): what bounds the chip then is register-file time, not one launch's latency -- and the fused selection holds a scan
         // workgroup's four waves and 126 VGPRs each for the 10 k cycles (28 % of its life on the SIFT1M shape, by phase stamps) in which
@@ -1326,8 +1328,10 @@ int run_twolevel(ivfadc_index *h, const float *d_q, int64_t nb, int w, int *d_pr
 }
 
 int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids,
-                    float *d_dists, int32_t *d_counts, bool single)   // single: the call's whole batch (hints and prefetched rows apply)
+                    float *d_dists, int32_t *d_counts, bool single,   // single: the call's whole batch (hints and prefetched rows apply)
+                    const int *pre_list = nullptr, const float *pre_dc = nullptr)   // the caller's probes of these nb queries (ivfadc_search_preassigned)
 {
+    const bool pre = pre_list != nullptr;
     const int kc = h->kc;
     const size_t np = (size_t)nb * w;
     TRY(ensure_common_ws(h));
@@ -1343,12 +1347,21 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
     // one wave per query leaves the chip empty on small batches: the stand-alone top-w uses a workgroup per query there
     const bool wpq4 = !pl.lanes && nb * 1 < (int64_t)8 * h->num_cu * 4 && h->kc >= 512 && !(pl.lb && !pl.fuse_topw);
     // the rows of these very queries may stand already: written by the previous search's launch behind a hint (ivfadc_set_next_queries)
-    const bool have_rows = single && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
+    const bool have_rows = single && !pre && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
     h->avail_q = nullptr;
     h->stats.last_rider = 0;
     h->stats.coarse_prefetched = have_rows ? 1 : 0;
     h->stats.last_twolevel = pl.twolevel ? 1 : 0;
-    if (pl.twolevel) {
+    if (pre) {
+        // index.jl:220-257 given the output of any coarse_search: the coarse stage and the top-w selection are this one launch
+        u32 *lc = (pl.query_major || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>();
+        hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, pre_list, pre_dc, (int)nb, kc, w,
+                           h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, (u32 *)nullptr,
+                           d_scanned);
+        HIP_TRY(hipGetLastError());
+        h->tmin_tiles = 0;
+        h->last_listed = false;
+    } else if (pl.twolevel) {
         u32 *lc = (pl.query_major || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>();
         TRY(run_twolevel(h, d_q, nb, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, d_scanned));
         h->tmin_tiles = 0;
@@ -1362,11 +1375,11 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
                        !pl.fuse_topw && !wpq4, w));
     }
     // riders: the hinted batch will take the exact small-problem coarse kernel whatever its K and w (no matrix-core filter at this kc)
-    const bool ride = single && !h->tl_use && h->hint_q != nullptr && h->hint_nq > 0 && pl.query_major && !pl.lb && pl.small_k && (h->d & 7) == 0 &&
+    const bool ride = single && !pre && !h->tl_use && h->hint_q != nullptr && h->hint_nq > 0 && pl.query_major && !pl.lb && pl.small_k && (h->d & 7) == 0 &&
                       (!h->allow_mfma || kc < h->mfma_min_kc) && (h->hint_nq + 4 * RIDER_QW - 1) / (4 * RIDER_QW) <= 65535 &&
                       (size_t)h->hint_nq * kc * 4 <= h->ws_budget / 4;
 
-    if (!pl.fuse_topw && !pl.twolevel) {
+    if (!pl.fuse_topw && !pl.twolevel && !pre) {
         u32 *lc = (pl.query_major || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>();   // probe histogram: grouped list-major only
         const size_t lds = (size_t)4 * pl.capw * 8;
         void (*fn)(const float *, int, int, int, int, const u32 *, int *, float *, u32 *, u32 *, u64 *, const RefineArgs, int, int);
@@ -1405,7 +1418,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         a.scanned_points = d_scanned;
         a.approx = pl.coarse_mfma ? 1 : 0;
         a.rf = refine_args(h, d_q);
-        a.prune = h->allow_prune ? 1 : 0;
+        a.prune = h->allow_prune ? (pre ? 2 : 1) : 0;   // 2: ranks in the caller's order -- a list above the bound is skipped, the query goes on
         a.lb.cb_split = h->lb_split.as<uint4>();
         a.lb.cb_n2 = h->lb_n2.as<float>();
         a.lb.cb_lab = h->lb_lab.as<float>();
@@ -1670,7 +1683,32 @@ int gen_sort(ivfadc_index *h, const u64 *in, u64 *out, int64_t total, int segmen
     return IVFADC_OK;
 }
 
-int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts)
+// stage A of the generic path: coarse distances (exact VALU kernel), rows -> keys -> sorted rows -> the w probes of na queries
+// (na x kc < 2^31 keys; h->gen_tot holds na words)
+int gen_stage_a(ivfadc_index *h, const float *qa, int64_t na, int w, int *d_pl, float *d_pd, u32 *d_pb, u64 *d_scanned)
+{
+    const int kc = h->kc;
+    TRY(run_coarse(h, qa, na, false));
+    const int64_t rk = na * kc;
+    TRY(h->gen_a.ensure((size_t)rk * 8));
+    TRY(h->gen_b.ensure((size_t)rk * 8));
+    hipLaunchKernelGGL(gen_row_keys_kernel, dim3((unsigned)std::min<int64_t>(8192, (rk + 255) / 256)), dim3(256), 0, h->stream,
+                       h->cdist.as<float>(), rk, kc, h->gen_a.as<u64>());
+    HIP_TRY(hipGetLastError());
+    std::vector<u32> off((size_t)na + 1);
+    for (int64_t q = 0; q <= na; ++q) off[q] = (u32)(q * kc);
+    TRY(h->gen_off.ensure(((size_t)na + 1) * 4));
+    TRY(h2d_copy(h->gen_off.p, off.data(), ((size_t)na + 1) * 4, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // `off` goes away
+    TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), rk, (int)na, h->gen_off.as<u32>()));
+    hipLaunchKernelGGL(gen_probes_kernel, dim3((unsigned)na), dim3(256), 0, h->stream, h->gen_b.as<u64>(), kc, w, h->list_len.as<u32>(),
+                       d_pl, d_pd, d_pb, h->gen_tot.as<u32>(), d_scanned);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
+                   const int *pre_list = nullptr, const float *pre_dc = nullptr)   // the caller's probes (ivfadc_search_preassigned): stage A is their ingest
 {
     const int kc = h->kc;
     const size_t lds = (align_up((size_t)h->d, 4) + (h->u16 ? (size_t)GEN16_TILE : (size_t)h->m * 256)) * 4;
@@ -1690,28 +1728,19 @@ int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, 
     for (int64_t a0 = 0; a0 < nq; a0 += nba) {
         const int64_t na = std::min(nba, nq - a0);
         const float *qa = d_q + (size_t)a0 * h->d;
-        // coarse distances (exact VALU kernel), rows -> keys -> sorted rows -> probes
-        TRY(run_coarse(h, qa, na, false));
-        const int64_t rk = na * kc;
-        TRY(h->gen_a.ensure((size_t)rk * 8));
-        TRY(h->gen_b.ensure((size_t)rk * 8));
-        hipLaunchKernelGGL(gen_row_keys_kernel, dim3((unsigned)std::min<int64_t>(8192, (rk + 255) / 256)), dim3(256), 0, h->stream,
-                           h->cdist.as<float>(), rk, kc, h->gen_a.as<u64>());
-        HIP_TRY(hipGetLastError());
-        off.resize((size_t)na + 1);
-        for (int64_t q = 0; q <= na; ++q) off[q] = (u32)(q * kc);
-        TRY(h->gen_off.ensure(((size_t)na + 1) * 4));
-        TRY(h2d_copy(h->gen_off.p, off.data(), ((size_t)na + 1) * 4, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));   // `off` is reused below
-        TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), rk, (int)na, h->gen_off.as<u32>()));
         const size_t np = (size_t)na * w;
         TRY(h->probe_list.ensure(np * 4));
         TRY(h->probe_dc.ensure(np * 4));
         TRY(h->probe_base.ensure(np * 4));
         TRY(h->gen_tot.ensure((size_t)na * 4));
-        hipLaunchKernelGGL(gen_probes_kernel, dim3((unsigned)na), dim3(256), 0, h->stream, h->gen_b.as<u64>(), kc, w, h->list_len.as<u32>(),
-                           h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), h->gen_tot.as<u32>(), d_scanned);
-        HIP_TRY(hipGetLastError());
+        if (pre_list) {
+            hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, h->stream, pre_list + (size_t)a0 * w,
+                               pre_dc + (size_t)a0 * w, (int)na, kc, w, h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(),
+                               h->probe_base.as<u32>(), (u32 *)nullptr, h->gen_tot.as<u32>(), d_scanned);
+            HIP_TRY(hipGetLastError());
+        } else {
+            TRY(gen_stage_a(h, qa, na, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), d_scanned));
+        }
         tot.resize((size_t)na);
         TRY(d2h_copy(tot.data(), h->gen_tot.p, (size_t)na * 4, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2017,7 +2046,13 @@ int build_twolevel(ivfadc_index *h)
     return IVFADC_OK;
 }
 
-int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts)
+// Probes supplied by the caller (ivfadc_search_preassigned, device pointers): row q = the w probes of query q in visit order.  With
+// them a search has no coarse stage of its own -- no latency path, no fused top-w, no matrix-core filter, no two-level search, no
+// riders -- and everything behind the probe arrays runs as it does for a plain search.
+struct PreProbes { const int *lists; const float *dcs; };
+
+int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
+               const PreProbes *pre = nullptr)
 {
     HintScope hint_scope{h};
     // Rows the previous search's riders left serve THIS search or none, whatever path it takes (small-batch, generic, sub-batched, failing):
@@ -2034,26 +2069,99 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
     if (h->dirty) TRY(upload_lists(h));
     if (nq == 0) return IVFADC_OK;
     // the grouping of a large quantizer is built on its first search (automatic mode), or on request (ivfadc_set_coarse_mode(h, 6))
-    if (!h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
+    if (!pre && !h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
     const bool parted = h->part_n > 1;
-    if (!parted && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
+    const int *prl = pre ? pre->lists : (const int *)nullptr;
+    const float *prd = pre ? pre->dcs : (const float *)nullptr;
+    if (!parted && !pre && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
     if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64 && !h->u16_wide)) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
-        return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
+        return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, prl, prd);
     }
     Plan pl;
     TRY(fb_poll(h));
-    TRY(h->u16 ? make_plan_u16(h, nq, K, w, pl) : make_plan(h, nq, K, w, pl));
+    TRY(h->u16 ? make_plan_u16(h, nq, K, w, pl, pre != nullptr) : make_plan(h, nq, K, w, pl, pre != nullptr));
     if (!pl.fits) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the selection kernels' LDS need exceeds a CU for this m and K");
-        return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts);   // "any K and w" holds for every m
+        return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, prl, prd);   // "any K and w" holds for every m
     }
     if (parted && pl.nb < nq)
         return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the batch must fit one sub-batch (raise ivfadc_set_workspace_limit or split the batch)");
     for (int64_t b0 = 0; b0 < nq; b0 += pl.nb) {
         const int64_t nb = std::min(pl.nb, nq - b0);
         TRY(search_subbatch(h, pl, nb, d_q + (size_t)b0 * h->d, K, w, d_ids + (size_t)b0 * K, d_dists + (size_t)b0 * K,
-                            d_counts + b0, pl.nb >= nq));
+                            d_counts + b0, pl.nb >= nq, pre ? prl + (size_t)b0 * w : prl, pre ? prd + (size_t)b0 * w : prd));
+    }
+    return IVFADC_OK;
+}
+
+// coarse_search(cq, point, w) (coarsequantizers.jl:33-37) for a batch, into the caller's device rows: the coarse stage a search plans --
+// exact VALU kernel, matrix-core filter + certified refine, or the certified two-level search; the same bytes from each -- with the
+// stand-alone top-w kernel (or the two-level kernel) writing lists and distances straight into d_lists / d_dists.  The visit-order
+// bases go to the handle's own probe_base, the B_alg counts to the sink: nothing is scanned.  w > IVFADC_MAX_W: the generic path's sort.
+int coarse_dev(ivfadc_index *h, int64_t nq, const float *d_q, int w, int32_t *d_lists, float *d_dists)
+{
+    HintScope hint_scope{h};
+    h->pf_q = nullptr; h->pf_nq = 0; h->pf_token = 0; h->cur_token = 0;
+    h->stats.coarse_prefetched = 0;
+    h->stats.last_rider = 0;
+    h->partial_nq = -1;   // (probe_base is rewritten)
+    TRY(set_device(h));
+    if (h->dirty) TRY(upload_lists(h));
+    if (nq == 0) return IVFADC_OK;
+    if (!h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
+    TRY(ensure_common_ws(h));
+    const int kc = h->kc;
+    u64 *d_sink = (u64 *)((char *)h->misc.p + MISC_SINK);
+    const bool generic = w > IVFADC_MAX_W;
+    const bool small_w = w <= 64;
+    const int capw = small_w ? 64 : std::max(128, pow2ceil(w + 64));
+    const bool twolevel = !generic && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 &&
+                          (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
+    const bool mfma = !generic && !twolevel && h->allow_mfma && w <= 48 && kc >= h->mfma_min_kc && (h->d & 3) == 0;
+    // sub-batches: the distance rows (generic: + two key rows) stay inside the workspace budget
+    const size_t per_q = (twolevel ? (size_t)h->tl_G : (size_t)kc) * (generic ? 20 : 4) + (size_t)w * 4 + 64;
+    int64_t nb = (int64_t)std::max<size_t>(generic ? 1 : 64, h->ws_budget / per_q);
+    nb = std::min<int64_t>(nb, (int64_t)1 << 22);
+    if (twolevel) nb = std::min<int64_t>(nb, std::max<int64_t>(1, ((int64_t)1 << 30) / std::max(1, h->tl_G)));
+    if (generic) nb = std::min<int64_t>(nb, std::min<int64_t>(65535, ((int64_t)1 << 31) / std::max(1, kc)));
+    nb = std::max<int64_t>(1, std::min<int64_t>(nb, nq));
+    TRY(h->probe_base.ensure((size_t)nb * w * 4));
+    h->stats.last_twolevel = twolevel ? 1 : 0;
+    h->stats.coarse_mfma = mfma ? 1 : 0;
+    for (int64_t b0 = 0; b0 < nq; b0 += nb) {
+        const int64_t n = std::min(nb, nq - b0);
+        const float *q = d_q + (size_t)b0 * h->d;
+        int *ol = (int *)d_lists + (size_t)b0 * w;
+        float *od = d_dists + (size_t)b0 * w;
+        if (generic) {
+            TRY(h->gen_tot.ensure((size_t)n * 4));
+            TRY(gen_stage_a(h, q, n, w, ol, od, h->probe_base.as<u32>(), d_sink));
+            continue;
+        }
+        if (twolevel) {
+            TRY(run_twolevel(h, q, n, w, ol, od, h->probe_base.as<u32>(), nullptr, d_sink));
+            h->tmin_tiles = 0;
+            h->last_listed = false;
+            continue;
+        }
+        const bool wpq4 = n < (int64_t)8 * h->num_cu * 4 && kc >= 512;   // (search_subbatch: a workgroup per query on small batches)
+        TRY(run_coarse(h, q, n, mfma, mfma && !wpq4, !wpq4, w));
+        const size_t lds = (size_t)4 * capw * 8;
+        void (*fn)(const float *, int, int, int, int, const u32 *, int *, float *, u32 *, u32 *, u64 *, const RefineArgs, int, int);
+        if (mfma)
+            fn = wpq4 ? topw_select_kernel<true, 4, true> : topw_select_kernel<true, 1, true>;
+        else if (small_w)
+            fn = wpq4 ? topw_select_kernel<true, 4, false> : topw_select_kernel<true, 1, false>;
+        else
+            fn = wpq4 ? topw_select_kernel<false, 4, false> : topw_select_kernel<false, 1, false>;
+        const unsigned grid = wpq4 ? (unsigned)n : (unsigned)((n + 3) / 4);
+        if (lds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)fn, lds, occ_unused, false)); }
+        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, h->stream, h->cdist.as<float>(), (int)n, kc, w, capw, h->list_len.as<u32>(), ol, od,
+                           h->probe_base.as<u32>(), (u32 *)nullptr, d_sink, refine_args(h, q), 1, 0);
+        HIP_TRY(hipGetLastError());
+        h->stats.coarse_f16 = (mfma && h->last_coarse_f16) ? 1 : 0;
+        h->stats.coarse_listed = h->last_listed ? 1 : 0;
     }
     return IVFADC_OK;
 }
@@ -2646,7 +2754,7 @@ void ivfadc_destroy(ivfadc_t *h)
     if (h->comm || h->comm_stream) (void)ivfadc_comm_destroy(h);
     for (auto &ep : h->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (auto &ep : h->free_ev) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-    DevBuf *bufs[] = {&h->lb_f16, &h->lb_isc, &h->cent_f16, &h->q_f16, &h->q_flags, &h->tl_centres, &h->tl_off, &h->tl_rad, &h->tl_cent, &h->tl_slot, &h->tl_gdist, &h->cdist2, &h->cent_t, &h->sq_keys, &h->sq_cnt, &h->sq_arrive, &h->lb_split, &h->lb_n2, &h->lb_lab, &h->lb_maxn, &h->nf_n2, &h->nf_lab, &h->wg8_tabs, &h->wg8_items, &h->centroids, &h->codebooks, &h->codebooks_t, &h->codebooks_p, &h->labels, &h->cnorm, &h->tmin, &h->tlist, &h->cent_hi, &h->cent_lo, &h->q_hi, &h->q_lo, &h->gen_a, &h->gen_b, &h->gen_tmp, &h->gen_off, &h->gen_tot, &h->list_pos, &h->list_len, &h->list_codeoff, &h->codes, &h->ids, &h->app_stage, &h->q_stage,
+    DevBuf *bufs[] = {&h->lb_f16, &h->lb_isc, &h->cent_f16, &h->q_f16, &h->q_flags, &h->tl_centres, &h->tl_off, &h->tl_rad, &h->tl_cent, &h->tl_slot, &h->tl_gdist, &h->cdist2, &h->pre_list, &h->pre_dc, &h->cent_t, &h->sq_keys, &h->sq_cnt, &h->sq_arrive, &h->lb_split, &h->lb_n2, &h->lb_lab, &h->lb_maxn, &h->nf_n2, &h->nf_lab, &h->wg8_tabs, &h->wg8_items, &h->centroids, &h->codebooks, &h->codebooks_t, &h->codebooks_p, &h->labels, &h->cnorm, &h->tmin, &h->tlist, &h->cent_hi, &h->cent_lo, &h->q_hi, &h->q_lo, &h->gen_a, &h->gen_b, &h->gen_tmp, &h->gen_off, &h->gen_tot, &h->list_pos, &h->list_len, &h->list_codeoff, &h->codes, &h->ids, &h->app_stage, &h->q_stage,
                       &h->cdist, &h->probe_list, &h->probe_dc, &h->probe_base, &h->list_cnt, &h->bucket_off, &h->wi_off, &h->cursor,
                       &h->bucket_items, &h->misc, &h->qthr, &h->part_keys, &h->part_cnt, &h->out_ids, &h->out_dists, &h->out_counts,
                       &h->assign, &h->enc_codes, &h->pts_stage, &h->dbg};
@@ -2730,7 +2838,7 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
                         &v->lb_maxn, &v->nf_n2, &v->nf_lab, &v->cent_t, &v->cent_hi, &v->cent_lo, &v->list_pos, &v->list_len, &v->list_codeoff,
                         &v->codes, &v->ids};
     for (DevBuf *b : shared) b->alias();
-    DevBuf *scratch[] = {&v->wg8_tabs, &v->wg8_items, &v->q_f16, &v->q_flags, &v->tl_gdist, &v->cdist2, &v->sq_keys, &v->sq_cnt, &v->sq_arrive, &v->tmin, &v->tlist, &v->q_hi, &v->q_lo, &v->gen_a, &v->gen_b, &v->gen_tmp,
+    DevBuf *scratch[] = {&v->wg8_tabs, &v->wg8_items, &v->q_f16, &v->q_flags, &v->tl_gdist, &v->cdist2, &v->pre_list, &v->pre_dc, &v->sq_keys, &v->sq_cnt, &v->sq_arrive, &v->tmin, &v->tlist, &v->q_hi, &v->q_lo, &v->gen_a, &v->gen_b, &v->gen_tmp,
                          &v->gen_off, &v->gen_tot, &v->app_stage, &v->q_stage, &v->cdist, &v->probe_list, &v->probe_dc, &v->probe_base, &v->list_cnt,
                          &v->bucket_off, &v->wi_off, &v->cursor, &v->bucket_items, &v->misc, &v->qthr, &v->part_keys, &v->part_cnt, &v->out_ids,
                          &v->out_dists, &v->out_counts, &v->assign, &v->enc_codes, &v->pts_stage, &v->dbg};
@@ -3323,7 +3431,9 @@ static int ingest_rows(ivfadc_index *h, hipStream_t s, const void *src, void *ds
 }
 
 // host-pointer search in two halves so several handles (devices) can be in flight at once (ivfadc_mg_search)
-static int search_enqueue(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+// pre_lists / pre_dcs (host, validated by the caller): the probes of ivfadc_search_preassigned
+static int search_enqueue(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists, int32_t *out_counts,
+                          const int32_t *pre_lists = nullptr, const float *pre_dcs = nullptr)
 try {
     TRY(set_device(h));
     h->dev_entry = false;
@@ -3345,7 +3455,7 @@ try {
     if (h->dirty) TRY(upload_lists(h));
     const float *d_q = src;
     static const bool no_zero_copy = getenv("IVFADC_NO_ZERO_COPY") != nullptr;
-    if (!no_zero_copy && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, K, w)) {
+    if (!no_zero_copy && !pre_lists && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, K, w)) {
         // the latency path: a handful of rows, read in place by the two launches (a few KB over PCIe; no ingest step in the chain)
         h->hstats.zero_copy++;
     } else {
@@ -3366,6 +3476,15 @@ try {
         od = (float *)(po + idb);
         oc = (int32_t *)(po + 2 * idb);
     }
+    if (pre_lists) {
+        const size_t pb = (size_t)nq * w * 4;
+        TRY(h->pre_list.ensure(pb));
+        TRY(h->pre_dc.ensure(pb));
+        TRY(h2d_copy(h->pre_list.p, pre_lists, pb, h->stream));
+        TRY(h2d_copy(h->pre_dc.p, pre_dcs, pb, h->stream));
+        const PreProbes pre{h->pre_list.as<int>(), h->pre_dc.as<float>()};
+        TRY(search_dev(h, nq, d_q, K, w, oi, od, oc, &pre));
+    } else
     TRY(search_dev(h, nq, d_q, K, w, oi, od, oc));
     h->hstats.stage_in_us += t1 - t0;
     h->hstats.enqueue_us += now_us() - t1;
@@ -3400,6 +3519,110 @@ try {
     const int rc = search_enqueue(h, nq, queries, K, w, out_ids, out_dists, out_counts);
     if (rc != IVFADC_OK) {
         // whatever was enqueued before the failure may still be writing the staging buffers (or the caller's arrays): it ends first
+        const std::string msg = g_err;
+        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+        return rc;
+    }
+    return search_finish(h, nq, K, out_ids, out_dists, out_counts);
+} IVF_CATCH
+
+// ---- the seam of the reference's knn_search (index.jl:204-258): coarse_search on one side, everything that reads its two vectors on
+// the other ("Caller-supplied probes") ----------------------------------------------------------------------------------
+static int check_coarse_args(ivfadc_index *h, int64_t nq, int w)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_view_current(h));
+    if (w < 1) return fail(IVFADC_ERR_ASSERT, "Number of clusters to search in must be w >= 1");
+    if (nq < 0) return fail(IVFADC_ERR_INVALID, "nq < 0");
+    if (w > h->kc) return fail(IVFADC_ERR_INVALID, "w = %d exceeds the %d cells of the coarse quantizer (sortperm(...)[1:w], coarsequantizers.jl:36)", w, h->kc);
+    if (!h->have_lists && !h->dirty) return fail(IVFADC_ERR_STATE, "no inverted lists set");
+    if ((int64_t)nq * w > ((int64_t)1 << 40)) return fail(IVFADC_ERR_INVALID, "nq x w = %lld probe slots", (long long)nq * w);
+    return IVFADC_OK;
+}
+
+int ivfadc_coarse_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int w, int32_t *d_lists, float *d_dists)
+try {
+    HandleLock lk_(h);
+    TRY(check_coarse_args(h, nq, w));
+    if (nq > 0 && (!d_queries || !d_lists || !d_dists)) return fail(IVFADC_ERR_INVALID, "null buffer");
+    return coarse_dev(h, nq, d_queries, w, d_lists, d_dists);
+} IVF_CATCH
+
+int ivfadc_coarse_search(ivfadc_t *h, int64_t nq, const float *queries, int w, int32_t *out_lists, float *out_dists)
+try {
+    HandleLock lk_(h);
+    TRY(check_coarse_args(h, nq, w));
+    if (nq == 0) return IVFADC_OK;
+    if (!queries || !out_lists || !out_dists) return fail(IVFADC_ERR_INVALID, "null buffer");
+    TRY(set_device(h));
+    const size_t qbytes = (size_t)nq * h->d * 4, pb = (size_t)nq * w * 4;
+    TRY(h->q_stage.ensure(qbytes));
+    TRY(h->pre_list.ensure(pb));
+    TRY(h->pre_dc.ensure(pb));
+    TRY(h2d_copy(h->q_stage.p, queries, qbytes, h->stream));
+    int rc = coarse_dev(h, nq, h->q_stage.as<float>(), w, h->pre_list.as<int32_t>(), h->pre_dc.as<float>());
+    if (rc == IVFADC_OK) rc = d2h_copy(out_lists, h->pre_list.p, pb, h->stream);
+    if (rc == IVFADC_OK) rc = d2h_copy(out_dists, h->pre_dc.p, pb, h->stream);
+    if (rc != IVFADC_OK) {   // whatever was enqueued before the failure ends first
+        const std::string msg = g_err;
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+    }
+    return rc;
+} IVF_CATCH
+
+// K, w and the handle's state, shared by the two preassigned entries (w is NOT clamped: the probes are nq x w as given)
+static int check_preassigned_args(ivfadc_index *h, int64_t nq, int K, int w)
+{
+    int wc = w;
+    TRY(check_search_args(h, nq, K, wc));
+    if (w > h->kc) return fail(IVFADC_ERR_INVALID, "w = %d exceeds the %d cells of the coarse quantizer: the probes of a query are distinct lists", w, h->kc);
+    if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "a list partition is set (ivfadc_set_list_partition): searches with supplied probes serve whole indexes only");
+    if ((int64_t)nq * w > ((int64_t)1 << 40)) return fail(IVFADC_ERR_INVALID, "nq x w = %lld probe slots", (long long)nq * w);
+    return IVFADC_OK;
+}
+
+int ivfadc_search_device_preassigned(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w, const int32_t *d_lists,
+                                     const float *d_coarse_dists, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
+try {
+    HandleLock lk_(h);
+    TRY(check_preassigned_args(h, nq, K, w));
+    if (nq > 0 && (!d_queries || !d_lists || !d_coarse_dists || !d_out_ids || !d_out_dists || !d_out_counts)) return fail(IVFADC_ERR_INVALID, "null buffer");
+    h->dev_entry = false;
+    const PreProbes pre{(const int *)d_lists, d_coarse_dists};
+    return search_dev(h, nq, d_queries, K, w, d_out_ids, d_out_dists, d_out_counts, &pre);
+} IVF_CATCH
+
+int ivfadc_search_preassigned(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, const int32_t *lists, const float *coarse_dists,
+                              uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+try {
+    HandleLock lk_(h);
+    TRY(check_preassigned_args(h, nq, K, w));
+    if (nq == 0) return IVFADC_OK;
+    if (!queries || !lists || !coarse_dists || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
+    // the preconditions of the probes, before any launch: lists in [0, kc), pairwise distinct within a query; distances finite and >= +0
+    // (exact pruning and the selectors compare float bits as unsigned)
+    {
+        const int kc = h->kc;
+        std::vector<int64_t> seen((size_t)kc, -1);
+        for (int64_t q = 0; q < nq; ++q)
+            for (int j = 0; j < w; ++j) {
+                const size_t o = (size_t)q * w + j;
+                const int32_t l = lists[o];
+                if (l < 0) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: negative list %d", (long long)q, j, l);
+                if (l >= kc) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: list %d out of range (kc = %d)", (long long)q, j, l, kc);
+                if (seen[l] == q) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: list %d repeated (the probes of a query are distinct lists)", (long long)q, j, l);
+                seen[l] = q;
+                uint32_t bits;
+                memcpy(&bits, &coarse_dists[o], 4);
+                if ((bits & 0x7FFFFFFFu) > 0x7F800000u) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: coarse distance is NaN", (long long)q, j);
+                if ((bits & 0x7FFFFFFFu) == 0x7F800000u) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: coarse distance is infinite", (long long)q, j);
+                if (bits & 0x80000000u) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: negative coarse distance (distances are >= +0)", (long long)q, j);
+            }
+    }
+    const int rc = search_enqueue(h, nq, queries, K, w, out_ids, out_dists, out_counts, lists, coarse_dists);
+    if (rc != IVFADC_OK) {
         const std::string msg = g_err;
         if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
         g_err = msg;

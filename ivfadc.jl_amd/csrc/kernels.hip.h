@@ -1705,6 +1705,60 @@ __global__ __launch_bounds__(256) void topw_select_kernel(const float *__restric
 }
 
 // ---------------------------------------------------------------------------------------
+// Probes supplied by the caller (ivfadc_search_preassigned: the output of ANY coarse_search,
+// coarsequantizers.jl:33-37 / :73-76): the tail of topw_select_kernel with the caller's rows
+// as its source.  One wave per query, 64 ranks per trip, any w.  Row q of src_list / src_dc
+// holds the w probes of query q in VISIT (rank) order; the visit-order base of rank j is the
+// exclusive prefix sum of the list lengths over the supplied ranks, whatever the distances
+// are.  A list number outside [0, kc) is clamped into it and a distance outside [+0, FLT_MAX]
+// (negative, -0, infinite, NaN: the keys compare float bits as unsigned) is read as +0, so a
+// violated precondition of the device-pointer entry cannot index outside the index or put a
+// key outside the selectors' domain; that query's results are then unspecified.
+// totals (generic path only, else null): points probed by each query.
+// ---------------------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void probe_ingest_kernel(const int *__restrict__ src_list, const float *__restrict__ src_dc, int nq, int kc,
+                                                           int w, const u32 *__restrict__ list_len, int *__restrict__ probe_list,
+                                                           float *__restrict__ probe_dc, u32 *__restrict__ probe_base,
+                                                           u32 *__restrict__ list_cnt, u32 *__restrict__ totals,
+                                                           u64 *__restrict__ scanned_points)
+{
+    const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
+    const int q = blockIdx.x * 4 + wv;
+    if (q >= nq) return;   // no workgroup barrier below
+    u32 running = 0;
+    for (int j0 = 0; j0 < w; j0 += 64) {
+        const int j = j0 + lane;
+        const size_t o = (size_t)q * w + j;
+        u32 len = 0;
+        int l = 0;
+        float dd = 0.0f;
+        if (j < w) {
+            l = min(max(src_list[o], 0), kc - 1);
+            dd = src_dc[o];
+            if (__float_as_uint(dd) > 0x7F7FFFFFu) dd = 0.0f;
+            len = list_len[l];
+        }
+        u32 incl = len;
+#pragma unroll
+        for (int off = 1; off < 64; off <<= 1) {
+            const u32 v = __shfl_up(incl, off);
+            if (lane >= off) incl += v;
+        }
+        if (j < w) {
+            probe_list[o] = l;
+            probe_dc[o] = dd;
+            probe_base[o] = running + incl - len;
+            if (list_cnt) atomicAdd(&list_cnt[l], 1u);
+        }
+        running += __shfl(incl, 63);
+    }
+    if (lane == 0) {
+        if (totals) totals[q] = running;
+        atomicAdd(scanned_points + (size_t)(q & 63) * 8, (u64)running);
+    }
+}
+
+// ---------------------------------------------------------------------------------------
 // Group the (query, probe) pairs by inverted list: exclusive scans of the probe histogram
 // (bucket offsets) and of the work items per list (ceil(cnt/QG) query groups x chunks).
 // ---------------------------------------------------------------------------------------
@@ -3453,15 +3507,22 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
         // query.  The bound is the workgroup-shared one (nothing writes it between the barrier above and the next scan, so
         // the decision is uniform); strict comparison of the high words: a key with an equal distance may still win on
         // visit order.
+        // prune == 2 (probes supplied by the caller, ivfadc_search_preassigned): the ranks come in the caller's order, not in
+        // ascending dc, so a list above the bound says nothing about the ranks behind it -- that probe alone is skipped (the
+        // per-list rule is exact in any order) and the query goes on; a round whose probes are all skipped builds no tables.
         if (a.prune) {
             const u32 thi = (u32)(readfirstlane64(L.sthr[0]) >> 32);
             if (__float_as_uint(dcv[0]) > thi) {
-                if (tid == 0) {
-                    u64 skipped = 0;
-                    for (int pj = j0; pj < w; ++pj) skipped += cached ? s_len[pj] : ix.list_len[prow_list[pj]];
-                    atomicAdd(a.scanned_points + (size_t)(q & 63) * 8 + 1, skipped);
+                if (a.prune == 1) {
+                    if (tid == 0) {
+                        u64 skipped = 0;
+                        for (int pj = j0; pj < w; ++pj) skipped += cached ? s_len[pj] : ix.list_len[prow_list[pj]];
+                        atomicAdd(a.scanned_points + (size_t)(q & 63) * 8 + 1, skipped);
+                    }
+                    break;
                 }
-                break;
+                if (tid == 0 && len[0] != 0) atomicAdd(a.scanned_points + (size_t)(q & 63) * 8 + 1, (u64)len[0]);
+                len[0] = 0;
             }
 #pragma unroll
             for (int s = 1; s < PG; ++s)
@@ -3469,6 +3530,18 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
                     if (tid == 0) atomicAdd(a.scanned_points + (size_t)(q & 63) * 8 + 1, (u64)len[s]);
                     len[s] = 0;
                 }
+            if (a.prune == 2) {
+                bool none = true;
+#pragma unroll
+                for (int s = 0; s < PG; ++s) none = none && len[s] == 0;
+                if (none) {   // uniform.  Nothing reads the residual buffer between the barrier above and the next round's build
+                    if (pipe && (j0 + np) < w) {
+                        resid_fetch(j0 + np);
+                        resid_store();
+                    }
+                    continue;
+                }
+            }
             if constexpr (PG == 2 && SMALL) {   // (K > 64: the LDS selectors' bound lags a round behind; measured -4 % there)
                 if (j0 == 0 && w > 1 && len[1] != 0 && dcv[1] > 2.0f * dcv[0]) {   // uniform: the closest cell alone first
                     len[1] = 0;

@@ -683,7 +683,7 @@ static __device__ __forceinline__ void lb_rounds(const IndexView &ix, const LbVi
         if (j0 > 0) lb_ub_merge(usel, sel, ubx, ubc, K, wv, lane, sthr, thr_hi);
         // exact pruning, as in the exact rounds: nothing writes the shared bound between barrier (A) and the next scan
         const u32 thi = (u32)(readfirstlane64(sthr[0]) >> 32);
-        if (prune && __float_as_uint(s_dc[j0]) > thi) {
+        if (prune == 1 && __float_as_uint(s_dc[j0]) > thi) {
             if (tid == 0) {
                 u64 skipped = 0;
                 for (int pj = j0; pj < w; ++pj) skipped += s_len[pj];
@@ -691,10 +691,25 @@ static __device__ __forceinline__ void lb_rounds(const IndexView &ix, const LbVi
             }
             break;
         }
+        // prune == 2 (probes in the caller's order, ivfadc_search_preassigned): a list above the bound ends nothing -- every probe of a
+        // round is judged alone, the first like the others below, and the rounds with nothing left to scan are stepped over right here
+        // (uniform: LDS words and the shared bound), before any table is built
+        if (prune == 2) {
+            for (; j0 < w; j0 += PG) {
+                bool none = true;
+                for (int s = 0; s < PG && (j0 + s) < w; ++s) none = none && (s_len[j0 + s] == 0 || __float_as_uint(s_dc[j0 + s]) > thi);
+                if (!none) break;
+                if (tid < PG && (j0 + tid) < w && s_len[j0 + tid] != 0) atomicAdd(scanned_points + (size_t)(q & 63) * 8 + 1, (u64)s_len[j0 + tid]);
+            }
+            if (j0 >= w) {
+                __syncthreads();   // the flush below stores the waves' upper-bound keys again: every wave is done reading them first
+                break;
+            }
+        }
         if (tid < PG) {
             const int s = tid;
             u32 len = (j0 + s) < w ? s_len[j0 + s] : 0u;
-            if (prune && s > 0 && len != 0 && __float_as_uint(s_dc[(j0 + s) < w ? j0 + s : j0]) > thi) {
+            if (prune && (s > 0 || prune == 2) && len != 0 && __float_as_uint(s_dc[(j0 + s) < w ? j0 + s : j0]) > thi) {
                 atomicAdd(scanned_points + (size_t)(q & 63) * 8 + 1, (u64)len);
                 len = 0;
             }

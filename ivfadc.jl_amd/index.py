@@ -95,7 +95,8 @@ class IVFADCIndex:
             "%d vectors require at least %d index bits" % (nvectors, bits_required)
         # :hnsw (coarsequantizers.jl:58-92) asks for an APPROXIMATE search of the coarse centroids through a graph; here the
         # centroids are searched exhaustively on the GPU, which is what that graph approximates -- the request is
-        # accepted and answered with the naive quantizer's (exact) cells
+        # accepted and answered with the naive quantizer's (exact) cells.  A caller who has such a graph (or any other
+        # coarse quantizer) searches with ITS cells through knn_search_preassigned
         self.requested_coarse_quantizer = coarse_quantizer
         if coarse_distance != "SqEuclidean" or quantization_distance != "SqEuclidean" or quantization_method != "pq":
             raise NotImplementedError("the HIP path implements SqEuclidean / :pq only (the reference defaults)")
@@ -354,6 +355,50 @@ class IVFADCIndex:
                                           nat.ptr(dists, C.c_float), nat.ptr(counts, C.c_int32)))
         return ids, dists, counts
 
+    # ---- the seam of knn_search: coarse_search on one side, everything that reads its two vectors on the other ------------
+    def coarse_search_raw(self, queries, w):
+        """coarse_search(cq, point, w) (coarsequantizers.jl:33-37) for a batch: (nq, d) -> lists (nq, w) int32 (0-based cells,
+        ascending distance, ties to the lower cell), dists (nq, w) float32, via ivfadc_coarse_search.  1 <= w <= kc."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        nq, wa = q.shape[0], max(int(w), 1)
+        lists = np.zeros((nq, wa), np.int32)
+        dists = np.zeros((nq, wa), np.float32)
+        nat.check(nat.lib().ivfadc_coarse_search(self._h, nq, nat.ptr(q, C.c_float), int(w), nat.ptr(lists, C.c_int32),
+                                                 nat.ptr(dists, C.c_float)))
+        return lists, dists
+
+    def search_preassigned_raw(self, queries, k, lists, dists):
+        """index.jl:220-257 given the output of ANY coarse_search: row q of lists / dists (nq, w) = the probes of query q in visit
+        order (0-based cells, pairwise distinct; distances finite and >= +0).  Returns (ids, dists, counts) as search_raw does,
+        via ivfadc_search_preassigned, which validates the probes on the host before anything is launched."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        nq = q.shape[0]
+        pl = np.ascontiguousarray(lists, np.int32)
+        pd = np.ascontiguousarray(dists, np.float32)
+        assert pl.ndim == 2 and pl.shape[0] == nq and pd.shape == pl.shape, "lists and dists must both be (nq, w)"
+        ka = max(int(k), 1)
+        ids = np.zeros((nq, ka), np.uint32)
+        out = np.full((nq, ka), np.inf, np.float32)
+        counts = np.zeros(nq, np.int32)
+        nat.check(nat.lib().ivfadc_search_preassigned(self._h, nq, nat.ptr(q, C.c_float), int(k), int(pl.shape[1]), nat.ptr(pl, C.c_int32),
+                                                      nat.ptr(pd, C.c_float), nat.ptr(ids, C.c_uint32), nat.ptr(out, C.c_float),
+                                                      nat.ptr(counts, C.c_int32)))
+        return ids, out, counts
+
+    def coarse_search_device(self, nq, q_ptr, w, lists_ptr, dists_ptr):
+        """Asynchronous coarse search on raw device pointers (ints); see ivfadc_coarse_search_device."""
+        nat.check(nat.lib().ivfadc_coarse_search_device(self._h, int(nq), C.c_void_p(q_ptr), int(w), C.c_void_p(lists_ptr),
+                                                        C.c_void_p(dists_ptr)))
+
+    def search_device_preassigned(self, nq, q_ptr, k, w, lists_ptr, cdists_ptr, ids_ptr, dists_ptr, counts_ptr):
+        """Asynchronous search with supplied probes on raw device pointers (ints); see ivfadc_search_device_preassigned: the
+        preconditions on the probes are the caller's here."""
+        nat.check(nat.lib().ivfadc_search_device_preassigned(self._h, int(nq), C.c_void_p(q_ptr), int(k), int(w), C.c_void_p(lists_ptr),
+                                                             C.c_void_p(cdists_ptr), C.c_void_p(ids_ptr), C.c_void_p(dists_ptr),
+                                                             C.c_void_p(counts_ptr)))
+
     # ---- measurement / tuning -------------------------------------------------------------------
     def set_profiling(self, on):
         """0 / False: off; 1 / True: HIP events around the coarse and scan kernels; 2: also the matrix-core table build alone."""
@@ -542,6 +587,51 @@ def knn_search(ivfadc, points, k, w=1):
                                               nat.ptr(dists, C.c_float), nat.ptr(counts, C.c_int32)))
         out_i = [ids[i, :counts[i]].astype(ivfadc.index_type) for i in range(nq)]
         out_d = [dists[i, :counts[i]].copy() for i in range(nq)]
+    if single:
+        return out_i[0], out_d[0]
+    return out_i, out_d
+
+
+def _as_points(ivfadc, points):
+    """(matrix (nq, d), single) of a vector, a matrix or a list of vectors, as knn_search takes them"""
+    single = isinstance(points, np.ndarray) and points.ndim == 1
+    if not single and not isinstance(points, np.ndarray):
+        points = np.stack([np.asarray(p, np.float32) for p in points]) if len(points) else np.zeros((0, ivfadc.d), np.float32)
+        single = points.ndim == 1
+    pts = np.asarray(points, np.float32)
+    if single:
+        pts = pts[None, :]
+    assert pts.ndim == 2 and pts.shape[1] == ivfadc.d, "queries must be (nq, %d)" % ivfadc.d
+    return pts, single
+
+
+def coarse_search(ivfadc, points, w):
+    """coarse_search(cq, point, w) (coarsequantizers.jl:33-37) on the index's coarse quantizer: (closest_clusters, coarse_distances),
+    the w closest cells in ascending distance, ties to the lower cell.  Cells are 0-based, as in `encode`.  A 1-D `points` is one
+    query and returns two (w,) arrays; a matrix or a list of vectors returns (nq, w) arrays."""
+    assert w >= 1, "Number of clusters to search in must be w >= 1"             # index.jl:211
+    pts, single = _as_points(ivfadc, points)
+    lists, dists = ivfadc.coarse_search_raw(pts, w)
+    if single:
+        return lists[0], dists[0]
+    return lists, dists
+
+
+def knn_search_preassigned(ivfadc, points, k, clusters, distances):
+    """knn_search (index.jl:204-258) behind its coarse_search call (index.jl:219): `clusters` / `distances` are what ANY
+    coarse_search returned for each query -- 0-based cells in visit order and their distances, (w,) for one query or (nq, w).
+    Returns what knn_search returns: (ids, dists) for one query, two lists of arrays otherwise."""
+    assert k >= 1, "Number of neighbors must be k >= 1"                          # index.jl:210
+    pts, single = _as_points(ivfadc, points)
+    cl = np.asarray(clusters, np.int32)
+    cd = np.asarray(distances, np.float32)
+    if single:
+        cl, cd = cl.reshape(1, -1), cd.reshape(1, -1)
+    assert cl.ndim == 2 and cl.shape[0] == pts.shape[0] and cd.shape == cl.shape, "clusters and distances must both be (nq, w)"
+    assert cl.shape[1] >= 1, "Number of clusters to search in must be w >= 1"   # index.jl:211
+    ids, dists, counts = ivfadc.search_preassigned_raw(pts, k, cl, cd)
+    out_i = [ids[i, :counts[i]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
+    out_d = [dists[i, :counts[i]].copy() for i in range(pts.shape[0])]
     if single:
         return out_i[0], out_d[0]
     return out_i, out_d

@@ -4,7 +4,8 @@
 # src/IVFADC.jl).  It adds MORE SPECIFIC methods of the reference's own generic functions -- knn_search
 # (src/index.jl:204-273), push! / pushfirst! (src/utils.jl:114-145), pop! / popfirst! (src/utils.jl:29-68),
 # delete_from_index! (src/utils.jl:90-105) -- for the element types the HIP library implements
-# (U = UInt8 or UInt16, T = Float32, SqEuclidean for both distances, NaiveQuantizer); every other index keeps the CPU methods.
+# (U = UInt8 or UInt16, T = Float32, SqEuclidean for both distances; NaiveQuantizer, or HNSWQuantizer for knn_search: its own
+# coarse_search runs on the CPU and the library searches the probes it returns); every other index keeps the CPU methods.
 # Every C symbol is declared in include/ivfadc_hip.h, which cites the reference interface it replaces.
 #
 # The same text is shown in INTEGRATION.md section 3 (tests/test_abi.py checks that the two stay identical and that every
@@ -13,7 +14,7 @@
 module IVFADCHip
 
 using IVFADC
-using IVFADC: IVFADCIndex, NaiveQuantizer
+using IVFADC: IVFADCIndex, NaiveQuantizer, HNSWQuantizer, coarse_search
 import IVFADC: knn_search, delete_from_index!
 import Base: push!, pushfirst!, pop!, popfirst!
 using Distances
@@ -91,7 +92,16 @@ end
 # buffers are untyped (Ptr{Cvoid}) in the C ABI and hold UInt16.  (GpuIndex{I} binds the index type I.)
 const GpuIndex = IVFADCIndex{U,I,Distances.SqEuclidean,Distances.SqEuclidean,Float32,
                              NaiveQuantizer{Distances.SqEuclidean,Float32}} where {I<:Unsigned, U<:Union{UInt8,UInt16}}
+# An index built with coarse_quantizer=:hnsw (coarsequantizers.jl:58-92): its centroids live in cq.hnsw.data and its coarse_search is an
+# APPROXIMATE graph search.  knn_search reads only what coarse_search returns (index.jl:219-257), so such an index is served with the
+# reference's semantics: coarse_search(cq, point, w) runs here, on the CPU, and ivfadc_search_preassigned does the rest on the probes it
+# returned.  Mutators keep the reference's CPU methods and drop the device copy (as on an :opq index).
+const HnswIndex = IVFADCIndex{U,I,Distances.SqEuclidean,Distances.SqEuclidean,Float32,
+                              <:HNSWQuantizer} where {I<:Unsigned, U<:Union{UInt8,UInt16}}
+const AnyGpuIndex = Union{GpuIndex,HnswIndex}
 _codetype(::IVFADCIndex{U}) where {U} = U
+_centroids(cq::NaiveQuantizer) = cq.vectors                                          # d×kc
+_centroids(cq::HNSWQuantizer) = Matrix{Float32}(reduce(hcat, cq.hnsw.data))          # the same matrix, from the graph's points
 
 # IVFADCIndex is an immutable struct (src/index.jl:39): it can carry no finalizer, and a WeakKeyDict would compare its mutable fields by
 # CONTENT.  Its inverse_index field is a Vector -- mutable, identity-stable, and exactly as long-lived as the index that holds it -- so
@@ -106,7 +116,7 @@ const _handles = Dict{UInt,HipHandle}()
 const _registry_lock = ReentrantLock()
 const _dead_lock = Base.Threads.SpinLock()
 const _dead_keys = UInt[]
-_key(ivfadc::GpuIndex) = objectid(ivfadc.inverse_index)
+_key(ivfadc::AnyGpuIndex) = objectid(ivfadc.inverse_index)
 function _drop_handle(lists)
     k = objectid(lists)
     lock(_dead_lock)
@@ -139,7 +149,7 @@ end
 _gpu_ok(ivfadc::GpuIndex) = ivfadc.residual_quantizer.rot == LinearAlgebra.I
 
 "Free the device copy of `ivfadc` now; the next GPU call uploads the Julia lists afresh."
-function hip_release!(ivfadc::GpuIndex)
+function hip_release!(ivfadc::AnyGpuIndex)
     lock(_registry_lock) do
         _drain_dead!()
         h = pop!(_handles, _key(ivfadc), nothing)
@@ -149,9 +159,10 @@ function hip_release!(ivfadc::GpuIndex)
 end
 
 "Upload (or refresh) the device copy of `ivfadc` from the Julia lists."
-function hip_sync!(ivfadc::GpuIndex; device::Int=0)
+function hip_sync!(ivfadc::AnyGpuIndex; device::Int=0)
     cq, rq = ivfadc.coarse_quantizer, ivfadc.residual_quantizer
-    d, kc = size(cq.vectors)
+    cent = _centroids(cq)
+    d, kc = size(cent)
     m = length(rq.codebooks); ksub = length(rq.codebooks[1].codes)
     _check_abi()
     h = lock(_registry_lock) do
@@ -164,11 +175,11 @@ function hip_sync!(ivfadc::GpuIndex; device::Int=0)
             labels16 = Vector{UInt16}(labels)                               # block after block, ksub labels each
             _check(ccall((:ivfadc_create_u16, LIBIVFADC), Cint,
                          (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{Cvoid}),
-                         out, device, d, kc, m, ksub, cq.vectors, cbs, labels16))
+                         out, device, d, kc, m, ksub, cent, cbs, labels16))
         else
             _check(ccall((:ivfadc_create, LIBIVFADC), Cint,
                          (Ref{Ptr{Cvoid}}, Cint, Cint, Cint, Cint, Cint, Ptr{Float32}, Ptr{Float32}, Ptr{UInt8}),
-                         out, device, d, kc, m, ksub, cq.vectors, cbs, labels))
+                         out, device, d, kc, m, ksub, cent, cbs, labels))
         end
         hh = HipHandle(out[])
         finalizer(hh) do x
@@ -195,7 +206,7 @@ function hip_sync!(ivfadc::GpuIndex; device::Int=0)
     return h
 end
 
-function _handle(ivfadc::GpuIndex)
+function _handle(ivfadc::AnyGpuIndex)
     h = lock(_registry_lock) do
         _drain_dead!()
         get(_handles, _key(ivfadc), nothing)
@@ -235,6 +246,74 @@ end
 
 knn_search(ivfadc::GpuIndex, point::Vector{Float32}, k::Int; w::Int=1) =
     first.(knn_search(ivfadc, [point], k; w=w))
+
+# knn_search on an index with an HNSW coarse quantizer: the reference's own coarse_search (coarsequantizers.jl:73-76) per query, then
+# index.jl:220-257 on the device for the probes it returned, in the order it returned them (ivfadc_search_preassigned: cells 0-based,
+# pairwise distinct; distances finite and >= +0).  A coarse result that is shorter than w or repeats a cell cannot be expressed as one
+# nq×w block: the call then falls back to the CPU method.
+function knn_search(ivfadc::HnswIndex{I,U}, points::Vector{Vector{Float32}}, k::Int; w::Int=1) where {I,U}
+    @assert k >= 1 "Number of neighbors must be k >= 1"
+    @assert w >= 1 "Number of clusters to search in must be w >= 1"
+    cpu() = invoke(knn_search, Tuple{IVFADCIndex{U,I,Distances.SqEuclidean,Distances.SqEuclidean,Float32},Vector{Vector{Float32}},Int},
+                   ivfadc, points, k; w=w)
+    nq = length(points)
+    nq == 0 && return Vector{I}[], Vector{Float32}[]
+    cq = ivfadc.coarse_quantizer
+    d, kc = size(cq)
+    wc = min(w, kc)                                                          # index.jl:216
+    lists = Matrix{Int32}(undef, wc, nq); cds = Matrix{Float32}(undef, wc, nq)
+    for i in 1:nq
+        @assert length(points[i]) == d "Searching requires $d-element vectors"
+        cl, cd = coarse_search(cq, points[i], wc)
+        (length(cl) == wc && length(cd) == wc && allunique(cl) && all(x -> isfinite(x) && !signbit(x), cd)) || return cpu()
+        lists[:, i] .= Int32.(cl .- 1)                                       # 0-based
+        cds[:, i] .= cd
+    end
+    h = _handle(ivfadc)
+    q, ids, dists, counts = _io(h, d, k, nq)
+    for i in 1:nq
+        copyto!(q, (i - 1) * d + 1, points[i], 1, d)
+    end
+    _check(ccall((:ivfadc_search_preassigned, LIBIVFADC), Cint,
+                 (Ptr{Cvoid}, Int64, Ptr{Float32}, Cint, Cint, Ptr{Int32}, Ptr{Float32}, Ptr{UInt32}, Ptr{Float32}, Ptr{Int32}),
+                 h.ptr, nq, q, k, wc, lists, cds, ids, dists, counts))
+    return [I.(ids[1:counts[i], i]) for i in 1:nq], [dists[1:counts[i], i] for i in 1:nq]
+end
+
+knn_search(ivfadc::HnswIndex, point::Vector{Float32}, k::Int; w::Int=1) =
+    first.(knn_search(ivfadc, [point], k; w=w))
+
+# ... and its mutators: the reference's CPU methods, after which the device copy is dropped, so that the next search uploads the
+# edited lists
+function push!(ivfadc::HnswIndex, point::Vector{Float32})
+    r = invoke(push!, Tuple{IVFADCIndex,Vector{Float32}}, ivfadc, point)
+    hip_release!(ivfadc)
+    return r
+end
+
+function pushfirst!(ivfadc::HnswIndex, point::Vector{Float32})
+    r = invoke(pushfirst!, Tuple{IVFADCIndex,Vector{Float32}}, ivfadc, point)
+    hip_release!(ivfadc)
+    return r
+end
+
+function pop!(ivfadc::HnswIndex)
+    rec = invoke(pop!, Tuple{IVFADCIndex}, ivfadc)
+    hip_release!(ivfadc)
+    return rec
+end
+
+function popfirst!(ivfadc::HnswIndex)
+    rec = invoke(popfirst!, Tuple{IVFADCIndex}, ivfadc)
+    hip_release!(ivfadc)
+    return rec
+end
+
+function delete_from_index!(ivfadc::HnswIndex, points::Vector{<:Integer})
+    invoke(delete_from_index!, Tuple{IVFADCIndex,Vector{<:Integer}}, ivfadc, points)
+    hip_release!(ivfadc)
+    return nothing
+end
 
 # A run of consecutive batches: `[knn_search(ivfadc, b, k; w=w) for b in batches]` as ONE native call (ivfadc_search_batches).  Inside,
 # every batch is searched with its successor already named (the serving-loop hint, ivfadc_set_next_queries, on buffers the library
