@@ -9,6 +9,7 @@ import numpy as np
 import pytest
 
 import helpers
+import write_path
 from oracle import oracle as ora
 
 pytestmark = pytest.mark.gpu
@@ -693,6 +694,8 @@ def test_delete_pop_pushfirst_in_place_on_device(native):
         for K, w in ((10, 5), (4, 13)):
             helpers.assert_same_results(gidx.search_raw(qs, K, w), onow.knn_search(qs, K, w), what="%s K=%d w=%d" % (what, K, w))
         assert len(gidx) == model.n()
+        # the whole device copy, against the MODEL's lists (not the mirror's): every stored point, its id and its distance bits
+        write_path.assert_device_equals(gidx, ora.OracleIndex(oidx.centroids, oidx.codebooks, oidx.labels, moff, mcodes, mids), qs[:2], what=what)
 
     pts = rng.integers(1, 901, 57).tolist() + [1, 900, 900, 5000]          # duplicates and an unknown id
     native.delete_from_index(gidx, pts)
