@@ -734,8 +734,8 @@ bool filt_shape(int m, int dsub) { return (m == 8 && dsub == 16) || (m == 16 && 
 // the shape the narrow-field list-major kernel exists for (nfscan.hip.h)
 bool nf_shape(int m, int dsub) { return m == 8 && dsub == 16; }
 
-// mirrors carve_lds() in kernels.hip.h
-size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool list_major = false)
+// mirrors carve_lds() in kernels.hip.h.  stripe: the plan's (Plan::stripe), for the width qg
+size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool list_major = false, bool stripe = false)
 {
     size_t b = (size_t)std::max(h->m, 2) * 256 * qg * 4;
     b += align_up((size_t)h->d * qg, 4) * 4;
@@ -744,8 +744,8 @@ size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool l
     b = align_up(b, 8) + (size_t)qg * 40;  // workgroup-shared thresholds + the four waves' quarter keys per slot (STHR_WORDS)
     b += 3 * 256;                           // query-major kernel: LDS copy of the query's probes (see qscan_kernel)
     if (list_major && qg == 4 && (h->m == 8 || h->m == 16))
-        b += 4 * 16 * 5 * 4;                // striped list-major kernels: 4 waves x CAND_CAP parked points x <= 5 dwords
-    if (list_major && qg == 4 && h->m == 8 && h->dsub == 16 && h->allow_filt && h->ksub == 256)
+        b += 4 * 16 * 5 * 4;                // groups of four at m = 8 / 16 (striped or not): 4 waves x CAND_CAP parked points x <= 5 dwords
+    if (stripe && h->m == 8)
         b += 256 * 64;                      // m = 8 striped: the 16-bit integer filter table behind the float tables (QF_BYTES)
     return b;
 }
@@ -761,6 +761,8 @@ bool w8_m16_dsub(int dsub) { return dsub == 4 || dsub == 8; }
 // the shapes (m, dsub) the handle's table mode admits, and the longest list the kernel's 28-bit positions and 31-bit byte offsets hold
 bool w8_md(const ivfadc_index *h) { return (h->m == 8 && w8_dsub(h->dsub)) || (h->m == 16 && w8_m16_dsub(h->dsub) && h->wg8_mode > 0); }
 int64_t w8_maxlen(const ivfadc_index *h) { return (int64_t)1 << (h->m == 16 ? 27 : 28); }
+typedef void (*nf_fn_t)(const ScanArgs, const NfView);
+typedef void (*u16_fn_t)(const ScanArgs, int);
 typedef void (*wg8_fn_t)(const ScanArgs, float *, const u32 *, u32 *, int);
 wg8_fn_t pick_wg8(bool q8, int m, int dsub)
 {
@@ -792,25 +794,98 @@ bool w8_default(const ivfadc_index *h) { return h->m == 8 && h->dsub == 16 && h-
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
 constexpr size_t MISC_BYTES = 4096 + 256 + 512 + 4096;
 constexpr size_t MISC_SINK = 4096 + 256 + 512;   // 64 counter lines nobody reads: where a coarse search alone (ivfadc_coarse_search) sends the B_alg counts of its top-w kernel
+// the eight queue heads of the narrow-field and the eight-wave kernel, zeroed in front of the launch that pulls from them
+int clear_xcd_heads(ivfadc_index *h, u32 *&xq)
+{
+    xq = (u32 *)((char *)h->misc.p + 4096 + 256);
+    HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
+    return IVFADC_OK;
+}
+
+// The scan a search runs.  Query-major: one workgroup per query (qscan_kernel), Lb with 8-bit lower-bound tables from the matrix cores
+// (lbscan.hip.h).  List-major: FourWave scan_kernel (striped tables: Plan::stripe); NarrowField nf_scan_kernel, eight queries per code
+// stream behind the 4-bit filter (nfscan.hip.h); EightWave wg8scan.hip.h, eight waves per workgroup on four conflict-free copies of
+// the integer filter table (Plan::q8: eight queries per stream; Plan::wide: the wide pool of 64 < K <= 128, the merge behind it is
+// the one of K > 64); U16 / U16Wide u16scan.hip.h on register / LDS selectors.
+enum class ScanForm { QueryMajor, QueryMajorLb, FourWave, NarrowField, EightWave, U16, U16Wide };
 
 struct Plan {
-    bool coarse_mfma;   // coarse scores on the matrix cores + certified exact refine (w <= 48)
-    bool fuse_topw;   // query-major only: top-w selection runs inside the scan kernel
-    bool query_major;
-    bool lb;            // query-major rounds with 8-bit lower-bound tables from the matrix cores (lbscan.hip.h)
-    bool nf;            // list-major with the narrow-field integer filter, eight queries per code stream (nfscan.hip.h)
-    bool wg8q8;         // ... its eight-query form (wg8_scan_kernel<8>)
-    bool wg8wide;       // ... with the wide pool (64 < K <= 128: wg8_wide_scan_kernel; the merge behind it is the one of K > 64)
-    bool wg8;           // list-major, eight waves per workgroup on four conflict-free copies of the integer filter table (wg8scan.hip.h)
-    bool lanes;         // several batches in flight on this replica: stand-alone top-w, a wave per query (see make_plan)
-    bool twolevel;      // coarse stage: certified two-level search (twolevel.hip.h) instead of the exhaustive kernels + top-w
-    bool small_k, small_w;
-    int qg, cap, capw, maxch;
-    uint32_t CH;
-    size_t lds;
-    int64_t nb;   // queries per sub-batch
-    bool fits;    // false: the selection kernels' LDS need exceeds the CU's 160 KB -> the caller takes the generic path
+    ScanForm form = ScanForm::QueryMajor;
+    bool stripe = false, q8 = false, wide = false;   // FourWave / EightWave only (see ScanForm)
+    const void *fn = nullptr;   // the scan kernel of the form: scan_fn_t, qscan_fn_t, wg8_fn_t, nf_fn_t or u16_fn_t
+    int threads = 256;          // ... and its workgroup size
+    bool coarse_mfma = false;   // coarse scores on the matrix cores + certified exact refine (w <= 48)
+    bool fuse_topw = false;   // query-major only: top-w selection runs inside the scan kernel
+    bool lanes = false;         // several batches in flight on this replica: stand-alone top-w, a wave per query (see make_plan)
+    bool twolevel = false;      // coarse stage: certified two-level search (twolevel.hip.h) instead of the exhaustive kernels + top-w
+    bool small_k = true, small_w = true;
+    int qg = 0, cap = 64, capw = 64, maxch = 1;
+    uint32_t CH = 0;
+    size_t lds = 0;
+    int64_t nb = 0;   // queries per sub-batch
+    bool fits = true;    // false: the selection kernels' LDS need exceeds the CU's 160 KB -> the caller takes the generic path
+    bool query_major() const { return form == ScanForm::QueryMajor || form == ScanForm::QueryMajorLb; }
+    // ivfadc_stats.last_striped of a list-major form: 1 striped four-wave tables; 2 / 3 eight-wave, four / eight queries; 4 / 5 its wide pool
+    int striped() const { return form == ScanForm::EightWave ? (wide ? 4 : 2) + (q8 ? 1 : 0) : (stripe ? 1 : 0); }
 };
+
+// selector capacity of the scan (K) and of the stand-alone top-w (w): registers up to 64, LDS buffers beyond
+int sel_cap(int k) { return k <= 64 ? 64 : std::max(128, pow2ceil(k + 64)); }
+
+// Coarse stage: the certified two-level search (twolevel.hip.h: its four waves keep their queries in LDS), or the matrix-core filter
+// -- which pays when the coarse search is large: below ~2k centroids the extra selection + refine work in the scan prologue costs
+// more than the VALU kernel it replaces (SIFT1M-shape: 92 -> 121 us per batch) -- or, with neither, the exact VALU kernels.
+// own: the search has a coarse stage of these kernels at all (not the caller's probes, not the generic path's sort); tl_batch: the
+// batch is one the two-level kernel's 32-bit indices hold
+struct CoarseForm { bool twolevel, mfma; };
+CoarseForm coarse_form(const ivfadc_index *h, int w, bool own, bool tl_batch)
+{
+    CoarseForm c;
+    c.twolevel = own && tl_batch && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
+    c.mfma = own && !c.twolevel && h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
+    return c;
+}
+
+// what both planners start from ...
+void plan_begin(const ivfadc_index *h, int64_t nq, int K, int w, bool pre, Plan &pl)
+{
+    pl = Plan{};
+    pl.small_k = K <= 64;
+    pl.small_w = w <= 64;
+    pl.cap = sel_cap(K);
+    pl.capw = sel_cap(w);
+    const CoarseForm c = coarse_form(h, w, !pre, nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G));
+    pl.twolevel = c.twolevel;
+    pl.coarse_mfma = c.mfma;
+}
+
+// ... the list-major ones go on, once pl.qg stands, with the chunk size (from ch0 points up; a forced one in multiples of align): enough
+// work items to fill the chip, as few table rebuilds as possible.  Two items per CU is the measured optimum on billion-scale lists
+// (SIFT1B-shape, 16..1024 queries, w = 1 and 8: every case at or within 5 % of its best chunk size; sixteen per CU rebuilt tables up
+// to 15 times per probe)
+void plan_chunks(const ivfadc_index *h, int64_t nq, int w, double avg_len, uint32_t ch0, uint32_t align, Plan &pl)
+{
+    const double ch = (double)nq * w * avg_len / pl.qg / (2.0 * h->num_cu);
+    uint32_t CH = ch0;
+    // (cap 2^18 points: on the billion-scale shapes a chunk then covers a whole list -- one table build and one selector
+    // warm-up per (list, query group) instead of two: SIFT1B-shape scan 8.64 -> 7.45 ms at w = 8, 1.87 -> 1.69 ms at w = 1)
+    while ((double)CH < ch && CH < (1u << 18)) CH <<= 1;
+    if (h->force_chunk > 0) CH = (uint32_t)align_up((size_t)h->force_chunk, align);
+    while ((h->maxlen + CH - 1) / CH > 64) CH <<= 1;   // bound the partial-result slots per probe
+    pl.CH = CH;
+    pl.maxch = (int)std::max<int64_t>(1, (h->maxlen + CH - 1) / CH);
+}
+
+// ... and both end with: sub-batches so the workspace stays inside the budget (partials: the list-major plans' partial results per probe and chunk)
+void plan_subbatch(const ivfadc_index *h, int64_t nq, int K, int w, bool partials, Plan &pl)
+{
+    const size_t per_q = (pl.twolevel ? (size_t)h->tl_G : (size_t)h->kc) * 4 + (partials ? (size_t)w * pl.maxch * ((size_t)K * 8 + 4) : 0) +
+                         (size_t)w * 20 + (size_t)K * 8 + 64;
+    int64_t nb = (int64_t)std::max<size_t>(64, h->ws_budget / per_q);
+    nb = std::min<int64_t>(nb, (int64_t)1 << 22);                                   // kernel arguments are 32-bit
+    nb = std::min<int64_t>(nb, std::max<int64_t>(64, ((int64_t)1 << 30) / std::max(1, w * pl.maxch)));
+    pl.nb = std::min<int64_t>(nq, nb);
+}
 
 // ---- how many probes a query-major round takes is a question about the DATA ---------------------------------------------------------
 // Two probes per round share every codeword fetch between two tables -- right when most probes are scanned; one probe per round lets
@@ -858,18 +933,9 @@ int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its s
 // read serves every pair of the item), halved for K > 64 until the selector buffers fit; chunks of whole passes, about two items per CU.
 int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)
 {
-    pl.fits = true;
-    pl.lanes = false;
-    pl.small_k = K <= 64;
-    pl.small_w = w <= 64;
-    pl.cap = pl.small_k ? 64 : std::max(128, pow2ceil(K + 64));
-    pl.capw = pl.small_w ? 64 : std::max(128, pow2ceil(w + 64));
-    pl.query_major = false;
-    pl.fuse_topw = pl.lb = pl.nf = pl.wg8 = pl.wg8q8 = pl.wg8wide = false;
-    pl.coarse_mfma = !pre && h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
-    pl.twolevel = !pre && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
-                  (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
-    if (pl.twolevel) pl.coarse_mfma = false;
+    plan_begin(h, nq, K, w, pre, pl);
+    pl.form = pl.small_k ? ScanForm::U16 : ScanForm::U16Wide;
+    pl.fn = (const void *)(pl.small_k ? (u16_fn_t)u16_scan_kernel : (u16_fn_t)u16_wide_scan_kernel);
     const double avg_len = (double)h->n / std::max(1, h->kc);
     const double ppl = (double)nq * w / std::max(1, h->kc);
     int qg = ppl >= 6.0 ? 8 : (ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1));
@@ -879,30 +945,133 @@ int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre 
     pl.qg = qg;
     pl.lds = pl.small_k ? u16_lds_bytes(h->m, h->dsub) : u16_wide_lds_bytes(h->m, h->dsub, qg, pl.cap);
     if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
-    const double ch = (double)nq * w * avg_len / qg / (2.0 * h->num_cu);
-    uint32_t CH = U16_PASS;
-    while ((double)CH < ch && CH < (1u << 18)) CH <<= 1;
-    if (h->force_chunk > 0) CH = (uint32_t)align_up((size_t)h->force_chunk, U16_PASS);
-    while ((h->maxlen + CH - 1) / CH > 64) CH <<= 1;   // bound the partial-result slots per probe
-    pl.CH = CH;
-    pl.maxch = (int)std::max<int64_t>(1, (h->maxlen + CH - 1) / CH);
-    const size_t per_q = (pl.twolevel ? (size_t)h->tl_G : (size_t)h->kc) * 4 + (size_t)w * pl.maxch * ((size_t)K * 8 + 4) + (size_t)w * 20 +
-                         (size_t)K * 8 + 64;
-    int64_t nb = (int64_t)std::max<size_t>(64, h->ws_budget / per_q);
-    nb = std::min<int64_t>(nb, (int64_t)1 << 22);
-    nb = std::min<int64_t>(nb, std::max<int64_t>(64, ((int64_t)1 << 30) / std::max(1, w * pl.maxch)));
-    pl.nb = std::min<int64_t>(nq, nb);
+    plan_chunks(h, nq, w, avg_len, U16_PASS, U16_PASS, pl);
+    plan_subbatch(h, nq, K, w, true, pl);
+    return IVFADC_OK;
+}
+
+// query-major: one workgroup per query, no grouping, no partial results
+int plan_query_major(ivfadc_index *h, int64_t nq, int w, bool pre, Plan &pl)
+{
+    // large kc: the selection is a 4*kc-byte stream per query, better done by the lean stand-alone kernel
+    pl.fuse_topw = pl.small_w && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel && !pre;
+    // Several batches in flight on this replica (the index has views, or this IS a view: ivfadc_search_batches' second lane, a serving
+    // loop's lanes): what bounds the chip then is register-file time, not one launch's latency -- and the fused selection holds a scan
+    // workgroup's four waves and 126 VGPRs each for the 10 k cycles (28 % of its life on the SIFT1M shape, by phase stamps) in which
+    // wave 0 selects and the others wait.  A stand-alone selection, one lean wave per query, costs a launch and gives the scan its
+    // registers back: 42.5 -> 44.7 M q/s with two batches in flight (profiles/r05_topw_probe.txt); one batch at a time keeps the fused form.
+    // (device-pointer entries only, and only while the lanes really run side by side -- h->dev_entry, set by the entry from the root
+    // index's tickets: the host entries are bound by the host's enqueue time, where one more launch per batch costs
+    // ivfadc_search_batches 27.8 -> 25.8 M q/s, and a caller who owns views but searches one batch at a time would pay a launch for nothing)
+    pl.lanes = h->dev_entry && (h->is_view || h->n_views.load() > 0) && nq >= 4 * (int64_t)h->num_cu && h->kc >= 512;
+    if (pl.lanes) pl.fuse_topw = false;
+    // probes per round: share each codeword fetch between PG tables, keep >= 4 workgroups per CU when possible
+    int pg = w >= 2 ? 2 : 1;   // measured: PG=2 beats PG=4 (register pressure halves the occupancy at 4)
+    if (pl.small_k && h->allow_prune && h->prune_est >= PG1_MIN_PRUNED) pg = 1;   // (fb_poll: most of what is probed gets pruned)
+    while (pg > 1 && scan_lds_bytes(h, pg, pl.cap, pl.small_k) > (size_t)(40 << 10)) pg >>= 1;
+    pl.qg = pg;
+    pl.lds = scan_lds_bytes(h, pg, pl.cap, pl.small_k);
+    // lower-bound tables on the matrix cores: four probes per round share one pass over the codebook (a quarter of the exact
+    // build's L1 traffic, a fraction of its vector-ALU work); register selectors and the LDS probe copy only
+    // (measured: m = 48, where the exact build re-reads 768 KB of codewords per probe, +20 % on the HD shape; m = 16 with 1.5 k-point
+    // lists -- the Deep1B shape -- loses 12 %: four barriers and the round's setup per four 24 KB lists cost what the cheaper tables
+    // save, so there the rounds run only on request, ivfadc_set_table_mode(h, 2))
+    const bool lb = h->allow_lb && h->allow_filt && h->lb_split.p != nullptr && lb_shape(h->m, h->dsub) && pl.small_k && w <= 32 &&
+                    h->ksub == 256 && (h->m >= 32 || h->force_lb);
+    pl.form = lb ? ScanForm::QueryMajorLb : ScanForm::QueryMajor;
+    if (lb) {
+        // the top-w selection of a large batch runs as its own launch, one wave per query at full occupancy (per-tile records,
+        // no score matrix); inside this kernel -- two workgroups per CU, three waves idle -- it was a sixth of the launch
+        if (nq >= 4 * (int64_t)h->num_cu || pl.twolevel) pl.fuse_topw = false;
+        pl.qg = w >= 3 ? 4 : w;
+        pl.lds = lb_lds_bytes(h->m, h->dsub, pl.qg);
+    }
+    if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }   // e.g. m = 48 with K near 2048: tables + selector buffers
+    pl.fn = (const void *)(lb ? pick_qscan_lb(h->m, h->dsub, pl.qg) : pick_qscan(h->m, h->dsub, pl.qg, pl.small_k));
+    return IVFADC_OK;
+}
+
+// list-major: work items of (list, group of qg queries that probe it, chunk of CH points), partial results merged behind the scan
+int plan_list_major(ivfadc_index *h, int64_t nq, int K, int w, double avg_len, bool long_lists, bool forced, Plan &pl)
+{
+    // query-group width from the expected number of probes per list
+    const double ppl = (double)nq * w / std::max(1, h->kc);
+    int qg = ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1);
+    // billion-scale lists (a list is megabytes: the stream, not the per-item work, is what a group shares): wider groups pay
+    // much earlier.  SIFT1B shape, step in ms at QG = 1 / 2 / 4 (profiles/r03_a_sift1b_plan_sweep.txt): probes per list 0.125:
+    // 0.26 / 0.30 / 0.38; 0.25: 0.45 / 0.42 / 0.54; 0.5: 0.90 / 0.70 / 0.81; 1.0: 1.55 / 1.07 / 1.15; 2.0: 2.93 / 1.81 / 1.57
+    // -- the regime of one rank of an 8-GPU run on a 16 384-query batch (2048 queries, w = 8)
+    if (long_lists) qg = ppl >= 1.5 ? 4 : (ppl >= 0.2 ? 2 : 1);
+    // ... and where the eight-wave kernel exists (it is planned below for groups of four) it pays from half a probe per list: scan ms of
+    // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
+    // 0.316 / 0.544 / 0.92-0.93 (round 6)
+    // (K the kernel's pool holds: 64, or 128 where table mode 8 / 9 asks for the wide pool -- a request, so wg8_mode > 0 there)
+    const bool w8_k = pl.small_k || (K <= W8_WIDE_MAX_K && h->wg8_wide && h->wg8_mode > 0 && h->m == 8);
+    // ... the kernel exists for the index and may run: every admission below is this and a reason to take it
+    // (positions and byte offsets of a list are 28- / 31-bit quantities in the kernel: lists of fewer than 2^28 points; m = 16: 27-bit
+    // lists -- a point is 16 bytes -- and on request only: w8_md)
+    const bool w8_base = w8_k && h->allow_filt && h->wg8_mode >= 0 && w8_md(h) && h->ksub == 256 && h->maxlen < w8_maxlen(h);
+    const bool w8_shape = w8_base && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
+    if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
+    if (forced) qg = h->force_qg;
+    // eight queries per code stream behind the 4-bit narrow-field filter (nfscan.hip.h): conflict-free gathers, a third of the vector
+    // instructions per (query, point), every list streamed once per eight queries -- where the shape has the kernel, K fits the
+    // register selectors and the lists are probed often enough to fill the groups
+    // (measured, SIFT1B shape, 16 384 x w = 8: 7.76 ms against 7.44 ms for the 16-bit four-query kernel -- DESIGN.md 4.11 -- so the kernel
+    // runs on request only: ivfadc_set_tuning(h, 8, 0))
+    const bool nf_ok = h->allow_nf && h->allow_filt && h->nf_n2.p != nullptr && nf_shape(h->m, h->dsub) && h->ksub == 256 && pl.small_k;
+    if (h->force_qg == 8 && !nf_ok) qg = 4;
+    if (nf_ok && h->force_qg == 8) {
+        pl.form = ScanForm::NarrowField;
+        pl.fn = (const void *)(nf_fn_t)nf_scan_kernel<4>;   // four points per lane and step (measured: two 9.2 ms, eight 8.1 ms -- and 74 spilled registers -- against 7.76 ms)
+        pl.qg = qg = 8;
+        pl.lds = (size_t)NfLds::END;
+    } else {
+        // keep two workgroups per CU when possible (a forced width only yields to the hard LDS limit)
+        // (groups of four that the wide-pool kernel takes below need none of the four-wave kernel's LDS selectors: its budget does not narrow them)
+        // (... nor do the groups of four of an m = 16 index that the kernel takes on request: the four-wave kernel's 64 KB of f32 tables are not built)
+        const bool w8_wide_ok = w8_base && h->wg8_mode > 0 && (!pl.small_k || h->m == 16);
+        // the four-wave kernel's striped form (and at m = 8 its 16-bit integer filter), and its LDS need, at a width
+        auto stripe_at = [&](int g) { return h->allow_filt && filt_shape(h->m, h->dsub) && g == 4 && h->ksub == 256; };
+        auto lds_at = [&](int g) { return scan_lds_bytes(h, g, pl.cap, pl.small_k, true, stripe_at(g)); };
+        while (qg > 1 && !(qg == 4 && w8_wide_ok) && lds_at(qg) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
+        if (!(qg == 4 && w8_wide_ok) && lds_at(qg) > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
+        // four queries per code stream on long lists of the m = 8 / dsub = 16 shape: the eight-wave kernel (a work item must feed
+        // eight waves: lists of at least 8 K points).  Measured on the SIFT1B shape against the four-wave kernel (profiles/r06_w8_sweep.txt,
+        // the eight-wave kernel with its workgroup pool): 16 384 queries, scan ms at w = 1 / 8: 1.36 / 5.73 against 1.68 / 7.46;
+        // 2048 x w = 8: 1.06 against 1.47.
+        // (The list-partitioned mode needs nothing of the kernel: the partition is applied in front of it -- the top-w kernel counts this rank's
+        // lists only into list_cnt, which bucket_scan_kernel turns into work items and item_list, bucket_scatter_kernel drops the other
+        // ranks' probes -- and behind it, in merge_kernel; a rank's work items are ordinary ones)
+        // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
+        if (qg == 4 && w8_base && (h->wg8_mode > 0 || (w8_default(h) && avg_len >= 8192.0))) {
+            pl.form = ScanForm::EightWave;
+            pl.wide = !pl.small_k;
+            // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
+            // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
+            pl.q8 = h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W8_Q8_MIN_PPL);
+            if (pl.q8) qg = 8;
+            pl.lds = h->m == 16 ? (pl.q8 ? (size_t)W8Lds<8, 1, 16>::END : (size_t)W8Lds<4, 1, 16>::END)
+                   : pl.wide    ? (pl.q8 ? (size_t)W8Lds<8, 2>::END : (size_t)W8Lds<4, 2>::END)
+                                : (pl.q8 ? (size_t)W8Lds<8>::END : (size_t)W8Lds<4>::END);
+            pl.fn = (const void *)(pl.wide ? (h->m == 8 ? pick_wg8_wide(pl.q8, h->dsub) : nullptr) : pick_wg8(pl.q8, h->m, h->dsub));
+            if (!pl.fn) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for m = %d, dsub = %d, which has no instantiation", h->m, h->dsub);
+            pl.threads = W8_THREADS;
+        } else {
+            pl.form = ScanForm::FourWave;
+            pl.stripe = stripe_at(qg);
+            pl.lds = lds_at(qg);
+            pl.fn = (const void *)pick_scan(h->m, h->dsub, qg, pl.small_k, pl.stripe);
+        }
+        pl.qg = qg;
+    }
+    plan_chunks(h, nq, w, avg_len, 4096, 1024, pl);
     return IVFADC_OK;
 }
 
 int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)   // pre: the probes are the caller's (PreProbes): no coarse stage of any kind
 {
-    pl.fits = true;
-    pl.lanes = false;
-    pl.small_k = K <= 64;
-    pl.small_w = w <= 64;
-    pl.cap = pl.small_k ? 64 : std::max(128, pow2ceil(K + 64));
-    pl.capw = pl.small_w ? 64 : std::max(128, pow2ceil(w + 64));
+    plan_begin(h, nq, K, w, pre, pl);
     const double avg_len = (double)h->n / std::max(1, h->kc);
     // list-major (queries that probe a list share its code stream; per-item grouping/merge overhead) wins when
     // the lists are very long (a query's probe must be split over workgroups anyway), or when a list is probed by
@@ -926,144 +1095,13 @@ int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = fa
     // 64 queries for w = 8 / 16; w <= 4 stays query-major (30 vs 33 us).  Not with a large kc, where the per-list
     // bookkeeping of the list-major plan costs more than it buys (Deep1B-shape 380 vs 234 us)
     const bool few_many = w >= 8 && nq <= 32 + (int64_t)w && nq <= h->num_cu / 4 && h->kc <= 8192;
-    pl.query_major = !(long_lists || shared || few_heavy || few_many);
-    if (h->force_qg == -1 || h->force_qg == -3) pl.query_major = true;
-    if (h->part_n > 1) pl.query_major = false;   // list-partitioned mode: the list-major plan is the one that skips other ranks' lists
+    bool query_major = !(long_lists || shared || few_heavy || few_many);
+    if (h->force_qg == -1 || h->force_qg == -3) query_major = true;
+    if (h->part_n > 1) query_major = false;   // list-partitioned mode: the list-major plan is the one that skips other ranks' lists
     const bool forced = (h->force_qg == 1 || h->force_qg == 2 || h->force_qg == 4 || h->force_qg == 8);
-    if (forced) pl.query_major = false;
-    pl.CH = 0;
-    pl.maxch = 1;
-    pl.wg8 = false;
-    pl.wg8q8 = false;
-    pl.wg8wide = false;
-    pl.fuse_topw = false;
-    pl.lb = false;
-    pl.nf = false;
-    // The filter pays when the coarse search is large: below ~2k centroids the extra selection + refine work in the
-    // scan prologue costs more than the VALU kernel it replaces (SIFT1M-shape: 92 -> 121 us per batch).
-    pl.coarse_mfma = !pre && h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
-    pl.twolevel = !pre && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G) &&
-                  (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);   // (its four waves keep their queries in LDS)
-    if (pl.twolevel) pl.coarse_mfma = false;
-    if (pl.query_major) {
-        // large kc: the selection is a 4*kc-byte stream per query, better done by the lean stand-alone kernel
-        pl.fuse_topw = pl.small_w && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel && !pre;
-        // Several batches in flight on this replica (the index has views, or this IS a view: ivfadc_search_batches' second lane, a serving
-        // loop's lanes): what bounds the chip then is register-file time, not one launch's latency -- and the fused selection holds a scan
-        // workgroup's four waves and 126 VGPRs each for the 10 k cycles (28 % of its life on the SIFT1M shape, by phase stamps) in which
-        // wave 0 selects and the others wait.  A stand-alone selection, one lean wave per query, costs a launch and gives the scan its
-        // registers back: 42.5 -> 44.7 M q/s with two batches in flight (profiles/r05_topw_probe.txt); one batch at a time keeps the fused form.
-        // (device-pointer entries only, and only while the lanes really run side by side -- h->dev_entry, set by the entry from the root
-        // index's tickets: the host entries are bound by the host's enqueue time, where one more launch per batch costs
-        // ivfadc_search_batches 27.8 -> 25.8 M q/s, and a caller who owns views but searches one batch at a time would pay a launch for nothing)
-        pl.lanes = h->dev_entry && (h->is_view || h->n_views.load() > 0) && nq >= 4 * (int64_t)h->num_cu && h->kc >= 512;
-        if (pl.lanes) pl.fuse_topw = false;
-        // probes per round: share each codeword fetch between PG tables, keep >= 4 workgroups per CU when possible
-        int pg = w >= 2 ? 2 : 1;   // measured: PG=2 beats PG=4 (register pressure halves the occupancy at 4)
-        if (pl.small_k && h->allow_prune && h->prune_est >= PG1_MIN_PRUNED) pg = 1;   // (fb_poll: most of what is probed gets pruned)
-        while (pg > 1 && scan_lds_bytes(h, pg, pl.cap, pl.small_k) > (size_t)(40 << 10)) pg >>= 1;
-        pl.qg = pg;
-        pl.lds = scan_lds_bytes(h, pg, pl.cap, pl.small_k);
-        // lower-bound tables on the matrix cores: four probes per round share one pass over the codebook (a quarter of the exact
-        // build's L1 traffic, a fraction of its vector-ALU work); register selectors and the LDS probe copy only
-        // (measured: m = 48, where the exact build re-reads 768 KB of codewords per probe, +20 % on the HD shape; m = 16 with 1.5 k-point
-        // lists -- the Deep1B shape -- loses 12 %: four barriers and the round's setup per four 24 KB lists cost what the cheaper tables
-        // save, so there the rounds run only on request, ivfadc_set_table_mode(h, 2))
-        pl.lb = h->allow_lb && h->allow_filt && h->lb_split.p != nullptr && lb_shape(h->m, h->dsub) && pl.small_k && w <= 32 &&
-                h->ksub == 256 && (h->m >= 32 || h->force_lb);
-        if (pl.lb) {
-            // the top-w selection of a large batch runs as its own launch, one wave per query at full occupancy (per-tile records,
-            // no score matrix); inside this kernel -- two workgroups per CU, three waves idle -- it was a sixth of the launch
-            if (nq >= 4 * (int64_t)h->num_cu || pl.twolevel) pl.fuse_topw = false;
-            pl.qg = w >= 3 ? 4 : w;
-            pl.lds = lb_lds_bytes(h->m, h->dsub, pl.qg);
-        }
-        if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }   // e.g. m = 48 with K near 2048: tables + selector buffers
-    } else {
-        // query-group width from the expected number of probes per list
-        const double ppl = (double)nq * w / std::max(1, h->kc);
-        int qg = ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1);
-        // billion-scale lists (a list is megabytes: the stream, not the per-item work, is what a group shares): wider groups pay
-        // much earlier.  SIFT1B shape, step in ms at QG = 1 / 2 / 4 (profiles/r03_a_sift1b_plan_sweep.txt): probes per list 0.125:
-        // 0.26 / 0.30 / 0.38; 0.25: 0.45 / 0.42 / 0.54; 0.5: 0.90 / 0.70 / 0.81; 1.0: 1.55 / 1.07 / 1.15; 2.0: 2.93 / 1.81 / 1.57
-        // -- the regime of one rank of an 8-GPU run on a 16 384-query batch (2048 queries, w = 8)
-        if (long_lists) qg = ppl >= 1.5 ? 4 : (ppl >= 0.2 ? 2 : 1);
-        // ... and where the eight-wave kernel exists (it is planned below for groups of four) it pays from half a probe per list: scan ms of
-        // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
-        // 0.316 / 0.544 / 0.92-0.93 (round 6)
-        // (K the kernel's pool holds: 64, or 128 where table mode 8 / 9 asks for the wide pool -- a request, so wg8_mode > 0 there)
-        const bool w8_wide_k = !pl.small_k && h->wg8_wide && h->wg8_mode > 0 && h->m == 8 && K <= W8_WIDE_MAX_K;
-        const bool w8_k = pl.small_k || w8_wide_k;
-        const bool w8_shape = w8_k && h->allow_filt && h->wg8_mode >= 0 && w8_md(h) && h->ksub == 256 &&
-                              h->maxlen < w8_maxlen(h) && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
-        if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
-        if (forced) qg = h->force_qg;
-        // eight queries per code stream behind the 4-bit narrow-field filter (nfscan.hip.h): conflict-free gathers, a third of the vector
-        // instructions per (query, point), every list streamed once per eight queries -- where the shape has the kernel, K fits the
-        // register selectors and the lists are probed often enough to fill the groups
-        // (measured, SIFT1B shape, 16 384 x w = 8: 7.76 ms against 7.44 ms for the 16-bit four-query kernel -- DESIGN.md 4.11 -- so the kernel
-        // runs on request only: ivfadc_set_tuning(h, 8, 0))
-        const bool nf_ok = h->allow_nf && h->allow_filt && h->nf_n2.p != nullptr && nf_shape(h->m, h->dsub) && h->ksub == 256 && pl.small_k;
-        if (h->force_qg == 8 && !nf_ok) qg = 4;
-        pl.nf = nf_ok && h->force_qg == 8;
-        if (pl.nf) {
-            qg = 8;
-            pl.qg = 8;
-            pl.lds = (size_t)NfLds::END;
-        } else {
-        // keep two workgroups per CU when possible (a forced width only yields to the hard LDS limit)
-        // (groups of four that the wide-pool kernel takes below need none of the four-wave kernel's LDS selectors: its budget does not narrow them)
-        // (... nor do the groups of four of an m = 16 index that the kernel takes on request: the four-wave kernel's 64 KB of f32 tables are not built)
-        const bool w8_m16_ok = pl.small_k && h->allow_filt && h->m == 16 && w8_md(h) && h->ksub == 256 && h->maxlen < w8_maxlen(h);
-        const bool w8_wide_ok = (w8_wide_k && h->allow_filt && h->m == 8 && w8_dsub(h->dsub) && h->ksub == 256 && h->maxlen < ((int64_t)1 << 28)) || w8_m16_ok;
-        while (qg > 1 && !(qg == 4 && w8_wide_ok) && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
-        if (!(qg == 4 && w8_wide_ok) && scan_lds_bytes(h, qg, pl.cap, pl.small_k, true) > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
-        pl.qg = qg;
-        pl.lds = scan_lds_bytes(h, qg, pl.cap, pl.small_k, true);
-        // four queries per code stream on long lists of the m = 8 / dsub = 16 shape: the eight-wave kernel (a work item must feed
-        // eight waves: lists of at least 8 K points).  Measured on the SIFT1B shape against the four-wave kernel (profiles/r06_w8_sweep.txt,
-        // the eight-wave kernel with its workgroup pool): 16 384 queries, scan ms at w = 1 / 8: 1.36 / 5.73 against 1.68 / 7.46;
-        // 2048 x w = 8: 1.06 against 1.47.
-        // (positions and byte offsets of a list are 28- / 31-bit quantities in the kernel: lists of fewer than 2^28 points.  The
-        // list-partitioned mode needs nothing of the kernel: the partition is applied in front of it -- the top-w kernel counts this rank's
-        // lists only into list_cnt, which bucket_scan_kernel turns into work items and item_list, bucket_scatter_kernel drops the other
-        // ranks' probes -- and behind it, in merge_kernel; a rank's work items are ordinary ones)
-        // (m = 16: 27-bit lists -- a point is 16 bytes -- and on request only: w8_md)
-        pl.wg8 = qg == 4 && w8_k && h->allow_filt && h->wg8_mode >= 0 && w8_md(h) && h->ksub == 256 &&
-                 h->maxlen < w8_maxlen(h) &&
-                 (h->wg8_mode > 0 || (w8_default(h) && avg_len >= 8192.0));   // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
-        pl.wg8wide = pl.wg8 && !pl.small_k;
-        if (pl.wg8) pl.lds = h->m == 16 ? (size_t)W8Lds<4, 1, 16>::END : (pl.wg8wide ? (size_t)W8Lds<4, 2>::END : (size_t)W8Lds<4>::END);
-        // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
-        // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
-        pl.wg8q8 = pl.wg8 && (h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W8_Q8_MIN_PPL));
-        if (pl.wg8q8) {
-            qg = 8;
-            pl.qg = 8;
-            pl.lds = h->m == 16 ? (size_t)W8Lds<8, 1, 16>::END : (pl.wg8wide ? (size_t)W8Lds<8, 2>::END : (size_t)W8Lds<8>::END);
-        }
-        }
-        // chunk size: enough work items to fill the chip, as few table rebuilds as possible.  Two items per CU is the
-        // measured optimum on billion-scale lists (SIFT1B-shape, 16..1024 queries, w = 1 and 8: every case at or within
-        // 5 % of its best chunk size; sixteen per CU rebuilt tables up to 15 times per probe)
-        const double items_target = 2.0 * h->num_cu;
-        const double ch = (double)nq * w * avg_len / qg / items_target;
-        uint32_t CH = 4096;
-        // (cap 2^18 points: on the billion-scale shapes a chunk then covers a whole list -- one table build and one selector
-        // warm-up per (list, query group) instead of two: SIFT1B-shape scan 8.64 -> 7.45 ms at w = 8, 1.87 -> 1.69 ms at w = 1)
-        while ((double)CH < ch && CH < (1u << 18)) CH <<= 1;
-        if (h->force_chunk > 0) CH = (uint32_t)align_up((size_t)h->force_chunk, 1024);
-        while ((h->maxlen + CH - 1) / CH > 64) CH <<= 1;   // bound the partial-result slots per probe
-        pl.CH = CH;
-        pl.maxch = (int)std::max<int64_t>(1, (h->maxlen + CH - 1) / CH);
-    }
-    // sub-batch so the workspace stays inside the budget
-    const size_t per_q = (pl.twolevel ? (size_t)h->tl_G : (size_t)h->kc) * 4 + (pl.query_major ? 0 : (size_t)w * pl.maxch * ((size_t)K * 8 + 4)) +
-                         (size_t)w * 20 + (size_t)K * 8 + 64;
-    int64_t nb = (int64_t)std::max<size_t>(64, h->ws_budget / per_q);
-    nb = std::min<int64_t>(nb, (int64_t)1 << 22);                                   // kernel arguments are 32-bit
-    nb = std::min<int64_t>(nb, std::max<int64_t>(64, ((int64_t)1 << 30) / std::max(1, w * pl.maxch)));
-    pl.nb = std::min<int64_t>(nq, nb);
+    if (forced) query_major = false;
+    TRY(query_major ? plan_query_major(h, nq, w, pre, pl) : plan_list_major(h, nq, K, w, avg_len, long_lists, forced, pl));
+    if (pl.fits) plan_subbatch(h, nq, K, w, !query_major, pl);
     return IVFADC_OK;
 }
 
@@ -1081,6 +1119,23 @@ int ensure_common_ws(ivfadc_index *h)
         h->list_cnt_armed = true;
     }
     return IVFADC_OK;
+}
+
+// The exact VALU distances of nb queries to n centres (the centroids, or the two-level search's group centres), out[nb][n].  Small
+// batches: narrower query tiles multiply the workgroup count until every SIMD has its four waves.  sgpr: small problems (every
+// workgroup resident at once) may take the centre-per-lane kernel, queries in SGPRs -- no LDS traffic to speak of, the wave's
+// instruction stream is the VALU minimum (SIFT1M-shape, 1024 queries: 14.9 -> see DESIGN 4.1)
+void launch_coarse_exact(ivfadc_index *h, const float *d_q, int64_t nb, const float *centres, int n, float *out, bool sgpr)
+{
+    const int64_t wg64 = (int64_t)((n + CO_T - 1) / CO_T) * ((nb + 63) / 64);
+    const int tq = wg64 >= 4 * (int64_t)h->num_cu ? 64 : (2 * wg64 >= 4 * (int64_t)h->num_cu ? 32 : 16);
+    const dim3 grid((n + CO_T - 1) / CO_T, (unsigned)((nb + tq - 1) / tq));
+    if (sgpr && (h->d & 7) == 0 && (nb + 15) / 16 <= 65535 && tq < 64)
+        hipLaunchKernelGGL(coarse_sgpr_kernel<4>, dim3((n + 63) / 64, (unsigned)((nb + 15) / 16)), dim3(256), 0, h->stream, d_q, centres, out,
+                           (int)nb, n, h->d);
+    else
+        hipLaunchKernelGGL((tq == 16 ? coarse_dist_kernel<16> : tq == 32 ? coarse_dist_kernel<32> : coarse_dist_kernel<64>), grid, dim3(256), 0,
+                           h->stream, d_q, centres, out, (int)nb, n, h->d, h->d);
 }
 
 // want_tmin: also write the per-tile minimum scores (stand-alone top-w with one wave per query reads them)
@@ -1118,6 +1173,13 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
         // against 15.3 us for the exact VALU kernel -- launch-bound either way -- and the refine costs the scan prologue 4 us)
         h->last_coarse_bf16 = big && h->allow_bf16;
         h->last_coarse_f16 = h->last_coarse_bf16 && h->allow_f16 && h->f16_scale > 0.f && h->cent_f16.p != nullptr;
+        uint4 *tl = nullptr;
+        if (listed) {   // (implies the f16 or the split-bf16 kernel below)
+            TRY(h->tlist.ensure((size_t)ntiles * nb * 16));
+            tl = h->tlist.as<uint4>();
+            h->last_listed = true;
+            h->tlist_ldq = (int)nb;
+        }
         if (h->last_coarse_f16) {
             // one f16 product per score (kernels.hip.h, "round 5"): scaled f16 queries + overflow flags, then the same tile kernel
             const int dp = h->dp32;
@@ -1127,13 +1189,6 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
             hipLaunchKernelGGL(split_f16_kernel, dim3((unsigned)std::min<int64_t>(4096, (nb * dp + 255) / 256)), dim3(256), 0, h->stream, d_q,
                                (int64_t)nb, h->d, dp, h->f16_scale, h->q_f16.as<unsigned short>(), h->q_flags.as<u32>());
             HIP_TRY(hipGetLastError());
-            uint4 *tl = nullptr;
-            if (listed) {
-                TRY(h->tlist.ensure((size_t)ntiles * nb * 16));
-                tl = h->tlist.as<uint4>();
-                h->last_listed = true;
-                h->tlist_ldq = (int)nb;
-            }
             const float neg2 = -2.0f / (h->f16_scale * h->f16_scale);
             hipLaunchKernelGGL((coarse_bf16_kernel<128, true>), grid, dim3(256), 0, h->stream, h->q_f16.as<unsigned short>(),
                                (const unsigned short *)nullptr, h->cent_f16.as<unsigned short>(), (const unsigned short *)nullptr,
@@ -1147,13 +1202,6 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
             hipLaunchKernelGGL(split_bf16_kernel, dim3((unsigned)std::min<int64_t>(4096, (nb * dp + 255) / 256)), dim3(256), 0, h->stream, d_q,
                                (int64_t)nb, h->d, dp, h->q_hi.as<unsigned short>(), h->q_lo.as<unsigned short>());
             HIP_TRY(hipGetLastError());
-            uint4 *tl = nullptr;
-            if (listed) {
-                TRY(h->tlist.ensure((size_t)ntiles * nb * 16));
-                tl = h->tlist.as<uint4>();
-                h->last_listed = true;
-                h->tlist_ldq = (int)nb;
-            }
             hipLaunchKernelGGL(coarse_bf16_kernel<128>, grid, dim3(256), 0, h->stream, h->q_hi.as<unsigned short>(),
                                h->q_lo.as<unsigned short>(), h->cent_hi.as<unsigned short>(), h->cent_lo.as<unsigned short>(),
                                h->cnorm.as<float>(), listed ? (float *)nullptr : h->cdist.as<float>(), (int)nb, h->kc, dp, tmin, ntiles, tl,
@@ -1167,27 +1215,8 @@ int run_coarse(ivfadc_index *h, const float *d_q, int64_t nb, bool mfma, bool wa
         else
             hipLaunchKernelGGL((coarse_mfma_kernel<64, 16>), grid, dim3(256), 0, h->stream, d_q, h->centroids.as<float>(),
                                h->cnorm.as<float>(), h->cdist.as<float>(), (int)nb, h->kc, h->d, tmin, ntiles);
-    } else {
-        // small batches: narrower query tiles multiply the workgroup count until every SIMD has its four waves
-        const int64_t wg64 = (int64_t)((h->kc + CO_T - 1) / CO_T) * ((nb + 63) / 64);
-        int tq = wg64 >= 4 * (int64_t)h->num_cu ? 64 : (2 * wg64 >= 4 * (int64_t)h->num_cu ? 32 : 16);
-        dim3 grid((h->kc + CO_T - 1) / CO_T, (unsigned)((nb + tq - 1) / tq));
-        // small problems (every workgroup resident at once): centroid per lane, queries in SGPRs -- no LDS traffic to
-        // speak of, the wave's instruction stream is the VALU minimum (SIFT1M-shape, 1024 queries: 14.9 -> see DESIGN 4.1)
-        const bool sgpr = (h->d & 7) == 0 && (nb + 15) / 16 <= 65535 && tq < 64;
-        if (sgpr)
-            hipLaunchKernelGGL(coarse_sgpr_kernel<4>, dim3((h->kc + 63) / 64, (unsigned)((nb + 15) / 16)), dim3(256), 0, h->stream, d_q,
-                               h->centroids.as<float>(), h->cdist.as<float>(), (int)nb, h->kc, h->d);
-        else if (tq == 16)
-            hipLaunchKernelGGL(coarse_dist_kernel<16>, grid, dim3(256), 0, h->stream, d_q, h->centroids.as<float>(),
-                               h->cdist.as<float>(), (int)nb, h->kc, h->d, h->d);
-        else if (tq == 32)
-            hipLaunchKernelGGL(coarse_dist_kernel<32>, grid, dim3(256), 0, h->stream, d_q, h->centroids.as<float>(),
-                               h->cdist.as<float>(), (int)nb, h->kc, h->d, h->d);
-        else
-            hipLaunchKernelGGL(coarse_dist_kernel<64>, grid, dim3(256), 0, h->stream, d_q, h->centroids.as<float>(),
-                               h->cdist.as<float>(), (int)nb, h->kc, h->d, h->d);
-    }
+    } else
+        launch_coarse_exact(h, d_q, nb, h->centroids.as<float>(), h->kc, h->cdist.as<float>(), true);
     HIP_TRY(hipGetLastError());
     if (h->profiling) TRY(ev_end(h, ep));
     return IVFADC_OK;
@@ -1297,18 +1326,8 @@ int run_twolevel(ivfadc_index *h, const float *d_q, int64_t nb, int w, int *d_pr
     TRY(h->tl_gdist.ensure((size_t)nb * G * 4));
     ivfadc_index::EvPair ep;
     if (h->profiling) TRY(ev_begin(h, 1, ep));
-    {
-        const int64_t wg64 = (int64_t)((G + CO_T - 1) / CO_T) * ((nb + 63) / 64);
-        const int tq = wg64 >= 4 * (int64_t)h->num_cu ? 64 : (2 * wg64 >= 4 * (int64_t)h->num_cu ? 32 : 16);
-        dim3 grid((G + CO_T - 1) / CO_T, (unsigned)((nb + tq - 1) / tq));
-        if (tq == 16)
-            hipLaunchKernelGGL(coarse_dist_kernel<16>, grid, dim3(256), 0, h->stream, d_q, h->tl_centres.as<float>(), h->tl_gdist.as<float>(), (int)nb, G, h->d, h->d);
-        else if (tq == 32)
-            hipLaunchKernelGGL(coarse_dist_kernel<32>, grid, dim3(256), 0, h->stream, d_q, h->tl_centres.as<float>(), h->tl_gdist.as<float>(), (int)nb, G, h->d, h->d);
-        else
-            hipLaunchKernelGGL(coarse_dist_kernel<64>, grid, dim3(256), 0, h->stream, d_q, h->tl_centres.as<float>(), h->tl_gdist.as<float>(), (int)nb, G, h->d, h->d);
-        HIP_TRY(hipGetLastError());
-    }
+    launch_coarse_exact(h, d_q, nb, h->tl_centres.as<float>(), G, h->tl_gdist.as<float>(), false);
+    HIP_TRY(hipGetLastError());
     TwoLevelView tv;
     tv.gdist = h->tl_gdist.as<float>();
     tv.g_off = h->tl_off.as<u32>();
@@ -1327,282 +1346,278 @@ int run_twolevel(ivfadc_index *h, const float *d_q, int64_t nb, int w, int *d_pr
     return IVFADC_OK;
 }
 
+// The stand-alone top-w selection over the n coarse rows in h->cdist (or the records run_coarse left instead): lists, distances and
+// visit-order bases of the w probes per query.  mfma: the rows are matrix-core scores (implies w <= 48: register selectors);
+// wpq4: a workgroup per query instead of a wave; lc: the probe histogram, where a grouped list-major scan follows
+int launch_topw(ivfadc_index *h, const float *d_q, int64_t n, int w, int capw, bool mfma, bool wpq4, int *out_list, float *out_dc, u32 *out_base,
+                u32 *lc, u64 *counters, int part_n, int part_i)
+{
+    const size_t lds = (size_t)4 * capw * 8;
+    void (*fn)(const float *, int, int, int, int, const u32 *, int *, float *, u32 *, u32 *, u64 *, const RefineArgs, int, int);
+    if (mfma)
+        fn = wpq4 ? topw_select_kernel<true, 4, true> : topw_select_kernel<true, 1, true>;
+    else if (w <= 64)
+        fn = wpq4 ? topw_select_kernel<true, 4, false> : topw_select_kernel<true, 1, false>;
+    else
+        fn = wpq4 ? topw_select_kernel<false, 4, false> : topw_select_kernel<false, 1, false>;
+    const unsigned grid = wpq4 ? (unsigned)n : (unsigned)((n + 3) / 4);
+    if (lds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)fn, lds, occ_unused, false)); }
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, h->stream, h->cdist.as<float>(), (int)n, h->kc, w, capw, h->list_len.as<u32>(), out_list,
+                       out_dc, out_base, lc, counters, refine_args(h, d_q), part_n, part_i);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+LbView lb_view(const ivfadc_index *h)
+{
+    LbView v;
+    v.cb_split = h->lb_split.as<uint4>();
+    v.cb_n2 = h->lb_n2.as<float>();
+    v.cb_lab = h->lb_lab.as<float>();
+    v.cb_maxn = h->lb_maxn.as<float>();
+    v.cb_f16 = (h->lb_use_f16 && h->lb_f16.p) ? h->lb_f16.as<uint4>() : (const uint4 *)nullptr;
+    v.cb_isc = h->lb_isc.as<float>();
+    v.mu = v.cb_f16 ? 1.48e-3f : 9.2e-5f;
+    return v;
+}
+
+// The probes of a sub-batch into probe_list / probe_dc / probe_base: the caller's (pre_list: index.jl:220-257 given the output of any
+// coarse_search -- the coarse stage and the top-w selection are one ingest launch), the two-level search's, or the coarse rows -- computed
+// here, or standing already (written by the previous search's launch behind a hint: ivfadc_set_next_queries) -- and, unless the scan
+// fuses it, the stand-alone top-w.  lc: the probe histogram (grouped list-major only)
+int probe_stage(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int w, bool single, u32 *lc, const int *pre_list, const float *pre_dc)
+{
+    const bool pre = pre_list != nullptr;
+    u64 *d_scanned = h->misc.as<u64>();          // 64 sharded counters
+    // one wave per query leaves the chip empty on small batches: the stand-alone top-w uses a workgroup per query there
+    const bool wpq4 = !pl.lanes && nb * 1 < (int64_t)8 * h->num_cu * 4 && h->kc >= 512 && !(pl.form == ScanForm::QueryMajorLb && !pl.fuse_topw);
+    const bool have_rows = single && !pre && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
+    h->avail_q = nullptr;
+    if (pre || pl.twolevel || have_rows) {
+        h->tmin_tiles = 0;
+        h->last_listed = false;
+    }
+    if (pre) {
+        hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, pre_list, pre_dc, (int)nb, h->kc, w,
+                           h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, (u32 *)nullptr,
+                           d_scanned);
+        HIP_TRY(hipGetLastError());
+    } else if (pl.twolevel) {
+        TRY(run_twolevel(h, d_q, nb, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, d_scanned));
+    } else if (have_rows) {
+        std::swap(h->cdist, h->cdist2);
+    } else {
+        TRY(run_coarse(h, d_q, nb, pl.coarse_mfma, pl.coarse_mfma && (pl.fuse_topw ? h->m > 16 : !wpq4),   // who reads them
+                       !pl.fuse_topw && !wpq4, w));
+    }
+    if (!pl.fuse_topw && !pl.twolevel && !pre)
+        TRY(launch_topw(h, d_q, nb, w, pl.capw, pl.coarse_mfma, wpq4, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc,
+                        d_scanned, h->part_n, h->part_i));
+    h->stats.last_rider = 0;
+    h->stats.coarse_prefetched = have_rows ? 1 : 0;
+    h->stats.last_twolevel = pl.twolevel ? 1 : 0;
+    h->stats.coarse_mfma = pl.coarse_mfma ? 1 : 0;
+    h->stats.coarse_f16 = (pl.coarse_mfma && h->last_coarse_f16 && !have_rows) ? 1 : 0;
+    h->stats.coarse_listed = h->last_listed ? 1 : 0;
+    return IVFADC_OK;
+}
+
+// query-major scan: a workgroup per query; single / pre: as search_subbatch's
+int scan_query_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
+                     bool single, bool pre)
+{
+    const int kc = h->kc;
+    const bool lb = pl.form == ScanForm::QueryMajorLb;
+    QScanArgs a;
+    a.ix = index_view(h);
+    a.queries = d_q;
+    a.nq = (int)nb; a.w = w; a.K = K; a.cap = pl.cap;
+    a.probe_list = h->probe_list.as<int>(); a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>();
+    a.out_ids = d_ids; a.out_dists = d_dists; a.out_counts = d_counts;
+    a.cdist = pl.fuse_topw ? h->cdist.as<float>() : (const float *)nullptr;
+    a.scanned_points = h->misc.as<u64>();
+    a.approx = pl.coarse_mfma ? 1 : 0;
+    a.rf = refine_args(h, d_q);
+    a.prune = h->allow_prune ? (pre ? 2 : 1) : 0;   // 2: ranks in the caller's order -- a list above the bound is skipped, the query goes on
+    a.lb = lb_view(h);
+    int occ = 0;
+    TRY(fn_occupancy(h, pl.fn, pl.lds, occ));
+    ivfadc_index::EvPair ep;
+    // riders: the hinted batch will take the exact small-problem coarse kernel whatever its K and w (no matrix-core filter at this kc)
+    const bool ride = single && !pre && !h->tl_use && h->hint_q != nullptr && h->hint_nq > 0 && !lb && pl.small_k && (h->d & 7) == 0 &&
+                      (!h->allow_mfma || kc < h->mfma_min_kc) && (h->hint_nq + 4 * RIDER_QW - 1) / (4 * RIDER_QW) <= 65535 &&
+                      (size_t)h->hint_nq * kc * 4 <= h->ws_budget / 4;
+    // a hinted next batch (ivfadc_set_next_queries): its exact coarse tiles ride behind this batch's scan in the same grid
+    qscan_coarse_fn_t fk = ride ? pick_qscan_coarse(h->m, h->dsub, pl.qg) : nullptr;
+    if (fk) {
+        TRY(h->cdist2.ensure((size_t)h->hint_nq * kc * 4));
+        CoarseNext cn;
+        cn.queries = h->hint_q; cn.out = h->cdist2.as<float>(); cn.nq = (int)h->hint_nq; cn.ncx = (kc + 63) / 64;
+        const size_t lds = std::max<size_t>(pl.lds, (size_t)64 * 132 * 4);
+        TRY(fn_raise_lds(h->device, (const void *)fk, lds, true));
+        const unsigned grid = (unsigned)(nb + (int64_t)cn.ncx * ((h->hint_nq + 4 * RIDER_QW - 1) / (4 * RIDER_QW)));
+        if (h->hint_ev) {   // the hinted rows' ingest (ivfadc_search_batches): in front of the one launch that reads them
+            HIP_TRY(hipStreamWaitEvent(h->stream, h->hint_ev, 0));
+            h->hint_ev = nullptr;
+        }
+        if (h->profiling) TRY(ev_begin(h, 0, ep));
+        hipLaunchKernelGGL(fk, dim3(grid), dim3(256), lds, h->stream, a, cn);
+        HIP_TRY(hipGetLastError());
+        if (h->profiling) TRY(ev_end(h, ep));
+        h->pf_q = h->hint_q;
+        h->pf_nq = h->hint_nq;
+        h->pf_token = h->hint_token;
+        h->stats.last_rider = 1;
+    } else {
+        if (h->profiling) TRY(ev_begin(h, 0, ep));
+        hipLaunchKernelGGL((qscan_fn_t)pl.fn, dim3((unsigned)nb), dim3(pl.threads), pl.lds, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        if (h->profiling) TRY(ev_end(h, ep));
+    }
+    h->stats.last_scan_grid = (int)nb;
+    if (!lb) TRY(fb_snapshot(h));
+    if (h->profiling_level >= 2 && lb && !pl.fuse_topw && pl.qg == 4) {
+        // the table build alone, over the probes this batch used (measurement only)
+        void (*bk)(const IndexView, const LbView, const float *, const int *, int, u32 *) =
+            (h->m == 48) ? lb_build_only_kernel<48, 16, 4> : lb_build_only_kernel<16, 6, 4>;
+        TRY(fn_raise_lds(h->device, (const void *)bk, pl.lds, false));
+        TRY(h->dbg.ensure((size_t)nb * 4));
+        ivfadc_index::EvPair eb;
+        TRY(ev_begin(h, 2, eb));
+        hipLaunchKernelGGL(bk, dim3((unsigned)nb), dim3(256), pl.lds, h->stream, a.ix, a.lb, d_q, h->probe_list.as<int>(), w,
+                           h->dbg.as<u32>());
+        HIP_TRY(hipGetLastError());
+        TRY(ev_end(h, eb));
+    }
+    return IVFADC_OK;
+}
+
+// One list-major scan launch, whichever the kernel: a persistent grid of as many workgroups as fit the chip, at most one per work item
+// (upper), between the profiling events of the scan; fn is pl.fn under its own type, extra what it takes behind the ScanArgs
+template <class... P, class... X>
+int launch_list_scan(ivfadc_index *h, const Plan &pl, size_t upper, void (*fn)(const ScanArgs, P...), const ScanArgs &a, X... extra)
+{
+    int occ = 0;
+    TRY(fn_occupancy(h, pl.fn, pl.lds, occ, true, pl.threads));   // (occupancy is clamped to 8 workgroups per CU)
+    const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
+    ivfadc_index::EvPair ep;
+    if (h->profiling) TRY(ev_begin(h, 0, ep));
+    hipLaunchKernelGGL(fn, dim3(grid), dim3(pl.threads), pl.lds, h->stream, a, extra...);
+    HIP_TRY(hipGetLastError());
+    if (h->profiling) TRY(ev_end(h, ep));
+    h->stats.last_scan_grid = (int)grid;
+    return IVFADC_OK;
+}
+
+// list-major scan: work items from the probe histogram (direct: one per (query, probe, chunk), nothing to group), the form's kernel,
+// and the merge of the partial results
+int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
+                    bool direct)
+{
+    const int kc = h->kc;
+    const size_t np = (size_t)nb * w;
+    const bool w8 = pl.form == ScanForm::EightWave;
+    u32 *d_qhead = (u32 *)((char *)h->misc.p + 4096);
+    TRY(h->bucket_items.ensure(np * 4));
+    TRY(h->part_keys.ensure(np * pl.maxch * K * 8));
+    TRY(h->part_cnt.ensure(np * pl.maxch * 4));
+    {
+        const size_t before = h->qthr.bytes;
+        TRY(h->qthr.ensure((size_t)nb * 8));
+        if (h->qthr.bytes != before) h->qthr_armed = 0;
+        if (h->qthr_armed < (size_t)nb) {
+            const size_t cnt = h->qthr.bytes / 8;
+            hipLaunchKernelGGL(fill_u64_kernel, dim3(256), dim3(256), 0, h->stream, h->qthr.as<u64>(), cnt, (u64)KEY_MAX);
+            HIP_TRY(hipGetLastError());
+            h->qthr_armed = cnt;
+        }
+    }
+    if (!direct) {
+        u32 *item_list = nullptr;
+        if (w8) {
+            TRY(h->wg8_items.ensure(np * (size_t)pl.maxch * 4));
+            item_list = h->wg8_items.as<u32>();
+        }
+        hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->list_cnt.as<u32>(), h->list_len.as<u32>(),
+                           kc, pl.qg, pl.CH, h->bucket_off.as<u32>(), h->wi_off.as<u32>(), h->cursor.as<u32>(), d_qhead, item_list);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(bucket_scatter_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream,
+                           h->probe_list.as<int>(), (int)np, h->bucket_off.as<u32>(), h->cursor.as<u32>(), h->bucket_items.as<u32>(),
+                           h->part_n, h->part_i);
+        HIP_TRY(hipGetLastError());
+    }
+
+    ScanArgs a;
+    a.ix = index_view(h);
+    a.queries = d_q;
+    a.w = w; a.K = K; a.cap = pl.cap;
+    a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>(); a.list_cnt = h->list_cnt.as<u32>();
+    a.bucket_off = h->bucket_off.as<u32>(); a.wi_off = h->wi_off.as<u32>(); a.bucket_items = h->bucket_items.as<u32>();
+    a.queue_head = d_qhead;
+    a.qthr = h->qthr.as<u64>();
+    a.part_keys = h->part_keys.as<u64>(); a.part_cnt = h->part_cnt.as<u32>(); a.maxch = pl.maxch; a.CH = pl.CH;
+    a.probe_list = h->probe_list.as<int>();
+    a.direct_items = direct ? (u32)(np * (size_t)pl.maxch) : 0u;
+    a.prune = h->allow_prune ? 1 : 0;
+    a.scanned_points = h->misc.as<u64>();
+
+    const size_t upper = np * (size_t)pl.maxch;
+    if (w8) {
+        u32 *xq = nullptr;
+        TRY(clear_xcd_heads(h, xq));
+        // (the larger form of the handle's m: eight queries)
+        TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * (h->m == 16 ? W8_GTAB_FLOATS<8, 16> : W8_GTAB_FLOATS<8>) * 4));
+        TRY(launch_list_scan(h, pl, upper, (wg8_fn_t)pl.fn, a, h->wg8_tabs.as<float>(), h->wg8_items.as<u32>(), xq, 8));
+    } else if (pl.form == ScanForm::NarrowField) {
+        NfView nv;
+        nv.n2 = h->nf_n2.as<float>();
+        nv.cb_lab = h->nf_lab.as<float>();
+        nv.maxn2 = h->nf_n2.as<float>() + (size_t)h->m * 256;
+        nv.nranges = 8;
+        TRY(clear_xcd_heads(h, nv.xq));
+        TRY(launch_list_scan(h, pl, upper, (nf_fn_t)pl.fn, a, nv));
+    } else if (pl.form == ScanForm::FourWave) {
+        TRY(launch_list_scan(h, pl, upper, (scan_fn_t)pl.fn, a));
+    } else {
+        TRY(launch_list_scan(h, pl, upper, (u16_fn_t)pl.fn, a, pl.qg));
+    }
+
+    const size_t mlds = pl.small_k ? 0 : (size_t)4 * pl.cap * 8;
+    auto mk = pl.small_k ? merge_kernel<true> : merge_kernel<false>;
+    if (mlds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)mk, mlds, occ_unused, false)); }
+    hipLaunchKernelGGL(mk, dim3((unsigned)((nb + 3) / 4)), dim3(256), mlds, h->stream, (int)nb, w, K, pl.cap, pl.maxch, pl.CH, kc,
+                       h->probe_list.as<int>(), h->probe_base.as<u32>(), h->list_pos.as<int64_t>(), h->list_len.as<u32>(),
+                       h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>(), h->part_keys.as<u64>(), h->part_cnt.as<u32>(), d_ids, d_dists,
+                       d_counts, h->qthr.as<u64>(), h->list_cnt.as<u32>(), d_qhead, h->part_n, h->part_i, (u64 *)h->partial_keys);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
 int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids,
                     float *d_dists, int32_t *d_counts, bool single,   // single: the call's whole batch (hints and prefetched rows apply)
                     const int *pre_list = nullptr, const float *pre_dc = nullptr)   // the caller's probes of these nb queries (ivfadc_search_preassigned)
 {
-    const bool pre = pre_list != nullptr;
-    const int kc = h->kc;
+    const bool qm = pl.query_major();
     const size_t np = (size_t)nb * w;
     TRY(ensure_common_ws(h));
     TRY(h->probe_list.ensure(np * 4));
     TRY(h->probe_dc.ensure(np * 4));
     TRY(h->probe_base.ensure(np * 4));
-    u64 *d_scanned = h->misc.as<u64>();          // 64 sharded counters
-    u32 *d_qhead = (u32 *)((char *)h->misc.p + 4096);
     // list-major with one query per code stream: every (query, probe) pair is a work item of its own, nothing to group
     // by list -- no probe histogram, no bucket kernels
-    const bool direct = !pl.query_major && pl.qg == 1 && np * (size_t)pl.maxch < ((size_t)1 << 31) && h->part_n <= 1;
-
-    // one wave per query leaves the chip empty on small batches: the stand-alone top-w uses a workgroup per query there
-    const bool wpq4 = !pl.lanes && nb * 1 < (int64_t)8 * h->num_cu * 4 && h->kc >= 512 && !(pl.lb && !pl.fuse_topw);
-    // the rows of these very queries may stand already: written by the previous search's launch behind a hint (ivfadc_set_next_queries)
-    const bool have_rows = single && !pre && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
-    h->avail_q = nullptr;
-    h->stats.last_rider = 0;
-    h->stats.coarse_prefetched = have_rows ? 1 : 0;
-    h->stats.last_twolevel = pl.twolevel ? 1 : 0;
-    if (pre) {
-        // index.jl:220-257 given the output of any coarse_search: the coarse stage and the top-w selection are this one launch
-        u32 *lc = (pl.query_major || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>();
-        hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, pre_list, pre_dc, (int)nb, kc, w,
-                           h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, (u32 *)nullptr,
-                           d_scanned);
-        HIP_TRY(hipGetLastError());
-        h->tmin_tiles = 0;
-        h->last_listed = false;
-    } else if (pl.twolevel) {
-        u32 *lc = (pl.query_major || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>();
-        TRY(run_twolevel(h, d_q, nb, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, d_scanned));
-        h->tmin_tiles = 0;
-        h->last_listed = false;
-    } else if (have_rows) {
-        std::swap(h->cdist, h->cdist2);
-        h->tmin_tiles = 0;
-        h->last_listed = false;
-    } else {
-        TRY(run_coarse(h, d_q, nb, pl.coarse_mfma, pl.coarse_mfma && (pl.fuse_topw ? h->m > 16 : !wpq4),   // who reads them
-                       !pl.fuse_topw && !wpq4, w));
-    }
-    // riders: the hinted batch will take the exact small-problem coarse kernel whatever its K and w (no matrix-core filter at this kc)
-    const bool ride = single && !pre && !h->tl_use && h->hint_q != nullptr && h->hint_nq > 0 && pl.query_major && !pl.lb && pl.small_k && (h->d & 7) == 0 &&
-                      (!h->allow_mfma || kc < h->mfma_min_kc) && (h->hint_nq + 4 * RIDER_QW - 1) / (4 * RIDER_QW) <= 65535 &&
-                      (size_t)h->hint_nq * kc * 4 <= h->ws_budget / 4;
-
-    if (!pl.fuse_topw && !pl.twolevel && !pre) {
-        u32 *lc = (pl.query_major || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>();   // probe histogram: grouped list-major only
-        const size_t lds = (size_t)4 * pl.capw * 8;
-        void (*fn)(const float *, int, int, int, int, const u32 *, int *, float *, u32 *, u32 *, u64 *, const RefineArgs, int, int);
-        if (pl.coarse_mfma)   // implies w <= 48: register selectors
-            fn = wpq4 ? topw_select_kernel<true, 4, true> : topw_select_kernel<true, 1, true>;
-        else if (pl.small_w)
-            fn = wpq4 ? topw_select_kernel<true, 4, false> : topw_select_kernel<true, 1, false>;
-        else
-            fn = wpq4 ? topw_select_kernel<false, 4, false> : topw_select_kernel<false, 1, false>;
-        const unsigned grid = wpq4 ? (unsigned)nb : (unsigned)((nb + 3) / 4);
-        if (lds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)fn, lds, occ_unused, false)); }
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, h->stream, h->cdist.as<float>(), (int)nb, kc, w, pl.capw,
-                           h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc,
-                           d_scanned, refine_args(h, d_q), h->part_n, h->part_i);
-        HIP_TRY(hipGetLastError());
-    }
-    h->stats.last_qg = pl.query_major ? 0 : pl.qg;
-    h->stats.coarse_mfma = pl.coarse_mfma ? 1 : 0;
-    h->stats.coarse_f16 = (pl.coarse_mfma && h->last_coarse_f16 && !have_rows) ? 1 : 0;
-    h->stats.coarse_listed = h->last_listed ? 1 : 0;
+    const bool direct = !qm && pl.qg == 1 && np * (size_t)pl.maxch < ((size_t)1 << 31) && h->part_n <= 1;
+    TRY(probe_stage(h, pl, nb, d_q, w, single, (qm || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>(), pre_list, pre_dc));
+    // what the plan runs (last_lb: of the latest query-major scan; last_striped, last_nf: of the latest list-major one)
+    h->stats.last_qg = qm ? 0 : pl.qg;
     h->stats.last_chunk = (int)pl.CH;
     h->stats.last_scan_lds = (int)pl.lds;
-
-    if (pl.query_major) {
-        QScanArgs a;
-        a.ix = index_view(h);
-        a.queries = d_q;
-        a.nq = (int)nb; a.w = w; a.K = K; a.cap = pl.cap;
-        a.probe_list = h->probe_list.as<int>();
-        a.probe_dc = h->probe_dc.as<float>();
-        a.probe_base = h->probe_base.as<u32>();
-        a.out_ids = d_ids;
-        a.out_dists = d_dists;
-        a.out_counts = d_counts;
-        a.cdist = pl.fuse_topw ? h->cdist.as<float>() : (const float *)nullptr;
-        a.scanned_points = d_scanned;
-        a.approx = pl.coarse_mfma ? 1 : 0;
-        a.rf = refine_args(h, d_q);
-        a.prune = h->allow_prune ? (pre ? 2 : 1) : 0;   // 2: ranks in the caller's order -- a list above the bound is skipped, the query goes on
-        a.lb.cb_split = h->lb_split.as<uint4>();
-        a.lb.cb_n2 = h->lb_n2.as<float>();
-        a.lb.cb_lab = h->lb_lab.as<float>();
-        a.lb.cb_maxn = h->lb_maxn.as<float>();
-        a.lb.cb_f16 = (h->lb_use_f16 && h->lb_f16.p) ? h->lb_f16.as<uint4>() : (const uint4 *)nullptr;
-        a.lb.cb_isc = h->lb_isc.as<float>();
-        a.lb.mu = a.lb.cb_f16 ? 1.48e-3f : 9.2e-5f;
-        h->stats.last_lb = pl.lb ? 1 : 0;
-        qscan_fn_t fn = pl.lb ? pick_qscan_lb(h->m, h->dsub, pl.qg) : pick_qscan(h->m, h->dsub, pl.qg, pl.small_k);
-        int occ = 0;
-        TRY(fn_occupancy(h, (const void *)fn, pl.lds, occ));
-        ivfadc_index::EvPair ep;
-        // a hinted next batch (ivfadc_set_next_queries): its exact coarse tiles ride behind this batch's scan in the same grid
-        void (*fk)(const QScanArgs, const CoarseNext) = nullptr;
-        if (ride) fk = pick_qscan_coarse(h->m, h->dsub, pl.qg);
-        if (fk) {
-            TRY(h->cdist2.ensure((size_t)h->hint_nq * kc * 4));
-            CoarseNext cn;
-            cn.queries = h->hint_q; cn.out = h->cdist2.as<float>(); cn.nq = (int)h->hint_nq; cn.ncx = (kc + 63) / 64;
-            const size_t lds = std::max<size_t>(pl.lds, (size_t)64 * 132 * 4);
-            TRY(fn_raise_lds(h->device, (const void *)fk, lds, true));
-            const unsigned grid = (unsigned)(nb + (int64_t)cn.ncx * ((h->hint_nq + 4 * RIDER_QW - 1) / (4 * RIDER_QW)));
-            if (h->hint_ev) {   // the hinted rows' ingest (ivfadc_search_batches): in front of the one launch that reads them
-                HIP_TRY(hipStreamWaitEvent(h->stream, h->hint_ev, 0));
-                h->hint_ev = nullptr;
-            }
-            if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(fk, dim3(grid), dim3(256), lds, h->stream, a, cn);
-            HIP_TRY(hipGetLastError());
-            if (h->profiling) TRY(ev_end(h, ep));
-            h->pf_q = h->hint_q;
-            h->pf_nq = h->hint_nq;
-            h->pf_token = h->hint_token;
-            h->stats.last_rider = 1;
-        } else {
-            if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(256), pl.lds, h->stream, a);
-            HIP_TRY(hipGetLastError());
-            if (h->profiling) TRY(ev_end(h, ep));
-        }
-        h->stats.last_scan_grid = (int)nb;
-        if (!pl.lb) TRY(fb_snapshot(h));
-        if (h->profiling_level >= 2 && pl.lb && !pl.fuse_topw && pl.qg == 4) {
-            // the table build alone, over the probes this batch used (measurement only)
-            void (*bk)(const IndexView, const LbView, const float *, const int *, int, u32 *) =
-                (h->m == 48) ? lb_build_only_kernel<48, 16, 4> : lb_build_only_kernel<16, 6, 4>;
-            TRY(fn_raise_lds(h->device, (const void *)bk, pl.lds, false));
-            TRY(h->dbg.ensure((size_t)nb * 4));
-            ivfadc_index::EvPair eb;
-            TRY(ev_begin(h, 2, eb));
-            hipLaunchKernelGGL(bk, dim3((unsigned)nb), dim3(256), pl.lds, h->stream, a.ix, a.lb, d_q, h->probe_list.as<int>(), w,
-                               h->dbg.as<u32>());
-            HIP_TRY(hipGetLastError());
-            TRY(ev_end(h, eb));
-        }
+    if (qm) {
+        h->stats.last_lb = pl.form == ScanForm::QueryMajorLb ? 1 : 0;
+        TRY(scan_query_major(h, pl, nb, d_q, K, w, d_ids, d_dists, d_counts, single, pre_list != nullptr));
     } else {
-        TRY(h->bucket_items.ensure(np * 4));
-        TRY(h->part_keys.ensure(np * pl.maxch * K * 8));
-        TRY(h->part_cnt.ensure(np * pl.maxch * 4));
-        {
-            const size_t before = h->qthr.bytes;
-            TRY(h->qthr.ensure((size_t)nb * 8));
-            if (h->qthr.bytes != before) h->qthr_armed = 0;
-            if (h->qthr_armed < (size_t)nb) {
-                const size_t cnt = h->qthr.bytes / 8;
-                hipLaunchKernelGGL(fill_u64_kernel, dim3(256), dim3(256), 0, h->stream, h->qthr.as<u64>(), cnt, (u64)KEY_MAX);
-                HIP_TRY(hipGetLastError());
-                h->qthr_armed = cnt;
-            }
-        }
-        if (!direct) {
-            u32 *item_list = nullptr;
-            if (pl.wg8) {
-                TRY(h->wg8_items.ensure(np * (size_t)pl.maxch * 4));
-                item_list = h->wg8_items.as<u32>();
-            }
-            hipLaunchKernelGGL(bucket_scan_kernel, dim3(1), dim3(1024), 0, h->stream, h->list_cnt.as<u32>(), h->list_len.as<u32>(),
-                               kc, pl.qg, pl.CH, h->bucket_off.as<u32>(), h->wi_off.as<u32>(), h->cursor.as<u32>(), d_qhead, item_list);
-            HIP_TRY(hipGetLastError());
-            hipLaunchKernelGGL(bucket_scatter_kernel, dim3((unsigned)((np + 255) / 256)), dim3(256), 0, h->stream,
-                               h->probe_list.as<int>(), (int)np, h->bucket_off.as<u32>(), h->cursor.as<u32>(), h->bucket_items.as<u32>(),
-                               h->part_n, h->part_i);
-            HIP_TRY(hipGetLastError());
-        }
-
-        ScanArgs a;
-        a.ix = index_view(h);
-        a.queries = d_q;
-        a.w = w; a.K = K; a.cap = pl.cap;
-        a.probe_dc = h->probe_dc.as<float>();
-        a.probe_base = h->probe_base.as<u32>();
-        a.list_cnt = h->list_cnt.as<u32>();
-        a.bucket_off = h->bucket_off.as<u32>();
-        a.wi_off = h->wi_off.as<u32>();
-        a.bucket_items = h->bucket_items.as<u32>();
-        a.queue_head = d_qhead;
-        a.qthr = h->qthr.as<u64>();
-        a.part_keys = h->part_keys.as<u64>();
-        a.part_cnt = h->part_cnt.as<u32>();
-        a.maxch = pl.maxch;
-        a.CH = pl.CH;
-        a.probe_list = h->probe_list.as<int>();
-        a.direct_items = direct ? (u32)(np * (size_t)pl.maxch) : 0u;
-        a.prune = h->allow_prune ? 1 : 0;
-        a.scanned_points = d_scanned;
-
-        const bool stripe = h->allow_filt && filt_shape(h->m, h->dsub) && pl.qg == 4 && h->ksub == 256;
-        h->stats.last_striped = stripe ? 1 : 0;
-        h->stats.last_nf = pl.nf ? 1 : 0;
-        const size_t upper = np * (size_t)pl.maxch;
-        ivfadc_index::EvPair ep;
-        if (h->u16) {
-            void (*uk)(const ScanArgs, int) = pl.small_k ? u16_scan_kernel : u16_wide_scan_kernel;
-            int occ = 0;
-            TRY(fn_occupancy(h, (const void *)uk, pl.lds, occ));
-            const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-            if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(uk, dim3(grid), dim3(256), pl.lds, h->stream, a, pl.qg);
-            HIP_TRY(hipGetLastError());
-            if (h->profiling) TRY(ev_end(h, ep));
-            h->stats.last_scan_grid = (int)grid;
-            h->stats.last_striped = 0;
-        } else if (pl.wg8 && !direct) {
-            wg8_fn_t wk = pl.wg8wide ? (h->m == 8 ? pick_wg8_wide(pl.wg8q8, h->dsub) : nullptr) : pick_wg8(pl.wg8q8, h->m, h->dsub);
-            if (!wk) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for m = %d, dsub = %d, which has no instantiation", h->m, h->dsub);
-            u32 *xq = (u32 *)((char *)h->misc.p + 4096 + 256);     // eight queue heads, 64 B apart (as the narrow-field kernel's)
-            HIP_TRY(hipMemsetAsync(xq, 0, 512, h->stream));
-            int occ = 0;
-            TRY(fn_occupancy(h, (const void *)wk, pl.lds, occ, true, W8_THREADS));
-            const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-            // (occupancy is clamped to 8 workgroups per CU; the larger form of the handle's m: eight queries)
-            TRY(h->wg8_tabs.ensure((size_t)h->num_cu * 8 * (h->m == 16 ? W8_GTAB_FLOATS<8, 16> : W8_GTAB_FLOATS<8>) * 4));
-            if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(wk, dim3(grid), dim3(W8_THREADS), pl.lds, h->stream, a, h->wg8_tabs.as<float>(), h->wg8_items.as<u32>(), xq, 8);
-            HIP_TRY(hipGetLastError());
-            if (h->profiling) TRY(ev_end(h, ep));
-            h->stats.last_scan_grid = (int)grid;
-            h->stats.last_striped = (pl.wg8wide ? 4 : 2) + (pl.wg8q8 ? 1 : 0);
-        } else if (pl.nf) {
-            // four points per lane and step (measured: two 9.2 ms, eight 8.1 ms -- and 74 spilled registers -- against 7.76 ms)
-            void (*nk)(const ScanArgs, const NfView) = nf_scan_kernel<4>;
-            NfView nv;
-            nv.n2 = h->nf_n2.as<float>();
-            nv.cb_lab = h->nf_lab.as<float>();
-            nv.maxn2 = h->nf_n2.as<float>() + (size_t)h->m * 256;
-            nv.xq = (u32 *)((char *)h->misc.p + 4096 + 256);
-            nv.nranges = 8;
-            HIP_TRY(hipMemsetAsync(nv.xq, 0, 512, h->stream));
-            int occ = 0;
-            TRY(fn_occupancy(h, (const void *)nk, pl.lds, occ));
-            const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-            if (h->profiling) TRY(ev_begin(h, 0, ep));
-            hipLaunchKernelGGL(nk, dim3(grid), dim3(256), pl.lds, h->stream, a, nv);
-            HIP_TRY(hipGetLastError());
-            if (h->profiling) TRY(ev_end(h, ep));
-            h->stats.last_scan_grid = (int)grid;
-        } else {
-        scan_fn_t fn = pick_scan(h->m, h->dsub, pl.qg, pl.small_k, stripe);
-        int occ = 0;
-        TRY(fn_occupancy(h, (const void *)fn, pl.lds, occ));
-        const unsigned grid = (unsigned)std::max<size_t>(1, std::min<size_t>(upper, (size_t)h->num_cu * occ));
-        if (h->profiling) TRY(ev_begin(h, 0, ep));
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), pl.lds, h->stream, a);
-        HIP_TRY(hipGetLastError());
-        if (h->profiling) TRY(ev_end(h, ep));
-        h->stats.last_scan_grid = (int)grid;
-        }
-
-        const size_t mlds = pl.small_k ? 0 : (size_t)4 * pl.cap * 8;
-        const u32 *idp = h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>();
-        if (mlds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)merge_kernel<false>, mlds, occ_unused, false)); }
-        if (pl.small_k)
-            hipLaunchKernelGGL(merge_kernel<true>, dim3((unsigned)((nb + 3) / 4)), dim3(256), mlds, h->stream, (int)nb, w, K, pl.cap,
-                               pl.maxch, pl.CH, kc, h->probe_list.as<int>(), h->probe_base.as<u32>(), h->list_pos.as<int64_t>(),
-                               h->list_len.as<u32>(), idp,
-                               h->part_keys.as<u64>(), h->part_cnt.as<u32>(), d_ids, d_dists, d_counts, h->qthr.as<u64>(),
-                               h->list_cnt.as<u32>(), d_qhead, h->part_n, h->part_i, (u64 *)h->partial_keys);
-        else
-            hipLaunchKernelGGL(merge_kernel<false>, dim3((unsigned)((nb + 3) / 4)), dim3(256), mlds, h->stream, (int)nb, w, K, pl.cap,
-                               pl.maxch, pl.CH, kc, h->probe_list.as<int>(), h->probe_base.as<u32>(), h->list_pos.as<int64_t>(),
-                               h->list_len.as<u32>(), idp,
-                               h->part_keys.as<u64>(), h->part_cnt.as<u32>(), d_ids, d_dists, d_counts, h->qthr.as<u64>(),
-                               h->list_cnt.as<u32>(), d_qhead, h->part_n, h->part_i, (u64 *)h->partial_keys);
-        HIP_TRY(hipGetLastError());
+        h->stats.last_striped = pl.striped();
+        h->stats.last_nf = pl.form == ScanForm::NarrowField ? 1 : 0;
+        TRY(scan_list_major(h, pl, nb, d_q, K, w, d_ids, d_dists, d_counts, direct));
     }
     h->stats.queries += nb;
     if (h->profiling && h->pending.size() > 2048) TRY(ev_fold(h));
@@ -2114,11 +2129,8 @@ int coarse_dev(ivfadc_index *h, int64_t nq, const float *d_q, int w, int32_t *d_
     const int kc = h->kc;
     u64 *d_sink = (u64 *)((char *)h->misc.p + MISC_SINK);
     const bool generic = w > IVFADC_MAX_W;
-    const bool small_w = w <= 64;
-    const int capw = small_w ? 64 : std::max(128, pow2ceil(w + 64));
-    const bool twolevel = !generic && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 &&
-                          (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
-    const bool mfma = !generic && !twolevel && h->allow_mfma && w <= 48 && kc >= h->mfma_min_kc && (h->d & 3) == 0;
+    const CoarseForm cf = coarse_form(h, w, !generic, true);   // (any batch size: the sub-batches below are clamped to the two-level kernel's)
+    const bool twolevel = cf.twolevel, mfma = cf.mfma;
     // sub-batches: the distance rows (generic: + two key rows) stay inside the workspace budget
     const size_t per_q = (twolevel ? (size_t)h->tl_G : (size_t)kc) * (generic ? 20 : 4) + (size_t)w * 4 + 64;
     int64_t nb = (int64_t)std::max<size_t>(generic ? 1 : 64, h->ws_budget / per_q);
@@ -2147,19 +2159,7 @@ int coarse_dev(ivfadc_index *h, int64_t nq, const float *d_q, int w, int32_t *d_
         }
         const bool wpq4 = n < (int64_t)8 * h->num_cu * 4 && kc >= 512;   // (search_subbatch: a workgroup per query on small batches)
         TRY(run_coarse(h, q, n, mfma, mfma && !wpq4, !wpq4, w));
-        const size_t lds = (size_t)4 * capw * 8;
-        void (*fn)(const float *, int, int, int, int, const u32 *, int *, float *, u32 *, u32 *, u64 *, const RefineArgs, int, int);
-        if (mfma)
-            fn = wpq4 ? topw_select_kernel<true, 4, true> : topw_select_kernel<true, 1, true>;
-        else if (small_w)
-            fn = wpq4 ? topw_select_kernel<true, 4, false> : topw_select_kernel<true, 1, false>;
-        else
-            fn = wpq4 ? topw_select_kernel<false, 4, false> : topw_select_kernel<false, 1, false>;
-        const unsigned grid = wpq4 ? (unsigned)n : (unsigned)((n + 3) / 4);
-        if (lds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)fn, lds, occ_unused, false)); }
-        hipLaunchKernelGGL(fn, dim3(grid), dim3(256), lds, h->stream, h->cdist.as<float>(), (int)n, kc, w, capw, h->list_len.as<u32>(), ol, od,
-                           h->probe_base.as<u32>(), (u32 *)nullptr, d_sink, refine_args(h, q), 1, 0);
-        HIP_TRY(hipGetLastError());
+        TRY(launch_topw(h, q, n, w, sel_cap(w), mfma, wpq4, ol, od, h->probe_base.as<u32>(), nullptr, d_sink, 1, 0));
         h->stats.coarse_f16 = (mfma && h->last_coarse_f16) ? 1 : 0;
         h->stats.coarse_listed = h->last_listed ? 1 : 0;
     }
@@ -4767,20 +4767,12 @@ try {
     if (rc == IVFADC_OK) {
         hipError_t e = hipMemcpyAsync(dq.p, query, (size_t)h->d * 4, hipMemcpyHostToDevice, h->stream);
         if (e == hipSuccess) {
-            QScanArgs a;
-            a.lb.cb_split = h->lb_split.as<uint4>();
-            a.lb.cb_n2 = h->lb_n2.as<float>();
-            a.lb.cb_lab = h->lb_lab.as<float>();
-            a.lb.cb_maxn = h->lb_maxn.as<float>();
-        a.lb.cb_f16 = (h->lb_use_f16 && h->lb_f16.p) ? h->lb_f16.as<uint4>() : (const uint4 *)nullptr;
-        a.lb.cb_isc = h->lb_isc.as<float>();
-        a.lb.mu = a.lb.cb_f16 ? 1.48e-3f : 9.2e-5f;
             const size_t lds = lb_lds_bytes(m, h->dsub, 1);
             void (*dk)(const IndexView, const LbView, const float *, int, unsigned char *, float *) =
                 (m == 48) ? lb_debug_kernel<48, 16> : lb_debug_kernel<16, 6>;
             rc = fn_raise_lds(h->device, (const void *)dk, lds, false);
             if (rc == IVFADC_OK) {
-                hipLaunchKernelGGL(dk, dim3(1), dim3(256), lds, h->stream, index_view(h), a.lb, dq.as<float>(), cell, dt.as<unsigned char>(),
+                hipLaunchKernelGGL(dk, dim3(1), dim3(256), lds, h->stream, index_view(h), lb_view(h), dq.as<float>(), cell, dt.as<unsigned char>(),
                                    df.as<float>());
                 e = hipGetLastError();
             }
