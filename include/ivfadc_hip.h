@@ -87,7 +87,10 @@ int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
  * ivfadc_set_table_mode(h, 10) the scan kernel also serves 64 < K through LDS selectors wherever
  *     32 (m dsp + qg cap) + 32 912 B <= 160 KB,  dsp = dsub rounded up to 4, cap = max(128, pow2ceil(K + 64)), qg = pairs per work item,
  * holds at qg = 1 (the plan halves qg until it holds: m dsp + qg cap <= 4091).  That is K <= 1984 for m dsp <= 2040, K <= 960 up to 3064,
- * K <= 448 up to 3576, K <= 192 up to 3832; any other K > 64 takes the generic path as in mode 0 (stats.last_qg == -2).        */
+ * K <= 448 up to 3576, K <= 192 up to 3832; any other K > 64 takes the generic path as in mode 0 (stats.last_qg == -2).
+ * ivfadc_set_u16_tables(h, 1 / 2) replaces the per-pass ADC tables by sums straight from the codebook (below); without a 32 KB table
+ * area its wide form reaches m dsp + qg cap <= 5115: K <= 1984 for m dsp <= 3064, K <= 960 up to 4088, K <= 448 up to 4600,
+ * K <= 192 up to 4856, and K <= IVFADC_MAX_K (cap = 4096) for m dsp <= 1016.                                                 */
 /* As ivfadc_create, for U = UInt16: 1 <= ksub <= 65536, code_labels is m x ksub uint16_t (distinct within a block).  Validation runs
  * before any device call.                                                                                                  */
 int ivfadc_create_u16(ivfadc_t **out, int device, int d, int kc, int m, int ksub,
@@ -403,7 +406,9 @@ typedef struct {
                                 * m = 8, dsub = 4 / 8 / 12 / 16, K <= 64; m = 16, dsub = 4 / 8, K <= 64 through table modes 6 / 7 only),
                                 * four / eight queries per code stream; 4 / 5 = its wide-pool
                                 * form (m = 8, 64 < K <= 128; table modes 8 / 9), four / eight queries per code stream -- also what a rank
-                                * of the list-partitioned mode reports (ivfadc_set_list_partition) */
+                                * of the list-partitioned mode reports (ivfadc_set_list_partition); 6 / 7 = the table-free scan of a
+                                * 16-bit handle (ivfadc_set_u16_tables), register selectors (K <= 64) / LDS selectors (64 < K); the
+                                * table forms of a 16-bit handle report 0 */
     int32_t  coarse_listed;    /* 1: the last batch's coarse filter wrote per-tile records (four smallest keys of every
                                 * (query, 64-centroid tile)) instead of the score matrix, and the top-w enumerated them */
     int64_t  pruned_points;    /* points of probed lists that were NOT scanned: the list's coarse distance already lay above
@@ -510,6 +515,17 @@ int ivfadc_set_query_token(ivfadc_t *h, uint64_t token);
  * handle 10 plans exactly what 0 plans.  Results are identical in every mode: whatever a filter lets through is recomputed in the reference's
  * order -- from the f32 tables or, in the matrix-core rounds, from the f32 codebook -- before it meets the bound.       */
 int ivfadc_set_table_mode(ivfadc_t *h, int mode);
+
+/* ADC tables of a 16-bit handle: 0 (default) = per-pass tables of all ksub codewords (u16_scan_kernel / u16_wide_scan_kernel);
+ * 1 = table-free wherever it is served; 2 = table-free where the rule below expects it to win.  An 8-bit handle accepts the call and
+ * plans what it planned before.  Results are identical in every mode.
+ * Table-free (u16_direct_scan_kernel, K <= 64; u16_direct_wide_scan_kernel, 64 < K under ivfadc_set_table_mode(h, 10)): every point
+ * gathers the codeword its code names and forms that one entry itself, in the entry's own accumulator and order (the same bits), so the
+ * cost follows the points probed (len x d per pair and list), not the codebook (ksub x d per pair and pass of 1024 points).
+ * Rule of mode 2: table-free iff min(n / kc, 1024) x U16_DIRECT_COST <= ksub (u16scan.hip.h; measured: DESIGN.md 4.7a).
+ * stats.last_striped == 6 / 7 tells that it ran.  NULL handle or a mode outside 0 ... 2: IVFADC_ERR_INVALID, before any device call.
+ * ivfadc_clone_view copies the setting; a view takes its own afterwards.  Not an environment variable.                     */
+int ivfadc_set_u16_tables(ivfadc_t *h, int mode);
 
 /* Test hook of the matrix-core table build: the 8-bit lower-bound table of ONE (query, cell) pair, built by
  * the code path the search uses (src/index.jl:232-236 is what it bounds).  out_table: m x 256 bytes (slot = code label);

@@ -120,6 +120,8 @@ def lib():
     L.ivfadc_set_query_token.argtypes = [vp, C.c_uint64]
     L.ivfadc_search_batches.argtypes = [vp, C.c_int, i64p, fp, C.c_int, C.c_int, u32p, fp, i32p]
     L.ivfadc_set_table_mode.argtypes = [vp, C.c_int]
+    L.ivfadc_set_u16_tables.argtypes = [vp, C.c_int]
+    L.ivfadc_set_u16_tables.restype = C.c_int
     L.ivfadc_delete_ids.argtypes = [vp, C.c_int64, u32p, i64p]
     L.ivfadc_shift_ids.argtypes = [vp, C.c_int32]
     L.ivfadc_save_index.argtypes = [vp, C.c_char_p, C.c_int]

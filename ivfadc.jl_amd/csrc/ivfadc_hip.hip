@@ -319,6 +319,7 @@ struct ivfadc_index {
     // f32 tables, 32 or 64 KB per workgroup
     DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
     int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
+    int u16_tables = 0;          // ivfadc_set_u16_tables: 0 per-pass ADC tables; 1 table-free (u16_direct_*_scan_kernel); 2 table-free where the rule of make_plan_u16 expects it to win
     bool u16_wide = false;       // table mode 10: a 16-bit handle runs 64 < K on the scan kernel's LDS-selector form (u16_wide_scan_kernel) where its LDS need fits
     bool wg8_wide = false;       // table modes 8 / 9: 64 < K <= 128 runs the kernel's wide-pool form (wg8_wide_scan_kernel) wherever wg8_mode takes the kernel
     // list-partitioned multi-GPU mode (ivfadc_set_list_partition): this handle scans the probed lists l with l % part_n == part_i only and
@@ -806,8 +807,8 @@ int clear_xcd_heads(ivfadc_index *h, u32 *&xq)
 // (lbscan.hip.h).  List-major: FourWave scan_kernel (striped tables: Plan::stripe); NarrowField nf_scan_kernel, eight queries per code
 // stream behind the 4-bit filter (nfscan.hip.h); EightWave wg8scan.hip.h, eight waves per workgroup on four conflict-free copies of
 // the integer filter table (Plan::q8: eight queries per stream; Plan::wide: the wide pool of 64 < K <= 128, the merge behind it is
-// the one of K > 64); U16 / U16Wide u16scan.hip.h on register / LDS selectors.
-enum class ScanForm { QueryMajor, QueryMajorLb, FourWave, NarrowField, EightWave, U16, U16Wide };
+// the one of K > 64); U16 / U16Wide u16scan.hip.h on register / LDS selectors, U16Direct / U16DirectWide its table-free entries.
+enum class ScanForm { QueryMajor, QueryMajorLb, FourWave, NarrowField, EightWave, U16, U16Wide, U16Direct, U16DirectWide };
 
 struct Plan {
     ScanForm form = ScanForm::QueryMajor;
@@ -825,8 +826,14 @@ struct Plan {
     int64_t nb = 0;   // queries per sub-batch
     bool fits = true;    // false: the selection kernels' LDS need exceeds the CU's 160 KB -> the caller takes the generic path
     bool query_major() const { return form == ScanForm::QueryMajor || form == ScanForm::QueryMajorLb; }
-    // ivfadc_stats.last_striped of a list-major form: 1 striped four-wave tables; 2 / 3 eight-wave, four / eight queries; 4 / 5 its wide pool
-    int striped() const { return form == ScanForm::EightWave ? (wide ? 4 : 2) + (q8 ? 1 : 0) : (stripe ? 1 : 0); }
+    // ivfadc_stats.last_striped of a list-major form: 1 striped four-wave tables; 2 / 3 eight-wave, four / eight queries; 4 / 5 its wide pool;
+    // 6 / 7 the table-free UInt16 scan on register / LDS selectors
+    int striped() const
+    {
+        if (form == ScanForm::U16Direct) return 6;
+        if (form == ScanForm::U16DirectWide) return 7;
+        return form == ScanForm::EightWave ? (wide ? 4 : 2) + (q8 ? 1 : 0) : (stripe ? 1 : 0);
+    }
 };
 
 // selector capacity of the scan (K) and of the stand-alone top-w (w): registers up to 64, LDS buffers beyond
@@ -931,19 +938,27 @@ int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its s
 // U = UInt16 (u16scan.hip.h): always list-major; K <= 64 on register selectors, 64 < K on LDS selectors where table mode 10 asks for
 // them (search_dev sends larger K to the generic path otherwise).  Pairs per work item from the expected probes per list (a codeword
 // read serves every pair of the item), halved for K > 64 until the selector buffers fit; chunks of whole passes, about two items per CU.
+// Table-free (ivfadc_set_u16_tables): 1 always; 2 where a pass holds fewer points, weighted by what a gather costs, than a table has
+// entries: min(avg_len, U16_PASS) * U16_DIRECT_COST <= ksub.
 int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)
 {
     plan_begin(h, nq, K, w, pre, pl);
-    pl.form = pl.small_k ? ScanForm::U16 : ScanForm::U16Wide;
-    pl.fn = (const void *)(pl.small_k ? (u16_fn_t)u16_scan_kernel : (u16_fn_t)u16_wide_scan_kernel);
     const double avg_len = (double)h->n / std::max(1, h->kc);
+    const bool tfree = h->u16_tables == 1 || (h->u16_tables == 2 && std::min(avg_len, (double)U16_PASS) * (double)U16_DIRECT_COST <= (double)h->ksub);
+    pl.form = tfree ? (pl.small_k ? ScanForm::U16Direct : ScanForm::U16DirectWide) : (pl.small_k ? ScanForm::U16 : ScanForm::U16Wide);
+    const u16_fn_t fns[4] = {u16_wide_scan_kernel, u16_scan_kernel, u16_direct_wide_scan_kernel, u16_direct_scan_kernel};
+    pl.fn = (const void *)fns[(tfree ? 2 : 0) + (pl.small_k ? 1 : 0)];
+    auto lds_of = [&](int g) {
+        if (tfree) return pl.small_k ? u16_direct_lds_bytes(h->m, h->dsub) : u16_direct_wide_lds_bytes(h->m, h->dsub, g, pl.cap);
+        return pl.small_k ? u16_lds_bytes(h->m, h->dsub) : u16_wide_lds_bytes(h->m, h->dsub, g, pl.cap);
+    };
     const double ppl = (double)nq * w / std::max(1, h->kc);
     int qg = ppl >= 6.0 ? 8 : (ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1));
     if (h->force_qg == 1 || h->force_qg == 2 || h->force_qg == 4 || h->force_qg == 8) qg = h->force_qg;
-    if (!pl.small_k)   // 4 x qg x cap keys beside the tables: m dsp + qg cap <= 4091 (u16scan.hip.h)
-        while (qg > 1 && u16_wide_lds_bytes(h->m, h->dsub, qg, pl.cap) > LDS_MAX) qg >>= 1;
+    if (!pl.small_k)   // 4 x qg x cap keys beside the tables: m dsp + qg cap <= 4091, table-free <= 5115 (u16scan.hip.h)
+        while (qg > 1 && lds_of(qg) > LDS_MAX) qg >>= 1;
     pl.qg = qg;
-    pl.lds = pl.small_k ? u16_lds_bytes(h->m, h->dsub) : u16_wide_lds_bytes(h->m, h->dsub, qg, pl.cap);
+    pl.lds = lds_of(qg);
     if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
     plan_chunks(h, nq, w, avg_len, U16_PASS, U16_PASS, pl);
     plan_subbatch(h, nq, K, w, true, pl);
@@ -2914,7 +2929,7 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
 // settings that change how a search runs, copied to the internal second lane before every use
 static void copy_search_config(ivfadc_index *dst, const ivfadc_index *src)
 {
-    dst->wg8_mode = src->wg8_mode; dst->wg8_wide = src->wg8_wide; dst->u16_wide = src->u16_wide;
+    dst->wg8_mode = src->wg8_mode; dst->wg8_wide = src->wg8_wide; dst->u16_wide = src->u16_wide; dst->u16_tables = src->u16_tables;
     dst->allow_nf = src->allow_nf; dst->allow_sq = src->allow_sq; dst->sq_inside = src->sq_inside; dst->allow_lb = src->allow_lb;
     dst->force_lb = src->force_lb; dst->allow_bf16 = src->allow_bf16; dst->allow_f16 = src->allow_f16; dst->lb_use_f16 = src->lb_use_f16; dst->allow_prune = src->allow_prune; dst->allow_listed = src->allow_listed;
     dst->allow_filt = src->allow_filt; dst->allow_mfma = src->allow_mfma; dst->mfma_min_kc = src->mfma_min_kc; dst->ws_budget = src->ws_budget;
@@ -4748,6 +4763,15 @@ try {
     // 10: as 0, and on a 16-bit handle 64 < K runs the scan kernel's LDS-selector form (u16_wide_scan_kernel) wherever its LDS need fits a
     // CU (K <= 1984 at small m x dsub: u16scan.hip.h) instead of the generic path; an 8-bit handle plans what mode 0 plans
     h->u16_wide = mode == 10;
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_set_u16_tables(ivfadc_t *h, int mode)
+try {
+    HandleLock lk_(h);
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    if (mode < 0 || mode > 2) return fail(IVFADC_ERR_INVALID, "mode must be 0 ... 2");
+    h->u16_tables = mode;   // (an 8-bit handle keeps it and never reads it: make_plan_u16 alone does)
     return IVFADC_OK;
 } IVF_CATCH
 

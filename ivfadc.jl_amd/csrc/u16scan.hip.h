@@ -26,6 +26,22 @@
 // Reach: 32 (m dsp + qg cap) + 32 912 B <= 160 KB, i.e. m dsp + qg cap <= 4091 (dsp = dsub rounded up to 4); the plan halves qg until
 // that holds.  cap = 4096 (K >= 1985) never fits, so K <= 1984 where m dsp <= 2040 (qg = 1), K <= 960 up to m dsp <= 3064, K <= 448 up
 // to 3576, K <= 192 up to 3832; beyond that (and for K > 1984) the search takes the generic path as before.
+//
+// TABLE-FREE (u16_direct_scan_kernel / u16_direct_wide_scan_kernel, on request: ivfadc_set_u16_tables): a point needs one entry per
+// sub-space, the one of its own code, and a pass holds at most U16_PASS points -- fewer than the ksub entries a table build computes
+// whenever ksub > 1024 or the list is shorter than ksub.  These entries compute that one entry for the point itself:
+//
+//   for ii = 0 .. m-1:  every point gathers the codeword its code names from codebooks ([m][ksub][dsub], 16-byte loads where
+//       dsub % 4 == 0, single floats otherwise), 16 bytes at a time with the next group in flight, and forms for each pair s
+//           sum = 0;  for t ascending: df = cw[t] - r_s[ii*dsub + t];  sum = sum + df*df;      then   acc[s] = acc[s] + sum
+//
+// The sum of a sub-space is formed in its own accumulator from zero and added afterwards: the table entry's expression, in its order,
+// hence its bits.  Everything around the accumulate phase is the table form's.  No table area, no tile loop, no barrier inside the
+// sub-space loop; a lane without a point (at or behind p1: the chunk's or the list's end) reads neither a code nor a codeword, and a
+// code is clamped to ksub - 1 before it becomes an address.  LDS: residuals + the wave-merge exchange (16 KB) for K <= 64
+// (u16_direct_lds_bytes); residuals + selbuf[4][qg][cap] beyond (u16_direct_wide_lds_bytes), so the wide reach grows to
+// 32 (m dsp + qg cap) + 144 B <= 160 KB, i.e. m dsp + qg cap <= 5115: K <= 1984 where m dsp <= 3064 (qg = 1), K <= 960 up to 4088,
+// K <= 448 up to 4600, K <= 192 up to 4856 -- and cap = 4096 fits where m dsp <= 1016, so there K reaches IVFADC_MAX_K = 2048.
 #pragma once
 #include "kernels.hip.h"
 
@@ -35,6 +51,11 @@ constexpr int U16_P = 8;                    // (query, probe) pairs per work ite
 constexpr int U16_PPT = 4;                  // points per thread and pass
 constexpr int U16_PASS = 256 * U16_PPT;     // points per pass
 constexpr int U16_TAB_FLOATS = 8192;        // table area: 32 KB, P x T floats (T = codewords per tile)
+constexpr int U16_XCH_FLOATS = 4 * U16_P * 64 * 2;   // the table-free K <= 64 entry keeps only the wave-merge exchange: 4 x P x 64 keys, 16 KB
+// ivfadc_set_u16_tables(h, 2): table-free iff min(avg_len, U16_PASS) * U16_DIRECT_COST <= ksub.  The arithmetic alone says 1, and the
+// measurement leaves it there: at k = 1024 the table-free scan is ahead at every avg_len of 128 ... 2048 (no crossover, so <= 1), at
+// k = 256 and avg_len 977 the tables are (so > 0.262); 1 is the largest such value (profiles/u16_direct.json)
+constexpr float U16_DIRECT_COST = 1.0f;
 
 // dynamic LDS of u16_scan_kernel: residuals [P][m][dsp] (dsp = dsub rounded up to 4: one 16-byte read serves four terms), table area
 // (the wave-merge exchange, 4 x P x 64 keys = 16 KB, aliases it), per-wave counts, two words of work-queue / verdict exchange
@@ -49,9 +70,21 @@ static inline size_t u16_wide_lds_bytes(int m, int dsub, int qg, int cap)
     return u16_lds_bytes(m, dsub) + (size_t)4 * qg * cap * 8;
 }
 
-// qg: the bucket grouping of the plan (1, 2, 4 or 8); items carry up to qg pairs.  SMALL: K <= 64, register selectors
-template <bool SMALL> static __device__ __forceinline__ void u16_scan_body(const ScanArgs &a, int qg)
+// ... of the table-free entries: no table area
+static inline size_t u16_direct_lds_bytes(int m, int dsub)
 {
+    return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)U16_XCH_FLOATS * 4 + 4 * U16_P * 4 + 16;
+}
+static inline size_t u16_direct_wide_lds_bytes(int m, int dsub, int qg, int cap)
+{
+    return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)4 * qg * cap * 8 + 4 * U16_P * 4 + 16;
+}
+
+// qg: the bucket grouping of the plan (1, 2, 4 or 8); items carry up to qg pairs.  SMALL: K <= 64, register selectors;
+// DIRECT: table-free accumulate phase
+template <bool SMALL, bool DIRECT> static __device__ __forceinline__ void u16_scan_body(const ScanArgs &a, int qg)
+{
+    constexpr int TABF = DIRECT ? (SMALL ? U16_XCH_FLOATS : 0) : U16_TAB_FLOATS;   // floats between the residuals and what follows
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     const IndexView &ix = a.ix;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
@@ -59,11 +92,11 @@ template <bool SMALL> static __device__ __forceinline__ void u16_scan_body(const
     const int cap = SMALL ? 64 : a.cap;
     const int dsp = (dsub + 3) & ~3, rstride = m * dsp;
     float *resid = (float *)smem_raw;                                  // [P][m][dsp]
-    float *tab = resid + (size_t)U16_P * rstride;                     // [P][T]
+    float *tab = resid + (size_t)U16_P * rstride;                     // [P][T] (DIRECT: the exchange only)
     // SMALL: xch[4 waves][P][64] aliases the tables after the scan; else the selector buffers [4 waves][qg][cap], which ARE the exchange
-    u64 *xch = SMALL ? (u64 *)tab : (u64 *)(tab + U16_TAB_FLOATS);
+    u64 *xch = SMALL ? (u64 *)tab : (u64 *)(tab + TABF);
     const size_t xw = SMALL ? (size_t)U16_P : (size_t)qg;              // selectors per wave in xch
-    int *scnt = SMALL ? (int *)(tab + U16_TAB_FLOATS) : (int *)(xch + (size_t)4 * qg * cap);   // [4][P]
+    int *scnt = SMALL ? (int *)(tab + TABF) : (int *)(xch + (size_t)4 * qg * cap);   // [4][P]
     u32 *swi = (u32 *)(scnt + 4 * U16_P);                              // [2]
     const bool direct = qg == 1 && a.direct_items != 0;
     const u32 total = direct ? a.direct_items : a.wi_off[ix.kc];
@@ -151,6 +184,7 @@ template <bool SMALL> static __device__ __forceinline__ void u16_scan_body(const
             const int ii = i / dsub;
             resid[s * rstride + ii * dsp + (i - ii * dsub)] = a.queries[(size_t)qs * d + i] - ix.centroids[(size_t)l * d + i];
         }
+        if (DIRECT) __syncthreads();   // (the table form's first tile barrier orders the residual writes)
         const int T = U16_TAB_FLOATS / nvalid;   // codewords per tile
         const uint16_t *cbase = (const uint16_t *)(ix.codes + ix.list_codeoff[l]);
 
@@ -160,6 +194,74 @@ template <bool SMALL> static __device__ __forceinline__ void u16_scan_body(const
             for (int k = 0; k < U16_PPT; ++k)
 #pragma unroll
                 for (int s = 0; s < U16_P; ++s) acc[k][s] = dc[s];
+            if (DIRECT) {
+                const bool al4 = (dsub & 3) == 0;
+                bool valid[U16_PPT];
+#pragma unroll
+                for (int k = 0; k < U16_PPT; ++k) valid[k] = pp + (u32)(k * 256 + tid) < p1;
+                // one group of a point's codeword: a lane without a point reads nothing; the terms behind dsub are never read, nor summed
+                auto group = [&](const float *cw, bool v, int g) {
+                    float4 o = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+                    if (v) {
+                        const float *src = cw + 4 * g;
+                        if (al4) o = *(const float4 *)src;
+                        else {
+                            const int nt = dsub - 4 * g;
+                            o.x = src[0];
+                            if (nt > 1) o.y = src[1];
+                            if (nt > 2) o.z = src[2];
+                            if (nt > 3) o.w = src[3];
+                        }
+                    }
+                    return o;
+                };
+                for (int ii = 0; ii < m; ++ii) {
+                    const float *cw[U16_PPT];
+                    float4 cur[U16_PPT];
+#pragma unroll
+                    for (int k = 0; k < U16_PPT; ++k) {
+                        const u32 p = pp + (u32)(k * 256 + tid);
+                        const u32 c = valid[k] ? min((u32)cbase[(size_t)p * cs2 + ii], (u32)(ksub - 1)) : 0u;
+                        cw[k] = ix.codebooks + ((size_t)ii * ksub + c) * dsub;
+                        cur[k] = group(cw[k], valid[k], 0);
+                    }
+                    const float *rr = resid + ii * dsp;
+                    float sum[U16_PPT][U16_P];
+#pragma unroll
+                    for (int k = 0; k < U16_PPT; ++k)
+#pragma unroll
+                        for (int s = 0; s < U16_P; ++s) sum[k][s] = 0.0f;
+                    for (int g = 0; g < ngrp; ++g) {
+                        float4 nxt[U16_PPT];
+#pragma unroll
+                        for (int k = 0; k < U16_PPT; ++k) nxt[k] = group(cw[k], valid[k] && g + 1 < ngrp, g + 1);
+                        const int nt = min(4, dsub - 4 * g);
+#pragma unroll
+                        for (int s = 0; s < U16_P; ++s)
+                            if (s < nvalid) {
+                                const float4 r4 = *(const float4 *)(rr + s * rstride + 4 * g);   // (uniform address: a broadcast)
+                                const float rv[4] = {r4.x, r4.y, r4.z, r4.w};
+#pragma unroll
+                                for (int k = 0; k < U16_PPT; ++k) {
+                                    const float vv[4] = {cur[k].x, cur[k].y, cur[k].z, cur[k].w};
+#pragma unroll
+                                    for (int j = 0; j < 4; ++j)
+                                        if (j < nt) {
+                                            const float df = vv[j] - rv[j];
+                                            sum[k][s] = sum[k][s] + df * df;
+                                        }
+                                }
+                            }
+#pragma unroll
+                        for (int k = 0; k < U16_PPT; ++k) cur[k] = nxt[k];
+                    }
+#pragma unroll
+                    for (int k = 0; k < U16_PPT; ++k)
+#pragma unroll
+                        for (int s = 0; s < U16_P; ++s)
+                            if (s < nvalid) acc[k][s] = acc[k][s] + sum[k][s];
+                }
+            } else
             for (int ii = 0; ii < m; ++ii) {
                 u32 code[U16_PPT];
 #pragma unroll
@@ -253,9 +355,12 @@ template <bool SMALL> static __device__ __forceinline__ void u16_scan_body(const
     }
 }
 
-__global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<true>(a, qg); }
+__global__ __launch_bounds__(256) void u16_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<true, false>(a, qg); }
 // 64 < K: LDS selectors beside the tables (a.cap; dynamic LDS u16_wide_lds_bytes)
-__global__ __launch_bounds__(256) void u16_wide_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<false>(a, qg); }
+__global__ __launch_bounds__(256) void u16_wide_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<false, false>(a, qg); }
+// table-free (ivfadc_set_u16_tables): dynamic LDS u16_direct_lds_bytes / u16_direct_wide_lds_bytes
+__global__ __launch_bounds__(256) void u16_direct_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<true, true>(a, qg); }
+__global__ __launch_bounds__(256) void u16_direct_wide_scan_kernel(const ScanArgs a, int qg) { u16_scan_body<false, true>(a, qg); }
 
 // _encode_point's quantize_data for UInt16 codes (utils.jl:148-161): per sub-space the codeword index with the smallest
 // sum_t (cb[t] - r[t])^2, first minimum on ties (keys f32 bits << 32 | index).  One workgroup per point; out: n x m uint16_t indices.

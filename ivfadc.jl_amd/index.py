@@ -474,6 +474,14 @@ class IVFADCIndex:
         Results are the same bytes in every mode."""
         nat.check(nat.lib().ivfadc_set_table_mode(self._h, int(mode)))
 
+    def set_u16_tables(self, mode):
+        """ADC tables of an index with UInt16 codes.  0 (default): per-pass tables of all ksub codewords; 1: table-free wherever it is
+        served -- every point's sums come straight from the codeword its code names, so the cost follows the lists probed, not the
+        codebook size (K <= 64, and 64 < K under set_table_mode(10)); 2: table-free where min(n / kc, 1024) * U16_DIRECT_COST <= ksub.
+        get_stats()["last_striped"] is 6 / 7 when the table-free scan ran (register / LDS selectors).  An index with UInt8 codes
+        accepts the call and plans what it planned before.  Results are the same bytes in every mode."""
+        nat.check(nat.lib().ivfadc_set_u16_tables(self._h, int(mode)))
+
     def debug_lb_table(self, query, cell):
         """Test hook: the 8-bit lower-bound ADC table of one (query, cell) pair as the matrix-core build makes it.
         Returns (table uint8 [m, 256], inv, sbase, nn, base [m], r2 [m])."""

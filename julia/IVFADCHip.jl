@@ -214,6 +214,9 @@ function _handle(ivfadc::AnyGpuIndex)
     return h === nothing ? hip_sync!(ivfadc) : h
 end
 
+# ADC tables of a UInt16 index: 0 per-pass tables (default), 1 table-free, 2 table-free where it is expected to win; same results
+hip_set_u16_tables!(ivfadc::AnyGpuIndex, mode::Integer) = (_check(ccall((:ivfadc_set_u16_tables, LIBIVFADC), Cint, (Ptr{Cvoid}, Cint), _handle(ivfadc).ptr, mode)); ivfadc)
+
 # Every mutator edits the device copy IN PLACE next to the Julia lists.  Should a device edit fail half way, the handle is dropped, so
 # that the next search uploads the Julia lists (the source of truth) afresh: a stale device copy cannot be searched.
 function _on_device(f, ivfadc::GpuIndex)

@@ -6,11 +6,17 @@ are random (the scan's cost does not depend on training); queries are data point
 device-resident batch, scan time from events, pruned fraction, table-build element operations (3 d ksub per (query, probe)) per
 second of scan time against the 78.6 T/s no-FMA vector-ALU peak, and codebook bytes read per table.
 
-    python tools/u16_bench.py [--reps 10] [--only sift1m_k1024,...] [--K 100] [--table-mode 10] [--windows 5]
+    python tools/u16_bench.py [--reps 10] [--only sift1m_k1024,...] [--K 100] [--table-mode 10] [--windows 5] [--u16-tables 1]
+                              [--sweep-len 128,256,512,1024,2048]
 
 --K overrides the shapes' K; --table-mode is passed to set_table_mode (10: K > 64 on the scan kernel's LDS-selector form instead of the
 generic path, whose scan_ms covers its own kernels).  --windows N times N windows of --reps searches and reports the median window and
 the spread (max - min) next to the mean; get_stats()["last_qg"] (pairs_per_item; -2 = generic path) tells which path ran.
+--u16-tables is passed to set_u16_tables (1: the table-free scan, 2: where its rule expects it to win; 0 makes no call at all, so the
+tool also runs against a library that lacks the entry); get_stats()["last_striped"] (6 / 7: table-free) is reported as "form".
+--sweep-len adds the crossover sweep: the SIFT1M-shape quantizers at k = 1024 (d = 128, m = 8, kc = 1024, 1024 queries, K = 10, w = 8)
+with n = L x kc points for every L given, named sift_k1024_len<L>: the list length at which tables and table-free sums cost the same
+is what U16_DIRECT_COST (csrc/u16scan.hip.h) records.
 """
 import argparse
 import json
@@ -52,17 +58,22 @@ def main():
     ap.add_argument("--K", type=int, default=0, help="K for every shape (default: the shape's own, 10)")
     ap.add_argument("--table-mode", type=int, default=0, help="ivfadc_set_table_mode (10: UInt16 scan kernel also for 64 < K)")
     ap.add_argument("--windows", type=int, default=1, help="timed windows of --reps searches each (median and spread are reported)")
+    ap.add_argument("--u16-tables", type=int, default=0, choices=[0, 1, 2], help="ivfadc_set_u16_tables (1: table-free scan, 2: by its rule)")
+    ap.add_argument("--sweep-len", default="", help="comma-separated average list lengths of the k = 1024 crossover sweep")
     args = ap.parse_args()
     only = set(filter(None, args.only.split(",")))
+    shapes = SHAPES + [("sift_k1024_len%d" % L, 128, 8, 1024, L * 1024, 1024, 1024, 10, 8) for L in map(int, filter(None, args.sweep_len.split(",")))]
     import torch
     out = {"tool": "u16_bench", "shapes": {}}
-    for name, d, m, ksub, n, kc, nq, K, w in SHAPES:
+    for name, d, m, ksub, n, kc, nq, K, w in shapes:
         if only and name not in only:
             continue
         K = args.K or K
         g, cent, lst = build(d, m, ksub, n, kc)
         if args.table_mode:
             g.set_table_mode(args.table_mode)
+        if args.u16_tables:
+            g.set_u16_tables(args.u16_tables)
         rng = np.random.default_rng(1)
         q = (cent[rng.integers(0, kc, nq)] + rng.normal(0, 0.05, (nq, d))).astype(np.float32)
         dq = torch.from_numpy(q).cuda()
@@ -95,7 +106,7 @@ def main():
         ops = 3.0 * d * ksub * tables * (1.0 - pruned)   # (an item that prunes builds no table: approximate by the point fraction)
         out["shapes"][name] = {
             "d": d, "m": m, "k": ksub, "n": n, "kc": kc, "nq": nq, "K": K, "w": w,
-            "table_mode": args.table_mode,
+            "table_mode": args.table_mode, "u16_tables": args.u16_tables, "form": st["last_striped"],
             "qps": nq / dt, "ms_per_batch": dt * 1e3, "ms_per_batch_median": float(np.median(wins)) * 1e3,
             "ms_per_batch_spread": (max(wins) - min(wins)) * 1e3, "windows": len(wins), "reps": args.reps,
             "scan_ms": scan_s * 1e3, "pruned_fraction": pruned,
