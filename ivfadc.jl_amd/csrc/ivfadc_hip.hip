@@ -11,6 +11,7 @@
 #include "generic.hip.h"
 #include "u16scan.hip.h"
 #include "twolevel.hip.h"
+#include "pack_operands.h"
 
 #include <algorithm>
 #include <atomic>
@@ -20,6 +21,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <memory>
 #include <mutex>
 #include <new>
 #include <stdexcept>
@@ -142,7 +144,6 @@ struct DevBuf {
         bytes = 0;
         owned = true;
     }
-    void forget() { p = nullptr; bytes = 0; owned = true; }   // (a copied struct: the memory belongs to the original)
     void alias() { owned = false; }
     template <class T> T *as() const { return (T *)p; }
 };
@@ -183,7 +184,6 @@ struct PinnedBuf {
         p = nullptr;
         bytes = 0;
     }
-    void forget() { p = nullptr; bytes = 0; }
 };
 
 static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
@@ -234,9 +234,6 @@ int h2d_copy(void *dst, const void *src, size_t bytes, hipStream_t s)
     return IVFADC_OK;
 }
 
-// (for code that threads a hipError_t through a chain of uploads: ivfadc_create)
-hipError_t h2d_hip(void *dst, const void *src, size_t bytes, hipStream_t s) { return h2d_copy(dst, src, bytes, s) == IVFADC_OK ? hipSuccess : hipErrorUnknown; }
-
 int d2h_copy(void *dst, const void *src, size_t bytes, hipStream_t s)
 {
     if (bytes == 0) return IVFADC_OK;
@@ -279,120 +276,79 @@ static inline int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; 
 // the generation under the view's own mutex: their writers hold it), a mutator holds g_topo_mu and every view's mutex for
 // as long as it edits the lists (MutationScope): no view search starts, or is still being enqueued, while the lists change, and the
 // first one afterwards sees the new generation and refuses.
-struct HandleMutex {
-    std::recursive_mutex m;
-    HandleMutex() = default;
-    HandleMutex(const HandleMutex &) {}                        // (a view is made by copying the index's struct: it gets a mutex of its own)
-    HandleMutex &operator=(const HandleMutex &) { return *this; }
-};
 static std::recursive_mutex g_topo_mu;
 
-// an int that may be read without the handle's lock (make_plan's hint); copies with the handle (a view starts from its index's fields)
+// an int that may be read without the handle's lock (make_plan's hint)
 struct RelaxedInt {
     std::atomic<int> v{0};
-    RelaxedInt() = default;
-    RelaxedInt(const RelaxedInt &o) : v(o.v.load(std::memory_order_relaxed)) {}
-    RelaxedInt &operator=(const RelaxedInt &o) { v.store(o.v.load(std::memory_order_relaxed), std::memory_order_relaxed); return *this; }
     int load() const { return v.load(std::memory_order_relaxed); }
     void store(int x) { v.store(x, std::memory_order_relaxed); }
     void fetch_add(int x) { v.fetch_add(x, std::memory_order_relaxed); }
     int fetch_add_get(int x) { return v.fetch_add(x, std::memory_order_relaxed); }
 };
 
-struct ivfadc_index {
-    HandleMutex mu;
+// ---- the handle, in ownership groups -----------------------------------------------------------------------------------------------
+// ivfadc_index is composed of the plain structs below ("The handle is its ownership groups").  A group that holds DevBufs
+// names them ONCE, in its each_buf, next to their declarations: ivfadc_destroy releases every group through it, clone_view aliases the
+// shared groups through it.  A new buffer is declared in its group and listed in that group's each_buf -- nowhere else.
+
+// shape and device: copied to a view
+struct Dims {
     int device = 0;
     int d = 0, kc = 0, m = 0, ksub = 0, dsub = 0, cs = 0;
     int num_cu = 256;
-    hipStream_t stream = nullptr;
+    // U = UInt16 (ivfadc_create_u16, u16scan.hip.h): the host mirror and the device hold CODEWORD INDICES (little-endian uint16, cb = 2m
+    // bytes per point); labels are translated at the boundary (set / get lists, encode, save / load), so a table needs m x ksub slots
+    bool u16 = false;
+    int cb = 0;                        // code bytes per point of the host mirror: m (UInt8) or 2m (UInt16)
+};
 
-    DevBuf centroids, codebooks, codebooks_t, codebooks_p, labels, cnorm, tmin, tlist;
+// the quantizers and every operand derived from them: written by ivfadc_create (the two-level grouping: by the index's first search of
+// a large quantizer), immutable afterwards; a view aliases the buffers and copies the rest
+struct Quantizers {
+    DevBuf centroids, codebooks, codebooks_t, codebooks_p, labels, cnorm;
     // lower-bound tables on the matrix cores (lbscan.hip.h): bf16 split of the codebook, ||codeword||^2 and the f32 codewords, all in
     // label order, and max ||codeword|| per sub-quantizer; present for the shapes lb_shape() names
     DevBuf lb_split, lb_n2, lb_lab, lb_maxn;
     DevBuf lb_f16, lb_isc;       // round 5: f16 codewords x 2^e_ii and 2^-e_ii for the one-product build (lb_build_tables_f16)
-    bool lb_use_f16 = true;      // ivfadc_set_table_mode(h, 3): the three-product bf16 split instead (A/B)
     // narrow-field list-major scan (nfscan.hip.h; m = 8, dsub = 16, ksub = 256): ||codeword||^2 by codeword index, f32 codewords by label
     DevBuf nf_n2, nf_lab;
-    bool allow_nf = true;
-    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64, with the wide pool K <= 128; m = 16, dsub = 4 / 8, K <= 64): the work items'
-    // f32 tables, 32 or 64 KB per workgroup
-    DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
-    int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
-    int u16_tables = 0;          // ivfadc_set_u16_tables: 0 per-pass ADC tables; 1 table-free (u16_direct_*_scan_kernel); 2 table-free where the rule of make_plan_u16 expects it to win
-    bool u16_wide = false;       // table mode 10: a 16-bit handle runs 64 < K on the scan kernel's LDS-selector form (u16_wide_scan_kernel) where its LDS need fits
-    bool wg8_wide = false;       // table modes 8 / 9: 64 < K <= 128 runs the kernel's wide-pool form (wg8_wide_scan_kernel) wherever wg8_mode takes the kernel
-    // list-partitioned multi-GPU mode (ivfadc_set_list_partition): this handle scans the probed lists l with l % part_n == part_i only and
-    // leaves partial top-K keys; partial_keys: where the running call wants them (null: ids as usual); the batch whose probe arrays stand
-    int part_n = 1, part_i = 0;
-    uint64_t *partial_keys = nullptr;
-    int64_t partial_nq = -1;
-    int partial_w = 0, partial_K = 0;
-    DevBuf sq_keys, sq_cnt, sq_arrive, cent_t;   // small-batch path (smallq.hip.h): partial results, arrival counters
-    bool allow_sq = true, sq_inside = false;
-    bool allow_lb = true;
-    bool force_lb = false;       // ivfadc_set_table_mode(h, 2): the matrix-core rounds wherever they are instantiated, not only where they pay
-    DevBuf cent_hi, cent_lo, q_hi, q_lo;   // bf16 split operands of coarse_bf16_kernel ([rows][dp], dp = d rounded up to 32)
-    // round 5: the one-product f16 form of the same filter: scaled f16 centroids, the batch's scaled f16 queries, per-query overflow flags
-    DevBuf cent_f16, q_f16, q_flags;
+    DevBuf cent_t;               // small-batch path (smallq.hip.h): centroids regrouped [d / 4][kc][4]
+    DevBuf cent_hi, cent_lo;     // bf16 split operands of coarse_bf16_kernel ([rows][dp], dp = d rounded up to 32)
+    DevBuf cent_f16;             // round 5: the one-product f16 form of the same filter: scaled f16 centroids
     float f16_scale = 0.f;       // power of two: 2^11 <= scale * max|centroid component| <= 2^12 (0: the form is not available)
-    bool allow_f16 = true, last_coarse_f16 = false;
     int dp32 = 0;
-    bool allow_bf16 = true, last_coarse_bf16 = false;
-    bool allow_prune = true;     // query-major scan: skip probes whose coarse distance exceeds the K-th best key (exact)
-    bool allow_listed = true, last_listed = false;   // listed mode: per-tile records instead of the score matrix (run_coarse)
-    // one-process-per-GPU result merge inside the library (ivfadc_comm_*): this rank's communicator, a side stream for the
-    // collectives and one completion event per result slot
-    void *comm = nullptr;
-    int comm_ranks = 0, comm_rank = 0;
-    hipStream_t comm_stream = nullptr;
-    hipEvent_t comm_ready = nullptr;
-    static constexpr int COMM_SLOTS = 8;
-    hipEvent_t comm_done[COMM_SLOTS] = {};
-    bool comm_busy[COMM_SLOTS] = {};
-    int64_t comm_collectives = 0;
-    // collectives complete in issue order on the side stream: seq numbers them, comm_slot_seq[s] = the last one that read slot s, and a
-    // search stream (this handle's, or a view's: its own copy of comm_waited) has waited for every collective up to comm_waited
-    int64_t comm_seq = 0, comm_slot_seq[COMM_SLOTS] = {}, comm_waited = 0;
-    bool allow_filt = true;       // striped tables + rotated-order filter sums in the list-major kernels (ivfadc_set_table_mode)
-    // certified two-level coarse search (twolevel.hip.h): group centres [G][d], slot ranges, radii, grouped centroids, slot -> cluster id;
-    // tl_mode: 0 = automatic (built on the first search of a large quantizer, used if a self-probe says the bounds cut), 1 = on, -1 = off
-    DevBuf tl_centres, tl_off, tl_rad, tl_cent, tl_slot, tl_gdist;
-    int tl_G = 0, tl_mode = 0;
-    bool dev_entry = false;   // the running search came in through a device-pointer entry AND another lane of this replica searched since this
-                              // handle's previous search (the caller drives several lanes side by side: see make_plan)
-    // feedback for make_plan's probes-per-round choice: how much of what the query-major scans probed was pruned (see fb_poll / fb_snapshot)
-    PinnedBuf fb_pin;          // 4 KB: a snapshot of the sharded counters
-    hipEvent_t fb_ev = nullptr;
-    bool fb_pending = false;
-    int fb_countdown = 0;
-    int64_t fb_sp = 0, fb_pp = 0;   // counters at the last snapshot that was read
-    float prune_est = -1.0f;        // smoothed pruned fraction of the probed points (< 0: not known yet)
-    RelaxedInt lane_ticket;   // root index only: one ticket per device-entry search on the index or any of its views
-    int my_ticket = -1;       // this handle's last ticket
-    RelaxedInt n_views;   // live views of this index (a hint for make_plan: several batches are in flight on this replica)
+    float cmaxn = 0.f;            // >= max ||centroid||, for the MFMA filter's error bound
+    // certified two-level coarse search (twolevel.hip.h): group centres [G][d], slot ranges, radii, grouped centroids, slot -> cluster id
+    DevBuf tl_centres, tl_off, tl_rad, tl_cent, tl_slot;
+    int tl_G = 0;
     bool tl_tried = false, tl_use = false;
     float tl_eps = 0.f, tl_probe_fraction = -1.f;
-    int64_t visited_base = 0;
-    DevBuf gen_a, gen_b, gen_tmp, gen_off, gen_tot;   // generic path: key buffers (sort in/out), rocPRIM scratch, offsets
-    int tlist_ldq = 0;
-    int tmin_tiles = 0, tmin_tile_w = 0;   // set by run_coarse when the last coarse launch wrote tile minima
-    float cmaxn = 0.f;            // >= max ||centroid||, for the MFMA filter's error bound
-    bool allow_mfma = true;
-    int mfma_min_kc = 2048;
-    // lists (device layout)
+    std::vector<uint8_t> h_label_ok;   // m x 256 validity
+    bool identity_labels = false;
+    std::vector<uint16_t> lab16;       // [m][ksub] labels of a 16-bit handle
+    std::vector<uint32_t> lab_sorted;  // [m][ksub] label << 16 | codeword index, ascending within each block (label -> index lookups)
+    // the residual quantizer's rotation as loaded from an index file (nrows x nrows, column by column as persistency.jl:62-64 writes it);
+    // empty = identity (:pq).  knn_search never reads it (index.jl:204-258): a rotated (:opq) index is SEARCHED as it is; quantize_data --
+    // push! / encode -- would need it (third-party arithmetic, unverifiable here), so those entries refuse on such a handle.
+    std::vector<float> rot;
+    template <class F> void each_buf(F f)
+    {
+        for (DevBuf *b : {&centroids, &codebooks, &codebooks_t, &codebooks_p, &labels, &cnorm, &lb_split, &lb_n2, &lb_lab, &lb_maxn, &lb_f16, &lb_isc,
+                          &nf_n2, &nf_lab, &cent_t, &cent_hi, &cent_lo, &cent_f16, &tl_centres, &tl_off, &tl_rad, &tl_cent, &tl_slot})
+            f(*b);
+    }
+};
+
+// the inverted lists as the device holds them: a view aliases the buffers and copies the layout
+struct Lists {
     int64_t n = 0;
     bool have_lists = false;
     bool synthetic = false;
     bool dirty = false;           // host mirror changed, device copy stale
     int64_t maxlen = 0;
-    int64_t inplace_appends = 0;
-    DevBuf list_pos, list_len, list_codeoff, codes, ids, app_stage;
-    // host mirror: one (codes, ids) pair per list -- the source of truth; the device copy gives every list spare
-    // capacity so push! writes in place (re-layout only when a list overflows)
+    DevBuf list_pos, list_len, list_codeoff, codes, ids;
     std::vector<int64_t> h_len;                  // [kc] points per list (kept for synthetic lists too)
-    std::vector<std::vector<uint8_t>> hl_codes;  // [kc] len x m bytes
-    std::vector<std::vector<uint32_t>> hl_ids;   // [kc]
     std::vector<int64_t> d_cap, d_pos, d_codeoff;   // device layout: capacity, id offset, code byte offset per list
     int64_t ntotal() const
     {
@@ -400,20 +356,68 @@ struct ivfadc_index {
         for (int64_t v : h_len) t += v;
         return t;
     }
-    std::vector<uint8_t> h_label_ok;   // m x 256 validity
-    bool identity_labels = false;
-    // U = UInt16 (ivfadc_create_u16, u16scan.hip.h): the host mirror and the device hold CODEWORD INDICES (little-endian uint16, cb = 2m
-    // bytes per point); labels are translated at the boundary (set / get lists, encode, save / load), so a table needs m x ksub slots
-    bool u16 = false;
-    int cb = 0;                        // code bytes per point of the host mirror: m (UInt8) or 2m (UInt16)
-    std::vector<uint16_t> lab16;       // [m][ksub] labels of a 16-bit handle
-    std::vector<uint32_t> lab_sorted;  // [m][ksub] label << 16 | codeword index, ascending within each block (label -> index lookups)
-    // the residual quantizer's rotation as loaded from an index file (nrows x nrows, column by column as persistency.jl:62-64 writes it);
-    // empty = identity (:pq).  knn_search never reads it (index.jl:204-258): a rotated (:opq) index is SEARCHED as it is; quantize_data --
-    // push! / encode -- would need it (third-party arithmetic, unverifiable here), so those entries refuse on such a handle.
-    std::vector<float> rot;
+    template <class F> void each_buf(F f)
+    {
+        for (DevBuf *b : {&list_pos, &list_len, &list_codeoff, &codes, &ids}) f(*b);
+    }
+};
 
-    // workspace
+// host mirror: one (codes, ids) pair per list -- the source of truth; the device copy gives every list spare
+// capacity so push! writes in place (re-layout only when a list overflows).  Stays with the index: a view never holds one.
+struct HostMirror {
+    std::vector<std::vector<uint8_t>> hl_codes;  // [kc] len x m bytes
+    std::vector<std::vector<uint32_t>> hl_ids;   // [kc]
+};
+
+// every field a setter or an environment switch writes and the planners read: a view starts from its index's, and the second lane of
+// ivfadc_search_batches is given the index's before every use (copy_search_config)
+struct SearchConfig {
+    bool lb_use_f16 = true;      // ivfadc_set_table_mode(h, 3): the three-product bf16 split instead (A/B)
+    bool allow_nf = true;
+    int wg8_mode = 0;            // ivfadc_set_tuning(h, 4, chunk) keeps the plan's choice; wg8_mode: 0 = where it pays, 1 = wherever it exists, -1 = never
+    int u16_tables = 0;          // ivfadc_set_u16_tables: 0 per-pass ADC tables; 1 table-free (u16_direct_*_scan_kernel); 2 table-free where the rule of make_plan_u16 expects it to win
+    bool u16_wide = false;       // table mode 10: a 16-bit handle runs 64 < K on the scan kernel's LDS-selector form (u16_wide_scan_kernel) where its LDS need fits
+    bool wg8_wide = false;       // table modes 8 / 9: 64 < K <= 128 runs the kernel's wide-pool form (wg8_wide_scan_kernel) wherever wg8_mode takes the kernel
+    // list-partitioned multi-GPU mode (ivfadc_set_list_partition): this handle scans the probed lists l with l % part_n == part_i only and
+    // leaves partial top-K keys
+    int part_n = 1, part_i = 0;
+    bool allow_sq = true, sq_inside = false;
+    bool allow_lb = true;
+    bool force_lb = false;       // ivfadc_set_table_mode(h, 2): the matrix-core rounds wherever they are instantiated, not only where they pay
+    bool allow_f16 = true;
+    bool allow_bf16 = true;
+    bool allow_prune = true;     // query-major scan: skip probes whose coarse distance exceeds the K-th best key (exact)
+    bool allow_listed = true;    // listed mode: per-tile records instead of the score matrix (run_coarse)
+    bool allow_filt = true;      // striped tables + rotated-order filter sums in the list-major kernels (ivfadc_set_table_mode)
+    int tl_mode = 0;             // two-level coarse search: 0 = automatic (built on the first search of a large quantizer, used if a self-probe says the bounds cut), 1 = on, -1 = off
+    bool allow_mfma = true;
+    int mfma_min_kc = 2048;
+    size_t ws_budget = (size_t)8 << 30;
+    int force_qg = 0, force_chunk = 0;
+};
+
+// what one lane's searches write and read between their launches: a view starts with an empty one of its own
+struct Workspace {
+    DevBuf tmin, tlist;
+    // eight-wave list-major scan (wg8scan.hip.h; m = 8, dsub = 4 / 8 / 12 / 16, ksub = 256, K <= 64, with the wide pool K <= 128; m = 16, dsub = 4 / 8, K <= 64): the work items'
+    // f32 tables, 32 or 64 KB per workgroup
+    DevBuf wg8_tabs, wg8_items;  // (wg8_items: work item -> list, written by bucket_scan_kernel)
+    // list-partitioned mode: partial_keys: where the running call wants the partial top-K keys (null: ids as usual); the batch whose
+    // probe arrays stand
+    uint64_t *partial_keys = nullptr;
+    int64_t partial_nq = -1;
+    int partial_w = 0, partial_K = 0;
+    DevBuf sq_keys, sq_cnt, sq_arrive;   // small-batch path (smallq.hip.h): partial results, arrival counters
+    DevBuf q_hi, q_lo;           // the batch's bf16 split queries (coarse_bf16_kernel)
+    DevBuf q_f16, q_flags;       // the batch's scaled f16 queries, per-query overflow flags
+    bool last_coarse_f16 = false, last_coarse_bf16 = false, last_listed = false;   // what the last coarse launch ran (run_coarse)
+    DevBuf tl_gdist;
+    bool dev_entry = false;   // the running search came in through a device-pointer entry AND another lane of this replica searched since this
+                              // handle's previous search (the caller drives several lanes side by side: see make_plan)
+    DevBuf gen_a, gen_b, gen_tmp, gen_off, gen_tot;   // generic path: key buffers (sort in/out), rocPRIM scratch, offsets
+    int tlist_ldq = 0;
+    int tmin_tiles = 0, tmin_tile_w = 0;   // set by run_coarse when the last coarse launch wrote tile minima
+    DevBuf app_stage;
     // ivfadc_set_next_queries: the hinted batch (good for one search), and the batch whose exact coarse rows stand in cdist2 -- written
     // by the tiles that rode behind the previous search's scan launch
     // A batch is named by (pointer, count, token): the token is the caller's generation number of the buffer's CONTENTS, so rows computed
@@ -430,15 +434,54 @@ struct ivfadc_index {
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
     bool hc_out_direct = false;   // the running host-pointer call: results go straight into the caller's arrays
+    size_t qthr_armed = 0;       // entries of qthr known to hold KEY_MAX
+    bool list_cnt_armed = false;
+    template <class F> void each_buf(F f)
+    {
+        for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
+                          &gen_tmp, &gen_off, &gen_tot, &app_stage, &cdist2, &pre_list, &pre_dc, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
+                          &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
+            f(*b);
+    }
+};
+
+// what belongs to this handle alone -- its lock and stream, statistics, feedback, the batches pipeline, the communicator, its place
+// among the views: never copied, a view starts with the defaults written here (clone_view hands it prune_est and fn_cfg)
+struct HandleState {
+    std::recursive_mutex mu;
+    hipStream_t stream = nullptr;
+    bool own_stream = true;
+    // one-process-per-GPU result merge inside the library (ivfadc_comm_*): this rank's communicator, a side stream for the
+    // collectives and one completion event per result slot
+    void *comm = nullptr;
+    int comm_ranks = 0, comm_rank = 0;
+    hipStream_t comm_stream = nullptr;
+    hipEvent_t comm_ready = nullptr;
+    static constexpr int COMM_SLOTS = 8;
+    hipEvent_t comm_done[COMM_SLOTS] = {};
+    bool comm_busy[COMM_SLOTS] = {};
+    int64_t comm_collectives = 0;
+    // collectives complete in issue order on the side stream: seq numbers them, comm_slot_seq[s] = the last one that read slot s, and a
+    // search stream (this handle's, or a view's: its own copy of comm_waited) has waited for every collective up to comm_waited
+    int64_t comm_seq = 0, comm_slot_seq[COMM_SLOTS] = {}, comm_waited = 0;
+    // feedback for make_plan's probes-per-round choice: how much of what the query-major scans probed was pruned (see fb_poll / fb_snapshot)
+    PinnedBuf fb_pin;          // 4 KB: a snapshot of the sharded counters
+    hipEvent_t fb_ev = nullptr;
+    bool fb_pending = false;
+    int fb_countdown = 0;
+    int64_t fb_sp = 0, fb_pp = 0;   // counters at the last snapshot that was read
+    float prune_est = -1.0f;        // smoothed pruned fraction of the probed points (< 0: not known yet)
+    RelaxedInt lane_ticket;   // root index only: one ticket per device-entry search on the index or any of its views
+    int my_ticket = -1;       // this handle's last ticket
+    RelaxedInt n_views;   // live views of this index (a hint for make_plan: several batches are in flight on this replica)
+    int64_t inplace_appends = 0;
     hipStream_t copy_stream = nullptr;               // ivfadc_search_batches: query ingest ahead of the searches
     hipStream_t copy_probed_a = nullptr, copy_probed_b = nullptr;   // ... probed to run beside these two (ensure_overlap)
     std::vector<hipEvent_t> ingest_ev;               // ... one event per upload group
     ivfadc_host_stats hstats{};
     // cumulative counters of internal views that no longer exist (a stale second lane of ivfadc_search_batches)
     int64_t carry_queries = 0, carry_scanned = 0, carry_pruned = 0, carry_surv = 0, carry_fallbacks = 0, carry_launches = 0;
-    size_t qthr_armed = 0;       // entries of qthr known to hold KEY_MAX
-    bool list_cnt_armed = false;
-    size_t ws_budget = (size_t)8 << 30;
 
     // profiling
     bool profiling = false;
@@ -447,9 +490,7 @@ struct ivfadc_index {
     std::vector<EvPair> pending;
     std::vector<EvPair> free_ev;
     ivfadc_stats stats{};
-    int64_t scanned_base = 0, fallback_base = 0, pruned_base = 0, surv_base = 0;
-    int force_qg = 0, force_chunk = 0;
-    bool own_stream = true;
+    int64_t scanned_base = 0, fallback_base = 0, pruned_base = 0, surv_base = 0, visited_base = 0;
     struct FnCfg { const void *fn; size_t lds; int occ; };
     std::vector<FnCfg> fn_cfg;
 
@@ -465,6 +506,16 @@ struct ivfadc_index {
     hipEvent_t pipe_ev_in = nullptr;
 };
 
+struct ivfadc_index : Dims, Quantizers, Lists, HostMirror, SearchConfig, Workspace, HandleState {
+    // every DevBuf of the handle, each group once
+    template <class F> void each_buf(F f)
+    {
+        Quantizers::each_buf(f);
+        Lists::each_buf(f);
+        Workspace::each_buf(f);
+    }
+};
+
 // the lock of an entry point on handle h (null: nothing to lock).  A view takes the topology mutex first and lets it go once its own
 // mutex is held: a mutator of its index, which holds the topology mutex while it waits for the views, is never waited for in a cycle.
 struct HandleLock {
@@ -474,12 +525,12 @@ struct HandleLock {
         if (!h) return;
         if (h->is_view) {
             std::lock_guard<std::recursive_mutex> topo(g_topo_mu);
-            h->mu.m.lock();
+            h->mu.lock();
         } else {
-            h->mu.m.lock();
+            h->mu.lock();
         }
     }
-    ~HandleLock() { if (h) h->mu.m.unlock(); }
+    ~HandleLock() { if (h) h->mu.unlock(); }
     HandleLock(const HandleLock &) = delete;
     HandleLock &operator=(const HandleLock &) = delete;
 };
@@ -505,6 +556,14 @@ int set_device(ivfadc_index *h)
     HIP_TRY(hipSetDevice(h->device));
     return IVFADC_OK;
 }
+
+// b <- bytes of host memory, grown to fit (synchronous: h2d_copy)
+int upload(ivfadc_index *h, DevBuf &b, const void *src, size_t bytes)
+{
+    TRY(b.ensure(bytes));
+    return h2d_copy(b.p, src, bytes, h->stream);
+}
+template <class T> int upload(ivfadc_index *h, DevBuf &b, const std::vector<T> &v) { return upload(h, b, v.data(), v.size() * sizeof(T)); }
 
 // ---- events ------------------------------------------------------------------------------
 int ev_begin(ivfadc_index *h, int kind, ivfadc_index::EvPair &ep)
@@ -1661,7 +1720,7 @@ struct MutationScope {
         h = x;
         g_topo_mu.lock();
         topo = true;
-        for (ivfadc_index *v : h->views) { v->mu.m.lock(); held.push_back(v); }
+        for (ivfadc_index *v : h->views) { v->mu.lock(); held.push_back(v); }
         h->generation++;
         // searches still in flight on views read the arrays that are about to change: they finish first
         if (!h->views.empty()) TRY(set_device(h));
@@ -1671,7 +1730,7 @@ struct MutationScope {
     }
     ~MutationScope()
     {
-        for (ivfadc_index *v : held) v->mu.m.unlock();
+        for (ivfadc_index *v : held) v->mu.unlock();
         if (topo) g_topo_mu.unlock();
     }
 };
@@ -2066,7 +2125,7 @@ int build_twolevel(ivfadc_index *h)
             u64 vis = 0;
             for (int i = 0; i < 64; ++i) vis += after[i * 8 + 3] - before[i * 8 + 3];
             // the probe's counts do not belong to any search: take them out again
-            HIP_TRY(h2d_hip(h->misc.p, before, sizeof(before), h->stream));
+            TRY(h2d_copy(h->misc.p, before, sizeof(before), h->stream));
             h->tl_probe_fraction = (float)((double)vis / ((double)ns * (double)kc));
         }
         pl_.release(); pd_.release(); pb_.release();
@@ -2416,44 +2475,120 @@ static int32_t find_label16(const std::vector<uint32_t> &sorted, int ksub, int i
     return (it != e && (*it >> 16) == v) ? (int32_t)(*it & 0xFFFFu) : -1;
 }
 
-// one of code_labels (U = UInt8) and lab16 (U = UInt16) is given
+// ---- ivfadc_create: validate, then one step per operand family (the layouts themselves: pack_operands.h) --------------------------
+struct CreateArgs {
+    int d, kc, m, ksub;
+    const float *centroids, *codebooks;
+    const uint8_t *code_labels;   // one of code_labels (U = UInt8) and lab16 (U = UInt16) is given
+    const uint16_t *lab16;
+};
+
+// `ok`: the m x 256 label validity of an 8-bit handle; `inv`: the sorted label table of a 16-bit one
+static int validate_create(const CreateArgs &a, std::vector<uint8_t> &ok, std::vector<uint32_t> &inv)
+{
+    const int d = a.d, kc = a.kc, m = a.m, ksub = a.ksub;
+    if (d < 1 || kc < 1 || m < 1 || ksub < 1) return fail(IVFADC_ERR_INVALID, "d, kc, m, ksub must be >= 1");
+    if (m > d) return fail(IVFADC_ERR_ASSERT, "Number of codebooks has to be between 1 and %d", d);
+    if (d % m != 0) return fail(IVFADC_ERR_INVALID, "d %% m != 0 is not supported (rowrange for ragged sub-spaces is unverifiable)");
+    if (!a.lab16 && ksub > 256) return fail(IVFADC_ERR_INVALID, "ksub > 256 does not fit UInt8 codes");
+    if (a.lab16 && ksub > 65536) return fail(IVFADC_ERR_INVALID, "ksub > 65536 does not fit UInt16 codes");
+    if (!a.centroids || !a.codebooks || (!a.code_labels && !a.lab16)) return fail(IVFADC_ERR_INVALID, "null array");
+    // Quantizers must be finite: every bound the filters certify (coarse score filter, lower-bound tables) is computed from their norms.
+    // (Queries are not scanned -- that would cost the hot path a pass over every batch: a query with a NaN or infinite component gets
+    // unspecified neighbours, valid ids and counts, and leaves the other queries of its batch untouched; tests/test_gpu_parity.py.)
+    for (size_t i = 0; i < (size_t)d * kc; ++i)
+        if (!std::isfinite(a.centroids[i])) return fail(IVFADC_ERR_INVALID, "centroid %zu has a non-finite component", i / (size_t)d);
+    for (size_t i = 0; i < (size_t)d * ksub; ++i)
+        if (!std::isfinite(a.codebooks[i])) return fail(IVFADC_ERR_INVALID, "codebook %zu has a non-finite component", i / ((size_t)(d / m) * ksub));
+    if (a.lab16) {
+        int db = 0, dl = 0;
+        if (!sort_labels16(a.lab16, m, ksub, inv, db, dl)) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", dl, db);
+    } else {
+        ok.assign((size_t)m * 256, 0);
+        for (int i = 0; i < m; ++i)
+            for (int c = 0; c < ksub; ++c) {
+                uint8_t lab = a.code_labels[(size_t)i * ksub + c];
+                if (ok[(size_t)i * 256 + lab]) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", (int)lab, i);
+                ok[(size_t)i * 256 + lab] = 1;
+            }
+    }
+    return IVFADC_OK;
+}
+
+// the quantizers as given, the regrouped codebooks, the labels
+static int create_quantizers(ivfadc_index *h, const CreateArgs &a)
+{
+    const int d = h->d, kc = h->kc, m = h->m, ksub = h->ksub, dsub = h->dsub;
+    TRY(upload(h, h->centroids, a.centroids, (size_t)d * kc * 4));
+    TRY(upload(h, h->codebooks, a.codebooks, (size_t)d * ksub * 4));
+    // (a 16-bit handle keeps the plain layout: u16_scan_kernel reads it)
+    TRY(upload(h, h->codebooks_t, pack::codebooks_t(a.codebooks, m, ksub, dsub, dsub == 6 && (m & 1) == 0 && !a.lab16)));
+    if (m == 48 && dsub == 16) TRY(upload(h, h->codebooks_p, pack::codebooks_p(a.codebooks, m, ksub, dsub)));
+    if (a.lab16) return upload(h, h->labels, a.lab16, (size_t)m * ksub * 2);
+    return upload(h, h->labels, a.code_labels, (size_t)m * ksub);
+}
+
+// what the filtering scans of 8-bit handles read: lower-bound operands (lbscan.hip.h), narrow-field operands (nfscan.hip.h)
+static int create_filter_operands(ivfadc_index *h, const CreateArgs &a)
+{
+    const int m = h->m, ksub = h->ksub, dsub = h->dsub;
+    if (a.lab16 || ksub != 256) return IVFADC_OK;
+    if (lb_shape(m, dsub)) {
+        const pack::LbOperands o = pack::lb_operands(a.codebooks, a.code_labels, m, ksub, dsub);
+        TRY(upload(h, h->lb_f16, o.f16));
+        TRY(upload(h, h->lb_isc, o.isc));
+        TRY(upload(h, h->lb_split, o.split));
+        TRY(upload(h, h->lb_n2, o.n2));
+        TRY(upload(h, h->lb_lab, o.lab));
+        TRY(upload(h, h->lb_maxn, o.maxn));
+    }
+    if (nf_shape(m, dsub)) {
+        const pack::NfOperands o = pack::nf_operands(a.codebooks, a.code_labels, m, ksub, dsub);
+        TRY(upload(h, h->nf_n2, o.n2));
+        TRY(upload(h, h->nf_lab, o.lab));
+    }
+    return IVFADC_OK;
+}
+
+// what the coarse stage reads: norms, the latency path's regrouped copy, the bf16 and f16 forms of the matrix-core filter
+static int create_coarse_operands(ivfadc_index *h, const CreateArgs &a)
+{
+    const int d = h->d, kc = h->kc;
+    const pack::CentroidNorms cn = pack::centroid_norms(a.centroids, d, kc);
+    h->cmaxn = cn.cmaxn;
+    if ((d & 3) == 0 && (size_t)d * kc <= ((size_t)16 << 20)) TRY(upload(h, h->cent_t, pack::cent_t(a.centroids, d, kc)));
+    if ((d & 3) == 0 && kc >= 2048) {
+        const int dp = (d + 31) & ~31;
+        h->dp32 = dp;
+        const pack::CentroidF16 f = pack::centroid_f16(a.centroids, d, kc, dp);
+        if (f.scale > 0.f) {
+            TRY(upload(h, h->cent_f16, f.rows));
+            h->f16_scale = f.scale;
+        }
+        const pack::CentroidBf16 b = pack::centroid_bf16(a.centroids, d, kc, dp);
+        TRY(upload(h, h->cent_hi, b.hi));
+        TRY(upload(h, h->cent_lo, b.lo));
+    } else {
+        h->allow_bf16 = false;
+    }
+    return upload(h, h->cnorm, cn.n2);
+}
+
 static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksub, const float *centroids, const float *codebooks,
                        const uint8_t *code_labels, const uint16_t *lab16)
 {
     if (!out) return fail(IVFADC_ERR_INVALID, "out is null");
     *out = nullptr;
-    if (d < 1 || kc < 1 || m < 1 || ksub < 1) return fail(IVFADC_ERR_INVALID, "d, kc, m, ksub must be >= 1");
-    if (m > d) return fail(IVFADC_ERR_ASSERT, "Number of codebooks has to be between 1 and %d", d);
-    if (d % m != 0) return fail(IVFADC_ERR_INVALID, "d %% m != 0 is not supported (rowrange for ragged sub-spaces is unverifiable)");
-    if (!lab16 && ksub > 256) return fail(IVFADC_ERR_INVALID, "ksub > 256 does not fit UInt8 codes");
-    if (lab16 && ksub > 65536) return fail(IVFADC_ERR_INVALID, "ksub > 65536 does not fit UInt16 codes");
-    if (!centroids || !codebooks || (!code_labels && !lab16)) return fail(IVFADC_ERR_INVALID, "null array");
-    // Quantizers must be finite: every bound the filters certify (coarse score filter, lower-bound tables) is computed from their norms.
-    // (Queries are not scanned -- that would cost the hot path a pass over every batch: a query with a NaN or infinite component gets
-    // unspecified neighbours, valid ids and counts, and leaves the other queries of its batch untouched; tests/test_gpu_parity.py.)
-    for (size_t i = 0; i < (size_t)d * kc; ++i)
-        if (!std::isfinite(centroids[i])) return fail(IVFADC_ERR_INVALID, "centroid %zu has a non-finite component", i / (size_t)d);
-    for (size_t i = 0; i < (size_t)d * ksub; ++i)
-        if (!std::isfinite(codebooks[i])) return fail(IVFADC_ERR_INVALID, "codebook %zu has a non-finite component", i / ((size_t)(d / m) * ksub));
+    const CreateArgs a{d, kc, m, ksub, centroids, codebooks, code_labels, lab16};
     std::vector<uint8_t> ok;
     std::vector<uint32_t> inv;
-    if (lab16) {
-        int db = 0, dl = 0;
-        if (!sort_labels16(lab16, m, ksub, inv, db, dl)) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", dl, db);
-    } else {
-        ok.assign((size_t)m * 256, 0);
-        for (int i = 0; i < m; ++i)
-            for (int c = 0; c < ksub; ++c) {
-                uint8_t lab = code_labels[(size_t)i * ksub + c];
-                if (ok[(size_t)i * 256 + lab]) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", (int)lab, i);
-                ok[(size_t)i * 256 + lab] = 1;
-            }
-    }
+    TRY(validate_create(a, ok, inv));
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail(IVFADC_ERR_HIP, "no HIP device");
     if (device < 0 || device >= ndev) return fail(IVFADC_ERR_INVALID, "device %d out of range [0,%d)", device, ndev);
-    ivfadc_index *h = new ivfadc_index();
+    struct Destroy { void operator()(ivfadc_index *p) const { ivfadc_destroy(p); } };
+    std::unique_ptr<ivfadc_index, Destroy> h(new ivfadc_index());   // destroyed on every early return
     h->device = device;
     h->d = d; h->kc = kc; h->m = m; h->ksub = ksub; h->dsub = d / m;
     h->u16 = lab16 != nullptr;
@@ -2470,248 +2605,23 @@ static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksu
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     hipDeviceProp_t prop;
     if (e == hipSuccess) e = hipGetDeviceProperties(&prop, device);
-    if (e != hipSuccess) { delete h; return fail(IVFADC_ERR_HIP, "device init failed: %s", hipGetErrorString(e)); }
+    if (e != hipSuccess) return fail(IVFADC_ERR_HIP, "device init failed: %s", hipGetErrorString(e));
     h->num_cu = prop.multiProcessorCount > 0 ? prop.multiProcessorCount : 256;
-    int rc = h->centroids.ensure((size_t)d * kc * 4);
-    if (rc == IVFADC_OK) rc = h->codebooks.ensure((size_t)d * ksub * 4);
-    if (rc == IVFADC_OK) rc = h->codebooks_t.ensure((size_t)m * (((d / m) + 3) & ~3) * ksub * 4);
-    if (rc == IVFADC_OK) rc = h->labels.ensure((size_t)m * ksub * (lab16 ? 2 : 1));
-    if (rc == IVFADC_OK) {
-        e = h2d_hip(h->centroids.p, centroids, (size_t)d * kc * 4, h->stream);
-        if (e == hipSuccess) e = h2d_hip(h->codebooks.p, codebooks, (size_t)d * ksub * 4, h->stream);
-        if (e == hipSuccess) {
-            // regrouped copy for the table build (IndexView::codebooks_t)
-            const int dsub = d / m, dp = (dsub + 3) & ~3;   // [m][dp / 4][ksub][4], zero-padded
-            std::vector<float> t((size_t)m * dp * ksub, 0.0f);
-            if (dsub == 6 && (m & 1) == 0 && !lab16) {   // (a 16-bit handle keeps the plain layout: u16_scan_kernel reads it)
-                // pair-packed (build_tables_t, DSUB == 6): [m / 2][3][ksub][4], element e = 0..11 of pair p, codeword c =
-                // dimension e of sub-quantizer 2p (e < 6) or dimension e - 6 of sub-quantizer 2p + 1
-                for (int p = 0; p < m / 2; ++p)
-                    for (int c = 0; c < ksub; ++c)
-                        for (int e2 = 0; e2 < 12; ++e2) {
-                            const int ii = 2 * p + e2 / 6, x = e2 % 6;
-                            t[(size_t)p * 12 * ksub + ((size_t)(e2 / 4) * ksub + c) * 4 + (e2 % 4)] = codebooks[((size_t)ii * ksub + c) * dsub + x];
-                        }
-            } else
-            for (int ii = 0; ii < m; ++ii)
-                for (int c = 0; c < ksub; ++c)
-                    for (int x = 0; x < dsub; ++x)
-                        t[(size_t)ii * dp * ksub + ((size_t)(x / 4) * ksub + c) * 4 + (x % 4)] =
-                            codebooks[((size_t)ii * ksub + c) * dsub + x];
-            e = h2d_hip(h->codebooks_t.p, t.data(), t.size() * 4, h->stream);
-            if (e == hipSuccess && m == 48 && dsub == 16) {
-                // pair-interleaved copy for the packed-FP32 table build of the m = 48 query-major kernel (IndexView::codebooks_p)
-                std::vector<float> pp((size_t)m * dsub * ksub);
-                for (int p = 0; p < m / 2; ++p)
-                    for (int c = 0; c < ksub; ++c)
-                        for (int x = 0; x < dsub; ++x)
-                            for (int hh = 0; hh < 2; ++hh)
-                                pp[(size_t)p * dsub * 2 * ksub + ((size_t)(x / 2) * ksub + c) * 4 + (x % 2) * 2 + hh] =
-                                    codebooks[((size_t)(2 * p + hh) * ksub + c) * dsub + x];
-                rc = h->codebooks_p.ensure(pp.size() * 4);
-                if (rc == IVFADC_OK) e = h2d_hip(h->codebooks_p.p, pp.data(), pp.size() * 4, h->stream);
-            }
-        }
-        if (e == hipSuccess)
-            e = lab16 ? h2d_hip(h->labels.p, lab16, (size_t)m * ksub * 2, h->stream) : h2d_hip(h->labels.p, code_labels, (size_t)m * ksub, h->stream);
-        if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-        if (rc == IVFADC_OK && !lab16 && lb_shape(m, d / m) && ksub == 256) {
-            // operands of the lower-bound table build (lbscan.hip.h), everything in LABEL order (table slot = code byte):
-            // split[ii][g][p][lane] = 8 bf16 of label 64 g + lane -- parts p < NP / 2: hi pieces of dimensions 8 p .. 8 p + 7,
-            // the others the lo pieces (x = hi + lo + O(2^-18 |x|)); n2 = ||codeword||^2 in double, rounded once
-            const int dsub = d / m, dsp = (dsub + 7) & ~7, np = dsp / 4;
-            auto to_bf16 = [](float x) {
-                uint32_t b;
-                memcpy(&b, &x, 4);
-                return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-            };
-            std::vector<uint16_t> sp((size_t)m * 4 * np * 64 * 8, 0);
-            std::vector<float> n2((size_t)m * 256, 0.0f), lab((size_t)m * 256 * dsub, 0.0f), mx((size_t)m, 0.0f);
-            for (int ii = 0; ii < m; ++ii) {
-                double mxn = 0.0;
-                for (int c = 0; c < ksub; ++c) {
-                    const int L = code_labels[(size_t)ii * ksub + c], g = L >> 6, ln = L & 63;
-                    const float *cw = codebooks + ((size_t)ii * ksub + c) * dsub;
-                    double acc = 0.0;
-                    for (int t = 0; t < dsub; ++t) {
-                        const float v = cw[t];
-                        acc += (double)v * v;
-                        lab[((size_t)ii * 256 + L) * dsub + t] = v;
-                        const uint16_t hb = to_bf16(v);
-                        const uint32_t hb32 = (uint32_t)hb << 16;
-                        float hf;
-                        memcpy(&hf, &hb32, 4);
-                        const uint16_t lb16 = to_bf16(v - hf);
-                        const size_t base = (((size_t)(ii * 4 + g) * np) * 64) * 8;
-                        sp[base + ((size_t)(t >> 3) * 64 + ln) * 8 + (t & 7)] = hb;
-                        sp[base + ((size_t)(np / 2 + (t >> 3)) * 64 + ln) * 8 + (t & 7)] = lb16;
-                    }
-                    n2[(size_t)ii * 256 + L] = (float)acc;
-                    mxn = std::max(mxn, acc);
-                }
-                mx[ii] = (float)(std::sqrt(mxn) * (1.0 + 1e-6));
-            }
-            {
-                // f16 operand of the one-product build: [ii][g][p][lane] = 8 f16 of label 64 g + lane, dimensions 8 p .. 8 p + 7, scaled by
-                // 2^e_ii with max |cb 2^e_ii| in [2^10, 2^11]
-                const int nph = dsp / 8;
-                std::vector<uint16_t> hf((size_t)m * 4 * nph * 64 * 8, 0);
-                std::vector<float> isc((size_t)m, 1.0f);
-                for (int ii = 0; ii < m; ++ii) {
-                    double mxa = 0.0;
-                    for (int c = 0; c < ksub; ++c)
-                        for (int t = 0; t < dsub; ++t) mxa = std::max(mxa, (double)std::fabs(codebooks[((size_t)ii * ksub + c) * dsub + t]));
-                    int ex = 0;
-                    if (mxa > 0.0) ex = std::max(-100, std::min(100, (int)std::floor(std::log2(2048.0 / mxa))));
-                    const float sc = std::ldexp(1.0f, ex);
-                    isc[ii] = std::ldexp(1.0f, -ex);
-                    for (int c = 0; c < ksub; ++c) {
-                        const int L = code_labels[(size_t)ii * ksub + c], g = L >> 6, ln = L & 63;
-                        for (int t = 0; t < dsub; ++t) {
-                            const _Float16 v = (_Float16)(codebooks[((size_t)ii * ksub + c) * dsub + t] * sc);
-                            memcpy(&hf[((((size_t)(ii * 4 + g) * nph) + (t >> 3)) * 64 + ln) * 8 + (t & 7)], &v, 2);
-                        }
-                    }
-                }
-                rc = h->lb_f16.ensure(hf.size() * 2);
-                if (rc == IVFADC_OK) rc = h->lb_isc.ensure(isc.size() * 4);
-                if (rc == IVFADC_OK) {
-                    e = h2d_hip(h->lb_f16.p, hf.data(), hf.size() * 2, h->stream);
-                    if (e == hipSuccess) e = h2d_hip(h->lb_isc.p, isc.data(), isc.size() * 4, h->stream);
-                    if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-                }
-            }
-            if (rc == IVFADC_OK) rc = h->lb_split.ensure(sp.size() * 2);
-            if (rc == IVFADC_OK) rc = h->lb_n2.ensure(n2.size() * 4);
-            if (rc == IVFADC_OK) rc = h->lb_lab.ensure(lab.size() * 4);
-            if (rc == IVFADC_OK) rc = h->lb_maxn.ensure(mx.size() * 4);
-            if (rc == IVFADC_OK) {
-                e = h2d_hip(h->lb_split.p, sp.data(), sp.size() * 2, h->stream);
-                if (e == hipSuccess) e = h2d_hip(h->lb_n2.p, n2.data(), n2.size() * 4, h->stream);
-                if (e == hipSuccess) e = h2d_hip(h->lb_lab.p, lab.data(), lab.size() * 4, h->stream);
-                if (e == hipSuccess) e = h2d_hip(h->lb_maxn.p, mx.data(), mx.size() * 4, h->stream);
-                if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-            }
-        }
-    }
-    if (rc == IVFADC_OK && !lab16 && nf_shape(m, d / m) && ksub == 256) {
-        // operands of the narrow-field list-major kernel (nfscan.hip.h): ||codeword||^2 by CODEWORD index (double, rounded once) for the
-        // filter tables, and the f32 codewords in LABEL order (table slot = code byte) for the exact sums of what the filter lets through
-        const int dsub = d / m;
-        std::vector<float> n2((size_t)m * 256 + m, 0.0f), lab((size_t)m * 256 * dsub, 0.0f);   // n2[m][256], then max ||codeword||^2 per block
-        for (int ii = 0; ii < m; ++ii)
-            for (int c = 0; c < ksub; ++c) {
-                const int L = code_labels[(size_t)ii * ksub + c];
-                const float *cw = codebooks + ((size_t)ii * ksub + c) * dsub;
-                double acc = 0.0;
-                for (int t = 0; t < dsub; ++t) {
-                    acc += (double)cw[t] * cw[t];
-                    lab[((size_t)ii * 256 + L) * dsub + t] = cw[t];
-                }
-                n2[(size_t)ii * 256 + c] = (float)acc;
-                n2[(size_t)m * 256 + ii] = std::max(n2[(size_t)m * 256 + ii], (float)(acc * (1.0 + 1e-6)));
-            }
-        rc = h->nf_n2.ensure(n2.size() * 4);
-        if (rc == IVFADC_OK) rc = h->nf_lab.ensure(lab.size() * 4);
-        if (rc == IVFADC_OK) {
-            hipError_t e2 = h2d_hip(h->nf_n2.p, n2.data(), n2.size() * 4, h->stream);
-            if (e2 == hipSuccess) e2 = h2d_hip(h->nf_lab.p, lab.data(), lab.size() * 4, h->stream);
-            if (e2 != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e2));
-        }
-    }
-    if (rc == IVFADC_OK) {
-        // ||c||^2 in double, rounded once: error <= u ||c||^2 (see refine_probes)
-        std::vector<float> cn((size_t)kc);
-        double mx = 0.0;
-        for (int c = 0; c < kc; ++c) {
-            double acc = 0.0;
-            for (int i = 0; i < d; ++i) acc += (double)centroids[(size_t)c * d + i] * centroids[(size_t)c * d + i];
-            cn[c] = (float)acc;
-            mx = std::max(mx, acc);
-        }
-        h->cmaxn = (float)(std::sqrt(mx) * (1.0 + 1e-6));
-        if ((d & 3) == 0 && (size_t)d * kc <= ((size_t)16 << 20)) {
-            // regrouped copy for the latency path's coarse search (smallq.hip.h: coarse_lane_kernel, and the search inside sq_kernel): [d / 4][kc][4]
-            std::vector<float> ct((size_t)d * kc);
-            for (int c = 0; c < kc; ++c)
-                for (int i = 0; i < d; ++i) ct[((size_t)(i >> 2) * kc + c) * 4 + (i & 3)] = centroids[(size_t)c * d + i];
-            rc = h->cent_t.ensure(ct.size() * 4);
-            if (rc == IVFADC_OK) {
-                e = h2d_hip(h->cent_t.p, ct.data(), ct.size() * 4, h->stream);
-                if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-            }
-        }
-        // bf16 split of the centroids for coarse_bf16_kernel: x = hi + lo + O(2^-18 |x|), rows zero-padded to 32 dimensions
-        if ((d & 3) == 0 && kc >= 2048) {
-            const int dp = (d + 31) & ~31;
-            h->dp32 = dp;
-            auto to_bf16 = [](float x) {
-                uint32_t b;
-                memcpy(&b, &x, 4);
-                return (uint16_t)((b + 0x7FFFu + ((b >> 16) & 1u)) >> 16);
-            };
-            std::vector<uint16_t> hi((size_t)kc * dp, 0), lo((size_t)kc * dp, 0);
-            for (int c = 0; c < kc; ++c)
-                for (int i = 0; i < d; ++i) {
-                    const float v = centroids[(size_t)c * d + i];
-                    const uint16_t hb = to_bf16(v);
-                    const uint32_t hb32 = (uint32_t)hb << 16;
-                    float hf;
-                    memcpy(&hf, &hb32, 4);
-                    hi[(size_t)c * dp + i] = hb;
-                    lo[(size_t)c * dp + i] = to_bf16(v - hf);
-                }
-            {
-                // the f16 form: one power-of-two scale for the whole quantizer (and for the queries, which live in the same space)
-                double maxabs = 0.0;
-                for (size_t i = 0; i < (size_t)kc * d; ++i) maxabs = std::max(maxabs, (double)std::fabs(centroids[i]));
-                if (maxabs > 0.0 && std::isfinite(maxabs)) {
-                    const int ex = (int)std::floor(std::log2(4096.0 / maxabs));
-                    if (ex > -100 && ex < 100) {
-                        const float sc = std::ldexp(1.0f, ex);
-                        std::vector<uint16_t> hf((size_t)kc * dp, 0);
-                        for (int c = 0; c < kc; ++c)
-                            for (int i = 0; i < d; ++i) {
-                                const _Float16 v = (_Float16)(centroids[(size_t)c * d + i] * sc);
-                                memcpy(&hf[(size_t)c * dp + i], &v, 2);
-                            }
-                        rc = h->cent_f16.ensure(hf.size() * 2);
-                        if (rc == IVFADC_OK) {
-                            e = h2d_hip(h->cent_f16.p, hf.data(), hf.size() * 2, h->stream);
-                            if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-                            else h->f16_scale = sc;
-                        }
-                    }
-                }
-            }
-            if (rc == IVFADC_OK) rc = h->cent_hi.ensure(hi.size() * 2);
-            if (rc == IVFADC_OK) rc = h->cent_lo.ensure(lo.size() * 2);
-            if (rc == IVFADC_OK) {
-                e = h2d_hip(h->cent_hi.p, hi.data(), hi.size() * 2, h->stream);
-                if (e == hipSuccess) e = h2d_hip(h->cent_lo.p, lo.data(), lo.size() * 2, h->stream);
-                if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-            }
-        } else {
-            h->allow_bf16 = false;
-        }
-        if (getenv("IVFADC_NO_PRUNE") != nullptr) h->allow_prune = false;
-        if (rc == IVFADC_OK) rc = h->cnorm.ensure((size_t)kc * 4);
-        if (rc == IVFADC_OK) {
-            e = h2d_hip(h->cnorm.p, cn.data(), (size_t)kc * 4, h->stream);
-            if (e != hipSuccess) rc = fail(IVFADC_ERR_HIP, "upload failed: %s", hipGetErrorString(e));
-        }
-        h->allow_filt = getenv("IVFADC_EXACT_TABLES") == nullptr;
-        h->allow_mfma = getenv("IVFADC_COARSE_EXACT") == nullptr;
-    }
-    if (rc != IVFADC_OK) { ivfadc_destroy(h); return rc; }
+    TRY(create_quantizers(h.get(), a));
+    TRY(create_filter_operands(h.get(), a));
+    TRY(create_coarse_operands(h.get(), a));
+    if (getenv("IVFADC_NO_PRUNE") != nullptr) h->allow_prune = false;
+    h->allow_filt = getenv("IVFADC_EXACT_TABLES") == nullptr;
+    h->allow_mfma = getenv("IVFADC_COARSE_EXACT") == nullptr;
     // an index starts with kc empty lists
     h->h_len.assign((size_t)kc, 0);
     h->hl_codes.assign((size_t)kc, {});
     h->hl_ids.assign((size_t)kc, {});
     h->dirty = true;
-    *out = h;
+    *out = h.release();
     return IVFADC_OK;
 }
+
 
 int ivfadc_create(ivfadc_t **out, int device, int d, int kc, int m, int ksub, const float *centroids, const float *codebooks,
                   const uint8_t *code_labels)
@@ -2743,8 +2653,8 @@ void ivfadc_destroy(ivfadc_t *h)
     // (destroying a handle that another thread is still calling into is the caller's bug; what IS guarded is the topology: a view leaving
     // its index's list while a mutator of that index walks it, an index telling its views that it is gone)
     std::unique_lock<std::recursive_mutex> topo(g_topo_mu);
-    h->mu.m.lock();
-    h->mu.m.unlock();   // a call still running on this handle (a mutator holding a view's mutex) has finished
+    h->mu.lock();
+    h->mu.unlock();   // a call still running on this handle (a mutator holding a view's mutex) has finished
     (void)hipSetDevice(h->device);
     if (h->pipe_view) { ivfadc_destroy(h->pipe_view); h->pipe_view = nullptr; }
     if (h->fb_ev) { (void)hipEventSynchronize(h->fb_ev); (void)hipEventDestroy(h->fb_ev); }
@@ -2756,7 +2666,7 @@ void ivfadc_destroy(ivfadc_t *h)
     // (under each view's own mutex -- topology first, then the view, the order of every mutator: a view call reads its link and the
     // generation with nothing but its own mutex held)
     for (ivfadc_index *v : h->views) {
-        std::lock_guard<std::recursive_mutex> vl(v->mu.m);
+        std::lock_guard<std::recursive_mutex> vl(v->mu);
         v->orphan = true;
         v->view_of = nullptr;
     }
@@ -2769,11 +2679,7 @@ void ivfadc_destroy(ivfadc_t *h)
     if (h->comm || h->comm_stream) (void)ivfadc_comm_destroy(h);
     for (auto &ep : h->pending) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
     for (auto &ep : h->free_ev) { (void)hipEventDestroy(ep.a); (void)hipEventDestroy(ep.b); }
-    DevBuf *bufs[] = {&h->lb_f16, &h->lb_isc, &h->cent_f16, &h->q_f16, &h->q_flags, &h->tl_centres, &h->tl_off, &h->tl_rad, &h->tl_cent, &h->tl_slot, &h->tl_gdist, &h->cdist2, &h->pre_list, &h->pre_dc, &h->cent_t, &h->sq_keys, &h->sq_cnt, &h->sq_arrive, &h->lb_split, &h->lb_n2, &h->lb_lab, &h->lb_maxn, &h->nf_n2, &h->nf_lab, &h->wg8_tabs, &h->wg8_items, &h->centroids, &h->codebooks, &h->codebooks_t, &h->codebooks_p, &h->labels, &h->cnorm, &h->tmin, &h->tlist, &h->cent_hi, &h->cent_lo, &h->q_hi, &h->q_lo, &h->gen_a, &h->gen_b, &h->gen_tmp, &h->gen_off, &h->gen_tot, &h->list_pos, &h->list_len, &h->list_codeoff, &h->codes, &h->ids, &h->app_stage, &h->q_stage,
-                      &h->cdist, &h->probe_list, &h->probe_dc, &h->probe_base, &h->list_cnt, &h->bucket_off, &h->wi_off, &h->cursor,
-                      &h->bucket_items, &h->misc, &h->qthr, &h->part_keys, &h->part_cnt, &h->out_ids, &h->out_dists, &h->out_counts,
-                      &h->assign, &h->enc_codes, &h->pts_stage, &h->dbg};
-    for (DevBuf *b : bufs) b->release();
+    h->each_buf([](DevBuf &b) { b.release(); });
     h->pin_in.release();
     h->pin_out.release();
     if (h->stream && h->own_stream) (void)hipStreamDestroy(h->stream);
@@ -2832,6 +2738,8 @@ static int ensure_overlap(const hipStream_t *fixed, int nfixed, hipStream_t *can
 }
 
 // A read-only view of `src`: the same device arrays (quantizers, derived tables, lists), a stream and a workspace of its own.
+// The view is a fresh handle that is GIVEN what it shares: the shape, the quantizers and the device lists as aliases, the settings, and
+// the few scalars named below.  Its workspace and everything in HandleState start from their defaults; the host mirror is never touched.
 static int clone_view(ivfadc_index *src, ivfadc_index **out)
 {
     *out = nullptr;
@@ -2840,103 +2748,46 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
     if (src->dirty) TRY(upload_lists(src));   // the device copy is what the view shares
     if (!src->have_lists) return fail(IVFADC_ERR_STATE, "no inverted lists set");
     HIP_TRY(hipStreamSynchronize(src->stream));   // uploads and in-place edits have landed
-    // (the host mirror stays with the index: moved aside while the struct is copied)
-    std::vector<std::vector<uint8_t>> keep_codes;
-    std::vector<std::vector<uint32_t>> keep_ids;
-    keep_codes.swap(src->hl_codes);
-    keep_ids.swap(src->hl_ids);
-    ivfadc_index *v = nullptr;
-    try { v = new ivfadc_index(*src); } catch (...) { keep_codes.swap(src->hl_codes); keep_ids.swap(src->hl_ids); throw; }
-    keep_codes.swap(src->hl_codes);
-    keep_ids.swap(src->hl_ids);
-    DevBuf *shared[] = {&v->lb_f16, &v->lb_isc, &v->cent_f16, &v->tl_centres, &v->tl_off, &v->tl_rad, &v->tl_cent, &v->tl_slot, &v->centroids, &v->codebooks, &v->codebooks_t, &v->codebooks_p, &v->labels, &v->cnorm, &v->lb_split, &v->lb_n2, &v->lb_lab,
-                        &v->lb_maxn, &v->nf_n2, &v->nf_lab, &v->cent_t, &v->cent_hi, &v->cent_lo, &v->list_pos, &v->list_len, &v->list_codeoff,
-                        &v->codes, &v->ids};
-    for (DevBuf *b : shared) b->alias();
-    DevBuf *scratch[] = {&v->wg8_tabs, &v->wg8_items, &v->q_f16, &v->q_flags, &v->tl_gdist, &v->cdist2, &v->pre_list, &v->pre_dc, &v->sq_keys, &v->sq_cnt, &v->sq_arrive, &v->tmin, &v->tlist, &v->q_hi, &v->q_lo, &v->gen_a, &v->gen_b, &v->gen_tmp,
-                         &v->gen_off, &v->gen_tot, &v->app_stage, &v->q_stage, &v->cdist, &v->probe_list, &v->probe_dc, &v->probe_base, &v->list_cnt,
-                         &v->bucket_off, &v->wi_off, &v->cursor, &v->bucket_items, &v->misc, &v->qthr, &v->part_keys, &v->part_cnt, &v->out_ids,
-                         &v->out_dists, &v->out_counts, &v->assign, &v->enc_codes, &v->pts_stage, &v->dbg};
-    for (DevBuf *b : scratch) b->forget();
-    v->pin_in.forget();
-    v->pin_out.forget();
-    v->pending.clear();
-    v->free_ev.clear();
-    v->views.clear();
-    v->n_views.store(0);
-    v->my_ticket = -1;
-    v->fb_pin.forget();      // (a view has counters, snapshots and an event of its own; it starts from its index's estimate)
-    v->fb_ev = nullptr;
-    v->fb_pending = false;
-    v->fb_countdown = 0;
-    v->fb_sp = v->fb_pp = 0;
-    v->pipe_view = nullptr;
-    v->pipe_ev_in = nullptr;
-    v->copy_stream = nullptr;
-    v->copy_probed_a = v->copy_probed_b = nullptr;
-    v->ingest_ev.clear();
-    v->hstats = ivfadc_host_stats{};
-    v->carry_queries = v->carry_scanned = v->carry_pruned = v->carry_surv = v->carry_fallbacks = v->carry_launches = 0;
-    v->comm = nullptr;
-    v->comm_stream = nullptr;
-    v->comm_ready = nullptr;
-    for (int i = 0; i < ivfadc_index::COMM_SLOTS; ++i) { v->comm_done[i] = nullptr; v->comm_busy[i] = false; }
-    v->comm_ranks = 0;
-    v->comm_rank = 0;
-    v->comm_collectives = 0;
-    v->comm_seq = 0;
-    v->comm_waited = 0;
-    for (int i = 0; i < ivfadc_index::COMM_SLOTS; ++i) v->comm_slot_seq[i] = 0;
-    v->hint_ev = nullptr;
-    v->hint_q = v->pf_q = v->avail_q = nullptr;
-    v->hint_nq = v->pf_nq = v->avail_nq = 0;
-    v->hint_token = v->pf_token = v->cur_token = 0;
-    v->partial_keys = nullptr;
-    v->partial_nq = -1;
-    v->qthr_armed = 0;
-    v->list_cnt_armed = false;
-    v->profiling = false;
-    v->profiling_level = 0;
-    v->stats = ivfadc_stats{};
-    v->scanned_base = v->fallback_base = v->pruned_base = v->surv_base = 0;
-    v->visited_base = 0;
-    v->inplace_appends = 0;
-    v->stream = nullptr;
-    v->own_stream = true;
+    std::unique_ptr<ivfadc_index> v(new ivfadc_index());   // (plain delete until it is handed out: it owns no device memory)
+    static_cast<Dims &>(*v) = *src;
+    static_cast<Quantizers &>(*v) = *src;
+    static_cast<Lists &>(*v) = *src;
+    v->Quantizers::each_buf([](DevBuf &b) { b.alias(); });
+    v->Lists::each_buf([](DevBuf &b) { b.alias(); });
+    static_cast<SearchConfig &>(*v) = *src;
+    v->prune_est = src->prune_est;   // (a view has counters, snapshots and an event of its own; it starts from its index's estimate)
+    v->fn_cfg = src->fn_cfg;         // what the index has already asked the runtime about its kernels holds for the view's launches
+    // what the index's last coarse launch and partial search left behind has always come along
+    v->tlist_ldq = src->tlist_ldq; v->tmin_tiles = src->tmin_tiles; v->tmin_tile_w = src->tmin_tile_w;
+    v->last_coarse_f16 = src->last_coarse_f16; v->last_coarse_bf16 = src->last_coarse_bf16; v->last_listed = src->last_listed;
+    v->partial_w = src->partial_w; v->partial_K = src->partial_K;
     v->is_view = true;
     v->view_of = src;
     v->view_gen = src->generation;
     const hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
-    if (e != hipSuccess) {
-        delete v;   // (nothing of its own yet: every buffer is an alias or empty)
-        return fail(IVFADC_ERR_HIP, "hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
-    }
+    if (e != hipSuccess) return fail(IVFADC_ERR_HIP, "hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
     // the point of a view is a second batch IN FLIGHT: its stream must not share a hardware queue with the index's
     {
         const hipStream_t fixed[1] = {src->stream};
         const int rc = ensure_overlap(fixed, 1, &v->stream, &src->hstats.streams_replaced);
-        if (rc != IVFADC_OK) { (void)hipStreamDestroy(v->stream); delete v; return rc; }
+        if (rc != IVFADC_OK) { (void)hipStreamDestroy(v->stream); return rc; }
     }
     {
         std::lock_guard<std::recursive_mutex> topo(g_topo_mu);
-        src->views.push_back(v);
+        src->views.push_back(v.get());
         src->n_views.fetch_add(1);
     }
-    *out = v;
+    *out = v.release();
     return IVFADC_OK;
 }
 
 // settings that change how a search runs, copied to the internal second lane before every use
 static void copy_search_config(ivfadc_index *dst, const ivfadc_index *src)
 {
-    dst->wg8_mode = src->wg8_mode; dst->wg8_wide = src->wg8_wide; dst->u16_wide = src->u16_wide; dst->u16_tables = src->u16_tables;
-    dst->allow_nf = src->allow_nf; dst->allow_sq = src->allow_sq; dst->sq_inside = src->sq_inside; dst->allow_lb = src->allow_lb;
-    dst->force_lb = src->force_lb; dst->allow_bf16 = src->allow_bf16; dst->allow_f16 = src->allow_f16; dst->lb_use_f16 = src->lb_use_f16; dst->allow_prune = src->allow_prune; dst->allow_listed = src->allow_listed;
-    dst->allow_filt = src->allow_filt; dst->allow_mfma = src->allow_mfma; dst->mfma_min_kc = src->mfma_min_kc; dst->ws_budget = src->ws_budget;
-    dst->force_qg = src->force_qg; dst->force_chunk = src->force_chunk;
-    dst->part_n = src->part_n; dst->part_i = src->part_i;
-    dst->tl_use = src->tl_use && dst->tl_cent.p != nullptr; dst->tl_mode = src->tl_mode;
+    static_cast<SearchConfig &>(*dst) = *src;
+    dst->tl_use = src->tl_use && dst->tl_cent.p != nullptr;
 }
+
 
 int ivfadc_clone_view(ivfadc_t *h, ivfadc_t **out)
 try {
@@ -3727,7 +3578,6 @@ try {
         if (!h->pipe_ev_in) HIP_TRY(hipEventCreateWithFlags(&h->pipe_ev_in, hipEventDisableTiming));
         lane2 = h->pipe_view;
         copy_search_config(lane2, h);
-        lane2->own_token = 0;
         HIP_TRY(hipEventRecord(h->pipe_ev_in, h->stream));            // in-place edits of the lists queued on this handle's stream come first
         HIP_TRY(hipStreamWaitEvent(lane2->stream, h->pipe_ev_in, 0));
     }
