@@ -213,6 +213,32 @@ int ivfadc_reset_host_stats(ivfadc_t *h);
  * Destroy views with ivfadc_destroy, before or after h (a view that outlives h refuses to search).                                  */
 int ivfadc_clone_view(ivfadc_t *h, ivfadc_t **out_view);
 
+/* A SUBSET view: filtered search (a tenant, a category, a time window, "everything except what I already showed") without touching h.
+ * Stands for: deleteat! of utils.jl:98-99 applied, on a copy of the lists, to every entry that is NOT selected -- WITHOUT the
+ * _shift_inverse_index! that delete_from_index! adds (utils.jl:101-104): the kept entries stay in their stored order within each list
+ * and keep their stored ids; the quantizers are h's.  A search on the view is knn_search (index.jl:204-258) on those lists: it visits in
+ * (probe rank, list position) order, breaks ties by that order and returns fewer than K results where the probed lists hold fewer
+ * points.  The view behaves exactly as a handle that was given the filtered lists through ivfadc_set_lists, and every scan form serves it.
+ *   bitmap      over STORED ids (the 0-based ones a search returns): id i is selected iff i < nbits and bit (i & 31) of word bits[i >> 5]
+ *               is set; bits holds ceil(nbits / 32) words, little-endian within a word.  Entries that share an id are all kept or all
+ *               dropped; ids at or above nbits are not selected.  nbits <= 2^32.  nbits == 0 is the empty subset (bits may be NULL):
+ *               a valid index with n = 0, every query returns count 0.
+ *   out_n       (may be NULL) the number of entries kept.
+ *   _device     the bitmap lies in device memory of h's GPU and is complete when the call is made (the compaction runs on h's stream).
+ * The compaction runs on the device from h's device arrays (two kernels, csrc/subset.hip.h; no host mirror involved), so it serves
+ * UInt8 and UInt16 handles, :opq-loaded handles and device-synthesised lists alike; the call is blocking.  A list partition set on h
+ * is copied, like every setting.
+ * View rules, as for ivfadc_clone_view: the quantizers and derived tables are SHARED with h, the lists are the view's own (freed by
+ * ivfadc_destroy), stream and workspace are its own.  The view is read-only: every mutator, ivfadc_get_lists and ivfadc_save_index
+ * return IVFADC_ERR_STATE; ivfadc_ntotal reports the subset.  Any change to h afterwards makes it refuse to search, as does destroying h
+ * (IVFADC_ERR_STATE); a mutator of h first waits for the view's stream.  Every search entry a plain view serves, a subset view serves.
+ * IVFADC_ERR_STATE: h is itself a view (plain or subset: take the subset from the index).  (A handle that was never given lists is an
+ * empty index, as for ivfadc_search, and so is every subset of it.)  IVFADC_ERR_INVALID, before any device call: NULL h, NULL out_view,
+ * NULL bits with nbits > 0, nbits > 2^32.
+ * Not covered: predicates evaluated per query inside the scan, and subsets of ivfadc_mg_* handles.                               */
+int ivfadc_clone_subset(ivfadc_t *h, const uint32_t *bits, uint64_t nbits, ivfadc_t **out_view, int64_t *out_n);
+int ivfadc_clone_subset_device(ivfadc_t *h, const uint32_t *d_bits, uint64_t nbits, ivfadc_t **out_view, int64_t *out_n);
+
 /* Same, with every buffer already resident in device memory of the handle's GPU.
  * Asynchronous on the handle's stream; pair with ivfadc_sync().                          */
 int ivfadc_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w,

@@ -11,6 +11,7 @@
 #include "generic.hip.h"
 #include "u16scan.hip.h"
 #include "twolevel.hip.h"
+#include "subset.hip.h"
 #include "pack_operands.h"
 
 #include <algorithm>
@@ -135,6 +136,14 @@ struct DevBuf {
         }
         if (e != hipSuccess) { p = nullptr; return fail(IVFADC_ERR_HIP, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e)); }
         bytes = want;
+        return IVFADC_OK;
+    }
+    // exactly `need` bytes, for a buffer that is written once and never grows (a subset view's lists); the buffer must be empty
+    int alloc_exact(size_t need)
+    {
+        const hipError_t e = hipMalloc(&p, need);
+        if (e != hipSuccess) { p = nullptr; return fail(IVFADC_ERR_HIP, "hipMalloc(%zu) failed: %s", need, hipGetErrorString(e)); }
+        bytes = need;
         return IVFADC_OK;
     }
     void release()
@@ -340,7 +349,8 @@ struct Quantizers {
     }
 };
 
-// the inverted lists as the device holds them: a view aliases the buffers and copies the layout
+// the inverted lists as the device holds them: a view aliases the buffers and copies the layout; a subset view (ivfadc_clone_subset) OWNS
+// compacted ones of its own, and the scalars here are then the subset's
 struct Lists {
     int64_t n = 0;
     bool have_lists = false;
@@ -1701,7 +1711,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
 // mutators: not on a view; every other holder of the device arrays learns that they changed
 int check_mutable(ivfadc_index *h, const char *what)
 {
-    if (h->is_view) return fail(IVFADC_ERR_STATE, "%s: this handle is a read-only view (ivfadc_clone_view)", what);
+    if (h->is_view) return fail(IVFADC_ERR_STATE, "%s: this handle is a read-only view (ivfadc_clone_view / ivfadc_clone_subset)", what);
     return IVFADC_OK;
 }
 
@@ -2737,23 +2747,24 @@ static int ensure_overlap(const hipStream_t *fixed, int nfixed, hipStream_t *can
     return rc;
 }
 
-// A read-only view of `src`: the same device arrays (quantizers, derived tables, lists), a stream and a workspace of its own.
-// The view is a fresh handle that is GIVEN what it shares: the shape, the quantizers and the device lists as aliases, the settings, and
-// the few scalars named below.  Its workspace and everything in HandleState start from their defaults; the host mirror is never touched.
-static int clone_view(ivfadc_index *src, ivfadc_index **out)
+// ---- views: clone_view (the index's lists, aliased) and clone_subset (lists of the view's own), from three shared steps ------------------
+// what every view starts from: the index's device copy is current and at rest
+static int view_source_ready(ivfadc_index *src, const char *of_a_view)
 {
-    *out = nullptr;
-    if (src->is_view) return fail(IVFADC_ERR_STATE, "a view of a view: take it from the index itself");
+    if (src->is_view) return fail(IVFADC_ERR_STATE, "%s: take it from the index itself", of_a_view);
     TRY(set_device(src));
-    if (src->dirty) TRY(upload_lists(src));   // the device copy is what the view shares
+    if (src->dirty) TRY(upload_lists(src));   // the device copy is what the view shares (a subset view: reads)
     if (!src->have_lists) return fail(IVFADC_ERR_STATE, "no inverted lists set");
     HIP_TRY(hipStreamSynchronize(src->stream));   // uploads and in-place edits have landed
-    std::unique_ptr<ivfadc_index> v(new ivfadc_index());   // (plain delete until it is handed out: it owns no device memory)
+    return IVFADC_OK;
+}
+
+// everything a view is given except its lists
+static void view_shell(ivfadc_index *src, ivfadc_index *v)
+{
     static_cast<Dims &>(*v) = *src;
     static_cast<Quantizers &>(*v) = *src;
-    static_cast<Lists &>(*v) = *src;
     v->Quantizers::each_buf([](DevBuf &b) { b.alias(); });
-    v->Lists::each_buf([](DevBuf &b) { b.alias(); });
     static_cast<SearchConfig &>(*v) = *src;
     v->prune_est = src->prune_est;   // (a view has counters, snapshots and an event of its own; it starts from its index's estimate)
     v->fn_cfg = src->fn_cfg;         // what the index has already asked the runtime about its kernels holds for the view's launches
@@ -2764,6 +2775,11 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
     v->is_view = true;
     v->view_of = src;
     v->view_gen = src->generation;
+}
+
+// the view's own stream, its place among the index's views, and out it goes
+static int view_hand_out(ivfadc_index *src, std::unique_ptr<ivfadc_index> &v, ivfadc_index **out)
+{
     const hipError_t e = hipStreamCreateWithFlags(&v->stream, hipStreamNonBlocking);
     if (e != hipSuccess) return fail(IVFADC_ERR_HIP, "hipStreamCreateWithFlags failed: %s", hipGetErrorString(e));
     // the point of a view is a second batch IN FLIGHT: its stream must not share a hardware queue with the index's
@@ -2781,6 +2797,107 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
     return IVFADC_OK;
 }
 
+// A read-only view of `src`: the same device arrays (quantizers, derived tables, lists), a stream and a workspace of its own.
+// The view is a fresh handle that is GIVEN what it shares: the shape, the quantizers and the device lists as aliases, the settings, and
+// the few scalars view_shell names.  Its workspace and everything in HandleState start from their defaults; the host mirror is never touched.
+static int clone_view(ivfadc_index *src, ivfadc_index **out)
+{
+    *out = nullptr;
+    TRY(view_source_ready(src, "a view of a view"));
+    std::unique_ptr<ivfadc_index> v(new ivfadc_index());   // (plain delete until it is handed out: it owns no device memory)
+    view_shell(src, v.get());
+    static_cast<Lists &>(*v) = *src;
+    v->Lists::each_buf([](DevBuf &b) { b.alias(); });
+    return view_hand_out(src, v, out);
+}
+
+// ---- subset views (subset.hip.h, subset_plan.h; DESIGN.md "Subset views") -------------------------------------------------------------
+// The view's OWN Lists group, filled from the index's device arrays: count per work item, one blocking copy of the counts, the layout
+// every index gets (layout_from_caps: 256-byte aligned code blocks, the CODE_SLACK tail; capacity = length, a view never appends), a
+// zeroed code buffer (alignment gaps and the tail are defined, as upload_lists' zeroed stage makes them), scatter.  Runs on the INDEX's
+// stream, which is at rest (view_source_ready) and stays the caller's for the whole call (the index's lock is held); v->stream is lent
+// that stream for the uploads and is given its own afterwards.  tmp: the call's scratch buffers, released by the caller on every path.
+struct SubsetScratch {
+    DevBuf bits, items, counts, bases;
+    void release() { for (DevBuf *b : {&bits, &items, &counts, &bases}) b->release(); }
+};
+
+static int fill_subset_lists(ivfadc_index *src, ivfadc_index *v, const uint32_t *bits, bool bits_on_device, uint64_t nbits, SubsetScratch &tmp)
+{
+    const int kc = src->kc;
+    hipStream_t s = src->stream;
+    const std::vector<subset::Item> items = subset::make_items(src->h_len);
+    std::vector<uint32_t> count(items.size(), 0), base;
+    const uint32_t *d_bits = bits;
+    const u32 *src_ids = src->synthetic ? (const u32 *)nullptr : src->ids.as<u32>();
+    const bool scan = nbits > 0 && !items.empty();   // (nbits == 0: the empty subset, nothing to read)
+    if (scan) {
+        if (!bits_on_device) {
+            const size_t words = (size_t)((nbits + 31) / 32);
+            TRY(tmp.bits.ensure(words * 4));
+            TRY(h2d_copy(tmp.bits.p, bits, words * 4, s));
+            d_bits = tmp.bits.as<uint32_t>();
+        }
+        static_assert(sizeof(subset::Item) == 8, "the item list is uploaded as it is");
+        TRY(tmp.items.ensure(items.size() * sizeof(subset::Item)));
+        TRY(h2d_copy(tmp.items.p, items.data(), items.size() * sizeof(subset::Item), s));
+        TRY(tmp.counts.ensure(items.size() * 4));
+        hipLaunchKernelGGL(subset_count_kernel, dim3((unsigned)items.size()), dim3(256), 0, s, tmp.items.as<subset::Item>(),
+                           src->list_pos.as<int64_t>(), src->list_len.as<u32>(), src_ids, d_bits, (uint64_t)nbits, tmp.counts.as<uint32_t>());
+        HIP_TRY(hipGetLastError());
+        TRY(d2h_copy(count.data(), tmp.counts.p, items.size() * 4, s));   // (blocking: the layout depends on it)
+    }
+    subset::make_bases(items, count, (size_t)kc, v->h_len, base);
+    for (int l = 0; l < kc; ++l)
+        if (v->h_len[l] > src->h_len[l]) return fail(IVFADC_ERR_HIP, "subset count of list %d exceeds the list", l);
+    v->d_cap = v->h_len;
+    size_t total = 0;
+    int64_t slots = 0;
+    TRY(layout_from_caps(v, total, slots));
+    TRY(v->codes.alloc_exact(total));
+    TRY(v->ids.alloc_exact((size_t)std::max<int64_t>(1, slots) * 4));
+    HIP_TRY(hipMemsetAsync(v->codes.p, 0, total, s));
+    v->stream = s;
+    const int rc = upload_list_tables(v);
+    v->stream = nullptr;
+    TRY(rc);
+    if (v->n > 0) {
+        TRY(tmp.bases.ensure(base.size() * 4));
+        TRY(h2d_copy(tmp.bases.p, base.data(), base.size() * 4, s));
+        hipLaunchKernelGGL(subset_scatter_kernel, dim3((unsigned)items.size()), dim3(256), 0, s, tmp.items.as<subset::Item>(),
+                           src->list_pos.as<int64_t>(), src->list_len.as<u32>(), src->list_codeoff.as<int64_t>(), src_ids,
+                           src->codes.as<uint8_t>(), d_bits, (uint64_t)nbits, tmp.bases.as<uint32_t>(), v->list_pos.as<int64_t>(),
+                           v->list_codeoff.as<int64_t>(), v->ids.as<uint32_t>(), v->codes.as<uint8_t>(), v->cs / 4);
+        HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    v->have_lists = true;
+    v->synthetic = false;   // (the kept entries of synthetic lists carry their ids like any others)
+    v->dirty = false;
+    return IVFADC_OK;
+}
+
+static int clone_subset(ivfadc_index *src, const uint32_t *bits, bool bits_on_device, uint64_t nbits, ivfadc_index **out, int64_t *out_n)
+{
+    *out = nullptr;
+    TRY(view_source_ready(src, "a subset of a view"));
+    std::unique_ptr<ivfadc_index> v(new ivfadc_index());
+    view_shell(src, v.get());
+    SubsetScratch tmp;
+    int rc = fill_subset_lists(src, v.get(), bits, bits_on_device, nbits, tmp);
+    if (rc != IVFADC_OK) (void)hipStreamSynchronize(src->stream);   // nothing still reads the scratch
+    tmp.release();
+    const int64_t kept = v->n;
+    ivfadc_index *raw = v.get();
+    if (rc == IVFADC_OK) rc = view_hand_out(src, v, out);
+    if (rc != IVFADC_OK) {   // (until it is handed out the view is deleted plainly: its lists go first)
+        raw->Lists::each_buf([](DevBuf &b) { b.release(); });
+        return rc;
+    }
+    if (out_n) *out_n = kept;
+    return IVFADC_OK;
+}
+
 // settings that change how a search runs, copied to the internal second lane before every use
 static void copy_search_config(ivfadc_index *dst, const ivfadc_index *src)
 {
@@ -2794,6 +2911,31 @@ try {
     HandleLock lk_(h);
     if (!h || !out) return fail(IVFADC_ERR_INVALID, "null argument");
     return clone_view(h, out);
+} IVF_CATCH
+
+// the arguments of both subset entries, before the handle is looked at and before any device call
+static int check_subset_args(ivfadc_t *h, const uint32_t *bits, uint64_t nbits, ivfadc_t **out)
+{
+    if (!out) return fail(IVFADC_ERR_INVALID, "ivfadc_clone_subset: null out_view");
+    *out = nullptr;
+    if (nbits > ((uint64_t)1 << 32)) return fail(IVFADC_ERR_INVALID, "ivfadc_clone_subset: nbits exceeds 2^32 (ids are UInt32)");
+    if (nbits > 0 && !bits) return fail(IVFADC_ERR_INVALID, "ivfadc_clone_subset: null bitmap with nbits > 0");
+    if (!h) return fail(IVFADC_ERR_INVALID, "ivfadc_clone_subset: null handle");
+    return IVFADC_OK;
+}
+
+int ivfadc_clone_subset(ivfadc_t *h, const uint32_t *bits, uint64_t nbits, ivfadc_t **out_view, int64_t *out_n)
+try {
+    HandleLock lk_(h);
+    TRY(check_subset_args(h, bits, nbits, out_view));
+    return clone_subset(h, bits, false, nbits, out_view, out_n);
+} IVF_CATCH
+
+int ivfadc_clone_subset_device(ivfadc_t *h, const uint32_t *d_bits, uint64_t nbits, ivfadc_t **out_view, int64_t *out_n)
+try {
+    HandleLock lk_(h);
+    TRY(check_subset_args(h, d_bits, nbits, out_view));
+    return clone_subset(h, d_bits, true, nbits, out_view, out_n);
 } IVF_CATCH
 
 // a 16-bit handle refuses the uint8_t entries, an 8-bit handle the _u16 ones

@@ -186,15 +186,42 @@ class IVFADCIndex:
     def clone_view(self):
         """A read-only view of this index (ivfadc_clone_view): the same device arrays, a stream and a workspace of its own, so that
         two batches can be in flight on one replica.  Any change to this index afterwards makes the view refuse to search."""
+        h = C.c_void_p()
+        nat.check(nat.lib().ivfadc_clone_view(self._h, C.byref(h)))
+        return self._view(h)
+
+    def _view(self, h):
+        """The Python object of a view handle `h` of this index (plain or subset): the quantizer arrays and the shape are this index's."""
         v = IVFADCIndex.__new__(IVFADCIndex)
-        v._h = C.c_void_p()
-        nat.check(nat.lib().ivfadc_clone_view(self._h, C.byref(v._h)))
+        v._h = h
         for name in ("_centroids", "_codebooks", "_labels", "kc", "d", "m", "ksub", "dsub", "index_type", "code_type"):
             setattr(v, name, getattr(self, name))
         v.device = getattr(self, "device", 0)
         v.requested_coarse_quantizer = getattr(self, "requested_coarse_quantizer", "naive")
         v._mirror = None
         v._view_of = self          # keeps the index alive as long as the view
+        return v
+
+    def subset(self, ids=None, mask=None):
+        """A read-only SUBSET view of this index (ivfadc_clone_subset): the entries whose stored id is selected, in their stored order
+        and with their stored ids, compacted on the device into lists of the view's own; quantizers, stream and workspace as for
+        clone_view.  `ids`: an integer array of 0-based stored ids (the ones knn_search returns); `mask`: a boolean array indexed by
+        id (ids at or above its length are not selected).  Exactly one of the two.  knn_search, coarse_search, knn_search_preassigned
+        and knn_search_batches take the view as they take any index; any change to this index afterwards makes it refuse to search."""
+        bits, nbits = pack_bitmap(ids=ids, mask=mask)
+        return self._subset(nat.lib().ivfadc_clone_subset, nat.ptr(bits, C.c_uint32) if nbits else None, nbits)
+
+    def subset_device(self, d_bits_ptr, nbits):
+        """subset() from a bitmap that already lies in device memory of this index's GPU (ivfadc_clone_subset_device): `d_bits_ptr` is
+        the raw device pointer (int) of ceil(nbits / 32) uint32 words, complete when the call is made."""
+        return self._subset(nat.lib().ivfadc_clone_subset_device, C.c_void_p(int(d_bits_ptr)) if nbits else None, int(nbits))
+
+    def _subset(self, entry, bits, nbits):
+        h = C.c_void_p()
+        kept = C.c_int64(0)
+        nat.check(entry(self._h, bits, C.c_uint64(nbits), C.byref(h), C.byref(kept)))
+        v = self._view(h)
+        v._subset_n = int(kept.value)       # what out_n said; len() asks the handle
         return v
 
     def __del__(self):
@@ -314,8 +341,9 @@ class IVFADCIndex:
         req = getattr(self, "requested_coarse_quantizer", "naive")
         cq = "naive" if req == "naive" else "%s (requested; served by the exact naive search)" % req
         csize = getattr(self, "code_type", np.dtype(np.uint8)).itemsize
-        return ("IVFADCIndex, %s coarse quantizer, %d-byte encoding (%d + %d×%d), %d Float32 vectors"
-                % (cq, csize * self.m + idxsize, idxsize, csize, self.m, len(self)))
+        what = "IVFADCIndex" if getattr(self, "_subset_n", None) is None else "Subset view of an IVFADCIndex"
+        return ("%s, %s coarse quantizer, %d-byte encoding (%d + %d×%d), %d Float32 vectors"
+                % (what, cq, csize * self.m + idxsize, idxsize, csize, self.m, len(self)))
 
     # ---- search --------------------------------------------------------------------------------
     def _io_lock(self):
@@ -566,6 +594,28 @@ def comm_unique_id():
     buf = np.zeros(128, np.uint8)
     nat.check(nat.lib().ivfadc_comm_unique_id(nat.ptr(buf, C.c_uint8)))
     return buf
+
+
+def pack_bitmap(ids=None, mask=None):
+    """The bitmap ivfadc_clone_subset takes, from a list of 0-based stored ids or from a boolean mask indexed by id: (uint32 words,
+    nbits) with id i at bit (i & 31) of word i >> 5.  nbits is len(mask), or the largest id + 1."""
+    assert (ids is None) != (mask is None), "subset takes exactly one of ids and mask"
+    if mask is not None:
+        mask = np.asarray(mask)
+        assert mask.dtype == np.bool_ and mask.ndim == 1, "mask must be a 1-D boolean array indexed by id"
+    else:
+        ids = np.asarray(ids)
+        assert ids.ndim == 1 and (ids.size == 0 or np.issubdtype(ids.dtype, np.integer)), "ids must be a 1-D integer array"
+        ids = ids.astype(np.int64)
+        assert ids.size == 0 or (ids.min() >= 0 and ids.max() < 2 ** 32), "ids are 0-based UInt32 values"
+        mask = np.zeros(int(ids.max()) + 1 if ids.size else 0, np.bool_)
+        mask[ids] = True
+    nbits = int(mask.shape[0])
+    assert nbits <= 2 ** 32, "ids are UInt32 values: at most 2^32 bits"
+    by = np.packbits(mask, bitorder="little")                      # bit (i & 7) of byte i >> 3
+    words = np.zeros((nbits + 31) // 32 * 4, np.uint8)
+    words[:by.shape[0]] = by
+    return np.ascontiguousarray(words.view("<u4")).astype(np.uint32), nbits
 
 
 def knn_search(ivfadc, points, k, w=1):

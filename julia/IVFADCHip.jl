@@ -21,7 +21,7 @@ using Distances
 using QuantizedArrays
 import LinearAlgebra
 
-export hip_sync!, hip_release!
+export hip_sync!, hip_release!, hip_subset
 
 # GPU methods for the knn_search hot path; everything else falls through to the CPU methods.
 const LIBIVFADC = get(ENV, "IVFADC_HIP_LIB", "libivfadc_hip.so")
@@ -427,6 +427,52 @@ function delete_from_index!(ivfadc::GpuIndex, points::Vector{<:Integer})
     invoke(delete_from_index!, Tuple{IVFADCIndex,Vector{<:Integer}}, ivfadc, points)   # `points` are 1-based (utils.jl:93)
     _gpu_delete!(ivfadc, UInt32.(unique(points) .- 1))
     return nothing
+end
+
+# Filtered search: a SUBSET VIEW of the device copy (ivfadc_clone_subset) -- deleteat! of utils.jl:98-99 applied, on a copy of the device
+# lists, to every entry that is NOT named, without the _shift_inverse_index! of delete_from_index!: the named points keep their order and
+# their ids, `ivfadc` itself is untouched.  `points` are 1-based, as delete_from_index! takes them (point p = stored id p - 1 = bit p - 1).
+# The view is read-only and refuses to search once `ivfadc` has changed on the device (take a new one); it holds `ivfadc` alive.
+struct HipSubset{I}
+    handle::HipHandle
+    parent::IVFADCIndex
+end
+
+function hip_subset(ivfadc::GpuIndex{I}, points::Vector{<:Integer}) where {I}
+    h = _handle(ivfadc)
+    nbits = isempty(points) ? 0 : Int(maximum(points))
+    bits = zeros(UInt32, cld(nbits, 32))
+    for p in points
+        @assert p >= 1 "points are 1-based"
+        bits[((p - 1) >> 5) + 1] |= UInt32(1) << ((p - 1) & 31)
+    end
+    out = Ref{Ptr{Cvoid}}(C_NULL)
+    _check(ccall((:ivfadc_clone_subset, LIBIVFADC), Cint, (Ptr{Cvoid}, Ptr{UInt32}, UInt64, Ref{Ptr{Cvoid}}, Ptr{Int64}),
+                 h.ptr, bits, nbits, out, C_NULL))
+    hh = HipHandle(out[])
+    finalizer(hh) do x
+        x.ptr == C_NULL || ccall((:ivfadc_destroy, LIBIVFADC), Cvoid, (Ptr{Cvoid},), x.ptr)
+        x.ptr = C_NULL
+        _release!(x.q); _release!(x.ids); _release!(x.dists); _release!(x.counts)
+    end
+    return HipSubset{I}(hh, ivfadc)
+end
+
+function knn_search(s::HipSubset{I}, points::Vector{Vector{Float32}}, k::Int; w::Int=1) where {I}
+    @assert k >= 1 "Number of neighbors must be k >= 1"
+    @assert w >= 1 "Number of clusters to search in must be w >= 1"
+    nq = length(points)
+    nq == 0 && return Vector{I}[], Vector{Float32}[]
+    d, kc = size(_centroids(s.parent.coarse_quantizer))
+    q, ids, dists, counts = _io(s.handle, d, k, nq)
+    for i in 1:nq
+        @assert length(points[i]) == d "Searching requires $d-element vectors"
+        copyto!(q, (i - 1) * d + 1, points[i], 1, d)
+    end
+    _check(ccall((:ivfadc_search, LIBIVFADC), Cint,
+                 (Ptr{Cvoid}, Int64, Ptr{Float32}, Cint, Cint, Ptr{UInt32}, Ptr{Float32}, Ptr{Int32}),
+                 s.handle.ptr, nq, q, k, min(w, kc), ids, dists, counts))
+    return [I.(ids[1:counts[i], i]) for i in 1:nq], [dists[1:counts[i], i] for i in 1:nq]
 end
 
 end # module
