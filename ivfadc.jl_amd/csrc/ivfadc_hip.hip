@@ -13,6 +13,7 @@
 #include "twolevel.hip.h"
 #include "subset.hip.h"
 #include "pack_operands.h"
+#include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 
 #include <algorithm>
 #include <atomic>
@@ -195,7 +196,6 @@ struct PinnedBuf {
     }
 };
 
-static inline size_t align_up(size_t x, size_t a) { return (x + a - 1) / a * a; }
 // ---- host <-> device copies of PAGEABLE memory go through the library's own page-locked bounce buffers ---------------------------------
 // hipMemcpy{,Async} stages pageable copies of up to 1 MB itself; beyond that the runtime page-locks the CALLER's pages, lets the copy
 // engine read or write them in place ("HSA Copy Using Pinned resource", rocblit.cpp; tools/pin_probe.py), and keeps the locked mapping in
@@ -266,8 +266,6 @@ int d2h_copy(void *dst, const void *src, size_t bytes, hipStream_t s)
     if (prev_n) memcpy((char *)dst + prev_off, g_bounce.buf[i ^ 1], prev_n);
     return IVFADC_OK;
 }
-
-static inline int pow2ceil(int x) { int p = 1; while (p < x) p <<= 1; return p; }
 
 }  // namespace
 
@@ -718,9 +716,7 @@ template <int M, int DS, bool SMALL> qscan_fn_t qscan_fn_pg(int pg)
 
 #define IVF_SHAPES(X) X(8, 16) X(16, 6) X(16, 8) X(48, 16)
 
-// shapes the matrix-core lower-bound rounds (qscan_kernel<..., LB = true>) are instantiated for
-bool lb_shape(int m, int dsub) { return (m == 48 && dsub == 16) || (m == 16 && dsub == 6); }
-
+// (the shapes the matrix-core lower-bound rounds -- qscan_kernel<..., LB = true> -- are instantiated for: lb_shape, scan_layouts.h)
 template <int M, int DS> qscan_fn_t pick_qscan_lb_pg(int pg)
 {
     switch (pg) {
@@ -738,18 +734,12 @@ qscan_fn_t pick_qscan_lb(int m, int dsub, int pg)
     return nullptr;
 }
 
-// mirrors LbCfg<M, DS, PG>::END + the tail of qscan_kernel's carve (scnt, swi, sthr, probe cache)
-size_t lb_lds_bytes(int m, int dsub, int pg)
-{
-    size_t b = align_up((size_t)pg * ((size_t)m * 256 + 32), 16);
-    b += (size_t)m * pg * ((dsub + 3) & ~3) * 4;   // f32 residuals of the round's probes (rows padded to 16-byte groups)
-    b += 2 * (size_t)m * pg * 4 + 128 + 256;   // norms, bases, per-probe constants of the round and of the query
-    b += (size_t)m * dsub * 4;              // query
-    b += (size_t)4 * (pg >= 4 ? 54 : 16) * (m / 4 + 2) * 4;   // parking pools (LbCfg::PCAP entries per wave)
-    b += 4 * 64 * 8;                        // upper-bound keys of the four waves
-    b += (size_t)4 * pg * 4 + 16 + (size_t)pg * 40 + 3 * 256;
-    return b;
-}
+// the plan's LDS figure of these kernels (lb_lds_bytes, scan_layouts.h) is the kernel's own layout: LbCfg<M, DS, PG>::END, and behind it
+// what qscan_body carves -- scnt [4][PG] int, swi [4] u32, sthr [PG][STHR_WORDS] u64, the 768-B copy of the query's probes
+template <int M, int DS, int PG> constexpr size_t lb_kernel_lds = LbCfg<M, DS, PG>::END + 4 * PG * 4 + 4 * 4 + PG * STHR_WORDS * 8 + 768;
+#define X(M_, D_, P_) static_assert(lb_lds_bytes(M_, D_, P_) == lb_kernel_lds<M_, D_, P_>, "the planned LDS bytes of qscan_kernel<M, DS, PG, true, true> are its carve");
+X(48, 16, 1) X(48, 16, 2) X(48, 16, 3) X(48, 16, 4) X(16, 6, 1) X(16, 6, 2) X(16, 6, 3) X(16, 6, 4)
+#undef X
 
 template <bool SMALL> scan_fn_t pick_scan_s(int m, int dsub, int qg, bool stripe)
 {
@@ -798,39 +788,8 @@ sq_fn_t pick_sq(int m, int dsub)
     return sq_kernel<0, 0>;
 }
 
-// shapes the striped list-major kernels exist for (IVF_SHAPES with m = 8 / 16)
-bool filt_shape(int m, int dsub) { return (m == 8 && dsub == 16) || (m == 16 && (dsub == 6 || dsub == 8)); }
-
-// the shape the narrow-field list-major kernel exists for (nfscan.hip.h)
-bool nf_shape(int m, int dsub) { return m == 8 && dsub == 16; }
-
-// mirrors carve_lds() in kernels.hip.h.  stripe: the plan's (Plan::stripe), for the width qg
-size_t scan_lds_bytes(const ivfadc_index *h, int qg, int cap, bool small, bool list_major = false, bool stripe = false)
-{
-    size_t b = (size_t)std::max(h->m, 2) * 256 * qg * 4;
-    b += align_up((size_t)h->d * qg, 4) * 4;
-    if (!small) b += (size_t)4 * (list_major ? qg : 1) * cap * 8;   // LDS selectors: per wave and query (query-major: one query)
-    b += (size_t)4 * qg * 4 + 16;
-    b = align_up(b, 8) + (size_t)qg * 40;  // workgroup-shared thresholds + the four waves' quarter keys per slot (STHR_WORDS)
-    b += 3 * 256;                           // query-major kernel: LDS copy of the query's probes (see qscan_kernel)
-    if (list_major && qg == 4 && (h->m == 8 || h->m == 16))
-        b += 4 * 16 * 5 * 4;                // groups of four at m = 8 / 16 (striped or not): 4 waves x CAND_CAP parked points x <= 5 dwords
-    if (stripe && h->m == 8)
-        b += 256 * 64;                      // m = 8 striped: the 16-bit integer filter table behind the float tables (QF_BYTES)
-    return b;
-}
-
-constexpr size_t LDS_MAX = 160 << 10;
-// the eight-wave list-major kernel (wg8scan.hip.h) as the plan's own choice on long lists (ivfadc_set_table_mode(h, 6) asks for it anywhere)
-constexpr double W8_Q8_MIN_PPL = 8.0;   // probes per list from which the eight-query form of the eight-wave kernel is planned
-// sub-space widths the eight-wave kernel is instantiated for (m = 8: d = 32, 64, 96, 128), and the instantiation of a form and a width
-bool w8_dsub(int dsub) { return w8_ds_ok(dsub); }
-// ... and m = 16 (d = 64, 128: wg8_m16_scan_kernel<NQ, DS>, K <= 64, no wide pool), which runs on request only -- table modes 6 / 7 (8 / 9):
-// not timed against the four-wave kernel yet
-bool w8_m16_dsub(int dsub) { return dsub == 4 || dsub == 8; }
-// the shapes (m, dsub) the handle's table mode admits, and the longest list the kernel's 28-bit positions and 31-bit byte offsets hold
-bool w8_md(const ivfadc_index *h) { return (h->m == 8 && w8_dsub(h->dsub)) || (h->m == 16 && w8_m16_dsub(h->dsub) && h->wg8_mode > 0); }
-int64_t w8_maxlen(const ivfadc_index *h) { return (int64_t)1 << (h->m == 16 ? 27 : 28); }
+// (filt_shape, nf_shape, w8_dsub, w8_m16_dsub -- the shapes the striped, the narrow-field and the eight-wave kernels are instantiated
+// for -- and the LDS figures of all of them: scan_layouts.h)
 typedef void (*nf_fn_t)(const ScanArgs, const NfView);
 typedef void (*u16_fn_t)(const ScanArgs, int);
 typedef void (*wg8_fn_t)(const ScanArgs, float *, const u32 *, u32 *, int);
@@ -849,8 +808,7 @@ wg8_fn_t pick_wg8(bool q8, int m, int dsub)
 #undef X
     return nullptr;
 }
-// the wide-pool form (two pool entries per lane: 64 < K <= 128; table modes 8 / 9)
-constexpr int W8_WIDE_MAX_K = 128;
+// the wide-pool form (two pool entries per lane: 64 < K <= W8_WIDE_MAX_K; table modes 8 / 9)
 wg8_fn_t pick_wg8_wide(bool q8, int dsub)
 {
 #define X(D_) if (dsub == D_) return q8 ? wg8_wide_scan_kernel<8, D_> : wg8_wide_scan_kernel<4, D_>;
@@ -858,8 +816,6 @@ wg8_fn_t pick_wg8_wide(bool q8, int dsub)
 #undef X
     return nullptr;
 }
-// ... and where the plan takes the kernel unasked (wg8_mode == 0; table modes 6 / 7 take it wherever it is instantiated): see make_plan
-bool w8_default(const ivfadc_index *h) { return h->m == 8 && h->dsub == 16 && h->part_n <= 1; }
 // misc device block: [0, 4096) 64 scanned-point counters at a 64-B stride; [4096] work-queue head; [4096 + 64] coarse fallbacks;
 // [4096 + 256, + 512) the eight per-XCD queue heads of the narrow-field kernel, 64 B apart
 constexpr size_t MISC_BYTES = 4096 + 256 + 512 + 4096;
@@ -872,106 +828,10 @@ int clear_xcd_heads(ivfadc_index *h, u32 *&xq)
     return IVFADC_OK;
 }
 
-// The scan a search runs.  Query-major: one workgroup per query (qscan_kernel), Lb with 8-bit lower-bound tables from the matrix cores
-// (lbscan.hip.h).  List-major: FourWave scan_kernel (striped tables: Plan::stripe); NarrowField nf_scan_kernel, eight queries per code
-// stream behind the 4-bit filter (nfscan.hip.h); EightWave wg8scan.hip.h, eight waves per workgroup on four conflict-free copies of
-// the integer filter table (Plan::q8: eight queries per stream; Plan::wide: the wide pool of 64 < K <= 128, the merge behind it is
-// the one of K > 64); U16 / U16Wide u16scan.hip.h on register / LDS selectors, U16Direct / U16DirectWide its table-free entries.
-enum class ScanForm { QueryMajor, QueryMajorLb, FourWave, NarrowField, EightWave, U16, U16Wide, U16Direct, U16DirectWide };
-
-struct Plan {
-    ScanForm form = ScanForm::QueryMajor;
-    bool stripe = false, q8 = false, wide = false;   // FourWave / EightWave only (see ScanForm)
-    const void *fn = nullptr;   // the scan kernel of the form: scan_fn_t, qscan_fn_t, wg8_fn_t, nf_fn_t or u16_fn_t
-    int threads = 256;          // ... and its workgroup size
-    bool coarse_mfma = false;   // coarse scores on the matrix cores + certified exact refine (w <= 48)
-    bool fuse_topw = false;   // query-major only: top-w selection runs inside the scan kernel
-    bool lanes = false;         // several batches in flight on this replica: stand-alone top-w, a wave per query (see make_plan)
-    bool twolevel = false;      // coarse stage: certified two-level search (twolevel.hip.h) instead of the exhaustive kernels + top-w
-    bool small_k = true, small_w = true;
-    int qg = 0, cap = 64, capw = 64, maxch = 1;
-    uint32_t CH = 0;
-    size_t lds = 0;
-    int64_t nb = 0;   // queries per sub-batch
-    bool fits = true;    // false: the selection kernels' LDS need exceeds the CU's 160 KB -> the caller takes the generic path
-    bool query_major() const { return form == ScanForm::QueryMajor || form == ScanForm::QueryMajorLb; }
-    // ivfadc_stats.last_striped of a list-major form: 1 striped four-wave tables; 2 / 3 eight-wave, four / eight queries; 4 / 5 its wide pool;
-    // 6 / 7 the table-free UInt16 scan on register / LDS selectors
-    int striped() const
-    {
-        if (form == ScanForm::U16Direct) return 6;
-        if (form == ScanForm::U16DirectWide) return 7;
-        return form == ScanForm::EightWave ? (wide ? 4 : 2) + (q8 ? 1 : 0) : (stripe ? 1 : 0);
-    }
-};
-
-// selector capacity of the scan (K) and of the stand-alone top-w (w): registers up to 64, LDS buffers beyond
-int sel_cap(int k) { return k <= 64 ? 64 : std::max(128, pow2ceil(k + 64)); }
-
-// Coarse stage: the certified two-level search (twolevel.hip.h: its four waves keep their queries in LDS), or the matrix-core filter
-// -- which pays when the coarse search is large: below ~2k centroids the extra selection + refine work in the scan prologue costs
-// more than the VALU kernel it replaces (SIFT1M-shape: 92 -> 121 us per batch) -- or, with neither, the exact VALU kernels.
-// own: the search has a coarse stage of these kernels at all (not the caller's probes, not the generic path's sort); tl_batch: the
-// batch is one the two-level kernel's 32-bit indices hold
-struct CoarseForm { bool twolevel, mfma; };
-CoarseForm coarse_form(const ivfadc_index *h, int w, bool own, bool tl_batch)
-{
-    CoarseForm c;
-    c.twolevel = own && tl_batch && h->tl_use && h->tl_G > 0 && w <= 64 && (h->d & 3) == 0 && (size_t)4 * h->d * 4 + 4 * 64 * 8 <= (size_t)(96 << 10);
-    c.mfma = own && !c.twolevel && h->allow_mfma && w <= 48 && h->kc >= h->mfma_min_kc && (h->d & 3) == 0;
-    return c;
-}
-
-// what both planners start from ...
-void plan_begin(const ivfadc_index *h, int64_t nq, int K, int w, bool pre, Plan &pl)
-{
-    pl = Plan{};
-    pl.small_k = K <= 64;
-    pl.small_w = w <= 64;
-    pl.cap = sel_cap(K);
-    pl.capw = sel_cap(w);
-    const CoarseForm c = coarse_form(h, w, !pre, nq <= ((int64_t)1 << 30) / std::max(1, h->tl_G));
-    pl.twolevel = c.twolevel;
-    pl.coarse_mfma = c.mfma;
-}
-
-// ... the list-major ones go on, once pl.qg stands, with the chunk size (from ch0 points up; a forced one in multiples of align): enough
-// work items to fill the chip, as few table rebuilds as possible.  Two items per CU is the measured optimum on billion-scale lists
-// (SIFT1B-shape, 16..1024 queries, w = 1 and 8: every case at or within 5 % of its best chunk size; sixteen per CU rebuilt tables up
-// to 15 times per probe)
-void plan_chunks(const ivfadc_index *h, int64_t nq, int w, double avg_len, uint32_t ch0, uint32_t align, Plan &pl)
-{
-    const double ch = (double)nq * w * avg_len / pl.qg / (2.0 * h->num_cu);
-    uint32_t CH = ch0;
-    // (cap 2^18 points: on the billion-scale shapes a chunk then covers a whole list -- one table build and one selector
-    // warm-up per (list, query group) instead of two: SIFT1B-shape scan 8.64 -> 7.45 ms at w = 8, 1.87 -> 1.69 ms at w = 1)
-    while ((double)CH < ch && CH < (1u << 18)) CH <<= 1;
-    if (h->force_chunk > 0) CH = (uint32_t)align_up((size_t)h->force_chunk, align);
-    while ((h->maxlen + CH - 1) / CH > 64) CH <<= 1;   // bound the partial-result slots per probe
-    pl.CH = CH;
-    pl.maxch = (int)std::max<int64_t>(1, (h->maxlen + CH - 1) / CH);
-}
-
-// ... and both end with: sub-batches so the workspace stays inside the budget (partials: the list-major plans' partial results per probe and chunk)
-void plan_subbatch(const ivfadc_index *h, int64_t nq, int K, int w, bool partials, Plan &pl)
-{
-    const size_t per_q = (pl.twolevel ? (size_t)h->tl_G : (size_t)h->kc) * 4 + (partials ? (size_t)w * pl.maxch * ((size_t)K * 8 + 4) : 0) +
-                         (size_t)w * 20 + (size_t)K * 8 + 64;
-    int64_t nb = (int64_t)std::max<size_t>(64, h->ws_budget / per_q);
-    nb = std::min<int64_t>(nb, (int64_t)1 << 22);                                   // kernel arguments are 32-bit
-    nb = std::min<int64_t>(nb, std::max<int64_t>(64, ((int64_t)1 << 30) / std::max(1, w * pl.maxch)));
-    pl.nb = std::min<int64_t>(nq, nb);
-}
-
-// ---- how many probes a query-major round takes is a question about the DATA ---------------------------------------------------------
-// Two probes per round share every codeword fetch between two tables -- right when most probes are scanned; one probe per round lets
-// exact pruning look at the bound after EVERY list -- right when the bound the closest cells leave prunes most of the rest.  SIFT1M
-// shape, two batches in flight (profiles/r05_pg12_matrix.txt): clustered data (93 % of the probed points pruned) 49.6 M q/s with one
-// probe per round against 44.8 M with two, w = 32 41.5 against 31.5 M; data where nothing prunes 19.5 against 22.5 M.  The scan kernels
-// count probed and pruned points anyway (ivfadc_stats); every few searches a 4 KB snapshot of the counters follows the scan on the
-// stream into pinned memory, and a later search that finds it arrived (hipEventQuery: no wait, ever) folds the pruned fraction into
-// h->prune_est.  Plans change with it, results cannot (every plan returns the reference's bytes).
-constexpr float PG1_MIN_PRUNED = 0.6f;
+// ---- the plan of a search: plan.h decides (a pure function of PlanFacts), this file reads the handle and picks the kernel -------------
+// Feedback for the probes-per-round choice of plan_query_major (PG1_MIN_PRUNED in plan.h says why): every few searches a 4 KB snapshot
+// of the scan kernels' probed / pruned counters follows the scan on the stream into pinned memory, and a later search that finds it
+// arrived (hipEventQuery: no wait, ever) folds the pruned fraction into h->prune_est.
 int fb_poll(ivfadc_index *h)
 {
     if (!h->fb_pending) return IVFADC_OK;
@@ -1004,188 +864,43 @@ int fb_snapshot(ivfadc_index *h)   // behind a query-major scan launch, on its s
     return IVFADC_OK;
 }
 
-// U = UInt16 (u16scan.hip.h): always list-major; K <= 64 on register selectors, 64 < K on LDS selectors where table mode 10 asks for
-// them (search_dev sends larger K to the generic path otherwise).  Pairs per work item from the expected probes per list (a codeword
-// read serves every pair of the item), halved for K > 64 until the selector buffers fit; chunks of whole passes, about two items per CU.
-// Table-free (ivfadc_set_u16_tables): 1 always; 2 where a pass holds fewer points, weighted by what a gather costs, than a table has
-// entries: min(avg_len, U16_PASS) * U16_DIRECT_COST <= ksub.
-int make_plan_u16(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)
+// the ONE place that reads the handle for planning
+PlanFacts plan_facts(const ivfadc_index *h)
 {
-    plan_begin(h, nq, K, w, pre, pl);
-    const double avg_len = (double)h->n / std::max(1, h->kc);
-    const bool tfree = h->u16_tables == 1 || (h->u16_tables == 2 && std::min(avg_len, (double)U16_PASS) * (double)U16_DIRECT_COST <= (double)h->ksub);
-    pl.form = tfree ? (pl.small_k ? ScanForm::U16Direct : ScanForm::U16DirectWide) : (pl.small_k ? ScanForm::U16 : ScanForm::U16Wide);
-    const u16_fn_t fns[4] = {u16_wide_scan_kernel, u16_scan_kernel, u16_direct_wide_scan_kernel, u16_direct_scan_kernel};
-    pl.fn = (const void *)fns[(tfree ? 2 : 0) + (pl.small_k ? 1 : 0)];
-    auto lds_of = [&](int g) {
-        if (tfree) return pl.small_k ? u16_direct_lds_bytes(h->m, h->dsub) : u16_direct_wide_lds_bytes(h->m, h->dsub, g, pl.cap);
-        return pl.small_k ? u16_lds_bytes(h->m, h->dsub) : u16_wide_lds_bytes(h->m, h->dsub, g, pl.cap);
-    };
-    const double ppl = (double)nq * w / std::max(1, h->kc);
-    int qg = ppl >= 6.0 ? 8 : (ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1));
-    if (h->force_qg == 1 || h->force_qg == 2 || h->force_qg == 4 || h->force_qg == 8) qg = h->force_qg;
-    if (!pl.small_k)   // 4 x qg x cap keys beside the tables: m dsp + qg cap <= 4091, table-free <= 5115 (u16scan.hip.h)
-        while (qg > 1 && lds_of(qg) > LDS_MAX) qg >>= 1;
-    pl.qg = qg;
-    pl.lds = lds_of(qg);
-    if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
-    plan_chunks(h, nq, w, avg_len, U16_PASS, U16_PASS, pl);
-    plan_subbatch(h, nq, K, w, true, pl);
-    return IVFADC_OK;
+    PlanFacts f;
+    f.d = h->d; f.kc = h->kc; f.m = h->m; f.dsub = h->dsub; f.ksub = h->ksub;
+    f.n = h->n; f.maxlen = h->maxlen;
+    f.num_cu = h->num_cu;
+    f.u16 = h->u16;
+    f.allow_filt = h->allow_filt; f.allow_lb = h->allow_lb; f.force_lb = h->force_lb; f.allow_nf = h->allow_nf;
+    f.allow_prune = h->allow_prune; f.allow_mfma = h->allow_mfma; f.mfma_min_kc = h->mfma_min_kc;
+    f.wg8_mode = h->wg8_mode; f.wg8_wide = h->wg8_wide; f.u16_tables = h->u16_tables; f.part_n = h->part_n;
+    f.force_qg = h->force_qg; f.force_chunk = h->force_chunk; f.ws_budget = h->ws_budget;
+    f.tl_use = h->tl_use; f.tl_G = h->tl_G;
+    f.prune_est = h->prune_est;
+    f.have_lb_operands = h->lb_split.p != nullptr;
+    f.have_nf_operands = h->nf_n2.p != nullptr;
+    f.lanes_active = h->dev_entry && (h->is_view || h->n_views.load() > 0);
+    return f;
 }
 
-// query-major: one workgroup per query, no grouping, no partial results
-int plan_query_major(ivfadc_index *h, int64_t nq, int w, bool pre, Plan &pl)
+// the kernel of a planned form (Plan::fn)
+int plan_kernel(Plan &pl, int m, int dsub)
 {
-    // large kc: the selection is a 4*kc-byte stream per query, better done by the lean stand-alone kernel
-    pl.fuse_topw = pl.small_w && h->kc <= 8192 && h->force_qg != -3 && !pl.twolevel && !pre;
-    // Several batches in flight on this replica (the index has views, or this IS a view: ivfadc_search_batches' second lane, a serving
-    // loop's lanes): what bounds the chip then is register-file time, not one launch's latency -- and the fused selection holds a scan
-    // workgroup's four waves and 126 VGPRs each for the 10 k cycles (28 % of its life on the SIFT1M shape, by phase stamps) in which
-    // wave 0 selects and the others wait.  A stand-alone selection, one lean wave per query, costs a launch and gives the scan its
-    // registers back: 42.5 -> 44.7 M q/s with two batches in flight (profiles/r05_topw_probe.txt); one batch at a time keeps the fused form.
-    // (device-pointer entries only, and only while the lanes really run side by side -- h->dev_entry, set by the entry from the root
-    // index's tickets: the host entries are bound by the host's enqueue time, where one more launch per batch costs
-    // ivfadc_search_batches 27.8 -> 25.8 M q/s, and a caller who owns views but searches one batch at a time would pay a launch for nothing)
-    pl.lanes = h->dev_entry && (h->is_view || h->n_views.load() > 0) && nq >= 4 * (int64_t)h->num_cu && h->kc >= 512;
-    if (pl.lanes) pl.fuse_topw = false;
-    // probes per round: share each codeword fetch between PG tables, keep >= 4 workgroups per CU when possible
-    int pg = w >= 2 ? 2 : 1;   // measured: PG=2 beats PG=4 (register pressure halves the occupancy at 4)
-    if (pl.small_k && h->allow_prune && h->prune_est >= PG1_MIN_PRUNED) pg = 1;   // (fb_poll: most of what is probed gets pruned)
-    while (pg > 1 && scan_lds_bytes(h, pg, pl.cap, pl.small_k) > (size_t)(40 << 10)) pg >>= 1;
-    pl.qg = pg;
-    pl.lds = scan_lds_bytes(h, pg, pl.cap, pl.small_k);
-    // lower-bound tables on the matrix cores: four probes per round share one pass over the codebook (a quarter of the exact
-    // build's L1 traffic, a fraction of its vector-ALU work); register selectors and the LDS probe copy only
-    // (measured: m = 48, where the exact build re-reads 768 KB of codewords per probe, +20 % on the HD shape; m = 16 with 1.5 k-point
-    // lists -- the Deep1B shape -- loses 12 %: four barriers and the round's setup per four 24 KB lists cost what the cheaper tables
-    // save, so there the rounds run only on request, ivfadc_set_table_mode(h, 2))
-    const bool lb = h->allow_lb && h->allow_filt && h->lb_split.p != nullptr && lb_shape(h->m, h->dsub) && pl.small_k && w <= 32 &&
-                    h->ksub == 256 && (h->m >= 32 || h->force_lb);
-    pl.form = lb ? ScanForm::QueryMajorLb : ScanForm::QueryMajor;
-    if (lb) {
-        // the top-w selection of a large batch runs as its own launch, one wave per query at full occupancy (per-tile records,
-        // no score matrix); inside this kernel -- two workgroups per CU, three waves idle -- it was a sixth of the launch
-        if (nq >= 4 * (int64_t)h->num_cu || pl.twolevel) pl.fuse_topw = false;
-        pl.qg = w >= 3 ? 4 : w;
-        pl.lds = lb_lds_bytes(h->m, h->dsub, pl.qg);
+    switch (pl.form) {
+    case ScanForm::QueryMajor: pl.fn = (const void *)pick_qscan(m, dsub, pl.qg, pl.small_k); break;
+    case ScanForm::QueryMajorLb: pl.fn = (const void *)pick_qscan_lb(m, dsub, pl.qg); break;
+    case ScanForm::FourWave: pl.fn = (const void *)pick_scan(m, dsub, pl.qg, pl.small_k, pl.stripe); break;
+    case ScanForm::NarrowField: pl.fn = (const void *)(nf_fn_t)nf_scan_kernel<4>; break;   // four points per lane and step (measured: two 9.2 ms, eight 8.1 ms -- and 74 spilled registers -- against 7.76 ms)
+    case ScanForm::EightWave:
+        pl.fn = (const void *)(pl.wide ? (m == 8 ? pick_wg8_wide(pl.q8, dsub) : nullptr) : pick_wg8(pl.q8, m, dsub));
+        if (!pl.fn) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for m = %d, dsub = %d, which has no instantiation", m, dsub);
+        break;
+    case ScanForm::U16: pl.fn = (const void *)(u16_fn_t)u16_scan_kernel; break;
+    case ScanForm::U16Wide: pl.fn = (const void *)(u16_fn_t)u16_wide_scan_kernel; break;
+    case ScanForm::U16Direct: pl.fn = (const void *)(u16_fn_t)u16_direct_scan_kernel; break;
+    case ScanForm::U16DirectWide: pl.fn = (const void *)(u16_fn_t)u16_direct_wide_scan_kernel; break;
     }
-    if (pl.lds > LDS_MAX) { pl.fits = false; return IVFADC_OK; }   // e.g. m = 48 with K near 2048: tables + selector buffers
-    pl.fn = (const void *)(lb ? pick_qscan_lb(h->m, h->dsub, pl.qg) : pick_qscan(h->m, h->dsub, pl.qg, pl.small_k));
-    return IVFADC_OK;
-}
-
-// list-major: work items of (list, group of qg queries that probe it, chunk of CH points), partial results merged behind the scan
-int plan_list_major(ivfadc_index *h, int64_t nq, int K, int w, double avg_len, bool long_lists, bool forced, Plan &pl)
-{
-    // query-group width from the expected number of probes per list
-    const double ppl = (double)nq * w / std::max(1, h->kc);
-    int qg = ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1);
-    // billion-scale lists (a list is megabytes: the stream, not the per-item work, is what a group shares): wider groups pay
-    // much earlier.  SIFT1B shape, step in ms at QG = 1 / 2 / 4 (profiles/r03_a_sift1b_plan_sweep.txt): probes per list 0.125:
-    // 0.26 / 0.30 / 0.38; 0.25: 0.45 / 0.42 / 0.54; 0.5: 0.90 / 0.70 / 0.81; 1.0: 1.55 / 1.07 / 1.15; 2.0: 2.93 / 1.81 / 1.57
-    // -- the regime of one rank of an 8-GPU run on a 16 384-query batch (2048 queries, w = 8)
-    if (long_lists) qg = ppl >= 1.5 ? 4 : (ppl >= 0.2 ? 2 : 1);
-    // ... and where the eight-wave kernel exists (it is planned below for groups of four) it pays from half a probe per list: scan ms of
-    // the SIFT1B shape at 0.25 / 0.5 / 1 probes per list, eight-wave kernel against scan_kernel<QG=2>: 0.355 / 0.525 / 0.70-0.75 against
-    // 0.316 / 0.544 / 0.92-0.93 (round 6)
-    // (K the kernel's pool holds: 64, or 128 where table mode 8 / 9 asks for the wide pool -- a request, so wg8_mode > 0 there)
-    const bool w8_k = pl.small_k || (K <= W8_WIDE_MAX_K && h->wg8_wide && h->wg8_mode > 0 && h->m == 8);
-    // ... the kernel exists for the index and may run: every admission below is this and a reason to take it
-    // (positions and byte offsets of a list are 28- / 31-bit quantities in the kernel: lists of fewer than 2^28 points; m = 16: 27-bit
-    // lists -- a point is 16 bytes -- and on request only: w8_md)
-    const bool w8_base = w8_k && h->allow_filt && h->wg8_mode >= 0 && w8_md(h) && h->ksub == 256 && h->maxlen < w8_maxlen(h);
-    const bool w8_shape = w8_base && (h->wg8_mode > 0 || w8_default(h)) && avg_len >= 8192.0;
-    if (long_lists && w8_shape && ppl >= 0.5) qg = 4;
-    if (forced) qg = h->force_qg;
-    // eight queries per code stream behind the 4-bit narrow-field filter (nfscan.hip.h): conflict-free gathers, a third of the vector
-    // instructions per (query, point), every list streamed once per eight queries -- where the shape has the kernel, K fits the
-    // register selectors and the lists are probed often enough to fill the groups
-    // (measured, SIFT1B shape, 16 384 x w = 8: 7.76 ms against 7.44 ms for the 16-bit four-query kernel -- DESIGN.md 4.11 -- so the kernel
-    // runs on request only: ivfadc_set_tuning(h, 8, 0))
-    const bool nf_ok = h->allow_nf && h->allow_filt && h->nf_n2.p != nullptr && nf_shape(h->m, h->dsub) && h->ksub == 256 && pl.small_k;
-    if (h->force_qg == 8 && !nf_ok) qg = 4;
-    if (nf_ok && h->force_qg == 8) {
-        pl.form = ScanForm::NarrowField;
-        pl.fn = (const void *)(nf_fn_t)nf_scan_kernel<4>;   // four points per lane and step (measured: two 9.2 ms, eight 8.1 ms -- and 74 spilled registers -- against 7.76 ms)
-        pl.qg = qg = 8;
-        pl.lds = (size_t)NfLds::END;
-    } else {
-        // keep two workgroups per CU when possible (a forced width only yields to the hard LDS limit)
-        // (groups of four that the wide-pool kernel takes below need none of the four-wave kernel's LDS selectors: its budget does not narrow them)
-        // (... nor do the groups of four of an m = 16 index that the kernel takes on request: the four-wave kernel's 64 KB of f32 tables are not built)
-        const bool w8_wide_ok = w8_base && h->wg8_mode > 0 && (!pl.small_k || h->m == 16);
-        // the four-wave kernel's striped form (and at m = 8 its 16-bit integer filter), and its LDS need, at a width
-        auto stripe_at = [&](int g) { return h->allow_filt && filt_shape(h->m, h->dsub) && g == 4 && h->ksub == 256; };
-        auto lds_at = [&](int g) { return scan_lds_bytes(h, g, pl.cap, pl.small_k, true, stripe_at(g)); };
-        while (qg > 1 && !(qg == 4 && w8_wide_ok) && lds_at(qg) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
-        if (!(qg == 4 && w8_wide_ok) && lds_at(qg) > LDS_MAX) { pl.fits = false; return IVFADC_OK; }
-        // four queries per code stream on long lists of the m = 8 / dsub = 16 shape: the eight-wave kernel (a work item must feed
-        // eight waves: lists of at least 8 K points).  Measured on the SIFT1B shape against the four-wave kernel (profiles/r06_w8_sweep.txt,
-        // the eight-wave kernel with its workgroup pool): 16 384 queries, scan ms at w = 1 / 8: 1.36 / 5.73 against 1.68 / 7.46;
-        // 2048 x w = 8: 1.06 against 1.47.
-        // (The list-partitioned mode needs nothing of the kernel: the partition is applied in front of it -- the top-w kernel counts this rank's
-        // lists only into list_cnt, which bucket_scan_kernel turns into work items and item_list, bucket_scatter_kernel drops the other
-        // ranks' probes -- and behind it, in merge_kernel; a rank's work items are ordinary ones)
-        // (w = 1 too since the workgroup pool: 1.36 against the four-wave kernel's 1.67 ms)
-        if (qg == 4 && w8_base && (h->wg8_mode > 0 || (w8_default(h) && avg_len >= 8192.0))) {
-            pl.form = ScanForm::EightWave;
-            pl.wide = !pl.small_k;
-            // ... and EIGHT queries per code stream (wg8_scan_kernel<8>: 16-byte entries, 32 instead of 48 instructions per point and eight queries)
-            // where the lists are probed often enough to fill groups of eight (table mode 7: wherever the kernel exists)
-            pl.q8 = h->wg8_mode == 2 || (h->wg8_mode == 0 && !forced && ppl >= W8_Q8_MIN_PPL);
-            if (pl.q8) qg = 8;
-            pl.lds = h->m == 16 ? (pl.q8 ? (size_t)W8Lds<8, 1, 16>::END : (size_t)W8Lds<4, 1, 16>::END)
-                   : pl.wide    ? (pl.q8 ? (size_t)W8Lds<8, 2>::END : (size_t)W8Lds<4, 2>::END)
-                                : (pl.q8 ? (size_t)W8Lds<8>::END : (size_t)W8Lds<4>::END);
-            pl.fn = (const void *)(pl.wide ? (h->m == 8 ? pick_wg8_wide(pl.q8, h->dsub) : nullptr) : pick_wg8(pl.q8, h->m, h->dsub));
-            if (!pl.fn) return fail(IVFADC_ERR_STATE, "eight-wave scan planned for m = %d, dsub = %d, which has no instantiation", h->m, h->dsub);
-            pl.threads = W8_THREADS;
-        } else {
-            pl.form = ScanForm::FourWave;
-            pl.stripe = stripe_at(qg);
-            pl.lds = lds_at(qg);
-            pl.fn = (const void *)pick_scan(h->m, h->dsub, qg, pl.small_k, pl.stripe);
-        }
-        pl.qg = qg;
-    }
-    plan_chunks(h, nq, w, avg_len, 4096, 1024, pl);
-    return IVFADC_OK;
-}
-
-int make_plan(ivfadc_index *h, int64_t nq, int K, int w, Plan &pl, bool pre = false)   // pre: the probes are the caller's (PreProbes): no coarse stage of any kind
-{
-    plan_begin(h, nq, K, w, pre, pl);
-    const double avg_len = (double)h->n / std::max(1, h->kc);
-    // list-major (queries that probe a list share its code stream; per-item grouping/merge overhead) wins when
-    // the lists are very long (a query's probe must be split over workgroups anyway), or when a list is probed by
-    // enough queries to fill the groups AND the batch makes enough work items to fill the chip; otherwise
-    // query-major (one workgroup per query, no grouping, no partial results).  Measured crossovers, m = 8,
-    // kc = 8192, 16 probes/list: list-major ahead from 10 KB lists on (1.74 vs 1.90 ms); SIFT1M-shape (8
-    // probes/list but only 2048 work items): query-major 92 vs 190 us; Deep1B-shape (4.9 probes/list): query-major.
-    const double ppl_ = (double)nq * w / std::max(1, h->kc);
-    const bool long_lists = avg_len * h->m > 256.0 * 1024.0;
-    // ... and the lists are long enough to amortise a fresh selection per (query, list): kc = 8192, 16 probes/list:
-    // 3.7k-point lists 1.88 vs 2.01 ms, 12k 2.70 vs 3.28 ms for list-major; SIFT1M-shape (1k-point lists) with 16k-64k
-    // queries: query-major 18-20 M q/s vs 12 M
-    const bool shared = ppl_ >= 6.0 && (double)nq * w / 4.0 >= 64.0 * h->num_cu && avg_len >= 3072.0;
-    // ... or when a handful of queries with heavy probes would leave most CUs idle at one workgroup per query: list-major
-    // spreads a query's probes over workgroups (HD-shape, 64 queries: w = 8 0.39 vs 0.31 M q/s, w = 32 0.21 vs 0.10;
-    // SIFT1M- and Deep1B-shape probes are too light for it: 1.4 vs 3.0 M and 0.2 vs 0.7 M q/s)
-    const bool few_heavy = nq <= h->num_cu && w >= 8 && avg_len * h->m >= 64.0 * 1024.0;   // 256 queries: +10 % (w = 8), +60 % (w = 32); 512: even
-    // ... or a very small batch with several probes each: one workgroup per query walks its w probes in sequence, list-major
-    // (ungrouped: one work item per (query, probe), no bucket kernels) runs them side by side.  SIFT1M-shape, measured
-    // query-major vs list-major per batch: 1 query w = 8 42 vs 35 us, w = 16 64 vs 42 us, w = 32 118 vs 56 us; even at
-    // 64 queries for w = 8 / 16; w <= 4 stays query-major (30 vs 33 us).  Not with a large kc, where the per-list
-    // bookkeeping of the list-major plan costs more than it buys (Deep1B-shape 380 vs 234 us)
-    const bool few_many = w >= 8 && nq <= 32 + (int64_t)w && nq <= h->num_cu / 4 && h->kc <= 8192;
-    bool query_major = !(long_lists || shared || few_heavy || few_many);
-    if (h->force_qg == -1 || h->force_qg == -3) query_major = true;
-    if (h->part_n > 1) query_major = false;   // list-partitioned mode: the list-major plan is the one that skips other ranks' lists
-    const bool forced = (h->force_qg == 1 || h->force_qg == 2 || h->force_qg == 4 || h->force_qg == 8);
-    if (forced) query_major = false;
-    TRY(query_major ? plan_query_major(h, nq, w, pre, pl) : plan_list_major(h, nq, K, w, avg_len, long_lists, forced, pl));
-    if (pl.fits) plan_subbatch(h, nq, K, w, !query_major, pl);
     return IVFADC_OK;
 }
 
@@ -1898,7 +1613,7 @@ bool sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
     if (off || !h->allow_sq || h->force_qg != 0 || h->u16) return false;
     if (K > 64 || w > 64 || nq > 64 || nq * w > 512) return false;
     if ((h->d & 3) != 0) return false;
-    const size_t lds = scan_lds_bytes(h, 1, 64, true) + 64 + (h->kc <= sq_inside_kc(h) ? (size_t)h->kc * 4 : 0);
+    const size_t lds = scan_lds_bytes(h->m, h->d, 1, 64, true) + 64 + (h->kc <= sq_inside_kc(h) ? (size_t)h->kc * 4 : 0);
     return lds <= LDS_MAX;
 }
 
@@ -1945,7 +1660,7 @@ int search_small(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, ui
     a.arrive = h->sq_arrive.as<u32>();
     a.out_ids = d_ids; a.out_dists = d_dists; a.out_counts = d_counts;
     a.scanned_points = h->misc.as<u64>();
-    const size_t lds = scan_lds_bytes(h, 1, 64, true) + 64 + (inside ? (size_t)h->kc * 4 : 0);
+    const size_t lds = scan_lds_bytes(h->m, h->d, 1, 64, true) + 64 + (inside ? (size_t)h->kc * 4 : 0);
     sq_fn_t fn = pick_sq(h->m, h->dsub);
     int occ = 0;
     TRY(fn_occupancy(h, (const void *)fn, lds, occ));
@@ -2177,13 +1892,14 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
         return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, prl, prd);
     }
-    Plan pl;
     TRY(fb_poll(h));
-    TRY(h->u16 ? make_plan_u16(h, nq, K, w, pl, pre != nullptr) : make_plan(h, nq, K, w, pl, pre != nullptr));
+    const PlanFacts facts = plan_facts(h);
+    Plan pl = h->u16 ? make_plan_u16(facts, nq, K, w, pre != nullptr) : make_plan(facts, nq, K, w, pre != nullptr);
     if (!pl.fits) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the selection kernels' LDS need exceeds a CU for this m and K");
         return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, prl, prd);   // "any K and w" holds for every m
     }
+    TRY(plan_kernel(pl, h->m, h->dsub));
     if (parted && pl.nb < nq)
         return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the batch must fit one sub-batch (raise ivfadc_set_workspace_limit or split the batch)");
     for (int64_t b0 = 0; b0 < nq; b0 += pl.nb) {
@@ -2213,7 +1929,7 @@ int coarse_dev(ivfadc_index *h, int64_t nq, const float *d_q, int w, int32_t *d_
     const int kc = h->kc;
     u64 *d_sink = (u64 *)((char *)h->misc.p + MISC_SINK);
     const bool generic = w > IVFADC_MAX_W;
-    const CoarseForm cf = coarse_form(h, w, !generic, true);   // (any batch size: the sub-batches below are clamped to the two-level kernel's)
+    const CoarseForm cf = coarse_form(plan_facts(h), w, !generic, true);   // (any batch size: the sub-batches below are clamped to the two-level kernel's)
     const bool twolevel = cf.twolevel, mfma = cf.mfma;
     // sub-batches: the distance rows (generic: + two key rows) stay inside the workspace budget
     const size_t per_q = (twolevel ? (size_t)h->tl_G : (size_t)kc) * (generic ? 20 : 4) + (size_t)w * 4 + 64;

@@ -16,6 +16,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <type_traits>
+#include "scan_layouts.h"   // the LDS layouts and sizes that the kernels below and the plan (plan.h) both read
 #include "wave_sort.hip.h"
 
 typedef unsigned long long u64;

@@ -40,31 +40,8 @@
 // < 1e-30, or nothing finite) get inv = 0: every field is 0, every point passes and is evaluated exactly -- slow, and correct.
 #pragma once
 
-constexpr int NF_QG = 8;                       // queries per code stream
-constexpr u32 NF_TAB_BYTES = 256u * 256u;      // 256 codes x (8 sub-quantizers x 2 copies x 16 bytes)
-constexpr int NF_POOL = 128;                   // parked (point, query) pairs per wave; drained from 64 on
-constexpr int NF_ES = 4;                       // dwords per parked pair: code bytes (2), list position, integer sum << 8 | query slot
-
-// LDS behind the table (byte offsets)
-struct NfLds {
-    static constexpr u32 RES = NF_TAB_BYTES;                  // f32 residuals [s][t4][ii][4]: 8 x 4 x 8 x 16 B = 4 KB
-    static constexpr u32 RN2 = RES + 4096u;                   // f32 [ii][s]: ||r_s,ii||^2 (1 - 2^-17)
-    static constexpr u32 SMIN = RN2 + 256u;                   // u32 [ii][s]: ordered bits of min_c e          (atomic)
-    static constexpr u32 SMAX = SMIN + 256u;                  // u32 [ii][s]: ordered bits of max_c e          (atomic)
-    static constexpr u32 BASE = SMAX + 256u;                  // f32 [ii][s]: base
-    static constexpr u32 QC = BASE + 256u;                    // f32 [4][8]: inv_s, sum of bases, dc_s, nn_s (sum over ii of max ||cb||^2 + ||r||^2)
-    static constexpr u32 QI = QC + 128u;                      // u32 [3][8]: probe index, query, visit-order base of slot s
-    static constexpr u32 HARD = QI + 96u;                     // u64 [8]: the bounds the item started from (from outside the workgroup)
-    static constexpr u32 STHR = HARD + 64u;                   // u64 [8]: workgroup-shared bounds
-    static constexpr u32 SCNT = STHR + 64u;                   // int [4][8]
-    static constexpr u32 SWI = SCNT + 128u;                   // u32 [4]
-    static constexpr u32 TW = SWI + 16u;                      // int [4][8]: each wave's integer budgets of the moment (read by lane-varying slot)
-    static constexpr u32 POOL = TW + 128u;                    // u32 [4][NF_POOL][NF_ES]
-    static constexpr u32 END = POOL + 4u * NF_POOL * NF_ES * 4u;
-};
-static_assert(NfLds::END <= 80u * 1024u, "two workgroups per CU");
-static_assert((NfLds::POOL & 15u) == 0, "16-byte pool entries");
-static_assert((NfLds::HARD & 7u) == 0, "8-byte bounds");
+// NF_QG, NF_TAB_BYTES, NF_POOL, NF_ES and the LDS layout NfLds are shared with the plan: scan_layouts.h, which kernels.hip.h includes in
+// front of namespace ivf
 
 static __device__ __forceinline__ u32 nf_perm(u32 s0, u32 s1, u32 sel)
 {

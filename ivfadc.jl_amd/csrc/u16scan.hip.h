@@ -44,41 +44,9 @@
 // K <= 448 up to 4600, K <= 192 up to 4856 -- and cap = 4096 fits where m dsp <= 1016, so there K reaches IVFADC_MAX_K = 2048.
 #pragma once
 #include "kernels.hip.h"
+#include "scan_layouts.h"   // U16_P ... U16_DIRECT_COST and the four u16_*_lds_bytes: shared with the plan
 
 namespace ivf {
-
-constexpr int U16_P = 8;                    // (query, probe) pairs per work item, at most
-constexpr int U16_PPT = 4;                  // points per thread and pass
-constexpr int U16_PASS = 256 * U16_PPT;     // points per pass
-constexpr int U16_TAB_FLOATS = 8192;        // table area: 32 KB, P x T floats (T = codewords per tile)
-constexpr int U16_XCH_FLOATS = 4 * U16_P * 64 * 2;   // the table-free K <= 64 entry keeps only the wave-merge exchange: 4 x P x 64 keys, 16 KB
-// ivfadc_set_u16_tables(h, 2): table-free iff min(avg_len, U16_PASS) * U16_DIRECT_COST <= ksub.  The arithmetic alone says 1, and the
-// measurement leaves it there: at k = 1024 the table-free scan is ahead at every avg_len of 128 ... 2048 (no crossover, so <= 1), at
-// k = 256 and avg_len 977 the tables are (so > 0.262); 1 is the largest such value (profiles/u16_direct.json)
-constexpr float U16_DIRECT_COST = 1.0f;
-
-// dynamic LDS of u16_scan_kernel: residuals [P][m][dsp] (dsp = dsub rounded up to 4: one 16-byte read serves four terms), table area
-// (the wave-merge exchange, 4 x P x 64 keys = 16 KB, aliases it), per-wave counts, two words of work-queue / verdict exchange
-static inline size_t u16_lds_bytes(int m, int dsub)
-{
-    return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)U16_TAB_FLOATS * 4 + 4 * U16_P * 4 + 16;
-}
-
-// ... of u16_wide_scan_kernel: the selector buffers [4 waves][qg][cap] u64 between the table area and the small words
-static inline size_t u16_wide_lds_bytes(int m, int dsub, int qg, int cap)
-{
-    return u16_lds_bytes(m, dsub) + (size_t)4 * qg * cap * 8;
-}
-
-// ... of the table-free entries: no table area
-static inline size_t u16_direct_lds_bytes(int m, int dsub)
-{
-    return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)U16_XCH_FLOATS * 4 + 4 * U16_P * 4 + 16;
-}
-static inline size_t u16_direct_wide_lds_bytes(int m, int dsub, int qg, int cap)
-{
-    return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)4 * qg * cap * 8 + 4 * U16_P * 4 + 16;
-}
 
 // qg: the bucket grouping of the plan (1, 2, 4 or 8); items carry up to qg pairs.  SMALL: K <= 64, register selectors;
 // DIRECT: table-free accumulate phase

@@ -50,15 +50,8 @@
 // where a list is probed by eight queries or more on average.
 #pragma once
 
-// Waves per workgroup.  Measured with more (round 6; the table build is laid out for 512 threads, further waves repeat the first ones' share --
-// the same values to the same places): TEN (640 threads at <= 96 registers) run one workgroup per CU -- a workgroup's waves spread 3-3-2-2
-// over the SIMDs, two of them would need six register sets on a SIMD -- 9.6 ms; TWELVE (<= 80 registers: the scan loop still holds no
-// spilled register, the candidate path 150) run two per CU and take 9.1 ms, 8.5 without candidates against 5.0: six waves per SIMD on the
-// same LDS are slower than four, whatever the guide's 2 cycles per ds_read_b64 leave free on paper.
-constexpr int W8_NW = 8;
-constexpr int W8_THREADS = 64 * W8_NW;
-constexpr int W8_ES = 3;                      // dwords per parked point: code bytes (2), list position (m = 16: W8Lds::ES = 5, four dwords of code bytes)
-constexpr u32 W8_TAB_BYTES = 256u * 256u;     // 256 codes x (32 / NQ copies x 8 sub-quantizers x 2 NQ bytes; m = 16: 16 / NQ copies x 16 sub-quantizers)
+// W8_NW, W8_THREADS, W8_ES, W8_TAB_BYTES, the LDS layout W8Lds<NQ, KP, M> and w8_ds_ok are shared with the plan: scan_layouts.h, which
+// kernels.hip.h includes in front of namespace ivf
 template <int NQ, int M = 8> constexpr u32 W8_GTAB_FLOATS = (u32)M * 256u * (u32)NQ;   // f32 tables of a work item in device memory: [ii][label][NQ queries]
 // the integer filter's cap per entry: M entries of at most W8_QCAP sum to less than 0x8000 (8 x 4095 = 32 760, 16 x 2047 = 32 752) -- see
 // THE FILTER AT SIXTEEN TERMS below
@@ -66,49 +59,7 @@ template <int M> constexpr u32 W8_QCAP = M == 8 ? 4095u : 2047u;
 static_assert(8u * W8_QCAP<8> <= 0x7FFFu && 16u * W8_QCAP<16> <= 0x7FFFu, "a point's integer sum stays below 0x8000");
 static_assert(0x8000u + 16u * W8_QCAP<16> < 0x10000u && 0x8000u + 8u * W8_QCAP<8> < 0x10000u, "a biased field never carries into its neighbour");
 
-// KP: the pool's entries per lane (1: K <= 64, the layout of every measurement so far; 2: K <= 128, the wide pool -- see w8_pool_offer)
-// M: sub-quantizers (8, or 16: SIXTEEN SUB-QUANTIZERS below).  Two sizes depend on it, both behind the pool, so everything the helpers
-// below read at fixed addresses stands where it stood: a parked point takes five dwords instead of three (16 code bytes), and the residuals
-// -- 16 x (DS + 1) x NQ x 4 B, 576 NQ bytes at DS = 8, which the block sized for m = 8 / DS = 16 (544 NQ bytes) does NOT hold -- are built
-// where the rings are: the rings are empty from the end of a work item's scan to the start of the next one's, the residuals live from
-// the top of a work item to the barrier behind its table build, and barriers separate the two (RESB; at m = 16 the block at RES is unused).
-template <int NQ, int KP = 1, int M = 8> struct W8Lds {
-    static_assert(NQ == 4 || NQ == 8, "four or eight queries per code stream");
-    static_assert(KP == 1 || KP == 2, "one or two pool entries per lane");
-    static_assert(M == 8 || (M == 16 && KP == 1), "eight sub-quantizers, or sixteen with the one-entry-per-lane pool");
-    static constexpr u32 ES = M == 8 ? (u32)W8_ES : 5u;      // dwords per parked point: M / 4 of code bytes, list position
-    static constexpr u32 RES = W8_TAB_BYTES;                  // f32 residuals [ii][t][s]: 8 x (DS x NQ + NQ of padding) x 4 B, sized for DS = 16 (W8_RES_STRIDE)
-    static constexpr u32 SMAX = RES + 8u * (16u * NQ + NQ) * 4u;   // u32 [NQ]: bits of the per-query largest entry (atomicMax); f32 inv[NQ] behind
-    static constexpr u32 QC = SMAX + 8u * NQ;                 // f32 dc[NQ]; u32 visit-order base[NQ]; u32 probe index[NQ]; u32 query[NQ]
-    static constexpr u32 HARD = QC + 16u * NQ;                // u64 [NQ]: the bounds the item started from
-    static constexpr u32 STHR = HARD + 8u * NQ;               // u64 [NQ]: workgroup-shared bounds
-    static constexpr u32 SWI = STHR + 8u * NQ;                // u32 [4]
-    static constexpr u32 POOL = SWI + 16u;                    // u64 [NQ][64 KP]: the workgroup's K smallest keys per slot, unordered (w8_pool_offer)
-    static constexpr u32 POOL_SLOT = 64u * KP * 8u;           // bytes of a slot's pool
-    static constexpr u32 PARK = POOL + NQ * POOL_SLOT;        // u32 [8][32][W8_ES]: the waves' rings of parked points (W8_RING)
-    static constexpr u32 COLD = PARK + (u32)W8_NW * 32u * ES * 4u;     // u32 [NQ][16]: a cold work item's first step, every wave's ceil(K / 8)-th smallest integer sum per slot
-    // (KP = 1: up to sixteen waves; the wide pool's 8 NQ more entries leave the eight-query form room for the eight waves there are: u32 [NQ][8])
-    static constexpr u32 COLD_SLOT = KP == 1 ? 64u : 4u * (u32)W8_NW;
-    static constexpr u32 END = COLD + COLD_SLOT * NQ;
-    static constexpr u32 RESB = M == 8 ? RES : PARK;          // where the residuals are built
-    static_assert(END <= 80u * 1024u, "two workgroups per CU");
-    static_assert((HARD & 7u) == 0 && (STHR & 7u) == 0 && (POOL & 7u) == 0, "8-byte bounds");
-    static_assert(M == 8 || 16u * (8u + 1u) * NQ * 4u <= COLD - PARK, "m = 16: the residuals of DS <= 8 fit the rings' block");
-    static_assert((RESB & 15u) == 0, "16-byte residual rows");
-};
-static_assert(W8Lds<4>::END == 73264u && W8Lds<8>::END == 77904u, "the layout the plan's LDS figures and the measurements were taken with");
-static_assert(W8Lds<4, 2>::END == 75184u && W8Lds<8, 2>::END == 81744u, "the wide pool's layouts: 2 / 4 KB more pool, 32 B per slot of cold-start words");
-static_assert(W8Lds<4, 2>::POOL == W8Lds<4>::POOL && W8Lds<8, 2>::POOL == W8Lds<8>::POOL, "everything in front of the pool stands where the helpers below read it");
-static_assert(W8Lds<4, 1, 16>::END == 75312u && W8Lds<8, 1, 16>::END == 79952u, "m = 16: 2 KB more of rings (five dwords per parked point), nothing else");
-static_assert(W8Lds<4, 1, 16>::PARK == W8Lds<4>::PARK && W8Lds<8, 1, 16>::PARK == W8Lds<8>::PARK, "m = 16: everything up to the rings stands where it stood");
-
-// Sub-space widths the kernel is instantiated for (d = 8 DS), and the residuals' floats per sub-quantizer: DS rows of NQ queries and ONE row
-// of padding.  A quad of the table build reads the rows of four neighbouring sub-quantizers at once, 16 B per lane (NQ = 8: 16 B of a
-// 32-byte row): sub-quantizer ii's block starts (DS + 1) ii rows on, and DS + 1 is ODD for every DS here, so ii -> (DS + 1) ii is
-// one-to-one modulo 16 four-bank groups (NQ = 4: 17, 13, 9 and 5 ii mod 16 are four different groups for ii = 0 .. 3 and for 4 .. 7) and
-// modulo 8 eight-bank groups (NQ = 8): the quad's four lanes read four different bank groups at DS = 4, 8, 12 and 16 alike.  Without
-// the padding row the blocks would start DS ii rows apart: the same group twice or four times over (DS = 16: always the same one).
-constexpr bool w8_ds_ok(int ds) { return ds == 4 || ds == 8 || ds == 12 || ds == 16; }
+// the residuals' floats per sub-quantizer: DS rows of NQ queries and ONE row of padding (why: at w8_ds_ok in scan_layouts.h)
 template <int NQ, int DS> constexpr u32 W8_RES_STRIDE = (u32)((DS + 1) * NQ);
 
 static __device__ __forceinline__ u32 w8_perm(u32 s0, u32 s1, u32 sel)

@@ -1,6 +1,6 @@
 """What tests/test_gpu_sequences.py needs and a CPU can check (tests/test_sequences_walk.py): the walk that puts every scan form behind
 every other on one handle, the draws of the sequence fuzz, and a restatement of the plan's rules -- which form a search with given
-settings must run -- from make_plan / make_plan_u16 / search_dev (csrc/ivfadc_hip.hip).  Nothing here touches the library."""
+settings must run -- from make_plan / make_plan_u16 (csrc/plan.h) and search_dev (csrc/ivfadc_hip.hip).  Nothing here touches the library."""
 import numpy as np
 
 LDS_MAX = 160 << 10
@@ -54,7 +54,7 @@ def w8_shape(m, dsub, on_request):
 
 
 def scan_lds_bytes(m, dsub, ksub, qg, cap, small, list_major, allow_filt):
-    """scan_lds_bytes of the four-wave kernels (mirrors carve_lds in kernels.hip.h)."""
+    """scan_lds_bytes of the four-wave kernels (csrc/scan_layouts.h; restates carve_lds in kernels.hip.h)."""
     d = m * dsub
     b = max(m, 2) * 256 * qg * 4
     b += ((d * qg + 3) & ~3) * 4

@@ -366,7 +366,7 @@ def test_8bit_handle_and_invalid_modes(native):
 # ---- 11. mode 2 --------------------------------------------------------------------------------------------------------------------------
 def test_mode_2_follows_the_rule(native):
     """Two indexes on either side of min(avg_len, 1024) * U16_DIRECT_COST <= ksub, the constant read from the source."""
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ivfadc.jl_amd", "csrc", "u16scan.hip.h")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ivfadc.jl_amd", "csrc", "scan_layouts.h")).read()   # (u16scan.hip.h includes it)
     cost = float(re.search(r"constexpr float U16_DIRECT_COST = ([0-9.]+)f;", src).group(1))
     assert cost >= 1.0
     d, m, kc = 16, 2, 4

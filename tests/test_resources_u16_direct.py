@@ -13,8 +13,9 @@ from test_resources_u16_wide import LDS_MAX, SMALL, WIDE, _one, kernels  # noqa:
 DIRECT, DIRECT_WIDE = "22u16_direct_scan_kernelE", "27u16_direct_wide_scan_kernelE"
 
 
-def _src():
-    return open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ivfadc.jl_amd", "csrc", "u16scan.hip.h")).read()
+def _src():   # the kernel header and the sizes it includes (scan_layouts.h: shared with the plan)
+    csrc = os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ivfadc.jl_amd", "csrc")
+    return open(os.path.join(csrc, "u16scan.hip.h")).read() + open(os.path.join(csrc, "scan_layouts.h")).read()
 
 
 def _no_scratch_no_static_lds(name, r):

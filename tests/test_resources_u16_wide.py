@@ -62,7 +62,7 @@ def test_wide_entry_compiles_and_fits_a_cu(kernels):
     assert r["vgpr_count"] <= 256 and r.get("vgpr_spill_count", 0) == 0, "%s: %r (two waves per SIMD need <= 256 VGPRs)" % (name, r)
     assert r.get("group_segment_fixed_size", 0) == 0, "%s carries static LDS" % name
     # u16_wide_lds_bytes with the constants of the source, at the reaches the header documents: m dsp + qg cap <= 4091
-    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ivfadc.jl_amd", "csrc", "u16scan.hip.h")).read()
+    src = open(os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "ivfadc.jl_amd", "csrc", "scan_layouts.h")).read()   # (u16scan.hip.h includes it)
     P = int(re.search(r"constexpr int U16_P = (\d+);", src).group(1))
     TF = int(re.search(r"constexpr int U16_TAB_FLOATS = (\d+);", src).group(1))
 
