@@ -235,9 +235,53 @@ int ivfadc_clone_view(ivfadc_t *h, ivfadc_t **out_view);
  * IVFADC_ERR_STATE: h is itself a view (plain or subset: take the subset from the index).  (A handle that was never given lists is an
  * empty index, as for ivfadc_search, and so is every subset of it.)  IVFADC_ERR_INVALID, before any device call: NULL h, NULL out_view,
  * NULL bits with nbits > 0, nbits > 2^32.
- * Not covered: predicates evaluated per query inside the scan, and subsets of ivfadc_mg_* handles.                               */
+ * Not covered: subsets of ivfadc_mg_* handles.  (Predicates evaluated per query inside the scan: ivfadc_search_masked, below.)          */
 int ivfadc_clone_subset(ivfadc_t *h, const uint32_t *bits, uint64_t nbits, ivfadc_t **out_view, int64_t *out_n);
 int ivfadc_clone_subset_device(ivfadc_t *h, const uint32_t *d_bits, uint64_t nbits, ivfadc_t **out_view, int64_t *out_n);
+
+/* PER-QUERY filtered search: one batch whose queries carry different predicates (a tenant per query, a category per query, "not what this
+ * user has already seen"), with no copy of the lists.  A MASK SET is nmasks bitmaps over STORED ids with the bit definition of
+ * ivfadc_clone_subset: id i is selected by mask r iff i < nbits and bit (i & 31) of word bits[r * ceil(nbits / 32) + (i >> 5)] is set.
+ * Entries that share an id are kept or dropped together; ids at or above nbits are never selected.  At creation the set is converted
+ * once, on the device, into one bit per stored entry in list order (csrc/maskset_plan.h, csrc/maskset.hip.h), which the list scan tests.
+ *
+ * ivfadc_search_masked gives every query a mask number, mask_of_query[q]:
+ *   r >= 0      the result of query q is knn_search (index.jl:204-258) on the lists with every entry mask r does not select removed by
+ *               deleteat! (utils.jl:98-99, without _shift_inverse_index!).  The w probed cells, their order and their coarse distances
+ *               are those of the UNFILTERED index (a filter does not move centroids); the visit order is (probe rank, stored position),
+ *               ties go by visit order, the count is min(K, selected entries in the probed lists).  Byte for byte what
+ *               ivfadc_clone_subset(h, mask r) returns for that query.
+ *   -1          (the -1 rule) no filter: the bytes of a plain ivfadc_search of that query.
+ *   NULL array  every query uses mask 0.
+ * The host entry validates mask_of_query before any launch: a value outside [-1, nmasks) is IVFADC_ERR_INVALID naming the query.  The
+ * device entry cannot validate without a synchronisation: its ingest clamps every value into [-1, nmasks), so a violated precondition
+ * cannot read outside the set; that query's results are then unspecified.
+ *
+ * Mask set creation: 1 <= nmasks, nbits <= 2^32; nbits == 0 is the empty mask (bits may be NULL).  out_kept (nmasks values, may be NULL):
+ * the entries each mask selects.  IVFADC_ERR_INVALID, before any device call: NULL h, NULL out, nmasks < 1, NULL bits with nbits > 0,
+ * nbits > 2^32.  The set is made from the index itself: a view or a subset view is refused with IVFADC_ERR_STATE (take it from the index
+ * itself).  Creation uploads pending list changes first and is blocking; _device: the bitmaps lie in device memory of h's GPU and are
+ * complete when the call is made.  It reads only ids, so it serves UInt8 and UInt16 handles, :opq-loaded handles and device-synthesised
+ * lists alike.  A mask set is immutable: any number of handles and threads may search with it at once; destroying it while a search with
+ * it is in flight is the caller's error, as for ivfadc_destroy.
+ *
+ * h and s (the view rule): h is the index s was made from, or a plain view of it (ivfadc_clone_view: the same lists, so two masked batches
+ * can be in flight on one replica).  IVFADC_ERR_STATE: a subset view; another index; an index that has changed since s was made (any
+ * mutator, by the generation rule of views); a handle with a list partition set.  K < 1 or w < 1: IVFADC_ERR_ASSERT, as ivfadc_search;
+ * w > kc is clamped as ivfadc_search clamps it.  Every K and w is served; batches are sub-batched under ivfadc_set_workspace_limit; a
+ * pending hint is dropped, as by any search.  There is no latency path, no fused top-w and no riders.  The 8-bit list scan is
+ * masked_scan_kernel (stats.last_striped == 8); K or w > 2048, ivfadc_set_tuning(h, -2, 0) and every UInt16 handle take the generic path,
+ * where a rejected point's key sorts behind every real key.  The device entry is asynchronous on the handle's stream.
+ * Not covered: masks in the query-major, eight-wave, narrow-field and UInt16 scan kernels; masks together with caller-supplied probes;
+ * ivfadc_search_batches, ivfadc_mg_*, the list-partitioned mode and the all-gather entries; predicates other than id bitmaps.         */
+typedef struct ivfadc_maskset ivfadc_maskset_t;
+int ivfadc_maskset_create(ivfadc_t *h, int nmasks, const uint32_t *bits, uint64_t nbits, ivfadc_maskset_t **out, int64_t *out_kept);
+int ivfadc_maskset_create_device(ivfadc_t *h, int nmasks, const uint32_t *d_bits, uint64_t nbits, ivfadc_maskset_t **out, int64_t *out_kept);
+void ivfadc_maskset_destroy(ivfadc_maskset_t *s);
+int ivfadc_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *queries, int K, int w,
+                         const int32_t *mask_of_query, uint32_t *out_ids, float *out_dists, int32_t *out_counts);
+int ivfadc_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, int K, int w,
+                                const int32_t *d_mask_of_query, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
 
 /* Same, with every buffer already resident in device memory of the handle's GPU.
  * Asynchronous on the handle's stream; pair with ivfadc_sync().                          */
@@ -434,7 +478,8 @@ typedef struct {
                                 * form (m = 8, 64 < K <= 128; table modes 8 / 9), four / eight queries per code stream -- also what a rank
                                 * of the list-partitioned mode reports (ivfadc_set_list_partition); 6 / 7 = the table-free scan of a
                                 * 16-bit handle (ivfadc_set_u16_tables), register selectors (K <= 64) / LDS selectors (64 < K); the
-                                * table forms of a 16-bit handle report 0 */
+                                * table forms of a 16-bit handle report 0; 8 = the masked scan of ivfadc_search_masked
+                                * (masked_scan_kernel, csrc/maskset.hip.h) */
     int32_t  coarse_listed;    /* 1: the last batch's coarse filter wrote per-tile records (four smallest keys of every
                                 * (query, 64-centroid tile)) instead of the score matrix, and the top-w enumerated them */
     int64_t  pruned_points;    /* points of probed lists that were NOT scanned: the list's coarse distance already lay above

@@ -13,6 +13,7 @@ SO_PATH = os.path.join(CSRC, "libivfadc_hip.so")
 SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "train.hip.h"), os.path.join(CSRC, "wave_sort.hip.h"),
            os.path.join(CSRC, "generic.hip.h"), os.path.join(CSRC, "lbscan.hip.h"), os.path.join(CSRC, "nfscan.hip.h"), os.path.join(CSRC, "smallq.hip.h"), os.path.join(CSRC, "twolevel.hip.h"), os.path.join(CSRC, "wg8scan.hip.h"), os.path.join(CSRC, "u16scan.hip.h"), os.path.join(CSRC, "pack_operands.h"),
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
+           os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]
@@ -160,6 +161,14 @@ def lib():
     L.ivfadc_clone_view.argtypes = [vp, C.POINTER(vp)]
     L.ivfadc_clone_subset.argtypes = [vp, u32p, C.c_uint64, C.POINTER(vp), i64p]
     L.ivfadc_clone_subset_device.argtypes = [vp, vp, C.c_uint64, C.POINTER(vp), i64p]
+    L.ivfadc_maskset_create.argtypes = [vp, C.c_int, u32p, C.c_uint64, C.POINTER(vp), i64p]
+    L.ivfadc_maskset_create_device.argtypes = [vp, C.c_int, vp, C.c_uint64, C.POINTER(vp), i64p]
+    L.ivfadc_maskset_destroy.argtypes = [vp]
+    L.ivfadc_maskset_destroy.restype = None
+    L.ivfadc_search_masked.argtypes = [vp, vp, C.c_int64, fp, C.c_int, C.c_int, i32p, u32p, fp, i32p]
+    L.ivfadc_search_device_masked.argtypes = [vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, vp]
+    for name in ("maskset_create", "maskset_create_device", "search_masked", "search_device_masked"):
+        getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_set_list_partition.argtypes = [vp, C.c_int, C.c_int]
     L.ivfadc_search_device_partial.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]
     L.ivfadc_merge_partials_device.argtypes = [vp, C.c_int64, C.c_int, C.c_int, vp, vp, vp, vp, vp]

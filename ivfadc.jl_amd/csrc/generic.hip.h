@@ -6,8 +6,11 @@
 // and the first K are the result (index.jl:225-257: the K smallest under (distance, visit order)).  The coarse top-w
 // is taken the same way: sort the kc keys f32_bits(distance) << 32 | cluster of a row, keep the first w
 // (coarsequantizers.jl:33-37, stable sortperm => ties to the lower cluster id).  Any m, ksub, labels, K and w.
+// A masked search (ivfadc_search_masked; maskset.hip.h) takes the same path: the dump kernels write the key of a point its query's mask
+// rejects as all ones, which sorts behind every real key, and gen_emit_kernel counts such keys out.
 #pragma once
 #include "kernels.hip.h"
+#include "maskset.hip.h"   // MaskView: the masked search takes this path too (mv.words null: no mask set, every point counts)
 
 namespace ivf {
 
@@ -70,7 +73,7 @@ __global__ __launch_bounds__(256) void gen_probes_kernel(const u64 *__restrict__
 __global__ __launch_bounds__(256) void gen_dump_kernel(const IndexView ix, const float *__restrict__ queries, int w,
                                                        const int *__restrict__ probe_list, const float *__restrict__ probe_dc,
                                                        const u32 *__restrict__ probe_base, const u32 *__restrict__ key_off,
-                                                       u64 *__restrict__ keys)
+                                                       u64 *__restrict__ keys, const MaskView mv)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float *resid = (float *)smem_raw;                       // [d]
@@ -99,11 +102,13 @@ __global__ __launch_bounds__(256) void gen_dump_kernel(const IndexView ix, const
     const u32 base = probe_base[(size_t)q * w + j];
     const uint8_t *codes = ix.codes + ix.list_codeoff[l];
     u64 *dst = keys + key_off[q] + base;
+    // masked search: a rejected point's key is all ones -- behind every real key (real keys are finite), counted out by gen_emit_kernel
+    const u32 *mrow = mv.words ? mask_row(mv, q, l) : (const u32 *)nullptr;
     for (u32 p = tid; p < len; p += 256) {
         const uint8_t *cp = codes + (size_t)p * ix.cs;
         float dist = dc;
         for (int ii = 0; ii < ix.m; ++ii) dist = dist + tab[ii * 256 + cp[ii]];
-        dst[p] = ((u64)__float_as_uint(dist) << 32) | (base + p);
+        dst[p] = (mrow && !maskset::slot_selected(mrow, p)) ? (u64)KEY_MAX : (((u64)__float_as_uint(dist) << 32) | (base + p));
     }
 }
 
@@ -115,7 +120,7 @@ constexpr int GEN16_TILE = 8192;
 __global__ __launch_bounds__(256) void gen_dump_u16_kernel(const IndexView ix, const float *__restrict__ queries, int w,
                                                            const int *__restrict__ probe_list, const float *__restrict__ probe_dc,
                                                            const u32 *__restrict__ probe_base, const u32 *__restrict__ key_off,
-                                                           u64 *__restrict__ keys)
+                                                           u64 *__restrict__ keys, const MaskView mv)
 {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
     float *resid = (float *)smem_raw;                       // [d]
@@ -152,7 +157,9 @@ __global__ __launch_bounds__(256) void gen_dump_u16_kernel(const IndexView ix, c
             }
         }
     }
-    for (u32 p = tid; p < len; p += 256) dst[p] = ((u64)(u32)dst[p] << 32) | (base + p);
+    const u32 *mrow = mv.words ? mask_row(mv, q, l) : (const u32 *)nullptr;   // (as gen_dump_kernel)
+    for (u32 p = tid; p < len; p += 256)
+        dst[p] = (mrow && !maskset::slot_selected(mrow, p)) ? (u64)KEY_MAX : (((u64)(u32)dst[p] << 32) | (base + p));
 }
 
 // first K sorted keys of every query -> ids and distances (index.jl:248,252,257)
@@ -165,10 +172,19 @@ __global__ __launch_bounds__(256) void gen_emit_kernel(const u64 *__restrict__ s
     const int q = blockIdx.x;
     const u32 tot = totals[q];
     const int cnt = tot < (u32)K ? (int)tot : K;
+    const u64 *row = sorted + key_off[q];
     for (int i = threadIdx.x; i < cnt; i += 256)
-        emit_result(sorted[key_off[q] + i], i, q, w, K, probe_list + (size_t)q * w, probe_base + (size_t)q * w, list_pos, ids, out_ids,
-                    out_dists);
-    if (threadIdx.x == 0) out_counts[q] = cnt;
+        if (row[i] != KEY_MAX)
+            emit_result(row[i], i, q, w, K, probe_list + (size_t)q * w, probe_base + (size_t)q * w, list_pos, ids, out_ids, out_dists);
+    if (threadIdx.x == 0) {
+        // the keys among the first cnt that are not all ones (a masked search's rejected points; sorted: they stand last)
+        int lo = 0, hi = cnt;
+        while (lo < hi) {
+            const int mid = (lo + hi) >> 1;
+            if (row[mid] != KEY_MAX) lo = mid + 1; else hi = mid;
+        }
+        out_counts[q] = lo;
+    }
 }
 
 }  // namespace ivf

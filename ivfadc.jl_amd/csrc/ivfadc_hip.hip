@@ -12,6 +12,7 @@
 #include "u16scan.hip.h"
 #include "twolevel.hip.h"
 #include "subset.hip.h"
+#include "maskset.hip.h"
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 
@@ -284,6 +285,11 @@ int d2h_copy(void *dst, const void *src, size_t bytes, hipStream_t s)
 // as long as it edits the lists (MutationScope): no view search starts, or is still being enqueued, while the lists change, and the
 // first one afterwards sees the new generation and refuses.
 static std::recursive_mutex g_topo_mu;
+static uint64_t next_handle_serial()
+{
+    static std::atomic<uint64_t> g_serial{0};
+    return g_serial.fetch_add(1, std::memory_order_relaxed) + 1;
+}
 
 // an int that may be read without the handle's lock (make_plan's hint)
 struct RelaxedInt {
@@ -438,6 +444,7 @@ struct Workspace {
     hipEvent_t hint_ev = nullptr;   // ivfadc_search_batches: the hinted rows are on the device once this event has fired (null: they are)
     DevBuf cdist2;
     DevBuf pre_list, pre_dc;   // ivfadc_search_preassigned (host pointers): the caller's probes on the device
+    DevBuf mask_q;             // ivfadc_search_masked: the batch's mask numbers on the device, every value in [-1, nmasks)
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
@@ -447,7 +454,7 @@ struct Workspace {
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
-                          &gen_tmp, &gen_off, &gen_tot, &app_stage, &cdist2, &pre_list, &pre_dc, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &gen_tmp, &gen_off, &gen_tot, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
                           &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
                           &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
             f(*b);
@@ -508,6 +515,10 @@ struct HandleState {
     // change anything; any change to the index it was taken from (generation) makes it refuse to search.
     ivfadc_index *view_of = nullptr;
     bool is_view = false, orphan = false;
+    bool is_subset = false;   // a view with lists of its own (ivfadc_clone_subset): a mask set of the index does not describe them
+    // what a mask set remembers of the index it was made from (ivfadc_maskset_create): a process-wide serial number, not the pointer --
+    // a new index may be allocated at a freed one's address
+    uint64_t serial = next_handle_serial();
     uint64_t generation = 0, view_gen = 0;
     std::vector<ivfadc_index *> views;
     ivfadc_index *pipe_view = nullptr;            // ivfadc_search_batches' second lane (created on first use)
@@ -522,6 +533,17 @@ struct ivfadc_index : Dims, Quantizers, Lists, HostMirror, SearchConfig, Workspa
         Lists::each_buf(f);
         Workspace::each_buf(f);
     }
+};
+
+// A mask set (ivfadc_maskset_create; maskset_plan.h, maskset.hip.h): nmasks slot-space bitmaps of the lists of ONE index as they stood at
+// ONE generation.  Immutable once made: any number of handles and threads search with it at once, nothing here is written again.
+struct ivfadc_maskset {
+    int device = 0;
+    DevBuf words;       // [nmasks][W] u32
+    DevBuf word_off;    // [kc + 1] u64
+    int nmasks = 0, kc = 0;
+    uint64_t W = 0;
+    uint64_t index_serial = 0, generation = 0;   // the index it was made from (HandleState::serial) and that index's generation then
 };
 
 // the lock of an entry point on handle h (null: nothing to lock).  A view takes the topology mutex first and lets it go once its own
@@ -884,6 +906,13 @@ PlanFacts plan_facts(const ivfadc_index *h)
     return f;
 }
 
+// masked_scan_kernel (maskset.hip.h): any m, dsub, ksub <= 256; groups of 1 / 2 / 4, register / LDS selectors
+masked_fn_t pick_masked(int qg, bool small)
+{
+    if (small) return qg == 4 ? masked_scan_kernel<4, true> : (qg == 2 ? masked_scan_kernel<2, true> : masked_scan_kernel<1, true>);
+    return qg == 4 ? masked_scan_kernel<4, false> : (qg == 2 ? masked_scan_kernel<2, false> : masked_scan_kernel<1, false>);
+}
+
 // the kernel of a planned form (Plan::fn)
 int plan_kernel(Plan &pl, int m, int dsub)
 {
@@ -900,6 +929,7 @@ int plan_kernel(Plan &pl, int m, int dsub)
     case ScanForm::U16Wide: pl.fn = (const void *)(u16_fn_t)u16_wide_scan_kernel; break;
     case ScanForm::U16Direct: pl.fn = (const void *)(u16_fn_t)u16_direct_scan_kernel; break;
     case ScanForm::U16DirectWide: pl.fn = (const void *)(u16_fn_t)u16_direct_wide_scan_kernel; break;
+    case ScanForm::Masked: pl.fn = (const void *)pick_masked(pl.qg, pl.small_k); break;
     }
     return IVFADC_OK;
 }
@@ -1311,7 +1341,7 @@ int launch_list_scan(ivfadc_index *h, const Plan &pl, size_t upper, void (*fn)(c
 // list-major scan: work items from the probe histogram (direct: one per (query, probe, chunk), nothing to group), the form's kernel,
 // and the merge of the partial results
 int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-                    bool direct)
+                    bool direct, const MaskView *mv = nullptr)   // mv: the mask rows of a masked search (ScanForm::Masked)
 {
     const int kc = h->kc;
     const size_t np = (size_t)nb * w;
@@ -1377,6 +1407,9 @@ int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
         TRY(launch_list_scan(h, pl, upper, (nf_fn_t)pl.fn, a, nv));
     } else if (pl.form == ScanForm::FourWave) {
         TRY(launch_list_scan(h, pl, upper, (scan_fn_t)pl.fn, a));
+    } else if (pl.form == ScanForm::Masked) {
+        if (!mv) return fail(IVFADC_ERR_STATE, "masked scan planned without a mask set");
+        TRY(launch_list_scan(h, pl, upper, (masked_fn_t)pl.fn, a, *mv));
     } else {
         TRY(launch_list_scan(h, pl, upper, (u16_fn_t)pl.fn, a, pl.qg));
     }
@@ -1394,7 +1427,8 @@ int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
 
 int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids,
                     float *d_dists, int32_t *d_counts, bool single,   // single: the call's whole batch (hints and prefetched rows apply)
-                    const int *pre_list = nullptr, const float *pre_dc = nullptr)   // the caller's probes of these nb queries (ivfadc_search_preassigned)
+                    const int *pre_list = nullptr, const float *pre_dc = nullptr,   // the caller's probes of these nb queries (ivfadc_search_preassigned)
+                    const MaskView *mv = nullptr)                                   // the mask rows and the mask numbers of these nb queries (ivfadc_search_masked)
 {
     const bool qm = pl.query_major();
     const size_t np = (size_t)nb * w;
@@ -1416,7 +1450,7 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
     } else {
         h->stats.last_striped = pl.striped();
         h->stats.last_nf = pl.form == ScanForm::NarrowField ? 1 : 0;
-        TRY(scan_list_major(h, pl, nb, d_q, K, w, d_ids, d_dists, d_counts, direct));
+        TRY(scan_list_major(h, pl, nb, d_q, K, w, d_ids, d_dists, d_counts, direct, mv));
     }
     h->stats.queries += nb;
     if (h->profiling && h->pending.size() > 2048) TRY(ev_fold(h));
@@ -1522,12 +1556,13 @@ int gen_stage_a(ivfadc_index *h, const float *qa, int64_t na, int w, int *d_pl, 
 }
 
 int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-                   const int *pre_list = nullptr, const float *pre_dc = nullptr)   // the caller's probes (ivfadc_search_preassigned): stage A is their ingest
+                   const int *pre_list = nullptr, const float *pre_dc = nullptr,   // the caller's probes (ivfadc_search_preassigned): stage A is their ingest
+                   const MaskView *mv = nullptr)   // a masked search: rejected points leave all-ones keys, which sort last and are counted out
 {
     const int kc = h->kc;
     const size_t lds = (align_up((size_t)h->d, 4) + (h->u16 ? (size_t)GEN16_TILE : (size_t)h->m * 256)) * 4;
     if (lds > LDS_MAX) return fail(IVFADC_ERR_INVALID, "m=%d needs %zu B of LDS in the generic path (> %zu)", h->m, lds, LDS_MAX);
-    void (*dump)(const IndexView, const float *, int, const int *, const float *, const u32 *, const u32 *, u64 *) =
+    void (*dump)(const IndexView, const float *, int, const int *, const float *, const u32 *, const u32 *, u64 *, const MaskView) =
         h->u16 ? gen_dump_u16_kernel : gen_dump_kernel;
     TRY(fn_raise_lds(h->device, (const void *)dump, lds, false));
     TRY(ensure_common_ws(h));
@@ -1577,9 +1612,11 @@ int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, 
             const u32 *pb = h->probe_base.as<u32>() + (size_t)g0 * w;
             for (int64_t y0 = 0; y0 < ng; y0 += 32768) {   // grid.y limit
                 const int64_t ny = std::min<int64_t>(32768, ng - y0);
+                MaskView mq{};   // (words null: no mask set)
+                if (mv) { mq = *mv; mq.mask_of_query = mv->mask_of_query + (a0 + g0 + y0); }
                 hipLaunchKernelGGL(dump, dim3((unsigned)w, (unsigned)ny), dim3(256), lds, h->stream, ix,
                                    qa + (size_t)(g0 + y0) * h->d, w, pl + (size_t)y0 * w, pd + (size_t)y0 * w, pb + (size_t)y0 * w,
-                                   h->gen_off.as<u32>() + y0, h->gen_a.as<u64>());
+                                   h->gen_off.as<u32>() + y0, h->gen_a.as<u64>(), mq);
                 HIP_TRY(hipGetLastError());
             }
             TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), keys, (int)ng, h->gen_off.as<u32>()));
@@ -1864,9 +1901,13 @@ int build_twolevel(ivfadc_index *h)
 // them a search has no coarse stage of its own -- no latency path, no fused top-w, no matrix-core filter, no two-level search, no
 // riders -- and everything behind the probe arrays runs as it does for a plain search.
 struct PreProbes { const int *lists; const float *dcs; };
+// The mask set of a masked search (ivfadc_search_masked) and the batch's mask numbers on the device, every value in [-1, nmasks).  The
+// coarse stage is the plain search's own, in any form; behind it the masked list scan (make_plan_masked) or the masked generic path --
+// no latency path, no fused top-w, no riders.  Together with PreProbes: out of scope (there is no entry for it).
+struct MaskArgs { const ivfadc_maskset *set; const int32_t *mask_of_query; };
 
 int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-               const PreProbes *pre = nullptr)
+               const PreProbes *pre = nullptr, const MaskArgs *mask = nullptr)
 {
     HintScope hint_scope{h};
     // Rows the previous search's riders left serve THIS search or none, whatever path it takes (small-batch, generic, sub-batched, failing):
@@ -1887,6 +1928,28 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
     const bool parted = h->part_n > 1;
     const int *prl = pre ? pre->lists : (const int *)nullptr;
     const float *prd = pre ? pre->dcs : (const float *)nullptr;
+    if (mask) {
+        if (pre || parted) return fail(IVFADC_ERR_STATE, "a masked search takes neither supplied probes nor a list partition");
+        MaskView mv;
+        mv.words = mask->set->words.as<u32>();
+        mv.word_off = mask->set->word_off.as<uint64_t>();
+        mv.W = mask->set->W;
+        mv.mask_of_query = mask->mask_of_query;
+        if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || h->u16)
+            return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, nullptr, nullptr, &mv);
+        TRY(fb_poll(h));
+        Plan pl = make_plan_masked(plan_facts(h), nq, K, w);
+        if (!pl.fits) return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, nullptr, nullptr, &mv);
+        TRY(plan_kernel(pl, h->m, h->dsub));
+        for (int64_t b0 = 0; b0 < nq; b0 += pl.nb) {
+            const int64_t nb = std::min(pl.nb, nq - b0);
+            MaskView mb = mv;
+            mb.mask_of_query = mv.mask_of_query + b0;   // the mask numbers advance with the sub-batch
+            TRY(search_subbatch(h, pl, nb, d_q + (size_t)b0 * h->d, K, w, d_ids + (size_t)b0 * K, d_dists + (size_t)b0 * K, d_counts + b0, false,
+                                nullptr, nullptr, &mb));
+        }
+        return IVFADC_OK;
+    }
     if (!parted && !pre && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
     if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64 && !h->u16_wide)) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
@@ -2599,6 +2662,7 @@ static int clone_subset(ivfadc_index *src, const uint32_t *bits, bool bits_on_de
     TRY(view_source_ready(src, "a subset of a view"));
     std::unique_ptr<ivfadc_index> v(new ivfadc_index());
     view_shell(src, v.get());
+    v->is_subset = true;
     SubsetScratch tmp;
     int rc = fill_subset_lists(src, v.get(), bits, bits_on_device, nbits, tmp);
     if (rc != IVFADC_OK) (void)hipStreamSynchronize(src->stream);   // nothing still reads the scratch
@@ -2652,6 +2716,164 @@ try {
     HandleLock lk_(h);
     TRY(check_subset_args(h, d_bits, nbits, out_view));
     return clone_subset(h, d_bits, true, nbits, out_view, out_n);
+} IVF_CATCH
+
+// ---- mask sets (maskset_plan.h, maskset.hip.h; DESIGN.md "Mask sets") -------------------------------------------------------------
+static int search_enqueue(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists, int32_t *out_counts,
+                          const int32_t *pre_lists, const float *pre_dcs, const MaskArgs *mask);
+static int search_finish(ivfadc_t *h, int64_t nq, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts);
+// the arguments of both creation entries, before the handle is looked at and before any device call
+static int check_maskset_args(ivfadc_t *h, int nmasks, const uint32_t *bits, uint64_t nbits, ivfadc_maskset_t **out)
+{
+    if (!out) return fail(IVFADC_ERR_INVALID, "ivfadc_maskset_create: null out");
+    *out = nullptr;
+    if (nmasks < 1) return fail(IVFADC_ERR_INVALID, "ivfadc_maskset_create: nmasks = %d (at least one mask)", nmasks);
+    if (nbits > ((uint64_t)1 << 32)) return fail(IVFADC_ERR_INVALID, "ivfadc_maskset_create: nbits exceeds 2^32 (ids are UInt32)");
+    if (nbits > 0 && !bits) return fail(IVFADC_ERR_INVALID, "ivfadc_maskset_create: null bitmap with nbits > 0");
+    if (!h) return fail(IVFADC_ERR_INVALID, "ivfadc_maskset_create: null handle");
+    return IVFADC_OK;
+}
+
+// Runs on the index's stream, which is at rest (view_source_ready) and stays the caller's for the whole call (the index's lock is held).
+static int maskset_fill(ivfadc_index *src, ivfadc_maskset *ms, int nmasks, const uint32_t *bits, bool bits_on_device, uint64_t nbits,
+                        int64_t *out_kept, SubsetScratch &tmp)
+{
+    hipStream_t s = src->stream;
+    const maskset::Layout lay = maskset::make_layout(src->h_len);
+    ms->device = src->device;
+    ms->nmasks = nmasks;
+    ms->kc = src->kc;
+    ms->W = lay.W;
+    ms->index_serial = src->serial;
+    ms->generation = src->generation;
+    const size_t nwords = (size_t)nmasks * (size_t)lay.W;
+    TRY(ms->words.alloc_exact(std::max<size_t>(8, nwords * 4)));
+    TRY(ms->word_off.alloc_exact(lay.word_off.size() * 8));
+    TRY(h2d_copy(ms->word_off.p, lay.word_off.data(), lay.word_off.size() * 8, s));
+    const std::vector<subset::Item> items = subset::make_items(src->h_len);
+    std::vector<unsigned long long> kept((size_t)nmasks, 0ull);
+    if (!items.empty()) {
+        const size_t stride = (size_t)((nbits + 31) / 32);
+        const uint32_t *d_bits = bits;
+        if (!bits_on_device && nbits > 0) {
+            TRY(tmp.bits.ensure((size_t)nmasks * stride * 4));
+            TRY(h2d_copy(tmp.bits.p, bits, (size_t)nmasks * stride * 4, s));
+            d_bits = tmp.bits.as<uint32_t>();
+        }
+        TRY(tmp.items.ensure(items.size() * sizeof(subset::Item)));
+        TRY(h2d_copy(tmp.items.p, items.data(), items.size() * sizeof(subset::Item), s));
+        TRY(tmp.counts.ensure((size_t)nmasks * 8));
+        HIP_TRY(hipMemsetAsync(tmp.counts.p, 0, (size_t)nmasks * 8, s));
+        hipLaunchKernelGGL(maskset_build_kernel, dim3((unsigned)items.size()), dim3(256), 0, s, tmp.items.as<subset::Item>(),
+                           src->list_pos.as<int64_t>(), src->list_len.as<u32>(), src->synthetic ? (const u32 *)nullptr : src->ids.as<u32>(), d_bits,
+                           (uint64_t)nbits, (uint64_t)stride, nmasks, ms->word_off.as<uint64_t>(), (uint64_t)lay.W, ms->words.as<uint32_t>(),
+                           out_kept ? tmp.counts.as<unsigned long long>() : (unsigned long long *)nullptr);
+        HIP_TRY(hipGetLastError());
+        if (out_kept) TRY(d2h_copy(kept.data(), tmp.counts.p, (size_t)nmasks * 8, s));
+    }
+    HIP_TRY(hipStreamSynchronize(s));
+    if (out_kept)
+        for (int r = 0; r < nmasks; ++r) out_kept[r] = (int64_t)kept[(size_t)r];
+    return IVFADC_OK;
+}
+
+static int maskset_create(ivfadc_index *src, int nmasks, const uint32_t *bits, bool bits_on_device, uint64_t nbits, ivfadc_maskset_t **out,
+                          int64_t *out_kept)
+{
+    TRY(view_source_ready(src, "a mask set of a view"));
+    std::unique_ptr<ivfadc_maskset> ms(new ivfadc_maskset());
+    SubsetScratch tmp;
+    const int rc = maskset_fill(src, ms.get(), nmasks, bits, bits_on_device, nbits, out_kept, tmp);
+    if (rc != IVFADC_OK) (void)hipStreamSynchronize(src->stream);   // nothing still reads the scratch
+    tmp.release();
+    if (rc != IVFADC_OK) {
+        ms->words.release();
+        ms->word_off.release();
+        return rc;
+    }
+    *out = ms.release();
+    return IVFADC_OK;
+}
+
+int ivfadc_maskset_create(ivfadc_t *h, int nmasks, const uint32_t *bits, uint64_t nbits, ivfadc_maskset_t **out, int64_t *out_kept)
+try {
+    HandleLock lk_(h);
+    TRY(check_maskset_args(h, nmasks, bits, nbits, out));
+    return maskset_create(h, nmasks, bits, false, nbits, out, out_kept);
+} IVF_CATCH
+
+int ivfadc_maskset_create_device(ivfadc_t *h, int nmasks, const uint32_t *d_bits, uint64_t nbits, ivfadc_maskset_t **out, int64_t *out_kept)
+try {
+    HandleLock lk_(h);
+    TRY(check_maskset_args(h, nmasks, d_bits, nbits, out));
+    return maskset_create(h, nmasks, d_bits, true, nbits, out, out_kept);
+} IVF_CATCH
+
+void ivfadc_maskset_destroy(ivfadc_maskset_t *s)
+{
+    if (!s) return;
+    if (hipSetDevice(s->device) == hipSuccess) {
+        s->words.release();
+        s->word_off.release();
+    }
+    delete s;
+}
+
+// h and s of a masked search: h is the index s was made from, unchanged since, or a plain view of it
+static int check_masked_args(ivfadc_index *h, const ivfadc_maskset *s, int64_t nq, int K, int &w)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    if (!s) return fail(IVFADC_ERR_INVALID, "null mask set");
+    TRY(check_search_args(h, nq, K, w));
+    if (h->is_subset) return fail(IVFADC_ERR_STATE, "ivfadc_search_masked: a subset view has lists of its own; search the index the mask set was made from, or a plain view of it");
+    const ivfadc_index *root = h->is_view ? h->view_of : h;   // (check_view_current: the link stands)
+    if (root->serial != s->index_serial) return fail(IVFADC_ERR_STATE, "ivfadc_search_masked: the mask set was made from another index");
+    if (root->generation != s->generation) return fail(IVFADC_ERR_STATE, "ivfadc_search_masked: the index has changed since the mask set was made: make a new one");
+    if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "a list partition is set (ivfadc_set_list_partition): masked searches serve whole indexes only");
+    return IVFADC_OK;
+}
+
+int ivfadc_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, int K, int w,
+                                const int32_t *d_mask_of_query, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
+try {
+    HandleLock lk_(h);
+    TRY(check_masked_args(h, s, nq, K, w));
+    if (nq == 0) return IVFADC_OK;
+    if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
+    TRY(set_device(h));
+    h->dev_entry = false;
+    TRY(h->mask_q.ensure((size_t)nq * 4));
+    hipLaunchKernelGGL(maskset_ingest_kernel, dim3((unsigned)std::min<int64_t>(4096, (nq + 255) / 256)), dim3(256), 0, h->stream, d_mask_of_query,
+                       nq, (int32_t)s->nmasks, h->mask_q.as<int32_t>());
+    HIP_TRY(hipGetLastError());
+    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
+    return search_dev(h, nq, d_queries, K, w, d_out_ids, d_out_dists, d_out_counts, nullptr, &ma);
+} IVF_CATCH
+
+int ivfadc_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *queries, int K, int w, const int32_t *mask_of_query,
+                         uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+try {
+    HandleLock lk_(h);
+    TRY(check_masked_args(h, s, nq, K, w));
+    if (nq == 0) return IVFADC_OK;
+    if (!queries || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
+    if (mask_of_query)   // before any launch
+        for (int64_t q = 0; q < nq; ++q)
+            if (mask_of_query[q] < -1 || mask_of_query[q] >= s->nmasks)
+                return fail(IVFADC_ERR_INVALID, "query %lld: mask %d is outside [-1, %d)", (long long)q, mask_of_query[q], s->nmasks);
+    TRY(set_device(h));
+    TRY(h->mask_q.ensure((size_t)nq * 4));
+    if (mask_of_query) TRY(h2d_copy(h->mask_q.p, mask_of_query, (size_t)nq * 4, h->stream));
+    else HIP_TRY(hipMemsetAsync(h->mask_q.p, 0, (size_t)nq * 4, h->stream));
+    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
+    const int rc = search_enqueue(h, nq, queries, K, w, out_ids, out_dists, out_counts, nullptr, nullptr, &ma);
+    if (rc != IVFADC_OK) {   // whatever was enqueued before the failure ends first
+        const std::string msg = g_err;
+        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+        return rc;
+    }
+    return search_finish(h, nq, K, out_ids, out_dists, out_counts);
 } IVF_CATCH
 
 // a 16-bit handle refuses the uint8_t entries, an 8-bit handle the _u16 ones
@@ -3157,7 +3379,7 @@ static int ingest_rows(ivfadc_index *h, hipStream_t s, const void *src, void *ds
 // host-pointer search in two halves so several handles (devices) can be in flight at once (ivfadc_mg_search)
 // pre_lists / pre_dcs (host, validated by the caller): the probes of ivfadc_search_preassigned
 static int search_enqueue(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists, int32_t *out_counts,
-                          const int32_t *pre_lists = nullptr, const float *pre_dcs = nullptr)
+                          const int32_t *pre_lists = nullptr, const float *pre_dcs = nullptr, const MaskArgs *mask = nullptr)   // mask: ivfadc_search_masked
 try {
     TRY(set_device(h));
     h->dev_entry = false;
@@ -3179,7 +3401,7 @@ try {
     if (h->dirty) TRY(upload_lists(h));
     const float *d_q = src;
     static const bool no_zero_copy = getenv("IVFADC_NO_ZERO_COPY") != nullptr;
-    if (!no_zero_copy && !pre_lists && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, K, w)) {
+    if (!no_zero_copy && !pre_lists && !mask && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, K, w)) {
         // the latency path: a handful of rows, read in place by the two launches (a few KB over PCIe; no ingest step in the chain)
         h->hstats.zero_copy++;
     } else {
@@ -3209,7 +3431,7 @@ try {
         const PreProbes pre{h->pre_list.as<int>(), h->pre_dc.as<float>()};
         TRY(search_dev(h, nq, d_q, K, w, oi, od, oc, &pre));
     } else
-    TRY(search_dev(h, nq, d_q, K, w, oi, od, oc));
+    TRY(search_dev(h, nq, d_q, K, w, oi, od, oc, nullptr, mask));
     h->hstats.stage_in_us += t1 - t0;
     h->hstats.enqueue_us += now_us() - t1;
     return IVFADC_OK;

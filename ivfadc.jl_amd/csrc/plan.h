@@ -43,7 +43,8 @@ struct PlanFacts {
 // stream behind the 4-bit filter (nfscan.hip.h); EightWave wg8scan.hip.h, eight waves per workgroup on four conflict-free copies of
 // the integer filter table (Plan::q8: eight queries per stream; Plan::wide: the wide pool of 64 < K <= 128, the merge behind it is
 // the one of K > 64); U16 / U16Wide u16scan.hip.h on register / LDS selectors, U16Direct / U16DirectWide its table-free entries.
-enum class ScanForm { QueryMajor, QueryMajorLb, FourWave, NarrowField, EightWave, U16, U16Wide, U16Direct, U16DirectWide };
+// Masked: masked_scan_kernel (maskset.hip.h), the list scan of ivfadc_search_masked -- planned by make_plan_masked alone, never by make_plan.
+enum class ScanForm { QueryMajor, QueryMajorLb, FourWave, NarrowField, EightWave, U16, U16Wide, U16Direct, U16DirectWide, Masked };
 
 struct Plan {
     ScanForm form = ScanForm::QueryMajor;
@@ -62,9 +63,10 @@ struct Plan {
     bool fits = true;    // false: the selection kernels' LDS need exceeds the CU's 160 KB -> the caller takes the generic path
     bool query_major() const { return form == ScanForm::QueryMajor || form == ScanForm::QueryMajorLb; }
     // ivfadc_stats.last_striped of a list-major form: 1 striped four-wave tables; 2 / 3 eight-wave, four / eight queries; 4 / 5 its wide pool;
-    // 6 / 7 the table-free UInt16 scan on register / LDS selectors
+    // 6 / 7 the table-free UInt16 scan on register / LDS selectors; 8 the masked scan
     int striped() const
     {
+        if (form == ScanForm::Masked) return 8;
         if (form == ScanForm::U16Direct) return 6;
         if (form == ScanForm::U16DirectWide) return 7;
         return form == ScanForm::EightWave ? (wide ? 4 : 2) + (q8 ? 1 : 0) : (stripe ? 1 : 0);
@@ -319,6 +321,28 @@ inline Plan make_plan(const PlanFacts &f, int64_t nq, int K, int w, bool pre = f
     if (forced) query_major = false;
     pl = query_major ? plan_query_major(f, nq, w, pre, pl) : plan_list_major(f, nq, K, w, avg_len, long_lists, forced, pl);
     return pl.fits ? plan_subbatch(f, nq, K, w, !query_major, pl) : pl;
+}
+
+// The masked search of an 8-bit handle (ivfadc_search_masked; masked_scan_kernel<QG, SMALL> in maskset.hip.h: any m, dsub, ksub <= 256):
+// always list-major -- the mask rows are per list, and the queries that probe a list share its code stream whatever their masks.  Width
+// from the probes-per-list rule of plan_list_major, narrowed until the four-wave layout without stripes fits two workgroups per CU (a
+// forced width yields to the hard limit only); !fits sends the search to the masked generic path.  No latency path, no fused top-w.
+inline Plan make_plan_masked(const PlanFacts &f, int64_t nq, int K, int w)
+{
+    Plan pl = plan_begin(f, nq, K, w, false);
+    pl.form = ScanForm::Masked;
+    const double avg_len = (double)f.n / std::max(1, f.kc);
+    const double ppl = (double)nq * w / std::max(1, f.kc);
+    int qg = ppl >= 2.5 ? 4 : (ppl >= 1.25 ? 2 : 1);
+    const bool forced = f.force_qg == 1 || f.force_qg == 2 || f.force_qg == 4;
+    if (forced) qg = f.force_qg;
+    auto lds_at = [&](int g) { return scan_lds_bytes(f.m, f.d, g, pl.cap, pl.small_k, true, false); };
+    while (qg > 1 && lds_at(qg) > (forced ? LDS_MAX : (size_t)(80 << 10))) qg >>= 1;
+    pl.qg = qg;
+    pl.lds = lds_at(qg);
+    if (pl.lds > LDS_MAX) { pl.fits = false; return pl; }
+    pl = plan_chunks(f, nq, w, avg_len, 4096, 1024, pl);
+    return plan_subbatch(f, nq, K, w, true, pl);
 }
 
 }  // namespace ivf

@@ -224,6 +224,59 @@ class IVFADCIndex:
         v._subset_n = int(kept.value)       # what out_n said; len() asks the handle
         return v
 
+    # ---- per-query filtered search: mask sets (ivfadc_maskset_create, ivfadc_search_masked) ------------------------------------
+    def maskset(self, masks=None, ids=None):
+        """A MaskSet of this index (ivfadc_maskset_create): one bitmap over stored ids per entry of `masks` (boolean arrays indexed
+        by id) or of `ids` (integer arrays of 0-based stored ids), exactly one of the two, each packed by pack_bitmap; nbits is the
+        longest of them.  Made from the index itself (not from a view); any change to the index afterwards makes searches with it
+        refuse.  search_masked_raw / knn_search_masked give every query one of the masks, or -1 for none."""
+        assert (masks is None) != (ids is None), "maskset takes exactly one of masks and ids"
+        src = masks if masks is not None else ids
+        assert len(src) >= 1, "a mask set holds at least one mask"
+        packed = [pack_bitmap(mask=np.asarray(x)) if masks is not None else pack_bitmap(ids=x) for x in src]
+        nbits = max(nb for _, nb in packed)
+        stride = (nbits + 31) // 32
+        bits = np.zeros((len(packed), stride), np.uint32)
+        for r, (words, _) in enumerate(packed):
+            bits[r, :words.shape[0]] = words
+        return self._maskset(nat.lib().ivfadc_maskset_create, nat.ptr(bits, C.c_uint32) if nbits else None, len(packed), nbits)
+
+    def maskset_device(self, d_bits_ptr, nmasks, nbits):
+        """maskset() from bitmaps that already lie in device memory of this index's GPU (ivfadc_maskset_create_device): `d_bits_ptr`
+        is the raw device pointer (int) of nmasks rows of ceil(nbits / 32) uint32 words, complete when the call is made."""
+        return self._maskset(nat.lib().ivfadc_maskset_create_device, C.c_void_p(int(d_bits_ptr)) if nbits else None, int(nmasks), int(nbits))
+
+    def _maskset(self, entry, bits, nmasks, nbits):
+        s = C.c_void_p()
+        kept = np.zeros(max(nmasks, 1), np.int64)
+        nat.check(entry(self._h, int(nmasks), bits, C.c_uint64(nbits), C.byref(s), nat.ptr(kept, C.c_int64)))
+        return MaskSet(s, nmasks, kept[:nmasks], self)
+
+    def search_masked_raw(self, queries, k, maskset, mask_of_query=None, w=1):
+        """search_raw with a mask per query (ivfadc_search_masked): mask_of_query (nq,) int32 in [-1, len(maskset)), -1 = no filter;
+        None = every query uses mask 0."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        nq = q.shape[0]
+        moq = None
+        if mask_of_query is not None:
+            moq = np.ascontiguousarray(mask_of_query, np.int32)
+            assert moq.shape == (nq,), "mask_of_query must be (nq,)"
+        ka = max(int(k), 1)
+        ids = np.zeros((nq, ka), np.uint32)
+        dists = np.full((nq, ka), np.inf, np.float32)
+        counts = np.zeros(nq, np.int32)
+        nat.check(nat.lib().ivfadc_search_masked(self._h, maskset._s, nq, nat.ptr(q, C.c_float), int(k), int(w), nat.ptr(moq, C.c_int32),
+                                                 nat.ptr(ids, C.c_uint32), nat.ptr(dists, C.c_float), nat.ptr(counts, C.c_int32)))
+        return ids, dists, counts
+
+    def search_device_masked(self, maskset, nq, q_ptr, k, w, mask_of_query_ptr, ids_ptr, dists_ptr, counts_ptr):
+        """Asynchronous masked search on raw device pointers (ints); see ivfadc_search_device_masked: mask_of_query_ptr may be 0
+        (every query uses mask 0); out-of-range mask numbers are clamped."""
+        nat.check(nat.lib().ivfadc_search_device_masked(self._h, maskset._s, int(nq), C.c_void_p(q_ptr), int(k), int(w),
+                                                        C.c_void_p(mask_of_query_ptr) if mask_of_query_ptr else None, C.c_void_p(ids_ptr),
+                                                        C.c_void_p(dists_ptr), C.c_void_p(counts_ptr)))
+
     def __del__(self):
         h = getattr(self, "_h", None)
         if h is not None and h.value:
@@ -596,6 +649,30 @@ def comm_unique_id():
     return buf
 
 
+class MaskSet:
+    """nmasks bitmaps over the stored ids of one index, on the device in list order (ivfadc_maskset_t; IVFADCIndex.maskset).  Immutable;
+    len() is the number of masks, `kept` the entries each selects.  Keeps its index alive; the native object goes with this one."""
+
+    def __init__(self, s, nmasks, kept, index):
+        self._s, self._n, self._kept, self._index = s, int(nmasks), np.asarray(kept, np.int64).copy(), index
+
+    @property
+    def kept(self):
+        return self._kept.copy()
+
+    def __len__(self):
+        return self._n
+
+    def __del__(self):
+        s = getattr(self, "_s", None)
+        if s is not None and s.value:
+            try:
+                nat.lib().ivfadc_maskset_destroy(s)
+            except Exception:
+                pass
+            self._s = C.c_void_p()
+
+
 def pack_bitmap(ids=None, mask=None):
     """The bitmap ivfadc_clone_subset takes, from a list of 0-based stored ids or from a boolean mask indexed by id: (uint32 words,
     nbits) with id i at bit (i & 31) of word i >> 5.  nbits is len(mask), or the largest id + 1."""
@@ -688,6 +765,23 @@ def knn_search_preassigned(ivfadc, points, k, clusters, distances):
     assert cl.ndim == 2 and cl.shape[0] == pts.shape[0] and cd.shape == cl.shape, "clusters and distances must both be (nq, w)"
     assert cl.shape[1] >= 1, "Number of clusters to search in must be w >= 1"   # index.jl:211
     ids, dists, counts = ivfadc.search_preassigned_raw(pts, k, cl, cd)
+    out_i = [ids[i, :counts[i]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
+    out_d = [dists[i, :counts[i]].copy() for i in range(pts.shape[0])]
+    if single:
+        return out_i[0], out_d[0]
+    return out_i, out_d
+
+
+def knn_search_masked(ivfadc, points, k, maskset, mask_of_query=None, w=1):
+    """knn_search (index.jl:204-258) with a predicate per query: query q sees only the entries whose stored id mask
+    mask_of_query[q] of `maskset` (IVFADCIndex.maskset) selects -- the lists after deleteat! (utils.jl:98-99) of every other entry --
+    or every entry for -1; None gives every query mask 0.  The probed cells are the unfiltered index's.  Returns what knn_search
+    returns: (ids, dists) for one query (mask_of_query may then be a plain integer), two lists of arrays otherwise."""
+    assert k >= 1, "Number of neighbors must be k >= 1"                          # index.jl:210
+    assert w >= 1, "Number of clusters to search in must be w >= 1"             # index.jl:211
+    pts, single = _as_points(ivfadc, points)
+    moq = None if mask_of_query is None else np.asarray(mask_of_query, np.int32).reshape(-1)
+    ids, dists, counts = ivfadc.search_masked_raw(pts, k, maskset, moq, w)
     out_i = [ids[i, :counts[i]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
     out_d = [dists[i, :counts[i]].copy() for i in range(pts.shape[0])]
     if single:
