@@ -302,10 +302,11 @@ def test_batches_are_independent_and_repeatable(native):
 
 
 @pytest.mark.parametrize("mode", [-1, 1, 4])
-@pytest.mark.parametrize("K", [10, 70])
+@pytest.mark.parametrize("K", [10, 16, 17, 70])
 def test_topk_concentrated_in_one_wave(native, mode, K):
     """Regression: all K best points sit in ONE wave's block of the list (positions 256..), so the workgroup-shared
-    pruning bound equals an entry that another wave must still accept when the four waves' results are merged."""
+    pruning bound equals an entry that another wave must still accept when the four waves' results are merged.
+    K = 16 | 17: both sides of the one-block merge (4 K <= 64)."""
     oidx, _ = helpers.build_index(60, 4096, 32, 2, 8, 256, mode="random")
     rng = np.random.default_rng(60)
     qs = rng.random((6, 32), dtype=np.float32)
