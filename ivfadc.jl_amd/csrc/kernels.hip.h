@@ -163,6 +163,8 @@ template <> struct WSel<true> {
     __device__ __forceinline__ u64 thr() const { return thr_; }
     // an upper bound of this selector's r-th smallest key, r in [1, 64] (KEY_MAX while it holds fewer): see publish_bound
     __device__ __forceinline__ u64 kth(int r) const { return readlane64(top, r - 1); }
+    // uniform: nothing accepted yet
+    __device__ __forceinline__ bool empty() const { return readlane64(top, 0) == KEY_MAX; }
     // adopt a bound found elsewhere (another wave's K-th key is >= the K-th key of the union)
     __device__ __forceinline__ void tighten(u64 t)
     {
@@ -197,7 +199,7 @@ template <> struct WSel<true> {
         const u64 pm = __builtin_amdgcn_ballot_w64(pred);
         u64 mask = __builtin_amdgcn_ballot_w64(key < thr) & pm;
         if (mask == 0) return;
-        if (__popcll(mask) >= 16 && readlane64(top, 0) == KEY_MAX) {   // uniform: selector still empty
+        if (__popcll(mask) >= 16 && empty()) {   // uniform: selector still empty
             seed_from_block(pred && key < thr, key, K, lane);
             return;
         }
@@ -1409,6 +1411,50 @@ static __device__ __forceinline__ void select_row(S &sel, const float *row, int 
                 const int c4 = ((b0 + u) * WPQ + (WPQ == 1 ? 0 : wv)) * 64 + lane;   // float4 index
                 dv[u] = (c4 * 4 < kc) ? row4[c4] : make_float4(0.f, 0.f, 0.f, 0.f);
             }
+            // One wave on the whole row with a register selector (the stand-alone top-w of large batches): the lane's share of the
+            // first 1024 entries is in registers, so the lane MINIMUM is offered first.  In block order the first 64 entries seed the
+            // empty selector (one wave sort) and the rest cost ~K ln(n / 64) serial insertions (kc = 1024, K = 8: 22); the K-th
+            // smallest of 64 lane minima has about K (1 + 1 / 64) of the row's entries below it, K of them in the seed: less than
+            // one insertion is left.  Same result: keys are unique (low word = centroid number, so the lower id still wins a tie;
+            // the minimum by (bits, position in the lane) is the minimum by key, since a lane's centroid numbers ascend with its
+            // position), and what a selector holds is the K smallest of the set it was offered, whatever the order (see
+            // sort_lane_keys).  The minimum is masked out of the second pass by its position: offered twice it would be held twice.
+            if constexpr (!SCORE && WPQ == 1 && std::is_same<S, WSel<true>>::value) {
+                if (b0 == 0) {   // (no shared bound at one wave per query: nothing to adopt or publish)
+                    u32 mb = 0xFFFFFFFFu;
+                    int imin = -1;
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const float de[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
+                        const bool ok = (u * 64 + lane) * 4 < kc;   // (kc % 4 == 0: a float4 is inside the row or outside it)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) {
+                            const bool lt = ok && __float_as_uint(de[e]) < mb;   // strict: the first of equal values stays
+                            mb = lt ? __float_as_uint(de[e]) : mb;
+                            imin = lt ? u * 4 + e : imin;
+                        }
+                    }
+                    const u64 kmin = ((u64)mb << 32) | (u32)((imin >> 2) * 256 + lane * 4 + (imin & 3));
+                    sel.push(imin >= 0 && kmin < sel.thr(), kmin, K, lane);
+#pragma unroll
+                    for (int u = 0; u < 4; ++u) {
+                        const int c = (u * 64 + lane) * 4;
+                        const float de[4] = {dv[u].x, dv[u].y, dv[u].z, dv[u].w};
+                        const u32 th = (u32)(sel.thr() >> 32);
+                        bool anyc = false;
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) anyc = anyc || (c < kc && __float_as_uint(de[e]) <= th && u * 4 + e != imin);
+                        if (__any(anyc)) {
+#pragma unroll
+                            for (int e = 0; e < 4; ++e) {
+                                const u64 key = ((u64)__float_as_uint(de[e]) << 32) | (u32)(c + e);
+                                sel.push(c < kc && key < sel.thr() && u * 4 + e != imin, key, K, lane);
+                            }
+                        }
+                    }
+                    continue;
+                }
+            }
 #pragma unroll
             for (int u = 0; u < 4; ++u) {
                 const int c = (((b0 + u) * WPQ + (WPQ == 1 ? 0 : wv)) * 64 + lane) * 4;
@@ -2274,9 +2320,43 @@ static __device__ __forceinline__ void scan_prefetch(CodeRegs<M, P> &cr, const u
     }
 }
 
+// Offer order of a candidate step (MINFIRST: one query per code stream with a register selector, the query-major scan at PG = 1).
+// A step offers a wave's 64 * PPL points to the selector PPL times, 64 at a time.  An EMPTY selector adopts the K smallest of the
+// first 64 it is offered in one wave sort (WSel<true>::seed_from_block) and takes the rest by serial insertion, ~23 vector and ~18
+// scalar instructions each.  In register order the first offer is an arbitrary quarter of the points: the other three quarters then
+// hold about K ln(PPL) keys below each running K-th key (K = 10, PPL = 4: 14 insertions).  With each lane's keys sorted first -- rank
+// 0 of every lane offered first, then rank 1, ... -- the seed's K-th key is the K-th smallest of 64 lane MINIMA; of 64 PPL uniformly
+// placed points about K (1 + 1 / 64 + ...) lie below it, K of them in the seed: less than one insertion is left (0.5 in the model of
+// tests/test_offer_order_model.py; measured, SIFT1M shape: 7.01 -> 6.49 M vector instructions per launch).  The sort is a
+// five-exchange network on 64-bit keys, paid once per wave and query (only while the selector is empty -- a uniform test; behind a
+// bound that is already tight a step inserts less than once on average and the sort would cost more than it saves).
+// Why nothing else changes:
+//   * keys are unique: the low word is the point's visit-order number sbase + position, different for every point of a query, so
+//     sorting a lane's keys orders them by (sum bits, register index r): point() ascends with r, ties in the sum keep visit order;
+//   * a selector's content after a step depends on the SET it was offered, not on the order: push() only ever rejects a key that is
+//     >= ext_ (a bound from outside) or >= the K-th smallest key it holds, neither of which can be among the K smallest keys below
+//     ext_ of everything offered; what it holds in lanes [0, K) is therefore exactly those, sorted, whichever way they arrived
+//     (seed_from_block and the insertion loop are two routes to the same state);
+//   * thr() = min(K-th key held, ext_) is a function of that content, so publish_bound() at the end of the step publishes the same
+//     value, every wave reads the same sthr[] before its next step, and the round-level pruning test (qscan_body) sees the same
+//     bound: scanned_points / pruned_points and the results are what they were.
+// Invalid points (past the list's end) get KEY_MAX, sort last and never pass key < thr().
+template <int PPL> static __device__ __forceinline__ void sort_lane_keys(u64 (&k)[PPL])
+{
+    static_assert(PPL == 2 || PPL == 4, "points per lane");
+    auto cx = [&](int i, int j) {
+        const bool sw = k[j] < k[i];
+        const u64 lo = sw ? k[j] : k[i], hi = sw ? k[i] : k[j];
+        k[i] = lo;
+        k[j] = hi;
+    };
+    if constexpr (PPL == 2) cx(0, 1);
+    else { cx(0, 1); cx(2, 3); cx(0, 2); cx(1, 3); cx(1, 2); }
+}
+
 // One step of a wave over the STEP = 64 * PPL points whose codes sit in `cr` (positions pb.. of a list of p1 points):
 // ADC sums for the QG queries (tables at absolute LDS offset tab_off), then selection of whatever beats the bounds.
-template <int M, int QG, class S>
+template <int M, int QG, bool MINFIRST = false, class S>
 static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>()> &cr, u32 tab_off, u32 pb, u32 p1,
                                                  const float (&dc)[QG], const u32 (&sbase)[QG], int nvalid, S (&sel)[QG],
                                                  u32 (&thr_hi)[QG], int K, int lane, u64 *sthr)
@@ -2333,10 +2413,27 @@ static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>
         if (__any(anyc)) {
 #pragma unroll
             for (int s = 0; s < QG; ++s) sel[s].tighten(readfirstlane64(sthr[s]));
+            bool ordered = false;
+            if constexpr (MINFIRST && QG == 1 && PPL > 1 && std::is_same<S, WSel<true>>::value) {
+                if (sel[0].empty()) {   // uniform: lane minima first (see sort_lane_keys)
+                    ordered = true;
+                    u64 k[PPL];
+#pragma unroll
+                    for (int r = 0; r < PPL; ++r) {
+                        const u32 p = CR::point(pb, r, lane);
+                        k[r] = (p < p1 && 0 < nvalid) ? make_key(acc[r][0], sbase[0] + p) : KEY_MAX;
+                    }
+                    sort_lane_keys<PPL>(k);
+#pragma unroll
+                    for (int r = 0; r < PPL; ++r) sel[0].push(k[r] < sel[0].thr(), k[r], K, lane);
+                }
+            }
+            if (!ordered) {
 #pragma unroll
             for (int r = 0; r < PPL; ++r) {
                 const u32 p = CR::point(pb, r, lane);
                 scan_emit<QG>(acc[r], p, p < p1, nvalid, sbase, sel, K, lane);
+            }
             }
 #pragma unroll
             for (int s = 0; s < QG; ++s) {
@@ -2349,7 +2446,8 @@ static __device__ __forceinline__ void scan_step(const CodeRegs<M, ppl_of<M, QG>
 // Scan points [p0, p1) of one list for the QG queries whose tables are in `tab`; the four waves
 // of the workgroup interleave blocks of the range.  sbase[s] + position = visit order of query s.
 // `cr` holds the wave's first block (scan_prefetch); later blocks are loaded one step ahead.
-template <int M, int QG, class S>
+// MINFIRST: see sort_lane_keys
+template <int M, int QG, bool MINFIRST = false, class S>
 static __device__ __forceinline__ void scan_range(const float *tab, u32 tab_off, const uint8_t *cbase, int cs, int m, u32 p0, u32 p1,
                                                   const float (&dc)[QG], const u32 (&sbase)[QG], int nvalid, S (&sel)[QG],
                                                   int K, int wv, int lane, CodeRegs<M, ppl_of<M, QG>()> cr, u64 *sthr)
@@ -2371,7 +2469,7 @@ static __device__ __forceinline__ void scan_range(const float *tab, u32 tab_off,
             const u32 pn = pb + 4 * STEP;
             if (pn < p1) nx.load(cbase, pn, lane);
             else nx = cr;
-            scan_step<M, QG>(cr, tab_off, pb, p1, dc, sbase, nvalid, sel, thr_hi, K, lane, sthr);
+            scan_step<M, QG, MINFIRST>(cr, tab_off, pb, p1, dc, sbase, nvalid, sel, thr_hi, K, lane, sthr);
             cr = nx;
         }
     } else {
@@ -3587,7 +3685,7 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
                 if (len[s] == 0) continue;   // uniform
                 const float dc1[1] = {dcv[s]};
                 const u32 sb1[1] = {sb[s]};
-                scan_range<M, 1>(L.tab + (size_t)s * m * 256, (u32)s * (u32)m * 1024u, cb[s], ix.cs, m, 0u, len[s], dc1, sb1, 1, sel, K, wv,
+                scan_range<M, 1, PG == 1>(L.tab + (size_t)s * m * 256, (u32)s * (u32)m * 1024u, cb[s], ix.cs, m, 0u, len[s], dc1, sb1, 1, sel, K, wv,
                                  lane, cr[s], L.sthr);
             }
         }
