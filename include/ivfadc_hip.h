@@ -283,6 +283,48 @@ int ivfadc_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, con
 int ivfadc_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, int K, int w,
                                 const int32_t *d_mask_of_query, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
 
+/* RANGE search: every stored point of the w probed lists within distance r of a query (NearestNeighbors.jl's inrange; other IVF
+ * libraries' range_search).  NO REFERENCE COUNTERPART: IVFADC.jl has knn_search only, so the six entries below are DEFINED through it.
+ * For a query q, a radius r (Float32, in the units of the index's distance: SQUARED Euclidean) and w probes, the result is
+ * knn_search(index, q, K; w) (index.jl:204-258) with K at least the number of points in the w probed lists, cut after the last entry whose
+ * Float32 distance d satisfies d <= r.  Hence: the same w cells (w > kc is clamped as ivfadc_search clamps it), the same sums (d = dc, then
+ * += tab[ii] in ascending ii), the same order (ascending distance, then probe rank, then list position), the same stored ids; ids and
+ * distance bits are those ivfadc_search returns for the same entries.  The comparison is INCLUSIVE: a run of ties at exactly r comes back
+ * whole, in visit order.  r < 0: no results.  r = +inf: every probed point.  A NaN radius: the host entry returns IVFADC_ERR_INVALID naming
+ * the query, before any launch; for the device entry "no NaN" is a precondition, and a NaN radius gives that query no results (d <= NaN is
+ * false).  radii holds one radius per query (a caller with one radius fills the array).
+ *
+ * The result's size is known only after the counting pass, so the result is an object the LIBRARY owns: CSR rows -- lims (nq + 1 int64,
+ * lims[0] = 0), ids and dists (lims[nq] each), query q's entries at [lims[q], lims[q + 1]) -- in device memory of the handle's GPU.
+ * ivfadc_range_result_sizes gives nq and the total, _copy copies to host arrays of those sizes (any of the three may be NULL), _device
+ * lends the device arrays (valid until the result is destroyed).  Both search entries are BLOCKING: the result is complete on return.
+ * A result belongs to no handle: it outlives later searches, mutators and ivfadc_destroy of the handle it came from -- destroying it
+ * after the handle is SAFE -- and is freed only by ivfadc_range_result_destroy (NULL: a no-op).
+ *
+ * max_total > 0 caps the result: when the counted total exceeds it the call returns IVFADC_ERR_INVALID with the needed total in
+ * ivfadc_last_error(), before anything of the result is allocated; *out stays NULL and the handle serves the next call as usual.
+ * max_total = 0: no cap.  IVFADC_ERR_INVALID, before the handle is looked at or the device is touched: NULL out, max_total < 0, nq < 0,
+ * NULL radii, NULL queries with nq > 0, a NaN radius (host entry), NULL h.  w < 1: IVFADC_ERR_ASSERT with the text of index.jl:211.
+ * IVFADC_ERR_STATE: a handle with UInt16 codes (8-bit handles only), a handle with a list partition set, no lists yet, a stale view.
+ * Served: plain handles, ivfadc_clone_view views, subset views, file-loaded handles (:opq included: a search never reads the rotation),
+ * stored ids and device-synthesised lists, indexes after push! / delete.  Batches are sub-batched under ivfadc_set_workspace_limit (queries
+ * are independent: the rows concatenate); the calls run on the handle's stream (ivfadc_set_stream) under the handle's lock; a pending hint
+ * is dropped, as by any search; the probed points count into stats.scanned_points and the queries into stats.queries, and that is ALL a
+ * range search writes into ivfadc_stats: last_qg, last_chunk, last_striped and the other last_* fields go on describing the last
+ * ivfadc_search-family call.  _copy and _destroy leave the calling thread's current device as they found it.  ivfadc_set_tuning's chunk_points, when not 0, is the
+ * points of a work item (rounded up to a multiple of 64); limits: a query's probed points < 2^32, the tables of one probe within the LDS
+ * of a compute unit (csrc/range_plan.h).
+ * Not covered: UInt16 handles, mask sets, the list-partitioned mode, ivfadc_mg_* and the all-gather entries, ivfadc_search_batches.        */
+typedef struct ivfadc_range_result ivfadc_range_result_t;
+int ivfadc_range_search(ivfadc_t *h, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
+                        ivfadc_range_result_t **out);
+int ivfadc_range_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, const float *d_radii, int w, int64_t max_total,
+                               ivfadc_range_result_t **out);
+int ivfadc_range_result_sizes(const ivfadc_range_result_t *r, int64_t *out_nq, int64_t *out_total);
+int ivfadc_range_result_copy(const ivfadc_range_result_t *r, int64_t *lims, uint32_t *ids, float *dists);
+int ivfadc_range_result_device(const ivfadc_range_result_t *r, const int64_t **d_lims, const uint32_t **d_ids, const float **d_dists);
+void ivfadc_range_result_destroy(ivfadc_range_result_t *r);
+
 /* Same, with every buffer already resident in device memory of the handle's GPU.
  * Asynchronous on the handle's stream; pair with ivfadc_sync().                          */
 int ivfadc_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w,

@@ -14,6 +14,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "generic.hip.h"), os.path.join(CSRC, "lbscan.hip.h"), os.path.join(CSRC, "nfscan.hip.h"), os.path.join(CSRC, "smallq.hip.h"), os.path.join(CSRC, "twolevel.hip.h"), os.path.join(CSRC, "wg8scan.hip.h"), os.path.join(CSRC, "u16scan.hip.h"), os.path.join(CSRC, "pack_operands.h"),
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
            os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
+           os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]
@@ -168,6 +169,15 @@ def lib():
     L.ivfadc_search_masked.argtypes = [vp, vp, C.c_int64, fp, C.c_int, C.c_int, i32p, u32p, fp, i32p]
     L.ivfadc_search_device_masked.argtypes = [vp, vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp, vp, vp]
     for name in ("maskset_create", "maskset_create_device", "search_masked", "search_device_masked"):
+        getattr(L, "ivfadc_" + name).restype = C.c_int
+    L.ivfadc_range_search.argtypes = [vp, C.c_int64, fp, fp, C.c_int, C.c_int64, C.POINTER(vp)]
+    L.ivfadc_range_search_device.argtypes = [vp, C.c_int64, vp, vp, C.c_int, C.c_int64, C.POINTER(vp)]
+    L.ivfadc_range_result_sizes.argtypes = [vp, i64p, i64p]
+    L.ivfadc_range_result_copy.argtypes = [vp, i64p, u32p, fp]
+    L.ivfadc_range_result_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
+    L.ivfadc_range_result_destroy.argtypes = [vp]
+    L.ivfadc_range_result_destroy.restype = None
+    for name in ("range_search", "range_search_device", "range_result_sizes", "range_result_copy", "range_result_device"):
         getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_set_list_partition.argtypes = [vp, C.c_int, C.c_int]
     L.ivfadc_search_device_partial.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]

@@ -13,6 +13,7 @@
 #include "twolevel.hip.h"
 #include "subset.hip.h"
 #include "maskset.hip.h"
+#include "range.hip.h"
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 
@@ -429,6 +430,7 @@ struct Workspace {
     bool dev_entry = false;   // the running search came in through a device-pointer entry AND another lane of this replica searched since this
                               // handle's previous search (the caller drives several lanes side by side: see make_plan)
     DevBuf gen_a, gen_b, gen_tmp, gen_off, gen_tot;   // generic path: key buffers (sort in/out), rocPRIM scratch, offsets
+    DevBuf rng_cnt, rng_off, rng_tot, rng_radii, rng_lims;   // range search (range.hip.h): item counts, their scan, per-query totals, the host entry's radii, a group's lims
     int tlist_ldq = 0;
     int tmin_tiles = 0, tmin_tile_w = 0;   // set by run_coarse when the last coarse launch wrote tile minima
     DevBuf app_stage;
@@ -454,7 +456,7 @@ struct Workspace {
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
-                          &gen_tmp, &gen_off, &gen_tot, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
                           &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
                           &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
             f(*b);
@@ -544,6 +546,29 @@ struct ivfadc_maskset {
     int nmasks = 0, kc = 0;
     uint64_t W = 0;
     uint64_t index_serial = 0, generation = 0;   // the index it was made from (HandleState::serial) and that index's generation then
+};
+
+// The result of a range search (ivfadc_range_search; range.hip.h): CSR rows in device memory the RESULT owns -- allocated for it alone, in no
+// ownership group of the handle -- complete when the search returns.  It holds no pointer to the handle: it outlives later searches, the
+// handle's mutators and the handle itself, and goes only by ivfadc_range_result_destroy.
+struct ivfadc_range_result {
+    int device = 0;
+    int64_t nq = 0, total = 0;
+    std::vector<int64_t> lims;     // [nq + 1], the host's copy
+    int64_t *d_lims = nullptr;     // [nq + 1]
+    uint32_t *d_ids = nullptr;     // [max(total, 1)]
+    float *d_dists = nullptr;      // [max(total, 1)]
+    ~ivfadc_range_result()
+    {
+        if (!d_lims && !d_ids && !d_dists) return;
+        int prev = -1;   // the calling thread's current device is the caller's: left as it was
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        if (hipSetDevice(device) != hipSuccess) return;
+        if (d_lims) (void)hipFree(d_lims);
+        if (d_ids) (void)hipFree(d_ids);
+        if (d_dists) (void)hipFree(d_dists);
+        if (prev >= 0 && prev != device) (void)hipSetDevice(prev);
+    }
 };
 
 // the lock of an entry point on handle h (null: nothing to lock).  A view takes the topology mutex first and lets it go once its own
@@ -1970,6 +1995,137 @@ int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint
         TRY(search_subbatch(h, pl, nb, d_q + (size_t)b0 * h->d, K, w, d_ids + (size_t)b0 * K, d_dists + (size_t)b0 * K,
                             d_counts + b0, pl.nb >= nq, pre ? prl + (size_t)b0 * w : prl, pre ? prd + (size_t)b0 * w : prd));
     }
+    return IVFADC_OK;
+}
+
+// ---- range search (range.hip.h; range_plan.h): count, scan, fill, sort the survivors, emit CSR -----------------------------------------
+range_plan::Facts range_facts(const ivfadc_index *h)
+{
+    range_plan::Facts f;
+    f.d = h->d; f.kc = h->kc; f.m = h->m; f.ksub = h->ksub;
+    f.n = 0; f.maxlen = 0;
+    for (int64_t v : h->h_len) { f.n += v; f.maxlen = std::max(f.maxlen, v); }
+    f.force_chunk = h->force_chunk;
+    f.ws_budget = h->ws_budget;
+    f.lds_max = LDS_MAX;
+    return f;
+}
+
+// d_q, d_r: nq queries and their radii in device memory.  Blocking: the result is complete when this returns.
+int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, int w, int64_t max_total, ivfadc_range_result **out)
+{
+    HintScope hint_scope{h};
+    // as any search: rows the previous search's riders left serve the very next search or none, and the probe arrays a pending
+    // ivfadc_merge_partials_device would read are about to be overwritten
+    h->avail_q = nullptr; h->avail_nq = 0;
+    h->pf_q = nullptr; h->pf_nq = 0; h->pf_token = 0; h->cur_token = 0;
+    h->stats.coarse_prefetched = 0;
+    h->stats.last_rider = 0;
+    h->partial_nq = -1;
+    TRY(set_device(h));
+    if (h->dirty) TRY(upload_lists(h));
+    const range_plan::Plan pl = range_plan::make_plan(range_facts(h), nq, w);
+    if (!pl.fits) return fail(IVFADC_ERR_INVALID, "range search (d=%d, m=%d, w=%d): %s", h->d, h->m, w, pl.why);
+    std::unique_ptr<ivfadc_range_result> res(new ivfadc_range_result);
+    res->device = h->device;
+    res->nq = nq;
+    std::vector<uint64_t> tot((size_t)nq, 0);
+    const IndexView ix = index_view(h);
+    if (nq > 0) {
+        TRY(fn_raise_lds(h->device, (const void *)range_count_kernel, pl.lds, true));
+        TRY(fn_raise_lds(h->device, (const void *)range_fill_kernel, pl.lds, true));
+        TRY(ensure_common_ws(h));
+    }
+    const int64_t items = pl.items;
+    // stage A of the generic path (exact coarse distances, sorted rows, the w probes) and the count pass of queries a0 .. a0 + na - 1
+    auto count_batch = [&](int64_t a0, int64_t na, u64 *d_scanned) -> int {
+        const size_t np = (size_t)na * w, ni = (size_t)na * (size_t)items;
+        TRY(h->probe_list.ensure(np * 4));
+        TRY(h->probe_dc.ensure(np * 4));
+        TRY(h->probe_base.ensure(np * 4));
+        TRY(h->gen_tot.ensure((size_t)na * 4));
+        TRY(h->rng_tot.ensure((size_t)na * 4));
+        TRY(h->rng_cnt.ensure(ni * 4));
+        TRY(h->rng_off.ensure(ni * 4));
+        TRY(gen_stage_a(h, d_q + (size_t)a0 * h->d, na, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), d_scanned));
+        RangeArgs a{};
+        a.ix = ix;
+        a.queries = d_q + (size_t)a0 * h->d;
+        a.radii = d_r + a0;
+        a.w = w; a.chunk = pl.chunk; a.maxch = (u32)pl.maxch;
+        a.probe_list = h->probe_list.as<int>(); a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>();
+        a.item_cnt = h->rng_cnt.as<u32>();
+        hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(range_offsets_kernel, dim3((unsigned)na), dim3(256), 0, h->stream, h->rng_cnt.as<u32>(), (u32)items, h->rng_off.as<u32>(),
+                           h->rng_tot.as<u32>());
+        HIP_TRY(hipGetLastError());
+        return IVFADC_OK;
+    };
+    const int64_t nbatches = nq == 0 ? 0 : (nq + pl.nb - 1) / pl.nb;
+    std::vector<u32> tot32, off;
+    for (int64_t a0 = 0; a0 < nq; a0 += pl.nb) {   // pass 1: every query's total, before anything of the result is allocated
+        const int64_t na = std::min(pl.nb, nq - a0);
+        TRY(count_batch(a0, na, h->misc.as<u64>()));
+        tot32.resize((size_t)na);
+        TRY(d2h_copy(tot32.data(), h->rng_tot.p, (size_t)na * 4, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        for (int64_t q = 0; q < na; ++q) tot[(size_t)(a0 + q)] = tot32[(size_t)q];
+    }
+    res->lims = range_plan::make_lims(tot);
+    res->total = res->lims[(size_t)nq];
+    if (max_total > 0 && res->total > max_total)
+        return fail(IVFADC_ERR_INVALID, "the range search holds %lld results, more than max_total = %lld", (long long)res->total, (long long)max_total);
+    HIP_TRY(hipMalloc((void **)&res->d_lims, ((size_t)nq + 1) * 8));
+    HIP_TRY(hipMalloc((void **)&res->d_ids, (size_t)std::max<int64_t>(1, res->total) * 4));
+    HIP_TRY(hipMalloc((void **)&res->d_dists, (size_t)std::max<int64_t>(1, res->total) * 4));
+    TRY(h2d_copy(res->d_lims, res->lims.data(), ((size_t)nq + 1) * 8, h->stream));
+    for (int64_t a0 = 0; a0 < nq && res->total > 0; a0 += pl.nb) {   // pass 2: fill, sort, emit
+        const int64_t na = std::min(pl.nb, nq - a0);
+        // several sub-batches: the probe arrays and item words of this one were overwritten; the same launches give the same words again
+        // (their B_alg counts go to the lines nobody reads: the points were counted in pass 1)
+        if (nbatches > 1) TRY(count_batch(a0, na, (u64 *)((char *)h->misc.p + MISC_SINK)));
+        const std::vector<uint64_t> tb(tot.begin() + a0, tot.begin() + a0 + na);
+        for (int64_t g0 = 0; g0 < na;) {
+            uint64_t keys = 0;
+            const int64_t g1 = range_plan::next_group(tb, g0, pl.cap_keys, &keys);
+            if (g1 == g0) return fail(IVFADC_ERR_INVALID, "a single query holds %llu results: too many for one sort", (unsigned long long)tb[(size_t)g0]);
+            const int64_t ng = g1 - g0;
+            if (keys > 0) {
+                off.resize((size_t)ng + 1);
+                off[0] = 0;
+                for (int64_t q = 0; q < ng; ++q) off[(size_t)q + 1] = off[(size_t)q] + (u32)tb[(size_t)(g0 + q)];
+                TRY(h->gen_a.ensure((size_t)keys * 8));
+                TRY(h->gen_b.ensure((size_t)keys * 8));
+                TRY(h->gen_off.ensure(((size_t)ng + 1) * 4));
+                TRY(h2d_copy(h->gen_off.p, off.data(), ((size_t)ng + 1) * 4, h->stream));
+                RangeArgs a{};
+                a.ix = ix;
+                a.queries = d_q + (size_t)(a0 + g0) * h->d;
+                a.radii = d_r + a0 + g0;
+                a.w = w; a.chunk = pl.chunk; a.maxch = (u32)pl.maxch;
+                a.probe_list = h->probe_list.as<int>() + (size_t)g0 * w;
+                a.probe_dc = h->probe_dc.as<float>() + (size_t)g0 * w;
+                a.probe_base = h->probe_base.as<u32>() + (size_t)g0 * w;
+                a.item_cnt = h->rng_cnt.as<u32>() + (size_t)g0 * (size_t)items;
+                a.item_off = h->rng_off.as<u32>() + (size_t)g0 * (size_t)items;
+                a.key_off = h->gen_off.as<u32>();
+                a.keys = h->gen_a.as<u64>();
+                hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a);
+                HIP_TRY(hipGetLastError());
+                TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), (int64_t)keys, (int)ng, h->gen_off.as<u32>()));
+                const unsigned ey = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)keys / ng + 1023) / 1024));
+                hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)ng, ey), dim3(256), 0, h->stream, h->gen_b.as<u64>(), h->gen_off.as<u32>(), w,
+                                   a.probe_list, a.probe_base, h->list_pos.as<int64_t>(), ix.ids, res->d_lims + a0 + g0, res->d_ids, res->d_dists);
+                HIP_TRY(hipGetLastError());
+                HIP_TRY(hipStreamSynchronize(h->stream));   // `off` and the key buffers are reused by the next group
+            }
+            g0 = g1;
+        }
+    }
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    h->stats.queries += nq;
+    *out = res.release();
     return IVFADC_OK;
 }
 
@@ -3472,6 +3628,101 @@ try {
     }
     return search_finish(h, nq, K, out_ids, out_dists, out_counts);
 } IVF_CATCH
+
+// ---- range search (include/ivfadc_hip.h: "RANGE search"; no reference counterpart) -------------------------------------------------
+// Every argument is judged before the handle is looked at or the device is touched; host_radii (the host entry's) are read for NaN.
+static int check_range_args(ivfadc_index *h, int64_t nq, const float *queries, const float *radii, const float *host_radii, int &w,
+                            int64_t max_total, ivfadc_range_result_t **out)
+{
+    if (!out) return fail(IVFADC_ERR_INVALID, "null out");
+    *out = nullptr;
+    if (max_total < 0) return fail(IVFADC_ERR_INVALID, "max_total < 0 (0: no cap)");
+    if (w < 1) return fail(IVFADC_ERR_ASSERT, "Number of clusters to search in must be w >= 1");
+    if (nq < 0) return fail(IVFADC_ERR_INVALID, "nq < 0");
+    if (!radii) return fail(IVFADC_ERR_INVALID, "null radii (one radius per query)");
+    if (nq > 0 && !queries) return fail(IVFADC_ERR_INVALID, "null queries");
+    if (host_radii)
+        for (int64_t q = 0; q < nq; ++q)
+            if (host_radii[q] != host_radii[q]) return fail(IVFADC_ERR_INVALID, "the radius of query %lld is NaN", (long long)q);
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_view_current(h));
+    if (h->u16) return fail(IVFADC_ERR_STATE, "range search serves handles with 8-bit codes only: this handle holds UInt16 codes");
+    if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "a list partition is set (ivfadc_set_list_partition): range search serves whole indexes only");
+    if (!h->have_lists && !h->dirty) return fail(IVFADC_ERR_STATE, "no inverted lists set");
+    w = std::min(w, h->kc);
+    return IVFADC_OK;
+}
+
+int ivfadc_range_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, const float *d_radii, int w, int64_t max_total,
+                               ivfadc_range_result_t **out)
+try {
+    HandleLock lk_(h);
+    TRY(check_range_args(h, nq, d_queries, d_radii, nullptr, w, max_total, out));
+    const int rc = range_dev(h, nq, d_queries, d_radii, w, max_total, out);
+    if (rc != IVFADC_OK) {   // whatever was enqueued before the failure ends first
+        const std::string msg = g_err;
+        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+    }
+    return rc;
+} IVF_CATCH
+
+int ivfadc_range_search(ivfadc_t *h, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
+                        ivfadc_range_result_t **out)
+try {
+    HandleLock lk_(h);
+    TRY(check_range_args(h, nq, queries, radii, radii, w, max_total, out));
+    TRY(set_device(h));
+    const size_t qbytes = (size_t)nq * h->d * 4;
+    int rc = h->q_stage.ensure(std::max<size_t>(qbytes, 16));
+    if (rc == IVFADC_OK) rc = h->rng_radii.ensure(std::max<size_t>((size_t)nq * 4, 16));
+    if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, (size_t)nq * 4, h->stream);
+    if (rc == IVFADC_OK) rc = range_dev(h, nq, h->q_stage.as<float>(), h->rng_radii.as<float>(), w, max_total, out);
+    if (rc != IVFADC_OK) {
+        const std::string msg = g_err;
+        if (h->stream) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+    }
+    return rc;
+} IVF_CATCH
+
+int ivfadc_range_result_sizes(const ivfadc_range_result_t *r, int64_t *out_nq, int64_t *out_total)
+try {
+    if (!r) return fail(IVFADC_ERR_INVALID, "null result");
+    if (out_nq) *out_nq = r->nq;
+    if (out_total) *out_total = r->total;
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_range_result_copy(const ivfadc_range_result_t *r, int64_t *lims, uint32_t *ids, float *dists)
+try {
+    if (!r) return fail(IVFADC_ERR_INVALID, "null result");
+    if (lims) memcpy(lims, r->lims.data(), r->lims.size() * sizeof(int64_t));
+    if (r->total > 0 && (ids || dists)) {
+        // the calling thread's current device is the caller's: restored on every way out
+        struct DeviceBack { int prev = -1; ~DeviceBack() { if (prev >= 0) (void)hipSetDevice(prev); } } back;
+        if (hipGetDevice(&back.prev) != hipSuccess || back.prev == r->device) back.prev = -1;
+        HIP_TRY(hipSetDevice(r->device));
+        if (ids) HIP_TRY(hipMemcpy(ids, r->d_ids, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+        if (dists) HIP_TRY(hipMemcpy(dists, r->d_dists, (size_t)r->total * 4, hipMemcpyDeviceToHost));
+    }
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_range_result_device(const ivfadc_range_result_t *r, const int64_t **d_lims, const uint32_t **d_ids, const float **d_dists)
+try {
+    if (!r) return fail(IVFADC_ERR_INVALID, "null result");
+    if (d_lims) *d_lims = r->d_lims;
+    if (d_ids) *d_ids = r->d_ids;
+    if (d_dists) *d_dists = r->d_dists;
+    return IVFADC_OK;
+} IVF_CATCH
+
+void ivfadc_range_result_destroy(ivfadc_range_result_t *r)
+{
+    delete r;   // (null: a no-op, as free(NULL); the result holds nothing of the handle it came from)
+}
 
 // ---- the seam of the reference's knn_search (index.jl:204-258): coarse_search on one side, everything that reads its two vectors on
 // the other ("Caller-supplied probes") ----------------------------------------------------------------------------------

@@ -436,6 +436,38 @@ class IVFADCIndex:
                                           nat.ptr(dists, C.c_float), nat.ptr(counts, C.c_int32)))
         return ids, dists, counts
 
+    # ---- range search (no reference counterpart: knn_search cut at the radius, include/ivfadc_hip.h "RANGE search") ------------
+    def range_search_raw(self, queries, radii, w=1, max_total=0):
+        """(nq, d) queries and (nq,) radii (squared distances) -> lims (nq + 1,) int64, ids (total,) uint32, dists (total,) float32 via
+        ivfadc_range_search: query q's entries are [lims[q], lims[q + 1]), in knn_search's order, every one with dist <= radii[q].
+        max_total > 0 caps the total (IVFADCError with the needed total otherwise); 0: no cap."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        r = np.ascontiguousarray(radii, np.float32).reshape(-1)
+        assert r.shape[0] == q.shape[0], "one radius per query"
+        L = nat.lib()
+        res = C.c_void_p()
+        nat.check(L.ivfadc_range_search(self._h, q.shape[0], nat.ptr(q, C.c_float), nat.ptr(r, C.c_float), int(w), int(max_total),
+                                        C.byref(res)))
+        try:
+            nq, total = C.c_int64(), C.c_int64()
+            nat.check(L.ivfadc_range_result_sizes(res, C.byref(nq), C.byref(total)))
+            lims = np.zeros(nq.value + 1, np.int64)
+            ids = np.zeros(total.value, np.uint32)
+            dists = np.zeros(total.value, np.float32)
+            nat.check(L.ivfadc_range_result_copy(res, nat.ptr(lims, C.c_int64), nat.ptr(ids, C.c_uint32), nat.ptr(dists, C.c_float)))
+        finally:
+            L.ivfadc_range_result_destroy(res)
+        return lims, ids, dists
+
+    def range_search_device(self, nq, q_ptr, radii_ptr, w=1, max_total=0):
+        """ivfadc_range_search_device on device pointers: returns the result HANDLE (a c_void_p the caller frees with
+        range_result_destroy; range_result_sizes / _copy / _device read it)."""
+        res = C.c_void_p()
+        nat.check(nat.lib().ivfadc_range_search_device(self._h, int(nq), C.c_void_p(q_ptr), C.c_void_p(radii_ptr), int(w), int(max_total),
+                                                       C.byref(res)))
+        return res
+
     # ---- the seam of knn_search: coarse_search on one side, everything that reads its two vectors on the other ------------
     def coarse_search_raw(self, queries, w):
         """coarse_search(cq, point, w) (coarsequantizers.jl:33-37) for a batch: (nq, d) -> lists (nq, w) int32 (0-based cells,
@@ -784,6 +816,51 @@ def knn_search_masked(ivfadc, points, k, maskset, mask_of_query=None, w=1):
     ids, dists, counts = ivfadc.search_masked_raw(pts, k, maskset, moq, w)
     out_i = [ids[i, :counts[i]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
     out_d = [dists[i, :counts[i]].copy() for i in range(pts.shape[0])]
+    if single:
+        return out_i[0], out_d[0]
+    return out_i, out_d
+
+
+def range_result_sizes(res):
+    """(nq, total) of a range-search result handle"""
+    nq, total = C.c_int64(), C.c_int64()
+    nat.check(nat.lib().ivfadc_range_result_sizes(res, C.byref(nq), C.byref(total)))
+    return nq.value, total.value
+
+
+def range_result_copy(res):
+    """(lims, ids, dists) host arrays of a range-search result handle"""
+    nq, total = range_result_sizes(res)
+    lims, ids, dists = np.zeros(nq + 1, np.int64), np.zeros(total, np.uint32), np.zeros(total, np.float32)
+    nat.check(nat.lib().ivfadc_range_result_copy(res, nat.ptr(lims, C.c_int64), nat.ptr(ids, C.c_uint32), nat.ptr(dists, C.c_float)))
+    return lims, ids, dists
+
+
+def range_result_device(res):
+    """(d_lims, d_ids, d_dists) device addresses of a range-search result handle, valid until it is destroyed"""
+    a, b, c = C.c_void_p(), C.c_void_p(), C.c_void_p()
+    nat.check(nat.lib().ivfadc_range_result_device(res, C.byref(a), C.byref(b), C.byref(c)))
+    return a.value, b.value, c.value
+
+
+def range_result_destroy(res):
+    nat.lib().ivfadc_range_result_destroy(res)
+
+
+def range_search(ivfadc, points, r, w=1):
+    """Every stored point of the w probed lists within distance r of a query: knn_search(ivfadc, point, k; w) (index.jl:204-258) with k at
+    least the number of probed points, cut after the last entry with dist <= r.  NO REFERENCE COUNTERPART (IVFADC.jl has knn_search
+    only; NearestNeighbors.jl calls this inrange).  r is in the units knn_search returns -- SQUARED Euclidean -- and inclusive; a scalar
+    is broadcast over a batch, an array gives one radius per query.  A 1-D `points` is one query and returns (ids[I], dists[float32]),
+    ascending; a 2-D array or a list of vectors returns (list of ids arrays, list of dists arrays)."""
+    assert w >= 1, "Number of clusters to search in must be w >= 1"             # index.jl:211
+    pts, single = _as_points(ivfadc, points)
+    rr = np.asarray(r, np.float32)
+    assert not np.isnan(rr).any(), "the radius must not be NaN"
+    radii = np.ascontiguousarray(np.broadcast_to(rr.reshape(-1) if rr.ndim else rr, (pts.shape[0],)), np.float32)
+    lims, ids, dists = ivfadc.range_search_raw(pts, radii, w)
+    out_i = [ids[lims[i]:lims[i + 1]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
+    out_d = [dists[lims[i]:lims[i + 1]].copy() for i in range(pts.shape[0])]
     if single:
         return out_i[0], out_d[0]
     return out_i, out_d
