@@ -314,7 +314,8 @@ int ivfadc_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t 
  * ivfadc_search-family call.  _copy and _destroy leave the calling thread's current device as they found it.  ivfadc_set_tuning's chunk_points, when not 0, is the
  * points of a work item (rounded up to a multiple of 64); limits: a query's probed points < 2^32, the tables of one probe within the LDS
  * of a compute unit (csrc/range_plan.h).
- * Not covered: UInt16 handles, mask sets, the list-partitioned mode, ivfadc_mg_* and the all-gather entries, ivfadc_search_batches.        */
+ * Not covered by these two entries: UInt16 handles and mask sets (both served by ivfadc_range_search_masked, below).  Not covered at all:
+ * the list-partitioned mode, ivfadc_mg_* and the all-gather entries, ivfadc_search_batches.                                               */
 typedef struct ivfadc_range_result ivfadc_range_result_t;
 int ivfadc_range_search(ivfadc_t *h, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
                         ivfadc_range_result_t **out);
@@ -324,6 +325,32 @@ int ivfadc_range_result_sizes(const ivfadc_range_result_t *r, int64_t *out_nq, i
 int ivfadc_range_result_copy(const ivfadc_range_result_t *r, int64_t *lims, uint32_t *ids, float *dists);
 int ivfadc_range_result_device(const ivfadc_range_result_t *r, const int64_t **d_lims, const uint32_t **d_ids, const float **d_dists);
 void ivfadc_range_result_destroy(ivfadc_range_result_t *r);
+
+/* MASKED range search: "everything within r that this query is allowed to see", and the range search of handles with UInt16 codes.  NO
+ * REFERENCE COUNTERPART.  Query q with mask r = mask_of_query[q] >= 0 of the set s gets what ivfadc_search_masked returns for it with K at
+ * least the number of probed points, cut after the last entry with d <= radii[q]: the w cells, their order and their coarse distances are
+ * those of the UNFILTERED index, the sums are the reference's (d = dc, then += tab_ii[code[ii]] in ascending ii), the order is (distance,
+ * probe rank, stored position) with ORIGINAL visit numbers, ids are the stored ids; ids and distance bits match.  -1 gives what
+ * ivfadc_range_search gives; mask_of_query == NULL with a set means mask 0 for every query.  Everything said above about the radius
+ * (inclusive, r < 0, +inf, NaN, -0), about max_total, the result object (an ordinary ivfadc_range_result_t: _sizes, _copy, _device and
+ * _destroy serve it), blocking, the stream, the lock, the dropped hint and ivfadc_stats (scanned_points -- every probed point once,
+ * selected or not -- and queries; nothing else) holds unchanged.
+ * s == NULL: no query is filtered; mask_of_query must then be NULL (IVFADC_ERR_INVALID otherwise), and the entry is ivfadc_range_search
+ * on every handle state that entry serves PLUS handles with UInt16 codes (256 < k <= 65536): their sums come straight from the codebook
+ * (no tables; csrc/range.hip.h), bit for bit what ivfadc_search returns.
+ * With a set, served: what ivfadc_search_masked serves -- the index the set was made from, unchanged since, or a plain ivfadc_clone_view
+ * view of it; 8-bit and UInt16 handles; file-loaded handles; after push! / delete with a set made after the change.  IVFADC_ERR_STATE: a
+ * subset view together with a set, a set of another index, an index changed since the set was made, a list partition, a stale view.
+ * Argument errors (IVFADC_ERR_INVALID, before the handle is looked at or the device is touched, in this order): NULL out, max_total < 0,
+ * nq < 0, NULL radii, NULL queries with nq > 0, a NaN radius (host entry), NULL h; w < 1 is IVFADC_ERR_ASSERT as above; *out is cleared
+ * on failure.  The host entry validates mask_of_query before any launch (a value outside [-1, nmasks): IVFADC_ERR_INVALID naming the
+ * query); the device entry clamps it into that range.  Limits: csrc/range_plan.h (UInt16: the residual within the LDS of a compute unit;
+ * a work item is 1024 points unless ivfadc_set_tuning's chunk_points says otherwise).
+ * Not covered: the list-partitioned mode, ivfadc_mg_* and the all-gather entries, ivfadc_search_batches, the Julia shim.               */
+int ivfadc_range_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *queries, const float *radii, int w,
+                               int64_t max_total, const int32_t *mask_of_query, ivfadc_range_result_t **out);
+int ivfadc_range_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, const float *d_radii,
+                                      int w, int64_t max_total, const int32_t *d_mask_of_query, ivfadc_range_result_t **out);
 
 /* Same, with every buffer already resident in device memory of the handle's GPU.
  * Asynchronous on the handle's stream; pair with ivfadc_sync().                          */

@@ -177,7 +177,10 @@ def lib():
     L.ivfadc_range_result_device.argtypes = [vp, C.POINTER(vp), C.POINTER(vp), C.POINTER(vp)]
     L.ivfadc_range_result_destroy.argtypes = [vp]
     L.ivfadc_range_result_destroy.restype = None
-    for name in ("range_search", "range_search_device", "range_result_sizes", "range_result_copy", "range_result_device"):
+    L.ivfadc_range_search_masked.argtypes = [vp, vp, C.c_int64, fp, fp, C.c_int, C.c_int64, i32p, C.POINTER(vp)]
+    L.ivfadc_range_search_device_masked.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int64, vp, C.POINTER(vp)]
+    for name in ("range_search", "range_search_device", "range_result_sizes", "range_result_copy", "range_result_device", "range_search_masked",
+                 "range_search_device_masked"):
         getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_set_list_partition.argtypes = [vp, C.c_int, C.c_int]
     L.ivfadc_search_device_partial.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]

@@ -2008,11 +2008,16 @@ range_plan::Facts range_facts(const ivfadc_index *h)
     f.force_chunk = h->force_chunk;
     f.ws_budget = h->ws_budget;
     f.lds_max = LDS_MAX;
+    f.table_free = h->u16;   // 16-bit codes: range_u16_*_kernel, sums straight from the codebook
     return f;
 }
 
 // d_q, d_r: nq queries and their radii in device memory.  Blocking: the result is complete when this returns.
-int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, int w, int64_t max_total, ivfadc_range_result **out)
+// mask (ivfadc_range_search_masked): the set and the batch's mask numbers on the device, every value in [-1, nmasks); null: no query
+// is filtered.  The kernel pair follows (16-bit codes, mask present): range_u16_* for a 16-bit handle with or without a set,
+// range_masked_* for an 8-bit handle with one, the plain pair otherwise.
+int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, int w, int64_t max_total, ivfadc_range_result **out,
+              const MaskArgs *mask = nullptr)
 {
     HintScope hint_scope{h};
     // as any search: rows the previous search's riders left serve the very next search or none, and the probe arrays a pending
@@ -2024,16 +2029,28 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
     h->partial_nq = -1;
     TRY(set_device(h));
     if (h->dirty) TRY(upload_lists(h));
-    const range_plan::Plan pl = range_plan::make_plan(range_facts(h), nq, w);
+    range_plan::Facts facts = range_facts(h);
+    facts.masked = mask != nullptr;
+    const range_plan::Plan pl = range_plan::make_plan(facts, nq, w);
     if (!pl.fits) return fail(IVFADC_ERR_INVALID, "range search (d=%d, m=%d, w=%d): %s", h->d, h->m, w, pl.why);
     std::unique_ptr<ivfadc_range_result> res(new ivfadc_range_result);
     res->device = h->device;
     res->nq = nq;
     std::vector<uint64_t> tot((size_t)nq, 0);
     const IndexView ix = index_view(h);
+    const bool with_mv = h->u16 || mask != nullptr;   // the kernels that take a MaskView
+    const range_masked_fn_t count_mv = h->u16 ? range_u16_count_kernel : range_masked_count_kernel;
+    const range_masked_fn_t fill_mv = h->u16 ? range_u16_fill_kernel : range_masked_fill_kernel;
+    MaskView mv{};   // (words null: no query is filtered)
+    if (mask) {
+        mv.words = mask->set->words.as<u32>();
+        mv.word_off = mask->set->word_off.as<uint64_t>();
+        mv.W = mask->set->W;
+        mv.mask_of_query = mask->mask_of_query;
+    }
     if (nq > 0) {
-        TRY(fn_raise_lds(h->device, (const void *)range_count_kernel, pl.lds, true));
-        TRY(fn_raise_lds(h->device, (const void *)range_fill_kernel, pl.lds, true));
+        TRY(fn_raise_lds(h->device, with_mv ? (const void *)count_mv : (const void *)range_count_kernel, pl.lds, true));
+        TRY(fn_raise_lds(h->device, with_mv ? (const void *)fill_mv : (const void *)range_fill_kernel, pl.lds, true));
         TRY(ensure_common_ws(h));
     }
     const int64_t items = pl.items;
@@ -2055,7 +2072,13 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
         a.w = w; a.chunk = pl.chunk; a.maxch = (u32)pl.maxch;
         a.probe_list = h->probe_list.as<int>(); a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>();
         a.item_cnt = h->rng_cnt.as<u32>();
-        hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a);
+        if (with_mv) {
+            MaskView mb = mv;
+            if (mask) mb.mask_of_query = mv.mask_of_query + a0;   // the mask numbers advance with the sub-batch (pass 1 and the re-run alike)
+            hipLaunchKernelGGL(count_mv, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a, mb);
+        } else {
+            hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a);
+        }
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(range_offsets_kernel, dim3((unsigned)na), dim3(256), 0, h->stream, h->rng_cnt.as<u32>(), (u32)items, h->rng_off.as<u32>(),
                            h->rng_tot.as<u32>());
@@ -2111,7 +2134,13 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
                 a.item_off = h->rng_off.as<u32>() + (size_t)g0 * (size_t)items;
                 a.key_off = h->gen_off.as<u32>();
                 a.keys = h->gen_a.as<u64>();
-                hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a);
+                if (with_mv) {
+                    MaskView mb = mv;
+                    if (mask) mb.mask_of_query = mv.mask_of_query + a0 + g0;   // ... and with the sort group, as the queries and radii do
+                    hipLaunchKernelGGL(fill_mv, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a, mb);
+                } else {
+                    hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a);
+                }
                 HIP_TRY(hipGetLastError());
                 TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), (int64_t)keys, (int)ng, h->gen_off.as<u32>()));
                 const unsigned ey = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)keys / ng + 1023) / 1024));
@@ -3631,8 +3660,10 @@ try {
 
 // ---- range search (include/ivfadc_hip.h: "RANGE search"; no reference counterpart) -------------------------------------------------
 // Every argument is judged before the handle is looked at or the device is touched; host_radii (the host entry's) are read for NaN.
+// masked_entry: the masked entries serve 16-bit handles (range_u16_*_kernel), the plain entries keep refusing them; stray_moq: such an
+// entry was given mask numbers and no set
 static int check_range_args(ivfadc_index *h, int64_t nq, const float *queries, const float *radii, const float *host_radii, int &w,
-                            int64_t max_total, ivfadc_range_result_t **out)
+                            int64_t max_total, ivfadc_range_result_t **out, bool masked_entry = false, bool stray_moq = false)
 {
     if (!out) return fail(IVFADC_ERR_INVALID, "null out");
     *out = nullptr;
@@ -3644,13 +3675,26 @@ static int check_range_args(ivfadc_index *h, int64_t nq, const float *queries, c
     if (host_radii)
         for (int64_t q = 0; q < nq; ++q)
             if (host_radii[q] != host_radii[q]) return fail(IVFADC_ERR_INVALID, "the radius of query %lld is NaN", (long long)q);
+    if (stray_moq) return fail(IVFADC_ERR_INVALID, "ivfadc_range_search_masked: mask_of_query without a mask set (a null set filters no query)");
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
     TRY(check_view_current(h));
-    if (h->u16) return fail(IVFADC_ERR_STATE, "range search serves handles with 8-bit codes only: this handle holds UInt16 codes");
+    if (h->u16 && !masked_entry)
+        return fail(IVFADC_ERR_STATE, "range search serves handles with 8-bit codes only: this handle holds UInt16 codes (ivfadc_range_search_masked with a null set serves them)");
     if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "a list partition is set (ivfadc_set_list_partition): range search serves whole indexes only");
     if (!h->have_lists && !h->dirty) return fail(IVFADC_ERR_STATE, "no inverted lists set");
     w = std::min(w, h->kc);
     return IVFADC_OK;
+}
+
+// the way out of the four range entries once the device has been touched: whatever was enqueued before a failure ends first
+static int range_sync_after_failure(ivfadc_index *h, int rc)
+{
+    if (rc != IVFADC_OK) {
+        const std::string msg = g_err;
+        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+    }
+    return rc;
 }
 
 int ivfadc_range_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, const float *d_radii, int w, int64_t max_total,
@@ -3658,13 +3702,7 @@ int ivfadc_range_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, 
 try {
     HandleLock lk_(h);
     TRY(check_range_args(h, nq, d_queries, d_radii, nullptr, w, max_total, out));
-    const int rc = range_dev(h, nq, d_queries, d_radii, w, max_total, out);
-    if (rc != IVFADC_OK) {   // whatever was enqueued before the failure ends first
-        const std::string msg = g_err;
-        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
-    }
-    return rc;
+    return range_sync_after_failure(h, range_dev(h, nq, d_queries, d_radii, w, max_total, out));
 } IVF_CATCH
 
 int ivfadc_range_search(ivfadc_t *h, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
@@ -3679,12 +3717,66 @@ try {
     if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
     if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, (size_t)nq * 4, h->stream);
     if (rc == IVFADC_OK) rc = range_dev(h, nq, h->q_stage.as<float>(), h->rng_radii.as<float>(), w, max_total, out);
-    if (rc != IVFADC_OK) {
-        const std::string msg = g_err;
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
+    return range_sync_after_failure(h, rc);
+} IVF_CATCH
+
+// h and s of a masked range search: s null (no query is filtered), or h is the index s was made from, unchanged since, or a plain view
+// of it -- check_masked_args's checks under this entry's name.  Behind check_range_args.
+static int check_range_masked_args(ivfadc_index *h, const ivfadc_maskset *s)
+{
+    if (!s) return IVFADC_OK;
+    if (h->is_subset) return fail(IVFADC_ERR_STATE, "ivfadc_range_search_masked: a subset view has lists of its own; search the index the mask set was made from, or a plain view of it");
+    const ivfadc_index *root = h->is_view ? h->view_of : h;   // (check_view_current: the link stands)
+    if (root->serial != s->index_serial) return fail(IVFADC_ERR_STATE, "ivfadc_range_search_masked: the mask set was made from another index");
+    if (root->generation != s->generation) return fail(IVFADC_ERR_STATE, "ivfadc_range_search_masked: the index has changed since the mask set was made: make a new one");
+    return IVFADC_OK;
+}
+
+int ivfadc_range_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, const float *d_radii, int w,
+                                      int64_t max_total, const int32_t *d_mask_of_query, ivfadc_range_result_t **out)
+try {
+    HandleLock lk_(h);
+    TRY(check_range_args(h, nq, d_queries, d_radii, nullptr, w, max_total, out, true, !s && d_mask_of_query));
+    TRY(check_range_masked_args(h, s));
+    if (!s) return range_sync_after_failure(h, range_dev(h, nq, d_queries, d_radii, w, max_total, out));
+    TRY(set_device(h));
+    int rc = h->mask_q.ensure(std::max<size_t>((size_t)nq * 4, 16));
+    if (rc == IVFADC_OK && nq > 0) {   // clamped into [-1, nmasks): a violated precondition cannot read outside the set
+        hipLaunchKernelGGL(maskset_ingest_kernel, dim3((unsigned)std::min<int64_t>(4096, (nq + 255) / 256)), dim3(256), 0, h->stream, d_mask_of_query,
+                           nq, (int32_t)s->nmasks, h->mask_q.as<int32_t>());
+        if (hipGetLastError() != hipSuccess) rc = fail(IVFADC_ERR_HIP, "maskset_ingest_kernel: the launch failed");
     }
-    return rc;
+    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
+    if (rc == IVFADC_OK) rc = range_dev(h, nq, d_queries, d_radii, w, max_total, out, &ma);
+    return range_sync_after_failure(h, rc);
+} IVF_CATCH
+
+int ivfadc_range_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *queries, const float *radii, int w,
+                               int64_t max_total, const int32_t *mask_of_query, ivfadc_range_result_t **out)
+try {
+    HandleLock lk_(h);
+    TRY(check_range_args(h, nq, queries, radii, radii, w, max_total, out, true, !s && mask_of_query));
+    TRY(check_range_masked_args(h, s));
+    if (s && mask_of_query)   // before any launch
+        for (int64_t q = 0; q < nq; ++q)
+            if (mask_of_query[q] < -1 || mask_of_query[q] >= s->nmasks)
+                return fail(IVFADC_ERR_INVALID, "query %lld: mask %d is outside [-1, %d)", (long long)q, mask_of_query[q], s->nmasks);
+    TRY(set_device(h));
+    const size_t qbytes = (size_t)nq * h->d * 4;
+    int rc = h->q_stage.ensure(std::max<size_t>(qbytes, 16));
+    if (rc == IVFADC_OK) rc = h->rng_radii.ensure(std::max<size_t>((size_t)nq * 4, 16));
+    if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, (size_t)nq * 4, h->stream);
+    if (rc == IVFADC_OK && s) {
+        rc = h->mask_q.ensure(std::max<size_t>((size_t)nq * 4, 16));
+        if (rc == IVFADC_OK && nq > 0) {
+            if (mask_of_query) rc = h2d_copy(h->mask_q.p, mask_of_query, (size_t)nq * 4, h->stream);
+            else if (hipMemsetAsync(h->mask_q.p, 0, (size_t)nq * 4, h->stream) != hipSuccess) rc = fail(IVFADC_ERR_HIP, "hipMemsetAsync failed");
+        }
+    }
+    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
+    if (rc == IVFADC_OK) rc = range_dev(h, nq, h->q_stage.as<float>(), h->rng_radii.as<float>(), w, max_total, out, s ? &ma : nullptr);
+    return range_sync_after_failure(h, rc);
 } IVF_CATCH
 
 int ivfadc_range_result_sizes(const ivfadc_range_result_t *r, int64_t *out_nq, int64_t *out_total)

@@ -9,6 +9,12 @@
 // LONGEST list: item j * maxch + c covers positions [c * chunk, min(len, (c + 1) * chunk)) of probe j's list and is empty where that
 // range is.  Two passes over the same grid: the count pass leaves one u32 per item, an exclusive scan of a query's items gives every
 // item its slot range among the query's keys, the fill pass writes the keys there.
+//
+// INVARIANT (masked items, range.hip.h): a chunk is a multiple of 64 points -- the default chunks are multiples of CHUNK_ALIGN = 256, the
+// table-free default is TABLE_FREE_CHUNK = 1024, a forced chunk is rounded up to FORCED_ALIGN = 64 -- so chunk_begin(c, chunk) is a
+// multiple of 64 for every c, and the 64 points a wave takes in a round of THREADS = 256 (positions chunk_begin + 256 k + 64 wave ...)
+// are exactly one round of a mask row (maskset_plan.h: maskset::round_word, two whole words).  chunk_is_round_aligned states it;
+// tests/c/range_masked_plan_check.cpp checks it and the word addressing of every item of every list.
 #pragma once
 
 #include <cstddef>
@@ -34,7 +40,18 @@ RANGE_HD uint64_t round_up(uint64_t v, uint64_t a) { return (v + a - 1) / a * a;
 // LDS of a work item: residual (d floats, padded to 4), m tables of 256 floats, the counter
 RANGE_HD size_t lds_bytes(int d, int m) { return ((size_t)round_up((uint64_t)d, 4) + (size_t)m * 256) * 4 + COUNTER_BYTES; }
 
-// Chunk length when none is forced.  A work item builds its probe's tables (ksub * d multiply-adds: m tables of ksub entries of dsub
+// Table-free items (16-bit codes, range_u16_*_kernel): no tables.  The residual lies in LDS as [m][dsp], dsp = dsub rounded up to 4 so
+// that one 16-byte broadcast read serves four terms, and the counter behind it.
+RANGE_HD size_t lds_bytes_table_free(int m, int dsub) { return (size_t)m * (size_t)round_up((uint64_t)(dsub > 0 ? dsub : 1), 4) * 4 + COUNTER_BYTES; }
+// Their default chunk: the 8 * ksub * d / m rule below prices a table build that does not exist here.  A table-free item pays only its
+// residual (d subtractions) and its launch slot, so the chunk is short: four rounds of 256 points keep the residual's cost below a
+// thousandth of the gathers and give a 100 000-point list about a hundred items to spread over the compute units.
+// REASONED, NOT MEASURED: no sweep of this constant has been run; ivfadc_set_tuning(h, qg, chunk_points) overrides it.
+constexpr uint32_t TABLE_FREE_CHUNK = 1024;
+
+RANGE_HD bool chunk_is_round_aligned(uint32_t chunk) { return chunk != 0 && chunk % 64u == 0; }
+
+// Chunk length when none is forced (table form).  A work item builds its probe's tables (ksub * d multiply-adds: m tables of ksub entries of dsub
 // terms) before it looks anything up (chunk * m lookups): the chunk is long enough that the build costs at most about an eighth of the
 // lookups -- chunk >= 8 * ksub * d / m -- rounded up to a multiple of 256.  REASONED, NOT MEASURED: no sweep of this constant has been
 // run; ivfadc_set_tuning(h, qg, chunk_points) overrides it.
@@ -80,6 +97,8 @@ struct Facts {
     int force_chunk = 0;             // ivfadc_set_tuning's chunk_points (0: the default)
     size_t ws_budget = 0;            // ivfadc_set_workspace_limit
     size_t lds_max = 0;              // LDS of a CU a workgroup may take (scan_layouts.h: LDS_MAX)
+    bool table_free = false;         // 16-bit codes: sums straight from the codebook, LDS from the residual alone (d = m * dsub)
+    bool masked = false;             // ivfadc_range_search_masked with a set: a query's share grows by its ingested mask number
 };
 
 struct Plan {
@@ -100,18 +119,18 @@ constexpr int64_t MAX_GRID_X = ((int64_t)1 << 32) / THREADS - 1, MAX_GRID_Y = 65
 inline Plan make_plan(const Facts &f, int64_t nq, int w)
 {
     Plan p;
-    p.lds = lds_bytes(f.d, f.m);
-    if (p.lds > f.lds_max) { p.why = "the tables of one probe exceed the LDS of a compute unit"; return p; }
+    p.lds = f.table_free ? lds_bytes_table_free(f.m, f.m > 0 ? f.d / f.m : f.d) : lds_bytes(f.d, f.m);
+    if (p.lds > f.lds_max) { p.why = f.table_free ? "the residual exceeds the LDS of a compute unit" : "the tables of one probe exceed the LDS of a compute unit"; return p; }
     // a query's visit orders count its probed points: fewer than 2^32 when the index holds fewer (the generic path's limit)
     if ((uint64_t)f.n >= VISIT_LIMIT) { p.why = "a query may probe 2^32 points or more: visit orders are 32-bit"; return p; }
-    p.chunk = f.force_chunk > 0 ? forced_chunk(f.force_chunk) : default_chunk(f.d, f.m, f.ksub);
+    p.chunk = f.force_chunk > 0 ? forced_chunk(f.force_chunk) : (f.table_free ? TABLE_FREE_CHUNK : default_chunk(f.d, f.m, f.ksub));
     p.maxch = (int64_t)chunks_of((uint64_t)(f.maxlen > 0 ? f.maxlen : 0), p.chunk);
     if (p.maxch < 1) p.maxch = 1;
     p.items = (int64_t)w * p.maxch;
     if (p.items > MAX_GRID_X) { p.why = "w x chunks of the longest list exceeds a launch grid: force a longer chunk"; return p; }
     // a query's share of the workspace: coarse row and its keys twice over (4 + 16), probe arrays (12), item counts and offsets (8 an
-    // item), total and key offset
-    p.per_query_bytes = (int64_t)f.kc * 20 + (int64_t)w * 12 + p.items * 8 + 64;
+    // item), total and key offset; masked: the ingested mask number (4)
+    p.per_query_bytes = (int64_t)f.kc * 20 + (int64_t)w * 12 + p.items * 8 + 64 + (f.masked ? 4 : 0);
     int64_t nb = (int64_t)(f.ws_budget / (size_t)p.per_query_bytes);
     if (nb < 1) nb = 1;
     const int64_t by_rows = (((int64_t)1 << 31) - 1) / (f.kc > 0 ? f.kc : 1);   // the coarse rows of a sub-batch are sorted in one call: fewer than 2^31 keys

@@ -468,6 +468,36 @@ class IVFADCIndex:
                                                        C.byref(res)))
         return res
 
+    def range_search_masked_raw(self, queries, radii, maskset=None, mask_of_query=None, w=1, max_total=0):
+        """range_search_raw with a mask per query (ivfadc_range_search_masked): mask_of_query (nq,) int32 in [-1, len(maskset)), -1 = no
+        filter; None with a set = every query uses mask 0.  maskset=None: no query is filtered (mask_of_query must then be None) -- the
+        way to a range search on an index with UInt16 codes.  Returns (lims, ids, dists) as range_search_raw does."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        r = np.ascontiguousarray(radii, np.float32).reshape(-1)
+        assert r.shape[0] == q.shape[0], "one radius per query"
+        moq = None
+        if mask_of_query is not None:
+            moq = np.ascontiguousarray(mask_of_query, np.int32)
+            assert moq.shape == (q.shape[0],), "mask_of_query must be (nq,)"
+        L = nat.lib()
+        res = C.c_void_p()
+        nat.check(L.ivfadc_range_search_masked(self._h, maskset._s if maskset is not None else None, q.shape[0], nat.ptr(q, C.c_float),
+                                               nat.ptr(r, C.c_float), int(w), int(max_total), nat.ptr(moq, C.c_int32), C.byref(res)))
+        try:
+            return range_result_copy(res)
+        finally:
+            L.ivfadc_range_result_destroy(res)
+
+    def range_search_device_masked(self, nq, q_ptr, radii_ptr, maskset=None, mask_of_query_ptr=0, w=1, max_total=0):
+        """ivfadc_range_search_device_masked on device pointers (ints): returns the result HANDLE, as range_search_device does.
+        mask_of_query_ptr may be 0 (with a set: every query uses mask 0); out-of-range mask numbers are clamped."""
+        res = C.c_void_p()
+        nat.check(nat.lib().ivfadc_range_search_device_masked(self._h, maskset._s if maskset is not None else None, int(nq), C.c_void_p(q_ptr),
+                                                              C.c_void_p(radii_ptr), int(w), int(max_total),
+                                                              C.c_void_p(mask_of_query_ptr) if mask_of_query_ptr else None, C.byref(res)))
+        return res
+
     # ---- the seam of knn_search: coarse_search on one side, everything that reads its two vectors on the other ------------
     def coarse_search_raw(self, queries, w):
         """coarse_search(cq, point, w) (coarsequantizers.jl:33-37) for a batch: (nq, d) -> lists (nq, w) int32 (0-based cells,
@@ -859,6 +889,26 @@ def range_search(ivfadc, points, r, w=1):
     assert not np.isnan(rr).any(), "the radius must not be NaN"
     radii = np.ascontiguousarray(np.broadcast_to(rr.reshape(-1) if rr.ndim else rr, (pts.shape[0],)), np.float32)
     lims, ids, dists = ivfadc.range_search_raw(pts, radii, w)
+    out_i = [ids[lims[i]:lims[i + 1]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
+    out_d = [dists[lims[i]:lims[i + 1]].copy() for i in range(pts.shape[0])]
+    if single:
+        return out_i[0], out_d[0]
+    return out_i, out_d
+
+
+def range_search_masked(ivfadc, points, r, maskset=None, mask_of_query=None, w=1):
+    """range_search with a predicate per query: query q sees only the entries whose stored id mask mask_of_query[q] of `maskset`
+    (IVFADCIndex.maskset) selects, or every entry for -1; None with a set gives every query mask 0.  The probed cells are the unfiltered
+    index's.  maskset=None filters nothing (mask_of_query must then be None) and serves indexes with UInt16 codes, which range_search
+    refuses.  NO REFERENCE COUNTERPART.  Returns what range_search returns (mask_of_query may be a plain integer for one query)."""
+    assert w >= 1, "Number of clusters to search in must be w >= 1"             # index.jl:211
+    pts, single = _as_points(ivfadc, points)
+    rr = np.asarray(r, np.float32)
+    assert not np.isnan(rr).any(), "the radius must not be NaN"
+    assert maskset is not None or mask_of_query is None, "mask_of_query needs a maskset"
+    radii = np.ascontiguousarray(np.broadcast_to(rr.reshape(-1) if rr.ndim else rr, (pts.shape[0],)), np.float32)
+    moq = None if mask_of_query is None else np.asarray(mask_of_query, np.int32).reshape(-1)
+    lims, ids, dists = ivfadc.range_search_masked_raw(pts, radii, maskset, moq, w)
     out_i = [ids[lims[i]:lims[i + 1]].astype(ivfadc.index_type) for i in range(pts.shape[0])]
     out_d = [dists[lims[i]:lims[i + 1]].copy() for i in range(pts.shape[0])]
     if single:
