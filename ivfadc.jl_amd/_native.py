@@ -14,7 +14,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "generic.hip.h"), os.path.join(CSRC, "lbscan.hip.h"), os.path.join(CSRC, "nfscan.hip.h"), os.path.join(CSRC, "smallq.hip.h"), os.path.join(CSRC, "twolevel.hip.h"), os.path.join(CSRC, "wg8scan.hip.h"), os.path.join(CSRC, "u16scan.hip.h"), os.path.join(CSRC, "pack_operands.h"),
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
            os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
-           os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"),
+           os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]

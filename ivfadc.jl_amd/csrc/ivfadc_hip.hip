@@ -16,6 +16,7 @@
 #include "range.hip.h"
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
+#include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
 
 #include <algorithm>
 #include <atomic>
@@ -1239,20 +1240,22 @@ LbView lb_view(const ivfadc_index *h)
 // coarse_search -- the coarse stage and the top-w selection are one ingest launch), the two-level search's, or the coarse rows -- computed
 // here, or standing already (written by the previous search's launch behind a hint: ivfadc_set_next_queries) -- and, unless the scan
 // fuses it, the stand-alone top-w.  lc: the probe histogram (grouped list-major only)
-int probe_stage(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int w, bool single, u32 *lc, const int *pre_list, const float *pre_dc)
+int probe_stage(ivfadc_index *h, const Plan &pl, const SearchCall &c, u32 *lc)
 {
-    const bool pre = pre_list != nullptr;
+    const bool pre = c.pre();
+    const int64_t nb = c.nq; const float *d_q = c.q; const int w = c.w;
     u64 *d_scanned = h->misc.as<u64>();          // 64 sharded counters
     // one wave per query leaves the chip empty on small batches: the stand-alone top-w uses a workgroup per query there
     const bool wpq4 = !pl.lanes && nb * 1 < (int64_t)8 * h->num_cu * 4 && h->kc >= 512 && !(pl.form == ScanForm::QueryMajorLb && !pl.fuse_topw);
-    const bool have_rows = single && !pre && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
+    // (a masked search takes no prefetched rows: its sub-batches never counted as the whole batch)
+    const bool have_rows = c.whole_batch && !pre && !c.masked() && !pl.coarse_mfma && !pl.twolevel && h->avail_q == d_q && h->avail_nq == nb && h->cdist2.p != nullptr;
     h->avail_q = nullptr;
     if (pre || pl.twolevel || have_rows) {
         h->tmin_tiles = 0;
         h->last_listed = false;
     }
     if (pre) {
-        hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, pre_list, pre_dc, (int)nb, h->kc, w,
+        hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, c.pre_list, c.pre_dc, (int)nb, h->kc, w,
                            h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), lc, (u32 *)nullptr,
                            d_scanned);
         HIP_TRY(hipGetLastError());
@@ -1276,18 +1279,18 @@ int probe_stage(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, i
     return IVFADC_OK;
 }
 
-// query-major scan: a workgroup per query; single / pre: as search_subbatch's
-int scan_query_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-                     bool single, bool pre)
+// query-major scan: a workgroup per query
+int scan_query_major(ivfadc_index *h, const Plan &pl, const SearchCall &c)
 {
-    const int kc = h->kc;
+    const int kc = h->kc, K = c.K, w = c.w;
+    const int64_t nb = c.nq; const float *d_q = c.q; const bool pre = c.pre();
     const bool lb = pl.form == ScanForm::QueryMajorLb;
     QScanArgs a;
     a.ix = index_view(h);
     a.queries = d_q;
     a.nq = (int)nb; a.w = w; a.K = K; a.cap = pl.cap;
     a.probe_list = h->probe_list.as<int>(); a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>();
-    a.out_ids = d_ids; a.out_dists = d_dists; a.out_counts = d_counts;
+    a.out_ids = c.ids; a.out_dists = c.dists; a.out_counts = c.counts;
     a.cdist = pl.fuse_topw ? h->cdist.as<float>() : (const float *)nullptr;
     a.scanned_points = h->misc.as<u64>();
     a.approx = pl.coarse_mfma ? 1 : 0;
@@ -1298,7 +1301,7 @@ int scan_query_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d
     TRY(fn_occupancy(h, pl.fn, pl.lds, occ));
     ivfadc_index::EvPair ep;
     // riders: the hinted batch will take the exact small-problem coarse kernel whatever its K and w (no matrix-core filter at this kc)
-    const bool ride = single && !pre && !h->tl_use && h->hint_q != nullptr && h->hint_nq > 0 && !lb && pl.small_k && (h->d & 7) == 0 &&
+    const bool ride = c.whole_batch && !pre && !h->tl_use && h->hint_q != nullptr && h->hint_nq > 0 && !lb && pl.small_k && (h->d & 7) == 0 &&
                       (!h->allow_mfma || kc < h->mfma_min_kc) && (h->hint_nq + 4 * RIDER_QW - 1) / (4 * RIDER_QW) <= 65535 &&
                       (size_t)h->hint_nq * kc * 4 <= h->ws_budget / 4;
     // a hinted next batch (ivfadc_set_next_queries): its exact coarse tiles ride behind this batch's scan in the same grid
@@ -1365,10 +1368,10 @@ int launch_list_scan(ivfadc_index *h, const Plan &pl, size_t upper, void (*fn)(c
 
 // list-major scan: work items from the probe histogram (direct: one per (query, probe, chunk), nothing to group), the form's kernel,
 // and the merge of the partial results
-int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-                    bool direct, const MaskView *mv = nullptr)   // mv: the mask rows of a masked search (ScanForm::Masked)
+int scan_list_major(ivfadc_index *h, const Plan &pl, const SearchCall &c, bool direct)
 {
-    const int kc = h->kc;
+    const int kc = h->kc, K = c.K, w = c.w;
+    const int64_t nb = c.nq;
     const size_t np = (size_t)nb * w;
     const bool w8 = pl.form == ScanForm::EightWave;
     u32 *d_qhead = (u32 *)((char *)h->misc.p + 4096);
@@ -1403,7 +1406,7 @@ int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
 
     ScanArgs a;
     a.ix = index_view(h);
-    a.queries = d_q;
+    a.queries = c.q;
     a.w = w; a.K = K; a.cap = pl.cap;
     a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>(); a.list_cnt = h->list_cnt.as<u32>();
     a.bucket_off = h->bucket_off.as<u32>(); a.wi_off = h->wi_off.as<u32>(); a.bucket_items = h->bucket_items.as<u32>();
@@ -1433,8 +1436,8 @@ int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
     } else if (pl.form == ScanForm::FourWave) {
         TRY(launch_list_scan(h, pl, upper, (scan_fn_t)pl.fn, a));
     } else if (pl.form == ScanForm::Masked) {
-        if (!mv) return fail(IVFADC_ERR_STATE, "masked scan planned without a mask set");
-        TRY(launch_list_scan(h, pl, upper, (masked_fn_t)pl.fn, a, *mv));
+        if (!c.masked()) return fail(IVFADC_ERR_STATE, "masked scan planned without a mask set");
+        TRY(launch_list_scan(h, pl, upper, (masked_fn_t)pl.fn, a, mask_view(c)));
     } else {
         TRY(launch_list_scan(h, pl, upper, (u16_fn_t)pl.fn, a, pl.qg));
     }
@@ -1444,19 +1447,18 @@ int scan_list_major(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
     if (mlds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)mk, mlds, occ_unused, false)); }
     hipLaunchKernelGGL(mk, dim3((unsigned)((nb + 3) / 4)), dim3(256), mlds, h->stream, (int)nb, w, K, pl.cap, pl.maxch, pl.CH, kc,
                        h->probe_list.as<int>(), h->probe_base.as<u32>(), h->list_pos.as<int64_t>(), h->list_len.as<u32>(),
-                       h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>(), h->part_keys.as<u64>(), h->part_cnt.as<u32>(), d_ids, d_dists,
-                       d_counts, h->qthr.as<u64>(), h->list_cnt.as<u32>(), d_qhead, h->part_n, h->part_i, (u64 *)h->partial_keys);
+                       h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>(), h->part_keys.as<u64>(), h->part_cnt.as<u32>(), c.ids, c.dists,
+                       c.counts, h->qthr.as<u64>(), h->list_cnt.as<u32>(), d_qhead, h->part_n, h->part_i, (u64 *)h->partial_keys);
     HIP_TRY(hipGetLastError());
     return IVFADC_OK;
 }
 
-int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_q, int K, int w, uint32_t *d_ids,
-                    float *d_dists, int32_t *d_counts, bool single,   // single: the call's whole batch (hints and prefetched rows apply)
-                    const int *pre_list = nullptr, const float *pre_dc = nullptr,   // the caller's probes of these nb queries (ivfadc_search_preassigned)
-                    const MaskView *mv = nullptr)                                   // the mask rows and the mask numbers of these nb queries (ivfadc_search_masked)
+// c: one sub-batch of the plan (c.whole_batch: the call's whole batch, to which hints and prefetched rows apply)
+int search_subbatch(ivfadc_index *h, const Plan &pl, const SearchCall &c)
 {
     const bool qm = pl.query_major();
-    const size_t np = (size_t)nb * w;
+    const int64_t nb = c.nq;
+    const size_t np = (size_t)nb * c.w;
     TRY(ensure_common_ws(h));
     TRY(h->probe_list.ensure(np * 4));
     TRY(h->probe_dc.ensure(np * 4));
@@ -1464,18 +1466,18 @@ int search_subbatch(ivfadc_index *h, const Plan &pl, int64_t nb, const float *d_
     // list-major with one query per code stream: every (query, probe) pair is a work item of its own, nothing to group
     // by list -- no probe histogram, no bucket kernels
     const bool direct = !qm && pl.qg == 1 && np * (size_t)pl.maxch < ((size_t)1 << 31) && h->part_n <= 1;
-    TRY(probe_stage(h, pl, nb, d_q, w, single, (qm || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>(), pre_list, pre_dc));
+    TRY(probe_stage(h, pl, c, (qm || direct) ? (u32 *)nullptr : h->list_cnt.as<u32>()));
     // what the plan runs (last_lb: of the latest query-major scan; last_striped, last_nf: of the latest list-major one)
     h->stats.last_qg = qm ? 0 : pl.qg;
     h->stats.last_chunk = (int)pl.CH;
     h->stats.last_scan_lds = (int)pl.lds;
     if (qm) {
         h->stats.last_lb = pl.form == ScanForm::QueryMajorLb ? 1 : 0;
-        TRY(scan_query_major(h, pl, nb, d_q, K, w, d_ids, d_dists, d_counts, single, pre_list != nullptr));
+        TRY(scan_query_major(h, pl, c));
     } else {
         h->stats.last_striped = pl.striped();
         h->stats.last_nf = pl.form == ScanForm::NarrowField ? 1 : 0;
-        TRY(scan_list_major(h, pl, nb, d_q, K, w, d_ids, d_dists, d_counts, direct, mv));
+        TRY(scan_list_major(h, pl, c, direct));
     }
     h->stats.queries += nb;
     if (h->profiling && h->pending.size() > 2048) TRY(ev_fold(h));
@@ -1580,11 +1582,48 @@ int gen_stage_a(ivfadc_index *h, const float *qa, int64_t na, int w, int *d_pl, 
     return IVFADC_OK;
 }
 
-int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-                   const int *pre_list = nullptr, const float *pre_dc = nullptr,   // the caller's probes (ivfadc_search_preassigned): stage A is their ingest
-                   const MaskView *mv = nullptr)   // a masked search: rejected points leave all-ones keys, which sort last and are counted out
+// The queries of a batch in groups the segmented sort can take (range_plan::next_group; tot: keys per query).  For every group: its 32-bit
+// offset row in gen_off, gen_a / gen_b sized for its keys (at least one key's worth), body(g0, ng, keys), and a synchronisation, since
+// all three are reused by the next group.  skip_empty: a group without keys is passed over (range search; the generic path still emits
+// its zero counts).  A batch holds at most range_plan::MAX_GRID_Y queries (the generic path's nba clamp, the range plan's nb): within
+// that bound next_group's grid-y term never cuts a group that the key budget would not (tests/c/search_call_check.cpp).
+template <class Body>
+int for_sort_groups(ivfadc_index *h, const std::vector<uint64_t> &tot, int64_t cap_keys, bool skip_empty, const char *verb, const char *noun, Body body)
 {
-    const int kc = h->kc;
+    const int64_t n = (int64_t)tot.size();
+    if (n > range_plan::MAX_GRID_Y) return fail(IVFADC_ERR_STATE, "a sort batch of %lld queries (at most %lld)", (long long)n, (long long)range_plan::MAX_GRID_Y);
+    std::vector<u32> off;
+    for (int64_t g0 = 0; g0 < n;) {
+        uint64_t keys = 0;
+        const int64_t g1 = range_plan::next_group(tot, g0, cap_keys, &keys);
+        if (g1 == g0)
+            return fail(IVFADC_ERR_INVALID, "a single query %s %llu %s: too many for one sort", verb, (unsigned long long)tot[(size_t)g0], noun);
+        const int64_t ng = g1 - g0;
+        if (keys > 0 || !skip_empty) {
+            off.resize((size_t)ng + 1);
+            off[0] = 0;
+            for (int64_t q = 0; q < ng; ++q) off[(size_t)q + 1] = off[(size_t)q] + (u32)tot[(size_t)(g0 + q)];
+            TRY(h->gen_a.ensure((size_t)std::max<uint64_t>(1, keys) * 8));
+            TRY(h->gen_b.ensure((size_t)std::max<uint64_t>(1, keys) * 8));
+            TRY(h->gen_off.ensure(((size_t)ng + 1) * 4));
+            TRY(h2d_copy(h->gen_off.p, off.data(), ((size_t)ng + 1) * 4, h->stream));
+            TRY(body(g0, ng, (int64_t)keys));
+            HIP_TRY(hipStreamSynchronize(h->stream));   // `off` and the key buffers are reused by the next group
+        }
+        g0 = g1;
+    }
+    return IVFADC_OK;
+}
+
+// the probe rows the coarse stage of the current batch left in the handle
+ProbeRows probe_rows(ivfadc_index *h, int w) { return ProbeRows{h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), w}; }
+
+// c.pre_list: the caller's probes (ivfadc_search_preassigned), stage A is their ingest.  A masked search: rejected points leave all-ones
+// keys, which sort last and are counted out.
+int search_generic(ivfadc_index *h, const SearchCall &c)
+{
+    const int kc = h->kc, K = c.K, w = c.w;
+    const int64_t nq = c.nq;
     const size_t lds = (align_up((size_t)h->d, 4) + (h->u16 ? (size_t)GEN16_TILE : (size_t)h->m * 256)) * 4;
     if (lds > LDS_MAX) return fail(IVFADC_ERR_INVALID, "m=%d needs %zu B of LDS in the generic path (> %zu)", h->m, lds, LDS_MAX);
     void (*dump)(const IndexView, const float *, int, const int *, const float *, const u32 *, const u32 *, u64 *, const MaskView) =
@@ -1598,60 +1637,46 @@ int search_generic(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, 
     const int64_t per_q = (int64_t)kc * (4 + 16) + (int64_t)w * 12 + 64;
     int64_t nba = std::max<int64_t>(1, (int64_t)(h->ws_budget / (size_t)per_q));
     nba = std::min<int64_t>(std::min<int64_t>(nba, nq), std::min<int64_t>(65535, ((int64_t)1 << 31) / std::max(1, kc)));
-    std::vector<u32> tot, off;
+    // stage B groups: as many queries as fit the key budget (two key buffers + sort scratch), at least one
+    const int64_t cap_keys = range_plan::sort_cap_keys(h->ws_budget);
+    std::vector<u32> tot32;
+    std::vector<uint64_t> tot;   // (the same, as next_group takes them)
     for (int64_t a0 = 0; a0 < nq; a0 += nba) {
-        const int64_t na = std::min(nba, nq - a0);
-        const float *qa = d_q + (size_t)a0 * h->d;
+        const SearchCall ca = c.slice(a0, std::min(nba, nq - a0));
+        const int64_t na = ca.nq;
         const size_t np = (size_t)na * w;
         TRY(h->probe_list.ensure(np * 4));
         TRY(h->probe_dc.ensure(np * 4));
         TRY(h->probe_base.ensure(np * 4));
         TRY(h->gen_tot.ensure((size_t)na * 4));
-        if (pre_list) {
-            hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, h->stream, pre_list + (size_t)a0 * w,
-                               pre_dc + (size_t)a0 * w, (int)na, kc, w, h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(),
-                               h->probe_base.as<u32>(), (u32 *)nullptr, h->gen_tot.as<u32>(), d_scanned);
+        if (ca.pre()) {
+            hipLaunchKernelGGL(probe_ingest_kernel, dim3((unsigned)((na + 3) / 4)), dim3(256), 0, h->stream, ca.pre_list, ca.pre_dc, (int)na, kc, w,
+                               h->list_len.as<u32>(), h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), (u32 *)nullptr,
+                               h->gen_tot.as<u32>(), d_scanned);
             HIP_TRY(hipGetLastError());
         } else {
-            TRY(gen_stage_a(h, qa, na, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), d_scanned));
+            TRY(gen_stage_a(h, ca.q, na, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), d_scanned));
         }
-        tot.resize((size_t)na);
-        TRY(d2h_copy(tot.data(), h->gen_tot.p, (size_t)na * 4, h->stream));
+        tot32.resize((size_t)na);
+        TRY(d2h_copy(tot32.data(), h->gen_tot.p, (size_t)na * 4, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
-        // stage B groups: as many queries as fit the key budget (two key buffers + sort scratch), at least one
-        const int64_t cap_keys = std::max<int64_t>(1 << 20, (int64_t)(h->ws_budget / 24));
-        for (int64_t g0 = 0; g0 < na;) {
-            int64_t g1 = g0, keys = 0;
-            while (g1 < na && (g1 == g0 || keys + tot[g1] <= cap_keys) && keys + tot[g1] < ((int64_t)1 << 32)) keys += tot[g1++];
-            if (g1 == g0) return fail(IVFADC_ERR_INVALID, "a single query probes %u points: too many for one sort", tot[g0]);
-            const int64_t ng = g1 - g0;
-            off.resize((size_t)ng + 1);
-            off[0] = 0;
-            for (int64_t q = 0; q < ng; ++q) off[q + 1] = off[q] + tot[g0 + q];
-            TRY(h->gen_a.ensure((size_t)std::max<int64_t>(1, keys) * 8));
-            TRY(h->gen_b.ensure((size_t)std::max<int64_t>(1, keys) * 8));
-            TRY(h->gen_off.ensure(((size_t)ng + 1) * 4));
-            TRY(h2d_copy(h->gen_off.p, off.data(), ((size_t)ng + 1) * 4, h->stream));
-            const int *pl = h->probe_list.as<int>() + (size_t)g0 * w;
-            const float *pd = h->probe_dc.as<float>() + (size_t)g0 * w;
-            const u32 *pb = h->probe_base.as<u32>() + (size_t)g0 * w;
+        tot.assign(tot32.begin(), tot32.end());
+        TRY(for_sort_groups(h, tot, cap_keys, false, "probes", "points", [&](int64_t g0, int64_t ng, int64_t keys) -> int {
+            const SearchCall cg = ca.slice(g0, ng);
+            const ProbeRows pg = probe_rows(h, w).slice(g0);
             for (int64_t y0 = 0; y0 < ng; y0 += 32768) {   // grid.y limit
-                const int64_t ny = std::min<int64_t>(32768, ng - y0);
-                MaskView mq{};   // (words null: no mask set)
-                if (mv) { mq = *mv; mq.mask_of_query = mv->mask_of_query + (a0 + g0 + y0); }
-                hipLaunchKernelGGL(dump, dim3((unsigned)w, (unsigned)ny), dim3(256), lds, h->stream, ix,
-                                   qa + (size_t)(g0 + y0) * h->d, w, pl + (size_t)y0 * w, pd + (size_t)y0 * w, pb + (size_t)y0 * w,
-                                   h->gen_off.as<u32>() + y0, h->gen_a.as<u64>(), mq);
+                const SearchCall cy = cg.slice(y0, std::min<int64_t>(32768, ng - y0));
+                const ProbeRows py = pg.slice(y0);
+                hipLaunchKernelGGL(dump, dim3((unsigned)w, (unsigned)cy.nq), dim3(256), lds, h->stream, ix, cy.q, w, py.list, py.dc, py.base,
+                                   h->gen_off.as<u32>() + y0, h->gen_a.as<u64>(), mask_view(cy));
                 HIP_TRY(hipGetLastError());
             }
             TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), keys, (int)ng, h->gen_off.as<u32>()));
             hipLaunchKernelGGL(gen_emit_kernel, dim3((unsigned)ng), dim3(256), 0, h->stream, h->gen_b.as<u64>(), h->gen_off.as<u32>(),
-                               h->gen_tot.as<u32>() + g0, w, K, pl, pb, h->list_pos.as<int64_t>(), idp, d_ids + (size_t)(a0 + g0) * K,
-                               d_dists + (size_t)(a0 + g0) * K, d_counts + a0 + g0);
+                               h->gen_tot.as<u32>() + g0, w, K, pg.list, pg.base, h->list_pos.as<int64_t>(), idp, cg.ids, cg.dists, cg.counts);
             HIP_TRY(hipGetLastError());
-            HIP_TRY(hipStreamSynchronize(h->stream));   // `off` and the key buffers are reused by the next group
-            g0 = g1;
-        }
+            return IVFADC_OK;
+        }));
         h->stats.queries += na;
     }
     h->stats.last_qg = -2;
@@ -1679,8 +1704,9 @@ bool sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
     return lds <= LDS_MAX;
 }
 
-int search_small(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts)
+int search_small(ivfadc_index *h, const SearchCall &c)
 {
+    const int64_t nq = c.nq; const float *d_q = c.q; const int K = c.K, w = c.w;
     TRY(ensure_common_ws(h));
     const bool inside = h->kc <= sq_inside_kc(h);
     if (!inside) {
@@ -1720,7 +1746,7 @@ int search_small(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, ui
     a.part_keys = h->sq_keys.as<u64>();
     a.part_cnt = h->sq_cnt.as<u32>();
     a.arrive = h->sq_arrive.as<u32>();
-    a.out_ids = d_ids; a.out_dists = d_dists; a.out_counts = d_counts;
+    a.out_ids = c.ids; a.out_dists = c.dists; a.out_counts = c.counts;
     a.scanned_points = h->misc.as<u64>();
     const size_t lds = scan_lds_bytes(h->m, h->d, 1, 64, true) + 64 + (inside ? (size_t)h->kc * 4 : 0);
     sq_fn_t fn = pick_sq(h->m, h->dsub);
@@ -1922,79 +1948,58 @@ int build_twolevel(ivfadc_index *h)
     return IVFADC_OK;
 }
 
-// Probes supplied by the caller (ivfadc_search_preassigned, device pointers): row q = the w probes of query q in visit order.  With
-// them a search has no coarse stage of its own -- no latency path, no fused top-w, no matrix-core filter, no two-level search, no
-// riders -- and everything behind the probe arrays runs as it does for a plain search.
-struct PreProbes { const int *lists; const float *dcs; };
-// The mask set of a masked search (ivfadc_search_masked) and the batch's mask numbers on the device, every value in [-1, nmasks).  The
-// coarse stage is the plain search's own, in any form; behind it the masked list scan (make_plan_masked) or the masked generic path --
-// no latency path, no fused top-w, no riders.  Together with PreProbes: out of scope (there is no entry for it).
-struct MaskArgs { const ivfadc_maskset *set; const int32_t *mask_of_query; };
-
-int search_dev(ivfadc_index *h, int64_t nq, const float *d_q, int K, int w, uint32_t *d_ids, float *d_dists, int32_t *d_counts,
-               const PreProbes *pre = nullptr, const MaskArgs *mask = nullptr)
+// The first lines of every search (search_dev, range_dev, coarse_dev).  Rows the previous search's riders left serve THIS search or none,
+// whatever path it takes (small-batch, generic, sub-batched, failing): they are taken over here and forgotten.  take_rows (search_dev
+// alone): they are offered when the caller declared this search's queries to be the very generation the rows were computed from (same
+// token, != 0) -- a staging buffer refilled in between carries another token.  Otherwise avail_q is cleared; coarse_dev used to leave that
+// to the HintScope of the search before it, which comes to the same: every search ends through a HintScope and nothing else sets avail_q.
+// partial_nq: the probe arrays a pending ivfadc_merge_partials_device would read are about to be overwritten.  group_centroids: the
+// grouping of a large quantizer is built on its first search with queries (automatic mode), or on request (ivfadc_set_coarse_mode(h, 6)).
+int begin_search(ivfadc_index *h, int64_t nq, bool take_rows, bool group_centroids)
 {
-    HintScope hint_scope{h};
-    // Rows the previous search's riders left serve THIS search or none, whatever path it takes (small-batch, generic, sub-batched, failing):
-    // they are taken over here and forgotten.  They are offered only when the caller declared this search's queries to be the very
-    // generation the rows were computed from (same token, != 0): a staging buffer refilled in between carries another token.
-    const bool declared = h->cur_token != 0 && h->cur_token == h->pf_token;
+    const bool declared = take_rows && h->cur_token != 0 && h->cur_token == h->pf_token;
     h->avail_q = declared ? h->pf_q : nullptr;
     h->avail_nq = declared ? h->pf_nq : 0;
     h->pf_q = nullptr; h->pf_nq = 0; h->pf_token = 0; h->cur_token = 0;
     h->stats.coarse_prefetched = 0;
     h->stats.last_rider = 0;
-    h->partial_nq = -1;   // the probe arrays a pending ivfadc_merge_partials_device would read are about to be overwritten
+    h->partial_nq = -1;
     TRY(set_device(h));
     if (h->dirty) TRY(upload_lists(h));
+    if (nq > 0 && group_centroids && !h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
+    return IVFADC_OK;
+}
+
+// Supplied probes (c.pre_list, ivfadc_search_preassigned): the search has no coarse stage of its own -- no latency path, no fused top-w,
+// no matrix-core filter, no two-level search, no riders -- and everything behind the probe arrays runs as it does for a plain search.
+// A mask set (c.mask_words, ivfadc_search_masked): the coarse stage is the plain search's own, in any form; behind it the masked list
+// scan (make_plan_masked) or the masked generic path -- no latency path, no fused top-w, no riders.  Both together: there is no entry.
+int search_dev(ivfadc_index *h, const SearchCall &c)
+{
+    HintScope hint_scope{h};
+    const bool pre = c.pre(), masked = c.masked();
+    const int64_t nq = c.nq;
+    const int K = c.K, w = c.w;
+    TRY(begin_search(h, nq, true, !pre));
     if (nq == 0) return IVFADC_OK;
-    // the grouping of a large quantizer is built on its first search (automatic mode), or on request (ivfadc_set_coarse_mode(h, 6))
-    if (!pre && !h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
     const bool parted = h->part_n > 1;
-    const int *prl = pre ? pre->lists : (const int *)nullptr;
-    const float *prd = pre ? pre->dcs : (const float *)nullptr;
-    if (mask) {
-        if (pre || parted) return fail(IVFADC_ERR_STATE, "a masked search takes neither supplied probes nor a list partition");
-        MaskView mv;
-        mv.words = mask->set->words.as<u32>();
-        mv.word_off = mask->set->word_off.as<uint64_t>();
-        mv.W = mask->set->W;
-        mv.mask_of_query = mask->mask_of_query;
-        if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || h->u16)
-            return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, nullptr, nullptr, &mv);
-        TRY(fb_poll(h));
-        Plan pl = make_plan_masked(plan_facts(h), nq, K, w);
-        if (!pl.fits) return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, nullptr, nullptr, &mv);
-        TRY(plan_kernel(pl, h->m, h->dsub));
-        for (int64_t b0 = 0; b0 < nq; b0 += pl.nb) {
-            const int64_t nb = std::min(pl.nb, nq - b0);
-            MaskView mb = mv;
-            mb.mask_of_query = mv.mask_of_query + b0;   // the mask numbers advance with the sub-batch
-            TRY(search_subbatch(h, pl, nb, d_q + (size_t)b0 * h->d, K, w, d_ids + (size_t)b0 * K, d_dists + (size_t)b0 * K, d_counts + b0, false,
-                                nullptr, nullptr, &mb));
-        }
-        return IVFADC_OK;
-    }
-    if (!parted && !pre && sq_eligible(h, nq, K, w)) return search_small(h, nq, d_q, K, w, d_ids, d_dists, d_counts);
-    if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && K > 64 && !h->u16_wide)) {
+    if (masked && (pre || parted)) return fail(IVFADC_ERR_STATE, "a masked search takes neither supplied probes nor a list partition");
+    if (!masked && !parted && !pre && sq_eligible(h, nq, K, w)) return search_small(h, c);
+    if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && (masked || (K > 64 && !h->u16_wide)))) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
-        return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, prl, prd);
+        return search_generic(h, c);
     }
     TRY(fb_poll(h));
     const PlanFacts facts = plan_facts(h);
-    Plan pl = h->u16 ? make_plan_u16(facts, nq, K, w, pre != nullptr) : make_plan(facts, nq, K, w, pre != nullptr);
+    Plan pl = masked ? make_plan_masked(facts, nq, K, w) : h->u16 ? make_plan_u16(facts, nq, K, w, pre) : make_plan(facts, nq, K, w, pre);
     if (!pl.fits) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the selection kernels' LDS need exceeds a CU for this m and K");
-        return search_generic(h, nq, d_q, K, w, d_ids, d_dists, d_counts, prl, prd);   // "any K and w" holds for every m
+        return search_generic(h, c);   // "any K and w" holds for every m
     }
     TRY(plan_kernel(pl, h->m, h->dsub));
     if (parted && pl.nb < nq)
         return fail(IVFADC_ERR_INVALID, "list-partitioned mode: the batch must fit one sub-batch (raise ivfadc_set_workspace_limit or split the batch)");
-    for (int64_t b0 = 0; b0 < nq; b0 += pl.nb) {
-        const int64_t nb = std::min(pl.nb, nq - b0);
-        TRY(search_subbatch(h, pl, nb, d_q + (size_t)b0 * h->d, K, w, d_ids + (size_t)b0 * K, d_dists + (size_t)b0 * K,
-                            d_counts + b0, pl.nb >= nq, pre ? prl + (size_t)b0 * w : prl, pre ? prd + (size_t)b0 * w : prd));
-    }
+    for (int64_t b0 = 0; b0 < nq; b0 += pl.nb) TRY(search_subbatch(h, pl, c.slice(b0, std::min(pl.nb, nq - b0))));
     return IVFADC_OK;
 }
 
@@ -2012,25 +2017,17 @@ range_plan::Facts range_facts(const ivfadc_index *h)
     return f;
 }
 
-// d_q, d_r: nq queries and their radii in device memory.  Blocking: the result is complete when this returns.
-// mask (ivfadc_range_search_masked): the set and the batch's mask numbers on the device, every value in [-1, nmasks); null: no query
-// is filtered.  The kernel pair follows (16-bit codes, mask present): range_u16_* for a 16-bit handle with or without a set,
+// c.q, c.radii: the queries and their radii in device memory.  Blocking: the result is complete when this returns.
+// c.mask_* (ivfadc_range_search_masked): the set and the batch's mask numbers on the device, every value in [-1, nmasks); no set: no
+// query is filtered.  The kernel pair follows (16-bit codes, mask present): range_u16_* for a 16-bit handle with or without a set,
 // range_masked_* for an 8-bit handle with one, the plain pair otherwise.
-int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, int w, int64_t max_total, ivfadc_range_result **out,
-              const MaskArgs *mask = nullptr)
+int range_dev(ivfadc_index *h, const SearchCall &c, int64_t max_total, ivfadc_range_result **out)
 {
     HintScope hint_scope{h};
-    // as any search: rows the previous search's riders left serve the very next search or none, and the probe arrays a pending
-    // ivfadc_merge_partials_device would read are about to be overwritten
-    h->avail_q = nullptr; h->avail_nq = 0;
-    h->pf_q = nullptr; h->pf_nq = 0; h->pf_token = 0; h->cur_token = 0;
-    h->stats.coarse_prefetched = 0;
-    h->stats.last_rider = 0;
-    h->partial_nq = -1;
-    TRY(set_device(h));
-    if (h->dirty) TRY(upload_lists(h));
+    TRY(begin_search(h, c.nq, false, false));
+    const int64_t nq = c.nq; const int w = c.w;
     range_plan::Facts facts = range_facts(h);
-    facts.masked = mask != nullptr;
+    facts.masked = c.masked();
     const range_plan::Plan pl = range_plan::make_plan(facts, nq, w);
     if (!pl.fits) return fail(IVFADC_ERR_INVALID, "range search (d=%d, m=%d, w=%d): %s", h->d, h->m, w, pl.why);
     std::unique_ptr<ivfadc_range_result> res(new ivfadc_range_result);
@@ -2038,24 +2035,29 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
     res->nq = nq;
     std::vector<uint64_t> tot((size_t)nq, 0);
     const IndexView ix = index_view(h);
-    const bool with_mv = h->u16 || mask != nullptr;   // the kernels that take a MaskView
+    const bool with_mv = h->u16 || c.masked();   // the kernels that take a MaskView
     const range_masked_fn_t count_mv = h->u16 ? range_u16_count_kernel : range_masked_count_kernel;
     const range_masked_fn_t fill_mv = h->u16 ? range_u16_fill_kernel : range_masked_fill_kernel;
-    MaskView mv{};   // (words null: no query is filtered)
-    if (mask) {
-        mv.words = mask->set->words.as<u32>();
-        mv.word_off = mask->set->word_off.as<uint64_t>();
-        mv.W = mask->set->W;
-        mv.mask_of_query = mask->mask_of_query;
-    }
     if (nq > 0) {
         TRY(fn_raise_lds(h->device, with_mv ? (const void *)count_mv : (const void *)range_count_kernel, pl.lds, true));
         TRY(fn_raise_lds(h->device, with_mv ? (const void *)fill_mv : (const void *)range_fill_kernel, pl.lds, true));
         TRY(ensure_common_ws(h));
     }
     const int64_t items = pl.items;
-    // stage A of the generic path (exact coarse distances, sorted rows, the w probes) and the count pass of queries a0 .. a0 + na - 1
-    auto count_batch = [&](int64_t a0, int64_t na, u64 *d_scanned) -> int {
+    // what both passes hand their kernels: the queries of cs, their probes pr and their item counts from query i0 of the sub-batch on
+    auto range_args = [&](const SearchCall &cs, const ProbeRows &pr, int64_t i0) {
+        RangeArgs a{};
+        a.ix = ix;
+        a.queries = cs.q;
+        a.radii = cs.radii;
+        a.w = w; a.chunk = pl.chunk; a.maxch = (u32)pl.maxch;
+        a.probe_list = pr.list; a.probe_dc = pr.dc; a.probe_base = pr.base;
+        a.item_cnt = h->rng_cnt.as<u32>() + (size_t)i0 * (size_t)items;
+        return a;
+    };
+    // stage A of the generic path (exact coarse distances, sorted rows, the w probes) and the count pass of the sub-batch ca
+    auto count_batch = [&](const SearchCall &ca, u64 *d_scanned) -> int {
+        const int64_t na = ca.nq;
         const size_t np = (size_t)na * w, ni = (size_t)na * (size_t)items;
         TRY(h->probe_list.ensure(np * 4));
         TRY(h->probe_dc.ensure(np * 4));
@@ -2064,21 +2066,10 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
         TRY(h->rng_tot.ensure((size_t)na * 4));
         TRY(h->rng_cnt.ensure(ni * 4));
         TRY(h->rng_off.ensure(ni * 4));
-        TRY(gen_stage_a(h, d_q + (size_t)a0 * h->d, na, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), d_scanned));
-        RangeArgs a{};
-        a.ix = ix;
-        a.queries = d_q + (size_t)a0 * h->d;
-        a.radii = d_r + a0;
-        a.w = w; a.chunk = pl.chunk; a.maxch = (u32)pl.maxch;
-        a.probe_list = h->probe_list.as<int>(); a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>();
-        a.item_cnt = h->rng_cnt.as<u32>();
-        if (with_mv) {
-            MaskView mb = mv;
-            if (mask) mb.mask_of_query = mv.mask_of_query + a0;   // the mask numbers advance with the sub-batch (pass 1 and the re-run alike)
-            hipLaunchKernelGGL(count_mv, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a, mb);
-        } else {
-            hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a);
-        }
+        TRY(gen_stage_a(h, ca.q, na, w, h->probe_list.as<int>(), h->probe_dc.as<float>(), h->probe_base.as<u32>(), d_scanned));
+        const RangeArgs a = range_args(ca, probe_rows(h, w), 0);
+        if (with_mv) hipLaunchKernelGGL(count_mv, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a, mask_view(ca));
+        else hipLaunchKernelGGL(range_count_kernel, dim3((unsigned)items, (unsigned)na), dim3(256), pl.lds, h->stream, a);
         HIP_TRY(hipGetLastError());
         hipLaunchKernelGGL(range_offsets_kernel, dim3((unsigned)na), dim3(256), 0, h->stream, h->rng_cnt.as<u32>(), (u32)items, h->rng_off.as<u32>(),
                            h->rng_tot.as<u32>());
@@ -2086,10 +2077,10 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
         return IVFADC_OK;
     };
     const int64_t nbatches = nq == 0 ? 0 : (nq + pl.nb - 1) / pl.nb;
-    std::vector<u32> tot32, off;
+    std::vector<u32> tot32;
     for (int64_t a0 = 0; a0 < nq; a0 += pl.nb) {   // pass 1: every query's total, before anything of the result is allocated
         const int64_t na = std::min(pl.nb, nq - a0);
-        TRY(count_batch(a0, na, h->misc.as<u64>()));
+        TRY(count_batch(c.slice(a0, na), h->misc.as<u64>()));
         tot32.resize((size_t)na);
         TRY(d2h_copy(tot32.data(), h->rng_tot.p, (size_t)na * 4, h->stream));
         HIP_TRY(hipStreamSynchronize(h->stream));
@@ -2104,53 +2095,27 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
     HIP_TRY(hipMalloc((void **)&res->d_dists, (size_t)std::max<int64_t>(1, res->total) * 4));
     TRY(h2d_copy(res->d_lims, res->lims.data(), ((size_t)nq + 1) * 8, h->stream));
     for (int64_t a0 = 0; a0 < nq && res->total > 0; a0 += pl.nb) {   // pass 2: fill, sort, emit
-        const int64_t na = std::min(pl.nb, nq - a0);
+        const SearchCall ca = c.slice(a0, std::min(pl.nb, nq - a0));
         // several sub-batches: the probe arrays and item words of this one were overwritten; the same launches give the same words again
         // (their B_alg counts go to the lines nobody reads: the points were counted in pass 1)
-        if (nbatches > 1) TRY(count_batch(a0, na, (u64 *)((char *)h->misc.p + MISC_SINK)));
-        const std::vector<uint64_t> tb(tot.begin() + a0, tot.begin() + a0 + na);
-        for (int64_t g0 = 0; g0 < na;) {
-            uint64_t keys = 0;
-            const int64_t g1 = range_plan::next_group(tb, g0, pl.cap_keys, &keys);
-            if (g1 == g0) return fail(IVFADC_ERR_INVALID, "a single query holds %llu results: too many for one sort", (unsigned long long)tb[(size_t)g0]);
-            const int64_t ng = g1 - g0;
-            if (keys > 0) {
-                off.resize((size_t)ng + 1);
-                off[0] = 0;
-                for (int64_t q = 0; q < ng; ++q) off[(size_t)q + 1] = off[(size_t)q] + (u32)tb[(size_t)(g0 + q)];
-                TRY(h->gen_a.ensure((size_t)keys * 8));
-                TRY(h->gen_b.ensure((size_t)keys * 8));
-                TRY(h->gen_off.ensure(((size_t)ng + 1) * 4));
-                TRY(h2d_copy(h->gen_off.p, off.data(), ((size_t)ng + 1) * 4, h->stream));
-                RangeArgs a{};
-                a.ix = ix;
-                a.queries = d_q + (size_t)(a0 + g0) * h->d;
-                a.radii = d_r + a0 + g0;
-                a.w = w; a.chunk = pl.chunk; a.maxch = (u32)pl.maxch;
-                a.probe_list = h->probe_list.as<int>() + (size_t)g0 * w;
-                a.probe_dc = h->probe_dc.as<float>() + (size_t)g0 * w;
-                a.probe_base = h->probe_base.as<u32>() + (size_t)g0 * w;
-                a.item_cnt = h->rng_cnt.as<u32>() + (size_t)g0 * (size_t)items;
-                a.item_off = h->rng_off.as<u32>() + (size_t)g0 * (size_t)items;
-                a.key_off = h->gen_off.as<u32>();
-                a.keys = h->gen_a.as<u64>();
-                if (with_mv) {
-                    MaskView mb = mv;
-                    if (mask) mb.mask_of_query = mv.mask_of_query + a0 + g0;   // ... and with the sort group, as the queries and radii do
-                    hipLaunchKernelGGL(fill_mv, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a, mb);
-                } else {
-                    hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a);
-                }
-                HIP_TRY(hipGetLastError());
-                TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), (int64_t)keys, (int)ng, h->gen_off.as<u32>()));
-                const unsigned ey = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, ((int64_t)keys / ng + 1023) / 1024));
-                hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)ng, ey), dim3(256), 0, h->stream, h->gen_b.as<u64>(), h->gen_off.as<u32>(), w,
-                                   a.probe_list, a.probe_base, h->list_pos.as<int64_t>(), ix.ids, res->d_lims + a0 + g0, res->d_ids, res->d_dists);
-                HIP_TRY(hipGetLastError());
-                HIP_TRY(hipStreamSynchronize(h->stream));   // `off` and the key buffers are reused by the next group
-            }
-            g0 = g1;
-        }
+        if (nbatches > 1) TRY(count_batch(ca, (u64 *)((char *)h->misc.p + MISC_SINK)));
+        const std::vector<uint64_t> tb(tot.begin() + a0, tot.begin() + a0 + ca.nq);
+        TRY(for_sort_groups(h, tb, pl.cap_keys, true, "holds", "results", [&](int64_t g0, int64_t ng, int64_t keys) -> int {
+            const SearchCall cg = ca.slice(g0, ng);
+            RangeArgs a = range_args(cg, probe_rows(h, w).slice(g0), g0);
+            a.item_off = h->rng_off.as<u32>() + (size_t)g0 * (size_t)items;
+            a.key_off = h->gen_off.as<u32>();
+            a.keys = h->gen_a.as<u64>();
+            if (with_mv) hipLaunchKernelGGL(fill_mv, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a, mask_view(cg));
+            else hipLaunchKernelGGL(range_fill_kernel, dim3((unsigned)items, (unsigned)ng), dim3(256), pl.lds, h->stream, a);
+            HIP_TRY(hipGetLastError());
+            TRY(gen_sort(h, h->gen_a.as<u64>(), h->gen_b.as<u64>(), keys, (int)ng, h->gen_off.as<u32>()));
+            const unsigned ey = (unsigned)std::max<int64_t>(1, std::min<int64_t>(64, (keys / ng + 1023) / 1024));
+            hipLaunchKernelGGL(range_emit_kernel, dim3((unsigned)ng, ey), dim3(256), 0, h->stream, h->gen_b.as<u64>(), h->gen_off.as<u32>(), w,
+                               a.probe_list, a.probe_base, h->list_pos.as<int64_t>(), ix.ids, res->d_lims + a0 + g0, res->d_ids, res->d_dists);
+            HIP_TRY(hipGetLastError());
+            return IVFADC_OK;
+        }));
     }
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->stats.queries += nq;
@@ -2162,17 +2127,14 @@ int range_dev(ivfadc_index *h, int64_t nq, const float *d_q, const float *d_r, i
 // exact VALU kernel, matrix-core filter + certified refine, or the certified two-level search; the same bytes from each -- with the
 // stand-alone top-w kernel (or the two-level kernel) writing lists and distances straight into d_lists / d_dists.  The visit-order
 // bases go to the handle's own probe_base, the B_alg counts to the sink: nothing is scanned.  w > IVFADC_MAX_W: the generic path's sort.
-int coarse_dev(ivfadc_index *h, int64_t nq, const float *d_q, int w, int32_t *d_lists, float *d_dists)
+// c.out_list / c.out_dc: the caller's device rows.
+int coarse_dev(ivfadc_index *h, const SearchCall &c)
 {
     HintScope hint_scope{h};
-    h->pf_q = nullptr; h->pf_nq = 0; h->pf_token = 0; h->cur_token = 0;
-    h->stats.coarse_prefetched = 0;
-    h->stats.last_rider = 0;
-    h->partial_nq = -1;   // (probe_base is rewritten)
-    TRY(set_device(h));
-    if (h->dirty) TRY(upload_lists(h));
+    const int64_t nq = c.nq;
+    const int w = c.w;
+    TRY(begin_search(h, nq, false, true));   // (partial_nq: probe_base is rewritten)
     if (nq == 0) return IVFADC_OK;
-    if (!h->tl_tried && !h->is_view && h->tl_mode >= 0 && (h->tl_mode > 0 || h->kc >= TL_AUTO_MIN_KC)) TRY(build_twolevel(h));
     TRY(ensure_common_ws(h));
     const int kc = h->kc;
     u64 *d_sink = (u64 *)((char *)h->misc.p + MISC_SINK);
@@ -2190,10 +2152,8 @@ int coarse_dev(ivfadc_index *h, int64_t nq, const float *d_q, int w, int32_t *d_
     h->stats.last_twolevel = twolevel ? 1 : 0;
     h->stats.coarse_mfma = mfma ? 1 : 0;
     for (int64_t b0 = 0; b0 < nq; b0 += nb) {
-        const int64_t n = std::min(nb, nq - b0);
-        const float *q = d_q + (size_t)b0 * h->d;
-        int *ol = (int *)d_lists + (size_t)b0 * w;
-        float *od = d_dists + (size_t)b0 * w;
+        const SearchCall cb = c.slice(b0, std::min(nb, nq - b0));
+        const int64_t n = cb.nq; const float *q = cb.q; int *ol = cb.out_list; float *od = cb.out_dc;
         if (generic) {
             TRY(h->gen_tot.ensure((size_t)n * 4));
             TRY(gen_stage_a(h, q, n, w, ol, od, h->probe_base.as<u32>(), d_sink));
@@ -2904,9 +2864,20 @@ try {
 } IVF_CATCH
 
 // ---- mask sets (maskset_plan.h, maskset.hip.h; DESIGN.md "Mask sets") -------------------------------------------------------------
-static int search_enqueue(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists, int32_t *out_counts,
-                          const int32_t *pre_lists, const float *pre_dcs, const MaskArgs *mask);
-static int search_finish(ivfadc_t *h, int64_t nq, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts);
+static int search_enqueue(ivfadc_t *h, const SearchCall &hc);
+static int search_finish(ivfadc_t *h, const SearchCall &hc);
+
+// The way out of an entry once the device has been touched: whatever was enqueued before a failure may still be writing the staging
+// buffers (or the caller's arrays) and ends first; the failure's message survives the drain.
+static int finish_entry(ivfadc_index *h, int rc)
+{
+    if (rc != IVFADC_OK) {
+        const std::string msg = g_err;
+        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
+        g_err = msg;
+    }
+    return rc;
+}
 // the arguments of both creation entries, before the handle is looked at and before any device call
 static int check_maskset_args(ivfadc_t *h, int nmasks, const uint32_t *bits, uint64_t nbits, ivfadc_maskset_t **out)
 {
@@ -3004,61 +2975,76 @@ void ivfadc_maskset_destroy(ivfadc_maskset_t *s)
     delete s;
 }
 
-// h and s of a masked search: h is the index s was made from, unchanged since, or a plain view of it
-static int check_masked_args(ivfadc_index *h, const ivfadc_maskset *s, int64_t nq, int K, int &w)
+// h and s of a masked entry (entry: its name): h is the index s was made from, unchanged since, or a plain view of it
+static int check_mask_link(const ivfadc_index *h, const ivfadc_maskset *s, const char *entry)
+{
+    if (h->is_subset) return fail(IVFADC_ERR_STATE, "%s: a subset view has lists of its own; search the index the mask set was made from, or a plain view of it", entry);
+    const ivfadc_index *root = h->is_view ? h->view_of : h;   // (check_view_current: the link stands)
+    if (root->serial != s->index_serial) return fail(IVFADC_ERR_STATE, "%s: the mask set was made from another index", entry);
+    if (root->generation != s->generation) return fail(IVFADC_ERR_STATE, "%s: the index has changed since the mask set was made: make a new one", entry);
+    return IVFADC_OK;
+}
+
+// the mask numbers of a host entry, before any launch (null: every query takes mask 0)
+static int check_mask_numbers(const ivfadc_maskset *s, int64_t nq, const int32_t *mask_of_query)
+{
+    for (int64_t q = 0; mask_of_query && q < nq; ++q)
+        if (mask_of_query[q] < -1 || mask_of_query[q] >= s->nmasks)
+            return fail(IVFADC_ERR_INVALID, "query %lld: mask %d is outside [-1, %d)", (long long)q, mask_of_query[q], s->nmasks);
+    return IVFADC_OK;
+}
+
+// The set and the mask numbers of c's queries into the call, the numbers staged in mask_q on the handle's stream: from host memory a copy
+// (zeros when there are none), from device memory clamped into [-1, nmasks), so that a violated precondition cannot read outside the set.
+static int stage_mask_numbers(ivfadc_index *h, const ivfadc_maskset *s, const int32_t *mask_of_query, bool on_device, SearchCall &c)
+{
+    const size_t bytes = (size_t)c.nq * 4;
+    TRY(h->mask_q.ensure(std::max<size_t>(bytes, 16)));
+    if (c.nq > 0 && on_device) {
+        hipLaunchKernelGGL(maskset_ingest_kernel, dim3((unsigned)std::min<int64_t>(4096, (c.nq + 255) / 256)), dim3(256), 0, h->stream, mask_of_query,
+                           c.nq, (int32_t)s->nmasks, h->mask_q.as<int32_t>());
+        HIP_TRY(hipGetLastError());
+    } else if (c.nq > 0 && mask_of_query) {
+        TRY(h2d_copy(h->mask_q.p, mask_of_query, bytes, h->stream));
+    } else if (c.nq > 0) {
+        HIP_TRY(hipMemsetAsync(h->mask_q.p, 0, bytes, h->stream));
+    }
+    c.mask_words = s->words.as<u32>(); c.mask_word_off = s->word_off.as<uint64_t>(); c.mask_W = s->W;
+    c.mask_of_query = h->mask_q.as<int32_t>();
+    return IVFADC_OK;
+}
+
+// Both masked K-nearest entries.  c: the call as the entry got it; host: everything the caller gave lies in host memory.
+static int search_masked_entry(ivfadc_index *h, const ivfadc_maskset *s, SearchCall c, const int32_t *mask_of_query, bool host)
 {
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
     if (!s) return fail(IVFADC_ERR_INVALID, "null mask set");
-    TRY(check_search_args(h, nq, K, w));
-    if (h->is_subset) return fail(IVFADC_ERR_STATE, "ivfadc_search_masked: a subset view has lists of its own; search the index the mask set was made from, or a plain view of it");
-    const ivfadc_index *root = h->is_view ? h->view_of : h;   // (check_view_current: the link stands)
-    if (root->serial != s->index_serial) return fail(IVFADC_ERR_STATE, "ivfadc_search_masked: the mask set was made from another index");
-    if (root->generation != s->generation) return fail(IVFADC_ERR_STATE, "ivfadc_search_masked: the index has changed since the mask set was made: make a new one");
+    TRY(check_search_args(h, c.nq, c.K, c.w));
+    TRY(check_mask_link(h, s, "ivfadc_search_masked"));
     if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "a list partition is set (ivfadc_set_list_partition): masked searches serve whole indexes only");
-    return IVFADC_OK;
+    if (c.nq == 0) return IVFADC_OK;
+    if (!c.q || !c.ids || !c.dists || !c.counts) return fail(IVFADC_ERR_INVALID, "null buffer");
+    if (host) TRY(check_mask_numbers(s, c.nq, mask_of_query));
+    TRY(set_device(h));
+    h->dev_entry = false;
+    c.d = h->d;
+    int rc = stage_mask_numbers(h, s, mask_of_query, !host, c);
+    if (rc == IVFADC_OK) rc = host ? search_enqueue(h, c) : search_dev(h, c);
+    return rc != IVFADC_OK || !host ? finish_entry(h, rc) : search_finish(h, c);
 }
 
 int ivfadc_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, int K, int w,
                                 const int32_t *d_mask_of_query, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
 try {
     HandleLock lk_(h);
-    TRY(check_masked_args(h, s, nq, K, w));
-    if (nq == 0) return IVFADC_OK;
-    if (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
-    TRY(set_device(h));
-    h->dev_entry = false;
-    TRY(h->mask_q.ensure((size_t)nq * 4));
-    hipLaunchKernelGGL(maskset_ingest_kernel, dim3((unsigned)std::min<int64_t>(4096, (nq + 255) / 256)), dim3(256), 0, h->stream, d_mask_of_query,
-                       nq, (int32_t)s->nmasks, h->mask_q.as<int32_t>());
-    HIP_TRY(hipGetLastError());
-    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
-    return search_dev(h, nq, d_queries, K, w, d_out_ids, d_out_dists, d_out_counts, nullptr, &ma);
+    return search_masked_entry(h, s, SearchCall{nq, 0, K, w, d_queries, d_out_ids, d_out_dists, d_out_counts}, d_mask_of_query, false);
 } IVF_CATCH
 
 int ivfadc_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *queries, int K, int w, const int32_t *mask_of_query,
                          uint32_t *out_ids, float *out_dists, int32_t *out_counts)
 try {
     HandleLock lk_(h);
-    TRY(check_masked_args(h, s, nq, K, w));
-    if (nq == 0) return IVFADC_OK;
-    if (!queries || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
-    if (mask_of_query)   // before any launch
-        for (int64_t q = 0; q < nq; ++q)
-            if (mask_of_query[q] < -1 || mask_of_query[q] >= s->nmasks)
-                return fail(IVFADC_ERR_INVALID, "query %lld: mask %d is outside [-1, %d)", (long long)q, mask_of_query[q], s->nmasks);
-    TRY(set_device(h));
-    TRY(h->mask_q.ensure((size_t)nq * 4));
-    if (mask_of_query) TRY(h2d_copy(h->mask_q.p, mask_of_query, (size_t)nq * 4, h->stream));
-    else HIP_TRY(hipMemsetAsync(h->mask_q.p, 0, (size_t)nq * 4, h->stream));
-    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
-    const int rc = search_enqueue(h, nq, queries, K, w, out_ids, out_dists, out_counts, nullptr, nullptr, &ma);
-    if (rc != IVFADC_OK) {   // whatever was enqueued before the failure ends first
-        const std::string msg = g_err;
-        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
-        return rc;
-    }
-    return search_finish(h, nq, K, out_ids, out_dists, out_counts);
+    return search_masked_entry(h, s, SearchCall{nq, 0, K, w, queries, out_ids, out_dists, out_counts}, mask_of_query, true);
 } IVF_CATCH
 
 // a 16-bit handle refuses the uint8_t entries, an 8-bit handle the _u16 ones
@@ -3460,7 +3446,7 @@ try {
         h->my_ticket = t;
     }
     struct Reset { ivfadc_index *h; ~Reset() { h->dev_entry = false; } } reset_{h};   // (also when an exception unwinds into IVF_CATCH)
-    return search_dev(h, nq, d_queries, K, w, d_out_ids, d_out_dists, d_out_counts);
+    return search_dev(h, SearchCall{nq, h->d, K, w, d_queries, d_out_ids, d_out_dists, d_out_counts});
 } IVF_CATCH
 
 // ---- list-partitioned multi-GPU mode: strong scaling of a FIXED global batch --------------------------------------------------------------
@@ -3490,7 +3476,7 @@ try {
     if (h->part_n < 2) return fail(IVFADC_ERR_STATE, "ivfadc_set_list_partition(h, nparts >= 2, part) first");
     h->partial_keys = d_keys;
     h->partial_nq = -1;
-    const int rc = search_dev(h, nq, d_queries, K, w, nullptr, nullptr, d_counts);
+    const int rc = search_dev(h, SearchCall{nq, h->d, K, w, d_queries, nullptr, nullptr, d_counts});
     h->partial_keys = nullptr;
     if (rc == IVFADC_OK) { h->partial_nq = nq; h->partial_w = w; h->partial_K = K; }
     return rc;
@@ -3507,12 +3493,7 @@ static int merge_partials_dev(ivfadc_t *h, int64_t nq, int K, int nparts, const 
     const size_t mlds = small_k ? 0 : (size_t)4 * cap * 8;
     const u32 *idp = h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>();
     if (mlds > (size_t)(32 << 10)) { int occ_unused = 0; TRY(fn_occupancy(h, (const void *)partial_merge_kernel<false>, mlds, occ_unused, false)); }
-    if (small_k)
-        hipLaunchKernelGGL(partial_merge_kernel<true>, dim3((unsigned)((nq + 3) / 4)), dim3(256), mlds, h->stream, (int)nq, h->partial_w, K, cap, nparts,
-                           (const u64 *)d_keys, stride_u64, (const int *)d_counts, stride_i32, h->probe_list.as<int>(), h->probe_base.as<u32>(),
-                           h->list_pos.as<int64_t>(), idp, d_ids, d_dists, d_out_counts);
-    else
-        hipLaunchKernelGGL(partial_merge_kernel<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), mlds, h->stream, (int)nq, h->partial_w, K, cap, nparts,
+    hipLaunchKernelGGL(small_k ? partial_merge_kernel<true> : partial_merge_kernel<false>, dim3((unsigned)((nq + 3) / 4)), dim3(256), mlds, h->stream, (int)nq, h->partial_w, K, cap, nparts,
                            (const u64 *)d_keys, stride_u64, (const int *)d_counts, stride_i32, h->probe_list.as<int>(), h->probe_base.as<u32>(),
                            h->list_pos.as<int64_t>(), idp, d_ids, d_dists, d_out_counts);
     HIP_TRY(hipGetLastError());
@@ -3562,78 +3543,77 @@ static int ingest_rows(ivfadc_index *h, hipStream_t s, const void *src, void *ds
 }
 
 // host-pointer search in two halves so several handles (devices) can be in flight at once (ivfadc_mg_search)
-// pre_lists / pre_dcs (host, validated by the caller): the probes of ivfadc_search_preassigned
-static int search_enqueue(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists, int32_t *out_counts,
-                          const int32_t *pre_lists = nullptr, const float *pre_dcs = nullptr, const MaskArgs *mask = nullptr)   // mask: ivfadc_search_masked
+// hc: this handle's whole batch as a host entry has it: queries, results and supplied probes (validated by the caller) in host memory,
+// mask rows on the device already (stage_mask_numbers)
+static int search_enqueue(ivfadc_t *h, const SearchCall &hc)
 try {
     TRY(set_device(h));
     h->dev_entry = false;
     const double t0 = now_us();
+    const int64_t nq = hc.nq;
     const size_t qbytes = (size_t)nq * h->d * 4;
-    const size_t idb = (size_t)nq * K * 4, cb = (size_t)nq * 4;
-    const size_t obytes = 2 * idb + cb;
+    const size_t idb = (size_t)nq * hc.K * 4, cb = (size_t)nq * 4;
     h->hstats.calls++;
     h->hstats.batches++;
-    const float *src = queries;
-    if (host_known(queries, qbytes)) {
+    const float *src = hc.q;
+    if (host_known(hc.q, qbytes)) {
         h->hstats.queries_direct++;
     } else {
         TRY(h->pin_in.ensure(qbytes));
-        memcpy(h->pin_in.p, queries, qbytes);
+        memcpy(h->pin_in.p, hc.q, qbytes);
         src = (const float *)h->pin_in.p;
     }
     const double t1 = now_us();
     if (h->dirty) TRY(upload_lists(h));
-    const float *d_q = src;
+    SearchCall c = hc;   // the same call in device terms
+    c.whole_batch = true;
+    c.q = src;
     static const bool no_zero_copy = getenv("IVFADC_NO_ZERO_COPY") != nullptr;
-    if (!no_zero_copy && !pre_lists && !mask && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, K, w)) {
+    if (!no_zero_copy && !hc.pre() && !hc.masked() && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, hc.K, hc.w)) {
         // the latency path: a handful of rows, read in place by the two launches (a few KB over PCIe; no ingest step in the chain)
         h->hstats.zero_copy++;
     } else {
         TRY(h->q_stage.ensure(qbytes));
         TRY(ingest_rows(h, h->stream, src, h->q_stage.p, qbytes));
-        d_q = h->q_stage.as<float>();
+        c.q = h->q_stage.as<float>();
     }
-    uint32_t *oi = out_ids;
-    float *od = out_dists;
-    int32_t *oc = out_counts;
-    h->hc_out_direct = host_known(out_ids, idb) && host_known(out_dists, idb) && host_known(out_counts, cb);
+    h->hc_out_direct = host_known(hc.ids, idb) && host_known(hc.dists, idb) && host_known(hc.counts, cb);
     if (h->hc_out_direct) {
         h->hstats.results_direct++;
     } else {
-        TRY(h->pin_out.ensure(obytes));
+        TRY(h->pin_out.ensure(2 * idb + cb));
         uint8_t *po = (uint8_t *)h->pin_out.p;
-        oi = (uint32_t *)po;
-        od = (float *)(po + idb);
-        oc = (int32_t *)(po + 2 * idb);
+        c.ids = (uint32_t *)po;
+        c.dists = (float *)(po + idb);
+        c.counts = (int32_t *)(po + 2 * idb);
     }
-    if (pre_lists) {
-        const size_t pb = (size_t)nq * w * 4;
+    if (hc.pre()) {
+        const size_t pb = (size_t)nq * hc.w * 4;
         TRY(h->pre_list.ensure(pb));
         TRY(h->pre_dc.ensure(pb));
-        TRY(h2d_copy(h->pre_list.p, pre_lists, pb, h->stream));
-        TRY(h2d_copy(h->pre_dc.p, pre_dcs, pb, h->stream));
-        const PreProbes pre{h->pre_list.as<int>(), h->pre_dc.as<float>()};
-        TRY(search_dev(h, nq, d_q, K, w, oi, od, oc, &pre));
-    } else
-    TRY(search_dev(h, nq, d_q, K, w, oi, od, oc, nullptr, mask));
+        TRY(h2d_copy(h->pre_list.p, hc.pre_list, pb, h->stream));
+        TRY(h2d_copy(h->pre_dc.p, hc.pre_dc, pb, h->stream));
+        c.pre_list = h->pre_list.as<int>();
+        c.pre_dc = h->pre_dc.as<float>();
+    }
+    TRY(search_dev(h, c));
     h->hstats.stage_in_us += t1 - t0;
     h->hstats.enqueue_us += now_us() - t1;
     return IVFADC_OK;
 } IVF_CATCH
 
-static int search_finish(ivfadc_t *h, int64_t nq, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+static int search_finish(ivfadc_t *h, const SearchCall &hc)
 try {
     TRY(set_device(h));
     const double t0 = now_us();
     TRY(wait_stream(h));
     const double t1 = now_us();
     if (!h->hc_out_direct) {
-        const size_t idb = (size_t)nq * K * 4, cb = (size_t)nq * 4;
+        const size_t idb = (size_t)hc.nq * hc.K * 4, cb = (size_t)hc.nq * 4;
         const uint8_t *hout = (const uint8_t *)h->pin_out.p;
-        memcpy(out_ids, hout, idb);
-        memcpy(out_dists, hout + idb, idb);
-        memcpy(out_counts, hout + 2 * idb, cb);
+        memcpy(hc.ids, hout, idb);
+        memcpy(hc.dists, hout + idb, idb);
+        memcpy(hc.counts, hout + 2 * idb, cb);
     }
     h->hstats.wait_us += t1 - t0;
     h->hstats.stage_out_us += now_us() - t1;
@@ -3647,15 +3627,9 @@ try {
     TRY(check_search_args(h, nq, K, w));
     if (nq == 0) return IVFADC_OK;
     if (!queries || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
-    const int rc = search_enqueue(h, nq, queries, K, w, out_ids, out_dists, out_counts);
-    if (rc != IVFADC_OK) {
-        // whatever was enqueued before the failure may still be writing the staging buffers (or the caller's arrays): it ends first
-        const std::string msg = g_err;
-        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
-        return rc;
-    }
-    return search_finish(h, nq, K, out_ids, out_dists, out_counts);
+    const SearchCall hc{nq, h->d, K, w, queries, out_ids, out_dists, out_counts};
+    const int rc = search_enqueue(h, hc);
+    return rc != IVFADC_OK ? finish_entry(h, rc) : search_finish(h, hc);
 } IVF_CATCH
 
 // ---- range search (include/ivfadc_hip.h: "RANGE search"; no reference counterpart) -------------------------------------------------
@@ -3686,97 +3660,56 @@ static int check_range_args(ivfadc_index *h, int64_t nq, const float *queries, c
     return IVFADC_OK;
 }
 
-// the way out of the four range entries once the device has been touched: whatever was enqueued before a failure ends first
-static int range_sync_after_failure(ivfadc_index *h, int rc)
+// The four range entries.  s null: no query is filtered; else h is the index s was made from, unchanged since, or a plain view of it.
+// host: queries, radii and mask numbers lie in host memory, and go to q_stage / rng_radii / mask_q on the handle's stream.
+static int range_entry(ivfadc_index *h, const ivfadc_maskset *s, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
+                       const int32_t *mask_of_query, ivfadc_range_result_t **out, bool host, bool masked_entry)
 {
-    if (rc != IVFADC_OK) {
-        const std::string msg = g_err;
-        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
+    TRY(check_range_args(h, nq, queries, radii, host ? radii : nullptr, w, max_total, out, masked_entry, !s && mask_of_query));
+    if (s) TRY(check_mask_link(h, s, "ivfadc_range_search_masked"));
+    if (s && host) TRY(check_mask_numbers(s, nq, mask_of_query));
+    if (s || host) TRY(set_device(h));
+    SearchCall c{nq, h->d, 0, w, queries, nullptr, nullptr, nullptr, radii};   // (no K, no result rows: the result is allocated once the totals are known)
+    int rc = IVFADC_OK;
+    if (host) {
+        const size_t qbytes = (size_t)nq * h->d * 4, rbytes = (size_t)nq * 4;
+        rc = h->q_stage.ensure(std::max<size_t>(qbytes, 16));
+        if (rc == IVFADC_OK) rc = h->rng_radii.ensure(std::max<size_t>(rbytes, 16));
+        if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
+        if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, rbytes, h->stream);
+        c.q = h->q_stage.as<float>(); c.radii = h->rng_radii.as<float>();
     }
-    return rc;
+    if (rc == IVFADC_OK && s) rc = stage_mask_numbers(h, s, mask_of_query, !host, c);
+    if (rc == IVFADC_OK) rc = range_dev(h, c, max_total, out);
+    return finish_entry(h, rc);
 }
 
 int ivfadc_range_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, const float *d_radii, int w, int64_t max_total,
                                ivfadc_range_result_t **out)
 try {
     HandleLock lk_(h);
-    TRY(check_range_args(h, nq, d_queries, d_radii, nullptr, w, max_total, out));
-    return range_sync_after_failure(h, range_dev(h, nq, d_queries, d_radii, w, max_total, out));
+    return range_entry(h, nullptr, nq, d_queries, d_radii, w, max_total, nullptr, out, false, false);
 } IVF_CATCH
 
 int ivfadc_range_search(ivfadc_t *h, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
                         ivfadc_range_result_t **out)
 try {
     HandleLock lk_(h);
-    TRY(check_range_args(h, nq, queries, radii, radii, w, max_total, out));
-    TRY(set_device(h));
-    const size_t qbytes = (size_t)nq * h->d * 4;
-    int rc = h->q_stage.ensure(std::max<size_t>(qbytes, 16));
-    if (rc == IVFADC_OK) rc = h->rng_radii.ensure(std::max<size_t>((size_t)nq * 4, 16));
-    if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, (size_t)nq * 4, h->stream);
-    if (rc == IVFADC_OK) rc = range_dev(h, nq, h->q_stage.as<float>(), h->rng_radii.as<float>(), w, max_total, out);
-    return range_sync_after_failure(h, rc);
+    return range_entry(h, nullptr, nq, queries, radii, w, max_total, nullptr, out, true, false);
 } IVF_CATCH
-
-// h and s of a masked range search: s null (no query is filtered), or h is the index s was made from, unchanged since, or a plain view
-// of it -- check_masked_args's checks under this entry's name.  Behind check_range_args.
-static int check_range_masked_args(ivfadc_index *h, const ivfadc_maskset *s)
-{
-    if (!s) return IVFADC_OK;
-    if (h->is_subset) return fail(IVFADC_ERR_STATE, "ivfadc_range_search_masked: a subset view has lists of its own; search the index the mask set was made from, or a plain view of it");
-    const ivfadc_index *root = h->is_view ? h->view_of : h;   // (check_view_current: the link stands)
-    if (root->serial != s->index_serial) return fail(IVFADC_ERR_STATE, "ivfadc_range_search_masked: the mask set was made from another index");
-    if (root->generation != s->generation) return fail(IVFADC_ERR_STATE, "ivfadc_range_search_masked: the index has changed since the mask set was made: make a new one");
-    return IVFADC_OK;
-}
 
 int ivfadc_range_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, const float *d_radii, int w,
                                       int64_t max_total, const int32_t *d_mask_of_query, ivfadc_range_result_t **out)
 try {
     HandleLock lk_(h);
-    TRY(check_range_args(h, nq, d_queries, d_radii, nullptr, w, max_total, out, true, !s && d_mask_of_query));
-    TRY(check_range_masked_args(h, s));
-    if (!s) return range_sync_after_failure(h, range_dev(h, nq, d_queries, d_radii, w, max_total, out));
-    TRY(set_device(h));
-    int rc = h->mask_q.ensure(std::max<size_t>((size_t)nq * 4, 16));
-    if (rc == IVFADC_OK && nq > 0) {   // clamped into [-1, nmasks): a violated precondition cannot read outside the set
-        hipLaunchKernelGGL(maskset_ingest_kernel, dim3((unsigned)std::min<int64_t>(4096, (nq + 255) / 256)), dim3(256), 0, h->stream, d_mask_of_query,
-                           nq, (int32_t)s->nmasks, h->mask_q.as<int32_t>());
-        if (hipGetLastError() != hipSuccess) rc = fail(IVFADC_ERR_HIP, "maskset_ingest_kernel: the launch failed");
-    }
-    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
-    if (rc == IVFADC_OK) rc = range_dev(h, nq, d_queries, d_radii, w, max_total, out, &ma);
-    return range_sync_after_failure(h, rc);
+    return range_entry(h, s, nq, d_queries, d_radii, w, max_total, d_mask_of_query, out, false, true);
 } IVF_CATCH
 
 int ivfadc_range_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *queries, const float *radii, int w,
                                int64_t max_total, const int32_t *mask_of_query, ivfadc_range_result_t **out)
 try {
     HandleLock lk_(h);
-    TRY(check_range_args(h, nq, queries, radii, radii, w, max_total, out, true, !s && mask_of_query));
-    TRY(check_range_masked_args(h, s));
-    if (s && mask_of_query)   // before any launch
-        for (int64_t q = 0; q < nq; ++q)
-            if (mask_of_query[q] < -1 || mask_of_query[q] >= s->nmasks)
-                return fail(IVFADC_ERR_INVALID, "query %lld: mask %d is outside [-1, %d)", (long long)q, mask_of_query[q], s->nmasks);
-    TRY(set_device(h));
-    const size_t qbytes = (size_t)nq * h->d * 4;
-    int rc = h->q_stage.ensure(std::max<size_t>(qbytes, 16));
-    if (rc == IVFADC_OK) rc = h->rng_radii.ensure(std::max<size_t>((size_t)nq * 4, 16));
-    if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, (size_t)nq * 4, h->stream);
-    if (rc == IVFADC_OK && s) {
-        rc = h->mask_q.ensure(std::max<size_t>((size_t)nq * 4, 16));
-        if (rc == IVFADC_OK && nq > 0) {
-            if (mask_of_query) rc = h2d_copy(h->mask_q.p, mask_of_query, (size_t)nq * 4, h->stream);
-            else if (hipMemsetAsync(h->mask_q.p, 0, (size_t)nq * 4, h->stream) != hipSuccess) rc = fail(IVFADC_ERR_HIP, "hipMemsetAsync failed");
-        }
-    }
-    const MaskArgs ma{s, h->mask_q.as<int32_t>()};
-    if (rc == IVFADC_OK) rc = range_dev(h, nq, h->q_stage.as<float>(), h->rng_radii.as<float>(), w, max_total, out, s ? &ma : nullptr);
-    return range_sync_after_failure(h, rc);
+    return range_entry(h, s, nq, queries, radii, w, max_total, mask_of_query, out, true, true);
 } IVF_CATCH
 
 int ivfadc_range_result_sizes(const ivfadc_range_result_t *r, int64_t *out_nq, int64_t *out_total)
@@ -3835,7 +3768,9 @@ try {
     HandleLock lk_(h);
     TRY(check_coarse_args(h, nq, w));
     if (nq > 0 && (!d_queries || !d_lists || !d_dists)) return fail(IVFADC_ERR_INVALID, "null buffer");
-    return coarse_dev(h, nq, d_queries, w, d_lists, d_dists);
+    SearchCall c{nq, h->d, 0, w, d_queries};
+    c.out_list = d_lists; c.out_dc = d_dists;   // (a coarse call: the queries and where their w probes go)
+    return coarse_dev(h, c);
 } IVF_CATCH
 
 int ivfadc_coarse_search(ivfadc_t *h, int64_t nq, const float *queries, int w, int32_t *out_lists, float *out_dists)
@@ -3850,15 +3785,12 @@ try {
     TRY(h->pre_list.ensure(pb));
     TRY(h->pre_dc.ensure(pb));
     TRY(h2d_copy(h->q_stage.p, queries, qbytes, h->stream));
-    int rc = coarse_dev(h, nq, h->q_stage.as<float>(), w, h->pre_list.as<int32_t>(), h->pre_dc.as<float>());
+    SearchCall c{nq, h->d, 0, w, h->q_stage.as<float>()};
+    c.out_list = h->pre_list.as<int32_t>(); c.out_dc = h->pre_dc.as<float>();
+    int rc = coarse_dev(h, c);
     if (rc == IVFADC_OK) rc = d2h_copy(out_lists, h->pre_list.p, pb, h->stream);
     if (rc == IVFADC_OK) rc = d2h_copy(out_dists, h->pre_dc.p, pb, h->stream);
-    if (rc != IVFADC_OK) {   // whatever was enqueued before the failure ends first
-        const std::string msg = g_err;
-        if (h->stream) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
-    }
-    return rc;
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 // K, w and the handle's state, shared by the two preassigned entries (w is NOT clamped: the probes are nq x w as given)
@@ -3879,8 +3811,9 @@ try {
     TRY(check_preassigned_args(h, nq, K, w));
     if (nq > 0 && (!d_queries || !d_lists || !d_coarse_dists || !d_out_ids || !d_out_dists || !d_out_counts)) return fail(IVFADC_ERR_INVALID, "null buffer");
     h->dev_entry = false;
-    const PreProbes pre{(const int *)d_lists, d_coarse_dists};
-    return search_dev(h, nq, d_queries, K, w, d_out_ids, d_out_dists, d_out_counts, &pre);
+    SearchCall c{nq, h->d, K, w, d_queries, d_out_ids, d_out_dists, d_out_counts};
+    c.pre_list = (const int *)d_lists; c.pre_dc = d_coarse_dists;
+    return search_dev(h, c);
 } IVF_CATCH
 
 int ivfadc_search_preassigned(ivfadc_t *h, int64_t nq, const float *queries, int K, int w, const int32_t *lists, const float *coarse_dists,
@@ -3910,14 +3843,10 @@ try {
                 if (bits & 0x80000000u) return fail(IVFADC_ERR_INVALID, "query %lld, rank %d: negative coarse distance (distances are >= +0)", (long long)q, j);
             }
     }
-    const int rc = search_enqueue(h, nq, queries, K, w, out_ids, out_dists, out_counts, lists, coarse_dists);
-    if (rc != IVFADC_OK) {
-        const std::string msg = g_err;
-        if (h->stream && hipSetDevice(h->device) == hipSuccess) (void)hipStreamSynchronize(h->stream);
-        g_err = msg;
-        return rc;
-    }
-    return search_finish(h, nq, K, out_ids, out_dists, out_counts);
+    SearchCall hc{nq, h->d, K, w, queries, out_ids, out_dists, out_counts};
+    hc.pre_list = (const int *)lists; hc.pre_dc = coarse_dists;
+    const int rc = search_enqueue(h, hc);
+    return rc != IVFADC_OK ? finish_entry(h, rc) : search_finish(h, hc);
 } IVF_CATCH
 
 // the cumulative counters of an internal view that is about to be destroyed stay in its index's totals
@@ -3982,7 +3911,7 @@ try {
     }
     const size_t nbat = start.size();
     h->hstats.batches += (int64_t)nbat;
-    const float *dq = h->q_stage.as<float>();
+    const SearchCall all{total, h->d, K, w, h->q_stage.as<float>(), oi, od, oc};
     const uint64_t base = h->own_token;
     h->own_token += nbat;
     auto token_of = [&](size_t i) { return (base + i + 1) | ((uint64_t)1 << 63); };   // never 0; the library's own numbering
@@ -4121,7 +4050,7 @@ try {
         ln->cur_token = token_of(i);         // batch i's rows, if any stand, were hinted with this very token by the lane's step before
         ln->hint_ev = nullptr;
         if (i + stride < nbat) {
-            ln->hint_q = dq + (size_t)start[i + stride] * h->d;
+            ln->hint_q = all.slice(start[i + stride], cnt[i + stride]).q;
             ln->hint_nq = cnt[i + stride];
             ln->hint_token = token_of(i + stride);
             // the successor's rows are read by the riders of this search's scan launch only: the wait for them goes in front of THAT
@@ -4130,7 +4059,9 @@ try {
             if (i >= stride) TRY(host_wait(ev));
             ln->hint_ev = ev;
         }
-        TRY(search_dev(ln, cnt[i], dq + (size_t)start[i] * h->d, K, w, oi + (size_t)start[i] * K, od + (size_t)start[i] * K, oc + start[i]));
+        SearchCall cb = all.slice(start[i], cnt[i]);
+        cb.whole_batch = true;   // (of its lane's search: the hint names its successor)
+        TRY(search_dev(ln, cb));
     }
     const double t_issued = now_us();
     if (lane2) TRY(wait_stream(lane2));
@@ -4383,12 +4314,13 @@ try {
     if (!queries || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
     const int64_t G = (int64_t)g->dev.size();
     const int d = g->dev[0]->d;
+    const SearchCall all{nq, d, K, w, queries, out_ids, out_dists, out_counts};   // (host memory: every device takes a slice)
     if (g->gather_mode == 0) {
         // enqueue every device's block, then collect: the devices run concurrently
         for (int64_t r = 0; r < G; ++r) {
             const int64_t a = mg_lo(r, nq, G), b = mg_lo(r + 1, nq, G);
             if (b <= a) continue;
-            const int rc = search_enqueue(g->dev[r], b - a, queries + (size_t)a * d, K, w, out_ids + (size_t)a * K, out_dists + (size_t)a * K, out_counts + a);
+            const int rc = search_enqueue(g->dev[r], all.slice(a, b - a));
             if (rc != IVFADC_OK) {
                 // the devices before r (and r itself, up to the failure) are writing the caller's arrays or the staging blocks: they end first
                 const std::string msg = g_err;
@@ -4400,7 +4332,7 @@ try {
         }
         for (int64_t r = 0; r < G; ++r) {
             const int64_t a = mg_lo(r, nq, G), b = mg_lo(r + 1, nq, G);
-            if (b > a) TRY(search_finish(g->dev[r], b - a, K, out_ids + (size_t)a * K, out_dists + (size_t)a * K, out_counts + a));
+            if (b > a) TRY(search_finish(g->dev[r], all.slice(a, b - a)));
         }
         return IVFADC_OK;
     }
@@ -4427,7 +4359,7 @@ try {
             if (b > a) {
                 const size_t qbytes = (size_t)(b - a) * d * 4;
                 TRY(h->q_stage.ensure(qbytes));
-                const float *src = queries + (size_t)a * d;
+                const float *src = all.slice(a, b - a).q;
                 if (!host_known(src, qbytes)) {
                     TRY(h->pin_in.ensure(qbytes));
                     memcpy(h->pin_in.p, src, qbytes);
@@ -4435,7 +4367,7 @@ try {
                 }
                 TRY(ingest_rows(h, h->stream, src, h->q_stage.p, qbytes));
                 uint32_t *o = h->out_ids.as<uint32_t>();
-                TRY(search_dev(h, b - a, h->q_stage.as<float>(), K, w, o, (float *)(o + (size_t)nql * K), (int32_t *)(o + 2 * (size_t)nql * K)));
+                TRY(search_dev(h, SearchCall{b - a, d, K, w, h->q_stage.as<float>(), o, (float *)(o + (size_t)nql * K), (int32_t *)(o + 2 * (size_t)nql * K)}));
             }
             return IVFADC_OK;
         };
@@ -4600,7 +4532,7 @@ try {
         }
     }
     uint32_t *ids = (uint32_t *)d_block;
-    TRY(search_dev(searcher, nq, d_queries, K, w, ids, (float *)(ids + (size_t)nq * K), (int32_t *)(ids + 2 * (size_t)nq * K)));
+    TRY(search_dev(searcher, SearchCall{nq, searcher->d, K, w, d_queries, ids, (float *)(ids + (size_t)nq * K), (int32_t *)(ids + 2 * (size_t)nq * K)}));
     HIP_TRY(hipEventRecord(h->comm_ready, searcher->stream));
     HIP_TRY(hipStreamWaitEvent(h->comm_stream, h->comm_ready, 0));
     RcclApi &api = rccl_api();

@@ -17,6 +17,7 @@
 
 #include "kernels.hip.h"
 #include "maskset_plan.h"
+#include "search_call.h"
 #include "subset_plan.h"
 
 namespace ivf {
@@ -71,6 +72,18 @@ struct MaskView {
     uint64_t W;
     const int32_t *mask_of_query;   // [queries of the sub-batch], every value in [-1, nmasks)
 };
+
+// The one place a MaskView is filled: the set and the mask numbers of the queries of c (host).  No set: words null, which the range and
+// generic kernels read as "no filter".
+inline MaskView mask_view(const SearchCall &c)
+{
+    MaskView mv{};
+    mv.words = c.mask_words;
+    mv.word_off = c.mask_word_off;
+    mv.W = c.mask_W;
+    mv.mask_of_query = c.mask_of_query;
+    return mv;
+}
 
 // the row of query q's mask for list l, or null (no filter)
 static __device__ __forceinline__ const u32 *mask_row(const MaskView &mv, int q, int l)

@@ -288,7 +288,7 @@ inline Plan plan_list_major(const PlanFacts &f, int64_t nq, int K, int w, double
     return plan_chunks(f, nq, w, avg_len, 4096, 1024, pl);
 }
 
-inline Plan make_plan(const PlanFacts &f, int64_t nq, int K, int w, bool pre = false)   // pre: the probes are the caller's (PreProbes): no coarse stage of any kind
+inline Plan make_plan(const PlanFacts &f, int64_t nq, int K, int w, bool pre = false)   // pre: the probes are the caller's (SearchCall::pre_list): no coarse stage of any kind
 {
     Plan pl = plan_begin(f, nq, K, w, pre);
     const double avg_len = (double)f.n / std::max(1, f.kc);

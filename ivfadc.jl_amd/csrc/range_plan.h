@@ -116,6 +116,14 @@ struct Plan {
 // a launch's gridDim.x * blockDim.x stays below 2^32 (HIP refuses the launch otherwise): 2^32 / THREADS - 1 work items of a query
 constexpr int64_t MAX_GRID_X = ((int64_t)1 << 32) / THREADS - 1, MAX_GRID_Y = 65535;
 
+// keys of a sort group (range search and the generic path alike): two key buffers and the sort's scratch, 24 B a key, inside the
+// workspace budget; never fewer than 2^20
+inline int64_t sort_cap_keys(size_t ws_budget)
+{
+    const int64_t cap = (int64_t)(ws_budget / 24);
+    return cap < ((int64_t)1 << 20) ? (int64_t)1 << 20 : cap;
+}
+
 inline Plan make_plan(const Facts &f, int64_t nq, int w)
 {
     Plan p;
@@ -139,8 +147,7 @@ inline Plan make_plan(const Facts &f, int64_t nq, int w)
     if (nq > 0 && nb > nq) nb = nq;
     if (nb < 1) nb = 1;
     p.nb = nb;
-    p.cap_keys = (int64_t)(f.ws_budget / 24);
-    if (p.cap_keys < ((int64_t)1 << 20)) p.cap_keys = (int64_t)1 << 20;
+    p.cap_keys = sort_cap_keys(f.ws_budget);
     p.fits = true;
     return p;
 }

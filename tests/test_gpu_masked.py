@@ -313,6 +313,31 @@ def test_sub_batches_advance_the_mask_numbers(native):
     helpers.assert_same_results(got, exp, what="sub-batched")
 
 
+def test_generic_path_batches_and_sort_groups_advance_the_mask_numbers(native):
+    """The masked generic path cut twice over.  Under the smallest workspace (1 MB) a stage-A batch holds 2^20 / (kc * 20 + w * 12 + 64) =
+    2340 queries at kc = w = 12, and a sort group 2^20 keys -- 536 queries of 1956 probed points each (a rejected point still leaves a
+    key).  2400 queries run as two stage-A batches (2340 + 60), the first in five sort groups: the dump, and with it the mask numbers,
+    start at queries 536, 1072, 1608, 2144 and 2340.  The queries are drawn, not tiled, so that no cut falls on a period of the mask
+    numbers: a slice that forgot to advance them would filter by another query's mask."""
+    stride, K, nq = "u8_m8", mk.K_REG, 2400
+    c = mk.case(stride)
+    g, ms = setup_of(native, stride)
+    pick = np.random.default_rng(536).integers(0, mk.NQ, nq)
+    for cut in (536, 1072, 1608, 2144, 2340):
+        assert mk.MASK_OF_QUERY[pick[cut]] != mk.MASK_OF_QUERY[pick[0]] and not np.array_equal(pick[cut:cut + 60], pick[:60]), cut
+    exp = tuple(x[pick] for x in model_of(stride, K))
+    g.set_workspace_limit(1 << 20)
+    g.set_tuning(-2, 0)
+    try:
+        got = g.search_masked_raw(c.qs[pick], K, ms, mk.MASK_OF_QUERY[pick], w=mk.KC)
+        st = g.get_stats()
+    finally:
+        g.set_tuning(0, 0)
+        g.set_workspace_limit(8 << 30)
+    assert st["last_qg"] == -2, st
+    helpers.assert_same_results(got, exp, what="masked generic path, stage-A batches and sort groups")
+
+
 # ---- 7. life cycle ---------------------------------------------------------------------------------------------------------------------
 def test_life_cycle(native):
     """what each call on a mask set must do (include/ivfadc_hip.h, "h and s")"""
