@@ -783,10 +783,10 @@ qscan_fn_t pick_qscan_lb(int m, int dsub, int pg)
 }
 
 // the plan's LDS figure of these kernels (lb_lds_bytes, scan_layouts.h) is the kernel's own layout: LbCfg<M, DS, PG>::END, and behind it
-// what qscan_body carves -- scnt [4][PG] int, swi [4] u32, sthr [PG][STHR_WORDS] u64, the 768-B copy of the query's probes
-template <int M, int DS, int PG> constexpr size_t lb_kernel_lds = LbCfg<M, DS, PG>::END + 4 * PG * 4 + 4 * 4 + PG * STHR_WORDS * 8 + 768;
+// the tail qscan_body carves (FwTail), whose size does not depend on where it stands
+template <int M, int DS, int PG> constexpr size_t lb_kernel_lds = LbCfg<M, DS, PG>::END + fw_tail(0, PG).end;
 #define X(M_, D_, P_) static_assert(lb_lds_bytes(M_, D_, P_) == lb_kernel_lds<M_, D_, P_>, "the planned LDS bytes of qscan_kernel<M, DS, PG, true, true> are its carve");
-X(48, 16, 1) X(48, 16, 2) X(48, 16, 3) X(48, 16, 4) X(16, 6, 1) X(16, 6, 2) X(16, 6, 3) X(16, 6, 4)
+IVF_LB_SHAPES(X)
 #undef X
 
 template <bool SMALL> scan_fn_t pick_scan_s(int m, int dsub, int qg, bool stripe)
@@ -1700,7 +1700,7 @@ bool sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
     if (off || !h->allow_sq || h->force_qg != 0 || h->u16) return false;
     if (K > 64 || w > 64 || nq > 64 || nq * w > 512) return false;
     if ((h->d & 3) != 0) return false;
-    const size_t lds = scan_lds_bytes(h->m, h->d, 1, 64, true) + 64 + (h->kc <= sq_inside_kc(h) ? (size_t)h->kc * 4 : 0);
+    const size_t lds = sq_lds_bytes(h->m, h->d, h->kc <= sq_inside_kc(h) ? h->kc : 0);
     return lds <= LDS_MAX;
 }
 
@@ -1748,7 +1748,7 @@ int search_small(ivfadc_index *h, const SearchCall &c)
     a.arrive = h->sq_arrive.as<u32>();
     a.out_ids = c.ids; a.out_dists = c.dists; a.out_counts = c.counts;
     a.scanned_points = h->misc.as<u64>();
-    const size_t lds = scan_lds_bytes(h->m, h->d, 1, 64, true) + 64 + (inside ? (size_t)h->kc * 4 : 0);
+    const size_t lds = sq_lds_bytes(h->m, h->d, inside ? h->kc : 0);
     sq_fn_t fn = pick_sq(h->m, h->dsub);
     int occ = 0;
     TRY(fn_occupancy(h, (const void *)fn, lds, occ));

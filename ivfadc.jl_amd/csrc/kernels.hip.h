@@ -290,8 +290,7 @@ template <class S> static __device__ __forceinline__ void sel_absorb(S &sel, con
 //     T: still a bound.  Keys are unique, so the exclusive test (key < bound) loses nothing: no scanned key equals another wave's key,
 //     and a wave's own key that IS T sits in its selector already.
 // Layout: sthr[0 .. QG) bounds, sthr[QG + 4 s + v] quarter key of wave v for slot s; whoever (re)arms sthr[s] for fresh selectors
-// re-arms the slot's quarter keys with it (arm_bound).
-constexpr int STHR_WORDS = 5;   // u64 words per slot
+// re-arms the slot's quarter keys with it (arm_bound).  STHR_WORDS (scan_layouts.h) u64 words per slot.
 template <int QG> static __device__ __forceinline__ void arm_bound(u64 *sthr, int s, u64 t0)
 {
     sthr[s] = t0;
@@ -2627,9 +2626,7 @@ template <int M> static __device__ __forceinline__ u32 relax_bound(u32 hi)
 // instructions per visit -- visited for one or two points at a time it took a third of the SIFT1B-shape scan.  So
 // survivors are PARKED: their code bytes and list position go to a small per-wave buffer in LDS, and the buffer is
 // worked off 64 / M points at a time.  Selection is order-free (k smallest of unique keys), so parking changes nothing
-// but the moment a bound tightens.
-constexpr int CAND_CAP = 16;   // entries per wave
-template <int M> static constexpr int cand_stride() { return M / 4 + 1; }   // dwords: code bytes, list position
+// but the moment a bound tightens.  CAND_CAP entries of cand_stride(M) dwords per wave (scan_layouts.h).
 
 // Reference-order sums of parked points, 64 / M per pass: the lanes of segment c (M consecutive lanes) take entry
 // base + c, lane ii of the segment looks sub-quantizer ii up -- M different stripes per point in ONE ds_read, where a
@@ -2643,7 +2640,7 @@ static __device__ __forceinline__ void drain_parked(const u32 *cbuf, int cnt, co
 {
     static_assert(QG == 4, "striped scan: four queries per code stream");
     constexpr int SHC = stripe_shift<M, QG>();
-    constexpr int NS = 64 / M, ES = cand_stride<M>();
+    constexpr int NS = 64 / M, ES = cand_stride(M);
     const int seg = lane / M, ii = lane & (M - 1);
     for (int base = 0; base < cnt; base += NS) {   // uniform
         const int e = base + seg;
@@ -2697,8 +2694,7 @@ static __device__ __forceinline__ void drain_parked(const u32 *cbuf, int cnt, co
 // X = (0x8000 | T_s) - sum_s per field has bit 15 set iff sum_s <= T_s and never borrows (sum_s <= 32760 < 2^15 + T_s).  What passes is
 // parked and gets its reference-order float sum from the f32 tables exactly as before (drain_parked): results stay bit-identical
 // (tests/test_gpu_parity.py::test_integer_filter_extremes: outlier codewords, zero / denormal / huge tables, dc far above the tables).
-constexpr u32 QF_OFF = 8u * 256u * 4u * 4u;   // the 16-bit table sits right behind the m = 8, QG = 4 float tables (32 KB)
-constexpr u32 QF_BYTES = 256u * 64u;
+// QF_OFF, QF_BYTES: scan_layouts.h.
 
 // all 256 threads, after the float tables are complete (caller barriers before and after): per-query maxima -> inv -> fields.
 // scratch: 8 floats of LDS (the residual area is free once the tables are built): [0..3] maxima (as bits), [4..7] inv
@@ -2774,7 +2770,7 @@ static __device__ __forceinline__ void striped_scan_step(const CodeRegs<M, ppl_o
     using CR = CodeRegs<M, ppl_of<M, QG>()>;
     constexpr int PPL = CR::PPL;
     constexpr int SHC = stripe_shift<M, QG>();
-    constexpr int ES = cand_stride<M>();
+    constexpr int ES = cand_stride(M);
     u32 pw[PPL][M / 4], rw[PPL][M / 4];
     u64 fm[PPL], anym = 0;
     if constexpr (QF) {
@@ -2906,7 +2902,7 @@ static __device__ __forceinline__ void striped_scan_step(const CodeRegs<M, ppl_o
 }
 
 // Striped counterpart of scan_range (list-major kernel, striped tables at LDS offset tab_off).  cbuf: CAND_CAP entries of
-// cand_stride<M>() dwords per wave.
+// cand_stride(M) dwords per wave.
 template <int M, int QG, bool QF, class S>
 static __device__ __forceinline__ void striped_scan_range(u32 tab_off, const uint8_t *cbase, u32 p0, u32 p1, const float (&dc)[QG],
                                                           const u32 (&sbase)[QG], int nvalid, S (&sel)[QG], int K, int wv, int lane,
@@ -2983,32 +2979,68 @@ static __device__ __forceinline__ void scan_pair(u32 toff0, u32 toff1, const uin
     }
 }
 
-// LDS carve shared by both scan kernels:
-//   tab    [m][256][QG] f32   (after the scan its first bytes are reused as the exchange area)
-//   resid  [d][QG] f32
-//   selbuf [4][QG][cap] u64   (only when !SMALL)
-//   scnt   [4][QG] int, swi [4] u32
-// Exchange area (SMALL): xch[4][QG][64] u64 = 2 KB * QG, always <= the table size (m KB * QG).
+// LDS carve of the four-wave scan kernels: pointers to the regions of FwLds / FwTail (scan_layouts.h: the layout and its sizes are there,
+// and the plan's scan_lds_bytes is the same layout's end).  The exchange area is the LDS selectors' own buffers, or with register
+// selectors (SMALL) xch [4][QG][64] u64 over the tables.  The struct stays at these eight members: with any more of them the list-major
+// kernels come out with other registers and more instructions (measured), so the rest of the tail has its own struct, LdsProbes.
 struct LdsCarve {
     float *tab, *resid;
     u64 *selbuf, *xch;
-    int *scnt;
+    int *scnt;   // where FwTail begins
     u32 *swi;
     u64 *sthr;   // [QG] workgroup-shared thresholds
     int xcap;
 };
 
+// FwTail's probe area: the query's probes at fw_probe_entries(w) entries each (s_len, s_coff: the 32-entry layout only), and the scratch
+// words behind the 32-entry arrays
+struct LdsProbes {
+    int *s_list;
+    float *s_dc;
+    u32 *s_base, *s_len, *s_coff;
+    u64 *wbound;
+    u32 *ccnt;
+    int *flag;
+};
+
+// The tail's pointers are constant offsets (FwTail from its own start: QG is a template constant) from where it begins, LdsCarve::scnt.
+// These helpers take that pointer by value: with the struct passed by reference the kernels come out with other registers (measured).
+template <int QG>
+static __device__ __forceinline__ LdsProbes carve_probes(int *tail, bool cached)
+{
+    constexpr FwTail T = fw_tail(0, QG);
+    unsigned char *base = (unsigned char *)tail;
+    const int PW = cached ? FW_PROBES_CACHED : FW_PROBES_WIDE;
+    LdsProbes p;
+    p.s_list = (int *)(base + T.probes);
+    p.s_dc = (float *)(p.s_list + PW);
+    p.s_base = (u32 *)(p.s_dc + PW);
+    p.s_len = p.s_base + PW;
+    p.s_coff = p.s_len + PW;
+    p.wbound = (u64 *)(base + T.wbound);
+    p.ccnt = (u32 *)(base + T.ccnt);
+    p.flag = (int *)(base + T.flag);
+    return p;
+}
+
+// wave wv's parking buffer (striped list-major kernel)
+template <int QG, int M>
+static __device__ __forceinline__ u32 *carve_park(int *tail, int wv)
+{
+    constexpr FwTail T = fw_tail(0, QG);
+    return (u32 *)((unsigned char *)tail + T.park) + wv * (CAND_CAP * cand_stride(M));
+}
+
 // NSEL = LDS selectors per wave (K > 64 only): one per query of the group in the list-major kernel, ONE in the query-major kernel, whose
-// PG tables all belong to the same query
+// PG tables all belong to the same query.  extra_bytes (a multiple of 16): the m = 8 striped kernel's QF_BYTES.  The regions in front of
+// the tail follow each other as in fw_lds, each as long as the same function says.
 template <int QG, bool SMALL, int NSEL = QG>
 static __device__ __forceinline__ LdsCarve carve_lds(unsigned char *smem, int m, int d, int cap, int extra_bytes = 0)
 {
     LdsCarve c;
     c.tab = (float *)smem;
-    // the table region is never smaller than the exchange area that later aliases it (m == 1); extra_bytes (a multiple of
-    // 16): room behind the tables for the m = 8 list-major kernel's 16-bit filter table
-    c.resid = c.tab + (size_t)(m < 2 ? 2 : m) * 256 * QG + (extra_bytes >> 2);
-    u64 *after = (u64 *)(c.resid + (((size_t)d * QG + 3) & ~(size_t)3));
+    c.resid = c.tab + fw_tab_floats(m, QG) + extra_bytes / 4;
+    u64 *after = (u64 *)(c.resid + fw_resid_floats(d, QG));
     if (SMALL) {
         c.selbuf = nullptr;
         c.xch = (u64 *)smem;
@@ -3018,10 +3050,11 @@ static __device__ __forceinline__ LdsCarve carve_lds(unsigned char *smem, int m,
         c.selbuf = after;
         c.xch = after;
         c.xcap = cap;
-        c.scnt = (int *)(after + (size_t)4 * NSEL * cap);
+        c.scnt = (int *)(after + fw_selbuf_keys(NSEL, cap));
     }
-    c.swi = (u32 *)(c.scnt + 4 * QG);
-    c.sthr = (u64 *)(c.swi + 4);
+    constexpr FwTail T = fw_tail(0, QG);
+    c.swi = (u32 *)((unsigned char *)c.scnt + T.swi);
+    c.sthr = (u64 *)((unsigned char *)c.scnt + T.sthr);
     return c;
 }
 
@@ -3173,9 +3206,7 @@ __global__ __launch_bounds__(256) void scan_kernel(const ScanArgs a)
         // otherwise starve (measured: +4 % on the SIFT1M shape, +1 % on SIFT1B, neutral elsewhere)
         __builtin_amdgcn_s_setprio(3);
         if constexpr (STRIPE)
-            striped_scan_range<M, QG, QF>(0u, cbase, p0, p1, dc, sbase, nvalid, sel, K, wv, lane, cr, L.sthr,
-                                          (u32 *)(L.sthr + STHR_WORDS * QG) + 192 + wv * (CAND_CAP * cand_stride<M>()),   // behind the 768-B probe cache
-                                          L.resid + 4);
+            striped_scan_range<M, QG, QF>(0u, cbase, p0, p1, dc, sbase, nvalid, sel, K, wv, lane, cr, L.sthr, carve_park<QG, M>(L.scnt, wv), L.resid + 4);
         else scan_range<M, QG>(L.tab, 0u, cbase, ix.cs, m, p0, p1, dc, sbase, nvalid, sel, K, wv, lane, cr, L.sthr);
         __builtin_amdgcn_s_setprio(0);
 
@@ -3404,9 +3435,10 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
         L.selbuf = nullptr;
         L.xch = (u64 *)smem_raw;
         L.xcap = 64;
+        constexpr FwTail T = fw_tail(0, PG);
         L.scnt = (int *)(smem_raw + C::END);
-        L.swi = (u32 *)(L.scnt + 4 * PG);
-        L.sthr = (u64 *)(L.swi + 4);
+        L.swi = (u32 *)((unsigned char *)L.scnt + T.swi);
+        L.sthr = (u64 *)((unsigned char *)L.scnt + T.sthr);
     }
 
     WSel<SMALL> sel[1];
@@ -3417,17 +3449,16 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
     const int *prow_list = a.probe_list + (size_t)q * w;
     const float *prow_dc = a.probe_dc + (size_t)q * w;
     const u32 *prow_base = a.probe_base + (size_t)q * w;
-    // LDS copy of the query's probes (768 B after the shared thresholds).  w <= 32: list, coarse distance, visit-order
-    // base, length and code offset (in 256-B units) of every probe, 32 entries each, so a round's bookkeeping never
-    // waits on global memory; the last 128 B are scratch for select_row_short.  32 < w <= 64 (fused top-w only):
-    // list, distance and base, 64 entries each.
+    // LDS copy of the query's probes (FwTail's probe area).  w <= 32: list, coarse distance, visit-order base, length and
+    // code offset (in 256-B units) of every probe, so a round's bookkeeping never waits on global memory; the scratch of
+    // select_row_short behind them.  32 < w <= 64 (fused top-w only): list, distance and base.
     const bool cached = w <= 32;
-    const int PW = cached ? 32 : 64;
-    int *s_list = (int *)(L.sthr + STHR_WORDS * PG);
-    float *s_dc = (float *)(s_list + PW);
-    u32 *s_base = (u32 *)(s_dc + PW);
-    u32 *s_len = s_base + PW;       // cached only
-    u32 *s_coff = s_len + PW;       // cached only
+    const LdsProbes P = carve_probes<PG>(L.scnt, cached);
+    int *s_list = P.s_list;
+    float *s_dc = P.s_dc;
+    u32 *s_base = P.s_base;
+    u32 *s_len = P.s_len;       // cached only
+    u32 *s_coff = P.s_coff;     // cached only
     if (a.cdist) {
         const int Ksel = a.approx ? approx_pool(w) : w;
         WSel<true> ws;
@@ -3438,29 +3469,25 @@ static __device__ __forceinline__ void qscan_body(const QScanArgs &a, unsigned c
         if constexpr (LB && M > 16) {
             // rows of up to 8192 scores through the short-row selection (16 / 32 keys per lane: this kernel has the registers)
             if (Ksel <= SHORT_ROW_MAXK && ix.kc > 2048 && ix.kc <= 8192 && (ix.kc & 3) == 0) {
-                u64 *wbound = (u64 *)(s_list + 160);
-                u32 *ccnt = (u32 *)(s_list + 168);
                 if (ix.kc <= 4096)
-                    have = a.approx ? select_row_short<true, 4>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt)
-                                    : select_row_short<false, 4>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt);
+                    have = a.approx ? select_row_short<true, 4>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, P.wbound, P.ccnt)
+                                    : select_row_short<false, 4>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, P.wbound, P.ccnt);
                 else
-                    have = a.approx ? select_row_short<true, 8>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt)
-                                    : select_row_short<false, 8>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt);
+                    have = a.approx ? select_row_short<true, 8>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, P.wbound, P.ccnt)
+                                    : select_row_short<false, 8>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, P.wbound, P.ccnt);
             }
         }
         if (!have && Ksel <= SHORT_ROW_MAXK && ix.kc <= 2048 && (ix.kc & 3) == 0) {
             // scratch: candidates in the exchange area; bounds + counter in the 128 B behind the five probe arrays
             // (w <= Ksel <= SHORT_ROW_MAXK < 32: the 32-entry layout), which nothing else writes, so late readers are safe
-            u64 *wbound = (u64 *)(s_list + 160);
-            u32 *ccnt = (u32 *)(s_list + 168);
-            have = a.approx ? select_row_short<true>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt)
-                            : select_row_short<false>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, wbound, ccnt);
+            have = a.approx ? select_row_short<true>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, P.wbound, P.ccnt)
+                            : select_row_short<false>(ws, row, ix.kc, Ksel, wv, lane, tid, L.xch, P.wbound, P.ccnt);
         }
         if constexpr (M > 16) {   // wide codes only: in the m = 8 / 16 kernels this path costs 40 VGPRs and a workgroup per CU
         if (!have && a.approx && a.rf.tmin != nullptr) {   // uniform
             // behind the MFMA filter the tile minima are there: wave 0 reads the ~Ksel tiles that can matter instead of
             // four waves streaming the row and merging (HD-shape: 39 k -> 27 k cycles)
-            int *flag = s_list + 170;                      // scratch word in the last 128 B of the probe area
+            int *flag = P.flag;                            // scratch word in the last 128 B of the probe area
             if (wv == 0) {
                 const bool ok = select_row_tiled(ws, row, a.rf.tmin + (size_t)q * a.rf.ntiles, a.rf.ntiles, a.rf.tile_w, ix.kc, Ksel, lane,
                                                  (int *)L.xch);

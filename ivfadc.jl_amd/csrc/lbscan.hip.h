@@ -61,31 +61,7 @@ struct LbView {
     float mu;                // slack of the upper bounds E <= base + (q + 1) / inv + mu N: 2^-13.4 (split) / 2^-9.4 (f16 codewords)
 };
 
-template <int M, int DS, int PG> struct LbCfg {
-    static constexpr int DSP = (DS + 7) & ~7;            // sub-space width in whole 16-byte parts of bf16
-    static constexpr int NP = DSP / 4;                   // parts per label: DSP hi + DSP lo bf16
-    static constexpr int NCH = DSP / 4;                  // 4-wide k-chunks of the MFMA
-    static constexpr u32 TS = (u32)M * 256u + 32u;       // one probe's u8 table; + 32 B: the PG tables start 8 banks apart
-    static constexpr u32 TAB_BYTES = (PG * TS + 15u) & ~15u;
-    static constexpr int DSR = (DS + 3) & ~3;            // a sub-space row of the f32 residuals, padded with zeros to whole 16-byte groups
-    static constexpr u32 R_OFF = TAB_BYTES;              // f32 residuals r = q - c of the round's probes [PG][M][DSR] (coarsequantizers.jl:40-45)
-    static constexpr u32 R_BYTES = (u32)PG * M * DSR * 4u;
-    static constexpr u32 CST_OFF = R_OFF + R_BYTES;      // f32 [M][PG]: ||r_ii||^2
-    static constexpr u32 BS_OFF = CST_OFF + (u32)M * PG * 4u;   // f32 [M][PG]: base
-    static constexpr u32 PC_OFF = BS_OFF + (u32)M * PG * 4u;    // per probe: inv[4], sbase[4], range max bits[4], effective length[4]
-    static constexpr u32 PP_OFF = PC_OFF + 128u;         // (+ nn[4]: sum over sub-quantizers of max ||cb||^2 + ||r_ii||^2, for the upper bound)
-    static constexpr u32 LQ_OFF = PP_OFF + 256u;         // per probe of the QUERY (w <= 32): inv[32], sbase[32] -- the pool outlives a round
-    static constexpr u32 PARK_OFF = LQ_OFF + (u32)M * DS * 4u;   // f32 query [M * DS]
-    static constexpr int ES = M / 4 + 2;                 // parked entry: code dwords, visit order, (integer sum << 8 | probe of the query)
-    static constexpr int PCAP = PG >= 4 ? 54 : 16;       // entries per wave (two workgroups per CU at PG = 4: LDS to spare)
-    static constexpr u32 PARK_BYTES = 4u * PCAP * ES * 4u;
-    static constexpr u32 UB_OFF = PARK_OFF + PARK_BYTES; // u64 [4][64]: the waves' upper-bound keys, exchanged at the round boundaries
-    static constexpr u32 END = UB_OFF + 4u * 64u * 8u;   // scnt[4], swi[4], sthr, probe cache follow (qscan_kernel)
-    static_assert(M % 4 == 0 && M <= 64, "four sub-quantizer groups per parked point; 64 * 255 < 2^15");
-    static_assert(DS % 2 == 0, "8-byte rows of the f32 codewords / centroid slices at least");
-    static_assert(M + DS <= 120, "scan test: (m + dsub + 4) u <= 2^-17");
-    static_assert(PG >= 1 && PG <= 4, "one MFMA column per probe");
-};
+// LbCfg<M, DS, PG>, the rounds' LDS layout: scan_layouts.h
 
 // (byte BI of dw) + add in one VALU instruction
 template <int BI> static __device__ __forceinline__ u32 sdwa_byte_add(u32 dw, u32 add)

@@ -2,8 +2,9 @@
 // they are instantiated for, the limits their index arithmetic sets.  Plain C++ (no HIP type), so the plan compiles and runs without
 // a GPU (tests/c/plan_check.cpp); the kernel headers include this file and read the very same names, namespace ivf:
 //   wg8scan.hip.h   W8_*, W8Lds, w8_ds_ok           nfscan.hip.h    NF_*, NfLds
-//   u16scan.hip.h   U16_*, u16_*_lds_bytes          lbscan.hip.h    LbCfg (lb_lds_bytes restates its END: asserted in ivfadc_hip.hip)
-//   kernels.hip.h   carve_lds (scan_lds_bytes restates it: see there)
+//   u16scan.hip.h   U16_*, u16_*_lds_bytes          lbscan.hip.h    LbCfg (lb_lds_bytes: its END and the four-wave tail)
+//   kernels.hip.h   carve_lds: FwLds / FwTail, whose end scan_lds_bytes returns (the carve adds up the lengths FwLds is made of and takes
+//                   the tail's offsets from fw_tail)                   smallq.hip.h    SqLds (sq_lds_bytes)
 #pragma once
 
 #include <cstddef>
@@ -132,46 +133,150 @@ static inline size_t u16_direct_wide_lds_bytes(int m, int dsub, int qg, int cap)
     return (size_t)U16_P * m * (((size_t)dsub + 3) & ~(size_t)3) * 4 + (size_t)4 * qg * cap * 8 + 4 * U16_P * 4 + 16;
 }
 
-// ---- the query-major kernel's matrix-core rounds (lbscan.hip.h, qscan_body<..., LB = true>) ------------------------------------------
-// shapes the matrix-core lower-bound rounds (qscan_kernel<..., LB = true>) are instantiated for
-inline bool lb_shape(int m, int dsub) { return (m == 48 && dsub == 16) || (m == 16 && dsub == 6); }
-
-// LbCfg<M, DS, PG>::END + the tail of qscan_body's carve (scnt, swi, sthr, probe cache): ivfadc_hip.hip asserts the equality for every
-// instantiated (M, DS, PG), next to pick_qscan_lb
-constexpr size_t lb_lds_bytes(int m, int dsub, int pg)
-{
-    size_t b = align_up((size_t)pg * ((size_t)m * 256 + 32), 16);
-    b += (size_t)m * pg * ((dsub + 3) & ~3) * 4;   // f32 residuals of the round's probes (rows padded to 16-byte groups)
-    b += 2 * (size_t)m * pg * 4 + 128 + 256;   // norms, bases, per-probe constants of the round and of the query
-    b += (size_t)m * dsub * 4;              // query
-    b += (size_t)4 * (pg >= 4 ? 54 : 16) * (m / 4 + 2) * 4;   // parking pools (LbCfg::PCAP entries per wave)
-    b += 4 * 64 * 8;                        // upper-bound keys of the four waves
-    b += (size_t)4 * pg * 4 + 16 + (size_t)pg * 40 + 3 * 256;
-    return b;
-}
-
-// ---- the four-wave kernels (kernels.hip.h: scan_kernel, qscan_kernel, sq_kernel) -----------------------------------------------------
+// ---- the four-wave kernels (kernels.hip.h: scan_kernel, qscan_kernel; maskset.hip.h: masked_scan_kernel; smallq.hip.h: sq_kernel) -----
 // shapes the striped list-major kernels exist for (IVF_SHAPES with m = 8 / 16)
 inline bool filt_shape(int m, int dsub) { return (m == 8 && dsub == 16) || (m == 16 && (dsub == 6 || dsub == 8)); }
 
 // the shape the narrow-field list-major kernel exists for (nfscan.hip.h)
 inline bool nf_shape(int m, int dsub) { return m == 8 && dsub == 16; }
 
-// restates carve_lds() in kernels.hip.h and what its callers carve behind it (a comment ties the two: carve_lds hands out pointers at run
-// time and names no end, so there is no constant to assert against without editing it).  stripe: the plan's (Plan::stripe), for the width qg
+constexpr int STHR_WORDS = 5;                 // u64 words per slot of the workgroup-shared bounds: the bound, the four waves' quarter keys (arm_bound)
+constexpr int CAND_CAP = 16;                  // parked points per wave (striped list-major kernel: drain_parked)
+constexpr int cand_stride(int m) { return m / 4 + 1; }   // dwords of a parked point: code bytes, list position
+constexpr u32 QF_OFF = 8u * 256u * 4u * 4u;   // the 16-bit table sits right behind the m = 8, QG = 4 float tables (32 KB)
+constexpr u32 QF_BYTES = 256u * 64u;
+
+// The tail of a four-wave carve (byte offsets), which the matrix-core rounds put behind LbCfg::END as it stands:
+//   scnt [4][qg] int, swi [4] u32, sthr [qg][STHR_WORDS] u64
+//   probes: 768 B, the query-major kernel's LDS copy of the query's probes.  w <= 32: list, coarse distance, visit-order base, length and
+//     code offset, 32 entries each, and behind these five arrays 128 B of scratch -- wbound u64 [4], ccnt u32 [2] and flag of the short-row
+//     and tiled selections; 32 < w <= 64 (fused top-w only): list, distance and base at 64 entries each, which fill the 768 B.  Before the
+//     probes are written the area is refine_probes_wg's scratch (66 ints).
+//   park: the striped list-major kernel's parking buffers, CAND_CAP entries of cand_stride(m) dwords for each of the four waves; sized
+//     for m = 16 (m = 8 leaves its last 512 B unused)
+constexpr size_t FW_PROBE_BYTES = 768;
+constexpr int FW_PROBES_CACHED = 32, FW_PROBES_WIDE = 64;   // entries of a probe array: w <= FW_PROBES_CACHED (five arrays), or up to 64 (three)
+constexpr int fw_probe_entries(int w) { return w <= FW_PROBES_CACHED ? FW_PROBES_CACHED : FW_PROBES_WIDE; }
+constexpr size_t FW_PARK_BYTES = (size_t)4 * CAND_CAP * cand_stride(16) * 4;
+struct FwTail {
+    size_t scnt, swi, sthr, probes, wbound, ccnt, flag, park, end;
+};
+constexpr FwTail fw_tail(size_t base, int qg, bool park = false)
+{
+    FwTail t{};
+    t.scnt = base;
+    t.swi = t.scnt + (size_t)4 * qg * 4;
+    t.sthr = align_up(t.swi + 4 * 4, 8);
+    t.probes = t.sthr + (size_t)qg * STHR_WORDS * 8;
+    t.wbound = t.probes + 5 * 32 * 4;
+    t.ccnt = t.wbound + 4 * 8;
+    t.flag = t.ccnt + 2 * 4;
+    t.park = t.probes + FW_PROBE_BYTES;
+    t.end = t.park + (park ? FW_PARK_BYTES : 0);
+    return t;
+}
+static_assert(fw_tail(0, 1).flag + 4 <= fw_tail(0, 1).park, "the scratch words lie in the 128 B the 32-entry probe arrays leave free");
+static_assert(3 * 64 * 4 == FW_PROBE_BYTES && 66 * 4 <= FW_PROBE_BYTES, "the 64-entry arrays fill the probe area; refine_probes_wg's scratch fits it");
+
+// The whole carve.  The plan takes its end; carve_lds (kernels.hip.h) lets the regions in front of the tail follow each other at the
+// lengths below (fw_tab_floats, fw_resid_floats, fw_selbuf_keys: typed pointer steps, which is what keeps the kernels' code as it was)
+// and places the tail's pointers at fw_tail(0, QG)'s offsets from where it begins; tests/c/scan_lds_check.cpp checks that both agree
+// with these offsets wherever the tail stands:
+//   tab    [m][256][qg] f32, never smaller than 2 x 256 x qg: after the scan its first bytes are the exchange area of the register
+//          selectors, xch [4][qg][64] u64 = 2 KB qg, which m = 1 would not hold
+//   qf     m = 8 striped only (extra = QF_BYTES, at QF_OFF): the 16-bit integer filter table
+//   resid  [d][qg] f32, rounded up to 16 bytes
+//   selbuf [4][nsel][cap] u64, LDS selectors (K > 64: !small) -- nsel = qg in the list-major kernels, 1 in the query-major kernel, whose
+//          qg tables all belong to one query
+struct FwLds {
+    size_t tab, qf, resid, selbuf;
+    FwTail t;
+};
+constexpr size_t fw_tab_floats(int m, int qg) { return (size_t)(m < 2 ? 2 : m) * 256 * qg; }
+constexpr size_t fw_resid_floats(int d, int qg) { return ((size_t)d * qg + 3) & ~(size_t)3; }
+constexpr size_t fw_selbuf_keys(int nsel, int cap) { return (size_t)4 * nsel * cap; }
+constexpr FwLds fw_lds(int m, int d, int qg, int nsel, int cap, bool small, size_t extra = 0, bool park = false)
+{
+    FwLds l{};
+    l.tab = 0;
+    l.qf = fw_tab_floats(m, qg) * 4;
+    l.resid = l.qf + extra;
+    l.selbuf = l.resid + fw_resid_floats(d, qg) * 4;
+    l.t = fw_tail(l.selbuf + (small ? 0 : fw_selbuf_keys(nsel, cap) * 8), qg, park);
+    return l;
+}
+static_assert(fw_lds(8, 128, 4, 4, 64, true, QF_BYTES).qf == QF_OFF, "the filter table's place is behind the m = 8, QG = 4 float tables");
+
+// the plan's figure: the end of that carve.  stripe: the plan's (Plan::stripe), for the width qg; groups of four at m = 8 / 16 get the
+// parking buffers, striped or not
 constexpr size_t scan_lds_bytes(int m, int d, int qg, int cap, bool small, bool list_major = false, bool stripe = false)
 {
-    size_t b = (size_t)(m > 2 ? m : 2) * 256 * qg * 4;
-    b += align_up((size_t)d * qg, 4) * 4;
-    if (!small) b += (size_t)4 * (list_major ? qg : 1) * cap * 8;   // LDS selectors: per wave and query (query-major: one query)
-    b += (size_t)4 * qg * 4 + 16;
-    b = align_up(b, 8) + (size_t)qg * 40;  // workgroup-shared thresholds + the four waves' quarter keys per slot (STHR_WORDS)
-    b += 3 * 256;                           // query-major kernel: LDS copy of the query's probes (see qscan_kernel)
-    if (list_major && qg == 4 && (m == 8 || m == 16))
-        b += 4 * 16 * 5 * 4;                // groups of four at m = 8 / 16 (striped or not): 4 waves x CAND_CAP parked points x <= 5 dwords
-    if (stripe && m == 8)
-        b += 256 * 64;                      // m = 8 striped: the 16-bit integer filter table behind the float tables (QF_BYTES)
-    return b;
+    return fw_lds(m, d, qg, list_major ? qg : 1, cap, small, stripe && m == 8 ? QF_BYTES : 0, list_major && qg == 4 && (m == 8 || m == 16)).t.end;
+}
+
+// sq_kernel (smallq.hip.h): the carve of one query with register selectors; its probes at 64 entries each fill the probe area, and behind
+// them come 64 B of the row selection's scratch -- wbound u64 [4], ccnt u32 [4], the gap to the next 16-byte boundary -- and, where the
+// coarse search runs inside the launch, the row of kc_inside coarse distances (16-byte rows: the selection reads float4)
+constexpr size_t SQ_SCRATCH_BYTES = 64;
+struct SqLds {
+    size_t s_list, s_dc, s_base, wbound, ccnt, row_lo, s_row, end;
+};
+// base: where the carve's tail begins (FwTail::scnt, a multiple of 16)
+constexpr SqLds sq_tail(size_t base, int kc_inside)
+{
+    const FwTail t = fw_tail(base, 1);
+    SqLds s{};
+    s.s_list = t.probes;
+    s.s_dc = s.s_list + 64 * 4;
+    s.s_base = s.s_dc + 64 * 4;
+    s.wbound = t.park;
+    s.ccnt = s.wbound + 4 * 8;
+    s.row_lo = s.ccnt + 4 * 4;
+    s.s_row = align_up(s.row_lo, 16);
+    s.end = s.wbound + SQ_SCRATCH_BYTES + (size_t)kc_inside * 4;
+    return s;
+}
+constexpr SqLds sq_lds(int m, int d, int kc_inside) { return sq_tail(fw_lds(m, d, 1, 1, 64, true).t.scnt, kc_inside); }
+static_assert(sq_tail(0, 0).s_row <= sq_tail(0, 0).end && sq_tail(8, 0).s_row <= sq_tail(8, 0).end, "the row starts inside the scratch block, whatever the gap");
+constexpr size_t sq_lds_bytes(int m, int d, int kc_inside) { return sq_lds(m, d, kc_inside).end; }
+
+// ---- the query-major kernel's matrix-core rounds (lbscan.hip.h, qscan_body<..., LB = true>) ------------------------------------------
+// shapes the matrix-core lower-bound rounds (qscan_kernel<..., LB = true>) are instantiated for, and their instantiations (M, DS, PG)
+inline bool lb_shape(int m, int dsub) { return (m == 48 && dsub == 16) || (m == 16 && dsub == 6); }
+#define IVF_LB_SHAPES(X) X(48, 16, 1) X(48, 16, 2) X(48, 16, 3) X(48, 16, 4) X(16, 6, 1) X(16, 6, 2) X(16, 6, 3) X(16, 6, 4)
+
+template <int M, int DS, int PG> struct LbCfg {
+    static constexpr int DSP = (DS + 7) & ~7;            // sub-space width in whole 16-byte parts of bf16
+    static constexpr int NP = DSP / 4;                   // parts per label: DSP hi + DSP lo bf16
+    static constexpr int NCH = DSP / 4;                  // 4-wide k-chunks of the MFMA
+    static constexpr u32 TS = (u32)M * 256u + 32u;       // one probe's u8 table; + 32 B: the PG tables start 8 banks apart
+    static constexpr u32 TAB_BYTES = (PG * TS + 15u) & ~15u;
+    static constexpr int DSR = (DS + 3) & ~3;            // a sub-space row of the f32 residuals, padded with zeros to whole 16-byte groups
+    static constexpr u32 R_OFF = TAB_BYTES;              // f32 residuals r = q - c of the round's probes [PG][M][DSR] (coarsequantizers.jl:40-45)
+    static constexpr u32 R_BYTES = (u32)PG * M * DSR * 4u;
+    static constexpr u32 CST_OFF = R_OFF + R_BYTES;      // f32 [M][PG]: ||r_ii||^2
+    static constexpr u32 BS_OFF = CST_OFF + (u32)M * PG * 4u;   // f32 [M][PG]: base
+    static constexpr u32 PC_OFF = BS_OFF + (u32)M * PG * 4u;    // per probe: inv[4], sbase[4], range max bits[4], effective length[4]
+    static constexpr u32 PP_OFF = PC_OFF + 128u;         // (+ nn[4]: sum over sub-quantizers of max ||cb||^2 + ||r_ii||^2, for the upper bound)
+    static constexpr u32 LQ_OFF = PP_OFF + 256u;         // per probe of the QUERY (w <= 32): inv[32], sbase[32] -- the pool outlives a round
+    static constexpr u32 PARK_OFF = LQ_OFF + (u32)M * DS * 4u;   // f32 query [M * DS]
+    static constexpr int ES = M / 4 + 2;                 // parked entry: code dwords, visit order, (integer sum << 8 | probe of the query)
+    static constexpr int PCAP = PG >= 4 ? 54 : 16;       // entries per wave (two workgroups per CU at PG = 4: LDS to spare)
+    static constexpr u32 PARK_BYTES = 4u * PCAP * ES * 4u;
+    static constexpr u32 UB_OFF = PARK_OFF + PARK_BYTES; // u64 [4][64]: the waves' upper-bound keys, exchanged at the round boundaries
+    static constexpr u32 END = UB_OFF + 4u * 64u * 8u;   // scnt[4], swi[4], sthr, probe cache follow (qscan_kernel)
+    static_assert(M % 4 == 0 && M <= 64, "four sub-quantizer groups per parked point; 64 * 255 < 2^15");
+    static_assert(DS % 2 == 0, "8-byte rows of the f32 codewords / centroid slices at least");
+    static_assert(M + DS <= 120, "scan test: (m + dsub + 4) u <= 2^-17");
+    static_assert(PG >= 1 && PG <= 4, "one MFMA column per probe");
+};
+// LDS of qscan_kernel<M, DS, PG, true, true>: LbCfg's regions, then the four-wave tail.  (size_t)-1: there is no such kernel
+constexpr size_t lb_lds_bytes(int m, int dsub, int pg)
+{
+#define X(M_, D_, P_) if (m == M_ && dsub == D_ && pg == P_) return fw_tail(LbCfg<M_, D_, P_>::END, P_).end;
+    IVF_LB_SHAPES(X)
+#undef X
+    return ~(size_t)0;
 }
 
 constexpr size_t LDS_MAX = 160 << 10;

@@ -98,14 +98,16 @@ __global__ __launch_bounds__(256) void sq_kernel(const SqArgs a)
     const int q = blockIdx.x / per_q, rem = blockIdx.x - q * per_q;
     const int j = rem / nch, c = rem - j * nch;
     const LdsCarve L = carve_lds<1, true>(smem_raw, m, ix.d, 64);
-    // behind the carve: probes of the query (64 entries each: cell, coarse distance, visit-order base), scratch of the row selection,
-    // then the row of coarse distances
-    int *s_list = (int *)(L.sthr + STHR_WORDS);
-    float *s_dc = (float *)(s_list + 64);
-    u32 *s_base = (u32 *)(s_dc + 64);
-    u64 *wbound = (u64 *)(s_base + 64);          // [4]
-    u32 *ccnt = (u32 *)(wbound + 4);             // [2]: candidate counter, "last arriver" flag
-    float *s_row = (float *)(((size_t)(ccnt + 4) + 15) & ~(size_t)15);   // 16-byte rows: the selection reads float4
+    // behind the carve (SqLds, scan_layouts.h; constant offsets from the tail's start): probes of the query (64 entries each: cell, coarse
+    // distance, visit-order base), scratch of the row selection, then the row of coarse distances
+    constexpr SqLds S = sq_tail(0, 0);
+    unsigned char *tail = (unsigned char *)L.scnt;
+    int *s_list = (int *)(tail + S.s_list);
+    float *s_dc = (float *)(tail + S.s_dc);
+    u32 *s_base = (u32 *)(tail + S.s_base);
+    u64 *wbound = (u64 *)(tail + S.wbound);      // [4]
+    u32 *ccnt = (u32 *)(tail + S.ccnt);          // [2]: candidate counter, "last arriver" flag
+    float *s_row = (float *)(((size_t)(tail + S.row_lo) + 15) & ~(size_t)15);   // S.s_row; 16-byte rows: the selection reads float4
     const float *qv = a.queries + (size_t)q * ix.d;
 
     // ---- coarse distances of the query
