@@ -357,6 +357,43 @@ int ivfadc_range_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, in
 int ivfadc_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w,
                          uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
 
+/* LOCATE and RECONSTRUCT: "what is stored under this id", on the device copy of the lists.
+ * Replaces: the search loop of _pop! (utils.jl:49-55) and _get_quantizer_vector(cq, cluster) + _decode_point(rq, codes) (utils.jl:58-59,
+ * 71-81) for a batch of ids, WITHOUT the removal (pop! = ivfadc_reconstruct of one id, then ivfadc_delete_ids of it).  No host mirror is
+ * involved (csrc/reconstruct_plan.h, csrc/reconstruct.hip.h).
+ * For a requested id v, a stored entry counts only if it lies below its list's length (list_len: spare capacity behind it holds stale rows).
+ *   location        locate(v) = (list l, position p), both 0-based, as the reference's loop finds them: l is the LAST list that holds v (the
+ *                   loop does not break, so later lists overwrite), p is the FIRST position of v within that list (findfirst).  Ids are
+ *                   unique in every index the reference can build; for caller-supplied lists with repeated ids this is still the rule.
+ *   reconstruction  reconstruct(v)[t] = centroid_l[t] + codebooks[ii][c][t - ii * dsub], ii = t / dsub, c = the codeword the stored code of
+ *                   sub-space ii names (an 8-bit code is a LABEL and is translated through code_labels; a 16-bit code likewise at the
+ *                   boundary): ONE IEEE Float32 addition per component, bit-identical to the reference's sum in Float32 -- subnormal,
+ *                   signed-zero and large-magnitude components included.
+ *   rotation        the rotation of an :opq file is NOT applied: _decode_point does not apply it either (utils.jl:71-81).
+ *   absent id       no list holds v: out_list = -1, out_pos = -1, found = 0 and the d floats of the vector are +0.0.  Not an error.
+ *   requests        answered slot by slot, in request order; an id may be requested any number of times.  Ids are unsigned 32-bit numbers
+ *                   everywhere (0xFFFFFFFF is an id).
+ * out_vectors is d x n (vector j at + j * d); out_found (n bytes) may be NULL.
+ * Served: 8-bit and UInt16 handles; plain views (ivfadc_clone_view); subset views (the view's OWN lists: an id the subset dropped is
+ * absent, a kept id is located in the subset's lists); file-loaded handles, :opq included; device-synthesised lists; an index after
+ * push! / delete / shift -- pending list changes (an append that overflowed a list) are laid out first, as a search does.  A view whose
+ * index has changed refuses with IVFADC_ERR_STATE, as for searches; so do a handle that was never given lists and a handle with a list
+ * partition set.
+ * The host entries block.  The _device entries take every pointer in device memory of h's GPU and follow the stream semantics of
+ * ivfadc_search_device: asynchronous on the handle's stream, pair with ivfadc_sync(); at most 2^31 - 1 ids per call.
+ * Argument errors, IVFADC_ERR_INVALID before the handle is looked at or the device is touched, each named in ivfadc_last_error(): null
+ * handle; n < 0; null ids with n > 0; a null output (out_found alone may be NULL).  n == 0 returns IVFADC_OK.
+ * Cost: ONE pass over the stored ids (4 bytes per entry) behind an exact bitmap over the span of the wanted ids, or, for at most 16 384
+ * ids that span more than 2^30 values or whose span the host does not know (_device entries), behind a hashed filter in LDS; then n
+ * workgroups of decode.  A _device call with more ids sizes the bitmap's buffer for the whole id space (512 MB of workspace that stays
+ * with the handle) and zeroes and reads only the ids' own span, which its kernels take from the sorted ids.  The _device entries upload
+ * nothing and wait for nothing: every step is enqueued on the stream (a workspace buffer that must grow is reallocated, as by a search).
+ * Not covered: ivfadc_mg_* handles and the list-partitioned mode.                                                                       */
+int ivfadc_locate(ivfadc_t *h, int64_t n, const uint32_t *ids, int32_t *out_list, int64_t *out_pos);
+int ivfadc_reconstruct(ivfadc_t *h, int64_t n, const uint32_t *ids, float *out_vectors, uint8_t *out_found);
+int ivfadc_locate_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, int32_t *d_out_list, int64_t *d_out_pos);
+int ivfadc_reconstruct_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, float *d_out_vectors, uint8_t *d_out_found);
+
 /* The seam of the reference's knn_search.  index.jl:204-258 calls coarse_search(cq, point, w) once (index.jl:219) and everything after it
  * -- residuals, ADC tables, the list scan seeded with dc, top-K (index.jl:220-257) -- reads only the two vectors it returns;
  * AbstractCoarseQuantizer (coarsequantizers.jl:6) is the reference's one plug-in interface.  The two halves are exported separately, so a

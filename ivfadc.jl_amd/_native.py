@@ -15,6 +15,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
            os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
            os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
+           os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]
@@ -181,6 +182,12 @@ def lib():
     L.ivfadc_range_search_device_masked.argtypes = [vp, vp, C.c_int64, vp, vp, C.c_int, C.c_int64, vp, C.POINTER(vp)]
     for name in ("range_search", "range_search_device", "range_result_sizes", "range_result_copy", "range_result_device", "range_search_masked",
                  "range_search_device_masked"):
+        getattr(L, "ivfadc_" + name).restype = C.c_int
+    L.ivfadc_locate.argtypes = [vp, C.c_int64, u32p, i32p, i64p]
+    L.ivfadc_reconstruct.argtypes = [vp, C.c_int64, u32p, fp, u8p]
+    L.ivfadc_locate_device.argtypes = [vp, C.c_int64, vp, vp, vp]
+    L.ivfadc_reconstruct_device.argtypes = [vp, C.c_int64, vp, vp, vp]
+    for name in ("locate", "reconstruct", "locate_device", "reconstruct_device"):
         getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_set_list_partition.argtypes = [vp, C.c_int, C.c_int]
     L.ivfadc_search_device_partial.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]

@@ -14,6 +14,7 @@
 #include "subset.hip.h"
 #include "maskset.hip.h"
 #include "range.hip.h"
+#include "reconstruct.hip.h"
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
@@ -43,6 +44,7 @@
 #include <rccl/rccl.h>   // types and prototypes only: the library is bound with dlopen (see rccl_api)
 
 #include <rocprim/device/device_segmented_radix_sort.hpp>   // generic path only (after <cstring>: its headers use memset)
+#include <rocprim/device/device_radix_sort.hpp>             // ivfadc_locate_device: the wanted ids, sorted on the device
 
 // Diagnostic (off unless IVFADC_ABORT_TRACE=<file> is set when the library is loaded; tests/conftest.py sets it): a process that dies in
 // abort() -- the HIP runtime after a queue error, glibc after a heap check, an escaped exception -- under a test runner that captures fd 2
@@ -322,6 +324,7 @@ struct Dims {
 // a large quantizer), immutable afterwards; a view aliases the buffers and copies the rest
 struct Quantizers {
     DevBuf centroids, codebooks, codebooks_t, codebooks_p, labels, cnorm;
+    DevBuf label_inv;            // 8-bit handles: label byte -> codeword index, [m][256] (pack::label_inverse; recon_decode_kernel)
     // lower-bound tables on the matrix cores (lbscan.hip.h): bf16 split of the codebook, ||codeword||^2 and the f32 codewords, all in
     // label order, and max ||codeword|| per sub-quantizer; present for the shapes lb_shape() names
     DevBuf lb_split, lb_n2, lb_lab, lb_maxn;
@@ -349,7 +352,7 @@ struct Quantizers {
     std::vector<float> rot;
     template <class F> void each_buf(F f)
     {
-        for (DevBuf *b : {&centroids, &codebooks, &codebooks_t, &codebooks_p, &labels, &cnorm, &lb_split, &lb_n2, &lb_lab, &lb_maxn, &lb_f16, &lb_isc,
+        for (DevBuf *b : {&centroids, &codebooks, &codebooks_t, &codebooks_p, &labels, &cnorm, &label_inv, &lb_split, &lb_n2, &lb_lab, &lb_maxn, &lb_f16, &lb_isc,
                           &nf_n2, &nf_lab, &cent_t, &cent_hi, &cent_lo, &cent_f16, &tl_centres, &tl_off, &tl_rad, &tl_cent, &tl_slot})
             f(*b);
     }
@@ -448,6 +451,9 @@ struct Workspace {
     DevBuf cdist2;
     DevBuf pre_list, pre_dc;   // ivfadc_search_preassigned (host pointers): the caller's probes on the device
     DevBuf mask_q;             // ivfadc_search_masked: the batch's mask numbers on the device, every value in [-1, nmasks)
+    // ivfadc_locate / ivfadc_reconstruct (reconstruct.hip.h): sorted wanted ids, one key per wanted slot, the exact bitmap, the lists' chunk
+    // prefix, rocPRIM scratch, and the host entries' staging of requests and results
+    DevBuf rc_want, rc_best, rc_bitmap, rc_chunk, rc_tmp, rc_req, rc_list, rc_pos, rc_found, rc_vec;
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
@@ -457,7 +463,7 @@ struct Workspace {
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
-                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_req, &rc_list, &rc_pos, &rc_found, &rc_vec, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
                           &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
                           &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
             f(*b);
@@ -2459,6 +2465,7 @@ static int create_quantizers(ivfadc_index *h, const CreateArgs &a)
     TRY(upload(h, h->codebooks_t, pack::codebooks_t(a.codebooks, m, ksub, dsub, dsub == 6 && (m & 1) == 0 && !a.lab16)));
     if (m == 48 && dsub == 16) TRY(upload(h, h->codebooks_p, pack::codebooks_p(a.codebooks, m, ksub, dsub)));
     if (a.lab16) return upload(h, h->labels, a.lab16, (size_t)m * ksub * 2);
+    TRY(upload(h, h->label_inv, pack::label_inverse(a.code_labels, m, ksub)));
     return upload(h, h->labels, a.code_labels, (size_t)m * ksub);
 }
 
@@ -3447,6 +3454,185 @@ try {
     }
     struct Reset { ivfadc_index *h; ~Reset() { h->dev_entry = false; } } reset_{h};   // (also when an exception unwinds into IVF_CATCH)
     return search_dev(h, SearchCall{nq, h->d, K, w, d_queries, d_out_ids, d_out_dists, d_out_counts});
+} IVF_CATCH
+
+// ---- locate / reconstruct (reconstruct_plan.h, reconstruct.hip.h) ----------------------------------------------------
+// "What is stored under this id": the reference's _pop! loop (utils.jl:49-55) and centre + _decode_point (utils.jl:58-59, 71-81) for a batch
+// of ids, on the device copy of the lists -- no host mirror involved, so every handle that can be searched is served.
+
+// the arguments of the four entries, before the handle is looked at and before any device call
+static int check_recon_args(const char *fn, ivfadc_t *h, int64_t n, const uint32_t *ids, const void *out_a, const char *name_a, const void *out_b,
+                            const char *name_b)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "%s: null handle", fn);
+    if (n < 0) return fail(IVFADC_ERR_INVALID, "%s: n = %lld < 0", fn, (long long)n);
+    if (n > 0 && !ids) return fail(IVFADC_ERR_INVALID, "%s: null ids with n > 0", fn);
+    if (!out_a) return fail(IVFADC_ERR_INVALID, "%s: null %s", fn, name_a);
+    if (name_b && !out_b) return fail(IVFADC_ERR_INVALID, "%s: null %s", fn, name_b);
+    return IVFADC_OK;
+}
+
+// the handle's state: a current view, lists, no list partition; pending list changes are laid out first, as a search does
+static int recon_begin(ivfadc_index *h, const char *fn)
+{
+    TRY(check_view_current(h));
+    if (!h->have_lists && !h->dirty) return fail(IVFADC_ERR_STATE, "no inverted lists set");
+    if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "%s: not served in the list-partitioned mode", fn);
+    TRY(set_device(h));
+    if (h->dirty) TRY(upload_lists(h));
+    return IVFADC_OK;
+}
+
+// the way out of the four entries once the device has been touched: finish_entry's drain on failure
+static int recon_exit(ivfadc_index *x, int rc) { return finish_entry(x, rc); }
+
+// d_want: nwant wanted ids in device memory, ascending as unsigned numbers (repeats allowed) -> h->rc_best: one key per slot
+static int locate_sorted(ivfadc_index *h, const uint32_t *d_want, uint64_t nwant, bool span_known, uint32_t want_lo, uint32_t want_hi)
+{
+    hipStream_t s = h->stream;
+    TRY(h->rc_best.ensure(std::max<size_t>(8, (size_t)nwant * 8)));
+    HIP_TRY(hipMemsetAsync(h->rc_best.p, 0, std::max<size_t>(8, (size_t)nwant * 8), s));
+    uint64_t items = 0;
+    for (int64_t len : h->h_len) items += recon::list_chunks((uint64_t)std::max<int64_t>(len, 0));
+    const recon::Plan pl = recon::make_plan(nwant, span_known, want_lo, want_hi, items, (uint64_t)h->ntotal(), h->num_cu);
+    if (pl.mode == recon::MODE_NONE) return IVFADC_OK;
+    // the work items' prefix, from the device's own list_len (== h_len once pending changes are laid out): nothing is uploaded, nothing waited for
+    TRY(h->rc_chunk.ensure(((size_t)h->kc + 1) * 8));
+    hipLaunchKernelGGL(recon_chunk_prefix_kernel, dim3(1), dim3(256), 0, s, h->list_len.as<u32>(), (u32)h->kc, h->rc_chunk.as<uint64_t>());
+    HIP_TRY(hipGetLastError());
+    const u32 *ids = h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>();
+    if (pl.mode == recon::MODE_BITMAP) {
+        TRY(h->rc_bitmap.ensure((size_t)pl.words * 4));
+        if (pl.span_from_want) {
+            hipLaunchKernelGGL(recon_bitmap_zero_kernel, dim3(2048), dim3(256), 0, s, d_want, nwant, h->rc_bitmap.as<u32>());
+            HIP_TRY(hipGetLastError());
+        } else {
+            HIP_TRY(hipMemsetAsync(h->rc_bitmap.p, 0, (size_t)pl.words * 4, s));
+        }
+        const unsigned fill_grid = (unsigned)std::min<uint64_t>(2048, (nwant + 255) / 256);
+        hipLaunchKernelGGL(recon_bitmap_fill_kernel, dim3(fill_grid), dim3(256), 0, s, d_want, nwant, pl.lo, pl.nbits, pl.span_from_want,
+                           h->rc_bitmap.as<u32>());
+        HIP_TRY(hipGetLastError());
+        hipLaunchKernelGGL(recon_locate_kernel<false>, dim3(pl.grid), dim3(256), 0, s, h->rc_chunk.as<uint64_t>(), (u32)h->kc, items,
+                           h->list_pos.as<int64_t>(), h->list_len.as<u32>(), ids, d_want, nwant, pl.lo, pl.nbits, pl.span_from_want,
+                           h->rc_bitmap.as<u32>(), h->rc_best.as<unsigned long long>());
+        HIP_TRY(hipGetLastError());
+        return IVFADC_OK;
+    }
+    hipLaunchKernelGGL(recon_locate_kernel<true>, dim3(pl.grid), dim3(256), 0, s, h->rc_chunk.as<uint64_t>(), (u32)h->kc, items,
+                       h->list_pos.as<int64_t>(), h->list_len.as<u32>(), ids, d_want, nwant, 0u, (uint64_t)0, false, (const u32 *)nullptr,
+                       h->rc_best.as<unsigned long long>());
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+// request order: d_req (n ids, device) against the sorted wanted ids and their keys -> list, position, found (device; any may be null)
+static int recon_resolve(ivfadc_index *h, const uint32_t *d_req, int64_t n, const uint32_t *d_want, uint64_t nwant, int32_t *d_list,
+                         int64_t *d_pos, uint8_t *d_found)
+{
+    const unsigned grid = (unsigned)std::min<int64_t>(2048, (n + 255) / 256);
+    hipLaunchKernelGGL(recon_resolve_kernel, dim3(grid), dim3(256), 0, h->stream, d_req, n, d_want, nwant, h->rc_best.as<unsigned long long>(),
+                       d_list, d_pos, d_found);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+static int recon_decode(ivfadc_index *h, int64_t n, const int32_t *d_list, const int64_t *d_pos, float *d_out)
+{
+    DecodeArgs a{};
+    a.centroids = h->centroids.as<float>();
+    a.codebooks = h->codebooks.as<float>();
+    a.label_inv = h->u16 ? (const uint8_t *)nullptr : h->label_inv.as<uint8_t>();
+    a.codes = h->codes.as<uint8_t>();
+    a.list_codeoff = h->list_codeoff.as<int64_t>();
+    a.d = h->d; a.m = h->m; a.dsub = h->dsub; a.ksub = h->ksub; a.cs = h->cs;
+    if (!h->u16 && !a.label_inv) return fail(IVFADC_ERR_STATE, "the handle has no inverse labels");
+    const unsigned grid = (unsigned)std::min<int64_t>(65536, n);
+    hipLaunchKernelGGL(recon_decode_kernel, dim3(grid), dim3(256), 0, h->stream, a, n, d_list, d_pos, d_out);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+// host entries: the requested ids sorted and made unique on the host (as ivfadc_delete_ids does), everything else on the device.
+// d_list / d_pos / d_found: h->rc_list / rc_pos / rc_found, filled for the n requests.
+static int locate_host(ivfadc_index *h, int64_t n, const uint32_t *ids)
+{
+    std::vector<uint32_t> want(ids, ids + n);
+    std::sort(want.begin(), want.end());
+    want.erase(std::unique(want.begin(), want.end()), want.end());
+    TRY(h->rc_want.ensure(want.size() * 4));
+    TRY(h2d_copy(h->rc_want.p, want.data(), want.size() * 4, h->stream));
+    TRY(h->rc_req.ensure((size_t)n * 4));
+    TRY(h2d_copy(h->rc_req.p, ids, (size_t)n * 4, h->stream));
+    TRY(h->rc_list.ensure((size_t)n * 4));
+    TRY(h->rc_pos.ensure((size_t)n * 8));
+    TRY(h->rc_found.ensure((size_t)n));
+    TRY(locate_sorted(h, h->rc_want.as<u32>(), want.size(), true, want.front(), want.back()));
+    return recon_resolve(h, h->rc_req.as<u32>(), n, h->rc_want.as<u32>(), want.size(), h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(),
+                         h->rc_found.as<uint8_t>());
+}
+
+// device entries: the requested ids are sorted on the device (rocPRIM; repeats stay); every step is enqueued on the handle's stream, nothing
+// is uploaded and nothing waited for (a workspace buffer that has to grow is reallocated, as by any search)
+static int locate_device(ivfadc_index *h, int64_t n, const uint32_t *d_ids, int32_t *d_list, int64_t *d_pos, uint8_t *d_found)
+{
+    if (n > (int64_t)0x7FFFFFFF) return fail(IVFADC_ERR_INVALID, "n = %lld ids in one call (the device entries sort at most 2^31 - 1)", (long long)n);
+    TRY(h->rc_want.ensure((size_t)n * 4));
+    size_t tmp = 0;
+    HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp, d_ids, h->rc_want.as<u32>(), (unsigned)n, 0, 32, h->stream));
+    TRY(h->rc_tmp.ensure(std::max<size_t>(tmp, 16)));
+    HIP_TRY(rocprim::radix_sort_keys(h->rc_tmp.p, tmp, d_ids, h->rc_want.as<u32>(), (unsigned)n, 0, 32, h->stream));
+    TRY(locate_sorted(h, h->rc_want.as<u32>(), (uint64_t)n, false, 0u, 0u));
+    return recon_resolve(h, d_ids, n, h->rc_want.as<u32>(), (uint64_t)n, d_list, d_pos, d_found);
+}
+
+int ivfadc_locate(ivfadc_t *h, int64_t n, const uint32_t *ids, int32_t *out_list, int64_t *out_pos)
+try {
+    TRY(check_recon_args("ivfadc_locate", h, n, ids, out_list, "out_list", out_pos, "out_pos"));
+    HandleLock lk_(h);
+    TRY(recon_begin(h, "ivfadc_locate"));
+    if (n == 0) return IVFADC_OK;
+    int rc = locate_host(h, n, ids);
+    if (rc == IVFADC_OK) rc = d2h_copy(out_list, h->rc_list.p, (size_t)n * 4, h->stream);
+    if (rc == IVFADC_OK) rc = d2h_copy(out_pos, h->rc_pos.p, (size_t)n * 8, h->stream);
+    return recon_exit(h, rc);
+} IVF_CATCH
+
+int ivfadc_reconstruct(ivfadc_t *h, int64_t n, const uint32_t *ids, float *out_vectors, uint8_t *out_found)
+try {
+    TRY(check_recon_args("ivfadc_reconstruct", h, n, ids, out_vectors, "out_vectors", nullptr, nullptr));
+    HandleLock lk_(h);
+    TRY(recon_begin(h, "ivfadc_reconstruct"));
+    if (n == 0) return IVFADC_OK;
+    const size_t vbytes = (size_t)n * h->d * 4;
+    int rc = locate_host(h, n, ids);
+    if (rc == IVFADC_OK) rc = h->rc_vec.ensure(vbytes);
+    if (rc == IVFADC_OK) rc = recon_decode(h, n, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), h->rc_vec.as<float>());
+    if (rc == IVFADC_OK) rc = d2h_copy(out_vectors, h->rc_vec.p, vbytes, h->stream);
+    if (rc == IVFADC_OK && out_found) rc = d2h_copy(out_found, h->rc_found.p, (size_t)n, h->stream);
+    return recon_exit(h, rc);
+} IVF_CATCH
+
+int ivfadc_locate_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, int32_t *d_out_list, int64_t *d_out_pos)
+try {
+    TRY(check_recon_args("ivfadc_locate_device", h, n, d_ids, d_out_list, "out_list", d_out_pos, "out_pos"));
+    HandleLock lk_(h);
+    TRY(recon_begin(h, "ivfadc_locate_device"));
+    if (n == 0) return IVFADC_OK;
+    return recon_exit(h, locate_device(h, n, d_ids, d_out_list, d_out_pos, nullptr));
+} IVF_CATCH
+
+int ivfadc_reconstruct_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, float *d_out_vectors, uint8_t *d_out_found)
+try {
+    TRY(check_recon_args("ivfadc_reconstruct_device", h, n, d_ids, d_out_vectors, "out_vectors", nullptr, nullptr));
+    HandleLock lk_(h);
+    TRY(recon_begin(h, "ivfadc_reconstruct_device"));
+    if (n == 0) return IVFADC_OK;
+    int rc = h->rc_list.ensure((size_t)n * 4);
+    if (rc == IVFADC_OK) rc = h->rc_pos.ensure((size_t)n * 8);
+    if (rc == IVFADC_OK) rc = locate_device(h, n, d_ids, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_out_found);
+    if (rc == IVFADC_OK) rc = recon_decode(h, n, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_out_vectors);
+    return recon_exit(h, rc);
 } IVF_CATCH
 
 // ---- list-partitioned multi-GPU mode: strong scaling of a FIXED global batch --------------------------------------------------------------

@@ -159,6 +159,16 @@ inline NfOperands nf_operands(const float *codebooks, const uint8_t *labels, int
     return o;
 }
 
+// inverse labels of an 8-bit handle (recon_decode_kernel, reconstruct.hip.h): [m][256], slot = the label byte a stored code holds,
+// value = the index of the codeword it names; a byte that is no label of its block maps to 0 (no stored code holds one)
+inline std::vector<uint8_t> label_inverse(const uint8_t *labels, int m, int ksub)
+{
+    std::vector<uint8_t> inv((size_t)m * 256, 0);
+    for (int ii = 0; ii < m; ++ii)
+        for (int c = 0; c < ksub; ++c) inv[(size_t)ii * 256 + labels[(size_t)ii * ksub + c]] = (uint8_t)c;
+    return inv;
+}
+
 // ||c||^2 in double, rounded once: error <= u ||c||^2 (see refine_probes); cmaxn >= max ||centroid||
 struct CentroidNorms {
     std::vector<float> n2;

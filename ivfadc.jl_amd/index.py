@@ -650,6 +650,35 @@ class IVFADCIndex:
         nat.check(nat.lib().ivfadc_search_device(self._h, int(nq), C.c_void_p(q_ptr), int(k), int(w), C.c_void_p(ids_ptr),
                                                  C.c_void_p(dists_ptr), C.c_void_p(counts_ptr)))
 
+    # ---- what is stored under an id (ivfadc_locate / ivfadc_reconstruct: on the device copy of the lists, no host mirror) ----
+    def locate_raw(self, ids):
+        """ids (n,) -> (lists (n,) int32, positions (n,) int64), 0-based; -1 / -1 for an id no list holds."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        n = ids.shape[0]
+        lists = np.full(n, -1, np.int32)
+        pos = np.full(n, -1, np.int64)
+        nat.check(nat.lib().ivfadc_locate(self._h, n, nat.ptr(ids, C.c_uint32), nat.ptr(lists, C.c_int32), nat.ptr(pos, C.c_int64)))
+        return lists, pos
+
+    def reconstruct_raw(self, ids):
+        """ids (n,) -> (vectors (n, d) float32, found (n,) bool): centre + codewords of each stored point; an absent id gives +0.0."""
+        ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+        n = ids.shape[0]
+        vec = np.zeros((n, self.d), np.float32)
+        found = np.zeros(n, np.uint8)
+        nat.check(nat.lib().ivfadc_reconstruct(self._h, n, nat.ptr(ids, C.c_uint32), nat.ptr(vec, C.c_float), nat.ptr(found, C.c_uint8)))
+        return vec, found.astype(bool)
+
+    def locate_device(self, n, ids_ptr, lists_ptr, pos_ptr):
+        """Asynchronous on raw device pointers (ints): n uint32 ids -> n int32 lists, n int64 positions; see ivfadc_locate_device."""
+        nat.check(nat.lib().ivfadc_locate_device(self._h, int(n), C.c_void_p(ids_ptr), C.c_void_p(lists_ptr), C.c_void_p(pos_ptr)))
+
+    def reconstruct_device(self, n, ids_ptr, vectors_ptr, found_ptr=None):
+        """Asynchronous on raw device pointers (ints): n uint32 ids -> n x d float32 (and n found bytes unless found_ptr is None);
+        see ivfadc_reconstruct_device."""
+        nat.check(nat.lib().ivfadc_reconstruct_device(self._h, int(n), C.c_void_p(ids_ptr), C.c_void_p(vectors_ptr),
+                                                      C.c_void_p(found_ptr) if found_ptr else None))
+
 
 def _comm_methods():
     """one-process-per-GPU merge inside the library (ivfadc_comm_*): methods of IVFADCIndex"""
@@ -963,15 +992,28 @@ def _decode_point(ivfadc, codes):
     return out
 
 
+def locate(ivfadc, ids):
+    """Where each id is stored: (lists, positions), 0-based, by the rule of _pop!'s loop (utils.jl:49-55: the last list that holds the
+    id, the first position within it); -1 / -1 for an id no list holds."""
+    return ivfadc.locate_raw(ids)
+
+
+def reconstruct(ivfadc, ids):
+    """The stored points under `ids` as an n x d Float32 array: centre + _decode_point (utils.jl:58-59, 71-81), computed on the device.
+    An id no list holds raises AssertionError naming the first such id."""
+    ids = np.ascontiguousarray(ids, np.uint32).reshape(-1)
+    vec, found = ivfadc.reconstruct_raw(ids)
+    if not found.all():
+        raise AssertionError("id %d is not stored in the index" % int(ids[int(np.argmin(found))]))
+    return vec
+
+
 def _pop(ivfadc, position):
-    """utils.jl:41-68."""
+    """utils.jl:41-68: reconstruct on the device, then delete."""
     n = len(ivfadc)
     assert n > 0, "Cannot pop element from empty index"
-    offsets, codes, ids = ivfadc._lists()
     vecid, shift = (n - 1, 0) if position == "last" else (0, 1)
-    pos = int(np.nonzero(ids == vecid)[0][-1])
-    cluster = int(np.searchsorted(offsets, pos, side="right") - 1)
-    rec = ivfadc._centroids[cluster] + _decode_point(ivfadc, codes[pos])
+    rec = reconstruct(ivfadc, np.array([vecid], np.uint32))[0]
     # deleteat! + _shift_down_inverse_index!(shift): removing id 0 lowers every other id by one, removing the
     # highest id lowers none -- exactly ivfadc_delete_ids' rule, applied in place on the device
     ivfadc._delete_ids(np.array([vecid], np.uint32))

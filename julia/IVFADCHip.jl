@@ -21,7 +21,7 @@ using Distances
 using QuantizedArrays
 import LinearAlgebra
 
-export hip_sync!, hip_release!, hip_subset
+export hip_sync!, hip_release!, hip_subset, hip_locate, hip_reconstruct
 
 # GPU methods for the knn_search hot path; everything else falls through to the CPU methods.
 const LIBIVFADC = get(ENV, "IVFADC_HIP_LIB", "libivfadc_hip.so")
@@ -473,6 +473,36 @@ function knn_search(s::HipSubset{I}, points::Vector{Vector{Float32}}, k::Int; w:
                  (Ptr{Cvoid}, Int64, Ptr{Float32}, Cint, Cint, Ptr{UInt32}, Ptr{Float32}, Ptr{Int32}),
                  s.handle.ptr, nq, q, k, min(w, kc), ids, dists, counts))
     return [I.(ids[1:counts[i], i]) for i in 1:nq], [dists[1:counts[i], i] for i in 1:nq]
+end
+
+# What is stored under a point (ivfadc_locate / ivfadc_reconstruct): the search loop of _pop! (utils.jl:49-55: the LAST list that holds
+# the id, the FIRST position within it) and centre + _decode_point (utils.jl:58-59, 71-81), for a batch of 1-based points, computed on
+# the DEVICE copy of the lists without removing anything.  hip_locate returns (clusters, positions), 1-based, 0 where no list holds the
+# point; hip_reconstruct returns one Vector{Float32} per point and asserts that every point is stored.  The rotation of an :opq index
+# is not applied: the reference's _decode_point does not apply it either.  The library's other two entries, ivfadc_locate_device and
+# ivfadc_reconstruct_device, take device pointers (ids a search left on the GPU become vectors on the GPU, asynchronously on the handle's
+# stream); this shim works on Julia arrays and does not call them.
+function hip_locate(ivfadc::AnyGpuIndex, points::Vector{<:Integer})
+    h = _handle(ivfadc)
+    ids = UInt32.(points .- 1)
+    lists = fill(Int32(-1), length(ids))
+    pos = fill(Int64(-1), length(ids))
+    _check(ccall((:ivfadc_locate, LIBIVFADC), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt32}, Ptr{Int32}, Ptr{Int64}),
+                 h.ptr, length(ids), ids, lists, pos))
+    return Int.(lists) .+ 1, Int.(pos) .+ 1
+end
+
+function hip_reconstruct(ivfadc::AnyGpuIndex, points::Vector{<:Integer})
+    h = _handle(ivfadc)
+    ids = UInt32.(points .- 1)
+    d = size(_centroids(ivfadc.coarse_quantizer), 1)
+    vecs = zeros(Float32, d, length(ids))
+    found = zeros(UInt8, length(ids))
+    _check(ccall((:ivfadc_reconstruct, LIBIVFADC), Cint, (Ptr{Cvoid}, Int64, Ptr{UInt32}, Ptr{Float32}, Ptr{UInt8}),
+                 h.ptr, length(ids), ids, vecs, found))
+    missing_at = findfirst(iszero, found)
+    @assert missing_at === nothing "point $(missing_at === nothing ? 0 : points[missing_at]) is not stored in the index"
+    return [vecs[:, j] for j in 1:length(ids)]
 end
 
 end # module
