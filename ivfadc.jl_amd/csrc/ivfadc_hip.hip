@@ -18,6 +18,7 @@
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
+#include "list_mirror.h"   // the host mirror of the lists, its edits, the label map and the device layout's arithmetic (pure)
 
 #include <algorithm>
 #include <atomic>
@@ -342,10 +343,7 @@ struct Quantizers {
     int tl_G = 0;
     bool tl_tried = false, tl_use = false;
     float tl_eps = 0.f, tl_probe_fraction = -1.f;
-    std::vector<uint8_t> h_label_ok;   // m x 256 validity
-    bool identity_labels = false;
-    std::vector<uint16_t> lab16;       // [m][ksub] labels of a 16-bit handle
-    std::vector<uint32_t> lab_sorted;  // [m][ksub] label << 16 | codeword index, ascending within each block (label -> index lookups)
+    list_mirror::LabelMap labmap;      // code labels <-> codeword indices, on the host (the entries validate and convert through it)
     // the residual quantizer's rotation as loaded from an index file (nrows x nrows, column by column as persistency.jl:62-64 writes it);
     // empty = identity (:pq).  knn_search never reads it (index.jl:204-258): a rotated (:opq) index is SEARCHED as it is; quantize_data --
     // push! / encode -- would need it (third-party arithmetic, unverifiable here), so those entries refuse on such a handle.
@@ -359,34 +357,20 @@ struct Quantizers {
 };
 
 // the inverted lists as the device holds them: a view aliases the buffers and copies the layout; a subset view (ivfadc_clone_subset) OWNS
-// compacted ones of its own, and the scalars here are then the subset's
-struct Lists {
-    int64_t n = 0;
+// compacted ones of its own, and the scalars here are then the subset's.  (DeviceLayout: d_cap, d_pos, d_codeoff)
+struct Lists : list_mirror::DeviceLayout {
     bool have_lists = false;
     bool synthetic = false;
-    bool dirty = false;           // host mirror changed, device copy stale
-    int64_t maxlen = 0;
+    bool dirty = false;           // host mirror changed, device copy stale (StaleGuard)
     DevBuf list_pos, list_len, list_codeoff, codes, ids;
-    std::vector<int64_t> h_len;                  // [kc] points per list (kept for synthetic lists too)
-    std::vector<int64_t> d_cap, d_pos, d_codeoff;   // device layout: capacity, id offset, code byte offset per list
-    int64_t ntotal() const
-    {
-        int64_t t = 0;
-        for (int64_t v : h_len) t += v;
-        return t;
-    }
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&list_pos, &list_len, &list_codeoff, &codes, &ids}) f(*b);
     }
 };
 
-// host mirror: one (codes, ids) pair per list -- the source of truth; the device copy gives every list spare
-// capacity so push! writes in place (re-layout only when a list overflows).  Stays with the index: a view never holds one.
-struct HostMirror {
-    std::vector<std::vector<uint8_t>> hl_codes;  // [kc] len x m bytes
-    std::vector<std::vector<uint32_t>> hl_ids;   // [kc]
-};
+// (the host mirror, list_mirror::ListMirror: one (codes, ids) pair per list -- the source of truth; the device copy gives every list spare
+// capacity so push! writes in place (re-layout only when a list overflows).  Its data stays with the index: a view is given the lengths.)
 
 // every field a setter or an environment switch writes and the planners read: a view starts from its index's, and the second lane of
 // ivfadc_search_batches is given the index's before every use (copy_search_config)
@@ -534,7 +518,8 @@ struct HandleState {
     hipEvent_t pipe_ev_in = nullptr;
 };
 
-struct ivfadc_index : Dims, Quantizers, Lists, HostMirror, SearchConfig, Workspace, HandleState {
+struct ivfadc_index : Dims, Quantizers, Lists, SearchConfig, Workspace, HandleState {
+    list_mirror::ListMirror mirror;   // lengths of every handle; codes and ids of an index (never of a view)
     // every DevBuf of the handle, each group once
     template <class F> void each_buf(F f)
     {
@@ -666,32 +651,35 @@ int ev_fold(ivfadc_index *h)
 }
 
 // ---- device layout of the lists --------------------------------------------------------------
-constexpr size_t CODE_SLACK = 64 << 10;
+using list_mirror::CODE_SLACK;
 
 int code_stride(int m) { return (int)align_up((size_t)m, 4); }   // every kernel variant reads this stride
 
-// capacities -> offsets of every list in the id array and in the code buffer (256-B aligned blocks)
-int layout_from_caps(ivfadc_index *h, size_t &code_bytes, int64_t &id_slots)
+// a list_mirror::Error in the entries' words.  wide: the codes are UInt16; prefix: the loader's "<path>: "
+int mirror_fail(const list_mirror::Error &e, bool wide, const char *prefix = "")
 {
-    const int kc = h->kc;
-    h->d_pos.assign(kc, 0);
-    h->d_codeoff.assign(kc, 0);
-    size_t run = 0;
-    int64_t pos = 0, maxlen = 0, n = 0;
-    for (int l = 0; l < kc; ++l) {
-        h->d_pos[l] = pos;
-        h->d_codeoff[l] = (int64_t)run;
-        pos += h->d_cap[l];
-        run += align_up((size_t)h->d_cap[l] * h->cs, 256);
-        maxlen = std::max(maxlen, h->h_len[l]);
-        n += h->h_len[l];
+    typedef list_mirror::Error E;
+    switch (e.kind) {
+    case E::None: return IVFADC_OK;
+    case E::OffsetsStart: return fail(IVFADC_ERR_INVALID, "offsets[0] must be 0");
+    case E::OffsetsOrder: return fail(IVFADC_ERR_INVALID, "offsets must be non-decreasing (list %d)", (int)e.list);
+    case E::TooManyPoints: return fail(IVFADC_ERR_ASSERT, "index capacity of UInt32 ids exceeded");
+    case E::NullArrays: return fail(IVFADC_ERR_INVALID, "null codes/ids");
+    case E::TooManySlots: return fail(IVFADC_ERR_INVALID, "id array with spare capacity exceeds 2^32 slots");
+    case E::NotALabel:
+        return fail(IVFADC_ERR_INVALID, "%scode %s%d of point %lld is not a label of codebook %d", prefix, wide ? "" : "byte ", e.value,
+                    (long long)e.point, e.codebook);
+    case E::DuplicateLabel: return fail(IVFADC_ERR_INVALID, "%sduplicate label %d in codebook %d", prefix, e.value, e.codebook);
     }
-    if (n > (int64_t)0xFFFFFFFFll) return fail(IVFADC_ERR_ASSERT, "index capacity of UInt32 ids exceeded");
-    if (pos > (int64_t)0xFFFFFFFFll) return fail(IVFADC_ERR_INVALID, "id array with spare capacity exceeds 2^32 slots");
-    h->maxlen = maxlen;
-    h->n = n;
-    code_bytes = run + CODE_SLACK;
-    id_slots = pos;
+    return fail(IVFADC_ERR_INVALID, "list mirror error %d", (int)e.kind);
+}
+
+// h->d_cap -> offsets of every list in the id array and in the code buffer, and the handle's n and maxlen (list_mirror.h)
+int layout_from_caps(ivfadc_index *h, list_mirror::LayoutTotals &tot)
+{
+    TRY(mirror_fail(list_mirror::layout_from_caps(*h, h->mirror.h_len, h->cs, tot), h->u16));
+    h->mirror.maxlen = tot.maxlen;
+    h->mirror.n = tot.n;
     return IVFADC_OK;
 }
 
@@ -699,7 +687,7 @@ int upload_list_tables(ivfadc_index *h)
 {
     const int kc = h->kc;
     std::vector<uint32_t> len32((size_t)kc);
-    for (int l = 0; l < kc; ++l) len32[l] = (uint32_t)h->h_len[l];
+    for (int l = 0; l < kc; ++l) len32[l] = (uint32_t)h->mirror.h_len[l];
     TRY(h->list_pos.ensure((size_t)kc * 8));
     TRY(h->list_len.ensure((size_t)kc * 4));
     TRY(h->list_codeoff.ensure((size_t)kc * 8));
@@ -709,36 +697,38 @@ int upload_list_tables(ivfadc_index *h)
     return IVFADC_OK;
 }
 
+// The device copy of the lists is stale until proven current.  Whoever is about to change the mirror, or the device copy itself, makes
+// one of these FIRST: the handle is marked stale there and then, and current() declares the copy current again only once the device
+// update has been queued and, where its staging is stack-owned, synchronised.  So a failure half-way (allocation, copy, launch) leaves
+// a handle whose next search lays the lists out again from the mirror, never one that searches stale lists; and a mutator that found
+// the copy already stale (!in_place()) edits the mirror only.
+struct StaleGuard {
+    ivfadc_index *h;
+    const bool was_dirty;
+    explicit StaleGuard(ivfadc_index *x) : h(x), was_dirty(x->dirty) { h->dirty = true; }
+    bool in_place() const { return h->have_lists && !was_dirty; }   // the device copy was current: the edit can be repeated on it
+    void current() { h->dirty = false; }
+};
+
 // full re-layout: host mirror -> device, every list gets spare capacity behind it
 int upload_lists(ivfadc_index *h)
 {
-    const int kc = h->kc, m = h->cb, cs = h->cs;
-    h->d_cap.assign(kc, 0);
-    for (int l = 0; l < kc; ++l) h->d_cap[l] = h->h_len[l] + std::max<int64_t>(32, h->h_len[l] / 8);
-    size_t total = 0;
-    int64_t slots = 0;
-    TRY(layout_from_caps(h, total, slots));
-    std::vector<uint8_t> stage(total, 0);
-    std::vector<uint32_t> idstage((size_t)std::max<int64_t>(1, slots), 0);
-    for (int l = 0; l < kc; ++l) {
-        const int64_t len = h->h_len[l];
-        uint8_t *dst = stage.data() + h->d_codeoff[l];
-        const uint8_t *src = h->hl_codes[l].data();
-        if (cs == m) {
-            if (len) memcpy(dst, src, (size_t)len * m);
-        } else {
-            for (int64_t p = 0; p < len; ++p) memcpy(dst + (size_t)p * cs, src + (size_t)p * m, m);
-        }
-        if (len) memcpy(idstage.data() + h->d_pos[l], h->hl_ids[l].data(), (size_t)len * 4);
-    }
-    TRY(h->codes.ensure(total));
+    StaleGuard stale(h);
+    h->d_cap.resize((size_t)h->kc);
+    for (int l = 0; l < h->kc; ++l) h->d_cap[l] = list_mirror::spare_cap(h->mirror.h_len[l]);
+    list_mirror::LayoutTotals tot;
+    TRY(layout_from_caps(h, tot));
+    std::vector<uint8_t> stage;
+    std::vector<uint32_t> idstage;
+    h->mirror.stage(*h, tot, h->cb, h->cs, stage, idstage);
+    TRY(h->codes.ensure(stage.size()));
     TRY(h->ids.ensure(idstage.size() * 4));
-    TRY(h2d_copy(h->codes.p, stage.data(), total, h->stream));
+    TRY(h2d_copy(h->codes.p, stage.data(), stage.size(), h->stream));
     TRY(h2d_copy(h->ids.p, idstage.data(), idstage.size() * 4, h->stream));
     TRY(upload_list_tables(h));
-    h->dirty = false;
     h->have_lists = true;
     h->synthetic = false;
+    stale.current();
     return IVFADC_OK;
 }
 
@@ -923,7 +913,7 @@ PlanFacts plan_facts(const ivfadc_index *h)
 {
     PlanFacts f;
     f.d = h->d; f.kc = h->kc; f.m = h->m; f.dsub = h->dsub; f.ksub = h->ksub;
-    f.n = h->n; f.maxlen = h->maxlen;
+    f.n = h->mirror.n; f.maxlen = h->mirror.maxlen;
     f.num_cu = h->num_cu;
     f.u16 = h->u16;
     f.allow_filt = h->allow_filt; f.allow_lb = h->allow_lb; f.force_lb = h->force_lb; f.allow_nf = h->allow_nf;
@@ -1129,7 +1119,7 @@ IndexView index_view(const ivfadc_index *h)
     ix.list_codeoff = h->list_codeoff.as<int64_t>();
     ix.ids = h->synthetic ? (const u32 *)nullptr : h->ids.as<u32>();
     ix.d = h->d; ix.kc = h->kc; ix.m = h->m; ix.ksub = h->ksub; ix.dsub = h->dsub; ix.cs = h->cs;
-    ix.identity_labels = h->identity_labels ? 1 : 0;
+    ix.identity_labels = h->labmap.identity ? 1 : 0;
     return ix;
 }
 
@@ -1733,9 +1723,9 @@ int search_small(ivfadc_index *h, const SearchCall &c)
     }
     // chunks: about two workgroups per CU in all, a chunk no shorter than 4096 points
     const int64_t items = nq * w;
-    int nch = (int)std::max<int64_t>(1, std::min<int64_t>((h->maxlen + 4095) / 4096, (2 * (int64_t)h->num_cu) / std::max<int64_t>(1, items)));
-    uint32_t CH = (uint32_t)align_up((size_t)std::max<int64_t>(1, (h->maxlen + nch - 1) / nch), 1024);
-    nch = (int)std::max<int64_t>(1, (h->maxlen + CH - 1) / CH);
+    int nch = (int)std::max<int64_t>(1, std::min<int64_t>((h->mirror.maxlen + 4095) / 4096, (2 * (int64_t)h->num_cu) / std::max<int64_t>(1, items)));
+    uint32_t CH = (uint32_t)align_up((size_t)std::max<int64_t>(1, (h->mirror.maxlen + nch - 1) / nch), 1024);
+    nch = (int)std::max<int64_t>(1, (h->mirror.maxlen + CH - 1) / CH);
     const size_t slots = (size_t)items * nch;
     TRY(h->sq_keys.ensure(slots * K * 8));
     TRY(h->sq_cnt.ensure(slots * 4));
@@ -2015,7 +2005,7 @@ range_plan::Facts range_facts(const ivfadc_index *h)
     range_plan::Facts f;
     f.d = h->d; f.kc = h->kc; f.m = h->m; f.ksub = h->ksub;
     f.n = 0; f.maxlen = 0;
-    for (int64_t v : h->h_len) { f.n += v; f.maxlen = std::max(f.maxlen, v); }
+    for (int64_t v : h->mirror.h_len) { f.n += v; f.maxlen = std::max(f.maxlen, v); }
     f.force_chunk = h->force_chunk;
     f.ws_budget = h->ws_budget;
     f.lds_max = LDS_MAX;
@@ -2393,28 +2383,6 @@ extern "C" {
 
 const char *ivfadc_last_error(void) { return g_err.c_str(); }
 
-// UInt16 labels -> per block (label << 16 | codeword index), ascending; false (and the block / label) on a duplicate label
-static bool sort_labels16(const uint16_t *lab16, int m, int ksub, std::vector<uint32_t> &out, int &dup_block, int &dup_label)
-{
-    out.resize((size_t)m * ksub);
-    for (int i = 0; i < m; ++i) {
-        uint32_t *b = out.data() + (size_t)i * ksub;
-        for (int c = 0; c < ksub; ++c) b[c] = ((uint32_t)lab16[(size_t)i * ksub + c] << 16) | (uint32_t)c;
-        std::sort(b, b + ksub);
-        for (int c = 1; c < ksub; ++c)
-            if ((b[c] >> 16) == (b[c - 1] >> 16)) { dup_block = i; dup_label = (int)(b[c] >> 16); return false; }
-    }
-    return true;
-}
-
-// codeword index of label v in block i of a sorted label table (sort_labels16), -1: not a label of the block
-static int32_t find_label16(const std::vector<uint32_t> &sorted, int ksub, int i, uint16_t v)
-{
-    const uint32_t *b = sorted.data() + (size_t)i * ksub, *e = b + ksub;
-    const uint32_t *it = std::lower_bound(b, e, (uint32_t)v << 16);
-    return (it != e && (*it >> 16) == v) ? (int32_t)(*it & 0xFFFFu) : -1;
-}
-
 // ---- ivfadc_create: validate, then one step per operand family (the layouts themselves: pack_operands.h) --------------------------
 struct CreateArgs {
     int d, kc, m, ksub;
@@ -2423,8 +2391,8 @@ struct CreateArgs {
     const uint16_t *lab16;
 };
 
-// `ok`: the m x 256 label validity of an 8-bit handle; `inv`: the sorted label table of a 16-bit one
-static int validate_create(const CreateArgs &a, std::vector<uint8_t> &ok, std::vector<uint32_t> &inv)
+// `lm`: the handle's label map, made here (a duplicate label fails)
+static int validate_create(const CreateArgs &a, list_mirror::LabelMap &lm)
 {
     const int d = a.d, kc = a.kc, m = a.m, ksub = a.ksub;
     if (d < 1 || kc < 1 || m < 1 || ksub < 1) return fail(IVFADC_ERR_INVALID, "d, kc, m, ksub must be >= 1");
@@ -2440,19 +2408,7 @@ static int validate_create(const CreateArgs &a, std::vector<uint8_t> &ok, std::v
         if (!std::isfinite(a.centroids[i])) return fail(IVFADC_ERR_INVALID, "centroid %zu has a non-finite component", i / (size_t)d);
     for (size_t i = 0; i < (size_t)d * ksub; ++i)
         if (!std::isfinite(a.codebooks[i])) return fail(IVFADC_ERR_INVALID, "codebook %zu has a non-finite component", i / ((size_t)(d / m) * ksub));
-    if (a.lab16) {
-        int db = 0, dl = 0;
-        if (!sort_labels16(a.lab16, m, ksub, inv, db, dl)) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", dl, db);
-    } else {
-        ok.assign((size_t)m * 256, 0);
-        for (int i = 0; i < m; ++i)
-            for (int c = 0; c < ksub; ++c) {
-                uint8_t lab = a.code_labels[(size_t)i * ksub + c];
-                if (ok[(size_t)i * 256 + lab]) return fail(IVFADC_ERR_INVALID, "duplicate label %d in codebook %d", (int)lab, i);
-                ok[(size_t)i * 256 + lab] = 1;
-            }
-    }
-    return IVFADC_OK;
+    return mirror_fail(a.lab16 ? lm.init16(a.lab16, m, ksub) : lm.init8(a.code_labels, m, ksub), a.lab16 != nullptr);
 }
 
 // the quantizers as given, the regrouped codebooks, the labels
@@ -2521,9 +2477,8 @@ static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksu
     if (!out) return fail(IVFADC_ERR_INVALID, "out is null");
     *out = nullptr;
     const CreateArgs a{d, kc, m, ksub, centroids, codebooks, code_labels, lab16};
-    std::vector<uint8_t> ok;
-    std::vector<uint32_t> inv;
-    TRY(validate_create(a, ok, inv));
+    list_mirror::LabelMap lm;
+    TRY(validate_create(a, lm));
     int ndev = 0;
     HIP_TRY(hipGetDeviceCount(&ndev));
     if (ndev < 1) return fail(IVFADC_ERR_HIP, "no HIP device");
@@ -2535,13 +2490,7 @@ static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksu
     h->u16 = lab16 != nullptr;
     h->cb = h->u16 ? 2 * m : m;
     h->cs = code_stride(h->cb);
-    h->h_label_ok.swap(ok);
-    h->lab_sorted.swap(inv);
-    if (lab16) h->lab16.assign(lab16, lab16 + (size_t)m * ksub);
-    h->identity_labels = true;
-    for (int i = 0; i < m && h->identity_labels; ++i)
-        for (int c = 0; c < ksub; ++c)
-            if ((lab16 ? (int)lab16[(size_t)i * ksub + c] : (int)code_labels[(size_t)i * ksub + c]) != c) { h->identity_labels = false; break; }
+    h->labmap = std::move(lm);
     hipError_t e = hipSetDevice(device);
     if (e == hipSuccess) e = hipStreamCreateWithFlags(&h->stream, hipStreamNonBlocking);
     hipDeviceProp_t prop;
@@ -2555,9 +2504,7 @@ static int create_impl(ivfadc_t **out, int device, int d, int kc, int m, int ksu
     h->allow_filt = getenv("IVFADC_EXACT_TABLES") == nullptr;
     h->allow_mfma = getenv("IVFADC_COARSE_EXACT") == nullptr;
     // an index starts with kc empty lists
-    h->h_len.assign((size_t)kc, 0);
-    h->hl_codes.assign((size_t)kc, {});
-    h->hl_ids.assign((size_t)kc, {});
+    h->mirror.reset(kc);
     h->dirty = true;
     *out = h.release();
     return IVFADC_OK;
@@ -2739,6 +2686,7 @@ static int clone_view(ivfadc_index *src, ivfadc_index **out)
     view_shell(src, v.get());
     static_cast<Lists &>(*v) = *src;
     v->Lists::each_buf([](DevBuf &b) { b.alias(); });
+    v->mirror.copy_lengths(src->mirror);
     return view_hand_out(src, v, out);
 }
 
@@ -2757,7 +2705,7 @@ static int fill_subset_lists(ivfadc_index *src, ivfadc_index *v, const uint32_t 
 {
     const int kc = src->kc;
     hipStream_t s = src->stream;
-    const std::vector<subset::Item> items = subset::make_items(src->h_len);
+    const std::vector<subset::Item> items = subset::make_items(src->mirror.h_len);
     std::vector<uint32_t> count(items.size(), 0), base;
     const uint32_t *d_bits = bits;
     const u32 *src_ids = src->synthetic ? (const u32 *)nullptr : src->ids.as<u32>();
@@ -2778,21 +2726,20 @@ static int fill_subset_lists(ivfadc_index *src, ivfadc_index *v, const uint32_t 
         HIP_TRY(hipGetLastError());
         TRY(d2h_copy(count.data(), tmp.counts.p, items.size() * 4, s));   // (blocking: the layout depends on it)
     }
-    subset::make_bases(items, count, (size_t)kc, v->h_len, base);
+    subset::make_bases(items, count, (size_t)kc, v->mirror.h_len, base);
     for (int l = 0; l < kc; ++l)
-        if (v->h_len[l] > src->h_len[l]) return fail(IVFADC_ERR_HIP, "subset count of list %d exceeds the list", l);
-    v->d_cap = v->h_len;
-    size_t total = 0;
-    int64_t slots = 0;
-    TRY(layout_from_caps(v, total, slots));
-    TRY(v->codes.alloc_exact(total));
-    TRY(v->ids.alloc_exact((size_t)std::max<int64_t>(1, slots) * 4));
-    HIP_TRY(hipMemsetAsync(v->codes.p, 0, total, s));
+        if (v->mirror.h_len[l] > src->mirror.h_len[l]) return fail(IVFADC_ERR_HIP, "subset count of list %d exceeds the list", l);
+    v->d_cap = v->mirror.h_len;
+    list_mirror::LayoutTotals tot;
+    TRY(layout_from_caps(v, tot));
+    TRY(v->codes.alloc_exact(tot.code_bytes));
+    TRY(v->ids.alloc_exact((size_t)std::max<int64_t>(1, tot.id_slots) * 4));
+    HIP_TRY(hipMemsetAsync(v->codes.p, 0, tot.code_bytes, s));
     v->stream = s;
     const int rc = upload_list_tables(v);
     v->stream = nullptr;
     TRY(rc);
-    if (v->n > 0) {
+    if (v->mirror.n > 0) {
         TRY(tmp.bases.ensure(base.size() * 4));
         TRY(h2d_copy(tmp.bases.p, base.data(), base.size() * 4, s));
         hipLaunchKernelGGL(subset_scatter_kernel, dim3((unsigned)items.size()), dim3(256), 0, s, tmp.items.as<subset::Item>(),
@@ -2819,7 +2766,7 @@ static int clone_subset(ivfadc_index *src, const uint32_t *bits, bool bits_on_de
     int rc = fill_subset_lists(src, v.get(), bits, bits_on_device, nbits, tmp);
     if (rc != IVFADC_OK) (void)hipStreamSynchronize(src->stream);   // nothing still reads the scratch
     tmp.release();
-    const int64_t kept = v->n;
+    const int64_t kept = v->mirror.n;
     ivfadc_index *raw = v.get();
     if (rc == IVFADC_OK) rc = view_hand_out(src, v, out);
     if (rc != IVFADC_OK) {   // (until it is handed out the view is deleted plainly: its lists go first)
@@ -2902,7 +2849,7 @@ static int maskset_fill(ivfadc_index *src, ivfadc_maskset *ms, int nmasks, const
                         int64_t *out_kept, SubsetScratch &tmp)
 {
     hipStream_t s = src->stream;
-    const maskset::Layout lay = maskset::make_layout(src->h_len);
+    const maskset::Layout lay = maskset::make_layout(src->mirror.h_len);
     ms->device = src->device;
     ms->nmasks = nmasks;
     ms->kc = src->kc;
@@ -2913,7 +2860,7 @@ static int maskset_fill(ivfadc_index *src, ivfadc_maskset *ms, int nmasks, const
     TRY(ms->words.alloc_exact(std::max<size_t>(8, nwords * 4)));
     TRY(ms->word_off.alloc_exact(lay.word_off.size() * 8));
     TRY(h2d_copy(ms->word_off.p, lay.word_off.data(), lay.word_off.size() * 8, s));
-    const std::vector<subset::Item> items = subset::make_items(src->h_len);
+    const std::vector<subset::Item> items = subset::make_items(src->mirror.h_len);
     std::vector<unsigned long long> kept((size_t)nmasks, 0ull);
     if (!items.empty()) {
         const size_t stride = (size_t)((nbits + 31) / 32);
@@ -3062,101 +3009,49 @@ static int check_width(ivfadc_index *h, bool want_u16, const char *what)
     return IVFADC_OK;
 }
 
-static int check_offsets(ivfadc_index *h, const int64_t *offsets, const void *codes, const uint32_t *ids)
-{
-    const int kc = h->kc;
-    if (offsets[0] != 0) return fail(IVFADC_ERR_INVALID, "offsets[0] must be 0");
-    for (int l = 0; l < kc; ++l)
-        if (offsets[l + 1] < offsets[l]) return fail(IVFADC_ERR_INVALID, "offsets must be non-decreasing (list %d)", l);
-    const int64_t n = offsets[kc];
-    if (n > (int64_t)0xFFFFFFFFll) return fail(IVFADC_ERR_ASSERT, "index capacity of UInt32 ids exceeded");
-    if (n > 0 && (!codes || !ids)) return fail(IVFADC_ERR_INVALID, "null codes/ids");
-    return IVFADC_OK;
-}
+// ---- the write side: one body per entry pair ----------------------------------------------------------------------------------------------
+// A body takes the width it serves (wide: the _u16 entry).  check_width is the first difference between the twins, the label conversion
+// at the boundary (list_mirror::LabelMap) the only other.  Every edit of the mirror is list_mirror.h's; what stays here is the order of
+// the checks, the MutationScope, the StaleGuard and the device's half of each edit.
 
-// mirror <- (offsets, codes in mirror form: cb bytes per point, ids), then the device copy
-static int set_lists_mirror(ivfadc_t *h, const int64_t *offsets, const uint8_t *codes, const uint32_t *ids, const char *what)
+// mirror <- (offsets that passed check_offsets, codes in mirror form, ids), then the device copy: both set_lists entries and the loader
+static int assign_lists(ivfadc_index *h, const int64_t *offsets, const uint8_t *codes, const uint32_t *ids, const char *what)
 {
-    const int kc = h->kc, cb = h->cb;
     TRY(set_device(h));
     MutationScope ms;
     TRY(ms.begin(h, what));
-    for (int l = 0; l < kc; ++l) {
-        const int64_t a = offsets[l], b = offsets[l + 1];
-        h->h_len[l] = b - a;
-        h->hl_codes[l].assign(codes + (size_t)a * cb, codes + (size_t)b * cb);
-        h->hl_ids[l].assign(ids + a, ids + b);
-    }
-    return upload_lists(h);
+    StaleGuard stale(h);
+    h->mirror.assign(offsets, codes, ids, h->cb);
+    return upload_lists(h);   // (declares the copy current)
 }
 
-// labels (n x m uint16_t) -> codeword indices in mirror form; ERR_INVALID names the first code that is not a label of its block
-static int labels_to_indices(const ivfadc_index *h, int64_t n, const uint16_t *lab, std::vector<uint8_t> &out)
+static int set_lists_entry(ivfadc_index *h, const int64_t *offsets, const void *codes, const uint32_t *ids, bool wide)
 {
-    const int m = h->m;
-    out.resize((size_t)n * h->cb);
-    uint16_t *dst = (uint16_t *)out.data();
-    for (int64_t p = 0; p < n; ++p)
-        for (int i = 0; i < m; ++i) {
-            const uint16_t v = lab[(size_t)p * m + i];
-            const int32_t c = h->identity_labels ? (v < h->ksub ? (int32_t)v : -1) : find_label16(h->lab_sorted, h->ksub, i, v);
-            if (c < 0) return fail(IVFADC_ERR_INVALID, "code %d of point %lld is not a label of codebook %d", (int)v, (long long)p, i);
-            dst[(size_t)p * m + i] = (uint16_t)c;
-        }
-    return IVFADC_OK;
-}
-
-// codeword indices (mirror form) -> labels, in place
-static void indices_to_labels(const ivfadc_index *h, int64_t n, uint16_t *codes)
-{
-    if (h->identity_labels) return;
-    const int m = h->m, ksub = h->ksub;
-    for (int64_t p = 0; p < n; ++p)
-        for (int i = 0; i < m; ++i) codes[(size_t)p * m + i] = h->lab16[(size_t)i * ksub + codes[(size_t)p * m + i]];
-}
-
-int ivfadc_set_lists_u16(ivfadc_t *h, const int64_t *offsets, const void *codes, const uint32_t *ids)
-try {
-    HandleLock lk_(h);
     if (!h || !offsets) return fail(IVFADC_ERR_INVALID, "null argument");
-    TRY(check_width(h, true, "ivfadc_set_lists"));
-    TRY(check_mutable(h, "ivfadc_set_lists_u16"));
-    TRY(check_offsets(h, offsets, codes, ids));
+    TRY(check_width(h, wide, "ivfadc_set_lists"));
+    const char *what = wide ? "ivfadc_set_lists_u16" : "ivfadc_set_lists";
+    TRY(check_mutable(h, what));
+    TRY(mirror_fail(list_mirror::ListMirror::check_offsets(h->kc, offsets, codes, ids), wide));
+    const int64_t n = offsets[h->kc];
+    if (!wide) {
+        TRY(mirror_fail(h->labmap.check8(n, (const uint8_t *)codes), false));
+        return assign_lists(h, offsets, (const uint8_t *)codes, ids, what);
+    }
     std::vector<uint8_t> idx;
-    TRY(labels_to_indices(h, offsets[h->kc], (const uint16_t *)codes, idx));
-    return set_lists_mirror(h, offsets, idx.data(), ids, "ivfadc_set_lists_u16");
-} IVF_CATCH
+    TRY(mirror_fail(h->labmap.to_indices(n, (const uint16_t *)codes, idx), true));
+    return assign_lists(h, offsets, idx.data(), ids, what);
+}
 
 int ivfadc_set_lists(ivfadc_t *h, const int64_t *offsets, const uint8_t *codes, const uint32_t *ids)
 try {
     HandleLock lk_(h);
-    if (!h || !offsets) return fail(IVFADC_ERR_INVALID, "null argument");
-    TRY(check_width(h, false, "ivfadc_set_lists"));
-    TRY(check_mutable(h, "ivfadc_set_lists"));
-    const int kc = h->kc, m = h->m;
-    if (offsets[0] != 0) return fail(IVFADC_ERR_INVALID, "offsets[0] must be 0");
-    for (int l = 0; l < kc; ++l)
-        if (offsets[l + 1] < offsets[l]) return fail(IVFADC_ERR_INVALID, "offsets must be non-decreasing (list %d)", l);
-    const int64_t n = offsets[kc];
-    if (n > (int64_t)0xFFFFFFFFll) return fail(IVFADC_ERR_ASSERT, "index capacity of UInt32 ids exceeded");
-    if (n > 0 && (!codes || !ids)) return fail(IVFADC_ERR_INVALID, "null codes/ids");
-    if (h->ksub < 256) {
-        for (int64_t p = 0; p < n; ++p)
-            for (int i = 0; i < m; ++i)
-                if (!h->h_label_ok[(size_t)i * 256 + codes[(size_t)p * m + i]])
-                    return fail(IVFADC_ERR_INVALID, "code byte %d of point %lld is not a label of codebook %d",
-                                (int)codes[(size_t)p * m + i], (long long)p, i);
-    }
-    TRY(set_device(h));
-    MutationScope ms;
-    TRY(ms.begin(h, "ivfadc_set_lists"));
-    for (int l = 0; l < kc; ++l) {
-        const int64_t a = offsets[l], b = offsets[l + 1];
-        h->h_len[l] = b - a;
-        h->hl_codes[l].assign(codes + (size_t)a * m, codes + (size_t)b * m);
-        h->hl_ids[l].assign(ids + a, ids + b);
-    }
-    return upload_lists(h);
+    return set_lists_entry(h, offsets, codes, ids, false);
+} IVF_CATCH
+
+int ivfadc_set_lists_u16(ivfadc_t *h, const int64_t *offsets, const void *codes, const uint32_t *ids)
+try {
+    HandleLock lk_(h);
+    return set_lists_entry(h, offsets, codes, ids, true);
 } IVF_CATCH
 
 int ivfadc_synth_lists(ivfadc_t *h, const int64_t *offsets, uint64_t seed)
@@ -3177,19 +3072,14 @@ try {
     MutationScope ms;
     TRY(ms.begin(h, "ivfadc_synth_lists"));
     // no spare capacity: the id of a point is its canonical global position (ids == nullptr in the kernels)
-    for (int l = 0; l < kc; ++l) {
-        h->h_len[l] = offsets[l + 1] - offsets[l];
-        std::vector<uint8_t>().swap(h->hl_codes[l]);
-        std::vector<uint32_t>().swap(h->hl_ids[l]);
-    }
-    h->d_cap = h->h_len;
-    size_t total = 0;
-    int64_t slots = 0;
-    TRY(layout_from_caps(h, total, slots));
-    TRY(h->codes.ensure(total));
+    h->mirror.assign_lengths(offsets);
+    h->d_cap = h->mirror.h_len;
+    list_mirror::LayoutTotals tot;
+    TRY(layout_from_caps(h, tot));
+    TRY(h->codes.ensure(tot.code_bytes));
     TRY(upload_list_tables(h));
-    HIP_TRY(hipMemsetAsync((uint8_t *)h->codes.p + (total - CODE_SLACK), 0, CODE_SLACK, h->stream));
-    const int64_t maxdw = h->maxlen * (h->cs / 4);
+    HIP_TRY(hipMemsetAsync((uint8_t *)h->codes.p + (tot.code_bytes - CODE_SLACK), 0, CODE_SLACK, h->stream));
+    const int64_t maxdw = h->mirror.maxlen * (h->cs / 4);
     const unsigned gy = (unsigned)std::max<int64_t>(1, std::min<int64_t>(1024, (maxdw + 256 * 8 - 1) / (256 * 8)));
     hipLaunchKernelGGL(synth_codes_kernel, dim3((unsigned)kc, gy), dim3(256), 0, h->stream, h->codes.as<uint8_t>(),
                        h->list_pos.as<int64_t>(), h->list_len.as<u32>(), h->list_codeoff.as<int64_t>(), kc, h->m, h->cs, (u64)seed);
@@ -3197,105 +3087,71 @@ try {
     HIP_TRY(hipStreamSynchronize(h->stream));
     h->have_lists = true;
     h->synthetic = true;
-    h->dirty = false;
+    h->dirty = false;   // (no StaleGuard: there is no mirror data a re-layout could be made from)
     return IVFADC_OK;
 } IVF_CATCH
+
+// The twins have always looked at the width at different places, and callers may rely on either: the 8-bit entry takes n == 0 from any
+// handle and names a null argument before the width; the _u16 entry looks at the width first.
+static int encode_entry(ivfadc_index *h, int64_t n, const float *pts, int32_t *out_list, void *out_codes, bool wide)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    if (n < 0) return fail(IVFADC_ERR_INVALID, "n < 0");
+    if (wide) TRY(check_width(h, true, "ivfadc_encode"));
+    if (n == 0) return IVFADC_OK;
+    if (!pts || !out_list || !out_codes) return fail(IVFADC_ERR_INVALID, "null argument");
+    if (!wide) TRY(check_width(h, false, "ivfadc_encode"));
+    if (!h->rot.empty())
+        return fail(IVFADC_ERR_STATE, "ivfadc_encode%s: the residual quantizer carries a rotation (:opq); this index is served for search only", wide ? "_u16" : "");
+    TRY(set_device(h));
+    TRY(encode_dev(h, n, pts, out_list, (uint8_t *)out_codes));
+    if (wide) h->labmap.to_labels(n, out_codes);
+    return IVFADC_OK;
+}
 
 int ivfadc_encode(ivfadc_t *h, int64_t n, const float *pts, int32_t *out_list, uint8_t *out_codes)
 try {
     HandleLock lk_(h);
-    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    if (n < 0) return fail(IVFADC_ERR_INVALID, "n < 0");
-    if (n == 0) return IVFADC_OK;
-    if (!pts || !out_list || !out_codes) return fail(IVFADC_ERR_INVALID, "null argument");
-    TRY(check_width(h, false, "ivfadc_encode"));
-    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_encode: the residual quantizer carries a rotation (:opq); this index is served for search only");
-    TRY(set_device(h));
-    return encode_dev(h, n, pts, out_list, out_codes);
+    return encode_entry(h, n, pts, out_list, out_codes, false);
 } IVF_CATCH
 
 int ivfadc_encode_u16(ivfadc_t *h, int64_t n, const float *pts, int32_t *out_list, void *out_codes)
 try {
     HandleLock lk_(h);
-    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    if (n < 0) return fail(IVFADC_ERR_INVALID, "n < 0");
-    TRY(check_width(h, true, "ivfadc_encode"));
-    if (n == 0) return IVFADC_OK;
-    if (!pts || !out_list || !out_codes) return fail(IVFADC_ERR_INVALID, "null argument");
-    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_encode_u16: the residual quantizer carries a rotation (:opq); this index is served for search only");
-    TRY(set_device(h));
-    TRY(encode_dev(h, n, pts, out_list, (uint8_t *)out_codes));
-    indices_to_labels(h, n, (uint16_t *)out_codes);
-    return IVFADC_OK;
+    return encode_entry(h, n, pts, out_list, out_codes, true);
 } IVF_CATCH
 
-// The mirror edit of push!: `lst` / `cod` are the (already computed) assignment and codes of the new points.  The
-// host mirror is the source of truth; the device copy is marked stale BEFORE the mirror changes and declared current
-// again only after the in-place device update has fully succeeded, so a failure half-way (allocation, copy, launch)
-// leaves a handle whose next search re-lays the lists out from the mirror instead of one that searches stale lists.
+// push! behind the encoder: `lst` / `cod` are the (already computed) assignment and codes (mirror form) of the new points.  In place when
+// the device layout is current and every target list has room; otherwise the host mirror takes the points and the next search re-lays the
+// lists out with fresh spare capacity.
 static int append_encoded(ivfadc_t *h, int64_t nnew, const int32_t *lst, const uint8_t *cod, const uint32_t *ids)
 {
-    const int m = h->cb, cs = h->cs;   // (cod: mirror form, cb bytes per point)
-    const int64_t n_old = h->ntotal();
+    const int cb = h->cb;
     MutationScope ms;
     TRY(ms.begin(h, "ivfadc_append"));
     TRY(set_device(h));
-    // In place when the device layout is current and every target list has room; otherwise the host mirror takes
-    // the points and the next search re-lays the lists out with fresh spare capacity.
-    bool inplace = h->have_lists && !h->dirty;
-    if (inplace) {
-        std::vector<int64_t> add((size_t)h->kc, 0);
-        for (int64_t i = 0; i < nnew; ++i) add[lst[i]]++;
-        for (int l = 0; l < h->kc && inplace; ++l)
-            if (h->h_len[l] + add[l] > h->d_cap[l]) inplace = false;
-    }
+    StaleGuard stale(h);
     std::vector<int64_t> dst;
-    if (inplace) dst.resize((size_t)nnew * 2);
-    // reserve first: the mirror edit below must not stop half-way on an allocation failure
-    {
-        std::vector<int64_t> add((size_t)h->kc, 0);
-        for (int64_t i = 0; i < nnew; ++i) add[lst[i]]++;
-        for (int l = 0; l < h->kc; ++l)
-            if (add[l]) {
-                h->hl_codes[l].reserve(h->hl_codes[l].size() + (size_t)add[l] * m);
-                h->hl_ids[l].reserve(h->hl_ids[l].size() + (size_t)add[l]);
-            }
-    }
-    h->dirty = true;
-    // new points go to the END of their list, in call order (utils.jl:143-144)
-    for (int64_t i = 0; i < nnew; ++i) {
-        const int l = lst[i];
-        if (inplace) {
-            dst[2 * i] = h->d_codeoff[l] + h->h_len[l] * cs;
-            dst[2 * i + 1] = h->d_pos[l] + h->h_len[l];
-        }
-        h->hl_codes[l].insert(h->hl_codes[l].end(), cod + (size_t)i * m, cod + (size_t)(i + 1) * m);
-        h->hl_ids[l].push_back(ids[i]);
-        h->h_len[l]++;
-        h->maxlen = std::max(h->maxlen, h->h_len[l]);
-    }
-    h->n = n_old + nnew;
-    if (inplace) {
-        const size_t o_ids = (size_t)nnew * 16, o_codes = o_ids + align_up((size_t)nnew * 4, 16);
-        const size_t bytes = o_codes + (size_t)nnew * m;
-        std::vector<uint8_t> stage(bytes);
-        memcpy(stage.data(), dst.data(), (size_t)nnew * 16);
-        memcpy(stage.data() + o_ids, ids, (size_t)nnew * 4);
-        memcpy(stage.data() + o_codes, cod, (size_t)nnew * m);
-        TRY(h->app_stage.ensure(bytes));
-        TRY(h2d_copy(h->app_stage.p, stage.data(), bytes, h->stream));
-        const uint8_t *base = (const uint8_t *)h->app_stage.p;
-        hipLaunchKernelGGL(append_scatter_kernel, dim3((unsigned)((nnew + 255) / 256)), dim3(256), 0, h->stream, nnew, m,
-                           (const int64_t *)base, base + o_codes, (const u32 *)(base + o_ids), h->codes.as<uint8_t>(), h->ids.as<u32>());
-        HIP_TRY(hipGetLastError());
-        // lengths: only the touched lists change, but kc u32 is a single small copy
-        std::vector<uint32_t> len32((size_t)h->kc);
-        for (int l = 0; l < h->kc; ++l) len32[l] = (uint32_t)h->h_len[l];
-        TRY(h2d_copy(h->list_len.p, len32.data(), (size_t)h->kc * 4, h->stream));
-        HIP_TRY(hipStreamSynchronize(h->stream));   // staging vectors are stack-owned
-        h->inplace_appends++;
-        h->dirty = false;                           // the device copy is current again
-    }
+    if (!h->mirror.append(nnew, lst, cod, ids, cb, stale.in_place() ? h : nullptr, h->cs, dst)) return IVFADC_OK;
+    const size_t o_ids = (size_t)nnew * 16, o_codes = o_ids + align_up((size_t)nnew * 4, 16);
+    const size_t bytes = o_codes + (size_t)nnew * cb;
+    std::vector<uint8_t> stage(bytes);
+    memcpy(stage.data(), dst.data(), (size_t)nnew * 16);
+    memcpy(stage.data() + o_ids, ids, (size_t)nnew * 4);
+    memcpy(stage.data() + o_codes, cod, (size_t)nnew * cb);
+    TRY(h->app_stage.ensure(bytes));
+    TRY(h2d_copy(h->app_stage.p, stage.data(), bytes, h->stream));
+    const uint8_t *base = (const uint8_t *)h->app_stage.p;
+    hipLaunchKernelGGL(append_scatter_kernel, dim3((unsigned)((nnew + 255) / 256)), dim3(256), 0, h->stream, nnew, cb,
+                       (const int64_t *)base, base + o_codes, (const u32 *)(base + o_ids), h->codes.as<uint8_t>(), h->ids.as<u32>());
+    HIP_TRY(hipGetLastError());
+    // lengths: only the touched lists change, but kc u32 is a single small copy
+    std::vector<uint32_t> len32((size_t)h->kc);
+    for (int l = 0; l < h->kc; ++l) len32[l] = (uint32_t)h->mirror.h_len[l];
+    TRY(h2d_copy(h->list_len.p, len32.data(), (size_t)h->kc * 4, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // staging vectors are stack-owned
+    h->inplace_appends++;
+    stale.current();
     return IVFADC_OK;
 }
 
@@ -3305,47 +3161,42 @@ static int append_check(ivfadc_t *h, int64_t nnew, const float *pts, const uint3
     if (h->synthetic) return fail(IVFADC_ERR_STATE, "append is not available on device-synthesised lists");
     if (nnew < 0) return fail(IVFADC_ERR_INVALID, "nnew < 0");
     if (nnew > 0 && (!pts || !ids)) return fail(IVFADC_ERR_INVALID, "null argument");
-    if (h->ntotal() + nnew > (int64_t)0xFFFFFFFFll) return fail(IVFADC_ERR_ASSERT, "Cannot index, exceeding index capacity of UInt32");
+    if (h->mirror.ntotal() + nnew > list_mirror::ID_LIMIT) return fail(IVFADC_ERR_ASSERT, "Cannot index, exceeding index capacity of UInt32");
+    return IVFADC_OK;
+}
+
+// (width before mutability, as the _u16 entry has always had it: both refusals are IVFADC_ERR_STATE)
+static int append_entry(ivfadc_index *h, int64_t nnew, const float *pts, const uint32_t *ids, int32_t *out_list, void *out_codes, bool wide)
+{
+    const char *what = wide ? "ivfadc_append_u16" : "ivfadc_append";
+    TRY(append_check(h, nnew, pts, ids));
+    TRY(check_width(h, wide, "ivfadc_append"));
+    TRY(check_mutable(h, what));
+    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "%s: the residual quantizer carries a rotation (:opq); this index is served for search only", what);
+    if (nnew == 0) return IVFADC_OK;
+    TRY(set_device(h));
+    std::vector<int32_t> lst((size_t)nnew);
+    std::vector<uint8_t> cod((size_t)nnew * h->cb);
+    TRY(encode_dev(h, nnew, pts, lst.data(), cod.data()));   // (a 16-bit handle: codeword indices) nothing has changed yet if this fails
+    TRY(append_encoded(h, nnew, lst.data(), cod.data(), ids));
+    if (out_list) memcpy(out_list, lst.data(), (size_t)nnew * 4);
+    if (out_codes) {
+        memcpy(out_codes, cod.data(), cod.size());
+        if (wide) h->labmap.to_labels(nnew, out_codes);
+    }
     return IVFADC_OK;
 }
 
 int ivfadc_append(ivfadc_t *h, int64_t nnew, const float *pts, const uint32_t *ids, int32_t *out_list, uint8_t *out_codes)
 try {
     HandleLock lk_(h);
-    TRY(append_check(h, nnew, pts, ids));
-    TRY(check_mutable(h, "ivfadc_append"));
-    TRY(check_width(h, false, "ivfadc_append"));
-    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_append: the residual quantizer carries a rotation (:opq); this index is served for search only");
-    if (nnew == 0) return IVFADC_OK;
-    TRY(set_device(h));
-    std::vector<int32_t> lst((size_t)nnew);
-    std::vector<uint8_t> cod((size_t)nnew * h->m);
-    TRY(encode_dev(h, nnew, pts, lst.data(), cod.data()));   // nothing has changed yet if this fails
-    TRY(append_encoded(h, nnew, lst.data(), cod.data(), ids));
-    if (out_list) memcpy(out_list, lst.data(), (size_t)nnew * 4);
-    if (out_codes) memcpy(out_codes, cod.data(), (size_t)nnew * h->m);
-    return IVFADC_OK;
+    return append_entry(h, nnew, pts, ids, out_list, out_codes, false);
 } IVF_CATCH
 
 int ivfadc_append_u16(ivfadc_t *h, int64_t nnew, const float *pts, const uint32_t *ids, int32_t *out_list, void *out_codes)
 try {
     HandleLock lk_(h);
-    TRY(append_check(h, nnew, pts, ids));
-    TRY(check_width(h, true, "ivfadc_append"));
-    TRY(check_mutable(h, "ivfadc_append_u16"));
-    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "ivfadc_append_u16: the residual quantizer carries a rotation (:opq); this index is served for search only");
-    if (nnew == 0) return IVFADC_OK;
-    TRY(set_device(h));
-    std::vector<int32_t> lst((size_t)nnew);
-    std::vector<uint8_t> cod((size_t)nnew * h->cb);
-    TRY(encode_dev(h, nnew, pts, lst.data(), cod.data()));   // codeword indices; nothing has changed yet if this fails
-    TRY(append_encoded(h, nnew, lst.data(), cod.data(), ids));
-    if (out_list) memcpy(out_list, lst.data(), (size_t)nnew * 4);
-    if (out_codes) {
-        memcpy(out_codes, cod.data(), (size_t)nnew * h->cb);
-        indices_to_labels(h, nnew, (uint16_t *)out_codes);
-    }
-    return IVFADC_OK;
+    return append_entry(h, nnew, pts, ids, out_list, out_codes, true);
 } IVF_CATCH
 
 int ivfadc_delete_ids(ivfadc_t *h, int64_t ndel, const uint32_t *del_ids, int64_t *out_removed)
@@ -3358,55 +3209,24 @@ try {
     if (out_removed) *out_removed = 0;
     if (ndel == 0) return IVFADC_OK;
     TRY(set_device(h));
-    std::vector<uint32_t> want(del_ids, del_ids + ndel);
-    std::sort(want.begin(), want.end());
-    want.erase(std::unique(want.begin(), want.end()), want.end());
-    // stale until the device-side compaction has succeeded (see append_encoded)
-    const bool was_dirty = h->dirty;
-    h->dirty = true;
-    // host mirror, pass 1: drop the entries (stable) and collect the ids that were really there
-    const int kc = h->kc, m = h->cb;
-    std::vector<uint32_t> rem;
-    for (int l = 0; l < kc; ++l) {
-        auto &lid = h->hl_ids[l];
-        auto &lco = h->hl_codes[l];
-        size_t wr = 0;
-        for (size_t p = 0; p < lid.size(); ++p) {
-            if (std::binary_search(want.begin(), want.end(), lid[p])) { rem.push_back(lid[p]); continue; }
-            if (wr != p) {
-                lid[wr] = lid[p];
-                memmove(lco.data() + wr * m, lco.data() + p * m, m);
-            }
-            ++wr;
-        }
-        lid.resize(wr);
-        lco.resize(wr * m);
-    }
-    if (rem.empty()) { h->dirty = was_dirty; return IVFADC_OK; }   // nothing was stored under these ids: mirror unchanged, views stay valid
+    // the ids that are really there, found without touching the mirror: nothing has changed yet if the scope cannot be opened
+    const std::vector<uint32_t> rem = h->mirror.find_ids(ndel, del_ids);
+    if (rem.empty()) return IVFADC_OK;   // nothing was stored under these ids: mirror unchanged, views stay valid
     MutationScope ms;
     TRY(ms.begin(h, "ivfadc_delete_ids"));
-    std::sort(rem.begin(), rem.end());
-    // pass 2: every surviving id drops by the number of removed ids below it (_shift_inverse_index!, utils.jl:11-27)
-    int64_t maxlen = 0, n = 0;
-    for (int l = 0; l < kc; ++l) {
-        for (uint32_t &v : h->hl_ids[l]) v -= (uint32_t)(std::lower_bound(rem.begin(), rem.end(), v) - rem.begin());
-        h->h_len[l] = (int64_t)h->hl_ids[l].size();
-        maxlen = std::max(maxlen, h->h_len[l]);
-        n += h->h_len[l];
-    }
-    h->maxlen = maxlen;
-    h->n = n;
+    StaleGuard stale(h);
+    h->mirror.erase_ids(rem, h->cb);
     if (out_removed) *out_removed = (int64_t)rem.size();
     // device copy: the same compaction in place, one workgroup per list
-    if (h->have_lists && !was_dirty) {
+    if (stale.in_place()) {
         TRY(h->app_stage.ensure(rem.size() * 4));
         TRY(h2d_copy(h->app_stage.p, rem.data(), rem.size() * 4, h->stream));
-        hipLaunchKernelGGL(delete_compact_kernel, dim3((unsigned)kc), dim3(256), 0, h->stream, h->app_stage.as<u32>(), (u32)rem.size(),
+        hipLaunchKernelGGL(delete_compact_kernel, dim3((unsigned)h->kc), dim3(256), 0, h->stream, h->app_stage.as<u32>(), (u32)rem.size(),
                            h->list_pos.as<int64_t>(), h->list_codeoff.as<int64_t>(), h->list_len.as<u32>(), h->codes.as<uint8_t>(),
                            h->ids.as<u32>(), h->cs);
         HIP_TRY(hipGetLastError());
         HIP_TRY(hipStreamSynchronize(h->stream));   // rem is stack-owned
-        h->dirty = false;
+        stale.current();
     }
     return IVFADC_OK;
 } IVF_CATCH
@@ -3421,11 +3241,9 @@ try {
     TRY(set_device(h));
     MutationScope ms;
     TRY(ms.begin(h, "ivfadc_shift_ids"));
-    const bool was_dirty = h->dirty;
-    h->dirty = true;
-    for (int l = 0; l < h->kc; ++l)
-        for (uint32_t &v : h->hl_ids[l]) v += (uint32_t)delta;
-    if (h->have_lists && !was_dirty) {
+    StaleGuard stale(h);
+    h->mirror.shift_ids((uint32_t)delta);
+    if (stale.in_place()) {
         int64_t slots = 0;
         for (int l = 0; l < h->kc; ++l) slots += h->d_cap[l];
         if (slots > 0) {
@@ -3433,7 +3251,7 @@ try {
                                h->ids.as<u32>(), slots, (u32)delta);
             HIP_TRY(hipGetLastError());
         }
-        h->dirty = false;
+        stale.current();
     }
     return IVFADC_OK;
 } IVF_CATCH
@@ -3493,8 +3311,8 @@ static int locate_sorted(ivfadc_index *h, const uint32_t *d_want, uint64_t nwant
     TRY(h->rc_best.ensure(std::max<size_t>(8, (size_t)nwant * 8)));
     HIP_TRY(hipMemsetAsync(h->rc_best.p, 0, std::max<size_t>(8, (size_t)nwant * 8), s));
     uint64_t items = 0;
-    for (int64_t len : h->h_len) items += recon::list_chunks((uint64_t)std::max<int64_t>(len, 0));
-    const recon::Plan pl = recon::make_plan(nwant, span_known, want_lo, want_hi, items, (uint64_t)h->ntotal(), h->num_cu);
+    for (int64_t len : h->mirror.h_len) items += recon::list_chunks((uint64_t)std::max<int64_t>(len, 0));
+    const recon::Plan pl = recon::make_plan(nwant, span_known, want_lo, want_hi, items, (uint64_t)h->mirror.ntotal(), h->num_cu);
     if (pl.mode == recon::MODE_NONE) return IVFADC_OK;
     // the work items' prefix, from the device's own list_len (== h_len once pending changes are laid out): nothing is uploaded, nothing waited for
     TRY(h->rc_chunk.ensure(((size_t)h->kc + 1) * 8));
@@ -4807,51 +4625,33 @@ int ivfadc_ntotal(ivfadc_t *h, int64_t *out_n, int64_t *list_sizes)
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    if (out_n) *out_n = h->ntotal();
+    if (out_n) *out_n = h->mirror.ntotal();
     if (list_sizes)
-        for (int l = 0; l < h->kc; ++l) list_sizes[l] = h->h_len[l];
+        for (int l = 0; l < h->kc; ++l) list_sizes[l] = h->mirror.h_len[l];
     return IVFADC_OK;
 } IVF_CATCH
+
+static int get_lists_entry(ivfadc_index *h, int64_t *offsets, void *codes, uint32_t *ids, bool wide)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    TRY(check_width(h, wide, "ivfadc_get_lists"));
+    if (h->is_view) return fail(IVFADC_ERR_STATE, "a view keeps no host mirror of the lists");
+    if (h->synthetic) return fail(IVFADC_ERR_STATE, "device-synthesised lists keep no host mirror");
+    h->mirror.gather(offsets, (uint8_t *)codes, ids, h->cb);
+    if (wide && codes) h->labmap.to_labels(h->mirror.ntotal(), codes);   // codeword indices -> labels
+    return IVFADC_OK;
+}
 
 int ivfadc_get_lists(ivfadc_t *h, int64_t *offsets, uint8_t *codes, uint32_t *ids)
 try {
     HandleLock lk_(h);
-    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    TRY(check_width(h, false, "ivfadc_get_lists"));
-    if (h->is_view) return fail(IVFADC_ERR_STATE, "a view keeps no host mirror of the lists");
-    if (h->synthetic) return fail(IVFADC_ERR_STATE, "device-synthesised lists keep no host mirror");
-    int64_t run = 0;
-    for (int l = 0; l < h->kc; ++l) {
-        const int64_t len = h->h_len[l];
-        if (offsets) offsets[l] = run;
-        if (codes && len) memcpy(codes + (size_t)run * h->m, h->hl_codes[l].data(), (size_t)len * h->m);
-        if (ids && len) memcpy(ids + run, h->hl_ids[l].data(), (size_t)len * 4);
-        run += len;
-    }
-    if (offsets) offsets[h->kc] = run;
-    return IVFADC_OK;
+    return get_lists_entry(h, offsets, codes, ids, false);
 } IVF_CATCH
 
 int ivfadc_get_lists_u16(ivfadc_t *h, int64_t *offsets, void *codes, uint32_t *ids)
 try {
     HandleLock lk_(h);
-    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    TRY(check_width(h, true, "ivfadc_get_lists"));
-    if (h->is_view) return fail(IVFADC_ERR_STATE, "a view keeps no host mirror of the lists");
-    int64_t run = 0;
-    for (int l = 0; l < h->kc; ++l) {
-        const int64_t len = h->h_len[l];
-        if (offsets) offsets[l] = run;
-        if (codes && len) {
-            uint16_t *dst = (uint16_t *)codes + (size_t)run * h->m;
-            memcpy(dst, h->hl_codes[l].data(), (size_t)len * h->cb);
-            indices_to_labels(h, len, dst);
-        }
-        if (ids && len) memcpy(ids + run, h->hl_ids[l].data(), (size_t)len * 4);
-        run += len;
-    }
-    if (offsets) offsets[h->kc] = run;
-    return IVFADC_OK;
+    return get_lists_entry(h, offsets, codes, ids, true);
 } IVF_CATCH
 
 int ivfadc_get_dims(ivfadc_t *h, int *d, int *kc, int *m, int *ksub)
@@ -4865,30 +4665,29 @@ try {
     return IVFADC_OK;
 } IVF_CATCH
 
-int ivfadc_get_quantizers(ivfadc_t *h, float *centroids, float *codebooks, uint8_t *code_labels)
-try {
-    HandleLock lk_(h);
+static int get_quantizers_entry(ivfadc_index *h, float *centroids, float *codebooks, void *code_labels, bool wide)
+{
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    TRY(check_width(h, false, "ivfadc_get_quantizers"));
+    TRY(check_width(h, wide, "ivfadc_get_quantizers"));
     TRY(set_device(h));
     HIP_TRY(hipStreamSynchronize(h->stream));
     if (centroids) TRY(d2h_copy(centroids, h->centroids.p, (size_t)h->d * h->kc * 4, h->stream));
     if (codebooks) TRY(d2h_copy(codebooks, h->codebooks.p, (size_t)h->d * h->ksub * 4, h->stream));
-    if (code_labels) HIP_TRY(hipMemcpy(code_labels, h->labels.p, (size_t)h->m * h->ksub, hipMemcpyDeviceToHost));
+    if (code_labels && wide) memcpy(code_labels, h->labmap.lab16.data(), h->labmap.lab16.size() * 2);
+    if (code_labels && !wide) HIP_TRY(hipMemcpy(code_labels, h->labels.p, (size_t)h->m * h->ksub, hipMemcpyDeviceToHost));
     return IVFADC_OK;
+}
+
+int ivfadc_get_quantizers(ivfadc_t *h, float *centroids, float *codebooks, uint8_t *code_labels)
+try {
+    HandleLock lk_(h);
+    return get_quantizers_entry(h, centroids, codebooks, code_labels, false);
 } IVF_CATCH
 
 int ivfadc_get_quantizers_u16(ivfadc_t *h, float *centroids, float *codebooks, void *code_labels)
 try {
     HandleLock lk_(h);
-    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    TRY(check_width(h, true, "ivfadc_get_quantizers"));
-    TRY(set_device(h));
-    HIP_TRY(hipStreamSynchronize(h->stream));
-    if (centroids) TRY(d2h_copy(centroids, h->centroids.p, (size_t)h->d * h->kc * 4, h->stream));
-    if (codebooks) TRY(d2h_copy(codebooks, h->codebooks.p, (size_t)h->d * h->ksub * 4, h->stream));
-    if (code_labels) memcpy(code_labels, h->lab16.data(), h->lab16.size() * 2);
-    return IVFADC_OK;
+    return get_quantizers_entry(h, centroids, codebooks, code_labels, true);
 } IVF_CATCH
 
 int ivfadc_abi_version(void) { return IVFADC_ABI_VERSION; }
@@ -5263,10 +5062,8 @@ try {
     if (index_bits != 8 && index_bits != 16 && index_bits != 32) return fail(IVFADC_ERR_INVALID, "index_bits must be 8, 16 or 32");
     TRY(set_device(h));
     if (index_bits < 32) {   // the reference asserts the capacity of I (index.jl:124-125, utils.jl:134-135): never truncate an id
-        const uint32_t lim = index_bits == 8 ? 0xFFu : 0xFFFFu;
-        for (int l = 0; l < h->kc; ++l)
-            for (uint32_t v : h->hl_ids[l])
-                if (v > lim) return fail(IVFADC_ERR_ASSERT, "id %u does not fit a %d-bit index type", v, index_bits);
+        uint32_t v = 0;
+        if (h->mirror.first_id_above(index_bits == 8 ? 0xFFu : 0xFFFFu, v)) return fail(IVFADC_ERR_ASSERT, "id %u does not fit a %d-bit index type", v, index_bits);
     }
     const int d = h->d, kc = h->kc, m = h->m, k = h->ksub, dsub = h->dsub;
     std::vector<float> cent((size_t)kc * d), cbs((size_t)d * k);
@@ -5275,14 +5072,22 @@ try {
     HIP_TRY(hipStreamSynchronize(h->stream));
     TRY(d2h_copy(cent.data(), h->centroids.p, cent.size() * 4, h->stream));
     TRY(d2h_copy(cbs.data(), h->codebooks.p, cbs.size() * 4, h->stream));
-    if (h->u16) memcpy(lab.data(), h->lab16.data(), lab.size());
+    if (h->u16) memcpy(lab.data(), h->labmap.lab16.data(), lab.size());
     else HIP_TRY(hipMemcpy(lab.data(), h->labels.p, lab.size(), hipMemcpyDeviceToHost));
+    // the lists one behind the other, codes as labels: what ivfadc_get_lists hands out
+    const int cb = h->cb;
+    const int64_t ntot = h->mirror.ntotal();
+    std::vector<int64_t> off((size_t)kc + 1);
+    std::vector<uint8_t> codes((size_t)ntot * cb), narrow;
+    std::vector<uint32_t> all_ids((size_t)ntot);
+    h->mirror.gather(off.data(), codes.data(), all_ids.data(), cb);
+    if (h->u16) h->labmap.to_labels(ntot, codes.data());
     FileCloser fc{fopen(path, "wb")};
     FILE *f = fc.f;
     if (!f) return fail(IVFADC_ERR_INVALID, "cannot open %s for writing", path);
     const char *iname = index_bits == 8 ? "UInt8" : (index_bits == 16 ? "UInt16" : "UInt32");
     fprintf(f, "%d %d\n%lld %d %d %d\nNaiveQuantizer\nQuantizedArrays.OrthogonalQuantization\n%s\n%s\n"
-               "Distances.SqEuclidean\nDistances.SqEuclidean\nFloat32\n", d, kc, (long long)h->ntotal(), m, k, dsub, h->u16 ? "UInt16" : "UInt8",
+               "Distances.SqEuclidean\nDistances.SqEuclidean\nFloat32\n", d, kc, (long long)ntot, m, k, dsub, h->u16 ? "UInt16" : "UInt8",
             iname);
     bool ok = fwrite(cent.data(), 4, cent.size(), f) == cent.size();                  // centroid c = column c
     std::vector<float> row((size_t)k);
@@ -5303,11 +5108,10 @@ try {
             rot[i] = 0.0f;
         }
     }
-    std::vector<uint8_t> narrow, wide;
     for (int l = 0; l < kc && ok; ++l) {
-        const int64_t len = h->h_len[l];
+        const int64_t len = off[l + 1] - off[l];
         ok = fwrite(&len, 8, 1, f) == 1;
-        const uint32_t *ids = h->hl_ids[l].data();
+        const uint32_t *ids = all_ids.data() + off[l];
         if (index_bits == 32) {
             ok = ok && (len == 0 || fwrite(ids, 4, (size_t)len, f) == (size_t)len);
         } else {
@@ -5319,12 +5123,7 @@ try {
             }
             ok = ok && (len == 0 || fwrite(narrow.data(), 1, narrow.size(), f) == narrow.size());
         }
-        if (h->u16) {   // codeword indices -> labels
-            wide = h->hl_codes[l];
-            indices_to_labels(h, len, (uint16_t *)wide.data());
-            ok = ok && (len == 0 || fwrite(wide.data(), 1, (size_t)len * h->cb, f) == (size_t)len * h->cb);
-        } else
-        ok = ok && (len == 0 || fwrite(h->hl_codes[l].data(), 1, (size_t)len * m, f) == (size_t)len * m);
+        ok = ok && (len == 0 || fwrite(codes.data() + (size_t)off[l] * cb, 1, (size_t)len * cb, f) == (size_t)len * cb);
     }
     if (!ok) return fail(IVFADC_ERR_INVALID, "short write to %s", path);
     return IVFADC_OK;
@@ -5434,22 +5233,21 @@ try {
     }
     if (offsets[nclusters] != n) return fail(IVFADC_ERR_INVALID, "%s: the lists hold %lld entries, the header says %lld", path, (long long)offsets[nclusters], n);
     ivfadc_t *h = nullptr;
+    std::vector<uint8_t> idx;
     if (ub == 2) {
         // UInt16: labels distinct per block and every code a label of its block, checked here, before any device call
-        const uint16_t *lab16 = (const uint16_t *)lab.data(), *c16 = (const uint16_t *)codes.data();
-        std::vector<uint32_t> sorted;
-        int db = 0, dl = 0;
-        if (!sort_labels16(lab16, (int)m, (int)k, sorted, db, dl)) return fail(IVFADC_ERR_INVALID, "%s: duplicate label %d in codebook %d", path, dl, db);
-        for (long long p = 0; p < n; ++p)
-            for (long long i = 0; i < m; ++i)
-                if (find_label16(sorted, (int)k, (int)i, c16[(size_t)p * m + i]) < 0)
-                    return fail(IVFADC_ERR_INVALID, "%s: code %d of point %lld is not a label of codebook %lld", path, (int)c16[(size_t)p * m + i], p, i);
+        const uint16_t *lab16 = (const uint16_t *)lab.data();
+        const std::string prefix = std::string(path) + ": ";
+        list_mirror::LabelMap lm;
+        TRY(mirror_fail(lm.init16(lab16, (int)m, (int)k), true, prefix.c_str()));
+        TRY(mirror_fail(lm.to_indices(n, (const uint16_t *)codes.data(), idx), true, prefix.c_str()));
         TRY(create_impl(&h, device, (int)nrows, (int)nclusters, (int)m, (int)k, cent.data(), cbs.data(), nullptr, lab16));
     } else {
         TRY(ivfadc_create(&h, device, (int)nrows, (int)nclusters, (int)m, (int)k, cent.data(), cbs.data(), lab.data()));
     }
-    const int rc = ub == 2 ? ivfadc_set_lists_u16(h, offsets.data(), codes.data(), ids.data())
-                           : ivfadc_set_lists(h, offsets.data(), codes.data(), ids.data());
+    // (the offsets were built above and the 16-bit codes are in mirror form already; 8-bit codes are checked against the handle's labels)
+    const int rc = ub == 2 ? assign_lists(h, offsets.data(), idx.data(), ids.data(), "ivfadc_set_lists_u16")
+                           : set_lists_entry(h, offsets.data(), codes.data(), ids.data(), false);
     if (rc != IVFADC_OK) { ivfadc_destroy(h); return rc; }
     if (!rot_identity) h->rot = std::move(rotm);
     if (out_index_bits) *out_index_bits = ibytes * 8;

@@ -139,13 +139,8 @@ class IVFADCIndex:
         self._centroids = np.zeros((kc, d), np.float32)
         self._codebooks = np.zeros((m, ksub, d // m), np.float32)
         self._labels = np.zeros((m, ksub), self.code_type)
-        if self.code_type == np.uint16:
-            nat.check(nat.lib().ivfadc_get_quantizers_u16(h, nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
-                                                          self._labels.ctypes.data_as(C.c_void_p)))
-        else:
-            nat.check(nat.lib().ivfadc_get_quantizers(h, self._centroids.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      self._codebooks.ctypes.data_as(C.POINTER(C.c_float)),
-                                                      self._labels.ctypes.data_as(C.POINTER(C.c_uint8))))
+        get_quantizers, labels = self._entry("get_quantizers", self._labels)
+        nat.check(get_quantizers(h, nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float), labels))
         self.kc, self.d = self._centroids.shape
         self.m, self.ksub, self.dsub = self._codebooks.shape
         self._mirror = None
@@ -161,6 +156,15 @@ class IVFADCIndex:
         nat.check(nat.lib().ivfadc_get_rotation(self._h, None, out.ctypes.data_as(C.POINTER(C.c_float))))
         return out
 
+    def _entry(self, name, codes=None):
+        """The native entry `name` for this index's code width -- ivfadc_<name> for UInt8 codes, ivfadc_<name>_u16 for UInt16 -- and
+        the array `codes` (codes or labels of the index's code type) as that entry takes it."""
+        wide = self.code_type == np.uint16
+        fn = getattr(nat.lib(), "ivfadc_" + name + ("_u16" if wide else ""))
+        if codes is None:
+            return fn, None
+        return fn, (codes.ctypes.data_as(C.c_void_p) if wide else nat.ptr(codes, C.c_uint8))
+
     def _init_native(self, centroids, codebooks, labels, index_type, device):
         self._centroids = np.ascontiguousarray(centroids, np.float32)
         self._codebooks = np.ascontiguousarray(codebooks, np.float32)
@@ -173,14 +177,9 @@ class IVFADCIndex:
         assert self.m * self.dsub == self.d and self._labels.shape == (self.m, self.ksub)
         self.index_type = np.dtype(index_type)
         self._h = C.c_void_p()
-        if self.code_type == np.uint16:
-            nat.check(nat.lib().ivfadc_create_u16(C.byref(self._h), int(device), self.d, self.kc, self.m, self.ksub,
-                                                  nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
-                                                  self._labels.ctypes.data_as(C.c_void_p)))
-        else:
-            nat.check(nat.lib().ivfadc_create(C.byref(self._h), int(device), self.d, self.kc, self.m, self.ksub,
-                                              nat.ptr(self._centroids, C.c_float), nat.ptr(self._codebooks, C.c_float),
-                                              nat.ptr(self._labels, C.c_uint8)))
+        create, labels = self._entry("create", self._labels)
+        nat.check(create(C.byref(self._h), int(device), self.d, self.kc, self.m, self.ksub, nat.ptr(self._centroids, C.c_float),
+                         nat.ptr(self._codebooks, C.c_float), labels))
         self._mirror = None
 
     def clone_view(self):
@@ -291,14 +290,9 @@ class IVFADCIndex:
         offsets = np.ascontiguousarray(offsets, np.int64)
         n = int(offsets[-1])
         ids = np.ascontiguousarray(ids, np.uint32)
-        if self.code_type == np.uint16:
-            codes = np.ascontiguousarray(codes, np.uint16).reshape(n, self.m)
-            nat.check(nat.lib().ivfadc_set_lists_u16(self._h, nat.ptr(offsets, C.c_int64), codes.ctypes.data_as(C.c_void_p),
-                                                     nat.ptr(ids, C.c_uint32)))
-        else:
-            codes = np.ascontiguousarray(codes, np.uint8).reshape(n, self.m)
-            nat.check(nat.lib().ivfadc_set_lists(self._h, nat.ptr(offsets, C.c_int64), nat.ptr(codes, C.c_uint8),
-                                                 nat.ptr(ids, C.c_uint32)))
+        codes = np.ascontiguousarray(codes, self.code_type).reshape(n, self.m)
+        set_lists, codes_p = self._entry("set_lists", codes)
+        nat.check(set_lists(self._h, nat.ptr(offsets, C.c_int64), codes_p, nat.ptr(ids, C.c_uint32)))
         self._mirror = None
 
     def synth_lists(self, offsets, seed):
@@ -312,19 +306,15 @@ class IVFADCIndex:
             offsets = np.zeros(self.kc + 1, np.int64)
             codes = np.zeros((n, self.m), self.code_type)
             ids = np.zeros(n, np.uint32)
-            if self.code_type == np.uint16:
-                nat.check(nat.lib().ivfadc_get_lists_u16(self._h, nat.ptr(offsets, C.c_int64), codes.ctypes.data_as(C.c_void_p),
-                                                         nat.ptr(ids, C.c_uint32)))
-            else:
-                nat.check(nat.lib().ivfadc_get_lists(self._h, nat.ptr(offsets, C.c_int64), nat.ptr(codes, C.c_uint8),
-                                                     nat.ptr(ids, C.c_uint32)))
+            get_lists, codes_p = self._entry("get_lists", codes)
+            nat.check(get_lists(self._h, nat.ptr(offsets, C.c_int64), codes_p, nat.ptr(ids, C.c_uint32)))
             self._mirror = (offsets, codes, ids)
         return self._mirror
 
     def _append(self, pts, ids):
         pts = np.ascontiguousarray(pts, np.float32)
         ids = np.ascontiguousarray(ids, np.uint32)
-        append = nat.lib().ivfadc_append_u16 if self.code_type == np.uint16 else nat.lib().ivfadc_append
+        append, _ = self._entry("append")
         nat.check(append(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(ids, C.c_uint32), None, None))
         self._mirror = None
 
@@ -348,12 +338,8 @@ class IVFADCIndex:
         assert pts.shape[1] == self.d
         lst = np.zeros(pts.shape[0], np.int32)
         codes = np.zeros((pts.shape[0], self.m), self.code_type)
-        if self.code_type == np.uint16:
-            nat.check(nat.lib().ivfadc_encode_u16(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(lst, C.c_int32),
-                                                  codes.ctypes.data_as(C.c_void_p)))
-        else:
-            nat.check(nat.lib().ivfadc_encode(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(lst, C.c_int32),
-                                              nat.ptr(codes, C.c_uint8)))
+        encode, codes_p = self._entry("encode", codes)
+        nat.check(encode(self._h, pts.shape[0], nat.ptr(pts, C.c_float), nat.ptr(lst, C.c_int32), codes_p))
         return lst, codes
 
     # ---- reference-shaped views ----------------------------------------------------------------

@@ -431,3 +431,101 @@ def test_grid_stride_shift(native):
     assert g._delete_ids(dele) == removed and n // 2 - 1 <= removed <= n // 2
     wp.assert_device_equals(g, wp.ref_with_lists(oidx, *state), q, what="half deleted", plans=(-2,), knn=wp.numpy_exhaustive)
     print("grid_stride_shift: %.1f s wall, %d slots" % (time.time() - t0, slots))
+
+
+# ---- both code widths through one chain ---------------------------------------------------------------------------------------------
+OK, ERR_STATE = 0, 4
+# ivfadc_encode / ivfadc_encode_u16 on a handle of the other width, n = 0 and n = 1 (valid pointers), as the entries have always
+# answered: the 8-bit entry returns on n == 0 before it looks at the width, the _u16 entry looks at the width first
+CROSS_WIDTH_ENCODE = {("encode", 16, 0): OK, ("encode", 16, 1): ERR_STATE, ("encode_u16", 8, 0): ERR_STATE, ("encode_u16", 8, 1): ERR_STATE}
+
+
+def test_both_widths_one_chain(native, tmp_path):
+    """d = 16, m = 4, ksub = 256, kc = 5, 600 points, list 2 empty.  An 8-bit handle and its 16-bit re-expression (same codewords,
+    permuted uint16 labels out of 0 .. 65535) go through set lists, search, append 3 in place, append past a list's capacity, delete
+    across three lists with an absent id, shift by 1, save and load.  After every step the two mirrors agree through the label maps
+    and equal the numpy model, inplace_appends agree, and a K = 5, w = kc search returns identical bytes from both."""
+    import ctypes as C
+    from ivfadc_jl_amd import _native as nat
+    d, m, kc, n = 16, 4, 5, 600
+    cent, cbs, lab8 = helpers.make_quantizers(530, d, kc, m, 256, label_perm=True)
+    rng = np.random.default_rng(530)
+    lab16 = np.stack([rng.permutation(65536)[:256].astype(np.uint16) for _ in range(m)])
+    inv8 = np.zeros((m, 256), np.int64)
+    for i in range(m):
+        inv8[i, lab8[i]] = np.arange(256)
+
+    def widen(codes8):                                    # 8-bit labels -> codeword indices -> 16-bit labels
+        return np.stack([lab16[i][inv8[i][codes8[:, i]]] for i in range(m)], 1).astype(np.uint16).reshape(-1, m)
+
+    sizes = np.array([200, 150, 0, 130, 120])
+    offsets = np.zeros(kc + 1, np.int64)
+    np.cumsum(sizes, out=offsets[1:])
+    codes = np.stack([lab8[i][rng.integers(0, 256, n)] for i in range(m)], 1).astype(np.uint8)
+    ref = ora.OracleIndex(cent, cbs, lab8, offsets, codes, rng.permutation(n).astype(np.uint32))
+    g8 = native.IVFADCIndex.from_arrays(cent, cbs, lab8)
+    g16 = native.IVFADCIndex.from_arrays(cent, cbs, lab16)
+    assert g8.code_type == np.uint8 and g16.code_type == np.uint16
+    qs = rng.random((6, d), dtype=f32)
+    state = wp.lists_of(ref)
+    inplace = 0
+
+    def check(what):
+        l8, l16 = g8._lists(), g16._lists()
+        _same_lists(l8, state, "%s (8-bit)" % what)
+        _same_lists(l16, (state[0], widen(state[1]), state[2]), "%s (16-bit)" % what)
+        r8, r16 = g8.search_raw(qs, 5, kc), g16.search_raw(qs, 5, kc)
+        for a, b in zip(r8, r16):
+            assert a.tobytes() == b.tobytes(), what
+        helpers.assert_same_results(r8, wp.ref_knn(wp.ref_with_lists(ref, *state), qs, 5, kc), what=what)
+        assert g8.get_stats()["inplace_appends"] == g16.get_stats()["inplace_appends"] == inplace, what
+        assert len(g8) == len(g16) == int(state[0][-1])
+
+    def append(pts, ids, what):
+        nonlocal state
+        lst, new = ref.encode(pts)
+        g8._append(pts, np.asarray(ids, np.uint32))
+        g16._append(pts, np.asarray(ids, np.uint32))
+        state = wp.np_append(*state, lst, new, ids)
+        check(what)
+        return lst
+
+    g8.set_lists(*state)
+    g16.set_lists(state[0], widen(state[1]), state[2])
+    check("set lists")                                                          # (its search lays the capacity out)
+    cap = wp.capacity(np.diff(state[0]))
+    pts, lst, _ = wp.append_batch(ref, 531, 3)
+    assert (np.diff(state[0]) + np.bincount(lst, minlength=kc) <= cap).all()
+    inplace += 1
+    append(pts, [n, n + 1, n + 2], "append 3 in place")
+    cell2 = (cent[2] + f32(1e-3) * rng.standard_normal((200, d))).astype(f32)
+    past = int(cap[2] - np.diff(state[0])[2]) + 1                               # one more than the room the layout left behind list 2
+    cell2 = cell2[ref.encode(cell2)[0] == 2][:past]
+    assert cap[2] == 32 and 30 <= cell2.shape[0] == past <= 33
+    append(cell2, np.arange(n + 3, n + 3 + past), "append past the capacity of the list that was empty")      # no in-place append: a re-layout
+    dele = np.concatenate([state[2][[0, 1, int(state[0][1]) + 5, int(state[0][3]) + 7]], [0x7FFFFFF0]]).astype(np.uint32)[::-1]
+    *state, removed = wp.np_delete(*state, dele)
+    assert removed == 4 and g8._delete_ids(dele) == 4 and g16._delete_ids(dele) == 4
+    check("delete across three lists, one id absent")
+    g8._shift_ids(1)
+    g16._shift_ids(1)
+    state = wp.np_shift(*state, 1)
+    check("shift by 1")
+    f8, f16 = str(tmp_path / "w8.bin"), str(tmp_path / "w16.bin")
+    native.save_ivfadc_index(f8, g8)
+    native.save_ivfadc_index(f16, g16)
+    keep = (g8, g16)
+    g8, g16 = native.load_ivfadc_index(f8), native.load_ivfadc_index(f16)
+    assert g8.code_type == np.uint8 and g16.code_type == np.uint16
+    inplace = 0
+    check("save, then load")
+    # the entries of the other width
+    lib = nat.lib()
+    for (entry, bits, npts), want in CROSS_WIDTH_ENCODE.items():
+        h = (keep[1] if bits == 16 else keep[0])._h
+        p = np.ascontiguousarray(qs[:1])
+        out_list, out_codes = np.zeros(1, np.int32), np.zeros(2 * m, np.uint8)
+        rc = getattr(lib, "ivfadc_" + entry)(h, npts, nat.ptr(p, C.c_float), nat.ptr(out_list, C.c_int32),
+                                              out_codes.ctypes.data_as(C.c_void_p if entry.endswith("_u16") else C.POINTER(C.c_uint8)))
+        print("cross-width %s on a %d-bit handle, n = %d: %d" % (entry, bits, npts, rc))
+        assert rc == want, (entry, bits, npts, rc)
