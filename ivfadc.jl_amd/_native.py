@@ -15,7 +15,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
            os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
            os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
-           os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"),
+           os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]

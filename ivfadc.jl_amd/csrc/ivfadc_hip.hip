@@ -18,6 +18,7 @@
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
+#include "batch_plan.h"    // the schedule of the host-pointer searches: batches, upload groups, tokens, result blocks, device split (pure)
 #include "list_mirror.h"   // the host mirror of the lists, its edits, the label map and the device layout's arithmetic (pure)
 
 #include <algorithm>
@@ -3546,6 +3547,48 @@ static int ingest_rows(ivfadc_index *h, hipStream_t s, const void *src, void *ds
     return IVFADC_OK;
 }
 
+// The staging of a host call.  The four time buckets of ivfadc_host_stats are laps of one clock per call.
+struct HostClock {
+    double t = now_us();
+    double lap() { const double n = now_us(), dt = n - t; t = n; return dt; }
+};
+
+// src (null on entry: not decided yet) = where the kernels read a host array of rows: the caller's own array when the library knows it,
+// else pin_in, which then takes bytes [off, off + len) of the rows
+static int stage_queries(ivfadc_index *h, const void *rows, size_t bytes, size_t off, size_t len, const uint8_t *&src)
+{
+    if (!src && host_known(rows, bytes)) src = (const uint8_t *)rows;
+    if (!src) {
+        TRY(h->pin_in.ensure(bytes));
+        src = (const uint8_t *)h->pin_in.p;
+    }
+    if (src != rows) memcpy((uint8_t *)h->pin_in.p + off, (const uint8_t *)rows + off, len);
+    return IVFADC_OK;
+}
+// Where the kernels write: c keeps the caller's arrays when the library knows all three (the handle remembers: hc_out_direct), else it is
+// pointed at the block carved out of pin_out, which copy_out hands over once the search has ended
+static int stage_results(ivfadc_index *h, SearchCall &c)
+{
+    const batch_plan::ResultBlock b = batch_plan::result_bytes((size_t)c.nq, (size_t)c.K);
+    h->hc_out_direct = host_known(c.ids, b.ids_len()) && host_known(c.dists, b.ids_len()) && host_known(c.counts, b.counts_len());
+    if (h->hc_out_direct) return IVFADC_OK;
+    TRY(h->pin_out.ensure(b.total));
+    uint8_t *po = (uint8_t *)h->pin_out.p;
+    c.ids = (uint32_t *)(po + b.ids);
+    c.dists = (float *)(po + b.dists);
+    c.counts = (int32_t *)(po + b.counts);
+    return IVFADC_OK;
+}
+// the first to.nq rows of a packed block of block_rows rows, into the three arrays of `to`
+static void copy_out(const SearchCall &to, const void *block, int64_t block_rows)
+{
+    const batch_plan::ResultBlock src = batch_plan::result_bytes((size_t)block_rows, (size_t)to.K), n = batch_plan::result_bytes((size_t)to.nq, (size_t)to.K);
+    const uint8_t *p = (const uint8_t *)block;
+    memcpy(to.ids, p + src.ids, n.ids_len());
+    memcpy(to.dists, p + src.dists, n.ids_len());
+    memcpy(to.counts, p + src.counts, n.counts_len());
+}
+
 // host-pointer search in two halves so several handles (devices) can be in flight at once (ivfadc_mg_search)
 // hc: this handle's whole batch as a host entry has it: queries, results and supplied probes (validated by the caller) in host memory,
 // mask rows on the device already (stage_mask_numbers)
@@ -3553,25 +3596,19 @@ static int search_enqueue(ivfadc_t *h, const SearchCall &hc)
 try {
     TRY(set_device(h));
     h->dev_entry = false;
-    const double t0 = now_us();
+    HostClock clk;
     const int64_t nq = hc.nq;
     const size_t qbytes = (size_t)nq * h->d * 4;
-    const size_t idb = (size_t)nq * hc.K * 4, cb = (size_t)nq * 4;
     h->hstats.calls++;
     h->hstats.batches++;
-    const float *src = hc.q;
-    if (host_known(hc.q, qbytes)) {
-        h->hstats.queries_direct++;
-    } else {
-        TRY(h->pin_in.ensure(qbytes));
-        memcpy(h->pin_in.p, hc.q, qbytes);
-        src = (const float *)h->pin_in.p;
-    }
-    const double t1 = now_us();
+    const uint8_t *src = nullptr;
+    TRY(stage_queries(h, hc.q, qbytes, 0, qbytes, src));
+    h->hstats.queries_direct += src == (const uint8_t *)hc.q;
+    const double t_in = clk.lap();
     if (h->dirty) TRY(upload_lists(h));
     SearchCall c = hc;   // the same call in device terms
     c.whole_batch = true;
-    c.q = src;
+    c.q = (const float *)src;
     static const bool no_zero_copy = getenv("IVFADC_NO_ZERO_COPY") != nullptr;
     if (!no_zero_copy && !hc.pre() && !hc.masked() && h->part_n <= 1 && (((uintptr_t)src) & 15) == 0 && sq_eligible(h, nq, hc.K, hc.w)) {
         // the latency path: a handful of rows, read in place by the two launches (a few KB over PCIe; no ingest step in the chain)
@@ -3581,16 +3618,8 @@ try {
         TRY(ingest_rows(h, h->stream, src, h->q_stage.p, qbytes));
         c.q = h->q_stage.as<float>();
     }
-    h->hc_out_direct = host_known(hc.ids, idb) && host_known(hc.dists, idb) && host_known(hc.counts, cb);
-    if (h->hc_out_direct) {
-        h->hstats.results_direct++;
-    } else {
-        TRY(h->pin_out.ensure(2 * idb + cb));
-        uint8_t *po = (uint8_t *)h->pin_out.p;
-        c.ids = (uint32_t *)po;
-        c.dists = (float *)(po + idb);
-        c.counts = (int32_t *)(po + 2 * idb);
-    }
+    TRY(stage_results(h, c));
+    h->hstats.results_direct += h->hc_out_direct;
     if (hc.pre()) {
         const size_t pb = (size_t)nq * hc.w * 4;
         TRY(h->pre_list.ensure(pb));
@@ -3601,26 +3630,19 @@ try {
         c.pre_dc = h->pre_dc.as<float>();
     }
     TRY(search_dev(h, c));
-    h->hstats.stage_in_us += t1 - t0;
-    h->hstats.enqueue_us += now_us() - t1;
+    h->hstats.stage_in_us += t_in;
+    h->hstats.enqueue_us += clk.lap();
     return IVFADC_OK;
 } IVF_CATCH
 
 static int search_finish(ivfadc_t *h, const SearchCall &hc)
 try {
     TRY(set_device(h));
-    const double t0 = now_us();
+    HostClock clk;
     TRY(wait_stream(h));
-    const double t1 = now_us();
-    if (!h->hc_out_direct) {
-        const size_t idb = (size_t)hc.nq * hc.K * 4, cb = (size_t)hc.nq * 4;
-        const uint8_t *hout = (const uint8_t *)h->pin_out.p;
-        memcpy(hc.ids, hout, idb);
-        memcpy(hc.dists, hout + idb, idb);
-        memcpy(hc.counts, hout + 2 * idb, cb);
-    }
-    h->hstats.wait_us += t1 - t0;
-    h->hstats.stage_out_us += now_us() - t1;
+    h->hstats.wait_us += clk.lap();
+    if (!h->hc_out_direct) copy_out(hc, h->pin_out.p, hc.nq);
+    h->hstats.stage_out_us += clk.lap();
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -3870,59 +3892,14 @@ static void fold_view_counters(ivfadc_index *h, ivfadc_index *v)
 }
 
 // A run of consecutive batches from host memory: what a serving loop of knn_search(ivfadc, points, k; w) calls does (index.jl:261-273 once
-// per batch), as ONE call -- batch i is searched with batch i + 1 named as its successor (ivfadc_set_next_queries / ivfadc_set_query_token
-// with tokens of the library's own, on buffers the library owns: nothing the caller does can make a stale row match).  Each batch's results
-// are exactly ivfadc_search's.  The queries are ingested batch by batch on a copy lane of their own (a stream that carries nothing else),
-// a few batches ahead of the searches, and every search writes its results where the caller reads them: the device never waits for the
-// host between batches, and the call ends when the two search lanes have drained.
-int ivfadc_search_batches(ivfadc_t *h, int nbatches, const int64_t *batch_nq, const float *queries, int K, int w, uint32_t *out_ids,
-                          float *out_dists, int32_t *out_counts)
-try {
-    HandleLock lk_(h);
-    if (nbatches < 0 || (nbatches > 0 && !batch_nq)) return fail(IVFADC_ERR_INVALID, "nbatches < 0 or null batch sizes");
-    int64_t total = 0;
-    for (int b = 0; b < nbatches; ++b) {
-        if (batch_nq[b] < 0) return fail(IVFADC_ERR_INVALID, "batch %d: nq < 0", b);
-        total += batch_nq[b];
-    }
-    TRY(check_search_args(h, total, K, w));
-    if (total == 0) return IVFADC_OK;
-    if (!queries || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
-    TRY(set_device(h));
-    const double t_enter = now_us();
-    const size_t qbytes = (size_t)total * h->d * 4;
-    const size_t idb = (size_t)total * K * 4, cb = (size_t)total * 4;
-    const size_t obytes = 2 * idb + cb;
-    const bool q_known = host_known(queries, qbytes);
-    const bool o_known = host_known(out_ids, idb) && host_known(out_dists, idb) && host_known(out_counts, cb);
-    TRY(h->q_stage.ensure(qbytes));
-    if (!q_known) TRY(h->pin_in.ensure(qbytes));
-    if (!o_known) TRY(h->pin_out.ensure(obytes));
-    // where the kernels write: the caller's arrays or the library's pinned block
-    uint8_t *ob = (uint8_t *)h->pin_out.p;
-    uint32_t *oi = o_known ? out_ids : (uint32_t *)ob;
-    float *od = o_known ? out_dists : (float *)(ob + idb);
-    int32_t *oc = o_known ? out_counts : (int32_t *)(ob + 2 * idb);
-    const uint8_t *qsrc = q_known ? (const uint8_t *)queries : (const uint8_t *)h->pin_in.p;
-    h->hstats.calls++;
-    if (q_known) h->hstats.queries_direct++;
-    if (o_known) h->hstats.results_direct++;
-    std::vector<int64_t> start, cnt;   // the non-empty batches, in order
-    int64_t run = 0;
-    for (int b = 0; b < nbatches; ++b) {
-        if (batch_nq[b] > 0) { start.push_back(run); cnt.push_back(batch_nq[b]); }
-        run += batch_nq[b];
-    }
-    const size_t nbat = start.size();
-    h->hstats.batches += (int64_t)nbat;
-    const SearchCall all{total, h->d, K, w, h->q_stage.as<float>(), oi, od, oc};
-    const uint64_t base = h->own_token;
-    h->own_token += nbat;
-    auto token_of = [&](size_t i) { return (base + i + 1) | ((uint64_t)1 << 63); };   // never 0; the library's own numbering
-    // Two batches in flight: even batches on this handle, odd ones on a view of it (second stream, second workspace), each lane naming
-    // ITS next batch (i + 2) as the successor.  Not while profiling (the statistics are this handle's) and not for a view.
+// per batch), as ONE call.  Each batch's results are exactly ivfadc_search's.  The schedule is batch_plan.h's.
+
+// The lanes: two batches in flight, even batches on this handle and odd ones on a view of it (second stream, second workspace) -- not
+// while profiling (the statistics are this handle's), not for a view, not for a single batch -- and the copy lane beside them.
+static int setup_batch_lanes(ivfadc_index *h, size_t nbat, ivfadc_index *&lane2)
+{
     static const bool no_pipe = getenv("IVFADC_NO_PIPELINE") != nullptr;
-    ivfadc_index *lane2 = nullptr;
+    lane2 = nullptr;
     if (h->pipe_view && h->pipe_view->view_gen != h->generation) {
         fold_view_counters(h, h->pipe_view);
         ivfadc_destroy(h->pipe_view);
@@ -3940,149 +3917,172 @@ try {
     // (stream priorities do not help here -- measured: a copy lane or a second lane of another priority class is no faster in a process
     // that owns few streams and up to 65 % slower in one that owns many; profiles/r05_batches_stream_priorities.txt)
     if (!h->copy_stream) HIP_TRY(hipStreamCreateWithFlags(&h->copy_stream, hipStreamNonBlocking));
-    {
-        // ... and the copy lane beside both search lanes (probed once per pair of lanes)
-        const hipStream_t l2 = lane2 ? lane2->stream : nullptr;
-        if (h->copy_probed_a != h->stream || h->copy_probed_b != l2) {
-            const hipStream_t fixed[2] = {h->stream, l2};
-            TRY(ensure_overlap(fixed, 2, &h->copy_stream, &h->hstats.streams_replaced));
-            h->copy_probed_a = h->stream;
-            h->copy_probed_b = l2;
-        }
+    // ... and the copy lane beside both search lanes (probed once per pair of lanes)
+    const hipStream_t l2 = lane2 ? lane2->stream : nullptr;
+    if (h->copy_probed_a != h->stream || h->copy_probed_b != l2) {
+        const hipStream_t fixed[2] = {h->stream, l2};
+        TRY(ensure_overlap(fixed, 2, &h->copy_stream, &h->hstats.streams_replaced));
+        h->copy_probed_a = h->stream;
+        h->copy_probed_b = l2;
     }
-    // However this call ends, nothing it enqueued is left running: a failing search returns with both lanes and the copy lane drained
-    // (the next call reuses the staging buffers, and the caller's arrays are the caller's again on return).
-    struct Drain {
-        ivfadc_index *h, *lane2;
-        bool armed;
-        ~Drain()
-        {
-            if (!armed) return;
-            const std::string keep = g_err;
-            if (hipSetDevice(h->device) == hipSuccess) {
-                if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
-                if (lane2 && lane2->stream) (void)hipStreamSynchronize(lane2->stream);
-                if (h->stream) (void)hipStreamSynchronize(h->stream);
+    return IVFADC_OK;
+}
+
+// However a run ends, nothing it enqueued is left running: a failing search returns with both lanes and the copy lane drained (the next
+// call reuses the staging buffers, and the caller's arrays are the caller's again on return).
+struct BatchDrain {
+    ivfadc_index *h, *lane2;
+    bool armed;
+    ~BatchDrain()
+    {
+        if (!armed) return;
+        const std::string keep = g_err;
+        if (hipSetDevice(h->device) == hipSuccess) {
+            if (h->copy_stream) (void)hipStreamSynchronize(h->copy_stream);
+            if (lane2 && lane2->stream) (void)hipStreamSynchronize(lane2->stream);
+            if (h->stream) (void)hipStreamSynchronize(h->stream);
+        }
+        g_err = keep;
+    }
+};
+
+// From a lane's second search on, the HOST waits for a missing ingest (the lane still has its previous search to run, and the copy lane
+// moves a batch in a third of the time a search takes, so this is rare and short): a wait in the search stream would cost the lane's queue
+// ~6 us per search whether or not the event has fired by the time the queue gets there.  ev is null on return once it has fired.
+static int host_wait(hipEvent_t &ev)
+{
+    if (!ev) return IVFADC_OK;
+    const double t0 = now_us();
+    for (;;) {
+        const hipError_t q = hipEventQuery(ev);
+        if (q == hipSuccess) { ev = nullptr; return IVFADC_OK; }
+        if (q != hipErrorNotReady) return fail(IVFADC_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+        if (now_us() - t0 > 500.0) return IVFADC_OK;   // (something else owns the copy engine's attention: let the stream wait)
+    }
+}
+
+// The issue loop of a run: batch_plan's schedule, in HIP calls and searches
+struct BatchRun {
+    ivfadc_index *h, *lane2;
+    const batch_plan::Batches &bt;
+    const batch_plan::Groups &gr;
+    const void *queries;    // the caller's rows ...
+    const uint8_t *qsrc;    // ... and where the copy lane reads them (stage_queries)
+    SearchCall all;         // the whole run in device terms: rows in q_stage, results where the kernels write them (stage_results)
+    uint64_t base;          // of the run's tokens
+    batch_plan::IngestTracker tr;
+    size_t up_next = 0;     // groups [0, up_next) are on their way
+    double t_stage = 0.0;   // host time spent filling pin_in
+
+    // the copy lane: one ingest launch and one event per group, until want_batches batches are on their way
+    int upload_until(size_t want_batches)
+    {
+        const size_t last = std::min(want_batches, bt.size());
+        for (; up_next < gr.size() && gr.first[up_next] < last; ++up_next) {
+            const batch_plan::ByteRange r = batch_plan::group_bytes(bt, gr, up_next, (size_t)h->d * 4);
+            if (qsrc != queries) {
+                HostClock c;
+                TRY(stage_queries(h, queries, 0, r.off, r.bytes, qsrc));
+                t_stage += c.lap();
             }
-            g_err = keep;
+            TRY(ingest_rows(h, h->copy_stream, qsrc + r.off, (uint8_t *)h->q_stage.p + r.off, r.bytes));
+            HIP_TRY(hipEventRecord(h->ingest_ev[up_next], h->copy_stream));
         }
-    } drain{h, lane2, true};
-    const size_t stride = lane2 ? 2 : 1;
-    auto lane_of = [&](size_t i) { return (lane2 && (i & 1)) ? lane2 : h; };
-    // Upload groups: consecutive batches that travel together (one ingest launch, one event): one batch per lane -- the first searches
-    // start as soon as THEIR rows are on the device, and the copy lane, which moves a batch in a third of the time a lane needs to search
-    // one, is further ahead with every group -- or more where a call brings more than ~500 batches (at most ~256 groups per call).
-    std::vector<size_t> gb;   // group g = batches [gb[g], gb[g + 1])
-    {
-        // (the very first groups are single batches: lane 0 starts when batch 0 has landed, while batch 1 is still on its way)
-        const size_t per = std::max<size_t>(stride, (nbat + 251) / 252);
-        size_t at = 0;
-        while (at < nbat) {
-            gb.push_back(at);
-            at += (at < stride) ? 1 : per;
-        }
-        gb.push_back(nbat);
+        return IVFADC_OK;
     }
-    const size_t ngroups = gb.size() - 1;
-    std::vector<size_t> group_of(nbat);
-    for (size_t g = 0; g < ngroups; ++g)
-        for (size_t i = gb[g]; i < gb[g + 1]; ++i) group_of[i] = g;
-    while (h->ingest_ev.size() < ngroups) {
+
+    // ev: the event the lane still has to wait for before it reads `batch` (null: none; one that has fired costs the lane nothing)
+    int pending_event(size_t lane, size_t batch, hipEvent_t &ev)
+    {
+        ev = nullptr;
+        const size_t g = tr.needs(lane, batch);
+        if (g == batch_plan::IngestTracker::NOTHING) return IVFADC_OK;
+        if (!tr.seen(g)) {
+            const hipError_t q = hipEventQuery(h->ingest_ev[g]);
+            if (q == hipSuccess) tr.fired(g);
+            else if (q != hipErrorNotReady) return fail(IVFADC_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(q));
+        }
+        if (!tr.seen(g)) ev = h->ingest_ev[g];
+        return IVFADC_OK;
+    }
+
+    int issue()
+    {
+        const size_t nbat = bt.size(), stride = lane2 ? 2 : 1;
+        for (size_t i = 0; i < nbat; ++i) {
+            const batch_plan::Step st = batch_plan::step_of(i, nbat, stride, base);
+            ivfadc_index *ln = st.lane ? lane2 : h;
+            TRY(upload_until(st.on_their_way));
+            hipEvent_t ev = nullptr;
+            TRY(pending_event(st.lane, i, ev));   // this batch's own rows: before the search's first launch
+            if (i >= stride) TRY(host_wait(ev));  // (the first search of a lane must start the moment its rows land: its wait goes into the stream)
+            if (ev) HIP_TRY(hipStreamWaitEvent(ln->stream, ev, 0));
+            ln->cur_token = st.token;             // batch i's rows, if any stand, were hinted with this very token by the lane's step before
+            ln->hint_ev = nullptr;
+            if (st.has_next) {
+                ln->hint_q = all.slice(bt.start[st.next], bt.cnt[st.next]).q;
+                ln->hint_nq = bt.cnt[st.next];
+                ln->hint_token = st.next_token;
+                TRY(pending_event(st.lane, st.next, ev));   // (read by this search's riders only: waited for in front of the scan launch)
+                if (i >= stride) TRY(host_wait(ev));
+                ln->hint_ev = ev;
+            }
+            SearchCall cb = all.slice(bt.start[i], bt.cnt[i]);
+            cb.whole_batch = true;   // (of its lane's search: the hint names its successor)
+            TRY(search_dev(ln, cb));
+        }
+        return IVFADC_OK;
+    }
+};
+
+int ivfadc_search_batches(ivfadc_t *h, int nbatches, const int64_t *batch_nq, const float *queries, int K, int w, uint32_t *out_ids,
+                          float *out_dists, int32_t *out_counts)
+try {
+    HandleLock lk_(h);
+    if (nbatches < 0 || (nbatches > 0 && !batch_nq)) return fail(IVFADC_ERR_INVALID, "nbatches < 0 or null batch sizes");
+    batch_plan::Batches bt;
+    const int bad = batch_plan::non_empty_batches(batch_nq, nbatches, bt);
+    if (bad >= 0) return fail(IVFADC_ERR_INVALID, "batch %d: nq < 0", bad);
+    TRY(check_search_args(h, bt.total, K, w));
+    if (bt.total == 0) return IVFADC_OK;
+    if (!queries || !out_ids || !out_dists || !out_counts) return fail(IVFADC_ERR_INVALID, "null buffer");
+    TRY(set_device(h));
+    HostClock clk;
+    const size_t nbat = bt.size(), qbytes = (size_t)bt.total * h->d * 4;
+    const SearchCall hc{bt.total, h->d, K, w, queries, out_ids, out_dists, out_counts};   // the run as the caller has it
+    TRY(h->q_stage.ensure(qbytes));
+    const uint8_t *qsrc = nullptr;
+    TRY(stage_queries(h, queries, qbytes, 0, 0, qsrc));   // (decided here; pin_in is filled group by group)
+    SearchCall all = hc;
+    all.q = h->q_stage.as<float>();
+    TRY(stage_results(h, all));
+    h->hstats.calls++;
+    h->hstats.queries_direct += qsrc == (const uint8_t *)queries;
+    h->hstats.results_direct += h->hc_out_direct;
+    h->hstats.batches += (int64_t)nbat;
+    const uint64_t base = h->own_token;
+    h->own_token += nbat;
+    ivfadc_index *lane2;
+    TRY(setup_batch_lanes(h, nbat, lane2));
+    BatchDrain drain{h, lane2, true};
+    const batch_plan::Groups gr = batch_plan::upload_groups(nbat, lane2 ? 2 : 1);
+    while (h->ingest_ev.size() < gr.size()) {
         hipEvent_t e;
         HIP_TRY(hipEventCreateWithFlags(&e, hipEventDisableTiming));
         h->ingest_ev.push_back(e);
     }
-    std::vector<char> ev_seen(ngroups, 0);   // 1: the group's ingest is known to have finished
-    size_t up_next = 0;                      // groups [0, up_next) are on their way
-    double t_stage = 0.0;
-    auto upload_until = [&](size_t want_batches) -> int {
-        const size_t last = std::min(want_batches, nbat);
-        while (up_next < ngroups && gb[up_next] < last) {
-            const size_t b0 = gb[up_next], b1 = gb[up_next + 1];
-            const size_t off = (size_t)start[b0] * h->d * 4;
-            const size_t bytes = ((size_t)start[b1 - 1] + (size_t)cnt[b1 - 1] - (size_t)start[b0]) * h->d * 4;
-            if (!q_known) {
-                const double t0 = now_us();
-                memcpy((uint8_t *)h->pin_in.p + off, (const uint8_t *)queries + off, bytes);
-                t_stage += now_us() - t0;
-            }
-            TRY(ingest_rows(h, h->copy_stream, qsrc + off, (uint8_t *)h->q_stage.p + off, bytes));
-            HIP_TRY(hipEventRecord(h->ingest_ev[up_next], h->copy_stream));
-            ++up_next;
-        }
-        return IVFADC_OK;
-    };
-    // A lane is held back only by an ingest that has not finished when its search is issued: events that have fired cost the lane nothing
-    // (a wait in a search stream idles its queue for microseconds whether the event has fired or not).  The copy lane is in order, so
-    // the newest group a search needs covers the ones before it.  Returns the event the lane still has to wait for (null: none).
-    std::vector<size_t> lane_done(2, 0);   // groups [0, lane_done[l]) are known complete to lane l (seen fired, or waited for in its stream)
-    auto pending_event = [&](size_t lane_ix, size_t batch, hipEvent_t &ev) -> int {
-        ev = nullptr;
-        const size_t g = group_of[std::min(batch, nbat - 1)];
-        if (lane_done[lane_ix] > g) return IVFADC_OK;
-        if (!ev_seen[g]) {
-            const hipError_t q = hipEventQuery(h->ingest_ev[g]);
-            if (q == hipSuccess) { for (size_t x = 0; x <= g; ++x) ev_seen[x] = 1; }
-            else if (q != hipErrorNotReady) return fail(IVFADC_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(q));
-        }
-        if (!ev_seen[g]) ev = h->ingest_ev[g];
-        lane_done[lane_ix] = g + 1;          // (the caller puts the wait into the lane's stream, or hands it to the search)
-        return IVFADC_OK;
-    };
-    // From a lane's second search on, the HOST waits for a missing ingest (the lane still has its previous search to run, and the copy
-    // lane moves a batch in a third of the time a search takes, so this is rare and short): a wait in the search stream would cost the
-    // lane's queue ~6 us per search whether or not the event has fired by the time the queue gets there.  The first search of a lane
-    // must start the moment its rows land: there the wait goes into the stream.
-    auto host_wait = [&](hipEvent_t &ev) -> int {
-        if (!ev) return IVFADC_OK;
-        const double t0 = now_us();
-        for (;;) {
-            const hipError_t q = hipEventQuery(ev);
-            if (q == hipSuccess) { ev = nullptr; return IVFADC_OK; }
-            if (q != hipErrorNotReady) return fail(IVFADC_ERR_HIP, "hipEventQuery failed: %s", hipGetErrorString(q));
-            if (now_us() - t0 > 500.0) return IVFADC_OK;   // (something else owns the copy engine's attention: let the stream wait)
-        }
-    };
-    for (size_t i = 0; i < nbat; ++i) {
-        ivfadc_index *ln = lane_of(i);
-        const size_t lane_ix = (lane2 && (i & 1)) ? 1 : 0;
-        TRY(upload_until(i + 2 * stride + 1));   // batch i, the one it names as its successor, and the group after that are on their way
-        hipEvent_t ev = nullptr;
-        TRY(pending_event(lane_ix, i, ev));  // this batch's own rows: before the search's first launch
-        if (i >= stride) TRY(host_wait(ev));
-        if (ev) HIP_TRY(hipStreamWaitEvent(ln->stream, ev, 0));
-        ln->cur_token = token_of(i);         // batch i's rows, if any stand, were hinted with this very token by the lane's step before
-        ln->hint_ev = nullptr;
-        if (i + stride < nbat) {
-            ln->hint_q = all.slice(start[i + stride], cnt[i + stride]).q;
-            ln->hint_nq = cnt[i + stride];
-            ln->hint_token = token_of(i + stride);
-            // the successor's rows are read by the riders of this search's scan launch only: the wait for them goes in front of THAT
-            // launch, behind the search's own coarse stage
-            TRY(pending_event(lane_ix, i + stride, ev));
-            if (i >= stride) TRY(host_wait(ev));
-            ln->hint_ev = ev;
-        }
-        SearchCall cb = all.slice(start[i], cnt[i]);
-        cb.whole_batch = true;   // (of its lane's search: the hint names its successor)
-        TRY(search_dev(ln, cb));
-    }
-    const double t_issued = now_us();
+    BatchRun run{h, lane2, bt, gr, queries, qsrc, all, base, batch_plan::IngestTracker(gr)};
+    TRY(run.issue());
+    const double t_issue = clk.lap();
     if (lane2) TRY(wait_stream(lane2));
     TRY(wait_stream(h));
     drain.armed = false;   // (the copy lane's work ended before the searches that read it)
-    const double t_done = now_us();
-    if (!o_known) {
-        const uint8_t *hout = (const uint8_t *)h->pin_out.p;
-        memcpy(out_ids, hout, idb);
-        memcpy(out_dists, hout + idb, idb);
-        memcpy(out_counts, hout + 2 * idb, cb);
-    }
-    const double t_out = now_us();
-    h->hstats.stage_in_us += t_stage;
-    h->hstats.enqueue_us += (t_issued - t_enter) - t_stage;
-    h->hstats.wait_us += t_done - t_issued;
-    h->hstats.stage_out_us += t_out - t_done;
+    const double t_wait = clk.lap();
+    if (!h->hc_out_direct) copy_out(hc, h->pin_out.p, hc.nq);
+    h->hstats.stage_in_us += run.t_stage;
+    h->hstats.enqueue_us += t_issue - run.t_stage;
+    h->hstats.wait_us += t_wait;
+    h->hstats.stage_out_us += clk.lap();
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -4303,9 +4303,6 @@ try {
     return first;
 } IVF_CATCH
 
-// device r's block of a batch of nq queries split over G devices: contiguous, sizes differ by at most one
-static inline int64_t mg_lo(int64_t r, int64_t nq, int64_t G) { return r * (nq / G) + std::min<int64_t>(r, nq % G); }
-
 int ivfadc_mg_search(ivfadc_mg_t *g, int64_t nq, const float *queries, int K, int w, uint32_t *out_ids, float *out_dists,
                      int32_t *out_counts)
 try {
@@ -4322,7 +4319,7 @@ try {
     if (g->gather_mode == 0) {
         // enqueue every device's block, then collect: the devices run concurrently
         for (int64_t r = 0; r < G; ++r) {
-            const int64_t a = mg_lo(r, nq, G), b = mg_lo(r + 1, nq, G);
+            const int64_t a = batch_plan::mg_lo(r, nq, G), b = batch_plan::mg_lo(r + 1, nq, G);
             if (b <= a) continue;
             const int rc = search_enqueue(g->dev[r], all.slice(a, b - a));
             if (rc != IVFADC_OK) {
@@ -4335,7 +4332,7 @@ try {
             }
         }
         for (int64_t r = 0; r < G; ++r) {
-            const int64_t a = mg_lo(r, nq, G), b = mg_lo(r + 1, nq, G);
+            const int64_t a = batch_plan::mg_lo(r, nq, G), b = batch_plan::mg_lo(r + 1, nq, G);
             if (b > a) TRY(search_finish(g->dev[r], all.slice(a, b - a)));
         }
         return IVFADC_OK;
@@ -4344,7 +4341,8 @@ try {
     // blocks, the collective's contract) in device memory; ONE all-gather per batch; the host reads device 0's copy
     RcclApi &api = rccl_api();
     const int64_t nql = (nq + G - 1) / G;
-    const size_t blk_words = (size_t)nql * (2 * (size_t)K + 1);
+    const batch_plan::ResultBlock blk = batch_plan::result_words((size_t)nql, (size_t)K);   // (in 32-bit words, the collective's unit)
+    const size_t blk_words = blk.total;
     // a failure on device r must not leave devices 0 .. r-1 with work in flight that nothing waits for, nor an RCCL group open (the
     // next collective of the process would be absorbed into it): remember the first failure, finish the bookkeeping, then report
     int first_rc = IVFADC_OK;
@@ -4355,7 +4353,7 @@ try {
     int64_t enq = 0;
     for (int64_t r = 0; r < G && first_rc == IVFADC_OK; ++r) {
         ivfadc_t *h = g->dev[r];
-        const int64_t a = mg_lo(r, nq, G), b = mg_lo(r + 1, nq, G);
+        const int64_t a = batch_plan::mg_lo(r, nq, G), b = batch_plan::mg_lo(r + 1, nq, G);
         auto one = [&]() -> int {
             TRY(set_device(h));
             TRY(h->out_ids.ensure(blk_words * 4));
@@ -4363,15 +4361,12 @@ try {
             if (b > a) {
                 const size_t qbytes = (size_t)(b - a) * d * 4;
                 TRY(h->q_stage.ensure(qbytes));
-                const float *src = all.slice(a, b - a).q;
-                if (!host_known(src, qbytes)) {
-                    TRY(h->pin_in.ensure(qbytes));
-                    memcpy(h->pin_in.p, src, qbytes);
-                    src = (const float *)h->pin_in.p;
-                }
+                const float *rows = all.slice(a, b - a).q;
+                const uint8_t *src = nullptr;
+                TRY(stage_queries(h, rows, qbytes, 0, qbytes, src));
                 TRY(ingest_rows(h, h->stream, src, h->q_stage.p, qbytes));
                 uint32_t *o = h->out_ids.as<uint32_t>();
-                TRY(search_dev(h, SearchCall{b - a, d, K, w, h->q_stage.as<float>(), o, (float *)(o + (size_t)nql * K), (int32_t *)(o + 2 * (size_t)nql * K)}));
+                TRY(search_dev(h, SearchCall{b - a, d, K, w, h->q_stage.as<float>(), o + blk.ids, (float *)(o + blk.dists), (int32_t *)(o + blk.counts)}));
             }
             return IVFADC_OK;
         };
@@ -4415,11 +4410,8 @@ try {
     }
     const uint32_t *hg = (const uint32_t *)g->host_gath.p;
     for (int64_t r = 0; r < G; ++r) {
-        const int64_t a = mg_lo(r, nq, G), b = mg_lo(r + 1, nq, G);
-        const uint32_t *blk = hg + (size_t)r * blk_words;
-        memcpy(out_ids + (size_t)a * K, blk, (size_t)(b - a) * K * 4);
-        memcpy(out_dists + (size_t)a * K, blk + (size_t)nql * K, (size_t)(b - a) * K * 4);
-        memcpy(out_counts + a, blk + 2 * (size_t)nql * K, (size_t)(b - a) * 4);
+        const int64_t a = batch_plan::mg_lo(r, nq, G), b = batch_plan::mg_lo(r + 1, nq, G);
+        copy_out(all.slice(a, b - a), hg + (size_t)r * blk_words, nql);
     }
     return IVFADC_OK;
 } IVF_CATCH

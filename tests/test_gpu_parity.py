@@ -2204,6 +2204,62 @@ def test_search_batches_known_memory_and_ragged_batches(native, known):
         p.close()
 
 
+_EDGE_CYCLE = (1, 0, 2, 3, 0, 0, 1)   # batch sizes: empty batches on both sides of the upload groups' boundaries
+_EDGE_CASE = {}
+
+
+def _schedule_edge_case():
+    """The index, the queries of the longest run (757 non-empty batches) and the oracle's answer to them, computed once: every shorter run
+    searches a prefix of the same rows."""
+    if not _EDGE_CASE:
+        oidx, _ = helpers.build_index(45, 3000, 128, 32, 8, 256)
+        sizes = _edge_sizes(757)
+        qs = np.random.default_rng(11).random((int(sizes.sum()), 128), dtype=np.float32)
+        exp = oidx.knn_search(qs, 10, 4)
+        for a in exp:
+            a.setflags(write=False)
+        _EDGE_CASE.update(oidx=oidx, qs=qs, exp=exp)
+    return _EDGE_CASE
+
+
+def _edge_sizes(nonempty):
+    sizes, have = [], 0
+    while have < nonempty:
+        sizes.append(_EDGE_CYCLE[len(sizes) % len(_EDGE_CYCLE)])
+        have += sizes[-1] > 0
+    return np.array(sizes, np.int64)
+
+
+@pytest.mark.parametrize("lanes,nonempty", [(2, n) for n in (1, 2, 3, 5, 504, 505, 757)] + [(1, n) for n in (1, 252, 253, 505)])
+def test_search_batches_at_the_edges_of_the_schedule(native, lanes, nonempty):
+    """The schedule of ivfadc_search_batches where it changes: one, two, three and five batches (single-batch first groups, a lane's last
+    step without a successor), 504 / 505 and 757 batches on two lanes and 252 / 253 and 505 on one (the upload groups grow from one batch
+    per lane to two and three), sizes cycling through (1, 0, 2, 3, 0, 0, 1) so that empty batches lie in front of, behind and between
+    groups, from pageable memory (the group-wise staging copy).  One lane: a view of the index (a view gets no second lane).  Every
+    batch's rows are the oracle's bit for bit and nothing behind the run's last row is written; 505 batches on two lanes run twice on
+    the same handle (the token base carries over, the events are reused)."""
+    import ctypes as C
+    from ivfadc_jl_amd import _native as nat
+    case = _schedule_edge_case()
+    K, w = 10, 4
+    sizes = _edge_sizes(nonempty)
+    total = int(sizes.sum())
+    q = np.ascontiguousarray(case["qs"][:total])
+    exp = tuple(a[:total] for a in case["exp"])
+    gidx = gpu_index(native, case["oidx"])
+    g = gidx if lanes == 2 else gidx.clone_view()
+    runs = 2 if (lanes, nonempty) == (2, 505) else 1
+    for rep in range(runs):
+        ids = np.full((total + 3, K), 0xDEADBEEF, np.uint32); dists = np.full((total + 3, K), -7.0, np.float32); counts = np.full(total + 3, -9, np.int32)
+        nat.check(nat.lib().ivfadc_search_batches(g._h, len(sizes), nat.ptr(sizes, C.c_int64), nat.ptr(q, C.c_float), K, w,
+                                                  nat.ptr(ids, C.c_uint32), nat.ptr(dists, C.c_float), nat.ptr(counts, C.c_int32)))
+        what = "%d batches (%d non-empty) on %d lane(s), run %d" % (len(sizes), nonempty, lanes, rep)
+        helpers.assert_same_results((ids[:total], dists[:total], counts[:total]), exp, what=what)
+        assert (ids[total:] == 0xDEADBEEF).all() and (dists[total:] == -7.0).all() and (counts[total:] == -9).all(), what
+    st = _host_stats(native, g)
+    assert st["batches"] == runs * nonempty and st["queries_direct"] == 0 and st["results_direct"] == 0
+
+
 def test_search_batches_error_leaves_nothing_running_and_stats_survive_a_push(native):
     """A failing batch run returns with both lanes drained, and the counters of a second lane that a push! made stale
     stay in the totals (they used to go backwards)."""
