@@ -394,6 +394,49 @@ int ivfadc_reconstruct(ivfadc_t *h, int64_t n, const uint32_t *ids, float *out_v
 int ivfadc_locate_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, int32_t *d_out_list, int64_t *d_out_pos);
 int ivfadc_reconstruct_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, float *d_out_vectors, uint8_t *d_out_found);
 
+/* SCORE caller-supplied candidate ids: "what distance would knn_search report between this query and these stored ids", with no scan of
+ * the lists (csrc/score_plan.h, csrc/score.hip.h).  For candidates that come from elsewhere: a hybrid retriever's lexical hits, a rerank
+ * stage, a seen-list, a consistency check between two indexes, the ADC distance of the true neighbours in a recall study.
+ * For query q and candidate id v let (l, p) = locate(v), as ivfadc_locate finds them (utils.jl:49-55: the LAST list that holds v, the
+ * FIRST position within it; entries at or behind list_len do not count).  Then, in Float32, one rounding per operation, nothing contracted:
+ *   dc   = 0;  t = 0 .. d-1:            u = C_l[t] - q[t];          dc = dc + u * u        (coarsequantizers.jl:33-34)
+ *   r[t] = q[t] - C_l[t]                                                                   (coarsequantizers.jl:40-45)
+ *   s_ii = 0;  t of sub-space ii, ascending:  u = CB_ii[c_ii][t] - r[t];  s_ii = s_ii + u * u   (index.jl:232-236)
+ *   dist = dc; ii = 0 .. m-1:           dist = dist + s_ii                                 (index.jl:242-246)
+ * c_ii is the codeword the stored code names, read as ivfadc_reconstruct reads it (an 8-bit code is a LABEL and goes through the inverse
+ * of code_labels; a 16-bit code is the codeword index).  dist is the number knn_search(index, q, K; w) -- ivfadc_search -- returns for v
+ * whenever v is among its results, BIT FOR BIT, on 8-bit and UInt16 handles alike, so scored candidates merge with search results.
+ *   rotation        the rotation of an :opq file is NOT applied: the scan does not apply it either.
+ *   absent id       no list holds v (or a subset view dropped it): dist = +Inf (bits 0x7F800000), found = 0.  Not an error; absent ids
+ *                   sort last.
+ *   layout          queries is d x nq, as for ivfadc_search.  Row q of ids starts at ids + q * ids_stride and holds C slots:
+ *                   ids_stride == C is one candidate list per query; ids_stride == 0 is ONE shared row scored against every query (all
+ *                   pairs; its locate runs once, over C ids); any other stride is IVFADC_ERR_INVALID.  counts may be NULL: all C slots
+ *                   are live.  Otherwise slot j >= counts[q] is dead: its id is not scored and it comes back as +Inf / 0.  The host entry
+ *                   refuses a counts[q] outside [0, C], naming the query; the _device entry clamps it.  out_dists is nq x C (pair (q, j)
+ *                   at q * C + j); out_found is nq x C bytes and may be NULL.
+ *   requests        answered slot by slot; an id may repeat within a row and across rows.  Ids are unsigned 32-bit numbers (0xFFFFFFFF
+ *                   is an id).  At most 2^31 - 1 pairs (nq x C) per call: more is IVFADC_ERR_INVALID.
+ *   non-finite      queries are not scanned, as for ivfadc_search: a NaN or infinite component propagates into that query's distances.
+ * Served: 8-bit and UInt16 handles; plain views (ivfadc_clone_view); subset views (the view's OWN lists: an id the subset dropped is
+ * absent, a kept id has the distance it has on the index); file-loaded handles, :opq included; device-synthesised lists; an index after
+ * push! / delete / shift -- pending list changes are laid out first, as a search or a locate does.  A view whose index has changed, a
+ * handle that was never given lists and a handle with a list partition set refuse with IVFADC_ERR_STATE, as ivfadc_locate does.
+ * The host entry blocks.  The _device entry takes every pointer in device memory of h's GPU and only enqueues on the handle's stream: it
+ * uploads nothing and waits for nothing (asynchronous; pair with ivfadc_sync()).  Both take the per-handle lock.
+ * Under ivfadc_set_workspace_limit the call is cut into slices of whole queries whose locate workspace (32 bytes per slot) fits; the
+ * shared row is located once and only the pair kernel is sliced.
+ * Argument errors, IVFADC_ERR_INVALID before the handle is looked at or the device is touched, each named in ivfadc_last_error(): null
+ * handle; nq < 0; C < 0; a stride that is neither C nor 0; more than 2^31 - 1 pairs; with nq > 0 and C > 0, null queries, null ids or
+ * null out_dists; (host entry) a counts[q] outside [0, C].  nq == 0 or C == 0 returns IVFADC_OK.
+ * Cost: the locate pass (one pass over the stored ids, 4 bytes per entry, per slice) plus, per pair, two reads of a centre row and one
+ * of m codewords, all cache-resident -- against n stored entries per QUERY for a masked search over the same ids.
+ * Not covered: ivfadc_mg_* handles, the list-partitioned mode, ivfadc_search_batches.                                                  */
+int ivfadc_score_ids(ivfadc_t *h, int64_t nq, const float *queries, int64_t C, int64_t ids_stride, const uint32_t *ids,
+                     const int32_t *counts, float *out_dists, uint8_t *out_found);
+int ivfadc_score_ids_device(ivfadc_t *h, int64_t nq, const float *d_queries, int64_t C, int64_t ids_stride, const uint32_t *d_ids,
+                            const int32_t *d_counts, float *d_out_dists, uint8_t *d_out_found);
+
 /* The seam of the reference's knn_search.  index.jl:204-258 calls coarse_search(cq, point, w) once (index.jl:219) and everything after it
  * -- residuals, ADC tables, the list scan seeded with dc, top-K (index.jl:220-257) -- reads only the two vectors it returns;
  * AbstractCoarseQuantizer (coarsequantizers.jl:6) is the reference's one plug-in interface.  The two halves are exported separately, so a

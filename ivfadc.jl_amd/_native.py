@@ -16,6 +16,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
            os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
            os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"),
+           os.path.join(CSRC, "score.hip.h"), os.path.join(CSRC, "score_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]
@@ -188,6 +189,10 @@ def lib():
     L.ivfadc_locate_device.argtypes = [vp, C.c_int64, vp, vp, vp]
     L.ivfadc_reconstruct_device.argtypes = [vp, C.c_int64, vp, vp, vp]
     for name in ("locate", "reconstruct", "locate_device", "reconstruct_device"):
+        getattr(L, "ivfadc_" + name).restype = C.c_int
+    L.ivfadc_score_ids.argtypes = [vp, C.c_int64, fp, C.c_int64, C.c_int64, u32p, i32p, fp, u8p]
+    L.ivfadc_score_ids_device.argtypes = [vp, C.c_int64, vp, C.c_int64, C.c_int64, vp, vp, vp, vp]
+    for name in ("score_ids", "score_ids_device"):
         getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_set_list_partition.argtypes = [vp, C.c_int, C.c_int]
     L.ivfadc_search_device_partial.argtypes = [vp, C.c_int64, vp, C.c_int, C.c_int, vp, vp]

@@ -15,6 +15,7 @@
 #include "maskset.hip.h"
 #include "range.hip.h"
 #include "reconstruct.hip.h"
+#include "score.hip.h"
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
@@ -439,6 +440,7 @@ struct Workspace {
     // ivfadc_locate / ivfadc_reconstruct (reconstruct.hip.h): sorted wanted ids, one key per wanted slot, the exact bitmap, the lists' chunk
     // prefix, rocPRIM scratch, and the host entries' staging of requests and results
     DevBuf rc_want, rc_best, rc_bitmap, rc_chunk, rc_tmp, rc_req, rc_list, rc_pos, rc_found, rc_vec;
+    DevBuf sc_q, sc_ids, sc_cnt, sc_dist, sc_found;   // ivfadc_score_ids (host pointers): the caller's queries, ids and counts on the device, the results
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
@@ -448,7 +450,7 @@ struct Workspace {
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
-                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_req, &rc_list, &rc_pos, &rc_found, &rc_vec, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_req, &rc_list, &rc_pos, &rc_found, &rc_vec, &sc_q, &sc_ids, &sc_cnt, &sc_dist, &sc_found, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
                           &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
                           &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
             f(*b);
@@ -3393,7 +3395,9 @@ static int locate_host(ivfadc_index *h, int64_t n, const uint32_t *ids)
 
 // device entries: the requested ids are sorted on the device (rocPRIM; repeats stay); every step is enqueued on the handle's stream, nothing
 // is uploaded and nothing waited for (a workspace buffer that has to grow is reallocated, as by any search)
-static int locate_device(ivfadc_index *h, int64_t n, const uint32_t *d_ids, int32_t *d_list, int64_t *d_pos, uint8_t *d_found)
+// (span_known: a caller that has seen the ids on the host passes their smallest and largest, and the bitmap covers that span alone)
+static int locate_device(ivfadc_index *h, int64_t n, const uint32_t *d_ids, int32_t *d_list, int64_t *d_pos, uint8_t *d_found,
+                         bool span_known = false, uint32_t want_lo = 0u, uint32_t want_hi = 0u)
 {
     if (n > (int64_t)0x7FFFFFFF) return fail(IVFADC_ERR_INVALID, "n = %lld ids in one call (the device entries sort at most 2^31 - 1)", (long long)n);
     TRY(h->rc_want.ensure((size_t)n * 4));
@@ -3401,7 +3405,7 @@ static int locate_device(ivfadc_index *h, int64_t n, const uint32_t *d_ids, int3
     HIP_TRY(rocprim::radix_sort_keys(nullptr, tmp, d_ids, h->rc_want.as<u32>(), (unsigned)n, 0, 32, h->stream));
     TRY(h->rc_tmp.ensure(std::max<size_t>(tmp, 16)));
     HIP_TRY(rocprim::radix_sort_keys(h->rc_tmp.p, tmp, d_ids, h->rc_want.as<u32>(), (unsigned)n, 0, 32, h->stream));
-    TRY(locate_sorted(h, h->rc_want.as<u32>(), (uint64_t)n, false, 0u, 0u));
+    TRY(locate_sorted(h, h->rc_want.as<u32>(), (uint64_t)n, span_known, want_lo, want_hi));
     return recon_resolve(h, d_ids, n, h->rc_want.as<u32>(), (uint64_t)n, d_list, d_pos, d_found);
 }
 
@@ -3452,6 +3456,116 @@ try {
     if (rc == IVFADC_OK) rc = locate_device(h, n, d_ids, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_out_found);
     if (rc == IVFADC_OK) rc = recon_decode(h, n, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_out_vectors);
     return recon_exit(h, rc);
+} IVF_CATCH
+
+// ---- score caller-supplied candidate ids (score_plan.h, score.hip.h) --------------------------------------------------
+// "What distance would knn_search report between this query and these stored ids": locate (above), then one lane per (query, id) pair
+// runs the canonical Float32 chains of the distance.  No scan of the lists, no table.
+
+// the arguments of both entries, before the handle is looked at and before any device call
+static int check_score_args(const char *fn, ivfadc_t *h, int64_t nq, const float *queries, int64_t C, int64_t ids_stride, const uint32_t *ids,
+                            const float *out_dists)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "%s: null handle", fn);
+    if (nq < 0) return fail(IVFADC_ERR_INVALID, "%s: nq = %lld < 0", fn, (long long)nq);
+    if (C < 0) return fail(IVFADC_ERR_INVALID, "%s: C = %lld < 0", fn, (long long)C);
+    if (score::stride_form(C, ids_stride) == score::FORM_BAD)
+        return fail(IVFADC_ERR_INVALID, "%s: ids_stride = %lld (C = %lld for per-query rows, 0 for one shared row)", fn, (long long)ids_stride,
+                    (long long)C);
+    if (!score::pairs_fit(nq, C))
+        return fail(IVFADC_ERR_INVALID, "%s: nq x C = %lld x %lld pairs in one call (at most 2^31 - 1)", fn, (long long)nq, (long long)C);
+    if (nq == 0 || C == 0) return IVFADC_OK;
+    if (!queries) return fail(IVFADC_ERR_INVALID, "%s: null queries", fn);
+    if (!ids) return fail(IVFADC_ERR_INVALID, "%s: null ids", fn);
+    if (!out_dists) return fail(IVFADC_ERR_INVALID, "%s: null out_dists", fn);
+    return IVFADC_OK;
+}
+
+// every pointer in device memory; only enqueues.  span_known: the smallest and largest id of the live slots, where the host has seen them
+static int score_enqueue(ivfadc_index *h, int64_t nq, const float *d_q, int64_t C, int64_t ids_stride, const uint32_t *d_ids,
+                         const int32_t *d_counts, float *d_dists, uint8_t *d_found, bool span_known, uint32_t want_lo, uint32_t want_hi)
+{
+    const score::Plan pl = score::make_plan(nq, C, ids_stride, h->d, (uint64_t)h->ws_budget);
+    DecodeArgs a{};
+    a.centroids = h->centroids.as<float>();
+    a.codebooks = h->codebooks.as<float>();
+    a.label_inv = h->u16 ? (const uint8_t *)nullptr : h->label_inv.as<uint8_t>();
+    a.codes = h->codes.as<uint8_t>();
+    a.list_codeoff = h->list_codeoff.as<int64_t>();
+    a.d = h->d; a.m = h->m; a.dsub = h->dsub; a.ksub = h->ksub; a.cs = h->cs;
+    if (!h->u16 && !a.label_inv) return fail(IVFADC_ERR_STATE, "the handle has no inverse labels");
+    TRY(h->rc_list.ensure((size_t)pl.locate_slots * 4));
+    TRY(h->rc_pos.ensure((size_t)pl.locate_slots * 8));
+    if (pl.shared) TRY(locate_device(h, C, d_ids, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), nullptr, span_known, want_lo, want_hi));
+    for (int64_t s = 0; s < pl.nslices; ++s) {
+        const int64_t q0 = score::slice_begin(pl, s), nqs = score::slice_queries(pl, s);
+        if (!pl.shared)
+            TRY(locate_device(h, nqs * C, &d_ids[score::id_index(q0, ids_stride, 0)], h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), nullptr,
+                              span_known, want_lo, want_hi));
+        hipLaunchKernelGGL(score_pairs_kernel, dim3(pl.grid_x, (unsigned)nqs), dim3(score::TILE), pl.lds, h->stream, a, h->kc, d_q, q0, C, pl.shared,
+                           d_counts, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_dists, d_found);
+        HIP_TRY(hipGetLastError());
+    }
+    return IVFADC_OK;
+}
+
+int ivfadc_score_ids(ivfadc_t *h, int64_t nq, const float *queries, int64_t C, int64_t ids_stride, const uint32_t *ids, const int32_t *counts,
+                     float *out_dists, uint8_t *out_found)
+try {
+    TRY(check_score_args("ivfadc_score_ids", h, nq, queries, C, ids_stride, ids, out_dists));
+    const bool shared = score::stride_form(C, ids_stride) == score::FORM_SHARED;
+    // counts in [0, C], and the span of the ids of the live slots (the bitmap of the locate pass covers it alone)
+    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
+    bool any = false;
+    if (nq > 0 && C > 0) {
+        int64_t longest = C;
+        if (counts) {
+            longest = 0;
+            for (int64_t q = 0; q < nq; ++q) {
+                if (counts[q] < 0 || (int64_t)counts[q] > C)
+                    return fail(IVFADC_ERR_INVALID, "ivfadc_score_ids: query %lld: counts = %d outside [0, %lld]", (long long)q, (int)counts[q], (long long)C);
+                longest = std::max<int64_t>(longest, counts[q]);
+            }
+        }
+        const int64_t rows = shared ? 1 : nq;
+        for (int64_t q = 0; q < rows; ++q) {
+            const int64_t live = shared ? longest : score::live_slots(counts != nullptr, counts ? counts[q] : 0, C);
+            const uint32_t *row = ids + score::id_index(q, ids_stride, 0);
+            for (int64_t j = 0; j < live; ++j) {
+                lo = std::min(lo, row[j]);
+                hi = std::max(hi, row[j]);
+                any = true;
+            }
+        }
+    }
+    if (nq == 0 || C == 0) return IVFADC_OK;   // (nothing to score: the handle is not looked at)
+    HandleLock lk_(h);
+    TRY(recon_begin(h, "ivfadc_score_ids"));
+    const size_t pairs = (size_t)nq * (size_t)C, nid = shared ? (size_t)C : pairs;
+    int rc = h->sc_q.ensure((size_t)nq * h->d * 4);
+    if (rc == IVFADC_OK) rc = h->sc_ids.ensure(nid * 4);
+    if (rc == IVFADC_OK) rc = h->sc_dist.ensure(pairs * 4);
+    if (rc == IVFADC_OK) rc = h->sc_found.ensure(pairs);
+    if (rc == IVFADC_OK && counts) rc = h->sc_cnt.ensure((size_t)nq * 4);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->sc_q.p, queries, (size_t)nq * h->d * 4, h->stream);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->sc_ids.p, ids, nid * 4, h->stream);
+    if (rc == IVFADC_OK && counts) rc = h2d_copy(h->sc_cnt.p, counts, (size_t)nq * 4, h->stream);
+    if (rc == IVFADC_OK)
+        rc = score_enqueue(h, nq, h->sc_q.as<float>(), C, ids_stride, h->sc_ids.as<u32>(), counts ? h->sc_cnt.as<int32_t>() : (const int32_t *)nullptr,
+                           h->sc_dist.as<float>(), h->sc_found.as<uint8_t>(), true, any ? lo : 0u, any ? hi : 0u);   // (no live slot: a span of one id)
+    if (rc == IVFADC_OK) rc = d2h_copy(out_dists, h->sc_dist.p, pairs * 4, h->stream);
+    if (rc == IVFADC_OK && out_found) rc = d2h_copy(out_found, h->sc_found.p, pairs, h->stream);
+    return recon_exit(h, rc);
+} IVF_CATCH
+
+int ivfadc_score_ids_device(ivfadc_t *h, int64_t nq, const float *d_queries, int64_t C, int64_t ids_stride, const uint32_t *d_ids,
+                            const int32_t *d_counts, float *d_out_dists, uint8_t *d_out_found)
+try {
+    TRY(check_score_args("ivfadc_score_ids_device", h, nq, d_queries, C, ids_stride, d_ids, d_out_dists));
+    if (nq == 0 || C == 0) return IVFADC_OK;   // (nothing to score: the handle is not looked at)
+    HandleLock lk_(h);
+    TRY(recon_begin(h, "ivfadc_score_ids_device"));
+    return recon_exit(h, score_enqueue(h, nq, d_queries, C, ids_stride, d_ids, d_counts, d_out_dists, d_out_found, false, 0u, 0u));
 } IVF_CATCH
 
 // ---- list-partitioned multi-GPU mode: strong scaling of a FIXED global batch --------------------------------------------------------------

@@ -665,6 +665,36 @@ class IVFADCIndex:
         nat.check(nat.lib().ivfadc_reconstruct_device(self._h, int(n), C.c_void_p(ids_ptr), C.c_void_p(vectors_ptr),
                                                       C.c_void_p(found_ptr) if found_ptr else None))
 
+    # ---- the distance knn_search would report for given ids (ivfadc_score_ids: locate, then one lane per pair; no scan) ----
+    def score_raw(self, queries, ids, counts=None):
+        """queries (nq, d), ids (nq, C) -- or (C,): ONE shared row scored against every query -- and optional counts (nq,) of live slots
+        per query -> (dists (nq, C) float32, found (nq, C) bool): the distance ivfadc_search reports for each id, bit for bit; +Inf /
+        False for an id no list holds and for a slot at or behind counts[q]."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        nq = q.shape[0]
+        ids = np.ascontiguousarray(ids, np.uint32)
+        assert ids.ndim in (1, 2), "ids must be (nq, C), or (C,) for one shared row"
+        shared = ids.ndim == 1
+        assert shared or ids.shape[0] == nq, "ids must hold one row per query"
+        ncand = ids.shape[-1]
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+            assert counts.shape[0] == nq, "counts must hold one number per query"
+        dists = np.full((nq, ncand), np.inf, np.float32)
+        found = np.zeros((nq, ncand), np.uint8)
+        nat.check(nat.lib().ivfadc_score_ids(self._h, nq, nat.ptr(q, C.c_float), ncand, 0 if shared else ncand, nat.ptr(ids, C.c_uint32),
+                                             nat.ptr(counts, C.c_int32), nat.ptr(dists, C.c_float), nat.ptr(found, C.c_uint8)))
+        return dists, found.astype(bool)
+
+    def score_device(self, nq, q_ptr, ncand, ids_stride, ids_ptr, counts_ptr, dists_ptr, found_ptr=None):
+        """Asynchronous on raw device pointers (ints): nq x d float32 queries, ids rows of ncand uint32 at ids_stride (ncand, or 0 for
+        one shared row), optional nq int32 counts -> nq x ncand float32 distances (and found bytes unless found_ptr is None); see
+        ivfadc_score_ids_device."""
+        nat.check(nat.lib().ivfadc_score_ids_device(self._h, int(nq), C.c_void_p(q_ptr), int(ncand), int(ids_stride), C.c_void_p(ids_ptr),
+                                                    C.c_void_p(counts_ptr) if counts_ptr else None, C.c_void_p(dists_ptr),
+                                                    C.c_void_p(found_ptr) if found_ptr else None))
+
 
 def _comm_methods():
     """one-process-per-GPU merge inside the library (ivfadc_comm_*): methods of IVFADCIndex"""
@@ -992,6 +1022,38 @@ def reconstruct(ivfadc, ids):
     if not found.all():
         raise AssertionError("id %d is not stored in the index" % int(ids[int(np.argmin(found))]))
     return vec
+
+
+def score(ivfadc, points, ids):
+    """The distance knn_search(ivfadc, point, k; w) reports between each query and each of the given stored ids, bit for bit, whether or
+    not the id's cell would have been probed: dc + the sub-space sums in the reference's order (coarsequantizers.jl:33-34, index.jl:232-246).
+    `ids` is (nq, C), one row per query, or (C,), one row scored against every query; an id no list holds gives +Inf.
+    A 1-D `points` is one query and returns a (C,) array; a matrix or a list of vectors returns (nq, C)."""
+    pts, single = _as_points(ivfadc, points)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    if single and ids.ndim == 2:
+        assert ids.shape[0] == 1, "one query takes one row of ids"
+    dists, _ = ivfadc.score_raw(pts, ids)
+    return dists[0] if single else dists
+
+
+def knn_among(ivfadc, points, ids, k):
+    """The k best of the given candidate ids per query, by score(): (ids, dists), ordered by (distance, position in the row); ids no
+    list holds are dropped, so a row may come back shorter than k.  One query returns two arrays, a batch two lists of arrays."""
+    assert k >= 1, "Number of neighbors must be k >= 1"                          # index.jl:210
+    pts, single = _as_points(ivfadc, points)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    dists, found = ivfadc.score_raw(pts, ids)
+    out_i, out_d = [], []
+    for i in range(pts.shape[0]):
+        row = ids if ids.ndim == 1 else ids[i]
+        order = np.argsort(dists[i], kind="stable")                              # stable: equal distances keep their row order
+        order = order[found[i][order]][:int(k)]
+        out_i.append(row[order].astype(ivfadc.index_type))
+        out_d.append(dists[i][order].copy())
+    if single:
+        return out_i[0], out_d[0]
+    return out_i, out_d
 
 
 def _pop(ivfadc, position):
