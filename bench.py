@@ -920,6 +920,9 @@ def measure_host_to_host(torch, pkg, idx, cfg, K, w, dev, device_index, data_kin
     ref = None
     same = True
     for kind in kinds:
+        if kind == "registered" and not nat.can_host_register():
+            out["registered_not_measured"] = "this system cannot page-lock the caller's own arrays (hipHostRegister fails)"
+            continue
         q, ids, dists, counts, cleanup = arrays(kind)
 
         def run_loop():

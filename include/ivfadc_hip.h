@@ -176,10 +176,13 @@ int ivfadc_search(ivfadc_t *h, int64_t nq, const float *queries, int K, int w,
  *   results     are written into the caller's out_ids / out_dists / out_counts by the final kernel of the search -- no device-side
  *               result block, no device-to-host copy (all three arrays must be known, otherwise the library's pinned block is used).
  * Arrays the library does not know are staged through its own pinned buffers as before; results are identical either way.
- *   ivfadc_host_alloc       page-locked memory owned by the library (any device may read / write it); free with ivfadc_host_free
+ *   ivfadc_host_alloc       page-locked memory owned by the library (any device may read / write it), zero-filled; free with
+ *                           ivfadc_host_free
  *   ivfadc_host_register    page-locks an array of the CALLER's (e.g. a Julia Matrix{Float32} that a serving loop refills): the caller
  *                           keeps it alive and unmoved until ivfadc_host_unregister(p).  Registering costs tens of microseconds per
- *                           megabyte: do it once per buffer, not per call.
+ *                           megabyte: do it once per buffer, not per call.  IVFADC_ERR_HIP where the system cannot page-lock memory a
+ *                           process already has (some virtual machines): nothing is registered then, the array is staged like any
+ *                           other -- or use ivfadc_host_alloc, which works everywhere.
  * Thread-safe (one process-wide table).  IVFADC_ERR_INVALID for a pointer the table does not hold / an overlapping registration. */
 int ivfadc_host_alloc(size_t bytes, void **out);
 int ivfadc_host_free(void *p);

@@ -266,3 +266,23 @@ def host_register(a):
 
 def host_unregister(a):
     check(lib().ivfadc_host_unregister(C.c_void_p(a.ctypes.data)))
+
+
+_can_register = None
+
+
+def can_host_register():
+    """Whether this system can page-lock memory the process already has (hipHostRegister; some virtual machines cannot, and
+    host_register raises there): probed once with one page.  Blocks from ivfadc_host_alloc (PinnedArray) work everywhere."""
+    global _can_register
+    if _can_register is None:
+        import numpy as np
+        a = np.zeros(1024, np.float32)
+        try:
+            host_register(a)
+        except IVFADCError:
+            _can_register = False
+        else:
+            host_unregister(a)
+            _can_register = True
+    return _can_register

@@ -105,8 +105,10 @@ static int fail(int code, const char *fmt, ...)
 #define HIP_TRY(expr)                                                                              \
     do {                                                                                           \
         hipError_t e_ = (expr);                                                                    \
-        if (e_ != hipSuccess)                                                                      \
+        if (e_ != hipSuccess) {                                                                    \
+            (void)hipGetLastError();   /* reported here: not once more by the next launch check */ \
             return fail(IVFADC_ERR_HIP, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(e_), __FILE__, __LINE__); \
+        }                                                                                          \
     } while (0)
 
 // No C++ exception crosses the C ABI: every extern "C" entry point is a function-try-block ending in IVF_CATCH
@@ -193,6 +195,10 @@ struct PinnedBuf {
         const size_t want = need + need / 4;
         hipError_t e = hipHostMalloc(&p, want, hipHostMallocPortable | hipHostMallocMapped);
         if (e != hipSuccess) { p = nullptr; return fail(IVFADC_ERR_HIP, "hipHostMalloc(%zu) failed: %s", want, hipGetErrorString(e)); }
+        // A result block is handed to the caller in whole rows, and the kernels write only the slots a query found: the slots past its
+        // count must not carry what the memory held before it was ours (the runtime may hand out page-locked memory it has used before,
+        // not only fresh zero pages).  Cleared once per allocation: they hold zeros, or an earlier search of this handle.
+        memset(p, 0, want);
         bytes = want;
         return IVFADC_OK;
     }
@@ -4829,6 +4835,7 @@ try {
     void *p = nullptr;
     const hipError_t e = hipHostMalloc(&p, bytes, hipHostMallocPortable | hipHostMallocMapped);
     if (e != hipSuccess) return fail(IVFADC_ERR_HIP, "hipHostMalloc(%zu) failed: %s", bytes, hipGetErrorString(e));
+    memset(p, 0, bytes);   // (as PinnedBuf: result slots past a query's count are not written)
     const int rc = host_range_add(p, bytes, true);
     if (rc != IVFADC_OK) { (void)hipHostFree(p); return rc; }
     *out = p;
@@ -4853,7 +4860,12 @@ try {
             if (a < r.hi && b > r.lo) return fail(IVFADC_ERR_INVALID, "host range overlaps one that is already registered");
     }
     const hipError_t e = hipHostRegister(p, bytes, hipHostRegisterPortable | hipHostRegisterMapped);
-    if (e != hipSuccess) return fail(IVFADC_ERR_HIP, "hipHostRegister(%zu) failed: %s", bytes, hipGetErrorString(e));
+    if (e != hipSuccess) {
+        // (some systems cannot page-lock memory a process already has.)  The runtime also keeps the error for the next
+        // hipGetLastError(): taken here, or the next launch check of any handle would report it as its own
+        (void)hipGetLastError();
+        return fail(IVFADC_ERR_HIP, "hipHostRegister(%zu) failed: %s", bytes, hipGetErrorString(e));
+    }
     // the kernels use the HOST address: it must be the address the device sees too (it is, wherever the runtime maps host memory at
     // its own virtual address; checked rather than assumed)
     void *dp = nullptr;

@@ -195,6 +195,45 @@ def assert_same_results(got, exp, what=""):
                 what, r, s, int(gi[r, s]), bad.shape[0], c, float(gd[r, s]).hex(), float(ed[r, s]).hex(), _ulps(gd[r, s], ed[r, s])))
 
 
+class KnownArrays:
+    """The caller's arrays as memory the library knows (a host-pointer search reads its queries in place and writes its results into
+    them).  Where the system can page-lock memory a process already has, `.arrays` are the very arrays, registered
+    (ivfadc_host_register; `.registered`); elsewhere they are copies in blocks from ivfadc_host_alloc, which the library treats alike.
+    release() unregisters / frees: the blocks are gone then, registered arrays are ordinary memory again."""
+
+    def __init__(self, arrays):
+        from ivfadc_jl_amd import _native as nat
+        self._nat = nat
+        self.registered = nat.can_host_register()
+        self._blocks = []
+        if self.registered:
+            self.arrays = list(arrays)
+            done = []
+            try:
+                for a in self.arrays:
+                    nat.host_register(a)
+                    done.append(a)
+            except BaseException:
+                for a in done:
+                    nat.host_unregister(a)
+                raise
+        else:
+            for a in arrays:
+                p = nat.PinnedArray(a.shape, a.dtype)
+                p.a[...] = a
+                self._blocks.append(p)
+            self.arrays = [p.a for p in self._blocks]
+
+    def release(self):
+        if self.registered:
+            for a in self.arrays:
+                self._nat.host_unregister(a)
+        self.arrays = []
+        for p in self._blocks:
+            p.close()
+        self._blocks = []
+
+
 def numpy_partial_keys(oidx, qs, K, w, nparts, part):
     """List-partitioned restatement: for every query the K smallest (distance, visit order) keys over the probed lists l with
     l % nparts == part -- visit orders counted over ALL w probes, as one rank of ivfadc_search_device_partial leaves them --

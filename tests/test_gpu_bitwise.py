@@ -186,16 +186,15 @@ def test_every_search_entry_returns_the_oracles_bytes(native, kind):
     # memory the library does not know
     res["ivfadc_search, pageable"] = g.search_raw(qs, K, w)
     # registered memory: queries read in place, results written into the caller's arrays
-    blocks = (qs.copy(), np.zeros((nq, K), np.uint32), np.zeros((nq, K), np.float32), np.zeros(nq, np.int32))
-    for a in blocks:
-        nat.host_register(a)
+    # (library-allocated blocks where the system cannot register the caller's own: helpers.KnownArrays)
+    known = helpers.KnownArrays((qs.copy(), np.zeros((nq, K), np.uint32), np.zeros((nq, K), np.float32), np.zeros(nq, np.int32)))
     try:
+        blocks = known.arrays
         nat.check(nat.lib().ivfadc_search(g._h, nq, nat.ptr(blocks[0], C.c_float), K, w, nat.ptr(blocks[1], C.c_uint32),
                                           nat.ptr(blocks[2], C.c_float), nat.ptr(blocks[3], C.c_int32)))
         res["ivfadc_search, registered"] = tuple(a.copy() for a in blocks[1:])
     finally:
-        for a in blocks:
-            nat.host_unregister(a)
+        known.release()
     # device pointers
     dev = torch.device("cuda:0")
     qd = torch.from_numpy(qs).to(dev)

@@ -2093,7 +2093,6 @@ def _raw_search(gidx, q, K, w, ids, dists, counts):
 def test_host_entries_known_memory_same_results(native, nq):
     """ivfadc_search with pageable arrays, with caller-registered arrays and with library-allocated page-locked arrays (queries ingested
     from / read in place in the caller's array, results written into the caller's arrays by the final kernel): one answer, the oracle's."""
-    from ivfadc_jl_amd import _native as nat
     oidx, data = helpers.build_index(41, 6000, 128, 64, 8, 256)
     rng = np.random.default_rng(nq)
     qs = np.concatenate([rng.random((nq - 1, 128), dtype=np.float32), data[:1]])
@@ -2106,11 +2105,11 @@ def test_host_entries_known_memory_same_results(native, nq):
     st0 = _host_stats(native, gidx)
     assert st0["queries_direct"] == 0 and st0["results_direct"] == 0
     # caller-registered, deliberately only 4-byte aligned (a slice one float into a larger registered block)
-    blk_q = np.zeros(nq * 128 + 1, np.float32)
-    blk_i = np.zeros(nq * K + 1, np.uint32); blk_d = np.zeros(nq * K + 1, np.float32); blk_c = np.zeros(nq + 1, np.int32)
-    for a in (blk_q, blk_i, blk_d, blk_c):
-        nat.host_register(a)
+    # (where the system cannot register memory a process already has, blocks the library allocated stand in: helpers.KnownArrays)
+    known = helpers.KnownArrays((np.zeros(nq * 128 + 1, np.float32), np.zeros(nq * K + 1, np.uint32), np.zeros(nq * K + 1, np.float32),
+                                 np.zeros(nq + 1, np.int32)))
     try:
+        blk_q, blk_i, blk_d, blk_c = known.arrays
         q = blk_q[1:].reshape(nq, 128); q[...] = qs
         ids = blk_i[1:].reshape(nq, K); dists = blk_d[1:].reshape(nq, K); counts = blk_c[1:]
         _raw_search(gidx, q, K, w, ids, dists, counts)
@@ -2123,11 +2122,11 @@ def test_host_entries_known_memory_same_results(native, nq):
         helpers.assert_same_results((ids2, d2, c2), exp, what="registered queries, pageable results")
         assert _host_stats(native, gidx)["results_direct"] == st1["results_direct"]
     finally:
-        for a in (blk_q, blk_i, blk_d, blk_c):
-            nat.host_unregister(a)
-    # once unregistered the same arrays are staged again
-    _raw_search(gidx, q, K, w, ids, dists, counts)
-    helpers.assert_same_results((ids, dists, counts), exp, what="after unregister")
+        known.release()
+    # once unregistered the same arrays are staged again (blocks of the library's are freed by then: nothing to search from)
+    if known.registered:
+        _raw_search(gidx, q, K, w, ids, dists, counts)
+        helpers.assert_same_results((ids, dists, counts), exp, what="after unregister")
     # library-allocated blocks through the reference-shaped entry (knn_search packs into them)
     oi, od = native.knn_search(gidx, [qs[i] for i in range(nq)], K, w)
     for r in range(nq):
@@ -2143,12 +2142,22 @@ def test_host_register_contract(native):
     import ctypes as C
     from ivfadc_jl_amd import _native as nat
     a = np.zeros(4096, np.float32)
-    nat.host_register(a)
-    with pytest.raises(nat.IVFADCError):          # overlapping registration
-        nat.host_register(a[10:100])
-    with pytest.raises(nat.IVFADCError):          # not the start of a registered range
-        nat.check(nat.lib().ivfadc_host_unregister(C.c_void_p(a.ctypes.data + 64)))
-    nat.host_unregister(a)
+    if nat.can_host_register():
+        nat.host_register(a)
+        with pytest.raises(nat.IVFADCError):          # overlapping registration
+            nat.host_register(a[10:100])
+        with pytest.raises(nat.IVFADCError):          # not the start of a registered range
+            nat.check(nat.lib().ivfadc_host_unregister(C.c_void_p(a.ctypes.data + 64)))
+        nat.host_unregister(a)
+    else:
+        # a system that cannot page-lock memory the process already has: the refusal names the call, nothing counts as registered, and
+        # the runtime's error does not stay behind for the next launch to report (a search right afterwards is the oracle's)
+        with pytest.raises(nat.IVFADCError, match="hipHostRegister"):
+            nat.host_register(a)
+        oidx, data = helpers.build_index(41, 6000, 128, 64, 8, 256)
+        gidx = gpu_index(native, oidx)
+        helpers.assert_same_results(gidx.search_raw(data[:7], 10, 5), oidx.knn_search(data[:7], 10, 5), what="after a refused registration")
+        assert _host_stats(native, gidx)["queries_direct"] == 0
     with pytest.raises(nat.IVFADCError):
         nat.host_unregister(a)
     p = nat.PinnedArray((16, 8), np.float32)
