@@ -272,7 +272,8 @@ int ivfadc_clone_subset_device(ivfadc_t *h, const uint32_t *d_bits, uint64_t nbi
  * can be in flight on one replica).  IVFADC_ERR_STATE: a subset view; another index; an index that has changed since s was made (any
  * mutator, by the generation rule of views); a handle with a list partition set.  K < 1 or w < 1: IVFADC_ERR_ASSERT, as ivfadc_search;
  * w > kc is clamped as ivfadc_search clamps it.  Every K and w is served; batches are sub-batched under ivfadc_set_workspace_limit; a
- * pending hint is dropped, as by any search.  There is no latency path, no fused top-w and no riders.  The 8-bit list scan is
+ * pending hint is dropped, as by any search.  There is no fused top-w and there are no riders; the latency path runs on request only
+ * (ivfadc_set_masked_latency, below: one launch for a handful of queries, stats.last_qg == -3).  The 8-bit list scan is
  * masked_scan_kernel (stats.last_striped == 8); K or w > 2048, ivfadc_set_tuning(h, -2, 0) and every UInt16 handle take the generic path,
  * where a rejected point's key sorts behind every real key.  The device entry is asynchronous on the handle's stream.
  * Not covered: masks in the query-major, eight-wave, narrow-field and UInt16 scan kernels; masks together with caller-supplied probes;
@@ -285,6 +286,19 @@ int ivfadc_search_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, con
                          const int32_t *mask_of_query, uint32_t *out_ids, float *out_dists, int32_t *out_counts);
 int ivfadc_search_device_masked(ivfadc_t *h, const ivfadc_maskset_t *s, int64_t nq, const float *d_queries, int K, int w,
                                 const int32_t *d_mask_of_query, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
+
+/* The latency path of the masked search: 0 (default) = every masked call plans as described above; 1 = a call that the plain search's
+ * latency path would admit -- an 8-bit handle, nq <= 64, nq x w <= 512, K <= 64, w <= 64, d % 4 == 0, ivfadc_set_tuning's qg == 0,
+ * IVFADC_NO_SMALLQ unset -- runs in ONE launch (two where the coarse quantizer is searched by a launch of its own): sq_masked_kernel, a
+ * workgroup per (query, probe, chunk) with a last-arriver merge, whose point loop reads the mask first and loads codes and looks tables up
+ * for selected entries only (8 bytes of mask per 64 positions; a chunk without a selected entry builds no tables).  Both masked entries
+ * take it; every other call, and every check of h and s, is what it was.  The device entry then has no ingest launch: mask numbers are
+ * clamped into [-1, nmasks) as the kernel reads them.  Results are the same bytes in both modes.  stats.last_qg == -3 tells that it ran,
+ * with last_chunk / last_scan_grid / last_scan_lds as the plain latency path sets them; scanned_points counts every probed point once,
+ * selected or not.  ivfadc_set_tuning's chunk_points, when not 0, is the points of a work item here, rounded up to a multiple of 64 and
+ * doubled while a probe would leave more than 64 partial results.  NULL handle or a mode other than 0 / 1: IVFADC_ERR_INVALID, before any
+ * device call.  ivfadc_clone_view copies the setting; a view takes its own afterwards.  Not an environment variable.            */
+int ivfadc_set_masked_latency(ivfadc_t *h, int mode);
 
 /* RANGE search: every stored point of the w probed lists within distance r of a query (NearestNeighbors.jl's inrange; other IVF
  * libraries' range_search).  NO REFERENCE COUNTERPART: IVFADC.jl has knn_search only, so the six entries below are DEFINED through it.

@@ -13,7 +13,7 @@ SO_PATH = os.path.join(CSRC, "libivfadc_hip.so")
 SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip.h"), os.path.join(CSRC, "train.hip.h"), os.path.join(CSRC, "wave_sort.hip.h"),
            os.path.join(CSRC, "generic.hip.h"), os.path.join(CSRC, "lbscan.hip.h"), os.path.join(CSRC, "nfscan.hip.h"), os.path.join(CSRC, "smallq.hip.h"), os.path.join(CSRC, "twolevel.hip.h"), os.path.join(CSRC, "wg8scan.hip.h"), os.path.join(CSRC, "u16scan.hip.h"), os.path.join(CSRC, "pack_operands.h"),
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
-           os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"),
+           os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"), os.path.join(CSRC, "sqmask.hip.h"),
            os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
            os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"),
            os.path.join(CSRC, "score.hip.h"), os.path.join(CSRC, "score_plan.h"),
@@ -127,6 +127,8 @@ def lib():
     L.ivfadc_set_table_mode.argtypes = [vp, C.c_int]
     L.ivfadc_set_u16_tables.argtypes = [vp, C.c_int]
     L.ivfadc_set_u16_tables.restype = C.c_int
+    L.ivfadc_set_masked_latency.argtypes = [vp, C.c_int]
+    L.ivfadc_set_masked_latency.restype = C.c_int
     L.ivfadc_delete_ids.argtypes = [vp, C.c_int64, u32p, i64p]
     L.ivfadc_shift_ids.argtypes = [vp, C.c_int32]
     L.ivfadc_save_index.argtypes = [vp, C.c_char_p, C.c_int]

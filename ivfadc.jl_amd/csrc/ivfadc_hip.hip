@@ -13,6 +13,7 @@
 #include "twolevel.hip.h"
 #include "subset.hip.h"
 #include "maskset.hip.h"
+#include "sqmask.hip.h"
 #include "range.hip.h"
 #include "reconstruct.hip.h"
 #include "score.hip.h"
@@ -393,6 +394,7 @@ struct SearchConfig {
     // leaves partial top-K keys
     int part_n = 1, part_i = 0;
     bool allow_sq = true, sq_inside = false;
+    bool masked_sq = false;      // ivfadc_set_masked_latency(h, 1): a masked search that sq_eligible admits runs sq_masked_kernel (sqmask.hip.h)
     bool allow_lb = true;
     bool force_lb = false;       // ivfadc_set_table_mode(h, 2): the matrix-core rounds wherever they are instantiated, not only where they pay
     bool allow_f16 = true;
@@ -839,6 +841,14 @@ sq_fn_t pick_sq(int m, int dsub)
     IVF_SHAPES(X)
 #undef X
     return sq_kernel<0, 0>;
+}
+// sq_masked_kernel (sqmask.hip.h): the same shapes
+sq_masked_fn_t pick_sq_masked(int m, int dsub)
+{
+#define X(M_, D_) if (m == M_ && dsub == D_) return sq_masked_kernel<M_, D_>;
+    IVF_SHAPES(X)
+#undef X
+    return sq_masked_kernel<0, 0>;
 }
 
 // (filt_shape, nf_shape, w8_dsub, w8_m16_dsub -- the shapes the striped, the narrow-field and the eight-wave kernels are instantiated
@@ -1709,7 +1719,19 @@ bool sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
     return lds <= LDS_MAX;
 }
 
-int search_small(ivfadc_index *h, const SearchCall &c)
+// The latency path of a masked search (sqmask.hip.h), on request: ivfadc_set_masked_latency(h, 1) and everything sq_eligible asks, with
+// the pending queues in the LDS figure.  The entries ask before they stage the mask numbers and search_dev asks again: one rule.
+bool masked_sq_eligible(const ivfadc_index *h, int64_t nq, int K, int w)
+{
+    if (!h->masked_sq || h->part_n > 1 || !sq_eligible(h, nq, K, w)) return false;
+    return sqm_lds_bytes(h->m, h->d, h->kc <= sq_inside_kc(h) ? h->kc : 0) <= LDS_MAX;
+}
+
+constexpr int64_t SQM_MAX_CHUNKS = 64;   // partial results per probe under a forced chunk, at most (the bound make_plan puts on one)
+
+// masked: c carries a mask set and sq_masked_kernel (sqmask.hip.h) stands in sq_kernel's place -- the same coarse launch, workspace and
+// arrival counters.  c.mask_of_query: staged on the device, or the device entry's own array (c.mask_raw); the kernel clamps either.
+static int search_small_as(ivfadc_index *h, const SearchCall &c, bool masked)
 {
     const int64_t nq = c.nq; const float *d_q = c.q; const int K = c.K, w = c.w;
     TRY(ensure_common_ws(h));
@@ -1734,6 +1756,12 @@ int search_small(ivfadc_index *h, const SearchCall &c)
     const int64_t items = nq * w;
     int nch = (int)std::max<int64_t>(1, std::min<int64_t>((h->mirror.maxlen + 4095) / 4096, (2 * (int64_t)h->num_cu) / std::max<int64_t>(1, items)));
     uint32_t CH = (uint32_t)align_up((size_t)std::max<int64_t>(1, (h->mirror.maxlen + nch - 1) / nch), 1024);
+    if (masked && h->force_chunk > 0) {
+        // ivfadc_set_tuning(h, 0, chunk_points): the points of a work item, in whole rounds of 64, so that short lists reach more than one
+        // chunk too (as the range search allows) -- doubled while a probe would leave more than SQM_MAX_CHUNKS partial results
+        CH = (uint32_t)align_up((size_t)h->force_chunk, 64);
+        while ((h->mirror.maxlen + CH - 1) / CH > SQM_MAX_CHUNKS) CH <<= 1;
+    }
     nch = (int)std::max<int64_t>(1, (h->mirror.maxlen + CH - 1) / CH);
     const size_t slots = (size_t)items * nch;
     TRY(h->sq_keys.ensure(slots * K * 8));
@@ -1753,13 +1781,15 @@ int search_small(ivfadc_index *h, const SearchCall &c)
     a.arrive = h->sq_arrive.as<u32>();
     a.out_ids = c.ids; a.out_dists = c.dists; a.out_counts = c.counts;
     a.scanned_points = h->misc.as<u64>();
-    const size_t lds = sq_lds_bytes(h->m, h->d, inside ? h->kc : 0);
-    sq_fn_t fn = pick_sq(h->m, h->dsub);
+    const size_t lds = masked ? sqm_lds_bytes(h->m, h->d, inside ? h->kc : 0) : sq_lds_bytes(h->m, h->d, inside ? h->kc : 0);
+    const sq_fn_t fn = pick_sq(h->m, h->dsub);
+    const sq_masked_fn_t mfn = pick_sq_masked(h->m, h->dsub);
     int occ = 0;
-    TRY(fn_occupancy(h, (const void *)fn, lds, occ));
+    TRY(fn_occupancy(h, masked ? (const void *)mfn : (const void *)fn, lds, occ));
     ivfadc_index::EvPair ep;
     if (h->profiling) TRY(ev_begin(h, 0, ep));
-    hipLaunchKernelGGL(fn, dim3((unsigned)slots), dim3(256), lds, h->stream, a);
+    if (masked) hipLaunchKernelGGL(mfn, dim3((unsigned)slots), dim3(256), lds, h->stream, a, mask_view(c), c.mask_nmasks);
+    else hipLaunchKernelGGL(fn, dim3((unsigned)slots), dim3(256), lds, h->stream, a);
     HIP_TRY(hipGetLastError());
     if (h->profiling) TRY(ev_end(h, ep));
     h->stats.queries += nq;
@@ -1772,6 +1802,8 @@ int search_small(ivfadc_index *h, const SearchCall &c)
     h->stats.last_scan_lds = (int)lds;
     return IVFADC_OK;
 }
+int search_small(ivfadc_index *h, const SearchCall &c) { return search_small_as(h, c, false); }
+int search_small_masked(ivfadc_index *h, const SearchCall &c) { return search_small_as(h, c, true); }
 
 // clears the hint of ivfadc_set_next_queries when a search ends, however it ends (a hint is good for ONE search)
 struct HintScope {
@@ -1978,7 +2010,8 @@ int begin_search(ivfadc_index *h, int64_t nq, bool take_rows, bool group_centroi
 // Supplied probes (c.pre_list, ivfadc_search_preassigned): the search has no coarse stage of its own -- no latency path, no fused top-w,
 // no matrix-core filter, no two-level search, no riders -- and everything behind the probe arrays runs as it does for a plain search.
 // A mask set (c.mask_words, ivfadc_search_masked): the coarse stage is the plain search's own, in any form; behind it the masked list
-// scan (make_plan_masked) or the masked generic path -- no latency path, no fused top-w, no riders.  Both together: there is no entry.
+// scan (make_plan_masked) or the masked generic path -- no fused top-w, no riders; the latency path on request only
+// (ivfadc_set_masked_latency: search_small_masked).  Both together: there is no entry.
 int search_dev(ivfadc_index *h, const SearchCall &c)
 {
     HintScope hint_scope{h};
@@ -1990,6 +2023,8 @@ int search_dev(ivfadc_index *h, const SearchCall &c)
     const bool parted = h->part_n > 1;
     if (masked && (pre || parted)) return fail(IVFADC_ERR_STATE, "a masked search takes neither supplied probes nor a list partition");
     if (!masked && !parted && !pre && sq_eligible(h, nq, K, w)) return search_small(h, c);
+    if (masked && masked_sq_eligible(h, nq, K, w)) return search_small_masked(h, c);
+    if (c.mask_raw) return fail(IVFADC_ERR_STATE, "unstaged mask numbers outside the masked latency path");
     if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && (masked || (K > 64 && !h->u16_wide)))) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
         return search_generic(h, c);
@@ -2991,7 +3026,17 @@ static int search_masked_entry(ivfadc_index *h, const ivfadc_maskset *s, SearchC
     TRY(set_device(h));
     h->dev_entry = false;
     c.d = h->d;
-    int rc = stage_mask_numbers(h, s, mask_of_query, !host, c);
+    // the device entry on the latency path: the kernel clamps the caller's array as it reads it -- no ingest launch in the chain
+    const bool raw = !host && masked_sq_eligible(h, c.nq, c.K, c.w);
+    int rc = IVFADC_OK;
+    if (raw) {
+        c.mask_words = s->words.as<u32>(); c.mask_word_off = s->word_off.as<uint64_t>(); c.mask_W = s->W;
+        c.mask_of_query = mask_of_query;
+        c.mask_raw = true;
+    } else {
+        rc = stage_mask_numbers(h, s, mask_of_query, !host, c);
+    }
+    c.mask_nmasks = s->nmasks;
     if (rc == IVFADC_OK) rc = host ? search_enqueue(h, c) : search_dev(h, c);
     return rc != IVFADC_OK || !host ? finish_entry(h, rc) : search_finish(h, c);
 }
@@ -5116,6 +5161,15 @@ try {
     }
     dq.release(); dt.release(); df.release();
     return rc;
+} IVF_CATCH
+
+int ivfadc_set_masked_latency(ivfadc_t *h, int mode)
+try {
+    HandleLock lk_(h);
+    if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
+    if (mode != 0 && mode != 1) return fail(IVFADC_ERR_INVALID, "mode must be 0 or 1");
+    h->masked_sq = mode == 1;
+    return IVFADC_OK;
 } IVF_CATCH
 
 int ivfadc_set_workspace_limit(ivfadc_t *h, uint64_t bytes)

@@ -5,6 +5,7 @@
 //   u16scan.hip.h   U16_*, u16_*_lds_bytes          lbscan.hip.h    LbCfg (lb_lds_bytes: its END and the four-wave tail)
 //   kernels.hip.h   carve_lds: FwLds / FwTail, whose end scan_lds_bytes returns (the carve adds up the lengths FwLds is made of and takes
 //                   the tail's offsets from fw_tail)                   smallq.hip.h    SqLds (sq_lds_bytes)
+//   sqmask.hip.h    SqmLds (sqm_lds_bytes): SqLds and the pending queues
 #pragma once
 
 #include <cstddef>
@@ -239,6 +240,27 @@ constexpr SqLds sq_tail(size_t base, int kc_inside)
 constexpr SqLds sq_lds(int m, int d, int kc_inside) { return sq_tail(fw_lds(m, d, 1, 1, 64, true).t.scnt, kc_inside); }
 static_assert(sq_tail(0, 0).s_row <= sq_tail(0, 0).end && sq_tail(8, 0).s_row <= sq_tail(8, 0).end, "the row starts inside the scratch block, whatever the gap");
 constexpr size_t sq_lds_bytes(int m, int d, int kc_inside) { return sq_lds(m, d, kc_inside).end; }
+
+// sq_masked_kernel (sqmask.hip.h): sq_kernel's carve as it stands and, behind the row of coarse distances, the four waves' pending queues --
+// SQM_QUEUE list positions each, used as a ring.  A wave pushes a round of up to 64 positions only while fewer than 64 are pending, so at
+// most 127 ever are: 128 is the smallest power of two that holds them.
+constexpr int SQM_QUEUE = 128;
+// sq_end: SqLds::end at kc_inside = 0, from the same base the result is meant from (the kernel: the tail's start; kc_inside is known at run time)
+constexpr size_t sqm_queue_off(size_t sq_end, int kc_inside) { return align_up(sq_end + (size_t)kc_inside * 4, 16); }
+struct SqmLds {
+    SqLds sq;
+    size_t queue, end;
+};
+constexpr SqmLds sqm_lds(int m, int d, int kc_inside)
+{
+    SqmLds s{};
+    s.sq = sq_lds(m, d, kc_inside);
+    s.queue = fw_lds(m, d, 1, 1, 64, true).t.scnt + sqm_queue_off(sq_tail(0, 0).end, kc_inside);
+    s.end = s.queue + (size_t)4 * SQM_QUEUE * 4;
+    return s;
+}
+static_assert(sqm_lds(8, 128, 0).queue >= sq_lds(8, 128, 0).end && sqm_lds(8, 128, 1000).queue >= sq_lds(8, 128, 1000).end, "the queues begin behind sq_kernel's carve");
+constexpr size_t sqm_lds_bytes(int m, int d, int kc_inside) { return sqm_lds(m, d, kc_inside).end; }
 
 // ---- the query-major kernel's matrix-core rounds (lbscan.hip.h, qscan_body<..., LB = true>) ------------------------------------------
 // shapes the matrix-core lower-bound rounds (qscan_kernel<..., LB = true>) are instantiated for, and their instantiations (M, DS, PG)

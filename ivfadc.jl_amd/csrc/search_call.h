@@ -26,7 +26,10 @@ struct SearchCall {
     const uint64_t *mask_word_off = nullptr;   // [kc + 1]
     uint64_t mask_W = 0;
     const int32_t *mask_of_query = nullptr;    // [nq]     ... and the mask number of every query, each in [-1, nmasks)
-    bool whole_batch = true;                   // this IS the entry's call, not a part of it: hints and prefetched rows apply
+    int mask_nmasks = 0;                       // masks of the set
+    bool mask_raw = false;                     // mask_of_query is the device entry's own array, untouched (null: mask 0; any value): the masked
+                                               // latency path alone takes it and clamps into [-1, mask_nmasks) as it reads
+    bool whole_batch = true;                  // this IS the entry's call, not a part of it: hints and prefetched rows apply
     bool pre() const { return pre_list != nullptr; }
     bool masked() const { return mask_words != nullptr; }
 

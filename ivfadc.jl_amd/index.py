@@ -611,6 +611,13 @@ class IVFADCIndex:
         accepts the call and plans what it planned before.  Results are the same bytes in every mode."""
         nat.check(nat.lib().ivfadc_set_u16_tables(self._h, int(mode)))
 
+    def set_masked_latency(self, mode):
+        """Latency path of the masked search.  0 (default): every masked search plans as before; 1: a masked search of a handful of
+        queries (UInt8 codes, nq <= 64, nq * w <= 512, K <= 64, w <= 64) runs in one launch whose point loop reads the mask first and
+        touches codes for selected entries only; get_stats()["last_qg"] is -3 when it ran.  Every other call plans as before.  Results
+        are the same bytes in both modes."""
+        nat.check(nat.lib().ivfadc_set_masked_latency(self._h, int(mode)))
+
     def debug_lb_table(self, query, cell):
         """Test hook: the 8-bit lower-bound ADC table of one (query, cell) pair as the matrix-core build makes it.
         Returns (table uint8 [m, 256], inv, sbase, nn, base [m], r2 [m])."""
