@@ -454,6 +454,66 @@ int ivfadc_score_ids(ivfadc_t *h, int64_t nq, const float *queries, int64_t C, i
 int ivfadc_score_ids_device(ivfadc_t *h, int64_t nq, const float *d_queries, int64_t C, int64_t ids_stride, const uint32_t *d_ids,
                             const int32_t *d_counts, float *d_out_dists, uint8_t *d_out_found);
 
+/* A VECTOR STORE: a device copy of the ORIGINAL vectors, owned by the library, made once and read-only afterwards -- what exact
+ * re-ranking (below) scores candidates against.  Owned the way a mask set is: it goes only by ivfadc_vectors_destroy, and any number of
+ * handles and threads read it at once.
+ *   data            n x d Float32, one vector per row (the memory of the reference's d x n matrix); d is h's.  The host entry takes a host
+ *                   pointer, the _device entry a device pointer on h's GPU.  The store is a COPY: data is not referred to afterwards.
+ *   store_type      0 keeps Float32.  1 keeps Float16, converted on the device with round-to-nearest-even (csrc/rerank.hip.h:
+ *                   vectors_to_f16_kernel); a FINITE component that overflows Float16 makes the call fail with IVFADC_ERR_INVALID and
+ *                   nothing is kept.  NaN and infinities are stored as they are.
+ *   row v           is "the vector stored under id v".  The store knows nothing of the lists: keeping that true across delete and shift
+ *                   (and choosing n to cover the ids in use) is the CALLER's business.
+ *   h               gives the device, d and, for the duration of the call, its stream and lock; the store holds no reference to h
+ *                   afterwards.  One store serves the index, its views and its subset views, and any other handle of the same d and GPU.
+ * Both entries block.  IVFADC_ERR_INVALID, each named in ivfadc_last_error(): null out, null handle, n < 0, n > 2^32, a store_type other
+ * than 0 and 1, null data with n > 0, d above 16384.  ivfadc_vectors_sizes reports n, d and store_type (any out pointer may be NULL).      */
+typedef struct ivfadc_vectors ivfadc_vectors_t;
+int ivfadc_vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_type, ivfadc_vectors_t **out);
+int ivfadc_vectors_create_device(ivfadc_t *h, int64_t n, const float *d_data, int store_type, ivfadc_vectors_t **out);
+void ivfadc_vectors_destroy(ivfadc_vectors_t *vs);
+int ivfadc_vectors_sizes(const ivfadc_vectors_t *vs, int64_t *out_n, int32_t *out_d, int32_t *out_store_type);
+
+/* EXACT RE-RANKING (IVFADC+R): candidate ids re-scored against the original vectors of a store, the K best kept (csrc/rerank_plan.h,
+ * csrc/rerank.hip.h).  The ADC distance cannot tell neighbours apart more finely than the codebooks allow; ask the search for more
+ * candidates than wanted, re-rank them, keep K.
+ * For query q and a live slot j whose id v = ids[q * C + j] is below the store's n, in Float32, one rounding per operation, nothing
+ * contracted -- the chain of the coarse distance (coarsequantizers.jl:33-34) with the stored vector in the centre's place:
+ *   s = 0;  t = 0 .. d-1:  u = x_v[t] - q[t];  s = s + u * u
+ * A Float16 row is widened exactly first.  Result of query q: the K smallest live slots under (s, slot position) ascending -- equal
+ * distances keep their order in the row -- fewer than K if fewer are live.
+ *   layout          queries is d x nq, as for ivfadc_search.  ids is nq x C uint32, row q at ids + q * C: the layout ivfadc_search_device
+ *                   writes with K = C.  counts may be NULL: all C slots are live; otherwise slot j >= counts[q] is dead.  The host entry
+ *                   refuses a counts[q] outside [0, C], naming the query; the _device entry clamps it.
+ *   out             out_ids (nq x K), out_dists (nq x K), out_counts (nq), shaped and ordered as ivfadc_search's; the slots of a row at
+ *                   or behind out_counts[q] are not written.
+ *   id >= n         dropped, as knn_among drops an absent id.  A repeated id is scored per slot and may appear twice.
+ *   non-finite      inputs are not scanned for; the place of a NaN distance in the order is unspecified.
+ *   h               gives d, the device, the stream, the lock and the workspace; its lists are not read (a handle without lists serves).
+ * The host entry blocks.  The _device entry takes every pointer in device memory of h's GPU and only enqueues on the handle's stream
+ * (asynchronous; pair with ivfadc_sync()).  Under ivfadc_set_workspace_limit the call is cut into slices of whole queries whose keys fit
+ * (8 bytes per slot; 16 where C > 4096 and the keys take the segmented sort).
+ * Argument errors, IVFADC_ERR_INVALID before the device is touched, each named in ivfadc_last_error(): null handle; null store; nq < 0;
+ * C < 0; K < 1; more than 2^31 - 1 pairs (nq x C); a store of another d or on another device; with nq > 0, null queries, null ids (C > 0),
+ * null out_ids, out_dists or out_counts; (host entry) a counts[q] outside [0, C].  nq == 0 returns IVFADC_OK; C == 0 finds nothing.
+ * Cost: one 128-byte line of HBM per 32 Float32 (64 Float16) components of every live pair, fetched by eight lanes per row, plus a sort of
+ * C keys per query.
+ * Not covered: ivfadc_mg_* handles, the list-partitioned mode, ivfadc_search_batches, the Julia shim.                                   */
+int ivfadc_rerank(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int64_t C, const uint32_t *ids,
+                  const int32_t *counts, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts);
+int ivfadc_rerank_device(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *d_queries, int64_t C, const uint32_t *d_ids,
+                         const int32_t *d_counts, int K, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
+
+/* The FUSED call: ivfadc_search with K = Kc into library workspace, then the re-rank above on its ids and counts, with no host round trip,
+ * on the handle's stream and under its lock.  Kc >= K is required (IVFADC_ERR_INVALID otherwise).  Whatever the plain search serves is
+ * served here, through its planner: 8-bit and UInt16 handles, views, subset views, :opq files; what it refuses (no lists, a stale view,
+ * w < 1) is refused in its words.  The distances returned are the re-rank's, not ADC distances.  Host entry blocks; _device entry only
+ * enqueues.  Argument errors as for ivfadc_rerank, with Kc in C's place.                                                                */
+int ivfadc_search_refined(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int K, int Kc, int w, uint32_t *out_ids,
+                          float *out_dists, int32_t *out_counts);
+int ivfadc_search_device_refined(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *d_queries, int K, int Kc, int w,
+                                 uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts);
+
 /* The seam of the reference's knn_search.  index.jl:204-258 calls coarse_search(cq, point, w) once (index.jl:219) and everything after it
  * -- residuals, ADC tables, the list scan seeded with dc, top-K (index.jl:220-257) -- reads only the two vectors it returns;
  * AbstractCoarseQuantizer (coarsequantizers.jl:6) is the reference's one plug-in interface.  The two halves are exported separately, so a

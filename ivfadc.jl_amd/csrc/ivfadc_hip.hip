@@ -17,6 +17,7 @@
 #include "range.hip.h"
 #include "reconstruct.hip.h"
 #include "score.hip.h"
+#include "rerank.hip.h"
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
@@ -449,6 +450,9 @@ struct Workspace {
     // prefix, rocPRIM scratch, and the host entries' staging of requests and results
     DevBuf rc_want, rc_best, rc_bitmap, rc_chunk, rc_tmp, rc_req, rc_list, rc_pos, rc_found, rc_vec;
     DevBuf sc_q, sc_ids, sc_cnt, sc_dist, sc_found;   // ivfadc_score_ids (host pointers): the caller's queries, ids and counts on the device, the results
+    // ivfadc_rerank (rerank.hip.h): the slice's keys, their sorted copy and segment offsets (sort form); the host entries' staging of queries,
+    // ids, counts and results; the fused call's candidates (the plain search's results with K = Kc)
+    DevBuf rr_keys, rr_sorted, rr_off, rr_q, rr_ids, rr_cnt, rr_oid, rr_od, rr_oc, rr_cid, rr_cd, rr_cc;
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
@@ -458,7 +462,7 @@ struct Workspace {
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
-                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_req, &rc_list, &rc_pos, &rc_found, &rc_vec, &sc_q, &sc_ids, &sc_cnt, &sc_dist, &sc_found, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_req, &rc_list, &rc_pos, &rc_found, &rc_vec, &sc_q, &sc_ids, &sc_cnt, &sc_dist, &sc_found, &rr_keys, &rr_sorted, &rr_off, &rr_q, &rr_ids, &rr_cnt, &rr_oid, &rr_od, &rr_oc, &rr_cid, &rr_cd, &rr_cc, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
                           &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
                           &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
             f(*b);
@@ -3310,10 +3314,11 @@ try {
     return IVFADC_OK;
 } IVF_CATCH
 
-int ivfadc_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w, uint32_t *d_out_ids, float *d_out_dists,
-                         int32_t *d_out_counts)
-try {
-    HandleLock lk_(h);
+// the body of ivfadc_search_device, for a caller that holds the handle's lock already (the fused refined call): a view's lock is taken
+// behind the topology mutex and never the other way round, so nothing that holds it may enter a public entry again
+static int search_device_locked(ivfadc_index *h, int64_t nq, const float *d_queries, int K, int w, uint32_t *d_out_ids, float *d_out_dists,
+                                int32_t *d_out_counts)
+{
     TRY(check_search_args(h, nq, K, w));
     if (nq > 0 && (!d_queries || !d_out_ids || !d_out_dists || !d_out_counts)) return fail(IVFADC_ERR_INVALID, "null buffer");
     {
@@ -3326,6 +3331,13 @@ try {
     }
     struct Reset { ivfadc_index *h; ~Reset() { h->dev_entry = false; } } reset_{h};   // (also when an exception unwinds into IVF_CATCH)
     return search_dev(h, SearchCall{nq, h->d, K, w, d_queries, d_out_ids, d_out_dists, d_out_counts});
+}
+
+int ivfadc_search_device(ivfadc_t *h, int64_t nq, const float *d_queries, int K, int w, uint32_t *d_out_ids, float *d_out_dists,
+                         int32_t *d_out_counts)
+try {
+    HandleLock lk_(h);
+    return search_device_locked(h, nq, d_queries, K, w, d_out_ids, d_out_dists, d_out_counts);
 } IVF_CATCH
 
 // ---- locate / reconstruct (reconstruct_plan.h, reconstruct.hip.h) ----------------------------------------------------
@@ -3617,6 +3629,317 @@ try {
     HandleLock lk_(h);
     TRY(recon_begin(h, "ivfadc_score_ids_device"));
     return recon_exit(h, score_enqueue(h, nq, d_queries, C, ids_stride, d_ids, d_counts, d_out_dists, d_out_found, false, 0u, 0u));
+} IVF_CATCH
+
+// ---- exact re-ranking against the original vectors (rerank_plan.h, rerank.hip.h) --------------------------------------
+// A vector store is a device copy of the original vectors, made once and read-only afterwards, owned the way a mask set is: it keeps the
+// device and d of the handle it was made with and nothing else of it.
+struct ivfadc_vectors {
+    int device = 0;
+    int d = 0;
+    int64_t n = 0;
+    int store_type = 0;
+    DevBuf data;     // n rows of d Float32 or Float16 components
+};
+
+// rows of one conversion pass of a host-pointer Float16 store: the Float32 piece sits in pts_stage (at most 64 MB of it)
+static int64_t vectors_piece_rows(int64_t n, int d) { return std::max<int64_t>(1, std::min<int64_t>(n, ((int64_t)64 << 20) / ((int64_t)d * 4))); }
+
+static int vectors_convert(ivfadc_index *h, const float *d_src, uint64_t total, unsigned short *d_dst, u32 *d_flag)
+{
+    if (total == 0) return IVFADC_OK;
+    const unsigned grid = (unsigned)std::min<uint64_t>(4096, (total + 255) / 256);
+    hipLaunchKernelGGL(vectors_to_f16_kernel, dim3(grid), dim3(256), 0, h->stream, d_src, total, d_dst, d_flag);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+static int vectors_fill(ivfadc_index *h, ivfadc_vectors *vs, const float *data, bool on_device)
+{
+    const bool f16 = vs->store_type == rerank::STORE_F16;
+    const uint64_t total = (uint64_t)vs->n * (uint64_t)vs->d;
+    TRY(vs->data.alloc_exact(std::max<size_t>(16, (size_t)rerank::store_bytes((uint64_t)vs->n, vs->d, f16))));
+    if (total == 0) return IVFADC_OK;
+    if (!f16) {
+        if (!on_device) return h2d_copy(vs->data.p, data, total * 4, h->stream);
+        HIP_TRY(hipMemcpyAsync(vs->data.p, data, total * 4, hipMemcpyDeviceToDevice, h->stream));
+        HIP_TRY(hipStreamSynchronize(h->stream));
+        return IVFADC_OK;
+    }
+    const u32 zero = 0;
+    u32 flag = 0;
+    TRY(h->rr_off.ensure(16));
+    TRY(h2d_copy(h->rr_off.p, &zero, 4, h->stream));
+    if (on_device) {
+        TRY(vectors_convert(h, data, total, vs->data.as<unsigned short>(), h->rr_off.as<u32>()));
+    } else {
+        const int64_t piece = vectors_piece_rows(vs->n, vs->d);
+        TRY(h->pts_stage.ensure((size_t)piece * vs->d * 4));
+        for (int64_t r0 = 0; r0 < vs->n; r0 += piece) {
+            const uint64_t rows = (uint64_t)std::min<int64_t>(piece, vs->n - r0), off = (uint64_t)r0 * (uint64_t)vs->d;
+            TRY(h2d_copy(h->pts_stage.p, data + off, rows * vs->d * 4, h->stream));
+            TRY(vectors_convert(h, h->pts_stage.as<float>(), rows * vs->d, vs->data.as<unsigned short>() + off, h->rr_off.as<u32>()));
+            HIP_TRY(hipStreamSynchronize(h->stream));   // the next piece overwrites pts_stage
+        }
+    }
+    TRY(d2h_copy(&flag, h->rr_off.p, 4, h->stream));
+    if (flag) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: a finite component overflows Float16 (store_type 1); nothing is kept");
+    return IVFADC_OK;
+}
+
+static int vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_type, ivfadc_vectors_t **out, bool on_device)
+{
+    if (!out) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: null out");
+    *out = nullptr;
+    if (!h) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: null handle");
+    if (n < 0) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: n = %lld < 0", (long long)n);
+    if (n > ((int64_t)1 << 32)) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: n exceeds 2^32 (ids are UInt32)");
+    if (store_type != rerank::STORE_F32 && store_type != rerank::STORE_F16)
+        return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: store_type = %d (0: Float32, 1: Float16)", store_type);
+    if (n > 0 && !data) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: null data with n > 0");
+    HandleLock lk_(h);
+    if (h->d > rerank::MAX_D) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: d = %d (a store takes vectors of at most %d components)", h->d, rerank::MAX_D);
+    TRY(set_device(h));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // rr_off and pts_stage are the handle's: nothing enqueued earlier still reads them
+    std::unique_ptr<ivfadc_vectors> vs(new ivfadc_vectors());
+    vs->device = h->device;
+    vs->d = h->d;
+    vs->n = n;
+    vs->store_type = store_type;
+    const int rc = vectors_fill(h, vs.get(), data, on_device);
+    if (rc != IVFADC_OK) {
+        (void)recon_exit(h, rc);   // drains the stream and keeps the message: nothing still writes the store
+        vs->data.release();
+        return rc;
+    }
+    *out = vs.release();
+    return IVFADC_OK;
+}
+
+int ivfadc_vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_type, ivfadc_vectors_t **out)
+try {
+    return vectors_create(h, n, data, store_type, out, false);
+} IVF_CATCH
+
+int ivfadc_vectors_create_device(ivfadc_t *h, int64_t n, const float *d_data, int store_type, ivfadc_vectors_t **out)
+try {
+    return vectors_create(h, n, d_data, store_type, out, true);
+} IVF_CATCH
+
+void ivfadc_vectors_destroy(ivfadc_vectors_t *vs)
+{
+    if (!vs) return;
+    int prev = -1;   // the calling thread's current device is the caller's: left as it was
+    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+    if (hipSetDevice(vs->device) == hipSuccess) vs->data.release();
+    if (prev >= 0 && prev != vs->device) (void)hipSetDevice(prev);
+    delete vs;
+}
+
+int ivfadc_vectors_sizes(const ivfadc_vectors_t *vs, int64_t *out_n, int32_t *out_d, int32_t *out_store_type)
+try {
+    if (!vs) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_sizes: null store");
+    if (out_n) *out_n = vs->n;
+    if (out_d) *out_d = vs->d;
+    if (out_store_type) *out_store_type = vs->store_type;
+    return IVFADC_OK;
+} IVF_CATCH
+
+// the arguments of the rerank entries, before the device is touched (Kc < 0: not the fused call)
+static int check_rerank_args(const char *fn, ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int64_t C, const uint32_t *ids,
+                             bool need_ids, int K, const uint32_t *out_ids, const float *out_dists, const int32_t *out_counts)
+{
+    if (!h) return fail(IVFADC_ERR_INVALID, "%s: null handle", fn);
+    if (!vs) return fail(IVFADC_ERR_INVALID, "%s: null vector store", fn);
+    if (nq < 0) return fail(IVFADC_ERR_INVALID, "%s: nq = %lld < 0", fn, (long long)nq);
+    if (C < 0) return fail(IVFADC_ERR_INVALID, "%s: C = %lld < 0", fn, (long long)C);
+    if (K < 1) return fail(IVFADC_ERR_INVALID, "%s: K = %d < 1", fn, K);
+    if (!rerank::pairs_fit(nq, C))
+        return fail(IVFADC_ERR_INVALID, "%s: nq x C = %lld x %lld pairs in one call (at most 2^31 - 1)", fn, (long long)nq, (long long)C);
+    if (nq == 0) return IVFADC_OK;
+    if (!queries) return fail(IVFADC_ERR_INVALID, "%s: null queries", fn);
+    if (need_ids && C > 0 && !ids) return fail(IVFADC_ERR_INVALID, "%s: null ids", fn);
+    if (!out_ids) return fail(IVFADC_ERR_INVALID, "%s: null out_ids", fn);
+    if (!out_dists) return fail(IVFADC_ERR_INVALID, "%s: null out_dists", fn);
+    if (!out_counts) return fail(IVFADC_ERR_INVALID, "%s: null out_counts", fn);
+    return IVFADC_OK;
+}
+
+// the store fits the handle (the last argument check: the only one that reads the two objects)
+static int check_rerank_link(const char *fn, const ivfadc_index *h, const ivfadc_vectors *vs)
+{
+    if (vs->d != h->d) return fail(IVFADC_ERR_INVALID, "%s: the vector store holds vectors of d = %d, the handle of d = %d", fn, vs->d, h->d);
+    if (vs->device != h->device) return fail(IVFADC_ERR_INVALID, "%s: the vector store lies on device %d, the handle on device %d", fn, vs->device, h->device);
+    return IVFADC_OK;
+}
+
+// every pointer in device memory; only enqueues.  nq > 0, C > 0
+static int rerank_enqueue(ivfadc_index *h, const ivfadc_vectors *vs, int64_t nq, const float *d_q, int64_t C, const uint32_t *d_ids,
+                          const int32_t *d_counts, int K, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
+{
+    const bool f16 = vs->store_type == rerank::STORE_F16;
+    const rerank::Plan pl = rerank::make_plan(nq, C, h->d, f16, (uint64_t)h->ws_budget);
+    void (*dist)(const RerankArgs) = f16 ? (pl.vec ? rerank_dist_kernel<true, true> : rerank_dist_kernel<true, false>)
+                                         : (pl.vec ? rerank_dist_kernel<false, true> : rerank_dist_kernel<false, false>);
+    TRY(fn_raise_lds(h->device, (const void *)dist, pl.dist_lds, false));
+    TRY(h->rr_keys.ensure((size_t)pl.slice_keys * 8));
+    if (pl.form == rerank::SELECT_SORT) {
+        TRY(h->rr_sorted.ensure((size_t)pl.slice_keys * 8));
+        TRY(h->rr_off.ensure((size_t)(pl.slice_nq + 1) * 4));
+    }
+    RerankArgs a{};
+    a.rows = vs->data.as<uint8_t>();
+    a.n = (uint64_t)vs->n;
+    a.d = h->d;
+    a.queries = d_q;
+    a.ids = d_ids;
+    a.counts = d_counts;
+    a.C = C;
+    a.keys = h->rr_keys.as<u64>();
+    for (int64_t s = 0; s < pl.nslices; ++s) {
+        const int64_t q0 = rerank::slice_begin(pl, s), nqs = rerank::slice_queries(pl, s);
+        a.q0 = q0;
+        hipLaunchKernelGGL(dist, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        if (pl.form == rerank::SELECT_LDS) {
+            hipLaunchKernelGGL(rerank_select_kernel<false>, dim3((unsigned)nqs), dim3(256), pl.select_lds, h->stream, h->rr_keys.as<u64>(), C, pl.padded,
+                               q0, d_ids, K, d_out_ids, d_out_dists, d_out_counts);
+        } else {
+            hipLaunchKernelGGL(rerank_offsets_kernel, dim3((unsigned)((nqs + 256) / 256)), dim3(256), 0, h->stream, h->rr_off.as<u32>(), nqs, C);
+            HIP_TRY(hipGetLastError());
+            TRY(gen_sort(h, h->rr_keys.as<u64>(), h->rr_sorted.as<u64>(), nqs * C, (int)nqs, h->rr_off.as<u32>()));
+            hipLaunchKernelGGL(rerank_select_kernel<true>, dim3((unsigned)nqs), dim3(256), 0, h->stream, h->rr_sorted.as<u64>(), C, 0, q0, d_ids, K,
+                               d_out_ids, d_out_dists, d_out_counts);
+        }
+        HIP_TRY(hipGetLastError());
+    }
+    return IVFADC_OK;
+}
+
+// C == 0: every query finds nothing
+static int rerank_empty(ivfadc_index *h, int64_t nq, int32_t *d_out_counts)
+{
+    hipLaunchKernelGGL(rerank_zero_counts_kernel, dim3((unsigned)std::min<int64_t>(4096, (nq + 255) / 256)), dim3(256), 0, h->stream, d_out_counts, nq);
+    HIP_TRY(hipGetLastError());
+    return IVFADC_OK;
+}
+
+int ivfadc_rerank_device(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *d_queries, int64_t C, const uint32_t *d_ids,
+                         const int32_t *d_counts, int K, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
+try {
+    TRY(check_rerank_args("ivfadc_rerank_device", h, vs, nq, d_queries, C, d_ids, true, K, d_out_ids, d_out_dists, d_out_counts));
+    if (nq == 0) return IVFADC_OK;
+    TRY(check_rerank_link("ivfadc_rerank_device", h, vs));
+    HandleLock lk_(h);
+    TRY(set_device(h));
+    if (C == 0) return recon_exit(h, rerank_empty(h, nq, d_out_counts));
+    return recon_exit(h, rerank_enqueue(h, vs, nq, d_queries, C, d_ids, d_counts, K, d_out_ids, d_out_dists, d_out_counts));
+} IVF_CATCH
+
+// A host entry stages rows of min(K, C) slots: no row can hold more results than it has candidates.
+static int rerank_stage_width(int K, int64_t C) { return (int)std::min<int64_t>(K, C); }
+
+// the results of a host entry, out of rr_oid / rr_od / rr_oc (rows of Kw slots): the first out_counts[q] slots of every row into the
+// caller's rows of K slots; the others are not written
+static int rerank_hand_over(ivfadc_index *h, int64_t nq, int Kw, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+{
+    const size_t slots = (size_t)nq * (size_t)Kw;
+    std::vector<uint32_t> ids(slots);
+    std::vector<float> dists(slots);
+    TRY(d2h_copy(out_counts, h->rr_oc.p, (size_t)nq * 4, h->stream));
+    TRY(d2h_copy(ids.data(), h->rr_oid.p, slots * 4, h->stream));
+    TRY(d2h_copy(dists.data(), h->rr_od.p, slots * 4, h->stream));
+    for (int64_t q = 0; q < nq; ++q) {
+        const size_t cnt = (size_t)std::max(0, std::min(out_counts[q], Kw)), from = (size_t)q * (size_t)Kw, at = (size_t)q * (size_t)K;
+        memcpy(out_ids + at, ids.data() + from, cnt * 4);
+        memcpy(out_dists + at, dists.data() + from, cnt * 4);
+    }
+    return IVFADC_OK;
+}
+
+static int rerank_out_buffers(ivfadc_index *h, int64_t nq, int Kw)
+{
+    const size_t slots = (size_t)nq * (size_t)Kw;
+    TRY(h->rr_oid.ensure(slots * 4));
+    TRY(h->rr_od.ensure(slots * 4));
+    TRY(h->rr_oc.ensure((size_t)nq * 4));
+    return IVFADC_OK;
+}
+
+int ivfadc_rerank(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int64_t C, const uint32_t *ids, const int32_t *counts,
+                  int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+try {
+    TRY(check_rerank_args("ivfadc_rerank", h, vs, nq, queries, C, ids, true, K, out_ids, out_dists, out_counts));
+    for (int64_t q = 0; counts && q < nq; ++q)
+        if (counts[q] < 0 || (int64_t)counts[q] > C)
+            return fail(IVFADC_ERR_INVALID, "ivfadc_rerank: query %lld: counts = %d outside [0, %lld]", (long long)q, (int)counts[q], (long long)C);
+    if (nq == 0) return IVFADC_OK;
+    TRY(check_rerank_link("ivfadc_rerank", h, vs));
+    if (C == 0) { memset(out_counts, 0, (size_t)nq * 4); return IVFADC_OK; }
+    HandleLock lk_(h);
+    TRY(set_device(h));
+    const size_t pairs = (size_t)nq * (size_t)C;
+    const int Kw = rerank_stage_width(K, C);
+    int rc = h->rr_q.ensure((size_t)nq * h->d * 4);
+    if (rc == IVFADC_OK) rc = h->rr_ids.ensure(pairs * 4);
+    if (rc == IVFADC_OK && counts) rc = h->rr_cnt.ensure((size_t)nq * 4);
+    if (rc == IVFADC_OK) rc = rerank_out_buffers(h, nq, Kw);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->rr_q.p, queries, (size_t)nq * h->d * 4, h->stream);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->rr_ids.p, ids, pairs * 4, h->stream);
+    if (rc == IVFADC_OK && counts) rc = h2d_copy(h->rr_cnt.p, counts, (size_t)nq * 4, h->stream);
+    if (rc == IVFADC_OK)
+        rc = rerank_enqueue(h, vs, nq, h->rr_q.as<float>(), C, h->rr_ids.as<u32>(), counts ? h->rr_cnt.as<int32_t>() : (const int32_t *)nullptr, Kw,
+                            h->rr_oid.as<u32>(), h->rr_od.as<float>(), h->rr_oc.as<int32_t>());
+    if (rc == IVFADC_OK) rc = rerank_hand_over(h, nq, Kw, K, out_ids, out_dists, out_counts);
+    return recon_exit(h, rc);
+} IVF_CATCH
+
+// the plain search with K = Kc into rr_cid / rr_cd / rr_cc (the body of ivfadc_search_device under the lock the entry holds: its planner,
+// its refusals), then the re-rank
+static int search_refined_dev(ivfadc_index *h, const ivfadc_vectors *vs, int64_t nq, const float *d_q, int K, int Kc, int w, uint32_t *d_out_ids,
+                              float *d_out_dists, int32_t *d_out_counts)
+{
+    const size_t slots = (size_t)nq * (size_t)Kc;
+    TRY(h->rr_cid.ensure(slots * 4));
+    TRY(h->rr_cd.ensure(slots * 4));
+    TRY(h->rr_cc.ensure((size_t)nq * 4));
+    TRY(search_device_locked(h, nq, d_q, Kc, w, h->rr_cid.as<u32>(), h->rr_cd.as<float>(), h->rr_cc.as<int32_t>()));
+    return rerank_enqueue(h, vs, nq, d_q, Kc, h->rr_cid.as<u32>(), h->rr_cc.as<int32_t>(), K, d_out_ids, d_out_dists, d_out_counts);
+}
+
+static int check_refined_args(const char *fn, ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int K, int Kc, int w,
+                              const uint32_t *out_ids, const float *out_dists, const int32_t *out_counts)
+{
+    if (h && vs && K >= 1 && Kc < K) return fail(IVFADC_ERR_INVALID, "%s: Kc = %d < K = %d (the search must hand over at least K candidates)", fn, Kc, K);
+    TRY(check_rerank_args(fn, h, vs, nq, queries, Kc, nullptr, false, K, out_ids, out_dists, out_counts));
+    if (w < 1) return fail(IVFADC_ERR_ASSERT, "Number of clusters to search in must be w >= 1");
+    return nq == 0 ? IVFADC_OK : check_rerank_link(fn, h, vs);
+}
+
+int ivfadc_search_device_refined(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *d_queries, int K, int Kc, int w,
+                                 uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
+try {
+    TRY(check_refined_args("ivfadc_search_device_refined", h, vs, nq, d_queries, K, Kc, w, d_out_ids, d_out_dists, d_out_counts));
+    if (nq == 0) return IVFADC_OK;
+    HandleLock lk_(h);
+    TRY(set_device(h));
+    return recon_exit(h, search_refined_dev(h, vs, nq, d_queries, K, Kc, w, d_out_ids, d_out_dists, d_out_counts));
+} IVF_CATCH
+
+int ivfadc_search_refined(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int K, int Kc, int w, uint32_t *out_ids,
+                          float *out_dists, int32_t *out_counts)
+try {
+    TRY(check_refined_args("ivfadc_search_refined", h, vs, nq, queries, K, Kc, w, out_ids, out_dists, out_counts));
+    if (nq == 0) return IVFADC_OK;
+    HandleLock lk_(h);
+    TRY(set_device(h));
+    int rc = h->rr_q.ensure((size_t)nq * h->d * 4);
+    if (rc == IVFADC_OK) rc = rerank_out_buffers(h, nq, K);
+    if (rc == IVFADC_OK) rc = h2d_copy(h->rr_q.p, queries, (size_t)nq * h->d * 4, h->stream);
+    if (rc == IVFADC_OK)
+        rc = search_refined_dev(h, vs, nq, h->rr_q.as<float>(), K, Kc, w, h->rr_oid.as<u32>(), h->rr_od.as<float>(), h->rr_oc.as<int32_t>());
+    if (rc == IVFADC_OK) rc = rerank_hand_over(h, nq, K, K, out_ids, out_dists, out_counts);   // (Kc >= K: the rows are K wide)
+    return recon_exit(h, rc);
 } IVF_CATCH
 
 // ---- list-partitioned multi-GPU mode: strong scaling of a FIXED global batch --------------------------------------------------------------

@@ -702,6 +702,71 @@ class IVFADCIndex:
                                                     C.c_void_p(counts_ptr) if counts_ptr else None, C.c_void_p(dists_ptr),
                                                     C.c_void_p(found_ptr) if found_ptr else None))
 
+    # ---- exact re-ranking against the original vectors (ivfadc_vectors_create, ivfadc_rerank, ivfadc_search_refined) ----
+    def vectors(self, data, dtype=np.float32):
+        """A VectorStore of `data` (n, d) on this index's GPU (ivfadc_vectors_create): row v is the vector stored under id v.
+        dtype np.float32 keeps the rows as they are, np.float16 rounds them to nearest even on the device (a finite component that
+        overflows Float16 raises IVFADCError).  The store is a copy and serves this index, its views and its subset views."""
+        data = np.ascontiguousarray(data, np.float32)
+        assert data.ndim == 2 and data.shape[1] == self.d, "data must be (n, %d)" % self.d
+        return self._vectors(nat.lib().ivfadc_vectors_create, nat.ptr(data, C.c_float) if data.shape[0] else None, data.shape[0], dtype)
+
+    def vectors_device(self, d_data_ptr, n, dtype=np.float32):
+        """vectors() from n x d float32 rows that already lie in device memory of this index's GPU (ivfadc_vectors_create_device)."""
+        return self._vectors(nat.lib().ivfadc_vectors_create_device, C.c_void_p(int(d_data_ptr)) if n else None, int(n), dtype)
+
+    def _vectors(self, entry, data, n, dtype):
+        dtype = np.dtype(dtype)
+        assert dtype in (np.dtype(np.float32), np.dtype(np.float16)), "a vector store keeps float32 or float16"
+        s = C.c_void_p()
+        nat.check(entry(self._h, int(n), data, 1 if dtype == np.dtype(np.float16) else 0, C.byref(s)))
+        return VectorStore(s)
+
+    def rerank_raw(self, store, queries, ids, k, counts=None):
+        """queries (nq, d), ids (nq, C) and optional counts (nq,) of live slots per query -> ids (nq, k) uint32, dists (nq, k) float32,
+        counts (nq,) int32 via ivfadc_rerank: per query the k live slots closest to it by the exact Float32 distance to the store's
+        rows, ordered by (distance, slot); an id at or beyond len(store) is dropped."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        nq = q.shape[0]
+        ids = np.ascontiguousarray(ids, np.uint32)
+        assert ids.ndim == 2 and ids.shape[0] == nq, "ids must be (nq, C)"
+        if counts is not None:
+            counts = np.ascontiguousarray(counts, np.int32).reshape(-1)
+            assert counts.shape[0] == nq, "counts must hold one number per query"
+        out = self._refined_out(nq, k)
+        nat.check(nat.lib().ivfadc_rerank(self._h, store._s, nq, nat.ptr(q, C.c_float), ids.shape[1], nat.ptr(ids, C.c_uint32),
+                                          nat.ptr(counts, C.c_int32), int(k), nat.ptr(out[0], C.c_uint32), nat.ptr(out[1], C.c_float),
+                                          nat.ptr(out[2], C.c_int32)))
+        return out
+
+    @staticmethod
+    def _refined_out(nq, k):
+        ka = max(int(k), 1)
+        return np.zeros((nq, ka), np.uint32), np.full((nq, ka), np.inf, np.float32), np.zeros(nq, np.int32)
+
+    def rerank_device(self, store, nq, q_ptr, ncand, ids_ptr, counts_ptr, k, out_ids_ptr, out_dists_ptr, out_counts_ptr):
+        """Asynchronous on raw device pointers (ints): nq x d float32 queries, nq x ncand uint32 ids (what search_device writes with
+        k = ncand), optional nq int32 counts -> nq x k ids and distances, nq counts; see ivfadc_rerank_device."""
+        nat.check(nat.lib().ivfadc_rerank_device(self._h, store._s, int(nq), C.c_void_p(q_ptr), int(ncand), C.c_void_p(ids_ptr),
+                                                 C.c_void_p(counts_ptr) if counts_ptr else None, int(k), C.c_void_p(out_ids_ptr),
+                                                 C.c_void_p(out_dists_ptr), C.c_void_p(out_counts_ptr)))
+
+    def search_refined_raw(self, store, queries, k, kc, w=1):
+        """search_raw with k = kc, then rerank_raw of its ids against `store`, in one native call with no host round trip
+        (ivfadc_search_refined): ids (nq, k), exact distances (nq, k), counts (nq,)."""
+        q = np.ascontiguousarray(queries, np.float32)
+        assert q.ndim == 2 and q.shape[1] == self.d, "queries must be (nq, %d)" % self.d
+        out = self._refined_out(q.shape[0], k)
+        nat.check(nat.lib().ivfadc_search_refined(self._h, store._s, q.shape[0], nat.ptr(q, C.c_float), int(k), int(kc), int(w),
+                                                  nat.ptr(out[0], C.c_uint32), nat.ptr(out[1], C.c_float), nat.ptr(out[2], C.c_int32)))
+        return out
+
+    def search_device_refined(self, store, nq, q_ptr, k, kc, w, ids_ptr, dists_ptr, counts_ptr):
+        """Asynchronous refined search on raw device pointers (ints); see ivfadc_search_device_refined."""
+        nat.check(nat.lib().ivfadc_search_device_refined(self._h, store._s, int(nq), C.c_void_p(q_ptr), int(k), int(kc), int(w),
+                                                         C.c_void_p(ids_ptr), C.c_void_p(dists_ptr), C.c_void_p(counts_ptr)))
+
 
 def _comm_methods():
     """one-process-per-GPU merge inside the library (ivfadc_comm_*): methods of IVFADCIndex"""
@@ -782,6 +847,30 @@ class MaskSet:
         if s is not None and s.value:
             try:
                 nat.lib().ivfadc_maskset_destroy(s)
+            except Exception:
+                pass
+            self._s = C.c_void_p()
+
+
+class VectorStore:
+    """The original vectors on the device, Float32 or Float16 (ivfadc_vectors_t; IVFADCIndex.vectors): what rerank and
+    knn_search_refined score candidates against.  Immutable; len() is the number of rows, `d` and `dtype` their shape and type.  It
+    keeps nothing of the index it was made with; the native object goes with this one."""
+
+    def __init__(self, s):
+        self._s = s
+        n, d, t = C.c_int64(), C.c_int32(), C.c_int32()
+        nat.check(nat.lib().ivfadc_vectors_sizes(s, C.byref(n), C.byref(d), C.byref(t)))
+        self._n, self.d, self.dtype = int(n.value), int(d.value), np.dtype(np.float16 if t.value == 1 else np.float32)
+
+    def __len__(self):
+        return self._n
+
+    def __del__(self):
+        s = getattr(self, "_s", None)
+        if s is not None and s.value:
+            try:
+                nat.lib().ivfadc_vectors_destroy(s)
             except Exception:
                 pass
             self._s = C.c_void_p()
@@ -1061,6 +1150,37 @@ def knn_among(ivfadc, points, ids, k):
     if single:
         return out_i[0], out_d[0]
     return out_i, out_d
+
+
+def _rows(ivfadc, ids, dists, counts, single):
+    """the raw result blocks as knn_search hands them out"""
+    out_i = [ids[i, :counts[i]].astype(ivfadc.index_type) for i in range(ids.shape[0])]
+    out_d = [dists[i, :counts[i]].copy() for i in range(ids.shape[0])]
+    return (out_i[0], out_d[0]) if single else (out_i, out_d)
+
+
+def rerank(ivfadc, store, points, ids, k):
+    """The k best of the given candidate ids per query by the EXACT distance to the original vectors in `store` (ivfadc_rerank), in
+    knn_among's shapes: (ids, dists), ordered by (distance, position in the row); an id at or beyond len(store) is dropped, so a row
+    may come back shorter than k.  `ids` is (nq, C), or (C,) for one row scored against every query.  One query returns two arrays, a
+    batch two lists of arrays."""
+    assert k >= 1, "Number of neighbors must be k >= 1"                          # index.jl:210
+    pts, single = _as_points(ivfadc, points)
+    ids = np.ascontiguousarray(ids, np.uint32)
+    if ids.ndim == 1:
+        ids = np.broadcast_to(ids, (pts.shape[0], ids.shape[0]))
+    return _rows(ivfadc, *ivfadc.rerank_raw(store, pts, ids, k), single)
+
+
+def knn_search_refined(ivfadc, store, points, k, w=1, kc=None):
+    """knn_search with exact re-ranking (IVFADC+R; ivfadc_search_refined): the search is asked for kc candidates (default 10 * k), they
+    are re-scored against the original vectors in `store` on the device, and the k best are returned with their exact distances."""
+    assert k >= 1, "Number of neighbors must be k >= 1"                          # index.jl:210
+    assert w >= 1, "Number of clusters to search in must be w >= 1"             # index.jl:211
+    kc = 10 * int(k) if kc is None else int(kc)
+    assert kc >= k, "kc must be at least k"
+    pts, single = _as_points(ivfadc, points)
+    return _rows(ivfadc, *ivfadc.search_refined_raw(store, pts, k, kc, w), single)
 
 
 def _pop(ivfadc, position):
