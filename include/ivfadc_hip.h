@@ -474,6 +474,45 @@ int ivfadc_vectors_create_device(ivfadc_t *h, int64_t n, const float *d_data, in
 void ivfadc_vectors_destroy(ivfadc_vectors_t *vs);
 int ivfadc_vectors_sizes(const ivfadc_vectors_t *vs, int64_t *out_n, int32_t *out_d, int32_t *out_store_type);
 
+/* A PQ STORE (store_type 2): a COMPRESSED vector store, re-ranking with source coding (Jegou, Tavenard, Douze, Amsaleg; IVFADC+R) -- for
+ * the shapes whose original vectors do not fit beside the index (csrc/vstore_pq_plan.h, csrc/rerank.hip.h).  Row v is one record: list_v
+ * (uint32), the m base codeword INDICES (not labels) of the row and m2 refinement codeword indices, one byte each, padded to the power of
+ * two at or above 4 + m + m2 (at least 8): 32 bytes at m = 8, m2 = 16 where a Float16 row of d = 128 takes 256.  The store also owns copies
+ * of h's centroids and base codebooks and of the m2 refinement codebooks, so it outlives edits of h as the other stores do.
+ * Creation, all on the device, in blocks of rows under h's workspace limit:
+ *   1. list_v and the base code are what ivfadc_encode returns for the row (nearest centre; per sub-space the first minimum), as indices.
+ *   2. second residual, Float32, one rounding per operation:  y1[t] = c[list][t] + p[t];  e[t] = x[t] - y1[t].
+ *   3. refine_codebooks: m2 blocks of dsub2 x k2 (dsub2 = d / m2), the layout ivfadc_create takes, a HOST pointer in both entries, used
+ *      as they are.  NULL: one k-means per sub-space (the trainer of ivfadc_train) on the residuals of the first min(n, ntrain) rows
+ *      (ntrain <= 0: all rows), maxiter iterations at most, seeds seed + 1 + j; deterministic per seed.
+ *   4. code2_j = argmin over c of sum_t (R_j[c][t] - e[t])^2, the encoder's chain, first minimum on ties.
+ * Steps 2, 4 and the record are ONE kernel; a row's residual never leaves LDS.
+ * The re-rank entries below take such a store unchanged; the distance of a live slot with id v < n is, in Float32, nothing contracted,
+ *   s = 0;  t = 0 .. d-1:  y = (c[list_v][t] + p_v[t]) + r_v[t];  u = y - q[t];  s = s + u * u
+ * -- the chain of the other stores with the reconstruction in the stored vector's place.  Order, ties, dead slots, ids >= n: unchanged.
+ * Both entries block.  Refused before anything is allocated, each named in ivfadc_last_error() -- IVFADC_ERR_INVALID: null out, null
+ * handle, n < 0, n > 2^32, null data with n > 0, m2 < 1, k2 outside 1..256, maxiter < 1 with no codebooks, d above 16384, d % m2 != 0,
+ * m + m2 above 124, k2 above the rows trained on, data that is not finite; IVFADC_ERR_STATE: a UInt16 handle, a file-loaded :opq handle
+ * (its encode is the CPU's), a handle in the list-partitioned mode.
+ * ivfadc_vectors_get_pq reads a PQ store back (any pointer may be NULL): the refinement codebooks in the layout above, n lists, n x m base
+ * codeword indices, n x m2 refinement indices, m2, k2.  ivfadc_vectors_bytes reports, for any store, the bytes of a row and the device
+ * bytes of the whole store (a PQ store: with its copies of the centroids and codebooks).  ivfadc_vectors_pq_shape reports what sizes those
+ * arrays from the store alone: kc, m and ksub of the handle it was made with (out_codes holds n x m bytes), and the route below.
+ * ivfadc_vectors_set_pq_route chooses how the distance pass gets its codeword pieces; results are bit for bit the same.  0 (the default,
+ * the faster where measured): straight through the L2.  1: a chunk's slices of both codebooks staged in LDS per workgroup;
+ * IVFADC_ERR_INVALID where d / m or d / m2 is no multiple of four or the slices do not fit a workgroup's LDS.  Not to be called while a
+ * call that reads the store runs.
+ * Not covered: in-place updates of a store, building one from blocks of data, UInt16 and :opq handles.                                  */
+int ivfadc_vectors_create_pq(ivfadc_t *h, int64_t n, const float *data, int m2, int k2, const float *refine_codebooks, int maxiter, uint64_t seed,
+                             int64_t ntrain, ivfadc_vectors_t **out);
+int ivfadc_vectors_create_pq_device(ivfadc_t *h, int64_t n, const float *d_data, int m2, int k2, const float *refine_codebooks, int maxiter,
+                                    uint64_t seed, int64_t ntrain, ivfadc_vectors_t **out);
+int ivfadc_vectors_get_pq(const ivfadc_vectors_t *vs, float *out_refine_codebooks, int32_t *out_lists, uint8_t *out_codes, uint8_t *out_codes2,
+                          int32_t *out_m2, int32_t *out_k2);
+int ivfadc_vectors_bytes(const ivfadc_vectors_t *vs, int64_t *out_bytes_per_row, int64_t *out_total_bytes);
+int ivfadc_vectors_pq_shape(const ivfadc_vectors_t *vs, int32_t *out_kc, int32_t *out_m, int32_t *out_ksub, int32_t *out_route);
+int ivfadc_vectors_set_pq_route(ivfadc_vectors_t *vs, int route);
+
 /* EXACT RE-RANKING (IVFADC+R): candidate ids re-scored against the original vectors of a store, the K best kept (csrc/rerank_plan.h,
  * csrc/rerank.hip.h).  The ADC distance cannot tell neighbours apart more finely than the codebooks allow; ask the search for more
  * candidates than wanted, re-rank them, keep K.

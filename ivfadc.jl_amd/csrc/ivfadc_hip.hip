@@ -3639,7 +3639,15 @@ struct ivfadc_vectors {
     int d = 0;
     int64_t n = 0;
     int store_type = 0;
-    DevBuf data;     // n rows of d Float32 or Float16 components
+    DevBuf data;     // n rows of d Float32 or Float16 components; a PQ store (store_type 2): n records of pq.stride bytes
+    // a PQ store's own copies of what its records index (vstore_pq_plan.h): it outlives edits of the handle, as the other stores do
+    PqBooks pq{};
+    int pq_route = vspq::ROUTE_L2;   // how the distance pass gets its codeword pieces (ivfadc_vectors_set_pq_route)
+    DevBuf centroids, codebooks, refine;
+    void release_all()
+    {
+        for (DevBuf *b : {&data, &centroids, &codebooks, &refine}) b->release();
+    }
 };
 
 // rows of one conversion pass of a host-pointer Float16 store: the Float32 piece sits in pts_stage (at most 64 MB of it)
@@ -3726,13 +3734,240 @@ try {
     return vectors_create(h, n, d_data, store_type, out, true);
 } IVF_CATCH
 
+// ---- the PQ store (store_type 2; vstore_pq_plan.h, rerank.hip.h) ------------------------------------------------------
+// rows [r0, r0 + rows) of `data` through the coarse search, the argmin and vstore_pq_encode_kernel, in blocks under the workspace limit.
+// d_resid null: the records of those rows are written.  d_resid given: the trainer's pass -- the second residuals of the rows, no record.
+static int vectors_pq_rows(ivfadc_index *h, ivfadc_vectors *vs, const float *data, bool on_device, int64_t rows, float *d_resid)
+{
+    const int d = vs->d;
+    const int64_t block = vspq::block_rows(rows, d, h->kc, (uint64_t)h->ws_budget);
+    const size_t lds = vspq::encode_lds_bytes(d, vs->pq.m, vs->pq.m2);
+    TRY(fn_raise_lds(h->device, (const void *)vstore_pq_encode_kernel, lds, false));
+    for (int64_t r0 = 0; r0 < rows; r0 += block) {
+        const int64_t nb = std::min(block, rows - r0);
+        const float *d_pts = data + (size_t)r0 * d;
+        if (!on_device) {
+            TRY(h->pts_stage.ensure((size_t)nb * d * 4));
+            TRY(h2d_copy(h->pts_stage.p, d_pts, (size_t)nb * d * 4, h->stream));
+            d_pts = h->pts_stage.as<float>();
+        }
+        TRY(h->assign.ensure((size_t)nb * 4));
+        TRY(run_coarse(h, d_pts, nb, false));   // exact distances, as the encoder's
+        hipLaunchKernelGGL(argmin_rows_kernel, dim3((unsigned)((nb + 3) / 4)), dim3(256), 0, h->stream, h->cdist.as<float>(), (int)nb, h->kc,
+                           h->assign.as<int>());
+        HIP_TRY(hipGetLastError());
+        PqEncodeArgs a{};
+        a.b = vs->pq;
+        if (d_resid) a.b.refine = nullptr;
+        a.pts = d_pts;
+        a.assign = h->assign.as<int>();
+        a.out_resid = d_resid ? d_resid + (size_t)r0 * d : nullptr;
+        a.records = vs->data.as<uint8_t>() + vspq::record_offset((uint64_t)r0, vs->pq.stride);
+        hipLaunchKernelGGL(vstore_pq_encode_kernel, dim3((unsigned)nb), dim3(256), lds, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next block overwrites pts_stage, assign and the distances
+    }
+    return IVFADC_OK;
+}
+
+// the refinement codebooks: one k-means per sub-space on the second residuals of the first `rows` rows, seeds seed + 1 + j (train_impl's rule)
+static int vectors_pq_train(ivfadc_index *h, ivfadc_vectors *vs, const float *data, bool on_device, int64_t rows, int maxiter, uint64_t seed)
+{
+    TrainCtx t;
+    t.stream = h->stream;
+    DevBuf resid;
+    auto body = [&]() -> int {
+        TRY(resid.ensure((size_t)rows * vs->d * 4));
+        TRY(vectors_pq_rows(h, vs, data, on_device, rows, resid.as<float>()));
+        for (int j = 0; j < vs->pq.m2; ++j)
+            TRY(kmeans_dev(t, resid.as<float>() + (size_t)j * vs->pq.dsub2, rows, vs->pq.dsub2, vs->d, vs->pq.k2, maxiter, seed + 1 + (uint64_t)j,
+                           vs->refine.as<float>() + vspq::codeword_elem(j, 0u, 0, vs->pq.dsub2, vs->pq.k2)));
+        return IVFADC_OK;
+    };
+    const int rc = body();
+    (void)hipStreamSynchronize(h->stream);
+    DevBuf *bufs[] = {&resid, &t.cdist, &t.assign, &t.mind, &t.partial, &t.acc, &t.counts, &t.flag, &t.blockmax};
+    for (DevBuf *b : bufs) b->release();
+    return rc;
+}
+
+static int vectors_pq_fill(ivfadc_index *h, ivfadc_vectors *vs, const float *data, bool on_device, const float *refine, int maxiter, uint64_t seed,
+                           int64_t train_rows)
+{
+    const PqBooks &b = vs->pq;
+    const size_t cen = (size_t)b.kc * b.d * 4, cbs = (size_t)b.m * b.ksub * b.dsub * 4, ref = (size_t)b.m2 * b.k2 * b.dsub2 * 4;
+    TRY(vs->centroids.alloc_exact(cen));
+    TRY(vs->codebooks.alloc_exact(cbs));
+    TRY(vs->refine.alloc_exact(ref));
+    TRY(vs->data.alloc_exact(std::max<size_t>(16, (size_t)vspq::store_bytes((uint64_t)vs->n, b.stride))));
+    vs->pq.centroids = vs->centroids.as<float>();
+    vs->pq.codebooks = vs->codebooks.as<float>();
+    vs->pq.refine = vs->refine.as<float>();
+    HIP_TRY(hipMemcpyAsync(vs->centroids.p, h->centroids.p, cen, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipMemcpyAsync(vs->codebooks.p, h->codebooks.p, cbs, hipMemcpyDeviceToDevice, h->stream));
+    HIP_TRY(hipStreamSynchronize(h->stream));
+    if (refine) TRY(h2d_copy(vs->refine.p, refine, ref, h->stream));
+    else TRY(vectors_pq_train(h, vs, data, on_device, train_rows, maxiter, seed));
+    return vectors_pq_rows(h, vs, data, on_device, vs->n, nullptr);
+}
+
+static int vectors_create_pq(ivfadc_t *h, int64_t n, const float *data, int m2, int k2, const float *refine, int maxiter, uint64_t seed, int64_t ntrain,
+                             ivfadc_vectors_t **out, bool on_device)
+{
+    const char *fn = "ivfadc_vectors_create_pq";
+    if (!out) return fail(IVFADC_ERR_INVALID, "%s: null out", fn);
+    *out = nullptr;
+    if (!h) return fail(IVFADC_ERR_INVALID, "%s: null handle", fn);
+    if (n < 0) return fail(IVFADC_ERR_INVALID, "%s: n = %lld < 0", fn, (long long)n);
+    if (n > ((int64_t)1 << 32)) return fail(IVFADC_ERR_INVALID, "%s: n exceeds 2^32 (ids are UInt32)", fn);
+    if (n > 0 && !data) return fail(IVFADC_ERR_INVALID, "%s: null data with n > 0", fn);
+    if (m2 < 1) return fail(IVFADC_ERR_INVALID, "%s: m2 = %d < 1", fn, m2);
+    if (k2 < 1 || k2 > vspq::MAX_K2) return fail(IVFADC_ERR_INVALID, "%s: k2 = %d outside 1..%d (a refinement code is one byte)", fn, k2, vspq::MAX_K2);
+    if (!refine && maxiter < 1) return fail(IVFADC_ERR_INVALID, "%s: maxiter = %d < 1 with no refinement codebooks supplied", fn, maxiter);
+    HandleLock lk_(h);
+    if (h->u16) return fail(IVFADC_ERR_STATE, "%s: this index has UInt16 codes; a PQ store keeps one byte per base code", fn);
+    if (!h->rot.empty()) return fail(IVFADC_ERR_STATE, "%s: the residual quantizer carries a rotation (:opq); this index is served for search only", fn);
+    if (h->part_n > 1) return fail(IVFADC_ERR_STATE, "%s: the handle is in the list-partitioned mode (ivfadc_set_list_partition)", fn);
+    if (h->d > rerank::MAX_D) return fail(IVFADC_ERR_INVALID, "%s: d = %d (a store takes vectors of at most %d components)", fn, h->d, rerank::MAX_D);
+    if (h->d % m2 != 0) return fail(IVFADC_ERR_INVALID, "%s: d %% m2 != 0 (d = %d, m2 = %d)", fn, h->d, m2);
+    if (!vspq::record_fits(h->m, m2))
+        return fail(IVFADC_ERR_INVALID, "%s: m + m2 = %d + %d code bytes (a record holds at most %d)", fn, h->m, m2, (int)vspq::MAX_RECORD - vspq::LIST_BYTES);
+    const int64_t trows = vspq::train_rows(n, ntrain);
+    if (!refine && (int64_t)k2 > trows)
+        return fail(IVFADC_ERR_INVALID, "%s: k2 = %d above the %lld rows trained on", fn, k2, (long long)trows);
+    if (!on_device)
+        for (int64_t e = 0; e < n * h->d; ++e)
+            if (!std::isfinite(data[e]))
+                return fail(IVFADC_ERR_INVALID, "%s: data is not finite: row %lld, component %d", fn, (long long)(e / h->d), (int)(e % h->d));
+    TRY(set_device(h));
+    HIP_TRY(hipStreamSynchronize(h->stream));   // rr_off, pts_stage, assign and the distances are the handle's: nothing enqueued earlier still reads them
+    if (on_device && n > 0) {
+        const u32 zero = 0;
+        u32 flag = 0;
+        const uint64_t total = (uint64_t)n * (uint64_t)h->d;
+        TRY(h->rr_off.ensure(16));
+        TRY(h2d_copy(h->rr_off.p, &zero, 4, h->stream));
+        hipLaunchKernelGGL(vstore_pq_finite_kernel, dim3((unsigned)std::min<uint64_t>(4096, (total + 255) / 256)), dim3(256), 0, h->stream, data, total,
+                           h->rr_off.as<u32>());
+        HIP_TRY(hipGetLastError());
+        TRY(d2h_copy(&flag, h->rr_off.p, 4, h->stream));
+        if (flag) return fail(IVFADC_ERR_INVALID, "%s: data is not finite", fn);
+    }
+    std::unique_ptr<ivfadc_vectors> vs(new ivfadc_vectors());
+    vs->device = h->device;
+    vs->d = h->d;
+    vs->n = n;
+    vs->store_type = vspq::STORE_PQ;
+    PqBooks &b = vs->pq;
+    b.kc = h->kc; b.d = h->d; b.m = h->m; b.ksub = h->ksub; b.dsub = h->dsub;
+    b.m2 = m2; b.k2 = k2; b.dsub2 = h->d / m2;
+    b.stride = vspq::stride(h->m, m2);
+    const int rc = vectors_pq_fill(h, vs.get(), data, on_device, refine, maxiter, seed, trows);
+    if (rc != IVFADC_OK) {
+        (void)recon_exit(h, rc);   // drains the stream and keeps the message: nothing still writes the store
+        vs->release_all();
+        return rc;
+    }
+    *out = vs.release();
+    return IVFADC_OK;
+}
+
+int ivfadc_vectors_create_pq(ivfadc_t *h, int64_t n, const float *data, int m2, int k2, const float *refine_codebooks, int maxiter, uint64_t seed,
+                             int64_t ntrain, ivfadc_vectors_t **out)
+try {
+    return vectors_create_pq(h, n, data, m2, k2, refine_codebooks, maxiter, seed, ntrain, out, false);
+} IVF_CATCH
+
+int ivfadc_vectors_create_pq_device(ivfadc_t *h, int64_t n, const float *d_data, int m2, int k2, const float *refine_codebooks, int maxiter,
+                                    uint64_t seed, int64_t ntrain, ivfadc_vectors_t **out)
+try {
+    return vectors_create_pq(h, n, d_data, m2, k2, refine_codebooks, maxiter, seed, ntrain, out, true);
+} IVF_CATCH
+
+// the thread's current device is the caller's: set to the store's for the lifetime of the scope, then put back
+struct VectorsDeviceScope {
+    int prev = -1;
+    bool ok = false;
+    explicit VectorsDeviceScope(int device)
+    {
+        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
+        ok = hipSetDevice(device) == hipSuccess;
+        if (!ok || prev == device) prev = -1;
+    }
+    ~VectorsDeviceScope() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+
+int ivfadc_vectors_get_pq(const ivfadc_vectors_t *vs, float *out_refine_codebooks, int32_t *out_lists, uint8_t *out_codes, uint8_t *out_codes2,
+                          int32_t *out_m2, int32_t *out_k2)
+try {
+    if (!vs) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_get_pq: null store");
+    if (vs->store_type != vspq::STORE_PQ) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_get_pq: store_type = %d is not a PQ store (2)", vs->store_type);
+    const PqBooks &b = vs->pq;
+    if (out_m2) *out_m2 = b.m2;
+    if (out_k2) *out_k2 = b.k2;
+    if (!out_refine_codebooks && !out_lists && !out_codes && !out_codes2) return IVFADC_OK;
+    VectorsDeviceScope dev(vs->device);
+    if (!dev.ok) return fail(IVFADC_ERR_HIP, "ivfadc_vectors_get_pq: no such HIP device %d", vs->device);
+    if (out_refine_codebooks) TRY(d2h_copy(out_refine_codebooks, vs->refine.p, (size_t)b.m2 * b.k2 * b.dsub2 * 4, nullptr));
+    if (!out_lists && !out_codes && !out_codes2) return IVFADC_OK;
+    const int64_t piece = std::max<int64_t>(1, ((int64_t)64 << 20) / b.stride);   // records of one copy: at most 64 MB
+    std::vector<uint8_t> rec;
+    for (int64_t r0 = 0; r0 < vs->n; r0 += piece) {
+        const int64_t rows = std::min(piece, vs->n - r0);
+        rec.resize((size_t)rows * b.stride);
+        TRY(d2h_copy(rec.data(), vs->data.as<uint8_t>() + vspq::record_offset((uint64_t)r0, b.stride), rec.size(), nullptr));
+        for (int64_t r = 0; r < rows; ++r) {
+            const uint8_t *p = rec.data() + (size_t)r * b.stride;
+            if (out_lists) memcpy(out_lists + r0 + r, p + vspq::off_list(), 4);
+            if (out_codes) memcpy(out_codes + (size_t)(r0 + r) * b.m, p + vspq::off_code(0), (size_t)b.m);
+            if (out_codes2) memcpy(out_codes2 + (size_t)(r0 + r) * b.m2, p + vspq::off_code2(b.m, 0), (size_t)b.m2);
+        }
+    }
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_vectors_bytes(const ivfadc_vectors_t *vs, int64_t *out_bytes_per_row, int64_t *out_total_bytes)
+try {
+    if (!vs) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_bytes: null store");
+    const bool pq = vs->store_type == vspq::STORE_PQ;
+    const int64_t row = pq ? (int64_t)vs->pq.stride : (int64_t)rerank::row_bytes(vs->d, vs->store_type == rerank::STORE_F16);
+    if (out_bytes_per_row) *out_bytes_per_row = row;
+    if (out_total_bytes) *out_total_bytes = vs->n * row + (pq ? (int64_t)(vs->centroids.bytes + vs->codebooks.bytes + vs->refine.bytes) : 0);
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_vectors_pq_shape(const ivfadc_vectors_t *vs, int32_t *out_kc, int32_t *out_m, int32_t *out_ksub, int32_t *out_route)
+try {
+    if (!vs) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_pq_shape: null store");
+    if (vs->store_type != vspq::STORE_PQ) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_pq_shape: store_type = %d is not a PQ store (2)", vs->store_type);
+    if (out_kc) *out_kc = vs->pq.kc;
+    if (out_m) *out_m = vs->pq.m;
+    if (out_ksub) *out_ksub = vs->pq.ksub;
+    if (out_route) *out_route = vs->pq_route;
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_vectors_set_pq_route(ivfadc_vectors_t *vs, int route)
+try {
+    const char *fn = "ivfadc_vectors_set_pq_route";
+    if (!vs) return fail(IVFADC_ERR_INVALID, "%s: null store", fn);
+    if (vs->store_type != vspq::STORE_PQ) return fail(IVFADC_ERR_INVALID, "%s: store_type = %d is not a PQ store (2)", fn, vs->store_type);
+    if (route != vspq::ROUTE_L2 && route != vspq::ROUTE_STAGED) return fail(IVFADC_ERR_INVALID, "%s: route = %d (0: through the L2, 1: staged in LDS)", fn, route);
+    const PqBooks &b = vs->pq;
+    if (route == vspq::ROUTE_STAGED && !vspq::staged_fits(b.d, b.m, b.m2, b.ksub, b.k2))
+        return fail(IVFADC_ERR_INVALID, "%s: the staged route does not serve this store (d / m = %d and d / m2 = %d multiples of four, %zu bytes of LDS of at most %zu)",
+                    fn, b.dsub, b.dsub2, vspq::staged_lds_bytes(b.d, b.stride, b.ksub, b.k2), vspq::STAGED_LDS_MAX);
+    vs->pq_route = route;
+    return IVFADC_OK;
+} IVF_CATCH
+
 void ivfadc_vectors_destroy(ivfadc_vectors_t *vs)
 {
     if (!vs) return;
-    int prev = -1;   // the calling thread's current device is the caller's: left as it was
-    if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-    if (hipSetDevice(vs->device) == hipSuccess) vs->data.release();
-    if (prev >= 0 && prev != vs->device) (void)hipSetDevice(prev);
+    {
+        VectorsDeviceScope dev(vs->device);
+        if (dev.ok) vs->release_all();
+    }
     delete vs;
 }
 
@@ -3777,11 +4012,16 @@ static int check_rerank_link(const char *fn, const ivfadc_index *h, const ivfadc
 static int rerank_enqueue(ivfadc_index *h, const ivfadc_vectors *vs, int64_t nq, const float *d_q, int64_t C, const uint32_t *d_ids,
                           const int32_t *d_counts, int K, uint32_t *d_out_ids, float *d_out_dists, int32_t *d_out_counts)
 {
-    const bool f16 = vs->store_type == rerank::STORE_F16;
-    const rerank::Plan pl = rerank::make_plan(nq, C, h->d, f16, (uint64_t)h->ws_budget);
+    const bool f16 = vs->store_type == rerank::STORE_F16, pq = vs->store_type == vspq::STORE_PQ;
+    rerank::Plan pl = rerank::make_plan(nq, C, h->d, f16, (uint64_t)h->ws_budget);
     void (*dist)(const RerankArgs) = f16 ? (pl.vec ? rerank_dist_kernel<true, true> : rerank_dist_kernel<true, false>)
                                          : (pl.vec ? rerank_dist_kernel<false, true> : rerank_dist_kernel<false, false>);
-    TRY(fn_raise_lds(h->device, (const void *)dist, pl.dist_lds, false));
+    // a PQ store: the same plan (slices, grid, chunks of 32 Float32 components, select pass), its own distance kernel and the records' LDS
+    const bool staged = pq && vs->pq_route == vspq::ROUTE_STAGED;   // the setter admits it only where vspq::staged_fits
+    void (*dist_pq)(const RerankPqArgs) = staged ? rerank_pq_dist_kernel<true, true>
+                                          : pq && vspq::vec4(h->d, vs->pq.m, vs->pq.m2) ? rerank_pq_dist_kernel<true, false> : rerank_pq_dist_kernel<false, false>;
+    if (pq) pl.dist_lds = staged ? vspq::staged_lds_bytes(h->d, vs->pq.stride, vs->pq.ksub, vs->pq.k2) : vspq::dist_lds_bytes(h->d, vs->pq.stride);
+    TRY(fn_raise_lds(h->device, pq ? (const void *)dist_pq : (const void *)dist, pl.dist_lds, false));
     TRY(h->rr_keys.ensure((size_t)pl.slice_keys * 8));
     if (pl.form == rerank::SELECT_SORT) {
         TRY(h->rr_sorted.ensure((size_t)pl.slice_keys * 8));
@@ -3799,7 +4039,8 @@ static int rerank_enqueue(ivfadc_index *h, const ivfadc_vectors *vs, int64_t nq,
     for (int64_t s = 0; s < pl.nslices; ++s) {
         const int64_t q0 = rerank::slice_begin(pl, s), nqs = rerank::slice_queries(pl, s);
         a.q0 = q0;
-        hipLaunchKernelGGL(dist, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, a);
+        if (pq) hipLaunchKernelGGL(dist_pq, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, RerankPqArgs{a, vs->pq});
+        else hipLaunchKernelGGL(dist, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, a);
         HIP_TRY(hipGetLastError());
         if (pl.form == rerank::SELECT_LDS) {
             hipLaunchKernelGGL(rerank_select_kernel<false>, dim3((unsigned)nqs), dim3(256), pl.select_lds, h->stream, h->rr_keys.as<u64>(), C, pl.padded,

@@ -28,6 +28,19 @@
 //                        segmented radix sort of the generic search path.  Then the first min(K, live) keys are emitted with the id of
 //                        their slot and their distance bits.
 //   vectors_to_f16_kernel   the Float16 store: round-to-nearest-even, one flag raised (plain atomic OR) when a FINITE component overflows.
+//   rerank_pq_dist_kernel<VEC, STAGED>   the distance pass against a PQ store (store_type 2; vstore_pq_plan.h): the same decomposition, but a row
+//                        is not fetched, it is RECONSTRUCTED.  The wave first brings its 64 records (8 .. 128 bytes each) into LDS, in
+//                        16-byte pieces, consecutive lanes on consecutive pieces.  Per chunk, the eight lanes of a row then each build
+//                        four components: a 16-byte piece of the centroid row, one of the base codeword of sub-space t / dsub, one of
+//                        the refinement codeword of sub-space t / dsub2 (all three read-only, a few hundred KB, served by the L2), two
+//                        additions, y = (c + p) + r, and the write into the tile.  Chunk c + 1 is reconstructed into the staging
+//                        registers before chunk c is consumed, as the fetch of the other stores is.  VEC false (dsub or dsub2 no
+//                        multiple of four): the four components are addressed one by one.  The chain itself is rerank_consume's.
+//                        STAGED (the other codebook route, on request: ivfadc_vectors_set_pq_route): per chunk the workgroup first copies
+//                        the chunk's slices of both codebooks into LDS (2 x 32 KB at k = 256) and the codeword pieces come from there.
+//   vstore_pq_encode_kernel        creation of a PQ store, one workgroup per row, the row's residual in LDS throughout: the base code
+//                        (encode_kernel's chain and tie rule on x - c), the second residual e = x - (c + p), optionally written out for
+//                        the trainer, the refinement code (the same chain on e), and the record.  Nothing but the record goes to memory.
 // Plain C++ and vector loads and stores only.
 #pragma once
 
@@ -35,6 +48,7 @@
 
 #include "kernels.hip.h"
 #include "rerank_plan.h"
+#include "vstore_pq_plan.h"
 
 namespace ivf {
 
@@ -274,6 +288,242 @@ __global__ __launch_bounds__(256) void vectors_to_f16_kernel(const float *__rest
         dst[e] = h;
     }
     if (over) atomicOr(flag, 1u);
+}
+
+// ---- the PQ store (vstore_pq_plan.h) ------------------------------------------------------------------------------------------------------
+struct PqBooks {
+    const float *centroids;   // [kc][d]
+    const float *codebooks;   // [m][ksub][dsub]
+    const float *refine;      // [m2][k2][dsub2]
+    int kc, d, m, ksub, dsub, m2, k2, dsub2;
+    u32 stride;               // bytes of a record
+};
+
+struct RerankPqArgs {
+    RerankArgs r;             // rows: the records
+    PqBooks b;
+};
+
+// the four components from t0 on of the row whose record lies at `rec` (LDS), reconstructed: (centre + base codeword) + refinement codeword.
+// j1 / a1, j2 / a2: sub-space and place in it of component t0 under the base and the refinement quantizer.  STAGED: the two codeword
+// pieces are piece g of the chunk's slices in LDS (vstore_pq_plan.h), not reads of the codebooks.
+template <bool VEC, bool STAGED>
+__device__ __forceinline__ uint4 rerank_pq_piece(const PqBooks &b, bool ok, const uint8_t *rec, int t0, int j1, int a1, int j2, int a2,
+                                                 const float *slices, int g)
+{
+    float y[4] = {0.0f, 0.0f, 0.0f, 0.0f};
+    if (ok && t0 < b.d) {
+        // (every record was written by vstore_pq_encode_kernel and names a list and two codewords; the bounds keep a damaged one inside the arrays)
+        const u32 list = min(*(const u32 *)(rec + vspq::off_list()), (u32)b.kc - 1u);
+        if constexpr (VEC) {
+            const u32 c1 = min((u32)rec[vspq::off_code(j1)], (u32)b.ksub - 1u), c2 = min((u32)rec[vspq::off_code2(b.m, j2)], (u32)b.k2 - 1u);
+            const float4 c = *(const float4 *)(b.centroids + vspq::centroid_elem(list, b.d, t0));
+            float4 p, r;
+            if constexpr (STAGED) {
+                p = *(const float4 *)(slices + vspq::slice_piece(c1, g));
+                r = *(const float4 *)(slices + vspq::slice_dwords(b.ksub) + vspq::slice_piece(c2, g));
+            } else {
+                p = *(const float4 *)(b.codebooks + vspq::codeword_elem(j1, c1, a1, b.dsub, b.ksub));
+                r = *(const float4 *)(b.refine + vspq::codeword_elem(j2, c2, a2, b.dsub2, b.k2));
+            }
+            y[0] = (c.x + p.x) + r.x; y[1] = (c.y + p.y) + r.y; y[2] = (c.z + p.z) + r.z; y[3] = (c.w + p.w) + r.w;
+        } else {
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                const int t = t0 + k;
+                if (t >= b.d) break;
+                const int s1 = vspq::sub_of(t, b.dsub), s2 = vspq::sub_of(t, b.dsub2);
+                const u32 c1 = min((u32)rec[vspq::off_code(s1)], (u32)b.ksub - 1u), c2 = min((u32)rec[vspq::off_code2(b.m, s2)], (u32)b.k2 - 1u);
+                y[k] = (b.centroids[vspq::centroid_elem(list, b.d, t)] + b.codebooks[vspq::codeword_elem(s1, c1, vspq::sub_at(t, b.dsub), b.dsub, b.ksub)])
+                       + b.refine[vspq::codeword_elem(s2, c2, vspq::sub_at(t, b.dsub2), b.dsub2, b.k2)];
+            }
+        }
+    }
+    return make_uint4(__float_as_uint(y[0]), __float_as_uint(y[1]), __float_as_uint(y[2]), __float_as_uint(y[3]));
+}
+
+// the reconstruction of chunk c of the rows this lane serves (fok: the row's slot is live with an id below n)
+template <bool VEC, bool STAGED>
+__device__ __forceinline__ void rerank_pq_stage(const PqBooks &b, const bool *fok, const uint8_t *recs, const float *slices, int c, int lane, uint4 *st)
+{
+    const int t0 = vspq::chunk_comp(c, rerank::gather_dword(lane, 0));   // the same four components of every row this lane serves
+    const int j1 = vspq::sub_of(t0, b.dsub), a1 = vspq::sub_at(t0, b.dsub), j2 = vspq::sub_of(t0, b.dsub2), a2 = vspq::sub_at(t0, b.dsub2);
+#pragma unroll
+    for (int i = 0; i < rerank::LOADS; ++i)
+        st[i] = rerank_pq_piece<VEC, STAGED>(b, fok[i], recs + (size_t)rerank::gather_row(lane, i) * b.stride, t0, j1, a1, j2, a2, slices,
+                                             rerank::gather_dword(lane, 0) / 4);
+}
+
+// the staged route: chunk c's slices of both codebooks into LDS, the workgroup's 256 lanes on consecutive pieces (a piece whose four
+// components lie at or beyond d is not read and never used)
+__device__ __forceinline__ void rerank_pq_fill_slices(const PqBooks &b, float *slices, int c, int tid)
+{
+    const u32 n1 = vspq::slice_pieces(b.ksub), n2 = vspq::slice_pieces(b.k2);
+#pragma unroll 4
+    for (u32 e = (u32)tid; e < n1 + n2; e += (u32)rerank::TILE) {
+        const bool base = e < n1;
+        const u32 f = base ? e : e - n1, code = vspq::slice_code(f);
+        const int g = vspq::slice_g(f), t0 = vspq::chunk_comp(c, 4 * g), ds = base ? b.dsub : b.dsub2;
+        if (t0 >= b.d) continue;
+        const float *src = (base ? b.codebooks : b.refine) + vspq::codeword_elem(vspq::sub_of(t0, ds), code, vspq::sub_at(t0, ds), ds, base ? b.ksub : b.k2);
+        *(float4 *)(slices + (base ? 0u : vspq::slice_dwords(b.ksub)) + vspq::slice_piece(code, g)) = *(const float4 *)src;
+    }
+}
+
+// STAGED (with VEC only): every wave of a workgroup that holds a slot below the live count walks the chunks, because every chunk begins
+// with the workgroup's copy of its slices between two barriers; the chunk is then reconstructed and consumed at once (the slices of chunk
+// c + 1 are not there yet, so nothing is built ahead).
+template <bool VEC, bool STAGED>
+__global__ __launch_bounds__(rerank::TILE) void rerank_pq_dist_kernel(const RerankPqArgs pa)
+{
+    static_assert(VEC || !STAGED, "the staged route serves the 16-byte form only");
+    extern __shared__ __align__(16) u32 rr_lds[];
+    const RerankArgs &a = pa.r;
+    const PqBooks &b = pa.b;
+    float *qs = (float *)rr_lds;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t qy = blockIdx.y, q = a.q0 + qy;
+    const float *__restrict__ qrow = a.queries + rerank::query_row(q, a.d);
+    for (int t = tid; t < a.d; t += rerank::TILE) qs[t] = qrow[t];
+    __syncthreads();
+    const int64_t j = rerank::tile_slot(blockIdx.x, tid);
+    const int64_t live = rerank::live_slots(a.counts != nullptr, a.counts ? a.counts[q] : 0, a.C);
+    u32 v = 0u;
+    bool ok = false;
+    if (j < live) {
+        v = a.ids[rerank::id_index(q, a.C, j)];
+        ok = (uint64_t)v < a.n;
+    }
+    const u64 mask = __ballot(ok);   // wave-uniform from here on
+    const bool active = mask != 0ull;
+    float s = 0.0f;
+    if (STAGED ? rerank::tile_slot(blockIdx.x, 0) < live : active) {   // STAGED: uniform over the workgroup
+        u32 *tile = rr_lds + rerank::tile_base(a.d, wv);
+        uint8_t *recs = (uint8_t *)(rr_lds + vspq::record_base(a.d, wv, b.stride));
+        float *slices = (float *)(rr_lds + vspq::slice_base(a.d, b.stride));
+        // the wave's 64 records into LDS: piece i is bytes piece_byte(i) .. of row piece_row(i) (pieces: a multiple of 64, every lane takes every turn)
+        const u32 np = vspq::pieces(b.stride);
+        for (u32 i = (u32)lane; i < np; i += 64u) {
+            const int r = vspq::piece_row(i, b.stride);
+            const u32 at = vspq::piece_byte(i, b.stride);
+            const u32 id = (u32)__shfl((int)v, r);
+            if ((mask >> r) & 1ull) {
+                const uint8_t *src = a.rows + vspq::record_offset(id, b.stride) + at;
+                uint8_t *dst = recs + (size_t)r * b.stride + at;
+                if (vspq::piece_bytes(b.stride) == 16u) *(uint4 *)dst = *(const uint4 *)src;
+                else *(u32 *)dst = *(const u32 *)src;
+            }
+        }
+        wave_sync();
+        bool fok[rerank::LOADS];
+#pragma unroll
+        for (int i = 0; i < rerank::LOADS; ++i) fok[i] = (mask >> rerank::gather_row(lane, i)) & 1ull;
+        const int nch = rerank::chunks(a.d, false);
+        uint4 st[rerank::LOADS];
+        if constexpr (!STAGED) rerank_pq_stage<VEC, false>(b, fok, recs, slices, 0, lane, st);
+        for (int c = 0; c < nch; ++c) {
+            if constexpr (STAGED) {
+                __syncthreads();   // every wave has taken its pieces of chunk c - 1's slices
+                rerank_pq_fill_slices(b, slices, c, tid);
+                __syncthreads();
+                if (!active) continue;
+                rerank_pq_stage<VEC, true>(b, fok, recs, slices, c, lane, st);
+            }
+            // the staged chunk c into the tile (the reads of chunk c - 1 are behind the wave_sync that ended its turn)
+#pragma unroll
+            for (int i = 0; i < rerank::LOADS; ++i) {
+                u32 *dst = tile + rerank::tile_index(rerank::gather_row(lane, i), rerank::gather_dword(lane, 0));
+                dst[0] = st[i].x; dst[1] = st[i].y; dst[2] = st[i].z; dst[3] = st[i].w;
+            }
+            wave_sync();
+            if constexpr (!STAGED)
+                if (c + 1 < nch) rerank_pq_stage<VEC, false>(b, fok, recs, slices, c + 1, lane, st);
+            s = rerank_consume<false>(s, tile + rerank::tile_index(lane, 0), qs + (size_t)c * rerank::CHUNK_DWORDS, rerank::chunk_len(a.d, false, c));
+            wave_sync();
+        }
+    }
+    if (j < a.C) a.keys[rerank::key_index(qy, a.C, j)] = ok ? (((u64)__float_as_uint(s) << 32) | (u32)j) : (u64)KEY_MAX;
+}
+
+struct PqEncodeArgs {
+    PqBooks b;                // refine null: the residual pass of the trainer (no refinement code, no record)
+    const float *pts;         // rows of this block, [rows][d]
+    const int *assign;        // their nearest centre
+    float *out_resid;         // null, or [rows][d]: the second residuals
+    uint8_t *records;         // the record of the block's first row
+};
+
+// best[j] <- min over c < k of (chain bits << 32 | c): encode_kernel's chain, first minimum on ties.  best[] holds KEY_MAX; k <= 256.
+__device__ __forceinline__ void vstore_pq_argmin(const float *__restrict__ books, const float *rr, int nsub, int k, int dsub, u64 *best, int tid)
+{
+    for (int e = tid; e < nsub * 256; e += 256) {
+        const int ii = e >> 8, c = e & 255;
+        u64 key = KEY_MAX;
+        if (c < k) {
+            const float *cw = books + vspq::codeword_elem(ii, (u32)c, 0, dsub, k);
+            const float *x = rr + (size_t)ii * dsub;
+            float sum = 0.0f;
+            for (int t = 0; t < dsub; ++t) {
+                const float df = cw[t] - x[t];
+                sum = sum + df * df;
+            }
+            key = make_key(sum, (u32)c);
+        }
+        // wave min, then one LDS atomic per wave (ii is wave-uniform: 256 % 64 == 0)
+#pragma unroll
+        for (int off = 32; off > 0; off >>= 1) {
+            const u64 o = __shfl_xor(key, off);
+            key = o < key ? o : key;
+        }
+        if ((tid & 63) == 0) atomicMin(&best[ii], key);
+    }
+}
+
+__global__ __launch_bounds__(256) void vstore_pq_encode_kernel(const PqEncodeArgs a)
+{
+    extern __shared__ __attribute__((aligned(16))) unsigned char smem_raw[];
+    const PqBooks &b = a.b;
+    float *resid = (float *)smem_raw;                                  // [d]: x - c, then e = x - (c + p)
+    u64 *best1 = (u64 *)(resid + rerank::query_dwords(b.d));           // [m]
+    u64 *best2 = best1 + b.m;                                          // [m2]
+    const int64_t p = blockIdx.x;
+    const int tid = threadIdx.x;
+    const int l = a.assign[p];
+    const float *__restrict__ x = a.pts + (size_t)p * b.d;
+    const float *__restrict__ centre = b.centroids + vspq::centroid_elem((u32)l, b.d, 0);
+    for (int i = tid; i < b.d; i += 256) resid[i] = x[i] - centre[i];
+    for (int i = tid; i < b.m + b.m2; i += 256) best1[i] = KEY_MAX;
+    __syncthreads();
+    vstore_pq_argmin(b.codebooks, resid, b.m, b.ksub, b.dsub, best1, tid);
+    __syncthreads();
+    for (int t = tid; t < b.d; t += 256) {
+        const int j = vspq::sub_of(t, b.dsub);
+        const float y1 = centre[t] + b.codebooks[vspq::codeword_elem(j, (u32)best1[j], vspq::sub_at(t, b.dsub), b.dsub, b.ksub)];
+        const float e = x[t] - y1;
+        resid[t] = e;
+        if (a.out_resid) a.out_resid[(size_t)p * b.d + t] = e;
+    }
+    if (!b.refine) return;
+    __syncthreads();
+    vstore_pq_argmin(b.refine, resid, b.m2, b.k2, b.dsub2, best2, tid);
+    __syncthreads();
+    uint8_t *rec = a.records + vspq::record_offset((uint64_t)p, b.stride);
+    for (u32 i = (u32)tid; i < b.stride; i += 256u) {
+        uint8_t byte = 0u;
+        if (i < (u32)vspq::LIST_BYTES) byte = (uint8_t)((u32)l >> (8u * i));
+        else if (i < vspq::off_code2(b.m, 0)) byte = (uint8_t)(u32)best1[i - vspq::off_code(0)];
+        else if (i < vspq::raw_bytes(b.m, b.m2)) byte = (uint8_t)(u32)best2[i - vspq::off_code2(b.m, 0)];
+        rec[i] = byte;
+    }
+}
+
+// *flag |= 1 when a component of src is not finite (the refusal of ivfadc_vectors_create_pq_device)
+__global__ __launch_bounds__(256) void vstore_pq_finite_kernel(const float *__restrict__ src, uint64_t total, u32 *__restrict__ flag)
+{
+    bool bad = false;
+    for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256)
+        bad |= (__float_as_uint(src[e]) & 0x7F800000u) == 0x7F800000u;
+    if (bad) atomicOr(flag, 1u);
 }
 
 }  // namespace ivf

@@ -722,6 +722,33 @@ class IVFADCIndex:
         nat.check(entry(self._h, int(n), data, 1 if dtype == np.dtype(np.float16) else 0, C.byref(s)))
         return VectorStore(s)
 
+    def vectors_pq(self, data, m2, k2=256, codebooks=None, maxiter=25, seed=0, ntrain=None):
+        """A compressed VectorStore of `data` (n, d) (ivfadc_vectors_create_pq; dtype "pq"): per row its list, its base codeword
+        indices and m2 refinement codeword indices of the residual the base code leaves, 4 + m + m2 bytes padded to a power of two.
+        rerank and knn_search_refined score against the reconstruction centre + codeword + refinement codeword.  codebooks
+        (m2, k2, d // m2) are used as they are; None trains them on the residuals of the first `ntrain` rows (None: all),
+        deterministically per seed.  UInt16 indexes, :opq files and list-partitioned handles are refused."""
+        data = np.ascontiguousarray(data, np.float32)
+        assert data.ndim == 2 and data.shape[1] == self.d, "data must be (n, %d)" % self.d
+        if codebooks is not None:
+            codebooks = np.ascontiguousarray(codebooks, np.float32)
+            assert m2 >= 1 and self.d % m2 == 0 and codebooks.shape == (m2, k2, self.d // m2), "codebooks must be (m2, k2, d // m2)"
+        s = C.c_void_p()
+        nat.check(nat.lib().ivfadc_vectors_create_pq(self._h, data.shape[0], nat.ptr(data, C.c_float) if data.shape[0] else None, int(m2), int(k2),
+                                                     nat.ptr(codebooks, C.c_float), int(maxiter), int(seed), int(ntrain or 0), C.byref(s)))
+        return VectorStore(s)
+
+    def vectors_pq_device(self, d_data_ptr, n, m2, k2=256, codebooks=None, maxiter=25, seed=0, ntrain=None):
+        """vectors_pq() from n x d float32 rows that already lie in device memory of this index's GPU (ivfadc_vectors_create_pq_device);
+        codebooks, if given, is a host array as for vectors_pq."""
+        if codebooks is not None:
+            codebooks = np.ascontiguousarray(codebooks, np.float32)
+            assert m2 >= 1 and self.d % m2 == 0 and codebooks.shape == (m2, k2, self.d // m2), "codebooks must be (m2, k2, d // m2)"
+        s = C.c_void_p()
+        nat.check(nat.lib().ivfadc_vectors_create_pq_device(self._h, int(n), C.c_void_p(int(d_data_ptr)) if n else None, int(m2), int(k2),
+                                                            nat.ptr(codebooks, C.c_float), int(maxiter), int(seed), int(ntrain or 0), C.byref(s)))
+        return VectorStore(s)
+
     def rerank_raw(self, store, queries, ids, k, counts=None):
         """queries (nq, d), ids (nq, C) and optional counts (nq,) of live slots per query -> ids (nq, k) uint32, dists (nq, k) float32,
         counts (nq,) int32 via ivfadc_rerank: per query the k live slots closest to it by the exact Float32 distance to the store's
@@ -853,18 +880,46 @@ class MaskSet:
 
 
 class VectorStore:
-    """The original vectors on the device, Float32 or Float16 (ivfadc_vectors_t; IVFADCIndex.vectors): what rerank and
-    knn_search_refined score candidates against.  Immutable; len() is the number of rows, `d` and `dtype` their shape and type.  It
+    """The original vectors on the device, Float32 or Float16 (ivfadc_vectors_t; IVFADCIndex.vectors), or their two-stage PQ
+    reconstructions (IVFADCIndex.vectors_pq: dtype "pq", with m2, k2 and pq_arrays()): what rerank and knn_search_refined score
+    candidates against.  Immutable; len() is the number of rows, `d` and `dtype` their shape and type, bytes_per_row and nbytes
+    what it takes on the device.  It
     keeps nothing of the index it was made with; the native object goes with this one."""
 
     def __init__(self, s):
         self._s = s
         n, d, t = C.c_int64(), C.c_int32(), C.c_int32()
         nat.check(nat.lib().ivfadc_vectors_sizes(s, C.byref(n), C.byref(d), C.byref(t)))
-        self._n, self.d, self.dtype = int(n.value), int(d.value), np.dtype(np.float16 if t.value == 1 else np.float32)
+        self._n, self.d = int(n.value), int(d.value)
+        self.dtype = "pq" if t.value == 2 else np.dtype(np.float16 if t.value == 1 else np.float32)
+        row, total = C.c_int64(), C.c_int64()
+        nat.check(nat.lib().ivfadc_vectors_bytes(s, C.byref(row), C.byref(total)))
+        self.bytes_per_row, self.nbytes = int(row.value), int(total.value)
+        if t.value == 2:                                        # a PQ store (IVFADCIndex.vectors_pq)
+            m2, k2 = C.c_int32(), C.c_int32()
+            nat.check(nat.lib().ivfadc_vectors_get_pq(s, None, None, None, None, C.byref(m2), C.byref(k2)))
+            self.m2, self.k2 = int(m2.value), int(k2.value)
+            m = C.c_int32()
+            nat.check(nat.lib().ivfadc_vectors_pq_shape(s, None, C.byref(m), None, None))
+            self._m = int(m.value)
 
     def __len__(self):
         return self._n
+
+    def set_pq_route(self, route):
+        """How re-ranking against this PQ store gets its codeword pieces (ivfadc_vectors_set_pq_route): 0 straight through the L2 (the
+        default), 1 a chunk's codebook slices staged in LDS per workgroup.  The results are the same bit for bit."""
+        nat.check(nat.lib().ivfadc_vectors_set_pq_route(self._s, int(route)))
+
+    def pq_arrays(self):
+        """The read-back of a PQ store (ivfadc_vectors_get_pq): refinement codebooks
+        (m2, k2, d // m2) float32, lists (n,) int32, base codeword indices (n, m) uint8, refinement indices (n, m2) uint8."""
+        assert self.dtype == "pq", "pq_arrays reads a PQ store"
+        books = np.zeros((self.m2, self.k2, self.d // self.m2), np.float32)
+        lists, codes, codes2 = np.zeros(self._n, np.int32), np.zeros((self._n, self._m), np.uint8), np.zeros((self._n, self.m2), np.uint8)
+        nat.check(nat.lib().ivfadc_vectors_get_pq(self._s, nat.ptr(books, C.c_float), nat.ptr(lists, C.c_int32), nat.ptr(codes, C.c_uint8),
+                                                  nat.ptr(codes2, C.c_uint8), None, None))
+        return books, lists, codes, codes2
 
     def __del__(self):
         s = getattr(self, "_s", None)
