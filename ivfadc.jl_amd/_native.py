@@ -15,7 +15,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "subset.hip.h"), os.path.join(CSRC, "subset_plan.h"), os.path.join(CSRC, "scan_layouts.h"), os.path.join(CSRC, "plan.h"),
            os.path.join(CSRC, "maskset.hip.h"), os.path.join(CSRC, "maskset_plan.h"), os.path.join(CSRC, "sqmask.hip.h"),
            os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
-           os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"),
+           os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"), os.path.join(CSRC, "host_stage.h"),
            os.path.join(CSRC, "score.hip.h"), os.path.join(CSRC, "score_plan.h"),
            os.path.join(CSRC, "rerank.hip.h"), os.path.join(CSRC, "rerank_plan.h"), os.path.join(CSRC, "vstore_pq_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]

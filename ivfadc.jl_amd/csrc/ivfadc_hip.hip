@@ -22,6 +22,7 @@
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
 #include "batch_plan.h"    // the schedule of the host-pointer searches: batches, upload groups, tokens, result blocks, device split (pure)
+#include "host_stage.h"    // the host-pointer service entries: the arena's layout, counts check, id span, row compaction (pure)
 #include "list_mirror.h"   // the host mirror of the lists, its edits, the label map and the device layout's arithmetic (pure)
 
 #include <algorithm>
@@ -429,7 +430,7 @@ struct Workspace {
     bool dev_entry = false;   // the running search came in through a device-pointer entry AND another lane of this replica searched since this
                               // handle's previous search (the caller drives several lanes side by side: see make_plan)
     DevBuf gen_a, gen_b, gen_tmp, gen_off, gen_tot;   // generic path: key buffers (sort in/out), rocPRIM scratch, offsets
-    DevBuf rng_cnt, rng_off, rng_tot, rng_radii, rng_lims;   // range search (range.hip.h): item counts, their scan, per-query totals, the host entry's radii, a group's lims
+    DevBuf rng_cnt, rng_off, rng_tot, rng_lims;   // range search (range.hip.h): item counts, their scan, per-query totals, a group's lims
     int tlist_ldq = 0;
     int tmin_tiles = 0, tmin_tile_w = 0;   // set by run_coarse when the last coarse launch wrote tile minima
     DevBuf app_stage;
@@ -446,13 +447,13 @@ struct Workspace {
     DevBuf cdist2;
     DevBuf pre_list, pre_dc;   // ivfadc_search_preassigned (host pointers): the caller's probes on the device
     DevBuf mask_q;             // ivfadc_search_masked: the batch's mask numbers on the device, every value in [-1, nmasks)
-    // ivfadc_locate / ivfadc_reconstruct (reconstruct.hip.h): sorted wanted ids, one key per wanted slot, the exact bitmap, the lists' chunk
-    // prefix, rocPRIM scratch, and the host entries' staging of requests and results
-    DevBuf rc_want, rc_best, rc_bitmap, rc_chunk, rc_tmp, rc_req, rc_list, rc_pos, rc_found, rc_vec;
-    DevBuf sc_q, sc_ids, sc_cnt, sc_dist, sc_found;   // ivfadc_score_ids (host pointers): the caller's queries, ids and counts on the device, the results
-    // ivfadc_rerank (rerank.hip.h): the slice's keys, their sorted copy and segment offsets (sort form); the host entries' staging of queries,
-    // ids, counts and results; the fused call's candidates (the plain search's results with K = Kc)
-    DevBuf rr_keys, rr_sorted, rr_off, rr_q, rr_ids, rr_cnt, rr_oid, rr_od, rr_oc, rr_cid, rr_cd, rr_cc;
+    // ivfadc_locate / ivfadc_reconstruct (reconstruct.hip.h), ivfadc_score_ids: sorted wanted ids, one key per wanted slot, the exact bitmap,
+    // the lists' chunk prefix, rocPRIM scratch, list and position of every request
+    DevBuf rc_want, rc_best, rc_bitmap, rc_chunk, rc_tmp, rc_list, rc_pos;
+    // ivfadc_rerank (rerank.hip.h): the slice's keys, their sorted copy and segment offsets (sort form); the fused call's candidates (the
+    // plain search's results with K = Kc)
+    DevBuf rr_keys, rr_sorted, rr_off, rr_cid, rr_cd, rr_cc;
+    DevBuf host_stage;   // the arena of the host-pointer service entries (HostStage): staging only, carved once per call, free at entry
     DevBuf q_stage, cdist, probe_list, probe_dc, probe_base, list_cnt, bucket_off, wi_off, cursor, bucket_items, misc,
         qthr, part_keys, part_cnt, out_ids, out_dists, out_counts, assign, enc_codes, pts_stage, dbg;
     PinnedBuf pin_in, pin_out;   // host staging of ivfadc_search: pageable user buffers <-> pinned (the kernels read / write it in place)
@@ -462,7 +463,7 @@ struct Workspace {
     template <class F> void each_buf(F f)
     {
         for (DevBuf *b : {&tmin, &tlist, &wg8_tabs, &wg8_items, &sq_keys, &sq_cnt, &sq_arrive, &q_hi, &q_lo, &q_f16, &q_flags, &tl_gdist, &gen_a, &gen_b,
-                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_radii, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_req, &rc_list, &rc_pos, &rc_found, &rc_vec, &sc_q, &sc_ids, &sc_cnt, &sc_dist, &sc_found, &rr_keys, &rr_sorted, &rr_off, &rr_q, &rr_ids, &rr_cnt, &rr_oid, &rr_od, &rr_oc, &rr_cid, &rr_cd, &rr_cc, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
+                          &gen_tmp, &gen_off, &gen_tot, &rng_cnt, &rng_off, &rng_tot, &rng_lims, &app_stage, &cdist2, &pre_list, &pre_dc, &mask_q, &rc_want, &rc_best, &rc_bitmap, &rc_chunk, &rc_tmp, &rc_list, &rc_pos, &rr_keys, &rr_sorted, &rr_off, &rr_cid, &rr_cd, &rr_cc, &host_stage, &q_stage, &cdist, &probe_list, &probe_dc, &probe_base,
                           &list_cnt, &bucket_off, &wi_off, &cursor, &bucket_items, &misc, &qthr, &part_keys, &part_cnt, &out_ids, &out_dists,
                           &out_counts, &assign, &enc_codes, &pts_stage, &dbg})
             f(*b);
@@ -541,6 +542,34 @@ struct ivfadc_index : Dims, Quantizers, Lists, SearchConfig, Workspace, HandleSt
         Quantizers::each_buf(f);
         Lists::each_buf(f);
         Workspace::each_buf(f);
+    }
+};
+
+// What a host-pointer service entry stages in the handle's arena (Workspace::host_stage; host_stage.h lays it out, DESIGN.md 4.8 states the
+// rule), in three steps: in() / out() DECLARE every part; commit() grows the arena once (never to nothing: a call of no rows still hands
+// pointers on) and only then at() gives device pointers; upload() goes in front of the enqueue and download() behind it, both through
+// h2d_copy / d2h_copy on the handle's stream in the order of declaration (an entry that works on its results downloads them itself).
+struct HostStage {
+    ivfadc_index *h;
+    host_stage::Layout lay;
+    const void *src[host_stage::MAX_PARTS] = {};   // an input's host array
+    void *dst[host_stage::MAX_PARTS] = {};         // an output's host array (null: download() leaves it alone)
+    explicit HostStage(ivfadc_index *x) : h(x) {}
+    int in(const void *host, size_t bytes) { const int i = lay.add(bytes); src[i] = host; return i; }
+    int out(size_t bytes, void *host = nullptr) { const int i = lay.add(bytes); dst[i] = host; return i; }
+    int commit() { return lay.overflow ? fail(IVFADC_ERR_INVALID, "the call's arrays exceed the address space") : h->host_stage.ensure(std::max(lay.total, host_stage::ALIGN)); }
+    template <class T> T *at(int part) const { return part < 0 ? (T *)nullptr : (T *)(h->host_stage.as<uint8_t>() + lay.off[part]); }   // (part < 0: an array not passed)
+    int upload() const
+    {
+        for (int i = 0; i < lay.parts; ++i)
+            if (src[i]) TRY(h2d_copy(at<void>(i), src[i], lay.len[i], h->stream));
+        return IVFADC_OK;
+    }
+    int download() const
+    {
+        for (int i = 0; i < lay.parts; ++i)
+            if (dst[i]) TRY(d2h_copy(dst[i], at<void>(i), lay.len[i], h->stream));
+        return IVFADC_OK;
     }
 };
 
@@ -3367,9 +3396,6 @@ static int recon_begin(ivfadc_index *h, const char *fn)
     return IVFADC_OK;
 }
 
-// the way out of the four entries once the device has been touched: finish_entry's drain on failure
-static int recon_exit(ivfadc_index *x, int rc) { return finish_entry(x, rc); }
-
 // d_want: nwant wanted ids in device memory, ascending as unsigned numbers (repeats allowed) -> h->rc_best: one key per slot
 static int locate_sorted(ivfadc_index *h, const uint32_t *d_want, uint64_t nwant, bool span_known, uint32_t want_lo, uint32_t want_hi)
 {
@@ -3421,9 +3447,10 @@ static int recon_resolve(ivfadc_index *h, const uint32_t *d_req, int64_t n, cons
     return IVFADC_OK;
 }
 
-static int recon_decode(ivfadc_index *h, int64_t n, const int32_t *d_list, const int64_t *d_pos, float *d_out)
+// what the kernels that decode a stored point read of the handle (recon_decode_kernel, score_pairs_kernel)
+static int decode_args(const ivfadc_index *h, DecodeArgs &a)
 {
-    DecodeArgs a{};
+    a = DecodeArgs{};
     a.centroids = h->centroids.as<float>();
     a.codebooks = h->codebooks.as<float>();
     a.label_inv = h->u16 ? (const uint8_t *)nullptr : h->label_inv.as<uint8_t>();
@@ -3431,6 +3458,13 @@ static int recon_decode(ivfadc_index *h, int64_t n, const int32_t *d_list, const
     a.list_codeoff = h->list_codeoff.as<int64_t>();
     a.d = h->d; a.m = h->m; a.dsub = h->dsub; a.ksub = h->ksub; a.cs = h->cs;
     if (!h->u16 && !a.label_inv) return fail(IVFADC_ERR_STATE, "the handle has no inverse labels");
+    return IVFADC_OK;
+}
+
+static int recon_decode(ivfadc_index *h, int64_t n, const int32_t *d_list, const int64_t *d_pos, float *d_out)
+{
+    DecodeArgs a;
+    TRY(decode_args(h, a));
     const unsigned grid = (unsigned)std::min<int64_t>(65536, n);
     hipLaunchKernelGGL(recon_decode_kernel, dim3(grid), dim3(256), 0, h->stream, a, n, d_list, d_pos, d_out);
     HIP_TRY(hipGetLastError());
@@ -3438,22 +3472,20 @@ static int recon_decode(ivfadc_index *h, int64_t n, const int32_t *d_list, const
 }
 
 // host entries: the requested ids sorted and made unique on the host (as ivfadc_delete_ids does), everything else on the device.
-// d_list / d_pos / d_found: h->rc_list / rc_pos / rc_found, filled for the n requests.
-static int locate_host(ivfadc_index *h, int64_t n, const uint32_t *ids)
+// st: the entry's committed arena, uploaded here; its parts req (the n ids as given) and found, and h->rc_list / rc_pos, serve the n requests.
+static int locate_host(ivfadc_index *h, const HostStage &st, int req, int found, int64_t n, const uint32_t *ids)
 {
     std::vector<uint32_t> want(ids, ids + n);
     std::sort(want.begin(), want.end());
     want.erase(std::unique(want.begin(), want.end()), want.end());
     TRY(h->rc_want.ensure(want.size() * 4));
     TRY(h2d_copy(h->rc_want.p, want.data(), want.size() * 4, h->stream));
-    TRY(h->rc_req.ensure((size_t)n * 4));
-    TRY(h2d_copy(h->rc_req.p, ids, (size_t)n * 4, h->stream));
+    TRY(st.upload());
     TRY(h->rc_list.ensure((size_t)n * 4));
     TRY(h->rc_pos.ensure((size_t)n * 8));
-    TRY(h->rc_found.ensure((size_t)n));
     TRY(locate_sorted(h, h->rc_want.as<u32>(), want.size(), true, want.front(), want.back()));
-    return recon_resolve(h, h->rc_req.as<u32>(), n, h->rc_want.as<u32>(), want.size(), h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(),
-                         h->rc_found.as<uint8_t>());
+    return recon_resolve(h, st.at<u32>(req), n, h->rc_want.as<u32>(), want.size(), h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(),
+                         st.at<uint8_t>(found));
 }
 
 // device entries: the requested ids are sorted on the device (rocPRIM; repeats stay); every step is enqueued on the handle's stream, nothing
@@ -3478,10 +3510,13 @@ try {
     HandleLock lk_(h);
     TRY(recon_begin(h, "ivfadc_locate"));
     if (n == 0) return IVFADC_OK;
-    int rc = locate_host(h, n, ids);
+    HostStage st(h);
+    const int req = st.in(ids, (size_t)n * 4), found = st.out((size_t)n);
+    int rc = st.commit();
+    if (rc == IVFADC_OK) rc = locate_host(h, st, req, found, n, ids);
     if (rc == IVFADC_OK) rc = d2h_copy(out_list, h->rc_list.p, (size_t)n * 4, h->stream);
     if (rc == IVFADC_OK) rc = d2h_copy(out_pos, h->rc_pos.p, (size_t)n * 8, h->stream);
-    return recon_exit(h, rc);
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 int ivfadc_reconstruct(ivfadc_t *h, int64_t n, const uint32_t *ids, float *out_vectors, uint8_t *out_found)
@@ -3490,13 +3525,13 @@ try {
     HandleLock lk_(h);
     TRY(recon_begin(h, "ivfadc_reconstruct"));
     if (n == 0) return IVFADC_OK;
-    const size_t vbytes = (size_t)n * h->d * 4;
-    int rc = locate_host(h, n, ids);
-    if (rc == IVFADC_OK) rc = h->rc_vec.ensure(vbytes);
-    if (rc == IVFADC_OK) rc = recon_decode(h, n, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), h->rc_vec.as<float>());
-    if (rc == IVFADC_OK) rc = d2h_copy(out_vectors, h->rc_vec.p, vbytes, h->stream);
-    if (rc == IVFADC_OK && out_found) rc = d2h_copy(out_found, h->rc_found.p, (size_t)n, h->stream);
-    return recon_exit(h, rc);
+    HostStage st(h);
+    const int req = st.in(ids, (size_t)n * 4), vec = st.out((size_t)n * h->d * 4, out_vectors), found = st.out((size_t)n, out_found);
+    int rc = st.commit();
+    if (rc == IVFADC_OK) rc = locate_host(h, st, req, found, n, ids);
+    if (rc == IVFADC_OK) rc = recon_decode(h, n, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), st.at<float>(vec));
+    if (rc == IVFADC_OK) rc = st.download();
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 int ivfadc_locate_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, int32_t *d_out_list, int64_t *d_out_pos)
@@ -3505,7 +3540,7 @@ try {
     HandleLock lk_(h);
     TRY(recon_begin(h, "ivfadc_locate_device"));
     if (n == 0) return IVFADC_OK;
-    return recon_exit(h, locate_device(h, n, d_ids, d_out_list, d_out_pos, nullptr));
+    return finish_entry(h, locate_device(h, n, d_ids, d_out_list, d_out_pos, nullptr));
 } IVF_CATCH
 
 int ivfadc_reconstruct_device(ivfadc_t *h, int64_t n, const uint32_t *d_ids, float *d_out_vectors, uint8_t *d_out_found)
@@ -3518,7 +3553,7 @@ try {
     if (rc == IVFADC_OK) rc = h->rc_pos.ensure((size_t)n * 8);
     if (rc == IVFADC_OK) rc = locate_device(h, n, d_ids, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_out_found);
     if (rc == IVFADC_OK) rc = recon_decode(h, n, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), d_out_vectors);
-    return recon_exit(h, rc);
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 // ---- score caller-supplied candidate ids (score_plan.h, score.hip.h) --------------------------------------------------
@@ -3549,14 +3584,8 @@ static int score_enqueue(ivfadc_index *h, int64_t nq, const float *d_q, int64_t 
                          const int32_t *d_counts, float *d_dists, uint8_t *d_found, bool span_known, uint32_t want_lo, uint32_t want_hi)
 {
     const score::Plan pl = score::make_plan(nq, C, ids_stride, h->d, (uint64_t)h->ws_budget);
-    DecodeArgs a{};
-    a.centroids = h->centroids.as<float>();
-    a.codebooks = h->codebooks.as<float>();
-    a.label_inv = h->u16 ? (const uint8_t *)nullptr : h->label_inv.as<uint8_t>();
-    a.codes = h->codes.as<uint8_t>();
-    a.list_codeoff = h->list_codeoff.as<int64_t>();
-    a.d = h->d; a.m = h->m; a.dsub = h->dsub; a.ksub = h->ksub; a.cs = h->cs;
-    if (!h->u16 && !a.label_inv) return fail(IVFADC_ERR_STATE, "the handle has no inverse labels");
+    DecodeArgs a;
+    TRY(decode_args(h, a));
     TRY(h->rc_list.ensure((size_t)pl.locate_slots * 4));
     TRY(h->rc_pos.ensure((size_t)pl.locate_slots * 8));
     if (pl.shared) TRY(locate_device(h, C, d_ids, h->rc_list.as<int32_t>(), h->rc_pos.as<int64_t>(), nullptr, span_known, want_lo, want_hi));
@@ -3577,48 +3606,25 @@ int ivfadc_score_ids(ivfadc_t *h, int64_t nq, const float *queries, int64_t C, i
 try {
     TRY(check_score_args("ivfadc_score_ids", h, nq, queries, C, ids_stride, ids, out_dists));
     const bool shared = score::stride_form(C, ids_stride) == score::FORM_SHARED;
-    // counts in [0, C], and the span of the ids of the live slots (the bitmap of the locate pass covers it alone)
-    uint32_t lo = 0xFFFFFFFFu, hi = 0u;
-    bool any = false;
-    if (nq > 0 && C > 0) {
-        int64_t longest = C;
-        if (counts) {
-            longest = 0;
-            for (int64_t q = 0; q < nq; ++q) {
-                if (counts[q] < 0 || (int64_t)counts[q] > C)
-                    return fail(IVFADC_ERR_INVALID, "ivfadc_score_ids: query %lld: counts = %d outside [0, %lld]", (long long)q, (int)counts[q], (long long)C);
-                longest = std::max<int64_t>(longest, counts[q]);
-            }
-        }
-        const int64_t rows = shared ? 1 : nq;
-        for (int64_t q = 0; q < rows; ++q) {
-            const int64_t live = shared ? longest : score::live_slots(counts != nullptr, counts ? counts[q] : 0, C);
-            const uint32_t *row = ids + score::id_index(q, ids_stride, 0);
-            for (int64_t j = 0; j < live; ++j) {
-                lo = std::min(lo, row[j]);
-                hi = std::max(hi, row[j]);
-                any = true;
-            }
-        }
-    }
     if (nq == 0 || C == 0) return IVFADC_OK;   // (nothing to score: the handle is not looked at)
+    // counts in [0, C], and the span of the ids of the live slots (the bitmap of the locate pass covers it alone)
+    const int64_t bad = host_stage::first_bad_count(counts, nq, C);
+    if (bad >= 0)
+        return fail(IVFADC_ERR_INVALID, "ivfadc_score_ids: query %lld: counts = %d outside [0, %lld]", (long long)bad, (int)counts[bad], (long long)C);
+    const host_stage::IdSpan span = host_stage::live_id_span(nq, C, shared, ids, counts);
     HandleLock lk_(h);
     TRY(recon_begin(h, "ivfadc_score_ids"));
-    const size_t pairs = (size_t)nq * (size_t)C, nid = shared ? (size_t)C : pairs;
-    int rc = h->sc_q.ensure((size_t)nq * h->d * 4);
-    if (rc == IVFADC_OK) rc = h->sc_ids.ensure(nid * 4);
-    if (rc == IVFADC_OK) rc = h->sc_dist.ensure(pairs * 4);
-    if (rc == IVFADC_OK) rc = h->sc_found.ensure(pairs);
-    if (rc == IVFADC_OK && counts) rc = h->sc_cnt.ensure((size_t)nq * 4);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->sc_q.p, queries, (size_t)nq * h->d * 4, h->stream);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->sc_ids.p, ids, nid * 4, h->stream);
-    if (rc == IVFADC_OK && counts) rc = h2d_copy(h->sc_cnt.p, counts, (size_t)nq * 4, h->stream);
+    const size_t pairs = (size_t)nq * (size_t)C;
+    HostStage st(h);
+    const int q = st.in(queries, (size_t)nq * h->d * 4), id = st.in(ids, (shared ? (size_t)C : pairs) * 4), cnt = counts ? st.in(counts, (size_t)nq * 4) : -1;
+    const int dist = st.out(pairs * 4, out_dists), found = st.out(pairs, out_found);
+    int rc = st.commit();
+    if (rc == IVFADC_OK) rc = st.upload();
     if (rc == IVFADC_OK)
-        rc = score_enqueue(h, nq, h->sc_q.as<float>(), C, ids_stride, h->sc_ids.as<u32>(), counts ? h->sc_cnt.as<int32_t>() : (const int32_t *)nullptr,
-                           h->sc_dist.as<float>(), h->sc_found.as<uint8_t>(), true, any ? lo : 0u, any ? hi : 0u);   // (no live slot: a span of one id)
-    if (rc == IVFADC_OK) rc = d2h_copy(out_dists, h->sc_dist.p, pairs * 4, h->stream);
-    if (rc == IVFADC_OK && out_found) rc = d2h_copy(out_found, h->sc_found.p, pairs, h->stream);
-    return recon_exit(h, rc);
+        rc = score_enqueue(h, nq, st.at<float>(q), C, ids_stride, st.at<u32>(id), st.at<int32_t>(cnt), st.at<float>(dist), st.at<uint8_t>(found), true,
+                           span.lo, span.hi);
+    if (rc == IVFADC_OK) rc = st.download();
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 int ivfadc_score_ids_device(ivfadc_t *h, int64_t nq, const float *d_queries, int64_t C, int64_t ids_stride, const uint32_t *d_ids,
@@ -3628,7 +3634,7 @@ try {
     if (nq == 0 || C == 0) return IVFADC_OK;   // (nothing to score: the handle is not looked at)
     HandleLock lk_(h);
     TRY(recon_begin(h, "ivfadc_score_ids_device"));
-    return recon_exit(h, score_enqueue(h, nq, d_queries, C, ids_stride, d_ids, d_counts, d_out_dists, d_out_found, false, 0u, 0u));
+    return finish_entry(h, score_enqueue(h, nq, d_queries, C, ids_stride, d_ids, d_counts, d_out_dists, d_out_found, false, 0u, 0u));
 } IVF_CATCH
 
 // ---- exact re-ranking against the original vectors (rerank_plan.h, rerank.hip.h) --------------------------------------
@@ -3716,7 +3722,7 @@ static int vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_t
     vs->store_type = store_type;
     const int rc = vectors_fill(h, vs.get(), data, on_device);
     if (rc != IVFADC_OK) {
-        (void)recon_exit(h, rc);   // drains the stream and keeps the message: nothing still writes the store
+        (void)finish_entry(h, rc);   // drains the stream and keeps the message: nothing still writes the store
         vs->data.release();
         return rc;
     }
@@ -3864,7 +3870,7 @@ static int vectors_create_pq(ivfadc_t *h, int64_t n, const float *data, int m2, 
     b.stride = vspq::stride(h->m, m2);
     const int rc = vectors_pq_fill(h, vs.get(), data, on_device, refine, maxiter, seed, trows);
     if (rc != IVFADC_OK) {
-        (void)recon_exit(h, rc);   // drains the stream and keeps the message: nothing still writes the store
+        (void)finish_entry(h, rc);   // drains the stream and keeps the message: nothing still writes the store
         vs->release_all();
         return rc;
     }
@@ -4073,37 +4079,31 @@ try {
     TRY(check_rerank_link("ivfadc_rerank_device", h, vs));
     HandleLock lk_(h);
     TRY(set_device(h));
-    if (C == 0) return recon_exit(h, rerank_empty(h, nq, d_out_counts));
-    return recon_exit(h, rerank_enqueue(h, vs, nq, d_queries, C, d_ids, d_counts, K, d_out_ids, d_out_dists, d_out_counts));
+    if (C == 0) return finish_entry(h, rerank_empty(h, nq, d_out_counts));
+    return finish_entry(h, rerank_enqueue(h, vs, nq, d_queries, C, d_ids, d_counts, K, d_out_ids, d_out_dists, d_out_counts));
 } IVF_CATCH
 
 // A host entry stages rows of min(K, C) slots: no row can hold more results than it has candidates.
 static int rerank_stage_width(int K, int64_t C) { return (int)std::min<int64_t>(K, C); }
 
-// the results of a host entry, out of rr_oid / rr_od / rr_oc (rows of Kw slots): the first out_counts[q] slots of every row into the
-// caller's rows of K slots; the others are not written
-static int rerank_hand_over(ivfadc_index *h, int64_t nq, int Kw, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
+// the result rows of a host entry in its arena: nq rows of Kw slots of ids and of distances, nq counts
+struct RerankOut { int ids, dists, counts; };
+static RerankOut rerank_out_buffers(HostStage &st, int64_t nq, int Kw)
+{
+    return RerankOut{st.out((size_t)nq * Kw * 4), st.out((size_t)nq * Kw * 4), st.out((size_t)nq * 4)};
+}
+
+// ... handed over: the first out_counts[q] slots of every row into the caller's rows of K slots; the others are not written
+static int rerank_hand_over(const HostStage &st, const RerankOut &o, int64_t nq, int Kw, int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
 {
     const size_t slots = (size_t)nq * (size_t)Kw;
     std::vector<uint32_t> ids(slots);
     std::vector<float> dists(slots);
-    TRY(d2h_copy(out_counts, h->rr_oc.p, (size_t)nq * 4, h->stream));
-    TRY(d2h_copy(ids.data(), h->rr_oid.p, slots * 4, h->stream));
-    TRY(d2h_copy(dists.data(), h->rr_od.p, slots * 4, h->stream));
-    for (int64_t q = 0; q < nq; ++q) {
-        const size_t cnt = (size_t)std::max(0, std::min(out_counts[q], Kw)), from = (size_t)q * (size_t)Kw, at = (size_t)q * (size_t)K;
-        memcpy(out_ids + at, ids.data() + from, cnt * 4);
-        memcpy(out_dists + at, dists.data() + from, cnt * 4);
-    }
-    return IVFADC_OK;
-}
-
-static int rerank_out_buffers(ivfadc_index *h, int64_t nq, int Kw)
-{
-    const size_t slots = (size_t)nq * (size_t)Kw;
-    TRY(h->rr_oid.ensure(slots * 4));
-    TRY(h->rr_od.ensure(slots * 4));
-    TRY(h->rr_oc.ensure((size_t)nq * 4));
+    TRY(d2h_copy(out_counts, st.at<void>(o.counts), (size_t)nq * 4, st.h->stream));
+    TRY(d2h_copy(ids.data(), st.at<void>(o.ids), slots * 4, st.h->stream));
+    TRY(d2h_copy(dists.data(), st.at<void>(o.dists), slots * 4, st.h->stream));
+    host_stage::compact_rows(nq, Kw, K, out_counts, ids.data(), out_ids);
+    host_stage::compact_rows(nq, Kw, K, out_counts, dists.data(), out_dists);
     return IVFADC_OK;
 }
 
@@ -4111,9 +4111,9 @@ int ivfadc_rerank(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const flo
                   int K, uint32_t *out_ids, float *out_dists, int32_t *out_counts)
 try {
     TRY(check_rerank_args("ivfadc_rerank", h, vs, nq, queries, C, ids, true, K, out_ids, out_dists, out_counts));
-    for (int64_t q = 0; counts && q < nq; ++q)
-        if (counts[q] < 0 || (int64_t)counts[q] > C)
-            return fail(IVFADC_ERR_INVALID, "ivfadc_rerank: query %lld: counts = %d outside [0, %lld]", (long long)q, (int)counts[q], (long long)C);
+    const int64_t bad = host_stage::first_bad_count(counts, nq, C);
+    if (bad >= 0)
+        return fail(IVFADC_ERR_INVALID, "ivfadc_rerank: query %lld: counts = %d outside [0, %lld]", (long long)bad, (int)counts[bad], (long long)C);
     if (nq == 0) return IVFADC_OK;
     TRY(check_rerank_link("ivfadc_rerank", h, vs));
     if (C == 0) { memset(out_counts, 0, (size_t)nq * 4); return IVFADC_OK; }
@@ -4121,18 +4121,16 @@ try {
     TRY(set_device(h));
     const size_t pairs = (size_t)nq * (size_t)C;
     const int Kw = rerank_stage_width(K, C);
-    int rc = h->rr_q.ensure((size_t)nq * h->d * 4);
-    if (rc == IVFADC_OK) rc = h->rr_ids.ensure(pairs * 4);
-    if (rc == IVFADC_OK && counts) rc = h->rr_cnt.ensure((size_t)nq * 4);
-    if (rc == IVFADC_OK) rc = rerank_out_buffers(h, nq, Kw);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->rr_q.p, queries, (size_t)nq * h->d * 4, h->stream);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->rr_ids.p, ids, pairs * 4, h->stream);
-    if (rc == IVFADC_OK && counts) rc = h2d_copy(h->rr_cnt.p, counts, (size_t)nq * 4, h->stream);
+    HostStage st(h);
+    const int q = st.in(queries, (size_t)nq * h->d * 4), id = st.in(ids, pairs * 4), cnt = counts ? st.in(counts, (size_t)nq * 4) : -1;
+    const RerankOut o = rerank_out_buffers(st, nq, Kw);
+    int rc = st.commit();
+    if (rc == IVFADC_OK) rc = st.upload();
     if (rc == IVFADC_OK)
-        rc = rerank_enqueue(h, vs, nq, h->rr_q.as<float>(), C, h->rr_ids.as<u32>(), counts ? h->rr_cnt.as<int32_t>() : (const int32_t *)nullptr, Kw,
-                            h->rr_oid.as<u32>(), h->rr_od.as<float>(), h->rr_oc.as<int32_t>());
-    if (rc == IVFADC_OK) rc = rerank_hand_over(h, nq, Kw, K, out_ids, out_dists, out_counts);
-    return recon_exit(h, rc);
+        rc = rerank_enqueue(h, vs, nq, st.at<float>(q), C, st.at<u32>(id), st.at<int32_t>(cnt), Kw, st.at<u32>(o.ids), st.at<float>(o.dists),
+                            st.at<int32_t>(o.counts));
+    if (rc == IVFADC_OK) rc = rerank_hand_over(st, o, nq, Kw, K, out_ids, out_dists, out_counts);
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 // the plain search with K = Kc into rr_cid / rr_cd / rr_cc (the body of ivfadc_search_device under the lock the entry holds: its planner,
@@ -4164,7 +4162,7 @@ try {
     if (nq == 0) return IVFADC_OK;
     HandleLock lk_(h);
     TRY(set_device(h));
-    return recon_exit(h, search_refined_dev(h, vs, nq, d_queries, K, Kc, w, d_out_ids, d_out_dists, d_out_counts));
+    return finish_entry(h, search_refined_dev(h, vs, nq, d_queries, K, Kc, w, d_out_ids, d_out_dists, d_out_counts));
 } IVF_CATCH
 
 int ivfadc_search_refined(ivfadc_t *h, const ivfadc_vectors_t *vs, int64_t nq, const float *queries, int K, int Kc, int w, uint32_t *out_ids,
@@ -4174,13 +4172,15 @@ try {
     if (nq == 0) return IVFADC_OK;
     HandleLock lk_(h);
     TRY(set_device(h));
-    int rc = h->rr_q.ensure((size_t)nq * h->d * 4);
-    if (rc == IVFADC_OK) rc = rerank_out_buffers(h, nq, K);
-    if (rc == IVFADC_OK) rc = h2d_copy(h->rr_q.p, queries, (size_t)nq * h->d * 4, h->stream);
+    HostStage st(h);
+    const int q = st.in(queries, (size_t)nq * h->d * 4);
+    const RerankOut o = rerank_out_buffers(st, nq, K);   // (Kc >= K: the rows are K wide)
+    int rc = st.commit();
+    if (rc == IVFADC_OK) rc = st.upload();
     if (rc == IVFADC_OK)
-        rc = search_refined_dev(h, vs, nq, h->rr_q.as<float>(), K, Kc, w, h->rr_oid.as<u32>(), h->rr_od.as<float>(), h->rr_oc.as<int32_t>());
-    if (rc == IVFADC_OK) rc = rerank_hand_over(h, nq, K, K, out_ids, out_dists, out_counts);   // (Kc >= K: the rows are K wide)
-    return recon_exit(h, rc);
+        rc = search_refined_dev(h, vs, nq, st.at<float>(q), K, Kc, w, st.at<u32>(o.ids), st.at<float>(o.dists), st.at<int32_t>(o.counts));
+    if (rc == IVFADC_OK) rc = rerank_hand_over(st, o, nq, K, K, out_ids, out_dists, out_counts);
+    return finish_entry(h, rc);
 } IVF_CATCH
 
 // ---- list-partitioned multi-GPU mode: strong scaling of a FIXED global batch --------------------------------------------------------------
@@ -4416,7 +4416,7 @@ static int check_range_args(ivfadc_index *h, int64_t nq, const float *queries, c
 }
 
 // The four range entries.  s null: no query is filtered; else h is the index s was made from, unchanged since, or a plain view of it.
-// host: queries, radii and mask numbers lie in host memory, and go to q_stage / rng_radii / mask_q on the handle's stream.
+// host: queries, radii and mask numbers lie in host memory, and go to the staging arena (queries, radii) and mask_q on the handle's stream.
 static int range_entry(ivfadc_index *h, const ivfadc_maskset *s, int64_t nq, const float *queries, const float *radii, int w, int64_t max_total,
                        const int32_t *mask_of_query, ivfadc_range_result_t **out, bool host, bool masked_entry)
 {
@@ -4427,12 +4427,11 @@ static int range_entry(ivfadc_index *h, const ivfadc_maskset *s, int64_t nq, con
     SearchCall c{nq, h->d, 0, w, queries, nullptr, nullptr, nullptr, radii};   // (no K, no result rows: the result is allocated once the totals are known)
     int rc = IVFADC_OK;
     if (host) {
-        const size_t qbytes = (size_t)nq * h->d * 4, rbytes = (size_t)nq * 4;
-        rc = h->q_stage.ensure(std::max<size_t>(qbytes, 16));
-        if (rc == IVFADC_OK) rc = h->rng_radii.ensure(std::max<size_t>(rbytes, 16));
-        if (rc == IVFADC_OK) rc = h2d_copy(h->q_stage.p, queries, qbytes, h->stream);
-        if (rc == IVFADC_OK) rc = h2d_copy(h->rng_radii.p, radii, rbytes, h->stream);
-        c.q = h->q_stage.as<float>(); c.radii = h->rng_radii.as<float>();
+        HostStage st(h);
+        const int q = st.in(queries, (size_t)nq * h->d * 4), r = st.in(radii, (size_t)nq * 4);
+        rc = st.commit();
+        if (rc == IVFADC_OK) rc = st.upload();
+        c.q = st.at<float>(q); c.radii = st.at<float>(r);
     }
     if (rc == IVFADC_OK && s) rc = stage_mask_numbers(h, s, mask_of_query, !host, c);
     if (rc == IVFADC_OK) rc = range_dev(h, c, max_total, out);
@@ -4535,16 +4534,15 @@ try {
     if (nq == 0) return IVFADC_OK;
     if (!queries || !out_lists || !out_dists) return fail(IVFADC_ERR_INVALID, "null buffer");
     TRY(set_device(h));
-    const size_t qbytes = (size_t)nq * h->d * 4, pb = (size_t)nq * w * 4;
-    TRY(h->q_stage.ensure(qbytes));
-    TRY(h->pre_list.ensure(pb));
-    TRY(h->pre_dc.ensure(pb));
-    TRY(h2d_copy(h->q_stage.p, queries, qbytes, h->stream));
-    SearchCall c{nq, h->d, 0, w, h->q_stage.as<float>()};
-    c.out_list = h->pre_list.as<int32_t>(); c.out_dc = h->pre_dc.as<float>();
+    const size_t pb = (size_t)nq * w * 4;
+    HostStage st(h);
+    const int q = st.in(queries, (size_t)nq * h->d * 4), lists = st.out(pb, out_lists), dists = st.out(pb, out_dists);
+    TRY(st.commit());
+    TRY(st.upload());
+    SearchCall c{nq, h->d, 0, w, st.at<float>(q)};
+    c.out_list = st.at<int32_t>(lists); c.out_dc = st.at<float>(dists);
     int rc = coarse_dev(h, c);
-    if (rc == IVFADC_OK) rc = d2h_copy(out_lists, h->pre_list.p, pb, h->stream);
-    if (rc == IVFADC_OK) rc = d2h_copy(out_dists, h->pre_dc.p, pb, h->stream);
+    if (rc == IVFADC_OK) rc = st.download();
     return finish_entry(h, rc);
 } IVF_CATCH
 

@@ -58,9 +58,10 @@ def test_header_is_plain_cpp_and_the_host_runtime_slices_with_it():
         assert not re.search(pat, host), pat
     # one sort-group loop, one failure exit
     assert host.count("range_plan::next_group(") == 1 and host.count("for_sort_groups(h, ") == 2 and host.count("range_plan::sort_cap_keys(") == 1
-    assert host.count("static int finish_entry(ivfadc_index *h, int rc)") == 1 and host.count("finish_entry(h, ") == 5
+    assert host.count("static int finish_entry(ivfadc_index *h, int rc)") == 1 and host.count("finish_entry(h, ") == 18 and "recon_exit" not in host
     # ... which the eight host and range entries reach through five bodies: ivfadc_search, ivfadc_search_preassigned, ivfadc_coarse_search,
-    # the masked pair's and the four range entries'
+    # the masked pair's and the four range entries'; the other thirteen are the exits of the locate / reconstruct / score / re-rank / vector
+    # store entries, which went through a second name for it (recon_exit) until that name was dropped
     for body in ("search_masked_entry(", "range_entry("):
         assert host.count("static int " + body) == 1, body
     assert host.count("return range_entry(h, ") == 4 and host.count("return search_masked_entry(h, s, ") == 2
