@@ -744,7 +744,9 @@ typedef struct {
                                 * of the list-partitioned mode reports (ivfadc_set_list_partition); 6 / 7 = the table-free scan of a
                                 * 16-bit handle (ivfadc_set_u16_tables), register selectors (K <= 64) / LDS selectors (64 < K); the
                                 * table forms of a 16-bit handle report 0; 8 = the masked scan of ivfadc_search_masked
-                                * (masked_scan_kernel, csrc/maskset.hip.h) */
+                                * (masked_scan_kernel, csrc/maskset.hip.h); 9 = the large-K search of ivfadc_set_tuning(h, -4, cap_keys)
+                                * (sel_scan_kernel, csrc/selscan.hip.h; a query-major scan that follows leaves the field as it is:
+                                * read it together with last_qg == -4) */
     int32_t  coarse_listed;    /* 1: the last batch's coarse filter wrote per-tile records (four smallest keys of every
                                 * (query, 64-centroid tile)) instead of the score matrix, and the top-w enumerated them */
     int64_t  pruned_points;    /* points of probed lists that were NOT scanned: the list's coarse distance already lay above
@@ -780,7 +782,17 @@ int ivfadc_get_stats(ivfadc_t *h, ivfadc_stats *out);
  * queries per code stream; m = 8, dsub = 16, ksub = 256, K <= 64 -- other shapes fall back to 4), -2 forces the generic
  * dump-and-sort path (an independent second implementation, used as a cross-check in the tests), -3 the query-major
  * kernel behind the stand-alone top-w selection whatever the batch size (what large batches take: tests);
- * chunk_points: points per list-major work item.  Results never depend on these.            */
+ * chunk_points: points per list-major work item.
+ * -4: the large-K search (csrc/selscan.hip.h), meant for 64 < K <= 2048 on batches of a few hundred queries or more:
+ * behind the stand-alone coarse stage one workgroup per query buffers the keys of its probed points in a compute unit's LDS, finds the
+ * K-th with a radix select whenever the buffer is full and sorts the K survivors once.  chunk_points is then the buffer's capacity in
+ * KEYS (0 = the largest that fits; rounded up to 1024, clamped between 2 pow2ceil(K), at least 2048, and what fits).  It serves plain
+ * searches of an 8-bit handle (ivfadc_search, _device, _refined, _device_refined, _batches) with K <= IVFADC_MAX_K, w <= IVFADC_MAX_W
+ * and a layout that fits (m up to about 96 at K = 2048); stats.last_qg == -4 and last_striped == 9 tell that it ran, last_chunk is the
+ * capacity, last_scan_lds the LDS bytes, last_scan_grid the workgroups of the last launch.  Every other search under -4 -- UInt16 handles,
+ * mask sets, supplied probes, a list partition, K or w above the limits, a layout that does not fit -- plans exactly what qg = 0 with
+ * chunk_points = 0 plans.  Slower than the default plan at K <= 100 (README).
+ * Results never depend on these.            */
 int ivfadc_set_tuning(ivfadc_t *h, int qg, int chunk_points);
 
 /* Coarse search implementation: 0 = automatic (matrix-core score filter + certified exact refine when w <= 48,

@@ -18,6 +18,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"), os.path.join(CSRC, "host_stage.h"),
            os.path.join(CSRC, "score.hip.h"), os.path.join(CSRC, "score_plan.h"),
            os.path.join(CSRC, "rerank.hip.h"), os.path.join(CSRC, "rerank_plan.h"), os.path.join(CSRC, "vstore_pq_plan.h"),
+           os.path.join(CSRC, "selscan.hip.h"), os.path.join(CSRC, "selscan_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
 HIPCC_FLAGS = ["--offload-arch=gfx950", "-O3", "-ffp-contract=off", "-fno-slp-vectorize", "-fPIC", "-shared", "-std=c++17"]

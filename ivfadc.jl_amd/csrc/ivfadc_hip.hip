@@ -18,6 +18,7 @@
 #include "reconstruct.hip.h"
 #include "score.hip.h"
 #include "rerank.hip.h"
+#include "selscan.hip.h"   // the large-K search (ivfadc_set_tuning(h, -4, cap_keys)); selscan_plan.h is its planner (pure)
 #include "pack_operands.h"
 #include "plan.h"   // the search planner (pure; on scan_layouts.h, which the kernel headers above share)
 #include "search_call.h"   // the batch a function works on, and the one function that slices it (pure)
@@ -1838,6 +1839,88 @@ static int search_small_as(ivfadc_index *h, const SearchCall &c, bool masked)
 int search_small(ivfadc_index *h, const SearchCall &c) { return search_small_as(h, c, false); }
 int search_small_masked(ivfadc_index *h, const SearchCall &c) { return search_small_as(h, c, true); }
 
+// ---- the large-K search (selscan.hip.h; selscan_plan.h): buffered scan, radix select in LDS -- on request, ivfadc_set_tuning(h, -4, cap_keys) ----
+selscan::Facts selscan_facts(const ivfadc_index *h)
+{
+    selscan::Facts f;
+    f.d = h->d; f.kc = h->kc; f.m = h->m;
+    f.u16 = h->u16;
+    f.max_k = IVFADC_MAX_K; f.max_w = IVFADC_MAX_W;
+    f.force_cap = h->force_chunk;
+    f.ws_budget = h->ws_budget;
+    f.lds_max = LDS_MAX;
+    return f;
+}
+
+typedef void (*selscan_fn_t)(const SelScanArgs);
+selscan_fn_t pick_selscan(int m, int dsub)
+{
+    if (m == 8) return dsub == 16 ? sel_scan_kernel<16, 8> : sel_scan_kernel<0, 8>;
+    if (m == 16) return dsub == 8 ? sel_scan_kernel<8, 16> : (dsub == 6 ? sel_scan_kernel<6, 16> : sel_scan_kernel<0, 16>);
+    return dsub == 16 ? sel_scan_kernel<16, 0> : sel_scan_kernel<0, 0>;
+}
+
+// Per sub-batch: the stand-alone coarse stage (probe_stage without a fused top-w: the exact or certified coarse kernels, then
+// topw_select_kernel or the two-level search -- what ivfadc_set_tuning(h, -3, 0) runs in front of the query-major kernel) and ONE launch
+// of sel_scan_kernel, a workgroup per query.  No host synchronisation.
+int search_select(ivfadc_index *h, const SearchCall &c, const selscan::Plan &sp)
+{
+    const int K = c.K, w = c.w;
+    const selscan_fn_t fn = pick_selscan(h->m, h->dsub);
+    TRY(fn_raise_lds(h->device, (const void *)fn, sp.lds, false));
+    TRY(ensure_common_ws(h));
+    for (int64_t b0 = 0; b0 < c.nq; b0 += sp.nb) {
+        const SearchCall cb = c.slice(b0, std::min(sp.nb, c.nq - b0));
+        const int64_t nb = cb.nq;
+        Plan pl = plan_begin(plan_facts(h), nb, K, w, false);   // the coarse form; the scan is not the plan's
+        pl.fuse_topw = false;
+        const size_t np = (size_t)nb * w;
+        TRY(h->probe_list.ensure(np * 4));
+        TRY(h->probe_dc.ensure(np * 4));
+        TRY(h->probe_base.ensure(np * 4));
+        TRY(probe_stage(h, pl, cb, nullptr));
+        SelScanArgs a;
+        a.ix = index_view(h);
+        a.queries = cb.q;
+        a.w = w; a.K = K; a.cap = (u32)sp.cap;
+        a.probe_list = h->probe_list.as<int>(); a.probe_dc = h->probe_dc.as<float>(); a.probe_base = h->probe_base.as<u32>();
+        a.out_ids = cb.ids; a.out_dists = cb.dists; a.out_counts = cb.counts;
+        a.scanned_points = h->misc.as<u64>();
+        a.prune = h->allow_prune ? 1 : 0;
+        ivfadc_index::EvPair ep;
+        if (h->profiling) TRY(ev_begin(h, 0, ep));
+        hipLaunchKernelGGL(fn, dim3((unsigned)nb), dim3(selscan::THREADS), sp.lds, h->stream, a);
+        HIP_TRY(hipGetLastError());
+        if (h->profiling) TRY(ev_end(h, ep));
+        h->stats.queries += nb;
+        h->stats.last_scan_grid = (int)nb;
+        if (h->profiling && h->pending.size() > 2048) TRY(ev_fold(h));
+    }
+    h->stats.last_qg = -4;
+    h->stats.last_striped = 9;
+    h->stats.last_chunk = (int)sp.cap;
+    h->stats.last_scan_lds = (int)sp.lds;
+    h->stats.last_lb = 0;
+    h->stats.last_nf = 0;
+    return IVFADC_OK;
+}
+
+// A search under ivfadc_set_tuning(h, -4, cap_keys) that the large-K path does not serve plans exactly what qg = 0 plans (cap_keys is
+// no chunk length): the handle's tuning reads 0 / 0 while that search runs.  The caller holds the handle's lock.
+struct DefaultTuningScope {
+    ivfadc_index *h;
+    const bool on;
+    const int qg, chunk;
+    DefaultTuningScope(ivfadc_index *x, bool on_) : h(x), on(on_), qg(x->force_qg), chunk(x->force_chunk)
+    {
+        if (on) { h->force_qg = 0; h->force_chunk = 0; }
+    }
+    ~DefaultTuningScope()
+    {
+        if (on) { h->force_qg = qg; h->force_chunk = chunk; }
+    }
+};
+
 // clears the hint of ivfadc_set_next_queries when a search ends, however it ends (a hint is good for ONE search)
 struct HintScope {
     ivfadc_index *h;
@@ -2055,9 +2138,14 @@ int search_dev(ivfadc_index *h, const SearchCall &c)
     if (nq == 0) return IVFADC_OK;
     const bool parted = h->part_n > 1;
     if (masked && (pre || parted)) return fail(IVFADC_ERR_STATE, "a masked search takes neither supplied probes nor a list partition");
+    // the large-K path (ivfadc_set_tuning(h, -4, cap_keys)): plain searches of an 8-bit handle whose layout fits; everything else under
+    // that setting is planned as under qg = 0
+    const selscan::Plan sel = (h->force_qg == -4 && !masked && !parted && !pre) ? selscan::make_plan(selscan_facts(h), nq, K, w) : selscan::Plan{};
+    const DefaultTuningScope as_default{h, h->force_qg == -4 && !sel.served};
     if (!masked && !parted && !pre && sq_eligible(h, nq, K, w)) return search_small(h, c);
     if (masked && masked_sq_eligible(h, nq, K, w)) return search_small_masked(h, c);
     if (c.mask_raw) return fail(IVFADC_ERR_STATE, "unstaged mask numbers outside the masked latency path");
+    if (sel.served) return search_select(h, c, sel);
     if (K > IVFADC_MAX_K || w > IVFADC_MAX_W || h->force_qg == -2 || (h->u16 && (masked || (K > 64 && !h->u16_wide)))) {
         if (parted) return fail(IVFADC_ERR_INVALID, "list-partitioned mode reaches K <= %d and w <= %d", IVFADC_MAX_K, IVFADC_MAX_W);
         return search_generic(h, c);
@@ -5746,8 +5834,8 @@ int ivfadc_set_tuning(ivfadc_t *h, int qg, int chunk_points)
 try {
     HandleLock lk_(h);
     if (!h) return fail(IVFADC_ERR_INVALID, "null handle");
-    if (!(qg == 0 || qg == -1 || qg == -2 || qg == -3 || qg == 1 || qg == 2 || qg == 4 || qg == 8))
-        return fail(IVFADC_ERR_INVALID, "qg must be 0, -1, -2, -3, 1, 2, 4 or 8");
+    if (!(qg == 0 || qg == -1 || qg == -2 || qg == -3 || qg == -4 || qg == 1 || qg == 2 || qg == 4 || qg == 8))
+        return fail(IVFADC_ERR_INVALID, "qg must be 0, -1, -2, -3, -4, 1, 2, 4 or 8");
     if (chunk_points < 0) return fail(IVFADC_ERR_INVALID, "chunk_points < 0");
     h->force_qg = qg;
     h->force_chunk = chunk_points;
