@@ -461,13 +461,16 @@ int ivfadc_score_ids_device(ivfadc_t *h, int64_t nq, const float *d_queries, int
  *                   pointer, the _device entry a device pointer on h's GPU.  The store is a COPY: data is not referred to afterwards.
  *   store_type      0 keeps Float32.  1 keeps Float16, converted on the device with round-to-nearest-even (csrc/rerank.hip.h:
  *                   vectors_to_f16_kernel); a FINITE component that overflows Float16 makes the call fail with IVFADC_ERR_INVALID and
- *                   nothing is kept.  NaN and infinities are stored as they are.
+ *                   nothing is kept.  NaN and infinities are stored as they are.  3 makes an 8-bit scalar-quantised store with a
+ *                   trained range (below: ivfadc_vectors_create_sq with lo = hi = NULL).  2 is refused here: a PQ store is made by
+ *                   ivfadc_vectors_create_pq.
  *   row v           is "the vector stored under id v".  The store knows nothing of the lists: keeping that true across delete and shift
  *                   (and choosing n to cover the ids in use) is the CALLER's business.
  *   h               gives the device, d and, for the duration of the call, its stream and lock; the store holds no reference to h
  *                   afterwards.  One store serves the index, its views and its subset views, and any other handle of the same d and GPU.
  * Both entries block.  IVFADC_ERR_INVALID, each named in ivfadc_last_error(): null out, null handle, n < 0, n > 2^32, a store_type other
- * than 0 and 1, null data with n > 0, d above 16384.  ivfadc_vectors_sizes reports n, d and store_type (any out pointer may be NULL).      */
+ * than 0, 1 and 3, null data with n > 0, d above 16384 (store_type 3: above 10240).  ivfadc_vectors_sizes reports n, d and store_type
+ * (any out pointer may be NULL).                                                                                                        */
 typedef struct ivfadc_vectors ivfadc_vectors_t;
 int ivfadc_vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_type, ivfadc_vectors_t **out);
 int ivfadc_vectors_create_device(ivfadc_t *h, int64_t n, const float *d_data, int store_type, ivfadc_vectors_t **out);
@@ -512,6 +515,33 @@ int ivfadc_vectors_get_pq(const ivfadc_vectors_t *vs, float *out_refine_codebook
 int ivfadc_vectors_bytes(const ivfadc_vectors_t *vs, int64_t *out_bytes_per_row, int64_t *out_total_bytes);
 int ivfadc_vectors_pq_shape(const ivfadc_vectors_t *vs, int32_t *out_kc, int32_t *out_m, int32_t *out_ksub, int32_t *out_route);
 int ivfadc_vectors_set_pq_route(ivfadc_vectors_t *vs, int route);
+
+/* AN SQ8 STORE (store_type 3): 8-bit scalar quantisation with a per-dimension range, the point between the Float16 store and the PQ store
+ * (csrc/vstore_sq_plan.h, csrc/rerank.hip.h).  Row v is d codes of one byte, component t at byte t, zero-padded to the
+ * stride, d rounded up to 16 bytes: a d = 128 row is one 128-byte line where a Float16 row is two.  Beside the rows the store owns three
+ * Float32 arrays of d entries, lo, step and inv.  It owes nothing to h's codebooks: a UInt16 handle, an :opq handle and a handle without
+ * lists are all served; h gives d, the device and, for the call, its stream and lock.
+ * Everything is Float32, one rounding per operation, nothing contracted.
+ *   range    lo / hi: HOST pointers in both entries, d floats each.  Both NULL: the per-dimension minimum and maximum of data, found on
+ *            the device (exact, independent of arrival order; n = 0: all zero).  The HOST then computes, in plain float arithmetic,
+ *            range[t] = hi[t] - lo[t], step[t] = range[t] / 255, inv[t] = 255 / range[t]; range[t] == 0 gives step[t] = inv[t] = 0.
+ *            The device never divides.
+ *   code     c = min(255, max(0, rintf((x[t] - lo[t]) * inv[t]))), round-half-to-even; values outside a supplied range clamp.
+ *   distance of a live slot with id v < n, in the re-rank entries below, which take such a store unchanged:
+ *              s = 0;  t = 0 .. d-1:  y = lo[t] + (float)c_v[t] * step[t];  u = y - q[t];  s = s + u * u
+ *            -- the chain of the other stores with the reconstruction in the stored vector's place.  Order, ties, dead slots, ids >= n
+ *            and the select pass: unchanged.
+ * Both entries block; a host pointer is walked in pieces (twice for a trained range: the range, then the codes).  IVFADC_ERR_INVALID,
+ * each named in ivfadc_last_error(), nothing kept: null out, null handle, n < 0, n > 2^32, null data with n > 0, only one of lo / hi
+ * given, d above 10240 (the query, lo and step stand whole in LDS beside the tiles), a lo or hi that is not finite, hi[t] < lo[t], a range
+ * hi[t] - lo[t] that is not finite, data with a component that is not finite (either entry, either range mode: rintf of a NaN has no code).
+ * ivfadc_vectors_get_sq reads the store back (any pointer may be NULL): lo, step, inv of d floats, and the codes as n x d bytes without
+ * the padding; a store of another type is IVFADC_ERR_INVALID.  ivfadc_vectors_bytes reports the padded stride and the total with the three
+ * arrays.  The _pq_ entries above refuse such a store.
+ * Not covered: 4-bit or FP8 rows, in-place updates of a store, building one from blocks of data.                                         */
+int ivfadc_vectors_create_sq(ivfadc_t *h, int64_t n, const float *data, const float *lo, const float *hi, ivfadc_vectors_t **out);
+int ivfadc_vectors_create_sq_device(ivfadc_t *h, int64_t n, const float *d_data, const float *lo, const float *hi, ivfadc_vectors_t **out);
+int ivfadc_vectors_get_sq(const ivfadc_vectors_t *vs, float *out_lo, float *out_step, float *out_inv, uint8_t *out_codes);
 
 /* EXACT RE-RANKING (IVFADC+R): candidate ids re-scored against the original vectors of a store, the K best kept (csrc/rerank_plan.h,
  * csrc/rerank.hip.h).  The ADC distance cannot tell neighbours apart more finely than the codebooks allow; ask the search for more

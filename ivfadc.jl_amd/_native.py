@@ -17,7 +17,7 @@ SOURCES = [os.path.join(CSRC, "ivfadc_hip.hip"), os.path.join(CSRC, "kernels.hip
            os.path.join(CSRC, "range.hip.h"), os.path.join(CSRC, "range_plan.h"), os.path.join(CSRC, "search_call.h"),
            os.path.join(CSRC, "reconstruct.hip.h"), os.path.join(CSRC, "reconstruct_plan.h"), os.path.join(CSRC, "list_mirror.h"), os.path.join(CSRC, "batch_plan.h"), os.path.join(CSRC, "host_stage.h"),
            os.path.join(CSRC, "score.hip.h"), os.path.join(CSRC, "score_plan.h"),
-           os.path.join(CSRC, "rerank.hip.h"), os.path.join(CSRC, "rerank_plan.h"), os.path.join(CSRC, "vstore_pq_plan.h"),
+           os.path.join(CSRC, "rerank.hip.h"), os.path.join(CSRC, "rerank_plan.h"), os.path.join(CSRC, "vstore_pq_plan.h"), os.path.join(CSRC, "vstore_sq_plan.h"),
            os.path.join(CSRC, "selscan.hip.h"), os.path.join(CSRC, "selscan_plan.h"),
            os.path.join(os.path.dirname(_HERE), "include", "ivfadc_hip.h")]
 
@@ -213,6 +213,11 @@ def lib():
     L.ivfadc_vectors_bytes.argtypes = [vp, i64p, i64p]
     L.ivfadc_vectors_pq_shape.argtypes = [vp, i32p, i32p, i32p, i32p]
     L.ivfadc_vectors_set_pq_route.argtypes = [vp, C.c_int]
+    L.ivfadc_vectors_create_sq.argtypes = [vp, C.c_int64, fp, fp, fp, C.POINTER(vp)]
+    L.ivfadc_vectors_create_sq_device.argtypes = [vp, C.c_int64, vp, fp, fp, C.POINTER(vp)]
+    L.ivfadc_vectors_get_sq.argtypes = [vp, fp, fp, fp, u8p]
+    for name in ("vectors_create_sq", "vectors_create_sq_device", "vectors_get_sq"):
+        getattr(L, "ivfadc_" + name).restype = C.c_int
     for name in ("vectors_create_pq", "vectors_create_pq_device", "vectors_get_pq", "vectors_bytes", "vectors_pq_shape", "vectors_set_pq_route", "vectors_create", "vectors_create_device", "vectors_sizes", "rerank", "rerank_device", "search_refined", "search_device_refined"):
         getattr(L, "ivfadc_" + name).restype = C.c_int
     L.ivfadc_set_list_partition.argtypes = [vp, C.c_int, C.c_int]

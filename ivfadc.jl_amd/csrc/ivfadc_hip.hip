@@ -3738,9 +3738,12 @@ struct ivfadc_vectors {
     PqBooks pq{};
     int pq_route = vspq::ROUTE_L2;   // how the distance pass gets its codeword pieces (ivfadc_vectors_set_pq_route)
     DevBuf centroids, codebooks, refine;
+    // an 8-bit scalar-quantised store (store_type 3; vstore_sq_plan.h): data holds n rows of sq_stride code bytes
+    u32 sq_stride = 0;
+    DevBuf sq_lo, sq_step, sq_inv;   // d floats each
     void release_all()
     {
-        for (DevBuf *b : {&data, &centroids, &codebooks, &refine}) b->release();
+        for (DevBuf *b : {&data, &centroids, &codebooks, &refine, &sq_lo, &sq_step, &sq_inv}) b->release();
     }
 };
 
@@ -3789,18 +3792,117 @@ static int vectors_fill(ivfadc_index *h, ivfadc_vectors *vs, const float *data, 
     return IVFADC_OK;
 }
 
-static int vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_type, ivfadc_vectors_t **out, bool on_device)
+// ---- the 8-bit scalar-quantised store (store_type 3; vstore_sq_plan.h, rerank.hip.h) --------------------------------
+// one launch over rows [r0, r0 + rows) that lie at d_src: the range kernel (a trained range), or the encoder.  rr_off holds the flag word,
+// then the images of the minima and of the maxima.
+static void vectors_sq_launch(ivfadc_index *h, const ivfadc_vectors *vs, const float *d_src, int64_t r0, int64_t rows, bool encode)
 {
-    if (!out) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: null out");
+    const int d = vs->d;
+    u32 *d_flag = h->rr_off.as<u32>(), *d_min = d_flag + 4, *d_max = d_min + d;
+    if (!encode) {
+        hipLaunchKernelGGL(vstore_sq_range_kernel, dim3(vssq::range_grid_x(d), vssq::range_grid_y(rows)), dim3(vssq::RANGE_LANES), 0, h->stream,
+                           SqRangeArgs{d_src, rows, d, d_min, d_max, d_flag});
+        return;
+    }
+    SqEncodeArgs a{};
+    a.src = d_src;
+    a.rows = rows;
+    a.d = d;
+    a.vec = vssq::encode_vec(d, (uint64_t)(uintptr_t)d_src);
+    a.lo = vs->sq_lo.as<float>();
+    a.inv = vs->sq_inv.as<float>();
+    a.dst = vs->data.as<uint8_t>() + vssq::row_offset((uint64_t)r0, vs->sq_stride);
+    a.flag = d_flag;
+    hipLaunchKernelGGL(vstore_sq_encode_kernel, dim3(vssq::encode_grid(rows, d)), dim3(vssq::ENCODE_LANES), vssq::encode_lds_bytes(d), h->stream, a);
+}
+
+// vectors_sq_launch over the rows of `data`: a device pointer in one piece; a host pointer in pieces that pass through pts_stage
+static int vectors_sq_walk(ivfadc_index *h, const ivfadc_vectors *vs, const float *data, bool on_device, bool encode)
+{
+    if (vs->n == 0) return IVFADC_OK;
+    if (on_device) {
+        vectors_sq_launch(h, vs, data, 0, vs->n, encode);
+        HIP_TRY(hipGetLastError());
+        return IVFADC_OK;
+    }
+    const int64_t piece = vectors_piece_rows(vs->n, vs->d);
+    TRY(h->pts_stage.ensure((size_t)piece * vs->d * 4));
+    for (int64_t r0 = 0; r0 < vs->n; r0 += piece) {
+        const int64_t rows = std::min<int64_t>(piece, vs->n - r0);
+        TRY(h2d_copy(h->pts_stage.p, data + (uint64_t)r0 * (uint64_t)vs->d, (size_t)rows * vs->d * 4, h->stream));
+        vectors_sq_launch(h, vs, h->pts_stage.as<float>(), r0, rows, encode);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipStreamSynchronize(h->stream));   // the next piece overwrites pts_stage
+    }
+    return IVFADC_OK;
+}
+
+// lo / hi null: the range is the per-dimension minimum and maximum of the data (one more walk, before the encoder's)
+static int vectors_sq_fill(const char *fn, ivfadc_index *h, ivfadc_vectors *vs, const float *data, bool on_device, const float *lo, const float *hi)
+{
+    const int d = vs->d;
+    const size_t arr = (size_t)rerank::query_dwords(d) * 4;
+    vs->sq_stride = vssq::stride(d);
+    TRY(vs->data.alloc_exact(std::max<size_t>(16, (size_t)vssq::store_bytes((uint64_t)vs->n, vs->sq_stride))));
+    for (DevBuf *b : {&vs->sq_lo, &vs->sq_step, &vs->sq_inv}) TRY(b->alloc_exact(arr));
+    // rr_off: the flag word, then (a trained range) the images of the minima and of the maxima
+    TRY(h->rr_off.ensure(16 + 2 * (size_t)d * 4));
+    u32 *d_flag = h->rr_off.as<u32>();
+    std::vector<u32> img(4 + 2 * (size_t)d, 0u);
+    std::fill(img.begin() + 4, img.begin() + 4 + d, vssq::IMAGE_MIN_INIT);
+    std::fill(img.begin() + 4 + d, img.end(), vssq::IMAGE_MAX_INIT);
+    TRY(h2d_copy(d_flag, img.data(), img.size() * 4, h->stream));
+    std::vector<float> l(d, 0.0f), u(d, 0.0f), step(d), inv(d);
+    if (lo) {
+        std::copy(lo, lo + d, l.begin());
+        std::copy(hi, hi + d, u.begin());
+    } else if (vs->n > 0) {
+        TRY(vectors_sq_walk(h, vs, data, on_device, false));
+        TRY(d2h_copy(img.data(), d_flag, img.size() * 4, h->stream));
+        if (img[0]) return fail(IVFADC_ERR_INVALID, "%s: data is not finite (store_type 3 has no code for it); nothing is kept", fn);
+        for (int t = 0; t < d; ++t) {
+            const u32 a = vssq::image_bits(img[4 + t]), b = vssq::image_bits(img[4 + d + t]);
+            memcpy(&l[t], &a, 4);
+            memcpy(&u[t], &b, 4);
+        }
+    }
+    for (int t = 0; t < d; ++t) {
+        if (!std::isfinite(l[t]) || !std::isfinite(u[t]))
+            return fail(IVFADC_ERR_INVALID, "%s: component %d: the range [%g, %g] is not finite", fn, t, (double)l[t], (double)u[t]);
+        if (u[t] < l[t]) return fail(IVFADC_ERR_INVALID, "%s: component %d: hi = %g < lo = %g", fn, t, (double)u[t], (double)l[t]);
+        if (!std::isfinite(u[t] - l[t]))
+            return fail(IVFADC_ERR_INVALID, "%s: component %d: the range hi - lo = %g - %g is not finite in Float32", fn, t, (double)u[t], (double)l[t]);
+        vssq::range_arrays(l[t], u[t], step[t], inv[t]);
+    }
+    TRY(h2d_copy(vs->sq_lo.p, l.data(), (size_t)d * 4, h->stream));
+    TRY(h2d_copy(vs->sq_step.p, step.data(), (size_t)d * 4, h->stream));
+    TRY(h2d_copy(vs->sq_inv.p, inv.data(), (size_t)d * 4, h->stream));
+    if (vs->n == 0) return IVFADC_OK;
+    TRY(vectors_sq_walk(h, vs, data, on_device, true));
+    u32 flag = 0;
+    TRY(d2h_copy(&flag, d_flag, 4, h->stream));
+    if (flag) return fail(IVFADC_ERR_INVALID, "%s: data is not finite (store_type 3 has no code for it); nothing is kept", fn);
+    return IVFADC_OK;
+}
+
+// fn: the entry's name.  lo / hi: the range of a store_type 3 store (host pointers, d floats each), both null for a trained one
+static int vectors_create(const char *fn, ivfadc_t *h, int64_t n, const float *data, int store_type, const float *lo, const float *hi,
+                          ivfadc_vectors_t **out, bool on_device)
+{
+    if (!out) return fail(IVFADC_ERR_INVALID, "%s: null out", fn);
     *out = nullptr;
-    if (!h) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: null handle");
-    if (n < 0) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: n = %lld < 0", (long long)n);
-    if (n > ((int64_t)1 << 32)) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: n exceeds 2^32 (ids are UInt32)");
-    if (store_type != rerank::STORE_F32 && store_type != rerank::STORE_F16)
-        return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: store_type = %d (0: Float32, 1: Float16)", store_type);
-    if (n > 0 && !data) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: null data with n > 0");
+    if (!h) return fail(IVFADC_ERR_INVALID, "%s: null handle", fn);
+    if (n < 0) return fail(IVFADC_ERR_INVALID, "%s: n = %lld < 0", fn, (long long)n);
+    if (n > ((int64_t)1 << 32)) return fail(IVFADC_ERR_INVALID, "%s: n exceeds 2^32 (ids are UInt32)", fn);
+    const bool sq = store_type == vssq::STORE_SQ;
+    if (store_type != rerank::STORE_F32 && store_type != rerank::STORE_F16 && !sq)
+        return fail(IVFADC_ERR_INVALID, "%s: store_type = %d (0: Float32, 1: Float16, 3: 8-bit scalar-quantised; a PQ store, 2, is made by ivfadc_vectors_create_pq)",
+                    fn, store_type);
+    if (n > 0 && !data) return fail(IVFADC_ERR_INVALID, "%s: null data with n > 0", fn);
+    if ((lo == nullptr) != (hi == nullptr)) return fail(IVFADC_ERR_INVALID, "%s: only one of lo and hi given (both, or neither for a trained range)", fn);
     HandleLock lk_(h);
-    if (h->d > rerank::MAX_D) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_create: d = %d (a store takes vectors of at most %d components)", h->d, rerank::MAX_D);
+    const int max_d = sq ? vssq::MAX_D : rerank::MAX_D;
+    if (h->d > max_d) return fail(IVFADC_ERR_INVALID, "%s: d = %d (a store of store_type %d takes vectors of at most %d components)", fn, h->d, store_type, max_d);
     TRY(set_device(h));
     HIP_TRY(hipStreamSynchronize(h->stream));   // rr_off and pts_stage are the handle's: nothing enqueued earlier still reads them
     std::unique_ptr<ivfadc_vectors> vs(new ivfadc_vectors());
@@ -3808,10 +3910,10 @@ static int vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_t
     vs->d = h->d;
     vs->n = n;
     vs->store_type = store_type;
-    const int rc = vectors_fill(h, vs.get(), data, on_device);
+    const int rc = sq ? vectors_sq_fill(fn, h, vs.get(), data, on_device, lo, hi) : vectors_fill(h, vs.get(), data, on_device);
     if (rc != IVFADC_OK) {
         (void)finish_entry(h, rc);   // drains the stream and keeps the message: nothing still writes the store
-        vs->data.release();
+        vs->release_all();
         return rc;
     }
     *out = vs.release();
@@ -3820,12 +3922,22 @@ static int vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_t
 
 int ivfadc_vectors_create(ivfadc_t *h, int64_t n, const float *data, int store_type, ivfadc_vectors_t **out)
 try {
-    return vectors_create(h, n, data, store_type, out, false);
+    return vectors_create("ivfadc_vectors_create", h, n, data, store_type, nullptr, nullptr, out, false);
 } IVF_CATCH
 
 int ivfadc_vectors_create_device(ivfadc_t *h, int64_t n, const float *d_data, int store_type, ivfadc_vectors_t **out)
 try {
-    return vectors_create(h, n, d_data, store_type, out, true);
+    return vectors_create("ivfadc_vectors_create", h, n, d_data, store_type, nullptr, nullptr, out, true);
+} IVF_CATCH
+
+int ivfadc_vectors_create_sq(ivfadc_t *h, int64_t n, const float *data, const float *lo, const float *hi, ivfadc_vectors_t **out)
+try {
+    return vectors_create("ivfadc_vectors_create_sq", h, n, data, vssq::STORE_SQ, lo, hi, out, false);
+} IVF_CATCH
+
+int ivfadc_vectors_create_sq_device(ivfadc_t *h, int64_t n, const float *d_data, const float *lo, const float *hi, ivfadc_vectors_t **out)
+try {
+    return vectors_create("ivfadc_vectors_create_sq", h, n, d_data, vssq::STORE_SQ, lo, hi, out, true);
 } IVF_CATCH
 
 // ---- the PQ store (store_type 2; vstore_pq_plan.h, rerank.hip.h) ------------------------------------------------------
@@ -4023,10 +4135,35 @@ try {
 int ivfadc_vectors_bytes(const ivfadc_vectors_t *vs, int64_t *out_bytes_per_row, int64_t *out_total_bytes)
 try {
     if (!vs) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_bytes: null store");
-    const bool pq = vs->store_type == vspq::STORE_PQ;
-    const int64_t row = pq ? (int64_t)vs->pq.stride : (int64_t)rerank::row_bytes(vs->d, vs->store_type == rerank::STORE_F16);
+    const bool pq = vs->store_type == vspq::STORE_PQ, sq = vs->store_type == vssq::STORE_SQ;
+    const int64_t row = pq ? (int64_t)vs->pq.stride : sq ? (int64_t)vs->sq_stride : (int64_t)rerank::row_bytes(vs->d, vs->store_type == rerank::STORE_F16);
     if (out_bytes_per_row) *out_bytes_per_row = row;
-    if (out_total_bytes) *out_total_bytes = vs->n * row + (pq ? (int64_t)(vs->centroids.bytes + vs->codebooks.bytes + vs->refine.bytes) : 0);
+    if (out_total_bytes)
+        *out_total_bytes = vs->n * row + (pq ? (int64_t)(vs->centroids.bytes + vs->codebooks.bytes + vs->refine.bytes) : 0)
+                           + (sq ? (int64_t)(vs->sq_lo.bytes + vs->sq_step.bytes + vs->sq_inv.bytes) : 0);
+    return IVFADC_OK;
+} IVF_CATCH
+
+int ivfadc_vectors_get_sq(const ivfadc_vectors_t *vs, float *out_lo, float *out_step, float *out_inv, uint8_t *out_codes)
+try {
+    if (!vs) return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_get_sq: null store");
+    if (vs->store_type != vssq::STORE_SQ)
+        return fail(IVFADC_ERR_INVALID, "ivfadc_vectors_get_sq: store_type = %d is not an 8-bit scalar-quantised store (3)", vs->store_type);
+    if (!out_lo && !out_step && !out_inv && !out_codes) return IVFADC_OK;
+    VectorsDeviceScope dev(vs->device);
+    if (!dev.ok) return fail(IVFADC_ERR_HIP, "ivfadc_vectors_get_sq: no such HIP device %d", vs->device);
+    if (out_lo) TRY(d2h_copy(out_lo, vs->sq_lo.p, (size_t)vs->d * 4, nullptr));
+    if (out_step) TRY(d2h_copy(out_step, vs->sq_step.p, (size_t)vs->d * 4, nullptr));
+    if (out_inv) TRY(d2h_copy(out_inv, vs->sq_inv.p, (size_t)vs->d * 4, nullptr));
+    if (!out_codes) return IVFADC_OK;
+    const int64_t piece = std::max<int64_t>(1, ((int64_t)64 << 20) / vs->sq_stride);   // rows of one copy: at most 64 MB
+    std::vector<uint8_t> rows;
+    for (int64_t r0 = 0; r0 < vs->n; r0 += piece) {
+        const int64_t nr = std::min(piece, vs->n - r0);
+        rows.resize((size_t)nr * vs->sq_stride);
+        TRY(d2h_copy(rows.data(), vs->data.as<uint8_t>() + vssq::row_offset((uint64_t)r0, vs->sq_stride), rows.size(), nullptr));
+        for (int64_t r = 0; r < nr; ++r) memcpy(out_codes + (size_t)(r0 + r) * vs->d, rows.data() + (size_t)r * vs->sq_stride, (size_t)vs->d);
+    }
     return IVFADC_OK;
 } IVF_CATCH
 
@@ -4115,7 +4252,13 @@ static int rerank_enqueue(ivfadc_index *h, const ivfadc_vectors *vs, int64_t nq,
     void (*dist_pq)(const RerankPqArgs) = staged ? rerank_pq_dist_kernel<true, true>
                                           : pq && vspq::vec4(h->d, vs->pq.m, vs->pq.m2) ? rerank_pq_dist_kernel<true, false> : rerank_pq_dist_kernel<false, false>;
     if (pq) pl.dist_lds = staged ? vspq::staged_lds_bytes(h->d, vs->pq.stride, vs->pq.ksub, vs->pq.k2) : vspq::dist_lds_bytes(h->d, vs->pq.stride);
-    TRY(fn_raise_lds(h->device, pq ? (const void *)dist_pq : (const void *)dist, pl.dist_lds, false));
+    // an 8-bit scalar-quantised store: the same plan again, but chunks of 128 components and lo / step in LDS beside the query
+    const bool sq = vs->store_type == vssq::STORE_SQ;
+    if (sq) {
+        pl.nchunks = vssq::chunks(h->d);
+        pl.dist_lds = vssq::dist_lds_bytes(h->d);
+    }
+    TRY(fn_raise_lds(h->device, sq ? (const void *)rerank_sq_dist_kernel : pq ? (const void *)dist_pq : (const void *)dist, pl.dist_lds, false));
     TRY(h->rr_keys.ensure((size_t)pl.slice_keys * 8));
     if (pl.form == rerank::SELECT_SORT) {
         TRY(h->rr_sorted.ensure((size_t)pl.slice_keys * 8));
@@ -4133,7 +4276,10 @@ static int rerank_enqueue(ivfadc_index *h, const ivfadc_vectors *vs, int64_t nq,
     for (int64_t s = 0; s < pl.nslices; ++s) {
         const int64_t q0 = rerank::slice_begin(pl, s), nqs = rerank::slice_queries(pl, s);
         a.q0 = q0;
-        if (pq) hipLaunchKernelGGL(dist_pq, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, RerankPqArgs{a, vs->pq});
+        if (sq)
+            hipLaunchKernelGGL(rerank_sq_dist_kernel, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream,
+                               RerankSqArgs{a, vs->sq_lo.as<float>(), vs->sq_step.as<float>(), vs->sq_stride});
+        else if (pq) hipLaunchKernelGGL(dist_pq, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, RerankPqArgs{a, vs->pq});
         else hipLaunchKernelGGL(dist, dim3(pl.grid_x, (unsigned)nqs), dim3(rerank::TILE), pl.dist_lds, h->stream, a);
         HIP_TRY(hipGetLastError());
         if (pl.form == rerank::SELECT_LDS) {

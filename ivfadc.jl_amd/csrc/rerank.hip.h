@@ -41,6 +41,19 @@
 //   vstore_pq_encode_kernel        creation of a PQ store, one workgroup per row, the row's residual in LDS throughout: the base code
 //                        (encode_kernel's chain and tie rule on x - c), the second residual e = x - (c + p), optionally written out for
 //                        the trainer, the refinement code (the same chain on e), and the record.  Nothing but the record goes to memory.
+//   rerank_sq_dist_kernel          the distance pass against an 8-bit scalar-quantised store (store_type 3; vstore_sq_plan.h): the same
+//                        decomposition and the same fetch, but a row's 128-byte line is now 128 components, so a d = 128 row is ONE line
+//                        where the Float16 store reads two.  Lane r takes dword w of its tile row apart with four byte-extract
+//                        conversions and decodes each code on its way into the chain, y = lo[t] + (float)c * step[t]; the chunk's q,
+//                        lo and step are wave-uniform LDS reads of 16 bytes (broadcasts), all three whole in LDS beside the tiles.  Rows
+//                        are padded to 16 bytes, so the kernel has one form and no VEC twin.
+//   vstore_sq_range_kernel         per-dimension minimum and maximum of a block of rows for a trained range: consecutive lanes on
+//                        consecutive columns, a running min / max per lane over the rows of its workgroup, then one atomic min and one
+//                        atomic max per column and workgroup on order-preserving unsigned images of the floats -- exact, the same for
+//                        any grid.  A non-finite component raises a flag (plain atomic OR).
+//   vstore_sq_encode_kernel        one lane per 16 output bytes: four float4 loads, sixteen codes c = min(255, max(0, rintf((x - lo) * inv))),
+//                        one uint4 store; lo / inv from LDS when they fit, through the L2 otherwise; the last piece of a row carries
+//                        its zero padding.  The same flag.  The device never divides: step and inv come from the host.
 // Plain C++ and vector loads and stores only.
 #pragma once
 
@@ -49,6 +62,7 @@
 #include "kernels.hip.h"
 #include "rerank_plan.h"
 #include "vstore_pq_plan.h"
+#include "vstore_sq_plan.h"
 
 namespace ivf {
 
@@ -524,6 +538,200 @@ __global__ __launch_bounds__(256) void vstore_pq_finite_kernel(const float *__re
     for (uint64_t e = (uint64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (uint64_t)gridDim.x * 256)
         bad |= (__float_as_uint(src[e]) & 0x7F800000u) == 0x7F800000u;
     if (bad) atomicOr(flag, 1u);
+}
+
+// ---- the 8-bit scalar-quantised store (vstore_sq_plan.h) ----------------------------------------------------------------------------------
+struct SqRangeArgs {
+    const float *src;         // rows of this block, [rows][d]
+    int64_t rows;
+    int d;
+    u32 *img_min, *img_max;   // [d] each: vssq::image of the smallest and the largest component seen so far
+    u32 *flag;                // |= 1: a component is not finite
+};
+
+__global__ __launch_bounds__(vssq::RANGE_LANES) void vstore_sq_range_kernel(const SqRangeArgs a)
+{
+    __shared__ u32 s_min[vssq::RANGE_LANES], s_max[vssq::RANGE_LANES];
+    const int tid = threadIdx.x, cols = vssq::range_cols(a.d), par = vssq::range_rows_par(a.d);
+    const int cx = tid % cols, ry = tid / cols;
+    const int t = (int)blockIdx.x * cols + cx;
+    const int64_t r0 = vssq::range_row_begin(a.rows, gridDim.y, blockIdx.y), r1 = vssq::range_row_begin(a.rows, gridDim.y, blockIdx.y + 1u);
+    u32 lo = vssq::IMAGE_MIN_INIT, hi = vssq::IMAGE_MAX_INIT;
+    bool bad = false;
+    if (t < a.d) {
+        const float *__restrict__ col = a.src + t;
+#pragma unroll 4
+        for (int64_t r = r0 + ry; r < r1; r += par) {
+            const u32 bits = __float_as_uint(col[(uint64_t)r * (uint64_t)a.d]);
+            const u32 img = vssq::image(bits);
+            bad |= vssq::not_finite(bits);
+            lo = min(lo, img);
+            hi = max(hi, img);
+        }
+    }
+    // the `par` lanes of a column meet in LDS: one atomic min and one atomic max per column and workgroup
+    s_min[tid] = lo;
+    s_max[tid] = hi;
+    __syncthreads();
+    if (ry == 0 && t < a.d) {
+        for (int k = 1; k < par; ++k) {
+            lo = min(lo, s_min[k * cols + cx]);
+            hi = max(hi, s_max[k * cols + cx]);
+        }
+        if (lo <= hi) {   // (a workgroup without rows has seen nothing)
+            atomicMin(a.img_min + t, lo);
+            atomicMax(a.img_max + t, hi);
+        }
+    }
+    if (bad) atomicOr(a.flag, 1u);
+}
+
+struct SqEncodeArgs {
+    const float *src;         // rows of this block, [rows][d]
+    int64_t rows;
+    int d;
+    bool vec;                 // vssq::encode_vec: a whole piece comes as four float4 loads
+    const float *lo, *inv;    // [d] each
+    uint8_t *dst;             // the block's first row in the store
+    u32 *flag;                // |= 1: a component is not finite
+};
+
+// the four codes of components t .. t + 3 in one dword, component t in the low byte
+__device__ __forceinline__ u32 vstore_sq_pack(float4 x, const float *lo, const float *inv, int t, bool &bad)
+{
+    bad |= vssq::not_finite(__float_as_uint(x.x)) | vssq::not_finite(__float_as_uint(x.y)) | vssq::not_finite(__float_as_uint(x.z)) |
+           vssq::not_finite(__float_as_uint(x.w));
+    return vssq::encode(x.x, lo[t], inv[t]) | vssq::encode(x.y, lo[t + 1], inv[t + 1]) << 8 | vssq::encode(x.z, lo[t + 2], inv[t + 2]) << 16 |
+           vssq::encode(x.w, lo[t + 3], inv[t + 3]) << 24;
+}
+
+__global__ __launch_bounds__(vssq::ENCODE_LANES) void vstore_sq_encode_kernel(const SqEncodeArgs a)
+{
+    extern __shared__ __align__(16) float vsq_lds[];
+    const int tid = threadIdx.x;
+    const float *lo = a.lo, *inv = a.inv;
+    if (vssq::encode_in_lds(a.d)) {
+        float *l = vsq_lds, *v = vsq_lds + rerank::query_dwords(a.d);
+        for (int t = tid; t < a.d; t += vssq::ENCODE_LANES) { l[t] = a.lo[t]; v[t] = a.inv[t]; }
+        __syncthreads();
+        lo = l;
+        inv = v;
+    }
+    const u32 ppr = vssq::pieces_per_row(a.d);
+    const uint64_t total = vssq::encode_pieces(a.rows, a.d);
+    bool bad = false;
+    for (uint64_t e = (uint64_t)blockIdx.x * vssq::ENCODE_LANES + tid; e < total; e += (uint64_t)gridDim.x * vssq::ENCODE_LANES) {
+        const uint64_t r = vssq::piece_row(e, ppr);
+        const int t0 = vssq::piece_comp(e, ppr);
+        const float *__restrict__ x = a.src + r * (uint64_t)a.d + t0;
+        u32 w[4] = {0u, 0u, 0u, 0u};
+        if (a.vec && t0 + vssq::PIECE <= a.d) {
+            const float4 x0 = ((const float4 *)x)[0], x1 = ((const float4 *)x)[1], x2 = ((const float4 *)x)[2], x3 = ((const float4 *)x)[3];
+            w[0] = vstore_sq_pack(x0, lo, inv, t0, bad);
+            w[1] = vstore_sq_pack(x1, lo, inv, t0 + 4, bad);
+            w[2] = vstore_sq_pack(x2, lo, inv, t0 + 8, bad);
+            w[3] = vstore_sq_pack(x3, lo, inv, t0 + 12, bad);
+        } else {
+            // the last piece of a row (its padding stays zero), and every piece of a source without 16-byte rows
+#pragma unroll
+            for (int k = 0; k < vssq::PIECE; ++k) {
+                if (t0 + k < a.d) {
+                    const float xv = x[k];
+                    bad |= vssq::not_finite(__float_as_uint(xv));
+                    w[k >> 2] |= vssq::encode(xv, lo[t0 + k], inv[t0 + k]) << vssq::comp_shift(k);
+                }
+            }
+        }
+        *(uint4 *)(a.dst + vssq::row_offset(r, vssq::stride(a.d)) + (uint64_t)t0) = make_uint4(w[0], w[1], w[2], w[3]);
+    }
+    if (bad) atomicOr(a.flag, 1u);
+}
+
+struct RerankSqArgs {
+    RerankArgs r;             // rows: the codes
+    const float *lo, *step;   // [d] each
+    u32 stride;               // bytes of a row
+};
+
+// the four components of dword x of a row, from component t on: decoded and taken into the chain.  qc, lo, st: the chunk's, in LDS.
+__device__ __forceinline__ float rerank_sq_dword(float s, u32 x, const float *qc, const float *lo, const float *st, int t)
+{
+    const float4 q = *(const float4 *)(qc + t), l = *(const float4 *)(lo + t), p = *(const float4 *)(st + t);   // wave-uniform: broadcasts
+    s = rerank_step(s, l.x + (float)(x & 0xFFu) * p.x, q.x);
+    s = rerank_step(s, l.y + (float)((x >> 8) & 0xFFu) * p.y, q.y);
+    s = rerank_step(s, l.z + (float)((x >> 16) & 0xFFu) * p.z, q.z);
+    s = rerank_step(s, l.w + (float)(x >> 24) * p.w, q.w);
+    return s;
+}
+
+__global__ __launch_bounds__(rerank::TILE) void rerank_sq_dist_kernel(const RerankSqArgs sa)
+{
+    extern __shared__ __align__(16) u32 rr_lds[];
+    const RerankArgs &a = sa.r;
+    float *qs = (float *)rr_lds, *los = qs + vssq::lo_base(a.d), *steps = qs + vssq::step_base(a.d);
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int64_t qy = blockIdx.y, q = a.q0 + qy;
+    const float *__restrict__ qrow = a.queries + rerank::query_row(q, a.d);
+    for (int t = tid; t < a.d; t += rerank::TILE) { qs[t] = qrow[t]; los[t] = sa.lo[t]; steps[t] = sa.step[t]; }
+    __syncthreads();
+    const int64_t j = rerank::tile_slot(blockIdx.x, tid);
+    const int64_t live = rerank::live_slots(a.counts != nullptr, a.counts ? a.counts[q] : 0, a.C);
+    u32 v = 0u;
+    bool ok = false;
+    if (j < live) {
+        v = a.ids[rerank::id_index(q, a.C, j)];
+        ok = (uint64_t)v < a.n;
+    }
+    const u64 mask = __ballot(ok);   // wave-uniform from here on
+    float s = 0.0f;
+    if (mask != 0ull) {
+        u32 *tile = rr_lds + vssq::tile_base(a.d, wv);
+        // this lane's 16 bytes of the line of row gather_row(lane, i): null where the slot is dead or the line ends before them
+        const uint8_t *frow[rerank::LOADS];
+        const u32 at = (u32)rerank::gather_dword(lane, 0) * 4u;
+#pragma unroll
+        for (int i = 0; i < rerank::LOADS; ++i) {
+            const int r = rerank::gather_row(lane, i);
+            const u32 id = (u32)__shfl((int)v, r);
+            frow[i] = (mask >> r) & 1ull ? a.rows + vssq::row_offset(id, sa.stride) + at : nullptr;
+        }
+        const int nch = vssq::chunks(a.d);
+        auto fetch = [&](int i, int c) -> uint4 {
+            const uint64_t b = rerank::chunk_byte(c, 0);
+            return frow[i] && b + at < sa.stride ? *(const uint4 *)(frow[i] + b) : make_uint4(0u, 0u, 0u, 0u);
+        };
+        uint4 st[rerank::LOADS];
+#pragma unroll
+        for (int i = 0; i < rerank::LOADS; ++i) st[i] = fetch(i, 0);
+        for (int c = 0; c < nch; ++c) {
+            // the staged chunk c into the tile (the reads of chunk c - 1 are behind the wave_sync that ended its turn)
+#pragma unroll
+            for (int i = 0; i < rerank::LOADS; ++i) {
+                u32 *dst = tile + rerank::tile_index(rerank::gather_row(lane, i), rerank::gather_dword(lane, 0));
+                dst[0] = st[i].x; dst[1] = st[i].y; dst[2] = st[i].z; dst[3] = st[i].w;
+            }
+            wave_sync();
+            if (c + 1 < nch) {
+#pragma unroll
+                for (int i = 0; i < rerank::LOADS; ++i) st[i] = fetch(i, c + 1);
+            }
+            const u32 *row = tile + rerank::tile_index(lane, 0);
+            const int t0 = c * vssq::CHUNK_ELEMS, len = vssq::chunk_len(a.d, c);
+            if (len == vssq::CHUNK_ELEMS) {
+#pragma unroll
+                for (int w = 0; w < rerank::CHUNK_DWORDS; ++w) s = rerank_sq_dword(s, row[w], qs + t0, los + t0, steps + t0, 4 * w);
+            } else {
+                int t = 0;
+                for (; t + 4 <= len; t += 4) s = rerank_sq_dword(s, row[vssq::comp_dword(t)], qs + t0, los + t0, steps + t0, t);
+                for (; t < len; ++t) {
+                    const u32 code = (row[vssq::comp_dword(t)] >> vssq::comp_shift(t)) & 0xFFu;
+                    s = rerank_step(s, vssq::decode(code, los[t0 + t], steps[t0 + t]), qs[t0 + t]);
+                }
+            }
+            wave_sync();
+        }
+    }
+    if (j < a.C) a.keys[rerank::key_index(qy, a.C, j)] = ok ? (((u64)__float_as_uint(s) << 32) | (u32)j) : (u64)KEY_MAX;
 }
 
 }  // namespace ivf

@@ -706,7 +706,8 @@ class IVFADCIndex:
     def vectors(self, data, dtype=np.float32):
         """A VectorStore of `data` (n, d) on this index's GPU (ivfadc_vectors_create): row v is the vector stored under id v.
         dtype np.float32 keeps the rows as they are, np.float16 rounds them to nearest even on the device (a finite component that
-        overflows Float16 raises IVFADCError).  The store is a copy and serves this index, its views and its subset views."""
+        overflows Float16 raises IVFADCError), "sq8" is vectors_sq with a trained range.  The store is a copy and serves this index, its
+        views and its subset views."""
         data = np.ascontiguousarray(data, np.float32)
         assert data.ndim == 2 and data.shape[1] == self.d, "data must be (n, %d)" % self.d
         return self._vectors(nat.lib().ivfadc_vectors_create, nat.ptr(data, C.c_float) if data.shape[0] else None, data.shape[0], dtype)
@@ -716,10 +717,34 @@ class IVFADCIndex:
         return self._vectors(nat.lib().ivfadc_vectors_create_device, C.c_void_p(int(d_data_ptr)) if n else None, int(n), dtype)
 
     def _vectors(self, entry, data, n, dtype):
-        dtype = np.dtype(dtype)
-        assert dtype in (np.dtype(np.float32), np.dtype(np.float16)), "a vector store keeps float32 or float16"
+        if isinstance(dtype, str) and dtype == "sq8":           # 8-bit scalar-quantised, the range trained on the data (vectors_sq)
+            store_type = 3
+        else:
+            dtype = np.dtype(dtype)
+            assert dtype in (np.dtype(np.float32), np.dtype(np.float16)), "a vector store keeps float32, float16 or \"sq8\""
+            store_type = 1 if dtype == np.dtype(np.float16) else 0
         s = C.c_void_p()
-        nat.check(entry(self._h, int(n), data, 1 if dtype == np.dtype(np.float16) else 0, C.byref(s)))
+        nat.check(entry(self._h, int(n), data, store_type, C.byref(s)))
+        return VectorStore(s)
+
+    def vectors_sq(self, data, lo=None, hi=None):
+        """An 8-bit scalar-quantised VectorStore of `data` (n, d) (ivfadc_vectors_create_sq; dtype "sq8"): one byte a component,
+        c = min(255, max(0, rint((x - lo) * inv))) with a per-dimension range; rerank and knn_search_refined score against
+        lo + c * step.  lo / hi (d,) give the range (values outside it clamp); both None trains it: the per-dimension minimum and maximum
+        of the data.  Data that is not finite is refused.  Unlike vectors_pq it serves UInt16 and :opq indexes too."""
+        data = np.ascontiguousarray(data, np.float32)
+        assert data.ndim == 2 and data.shape[1] == self.d, "data must be (n, %d)" % self.d
+        return self._vectors_sq(nat.lib().ivfadc_vectors_create_sq, nat.ptr(data, C.c_float) if data.shape[0] else None, data.shape[0], lo, hi)
+
+    def vectors_sq_device(self, d_data_ptr, n, lo=None, hi=None):
+        """vectors_sq() from n x d float32 rows that already lie in device memory of this index's GPU (ivfadc_vectors_create_sq_device);
+        lo / hi, if given, are host arrays as for vectors_sq."""
+        return self._vectors_sq(nat.lib().ivfadc_vectors_create_sq_device, C.c_void_p(int(d_data_ptr)) if n else None, int(n), lo, hi)
+
+    def _vectors_sq(self, entry, data, n, lo, hi):
+        lo, hi = (None if a is None else np.ascontiguousarray(np.broadcast_to(np.asarray(a, np.float32), (self.d,))) for a in (lo, hi))
+        s = C.c_void_p()
+        nat.check(entry(self._h, int(n), data, nat.ptr(lo, C.c_float), nat.ptr(hi, C.c_float), C.byref(s)))
         return VectorStore(s)
 
     def vectors_pq(self, data, m2, k2=256, codebooks=None, maxiter=25, seed=0, ntrain=None):
@@ -881,8 +906,8 @@ class MaskSet:
 
 class VectorStore:
     """The original vectors on the device, Float32 or Float16 (ivfadc_vectors_t; IVFADCIndex.vectors), or their two-stage PQ
-    reconstructions (IVFADCIndex.vectors_pq: dtype "pq", with m2, k2 and pq_arrays()): what rerank and knn_search_refined score
-    candidates against.  Immutable; len() is the number of rows, `d` and `dtype` their shape and type, bytes_per_row and nbytes
+    reconstructions (IVFADCIndex.vectors_pq: dtype "pq", with m2, k2 and pq_arrays()), or their 8-bit scalar-quantised codes
+    (IVFADCIndex.vectors_sq: dtype "sq8", with sq_arrays()): what rerank and knn_search_refined score candidates against.  Immutable; len() is the number of rows, `d` and `dtype` their shape and type, bytes_per_row and nbytes
     what it takes on the device.  It
     keeps nothing of the index it was made with; the native object goes with this one."""
 
@@ -891,7 +916,7 @@ class VectorStore:
         n, d, t = C.c_int64(), C.c_int32(), C.c_int32()
         nat.check(nat.lib().ivfadc_vectors_sizes(s, C.byref(n), C.byref(d), C.byref(t)))
         self._n, self.d = int(n.value), int(d.value)
-        self.dtype = "pq" if t.value == 2 else np.dtype(np.float16 if t.value == 1 else np.float32)
+        self.dtype = "pq" if t.value == 2 else "sq8" if t.value == 3 else np.dtype(np.float16 if t.value == 1 else np.float32)
         row, total = C.c_int64(), C.c_int64()
         nat.check(nat.lib().ivfadc_vectors_bytes(s, C.byref(row), C.byref(total)))
         self.bytes_per_row, self.nbytes = int(row.value), int(total.value)
@@ -920,6 +945,15 @@ class VectorStore:
         nat.check(nat.lib().ivfadc_vectors_get_pq(self._s, nat.ptr(books, C.c_float), nat.ptr(lists, C.c_int32), nat.ptr(codes, C.c_uint8),
                                                   nat.ptr(codes2, C.c_uint8), None, None))
         return books, lists, codes, codes2
+
+    def sq_arrays(self):
+        """The read-back of an 8-bit scalar-quantised store (ivfadc_vectors_get_sq): lo, step, inv (d,) float32 and the codes (n, d)
+        uint8, without the padding of the rows."""
+        lo, step, inv = (np.zeros(self.d, np.float32) for _ in range(3))
+        codes = np.zeros((self._n, self.d), np.uint8)
+        nat.check(nat.lib().ivfadc_vectors_get_sq(self._s, nat.ptr(lo, C.c_float), nat.ptr(step, C.c_float), nat.ptr(inv, C.c_float),
+                                                  nat.ptr(codes, C.c_uint8)))
+        return lo, step, inv, codes
 
     def __del__(self):
         s = getattr(self, "_s", None)
